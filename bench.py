@@ -6,7 +6,12 @@ pyramid, FAST + quadtree + rBRIEF, BASELINE config 2) and brute-force Hamming ma
 the device (config 3's kernel on the extracted descriptors).  `value` is features extracted+matched per second over
 all ranks (frames are sharded by rank, weak scaling, no collective); `config.residency` says "device".
 
-The same JSON line carries, all measured in this run unless a field says where else it comes from:
+A plain run sets up, warms up, times --steps steps and prints the line; everything else is measured only with --full.
+--dump-outputs DIR writes what the last timed step computed on rank 0 (keypoints, descriptors, counts, matches) as
+float32 .npy files into DIR; the inputs are seeded, so two builds can be compared output for output.
+
+With --full the same JSON line also carries, all measured in this run unless a field says where else it comes from:
+  kernels         per-kernel milliseconds per step (a second pass of --steps steps with HIP events on)
   roofline        the slowest extraction kernel against the HBM roofline (HIP events on the library's stream)
   match_10k       config 3 at its stated size: 10,000 pairs of 1000x1000 descriptors, one launch (N=1 only)
   pcie_inclusive  the drop-in call with host buffers: 256 frames, and the single-frame latency Tracking sees (N=1 only)
@@ -15,7 +20,7 @@ The same JSON line carries, all measured in this run unless a field says where e
                   all-reduce per LM trial): LM iterations/s over the whole call and over the LM loop alone, per-phase
                   roofline figures, and the oracle timed on the same graph
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -63,10 +68,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--gba-iters", type=int, default=20, help="LM iterations of the timed global-BA call (the reference's GBA runs 20)")
-    ap.add_argument("--no-gba", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the match_10k and pcie_inclusive legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure per-kernel times and the roofline, match_10k, pcie_inclusive, the CPU baselines and global BA")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results (rank 0) as float32 .npy files into DIR")
+    ap.add_argument("--gba-iters", type=int, default=20, help="--full: LM iterations of the timed global-BA call (the reference's GBA runs 20)")
+    ap.add_argument("--no-gba", action="store_true", help="--full: skip the global-BA leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the match_10k and pcie_inclusive legs")
     args = ap.parse_args()
 
     import torch
@@ -145,50 +153,69 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = feats_all * args.steps / dt / 1e6
 
+    # ---- what the last timed step computed, as a caller of the device path receives it (before any further step runs).  Rows past
+    # a frame's keypoint count are filled (0 for keypoints and descriptors, -1 for matches): memory the step did not write never
+    # enters a comparison.  256 x 1096 keypoints as float32 come to 47 MB in all.
+    if args.dump_outputs and rank == 0:
+        kps, desc, counts = ex.fetch()
+        valid = np.arange(m)[None, :] < counts[:, None]
+        kp = np.stack([kps[name].astype(np.float32) for name in kps.dtype.names], axis=-1)    # x y size angle response octave class_id
+        dump = {"counts": counts.astype(np.float32),
+                "keypoints": np.where(valid[..., None], kp, np.float32(0)),
+                "descriptors": np.where(valid[..., None], desc, 0).astype(np.float32)}       # one byte per element
+        for name, t in (("match_best_idx", bi), ("match_best_dist", bd), ("match_second_dist", sd)):
+            dump[name] = np.where(valid[:n_pairs], t.cpu().numpy(), -1).astype(np.float32)  # pair p: frame p's queries
+        assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
     # ---- per-kernel durations: HIP events on the stream the kernels are launched on
-    ctx.profile(True)
-    for _ in range(args.steps):
-        step()
-    prof = ctx.profile_read()
-    ctx.profile(False)
-    kern = {}
-    for k, (ms, n) in prof.items():
-        if n:
-            per_step = ms / args.steps
-            kern[k] = {"ms_per_step": round(per_step, 4), "launches_per_step": n // args.steps}
-    if "k_cell_nms" not in kern and "k_fast_score" in kern:      # the fused kernel is timed under the score label
-        kern["k_fast_cells"] = kern.pop("k_fast_score")
-    if "k_hamming_bf" in kern and m <= 2048 and os.environ.get("CCM_BF_VARIANT", "3") == "3":
-        kern["k_hamming_mfma"] = kern.pop("k_hamming_bf")        # <= 2048 train rows: the matrix-core kernel runs under this label
-    dom = max((k for k in kern if k in ALG_BYTES), key=lambda k: kern[k]["ms_per_step"])
-    dom_bytes = ALG_BYTES[dom] * FRAMES
-    dom_s = kern[dom]["ms_per_step"] * 1e-3
-    achieved = dom_bytes / dom_s / 1e9 if dom_s > 0 else 0.0
-    traffic = None
-    pmc = {}
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            pmc = json.load(open(tpath)).get(dom, {})
-            traffic = pmc.get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-    extract_ms = sum(v["ms_per_step"] for k, v in kern.items() if not k.startswith("k_hamming"))
-    roofline = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                # traffic and the issue figures are NOT measured in this run: they are read from the committed rocprofv3 --pmc
-                # passes of this same command (separate FETCH_SIZE / WRITE_SIZE / SQ passes, tools/profile_round.sh)
-                "traffic_from": "profiles/pmc_traffic.json" if traffic is not None else None,
-                "algorithmic_bytes_per_launch": dom_bytes,
-                # vector-issue occupancy of the same kernel: SQ_INSTS_VALU x c / (1024 SIMDs x busy cycles) with c = 2.3 cycles
-                # (every instruction full rate) and c = 4.2 (every instruction a packed / 3-operand one); the two costs are
-                # measured, profiles/r02_valu_issue_calibration.txt
-                "valu_issue_frac_bounds": pmc.get("valu_issue_frac_bounds"), "valu_issue_frac_from": "profiles/pmc_traffic.json",
-                "pipeline_algorithmic_GBps": round(ALG_BYTES_FRAME * FRAMES / (extract_ms * 1e-3) / 1e9, 2) if extract_ms else None}
+    kern = roofline = None
+    if args.full:
+        ctx.profile(True)
+        for _ in range(args.steps):
+            step()
+        prof = ctx.profile_read()
+        ctx.profile(False)
+        kern = {}
+        for k, (ms, n) in prof.items():
+            if n:
+                per_step = ms / args.steps
+                kern[k] = {"ms_per_step": round(per_step, 4), "launches_per_step": n // args.steps}
+        if "k_cell_nms" not in kern and "k_fast_score" in kern:      # the fused kernel is timed under the score label
+            kern["k_fast_cells"] = kern.pop("k_fast_score")
+        if "k_hamming_bf" in kern and m <= 2048 and os.environ.get("CCM_BF_VARIANT", "3") == "3":
+            kern["k_hamming_mfma"] = kern.pop("k_hamming_bf")        # <= 2048 train rows: the matrix-core kernel runs under this label
+        dom = max((k for k in kern if k in ALG_BYTES), key=lambda k: kern[k]["ms_per_step"])
+        dom_bytes = ALG_BYTES[dom] * FRAMES
+        dom_s = kern[dom]["ms_per_step"] * 1e-3
+        achieved = dom_bytes / dom_s / 1e9 if dom_s > 0 else 0.0
+        traffic = None
+        pmc = {}
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                pmc = json.load(open(tpath)).get(dom, {})
+                traffic = pmc.get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+        extract_ms = sum(v["ms_per_step"] for k, v in kern.items() if not k.startswith("k_hamming"))
+        roofline = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                    # traffic and the issue figures are NOT measured in this run: they are read from the committed rocprofv3 --pmc
+                    # passes of this same command (separate FETCH_SIZE / WRITE_SIZE / SQ passes, tools/profile_round.sh)
+                    "traffic_from": "profiles/pmc_traffic.json" if traffic is not None else None,
+                    "algorithmic_bytes_per_launch": dom_bytes,
+                    # vector-issue occupancy of the same kernel: SQ_INSTS_VALU x c / (1024 SIMDs x busy cycles) with c = 2.3 cycles
+                    # (every instruction full rate) and c = 4.2 (every instruction a packed / 3-operand one); the two costs are
+                    # measured, profiles/r02_valu_issue_calibration.txt
+                    "valu_issue_frac_bounds": pmc.get("valu_issue_frac_bounds"), "valu_issue_frac_from": "profiles/pmc_traffic.json",
+                    "pipeline_algorithmic_GBps": round(ALG_BYTES_FRAME * FRAMES / (extract_ms * 1e-3) / 1e9, 2) if extract_ms else None}
 
     # ---- config 3 at its stated size: 10,000 independent 1000x1000 pairs, descriptors resident in HBM, one launch
     match10k = None
-    if solo and not args.no_extra:
+    if args.full and solo and not args.no_extra:
         NP = 10000
         qa, tb = synth.descriptor_pairs_torch(0, NP, device="cuda")
         b10 = torch.empty((NP, 1000), dtype=torch.int32, device="cuda"); d10 = torch.empty_like(b10); s10 = torch.empty_like(b10)
@@ -226,7 +253,7 @@ def main():
 
     # ---- the drop-in call with host buffers (what cslam::ORBextractor::operator() hands over): PCIe both ways included
     pcie = None
-    if solo and not args.no_extra:
+    if args.full and solo and not args.no_extra:
         ex.extract_batch(frames)                                   # first touch of the library's staging
         ts = []
         for _ in range(5):
@@ -276,7 +303,7 @@ def main():
     # ---- CPU oracle on this box's host cores (rank 0, N=1 only): the same batch, one core like the reference, then all cores
     cpu = None
     cpu_all = None
-    if solo and not args.no_cpu:
+    if args.full and solo and not args.no_cpu:
         from oracle import oracle_py as O
         par = O.default_params()
         t1 = time.perf_counter()
@@ -436,7 +463,7 @@ def main():
 
     gba = None
     timed_out = False
-    if not args.no_gba:
+    if args.full and not args.no_gba:
         th = threading.Thread(target=run_gba, daemon=True)
         th.start()
         th.join(timeout=420.0)

@@ -7,6 +7,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# torch is loaded before any test module loads libccm_hot.so (test_abi_cpu.py does, and runs first when the whole suite runs in one process): the library then
+# binds to torch's HIP runtime, which carries the same soname.  Loaded first, it brings in the system runtime as a second copy
+# beside torch's, and ccm_create later finds no device.
+try:
+    import torch  # noqa: F401
+except ImportError:
+    pass
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

@@ -3,13 +3,13 @@
 # A/B timing of builds of libccm_hot.so on ONE box (box-to-box spread of k_fast_cells is ~3 %, the effects looked for are smaller):
 # the front-end leg of bench.py per library, the libraries interleaved, ROUNDS times.
 rounds=$1; shift
-mkdir -p gpurun_out
+err=$(mktemp)
 for r in $(seq $rounds); do
   for lib in "$@"; do
-    CCM_HOT_LIB=$PWD/$lib timeout -k 10 120 python3 bench.py --no-cpu --no-gba --no-extra 2> gpurun_out/ab_err.log | grep '^{' | python3 -c "
+    CCM_HOT_LIB=$PWD/$lib timeout -k 10 120 python3 bench.py --full --no-cpu --no-gba --no-extra 2> "$err" | grep '^{' | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); r = d['roofline']
 print('$lib round $r: step %.4f ms  value %.1f  %s %.4f ms' % (d['ms_per_step'], d['value'], r['kernel'], r['algorithmic_bytes_per_launch'] / r['achieved'] / 1e6))
-" || { tail -5 gpurun_out/ab_err.log; exit 1; }
+" || { tail -5 "$err"; exit 1; }
   done
 done

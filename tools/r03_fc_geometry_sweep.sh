@@ -6,7 +6,7 @@ tag=$1; O=gpurun_out; mkdir -p $O
 run() {  # name, build flags, pcap, surv
   touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip
   make -s -C motioncheck_ccm_slam_amd/csrc EXTRA="$2" > $O/${tag}_fcg_$1.build 2>&1 || { echo "$1: build failed"; return; }
-  CCM_FC_PCAP=$3 CCM_FC_SURV=$4 timeout -k 10 200 python3 bench.py --no-cpu --no-gba --no-extra > $O/${tag}_fcg_$1.log 2>&1 || { echo "$1: run failed"; tail -3 $O/${tag}_fcg_$1.log; return; }
+  CCM_FC_PCAP=$3 CCM_FC_SURV=$4 timeout -k 10 200 python3 bench.py --full --no-cpu --no-gba --no-extra > $O/${tag}_fcg_$1.log 2>&1 || { echo "$1: run failed"; tail -3 $O/${tag}_fcg_$1.log; return; }
   python3 - $1 $O/${tag}_fcg_$1.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])

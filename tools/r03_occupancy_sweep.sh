@@ -6,7 +6,7 @@
 tag=$1; O=gpurun_out; mkdir -p $O
 for k in 8 6 5 4 3 2; do
   lds=$(( 163840 / k - 256 )); [ $k = 8 ] && lds=0
-  CCM_FC_LDS_MIN=$lds CCM_OD_LDS_PAD=$(( lds > 16384 ? lds - 16384 : 0 )) timeout -k 10 200 python3 bench.py --no-cpu --no-gba --no-extra > $O/${tag}_occ_$k.log 2>&1 || exit 1
+  CCM_FC_LDS_MIN=$lds CCM_OD_LDS_PAD=$(( lds > 16384 ? lds - 16384 : 0 )) timeout -k 10 200 python3 bench.py --full --no-cpu --no-gba --no-extra > $O/${tag}_occ_$k.log 2>&1 || exit 1
   python3 - $k $O/${tag}_occ_$k.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])

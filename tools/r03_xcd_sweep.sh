@@ -1,5 +1,5 @@
 #!/bin/bash
-run() { python3 bench.py --no-cpu --no-gba --no-extra 2>/dev/null | python3 -c "
+run() { python3 bench.py --full --no-cpu --no-gba --no-extra 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

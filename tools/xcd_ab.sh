@@ -2,7 +2,7 @@
 # A/B of the XCD-aware work order of k_fast_cells / k_orient_desc: timing and FETCH_SIZE per setting (GPU box, repo root)
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; cd /tmp; export TMPDIR=/tmp
 for x in "$@"; do
-  CCM_ORB_XCD=$x python3 $R/bench.py --no-gba --no-cpu --no-extra > $O/xcd_$x.log 2>&1
+  CCM_ORB_XCD=$x python3 $R/bench.py --full --no-gba --no-cpu --no-extra > $O/xcd_$x.log 2>&1
   CCM_ORB_XCD=$x rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/xcd_fetch_$x -- python3 $R/bench.py --no-cpu --no-gba --no-extra --steps 3 --warmup 1 > $O/xcd_fetch_$x.log 2>&1
   python3 $R/tools/pmc_table.py $O/xcd_fetch_$x > $O/xcd_fetch_$x.txt
   python3 - <<PY
