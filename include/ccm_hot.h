@@ -21,8 +21,9 @@
 extern "C" {
 #endif
 
-/* Bumped whenever a struct, an enum count or a prototype changes (3: ccm_ba_result.pcg_pipelined; round 2 had already changed
- * ccm_essential_graph, CCM_PROF_COUNT and removed ccm_comm_init_shm under version 1).  A caller compiled against another version
+/* Bumped whenever an existing struct, enum count or prototype changes (3: ccm_ba_result.pcg_pipelined; round 2 had already changed
+ * ccm_essential_graph, CCM_PROF_COUNT and removed ccm_comm_init_shm under version 1).  New entry points and new types are additions
+ * and do not bump it (the frame handles, ccm_frame_*, came under version 3).  A caller compiled against another version
  * must not call further: ccm_abi_version() returns the library's value, compare it with this macro (the Python mirror and
  * shim/ccm_shim.h do). */
 #define CCM_ABI_VERSION 3
@@ -401,6 +402,64 @@ typedef struct {
     int32_t*       n_inliers;  /* [n_frames] out */
 } ccm_pose_problem;
 int ccm_pose_optimize(ccm_ctx*, ccm_pose_problem*);
+
+/* ------------------------------------------------------------------ frame handles
+ * One tracked image is matched and posed several times (TrackWithMotionModel, src/Tracking.cpp:571-597: SearchByProjection
+ * (Current, Last), maybe again with a wider window, then PoseOptimizationClient; TrackLocalMap, :905-920: SearchByProjection
+ * (Frame, local map points), then PoseOptimizationClient again; on the next image it is mLastFrame).  A ccm_frame keeps one
+ * Frame's undistorted keypoints (mvKeysUn: x, y, octave, angle), mDescriptors, its feature grid (mGrid, built on the device)
+ * and mvpMapPoints (as ids into the caller's map-point table, -1 = none) in device memory for the frame's lifetime, so the
+ * per-frame calls below upload only their per-call inputs (one page-locked staging copy) and return with one download.
+ * A frame belongs to the context that made it: passing it with another context returns CCM_E_ARG.  Frames should be destroyed
+ * before their context; ccm_destroy releases the device memory of frames still alive, which then only accept ccm_frame_destroy
+ * (and ccm_frame_size); every other call on them returns CCM_E_STATE.  Creating and destroying one frame per image recycles
+ * device memory through a pool on the context: no hipMalloc in steady state. */
+typedef struct ccm_frame ccm_frame;
+/* Frame constructor's host side (src/Frame.cpp:80-118): the features g describes (g->kp_x/kp_y = mvKeysUn, octave, desc) and
+ * their grid geometry; angle[n] = mvKeysUn[i].angle or NULL (the frame then takes no part in an orientation-checked
+ * frame-to-frame match: such a call returns CCM_E_ARG).  Uploads once and builds the grid on the device (AssignFeaturesToGrid). */
+int ccm_frame_create(ccm_ctx*, const ccm_frame_grid* g, const float* angle, ccm_frame** out);
+/* The same from image `image` of the last ccm_orb_extract / ccm_orb_extract_dev on this context: octave, angle and descriptor
+ * rows are copied device to device.  kp_x_un / kp_y_un [n]: the caller's undistorted coordinates (Frame::UndistortKeyPoints,
+ * src/Frame.cpp:277), or NULL for the extracted ones (the zero-distortion early return).  n = keypoint count, or -1 to read it
+ * (synchronises).  The frame owns its copies: a later extract does not touch it.  CCM_E_STATE: no extract on this context yet;
+ * CCM_E_ARG: image out of range, n above the extract's max_per_image. */
+int ccm_frame_from_extract(ccm_ctx*, int image, int n, const float* kp_x_un, const float* kp_y_un, float min_x, float min_y,
+                           float inv_w, float inv_h, int grid_cols, int grid_rows, ccm_frame** out);
+/* NULL is a no-op. */
+void ccm_frame_destroy(ccm_frame*);
+/* Frame::N, or CCM_E_ARG for NULL. */
+int ccm_frame_size(const ccm_frame*);
+/* Frame::mvpMapPoints as ids (-1 = none); set(NULL) = all -1, the fill(..., nullptr) of Tracking.cpp:579, :589.  set is also how
+ * the caller applies "discard outliers" (:599-618). */
+int ccm_frame_set_map_points(ccm_frame*, const int32_t* mp_id);
+int ccm_frame_get_map_points(ccm_frame*, int32_t* mp_id);
+/* Test tap (host copies, synchronises): cell_first[cols*rows+1], cell_items[cell_first[cols*rows]] with cell k = px*rows + py,
+ * features of a cell in ascending index, as ccm_window_candidates builds the grid from host arrays. */
+int ccm_frame_debug_grid(ccm_frame*, int32_t* cell_first, int32_t* cell_items);
+/* ccm_search_by_projection (ORBmatcher.cpp:71-148) with the frame side taken from the handle; same results.  occupied [N] stays
+ * host in/out (the caller computes Observations() > 0).  For every newly matched feature i the handle's mp_id[i] becomes
+ * query_mp_id[q], or q when query_mp_id is NULL. */
+int ccm_frame_search_by_projection(ccm_ctx*, ccm_frame* f, const float* scale_factors, int n_mp, const uint8_t* in_view,
+                                   const int32_t* level, const float* view_cos, const float* proj_x, const float* proj_y,
+                                   const uint8_t* mp_desc, const uint8_t* mp_has_obs, const int32_t* query_mp_id,
+                                   uint8_t* occupied, float th, float nnratio, int32_t* match);
+/* ccm_search_by_projection_frame, both overloads (ORBmatcher.cpp:1350-1476, :1478-1605), cur_angle from `cur`.  last != NULL:
+ * n_last must equal its N, and the octaves, the angles and (when query_mp_id is NULL) the map-point ids come from the handle
+ * (CurrentFrame.mvpMapPoints[i2] = LastFrame.mvpMapPoints[i], :1442); last_octave / last_angle may then be NULL.  last == NULL:
+ * the arrays are used (the relocalisation overload with a keyframe's points) and new ids are query_mp_id[i] or i. */
+int ccm_frame_search_by_projection_frame(ccm_ctx*, ccm_frame* cur, const ccm_frame* last, const float* scale_factors, int n_last,
+                                         const uint8_t* valid, const float* u, const float* v, const int32_t* last_octave,
+                                         const float* last_angle, const uint8_t* mp_desc, const uint8_t* mp_has_obs,
+                                         const int32_t* query_mp_id, uint8_t* occupied, float th, int check_ori, int orb_dist,
+                                         int32_t* match);
+/* Optimizer::PoseOptimizationClient (src/Optimizer.cpp:215-347) for one frame.  Correspondences = the features with
+ * mp_id >= 0 in feature order: obs = the handle's undistorted coordinates widened to double, info = inv_level_sigma2[octave],
+ * point = mp_xyz[mp_id] ([n_mp][3]).  pose7 in/out, outlier[N] per feature (0 where there is no point), *n_inliers = the
+ * function's return value -- the values ccm_pose_optimize gives for the problem shim/cslam_optimizer.cpp assembles.  An mp_id
+ * outside [0, n_mp) or an octave outside [0, n_levels) returns CCM_E_ARG with the outputs untouched. */
+int ccm_frame_pose_optimize(ccm_ctx*, ccm_frame* f, int n_mp, const double* mp_xyz, const float* inv_level_sigma2, int n_levels,
+                            const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers);
 
 /* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:867-1062), next row F4,
  * batched over candidate keyframe pairs: one VertexSim3Expmap, fixed points, EdgeSim3ProjectXYZ +

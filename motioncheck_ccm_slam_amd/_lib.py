@@ -34,6 +34,9 @@ SYMBOLS = [
     "ccm_bow_vector", "ccm_bow_score_l1", "ccm_distinctive_descriptors", "ccm_optimize_sim3", "ccm_optimize_essential_graph", "ccm_correct_map_points",
     "ccm_ba_solve", "ccm_ba_landmark_cuts", "ccm_pose_optimize", "ccm_comm_unique_id", "ccm_comm_init", "ccm_comm_attach", "ccm_comm_destroy",
     "ccm_pose_from_mat4f", "ccm_pose_to_mat4f",
+    "ccm_frame_create", "ccm_frame_from_extract", "ccm_frame_destroy", "ccm_frame_size", "ccm_frame_set_map_points",
+    "ccm_frame_get_map_points", "ccm_frame_debug_grid", "ccm_frame_search_by_projection", "ccm_frame_search_by_projection_frame",
+    "ccm_frame_pose_optimize",
 ]
 
 
@@ -175,6 +178,17 @@ def load():
     lib.ccm_comm_destroy.argtypes = [vp]
     lib.ccm_pose_from_mat4f.argtypes = [vp, vp]
     lib.ccm_pose_to_mat4f.argtypes = [vp, vp]
+    lib.ccm_frame_create.argtypes = [vp, C.POINTER(FrameGrid), vp, C.POINTER(vp)]
+    lib.ccm_frame_from_extract.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                           C.POINTER(vp)]
+    lib.ccm_frame_destroy.argtypes = [vp]; lib.ccm_frame_destroy.restype = None
+    lib.ccm_frame_size.argtypes = [vp]
+    lib.ccm_frame_set_map_points.argtypes = [vp, vp]
+    lib.ccm_frame_get_map_points.argtypes = [vp, vp]
+    lib.ccm_frame_debug_grid.argtypes = [vp, vp, vp]
+    lib.ccm_frame_search_by_projection.argtypes = [vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_float, vp]
+    lib.ccm_frame_search_by_projection_frame.argtypes = [vp, vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_int, C.c_int, vp]
+    lib.ccm_frame_pose_optimize.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -46,6 +46,7 @@ void ccm_destroy(ccm_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    frame_state_free(c);
     comm_state_free(c);
     orb_state_free(c->orb);
     match_state_free(c->match);

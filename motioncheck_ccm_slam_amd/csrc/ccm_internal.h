@@ -17,6 +17,7 @@ struct CommState;
 struct PoseState;
 struct Sim3State;
 struct EssState;
+struct FrameState;
 
 struct ProfLabel { std::vector<std::pair<hipEvent_t, hipEvent_t>> ev; size_t used = 0; };
 
@@ -40,6 +41,7 @@ struct ccm_ctx {
     PoseState* pose = nullptr;
     Sim3State* sim3 = nullptr;
     EssState* ess = nullptr;
+    FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_host.cpp)
 };
 
 // grow-only device buffer
@@ -114,3 +116,4 @@ void comm_state_free(ccm_ctx*);
 void pose_state_free(PoseState*);
 void sim3_state_free(Sim3State*);
 void ess_state_free(EssState*);
+void frame_state_free(ccm_ctx*);                       // also orphans the frames still alive

@@ -1,0 +1,577 @@
+// frame_host.cpp -- C ABI of the frame handles (include/ccm_hot.h "frame handles"): one Frame's features, descriptors, grid and
+// map-point ids in device memory, reused by the per-frame matchers and the pose optimisation of Tracking
+// (TrackWithMotionModel src/Tracking.cpp:571-597, TrackLocalMap :905-920).
+//
+// Per call, every input goes into one page-locked staging area of the context laid out like its device twin `io`:
+//   [ results | inputs ]   one host-to-device copy of the inputs, the kernels, one device-to-host copy of the results, one
+// stream synchronisation.  The results come first so that in/out data (the occupancy flags, the pose) sits at the seam and
+// travels both ways without a second copy.
+#include "ccm_internal.h"
+#include "window_types.h"
+#include <algorithm>
+#include <climits>
+#include <new>
+
+struct FrameBuildArgs {                          // must match frame_kernels.hip
+    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
+    const ccm_keypoint* kps; const uint8_t* src_desc;
+    int keep_xy;
+    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
+};
+struct PoseGatherArgs {                          // must match frame_kernels.hip
+    int n; const float* kx; const float* ky; const int* oct; const int* mp_id;
+    int n_mp; const double* xyz; const float* inv_sigma2; int n_levels;
+    int* first; double* pts; double* obs; double* info; int* kof; int* status;
+};
+struct PoseDev {                                 // must match pose_kernels.hip
+    int n_frames; double* poses; const double* intr; const int* first; const double* pts; const double* obs;
+    const double* info; double* err; uint8_t* outlier; int* n_inliers;
+};
+void pose_launch(hipStream_t, const PoseDev&);
+size_t frame_build_lds(int cells);
+int frame_launch_build(hipStream_t, const FrameBuildArgs&);
+void frame_launch_prep_last(hipStream_t, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl);
+void frame_launch_scatter_ids(hipStream_t, int n, const int* match, const int* src, const int* status, int* mp_id);
+void frame_launch_pose_gather(hipStream_t, const PoseGatherArgs&);
+void frame_launch_pose_scatter(hipStream_t, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier);
+int orb_last_result(ccm_ctx*, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
+                    int* nlevels);
+
+struct FrameMem { DevBuf buf; };                 // one device block per frame, recycled through the context's pool
+
+// Device layout of a frame (one block, 64-byte aligned segments): kx, ky [n] f32 | octave [n] i32 | angle [n] f32 |
+// desc [n][32] | mp_id [n] i32 | cell_items [n] i32 | cell_first [cols*rows+1] i32.  The first five are what a host upload
+// fills, in one copy.
+struct ccm_frame {
+    ccm_ctx* ctx = nullptr;                      // nullptr once the context is gone
+    FrameMem* mem = nullptr;
+    int n = 0, cols = 0, rows = 0, n_levels = 0; // n_levels: octaves are in [0, n_levels)
+    float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;
+    bool has_angle = false;
+    float* kx = nullptr; float* ky = nullptr; int* oct = nullptr; float* angle = nullptr; uint8_t* desc = nullptr;
+    int* mp_id = nullptr; int* cell_items = nullptr; int* cell_first = nullptr;
+};
+
+struct FrameState {
+    std::vector<FrameMem*> pool;                 // free blocks
+    std::vector<ccm_frame*> live;
+    DevBuf io;                                   // per-call device staging, [results | inputs]
+    uint8_t* host = nullptr; size_t host_cap = 0;  // page-locked, same layout as io
+    hipEvent_t host_free = nullptr; bool pending = false;   // recorded behind the last upload from `host`
+    DevBuf ci, cd, cn, ev, pts, obs, info, err, outl, kof, first;
+};
+
+static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
+
+struct FrameLayout { size_t kx, ky, oct, angle, desc, upload_end, mp_id, items, first, bytes; };
+static FrameLayout frame_layout(int n, int cells)
+{
+    const size_t m = (size_t)std::max(n, 1);
+    FrameLayout L; size_t off = 0;
+    L.kx = seg(off, m * 4); L.ky = seg(off, m * 4); L.oct = seg(off, m * 4); L.angle = seg(off, m * 4); L.desc = seg(off, m * 32);
+    L.upload_end = off;
+    L.mp_id = seg(off, m * 4); L.items = seg(off, m * 4); L.first = seg(off, ((size_t)cells + 1) * 4);
+    L.bytes = off;
+    return L;
+}
+
+static FrameState* frame_state(ccm_ctx* c)
+{
+    if (!c->frame) c->frame = new FrameState();
+    return c->frame;
+}
+
+void frame_state_free(ccm_ctx* c)
+{
+    FrameState* S = c->frame;
+    if (!S) return;
+    for (ccm_frame* f : S->live) {               // frames the caller did not destroy: memory goes, the handle stays (ccm_frame_destroy)
+        if (f->mem) { f->mem->buf.release(); delete f->mem; }
+        *f = ccm_frame();
+    }
+    for (FrameMem* m : S->pool) { m->buf.release(); delete m; }
+    DevBuf* all[] = { &S->io, &S->ci, &S->cd, &S->cn, &S->ev, &S->pts, &S->obs, &S->info, &S->err, &S->outl, &S->kof, &S->first };
+    for (DevBuf* b : all) b->release();
+    if (S->host) (void)hipHostFree(S->host);
+    if (S->host_free) (void)hipEventDestroy(S->host_free);
+    delete S;
+    c->frame = nullptr;
+}
+
+// The page-locked staging area with at least `bytes`, free to write (the last upload from it has completed), and io as large.
+static int staging(ccm_ctx* c, size_t bytes, uint8_t** host)
+{
+    FrameState& S = *frame_state(c);
+    if (!S.host_free) CCM_HIP(c, hipEventCreateWithFlags(&S.host_free, hipEventDisableTiming));
+    if (S.pending) { CCM_HIP(c, hipEventSynchronize(S.host_free)); S.pending = false; }
+    if (bytes > S.host_cap) {
+        if (S.host) (void)hipHostFree(S.host);
+        S.host = nullptr; S.host_cap = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        if (hipHostMalloc((void**)&S.host, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError(); S.host = nullptr;
+            return ccm_fail(c, CCM_E_NOMEM, "page-locked staging of %zu bytes failed", want);
+        }
+        S.host_cap = want;
+    }
+    CCM_RESERVE(c, S.io, bytes);
+    *host = S.host;
+    return CCM_OK;
+}
+
+// host[a, b) -> dst (default: io at the same offsets), asynchronous; the staging area stays busy until the copy has run
+static int upload(ccm_ctx* c, size_t a, size_t b, void* dst = nullptr)
+{
+    FrameState& S = *c->frame;
+    if (b <= a) return CCM_OK;
+    CCM_HIP(c, hipMemcpyAsync(dst ? dst : S.io.as<uint8_t>() + a, S.host + a, b - a, hipMemcpyHostToDevice, c->stream));
+    CCM_HIP(c, hipEventRecord(S.host_free, c->stream));
+    S.pending = true;
+    return CCM_OK;
+}
+
+// io[0, b) -> host[0, b), then wait for the stream
+static int download(ccm_ctx* c, size_t b)
+{
+    FrameState& S = *c->frame;
+    CCM_HIP(c, hipMemcpyAsync(S.host, S.io.p, b, hipMemcpyDeviceToHost, c->stream));
+    CCM_HIP(c, hipStreamSynchronize(c->stream));
+    S.pending = false;
+    return CCM_OK;
+}
+
+static int fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes)   // rare paths (fallbacks, test taps)
+{
+    if (!bytes) return CCM_OK;
+    CCM_HIP(c, hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    CCM_HIP(c, hipStreamSynchronize(c->stream));
+    return CCM_OK;
+}
+
+static int frame_alloc(ccm_ctx* c, int n, int cols, int rows, ccm_frame** out)
+{
+    FrameState& S = *frame_state(c);
+    const FrameLayout L = frame_layout(n, cols * rows);
+    // best fit among the free blocks, else the largest one grown, else a new block
+    int pick = -1;
+    for (int i = 0; i < (int)S.pool.size(); i++)
+        if (S.pool[i]->buf.cap >= L.bytes && (pick < 0 || S.pool[i]->buf.cap < S.pool[pick]->buf.cap)) pick = i;
+    if (pick < 0)
+        for (int i = 0; i < (int)S.pool.size(); i++) if (pick < 0 || S.pool[i]->buf.cap > S.pool[pick]->buf.cap) pick = i;
+    FrameMem* m;
+    if (pick >= 0) { m = S.pool[pick]; S.pool.erase(S.pool.begin() + pick); }
+    else m = new FrameMem();
+    if (m->buf.reserve(L.bytes)) {
+        S.pool.push_back(m);
+        return ccm_fail(c, CCM_E_NOMEM, "frame: device alloc of %zu bytes failed", L.bytes);
+    }
+    ccm_frame* f = new ccm_frame();
+    uint8_t* base = m->buf.as<uint8_t>();
+    f->ctx = c; f->mem = m; f->n = n; f->cols = cols; f->rows = rows;
+    f->kx = (float*)(base + L.kx); f->ky = (float*)(base + L.ky); f->oct = (int*)(base + L.oct); f->angle = (float*)(base + L.angle);
+    f->desc = base + L.desc; f->mp_id = (int*)(base + L.mp_id); f->cell_items = (int*)(base + L.items); f->cell_first = (int*)(base + L.first);
+    S.live.push_back(f);
+    *out = f;
+    return CCM_OK;
+}
+
+static void frame_release(ccm_frame* f)
+{
+    if (f->ctx && f->ctx->frame) {
+        FrameState& S = *f->ctx->frame;
+        S.live.erase(std::remove(S.live.begin(), S.live.end(), f), S.live.end());
+        if (f->mem) S.pool.push_back(f->mem);    // stream order keeps queued work on it ahead of the next user
+    }
+    delete f;
+}
+
+static int frame_build(ccm_ctx* c, ccm_frame* f, const ccm_keypoint* kps, const uint8_t* src_desc, int keep_xy)
+{
+    FrameBuildArgs A{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, kps, src_desc, keep_xy,
+                      f->kx, f->ky, f->oct, f->angle, f->desc, f->cell_first, f->cell_items, f->mp_id };
+    if (frame_launch_build(c->stream, A)) return ccm_fail(c, CCM_E_DEVICE, "k_frame_build: LDS request refused");
+    CCM_HIP(c, hipGetLastError());
+    return CCM_OK;
+}
+
+static bool grid_ok(int cols, int rows) { return cols >= 1 && rows >= 1 && (long long)cols * rows <= 16384; }
+
+// The windowed matchers through a handle.  mode 0: SearchByProjection(Frame, map points); mode 2: SearchByProjection(Frame,
+// Frame | KeyFrame).  Queries come with their radius / level window (qr != nullptr) or, for a `last` handle, get them on the device.
+struct WinCall {
+    int mode, nq;
+    const float* qx; const float* qy; const float* qr; const int32_t* minl; const int32_t* maxl;
+    const uint8_t* qdesc; const uint8_t* active; const uint8_t* qflag; const int32_t* qid;
+    const ccm_frame* last; const float* scale; float th;      // device-side query set-up (qr == nullptr)
+    const float* q_angle;                                     // mode 2, check_ori, no `last`: the last side's angles (host)
+    float nnratio; int orb_dist, check_ori;
+};
+
+static int frame_window(ccm_ctx* c, ccm_frame* f, const WinCall& w, uint8_t* occupied, int32_t* match)
+{
+    FrameState& S = *frame_state(c);
+    hipStream_t st = c->stream;
+    const int n = f->n, nq = w.nq;
+    const bool dev_prep = w.qr == nullptr;
+    const bool need_qang = w.mode == 2 && w.check_ori && !w.last;
+    size_t off = 0;
+    const size_t o_status = seg(off, 16), o_out = seg(off, (size_t)n * 4), o_flag = seg(off, (size_t)n);
+    const size_t res_end = o_flag + n;
+    const size_t o_qx = seg(off, (size_t)nq * 4), o_qy = seg(off, (size_t)nq * 4), o_qr = seg(off, (size_t)nq * 4);
+    const size_t o_minl = seg(off, (size_t)nq * 4), o_maxl = seg(off, (size_t)nq * 4), o_qdesc = seg(off, (size_t)nq * 32);
+    const size_t o_act = seg(off, (size_t)nq), o_qflag = seg(off, (size_t)nq);
+    const size_t o_qid = seg(off, w.qid ? (size_t)nq * 4 : 0), o_qang = seg(off, need_qang ? (size_t)nq * 4 : 0);
+    const size_t o_scale = seg(off, dev_prep ? (size_t)w.last->n_levels * 4 : 0);
+    const size_t end = off;
+    uint8_t* h = nullptr;
+    int rc = staging(c, end, &h);
+    if (rc) return rc;
+    std::memset(h + o_out, 0xFF, (size_t)n * 4);
+    std::memcpy(h + o_flag, occupied, n);
+    std::memcpy(h + o_qx, w.qx, (size_t)nq * 4); std::memcpy(h + o_qy, w.qy, (size_t)nq * 4);
+    if (!dev_prep) {
+        std::memcpy(h + o_qr, w.qr, (size_t)nq * 4); std::memcpy(h + o_minl, w.minl, (size_t)nq * 4); std::memcpy(h + o_maxl, w.maxl, (size_t)nq * 4);
+    } else {
+        std::memcpy(h + o_scale, w.scale, (size_t)w.last->n_levels * 4);
+    }
+    std::memcpy(h + o_qdesc, w.qdesc, (size_t)nq * 32);
+    std::memcpy(h + o_act, w.active, nq); std::memcpy(h + o_qflag, w.qflag, nq);
+    if (w.qid) std::memcpy(h + o_qid, w.qid, (size_t)nq * 4);
+    if (need_qang) std::memcpy(h + o_qang, w.q_angle, (size_t)nq * 4);
+    if ((rc = upload(c, o_out, end))) return rc;
+
+    uint8_t* io = S.io.as<uint8_t>();
+    int* d_status = (int*)(io + o_status); int* d_out = (int*)(io + o_out); uint8_t* d_flag = io + o_flag;
+    const float* d_qx = (const float*)(io + o_qx); const float* d_qy = (const float*)(io + o_qy);
+    float* d_qr = (float*)(io + o_qr); int* d_minl = (int*)(io + o_minl); int* d_maxl = (int*)(io + o_maxl);
+    const uint8_t* d_qdesc = io + o_qdesc; const uint8_t* d_act = io + o_act; const uint8_t* d_qflag = io + o_qflag;
+    const int* d_qid = w.qid ? (const int*)(io + o_qid) : nullptr;
+    const float* d_qang = need_qang ? (const float*)(io + o_qang) : (w.last ? w.last->angle : nullptr);
+    const int* id_src = d_qid ? d_qid : (w.last ? w.last->mp_id : nullptr);
+    if (dev_prep) {
+        frame_launch_prep_last(st, nq, d_act, w.last->oct, (const float*)(io + o_scale), w.th, d_qr, d_minl, d_maxl);
+        CCM_HIP(c, hipGetLastError());
+    }
+    const WinGrid G{ n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+    auto lists = [&](int cap) -> int {
+        CCM_RESERVE(c, S.ci, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cd, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cn, (size_t)nq * 4);
+        match_launch_window(st, G, nq, d_qx, d_qy, d_qr, d_minl, d_maxl, d_qdesc, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>());
+        CCM_HIP(c, hipGetLastError());
+        return CCM_OK;
+    };
+
+    if (!window_host_accept_forced() && match_window_greedy_lds(n, nq) <= kGreedyLdsMax) {
+        int cap = 64;
+        CCM_RESERVE(c, S.ev, std::max<size_t>((size_t)nq * 4, 16));
+        for (int attempt = 0; attempt < 3; attempt++) {
+            if ((rc = lists(cap))) return rc;
+            GreedyArgs A{ nq, n, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>(), d_act, nullptr, f->oct, d_qflag, d_flag, w.nnratio,
+                          d_out, d_status, w.orb_dist, w.check_ori, d_qang, f->angle, S.ev.as<int>(), nullptr };
+            if (match_launch_window_greedy(st, w.mode, A)) return ccm_fail(c, CCM_E_DEVICE, "k_window_greedy: LDS request refused");
+            CCM_HIP(c, hipGetLastError());
+            frame_launch_scatter_ids(st, n, d_out, id_src, d_status, f->mp_id);
+            CCM_HIP(c, hipGetLastError());
+            if ((rc = download(c, res_end))) return rc;
+            int status[2];
+            std::memcpy(status, S.host + o_status, 8);
+            if (status[0] < 0) { cap = status[1]; continue; }                  // rare: a denser window than expected
+            std::memcpy(match, S.host + o_out, (size_t)n * 4);
+            std::memcpy(occupied, S.host + o_flag, n);
+            return status[0];
+        }
+        return ccm_fail(c, CCM_E_CAPACITY, "window candidate lists keep overflowing");
+    }
+
+    // host acceptance (CCM_WINDOW_HOST_ACCEPT=1, or a frame too large for the single workgroup's LDS): lists to the host, the loops
+    // of match_host.cpp on the frame's octaves / angles fetched from the device, the new ids scattered on the device
+    int cap = 64;
+    std::vector<int32_t> ci, cd, cn(nq);
+    for (;;) {
+        if ((rc = lists(cap))) return rc;
+        ci.resize((size_t)nq * cap); cd.resize((size_t)nq * cap);
+        if ((rc = fetch(c, cn.data(), S.cn.p, (size_t)nq * 4))) return rc;
+        int mx = 0;
+        for (int v : cn) mx = std::max(mx, v);
+        if (mx > cap) { cap = mx; continue; }
+        if ((rc = fetch(c, ci.data(), S.ci.p, ci.size() * 4)) || (rc = fetch(c, cd.data(), S.cd.p, cd.size() * 4))) return rc;
+        break;
+    }
+    int nmatches;
+    if (w.mode == 0) {
+        std::vector<int32_t> oct(n);
+        if ((rc = fetch(c, oct.data(), f->oct, (size_t)n * 4))) return rc;
+        nmatches = window_accept_projection_host(nq, w.active, ci.data(), cd.data(), cn.data(), cap, oct.data(), w.qflag, occupied, w.nnratio, match);
+    } else {
+        std::vector<float> cur_angle, last_angle;
+        if (w.check_ori) {
+            cur_angle.resize(n);
+            if ((rc = fetch(c, cur_angle.data(), f->angle, (size_t)n * 4))) return rc;
+            if (w.last) { last_angle.resize(nq); if ((rc = fetch(c, last_angle.data(), w.last->angle, (size_t)nq * 4))) return rc; }
+        }
+        nmatches = window_accept_frame_host(nq, w.active, ci.data(), cd.data(), cn.data(), cap, w.qflag, occupied, w.orb_dist, w.check_ori,
+                                            w.last ? last_angle.data() : w.q_angle, cur_angle.data(), match);
+    }
+    std::memcpy(S.host + o_out, match, (size_t)n * 4);                       // the stream is idle: the staging area is free
+    if ((rc = upload(c, o_out, o_out + (size_t)n * 4))) return rc;
+    frame_launch_scatter_ids(st, n, d_out, id_src, nullptr, f->mp_id);
+    CCM_HIP(c, hipGetLastError());
+    return nmatches;
+}
+
+static int check_frame(ccm_ctx* c, const ccm_frame* f)
+{
+    if (!f->ctx) return ccm_fail(c, CCM_E_ARG, "frame handle outlived its context");
+    if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "frame handle belongs to another context");
+    return CCM_OK;
+}
+
+#define CCM_FRAME_GUARD(c, name, ...)                                                                                            \
+    try { __VA_ARGS__ }                                                                                                           \
+    catch (const std::bad_alloc&) { return (c) ? ccm_fail((c), CCM_E_NOMEM, name ": host allocation failed") : CCM_E_NOMEM; }   \
+    catch (const std::exception& e) { return (c) ? ccm_fail((c), CCM_E_DEVICE, name ": %s", e.what()) : CCM_E_DEVICE; }         \
+    catch (...) { return (c) ? ccm_fail((c), CCM_E_DEVICE, name ": unknown exception") : CCM_E_DEVICE; }
+
+extern "C" {
+
+int ccm_frame_create(ccm_ctx* c, const ccm_frame_grid* g, const float* angle, ccm_frame** out)
+{
+    RoctxRange roctx_("ccm_frame_create");
+    if (out) *out = nullptr;
+    if (!c || !g || !out) return CCM_E_ARG;
+    if (g->n < 0 || !grid_ok(g->grid_cols, g->grid_rows) || (g->n > 0 && (!g->kp_x || !g->kp_y || !g->kp_octave || !g->desc)))
+        return ccm_fail(c, CCM_E_ARG, "bad frame arguments (grid of at most 16384 cells)");
+    CCM_FRAME_GUARD(c, "ccm_frame_create", {
+        int max_oct = -1;
+        for (int i = 0; i < g->n; i++) {
+            if (g->kp_octave[i] < 0 || g->kp_octave[i] > 255) return ccm_fail(c, CCM_E_ARG, "octave of feature %d out of [0, 255]", i);
+            max_oct = std::max(max_oct, (int)g->kp_octave[i]);
+        }
+        CCM_HIP(c, hipSetDevice(c->device));
+        const int n = g->n;
+        const FrameLayout L = frame_layout(n, g->grid_cols * g->grid_rows);
+        uint8_t* h = nullptr;
+        int rc = staging(c, L.upload_end, &h);
+        if (rc) return rc;
+        std::memcpy(h + L.kx, g->kp_x, (size_t)n * 4); std::memcpy(h + L.ky, g->kp_y, (size_t)n * 4);
+        std::memcpy(h + L.oct, g->kp_octave, (size_t)n * 4);
+        if (angle) std::memcpy(h + L.angle, angle, (size_t)n * 4);
+        else std::memset(h + L.angle, 0, (size_t)n * 4);
+        std::memcpy(h + L.desc, g->desc, (size_t)n * 32);
+        ccm_frame* f = nullptr;
+        if ((rc = frame_alloc(c, n, g->grid_cols, g->grid_rows, &f))) return rc;
+        f->n_levels = max_oct + 1; f->has_angle = angle != nullptr;
+        f->min_x = g->min_x; f->min_y = g->min_y; f->inv_w = g->inv_w; f->inv_h = g->inv_h;
+        if ((rc = upload(c, 0, L.upload_end, f->mem->buf.p)) || (rc = frame_build(c, f, nullptr, nullptr, 0))) { frame_release(f); return rc; }
+        *out = f;
+        return CCM_OK;
+    })
+}
+
+int ccm_frame_from_extract(ccm_ctx* c, int image, int n, const float* kp_x_un, const float* kp_y_un, float min_x, float min_y,
+                           float inv_w, float inv_h, int grid_cols, int grid_rows, ccm_frame** out)
+{
+    RoctxRange roctx_("ccm_frame_from_extract");
+    if (out) *out = nullptr;
+    if (!c || !out) return CCM_E_ARG;
+    if (!grid_ok(grid_cols, grid_rows) || (!kp_x_un) != (!kp_y_un) || n < -1)
+        return ccm_fail(c, CCM_E_ARG, "bad frame arguments (grid of at most 16384 cells, both or neither coordinate array)");
+    CCM_FRAME_GUARD(c, "ccm_frame_from_extract", {
+        const ccm_keypoint* kps = nullptr; const uint8_t* desc = nullptr; const int32_t* counts = nullptr;
+        int n_images = 0, max_per_image = 0, nlevels = 0;
+        int rc = orb_last_result(c, &kps, &desc, &counts, &n_images, &max_per_image, &nlevels);
+        if (rc) return rc;
+        if (image < 0 || image >= n_images) return ccm_fail(c, CCM_E_ARG, "image %d out of range [0, %d)", image, n_images);
+        if (n > max_per_image) return ccm_fail(c, CCM_E_ARG, "n %d above the extract's max_per_image %d", n, max_per_image);
+        CCM_HIP(c, hipSetDevice(c->device));
+        if (n < 0) {
+            int32_t cnt = 0;
+            if ((rc = fetch(c, &cnt, counts + image, 4))) return rc;
+            n = std::min<int>(cnt, max_per_image);
+        }
+        const FrameLayout L = frame_layout(n, grid_cols * grid_rows);
+        if (kp_x_un) {
+            uint8_t* h = nullptr;
+            if ((rc = staging(c, L.oct, &h))) return rc;
+            std::memcpy(h + L.kx, kp_x_un, (size_t)n * 4); std::memcpy(h + L.ky, kp_y_un, (size_t)n * 4);
+        }
+        ccm_frame* f = nullptr;
+        if ((rc = frame_alloc(c, n, grid_cols, grid_rows, &f))) return rc;
+        f->n_levels = nlevels; f->has_angle = true;
+        f->min_x = min_x; f->min_y = min_y; f->inv_w = inv_w; f->inv_h = inv_h;
+        if ((kp_x_un && (rc = upload(c, 0, L.oct, f->mem->buf.p))) ||
+            (rc = frame_build(c, f, kps + (size_t)image * max_per_image, desc + (size_t)image * max_per_image * 32, kp_x_un ? 1 : 0))) {
+            frame_release(f); return rc;
+        }
+        *out = f;
+        return CCM_OK;
+    })
+}
+
+void ccm_frame_destroy(ccm_frame* f)
+{
+    if (!f) return;
+    try { frame_release(f); } catch (...) {}
+}
+
+int ccm_frame_size(const ccm_frame* f) { return f ? f->n : CCM_E_ARG; }
+
+int ccm_frame_set_map_points(ccm_frame* f, const int32_t* mp_id)
+{
+    if (!f) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    if (f->n == 0) return CCM_OK;
+    CCM_FRAME_GUARD(c, "ccm_frame_set_map_points", {
+        CCM_HIP(c, hipSetDevice(c->device));
+        if (!mp_id) { CCM_HIP(c, hipMemsetAsync(f->mp_id, 0xFF, (size_t)f->n * 4, c->stream)); return CCM_OK; }
+        uint8_t* h = nullptr;
+        int rc = staging(c, (size_t)f->n * 4, &h);
+        if (rc) return rc;
+        std::memcpy(h, mp_id, (size_t)f->n * 4);
+        return upload(c, 0, (size_t)f->n * 4, f->mp_id);
+    })
+}
+
+int ccm_frame_get_map_points(ccm_frame* f, int32_t* mp_id)
+{
+    if (!f || !mp_id) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    CCM_HIP(c, hipSetDevice(c->device));
+    return fetch(c, mp_id, f->mp_id, (size_t)f->n * 4);
+}
+
+int ccm_frame_debug_grid(ccm_frame* f, int32_t* cell_first, int32_t* cell_items)
+{
+    if (!f || !cell_first || !cell_items) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    CCM_HIP(c, hipSetDevice(c->device));
+    const int cells = f->cols * f->rows;
+    int rc = fetch(c, cell_first, f->cell_first, ((size_t)cells + 1) * 4);
+    if (rc) return rc;
+    if (cell_first[cells] < 0 || cell_first[cells] > f->n) return ccm_fail(c, CCM_E_DEVICE, "grid of %d items for %d features", cell_first[cells], f->n);
+    return fetch(c, cell_items, f->cell_items, (size_t)cell_first[cells] * 4);
+}
+
+// ORBmatcher::SearchByProjection(Frame&, const vector<mpptr>&, th), ORBmatcher.cpp:71-148, frame side from the handle
+int ccm_frame_search_by_projection(ccm_ctx* c, ccm_frame* f, const float* scale_factors, int n_mp, const uint8_t* in_view,
+                                   const int32_t* level, const float* view_cos, const float* proj_x, const float* proj_y,
+                                   const uint8_t* mp_desc, const uint8_t* mp_has_obs, const int32_t* query_mp_id,
+                                   uint8_t* occupied, float th, float nnratio, int32_t* match)
+{
+    RoctxRange roctx_("ccm_frame_search_by_projection");
+    if (!c || !f) return CCM_E_ARG;
+    int rc = check_frame(c, f);
+    if (rc) return rc;
+    if (n_mp < 0 || (f->n > 0 && (!match || !occupied)) ||
+        (n_mp > 0 && (!scale_factors || !in_view || !level || !view_cos || !proj_x || !proj_y || !mp_desc || !mp_has_obs)))
+        return ccm_fail(c, CCM_E_ARG, "bad SearchByProjection arguments");
+    for (int i = 0; i < f->n; i++) match[i] = -1;
+    if (n_mp == 0 || f->n == 0) return 0;
+    CCM_FRAME_GUARD(c, "ccm_frame_search_by_projection", {
+        CCM_HIP(c, hipSetDevice(c->device));
+        const bool bFactor = th != 1.0;                                            // as match_host.cpp
+        std::vector<float> qr(n_mp); std::vector<int32_t> minl(n_mp), maxl(n_mp);
+        for (int m = 0; m < n_mp; m++) {
+            if (!in_view[m]) { qr[m] = -1.f; minl[m] = 0; maxl[m] = 0; continue; }
+            float r = view_cos[m] > 0.998 ? 2.5f : 4.0f;                          // RadiusByViewingCos :150-156
+            if (bFactor) r *= th;
+            qr[m] = r * scale_factors[level[m]];
+            minl[m] = level[m] - 1; maxl[m] = level[m];
+        }
+        WinCall w{ 0, n_mp, proj_x, proj_y, qr.data(), minl.data(), maxl.data(), mp_desc, in_view, mp_has_obs, query_mp_id,
+                   nullptr, nullptr, 0.f, nullptr, nnratio, 0, 0 };
+        return frame_window(c, f, w, occupied, match);
+    })
+}
+
+// ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, th), ORBmatcher.cpp:1350-1476, and the relocalisation
+// overload (:1478-1605), current frame (and last frame) from handles
+int ccm_frame_search_by_projection_frame(ccm_ctx* c, ccm_frame* cur, const ccm_frame* last, const float* scale_factors, int n_last,
+                                         const uint8_t* valid, const float* u, const float* v, const int32_t* last_octave,
+                                         const float* last_angle, const uint8_t* mp_desc, const uint8_t* mp_has_obs,
+                                         const int32_t* query_mp_id, uint8_t* occupied, float th, int check_ori, int orb_dist,
+                                         int32_t* match)
+{
+    RoctxRange roctx_("ccm_frame_search_by_projection_frame");
+    if (!c || !cur) return CCM_E_ARG;
+    int rc = check_frame(c, cur);
+    if (rc || (last && (rc = check_frame(c, last)))) return rc;
+    if (n_last < 0 || (last && n_last != last->n)) return ccm_fail(c, CCM_E_ARG, "n_last must be >= 0 and equal the last frame's N");
+    if (check_ori && (!cur->has_angle || (last && !last->has_angle)))
+        return ccm_fail(c, CCM_E_ARG, "orientation check against a frame created without angles");
+    if ((cur->n > 0 && (!match || !occupied)) ||
+        (n_last > 0 && (!scale_factors || !valid || !u || !v || !mp_desc || !mp_has_obs || (!last && (!last_octave || (check_ori && !last_angle))))))
+        return ccm_fail(c, CCM_E_ARG, "bad SearchByProjection(frame, frame) arguments");
+    for (int i = 0; i < cur->n; i++) match[i] = -1;
+    if (n_last == 0 || cur->n == 0) return 0;
+    CCM_FRAME_GUARD(c, "ccm_frame_search_by_projection_frame", {
+        CCM_HIP(c, hipSetDevice(c->device));
+        std::vector<float> qr; std::vector<int32_t> minl, maxl;
+        if (!last) {
+            qr.resize(n_last); minl.resize(n_last); maxl.resize(n_last);
+            for (int i = 0; i < n_last; i++) {
+                if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = 0; continue; }
+                qr[i] = th * scale_factors[last_octave[i]];                       // :1401
+                minl[i] = last_octave[i] - 1; maxl[i] = last_octave[i] + 1;       // :1405
+            }
+        }
+        WinCall w{ 2, n_last, u, v, last ? nullptr : qr.data(), last ? nullptr : minl.data(), last ? nullptr : maxl.data(), mp_desc, valid,
+                   mp_has_obs, query_mp_id, last, scale_factors, th, last_angle, 0.f, orb_dist, check_ori ? 1 : 0 };
+        return frame_window(c, cur, w, occupied, match);
+    })
+}
+
+// Optimizer::PoseOptimizationClient(Frame&), src/Optimizer.cpp:215-347, the frame's correspondences gathered on the device
+int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp_xyz, const float* inv_level_sigma2, int n_levels,
+                            const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers)
+{
+    RoctxRange roctx_("ccm_frame_pose_optimize");
+    if (!c || !f) return CCM_E_ARG;
+    int rc = check_frame(c, f);
+    if (rc) return rc;
+    if (!intr || !pose7 || !n_inliers || n_mp < 0 || (n_mp > 0 && !mp_xyz) || (f->n > 0 && (!outlier || !inv_level_sigma2 || n_levels < 1)))
+        return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
+    if (f->n == 0) { *n_inliers = 0; return CCM_OK; }
+    CCM_FRAME_GUARD(c, "ccm_frame_pose_optimize", {
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        hipStream_t st = c->stream;
+        const int n = f->n;
+        size_t off = 0;
+        const size_t o_ninl = seg(off, 16), o_outl = seg(off, (size_t)n), o_pose = seg(off, 56);
+        const size_t res_end = o_pose + 56;
+        const size_t o_intr = seg(off, 32), o_is2 = seg(off, (size_t)n_levels * 4), o_xyz = seg(off, (size_t)n_mp * 24);
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = staging(c, end, &h))) return rc;
+        std::memcpy(h + o_pose, pose7, 56); std::memcpy(h + o_intr, intr, 32);
+        std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4); std::memcpy(h + o_xyz, mp_xyz, (size_t)n_mp * 24);
+        if ((rc = upload(c, o_pose, end))) return rc;
+        CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
+        CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
+        uint8_t* io = S.io.as<uint8_t>();
+        int* d_ninl = (int*)(io + o_ninl); int* d_status = d_ninl + 1;
+        PoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, n_mp, (const double*)(io + o_xyz), (const float*)(io + o_is2), n_levels,
+                          S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
+        frame_launch_pose_gather(st, G);
+        CCM_HIP(c, hipGetLastError());
+        PoseDev D{ 1, (double*)(io + o_pose), (const double*)(io + o_intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
+                   S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
+        pose_launch(st, D);
+        CCM_HIP(c, hipGetLastError());
+        frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = download(c, res_end))) return rc;
+        int head[2];
+        std::memcpy(head, S.host + o_ninl, 8);
+        if (head[1]) return ccm_fail(c, CCM_E_ARG, "a map-point id outside [0, %d) or an octave outside [0, %d)", n_mp, n_levels);
+        std::memcpy(pose7, S.host + o_pose, 56);
+        std::memcpy(outlier, S.host + o_outl, n);
+        *n_inliers = head[0];
+        return CCM_OK;
+    })
+}
+
+}  // extern "C"

@@ -1,0 +1,191 @@
+// frame_kernels.hip -- device side of the frame handles (frame_host.cpp, include/ccm_hot.h "frame handles"):
+//   k_frame_build         gather of an extracted image's keypoints / descriptors (ccm_frame_from_extract) and the feature grid
+//                         (Frame::AssignFeaturesToGrid / PosInGrid, src/Frame.cpp:103-118, 255-266), one workgroup per frame
+//   k_frame_prep_last     query radius and level window of SearchByProjection(Current, Last) from the last frame's octaves
+//   k_frame_scatter_ids   mvpMapPoints of the newly matched features
+//   k_frame_pose_gather   the correspondences of PoseOptimizationClient in feature order (compaction, first[] on the device)
+//   k_frame_pose_scatter  mvbOutlier per feature
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "../../include/ccm_hot.h"
+
+#define FB_TPB 1024
+
+struct FrameBuildArgs {                          // must match frame_host.cpp
+    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
+    const ccm_keypoint* kps; const uint8_t* src_desc;  // gather source (an extracted image) or nullptr: x..desc already written
+    int keep_xy;                                       // with kps: x / y were uploaded (undistorted), take only octave / angle / desc
+    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
+};
+
+// PosInGrid (src/Frame.cpp:255-266) exactly as the host build in match_host.cpp: round() in float, half away from zero; features
+// outside the grid get no cell.  A NaN coordinate gets none either (x86's conversion gives INT_MIN, the device's 0).
+__device__ inline int fb_cell(const FrameBuildArgs& A, float x, float y)
+{
+    const float fx = roundf((x - A.min_x) * A.inv_w), fy = roundf((y - A.min_y) * A.inv_h);
+    if (fx != fx || fy != fy) return -1;
+    const int px = (int)fx, py = (int)fy;
+    return (px < 0 || px >= A.cols || py < 0 || py >= A.rows) ? -1 : px * A.rows + py;
+}
+
+// One workgroup.  LDS: first[cells + 1] and fill[cells] counters.  Cell counts by LDS atomics, an exclusive scan, atomic placement,
+// then each cell's items sorted by feature index (a cell holds a handful of features): the order the host build's index-order
+// fill gives.
+__global__ __launch_bounds__(FB_TPB) void k_frame_build(FrameBuildArgs A)
+{
+    extern __shared__ int fb_lds[];
+    const int cells = A.cols * A.rows, tid = threadIdx.x;
+    int* s_first = fb_lds;                 // [cells + 1]
+    int* s_fill = fb_lds + cells + 1;      // [cells]
+    __shared__ int s_part[FB_TPB];
+    if (A.kps) {
+        for (int i = tid; i < A.n; i += FB_TPB) {
+            const ccm_keypoint k = A.kps[i];
+            if (!A.keep_xy) { A.kx[i] = k.x; A.ky[i] = k.y; }
+            A.oct[i] = k.octave; A.angle[i] = k.angle;
+            const uint4* s = reinterpret_cast<const uint4*>(A.src_desc + (size_t)i * 32);
+            uint4* d = reinterpret_cast<uint4*>(A.desc + (size_t)i * 32);
+            d[0] = s[0]; d[1] = s[1];
+        }
+    }
+    for (int i = tid; i < A.n; i += FB_TPB) A.mp_id[i] = -1;
+    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = 0;
+    __syncthreads();
+    for (int i = tid; i < A.n; i += FB_TPB) {
+        const int c = fb_cell(A, A.kx[i], A.ky[i]);
+        if (c >= 0) atomicAdd(&s_fill[c], 1);
+    }
+    __syncthreads();
+    // exclusive scan of the counts: a contiguous slice of cells per thread, then a scan of the slice sums
+    const int per = (cells + FB_TPB - 1) / FB_TPB, lo = min(tid * per, cells), hi = min(lo + per, cells);
+    int sum = 0;
+    for (int k = lo; k < hi; k++) sum += s_fill[k];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < FB_TPB; off <<= 1) {
+        const int v = tid >= off ? s_part[tid - off] : 0;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    int run = s_part[tid] - sum;
+    for (int k = lo; k < hi; k++) { const int cnt = s_fill[k]; s_first[k] = run; run += cnt; }
+    if (tid == FB_TPB - 1) s_first[cells] = s_part[FB_TPB - 1];
+    __syncthreads();
+    for (int k = tid; k <= cells; k += FB_TPB) A.cell_first[k] = s_first[k];
+    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = s_first[k];
+    __syncthreads();
+    for (int i = tid; i < A.n; i += FB_TPB) {
+        const int c = fb_cell(A, A.kx[i], A.ky[i]);
+        if (c >= 0) A.cell_items[atomicAdd(&s_fill[c], 1)] = i;
+    }
+    __syncthreads();                       // the placement's global writes are visible to the workgroup
+    for (int k = tid; k < cells; k += FB_TPB) {
+        const int a = s_first[k], b = s_first[k + 1];
+        for (int p = a + 1; p < b; p++) {  // insertion sort of one cell
+            const int v = A.cell_items[p];
+            int q = p - 1;
+            while (q >= a && A.cell_items[q] > v) { A.cell_items[q + 1] = A.cell_items[q]; q--; }
+            A.cell_items[q + 1] = v;
+        }
+    }
+}
+
+// SearchByProjection(Current, Last) query set-up (ORBmatcher.cpp:1401-1405) from the last frame's octaves in HBM: the host
+// computes the same in match_host.cpp (th * scale_factors[octave] in float; levels octave-1 .. octave+1; skipped: r = -1).
+__global__ void k_frame_prep_last(int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = 0; return; }
+    const int o = oct[i];
+    qr[i] = th * scale[o];
+    minl[i] = o - 1; maxl[i] = o + 1;
+}
+
+// mp_id[i] = src[match[i]] (or match[i] when src is null) for every matched feature; nothing when the acceptance kernel reported a
+// list overflow (status[0] < 0: the host repeats the call)
+__global__ void k_frame_scatter_ids(int n, const int* match, const int* src, const int* status, int* mp_id)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || (status && status[0] < 0)) return;
+    const int q = match[i];
+    if (q >= 0) mp_id[i] = src ? src[q] : q;
+}
+
+struct PoseGatherArgs {                          // must match frame_host.cpp
+    int n; const float* kx; const float* ky; const int* oct; const int* mp_id;
+    int n_mp; const double* xyz; const float* inv_sigma2; int n_levels;
+    int* first; double* pts; double* obs; double* info; int* kof; int* status;
+};
+
+// One workgroup: the features with mp_id >= 0, in feature order (the loop of Optimizer.cpp:244-281), compacted by a ballot scan.
+// kof[i] = the correspondence of feature i or -1.  A bad id or octave sets status[0] and leaves no correspondence (first[1] = 0),
+// so the pose kernel behind it leaves the pose alone and the host reports CCM_E_ARG.
+__global__ __launch_bounds__(FB_TPB) void k_frame_pose_gather(PoseGatherArgs A)
+{
+    __shared__ int s_wave[FB_TPB / 64];
+    __shared__ int s_base, s_bad;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) { s_base = 0; s_bad = 0; }
+    __syncthreads();
+    for (int base = 0; base < A.n; base += FB_TPB) {
+        const int i = base + tid;
+        const int id = i < A.n ? A.mp_id[i] : -1;
+        const bool has = id >= 0;
+        const int o = has ? A.oct[i] : 0;
+        const bool bad = has && (id >= A.n_mp || o < 0 || o >= A.n_levels);
+        if (bad) s_bad = 1;
+        const unsigned long long ball = __ballot(has);
+        const int before = __popcll(ball & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wv] = __popcll(ball);
+        __syncthreads();
+        int off = s_base;
+        for (int w = 0; w < wv; w++) off += s_wave[w];
+        const int k = off + before;
+        if (i < A.n) A.kof[i] = has ? k : -1;
+        if (has) {
+            for (int d = 0; d < 3; d++) A.pts[3 * (size_t)k + d] = bad ? 0.0 : A.xyz[3 * (size_t)id + d];
+            A.obs[2 * (size_t)k] = (double)A.kx[i]; A.obs[2 * (size_t)k + 1] = (double)A.ky[i];
+            A.info[k] = bad ? 0.0 : (double)A.inv_sigma2[o];
+        }
+        __syncthreads();
+        if (tid == 0) { int t = 0; for (int w = 0; w < FB_TPB / 64; w++) t += s_wave[w]; s_base += t; }
+        __syncthreads();
+    }
+    if (tid == 0) { A.first[0] = 0; A.first[1] = s_bad ? 0 : s_base; A.status[0] = s_bad; }
+}
+
+__global__ void k_frame_pose_scatter(int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = kof[i];
+    outlier[i] = (k >= 0 && k < first[1]) ? outl[k] : 0;
+}
+
+size_t frame_build_lds(int cells) { return ((size_t)2 * cells + 1) * 4; }
+
+int frame_launch_build(hipStream_t s, const FrameBuildArgs& A)
+{
+    const size_t lds = frame_build_lds(A.cols * A.rows);
+    if (hipFuncSetAttribute((const void*)k_frame_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_frame_build, dim3(1), dim3(FB_TPB), lds, s, A);
+    return 0;
+}
+void frame_launch_prep_last(hipStream_t s, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl)
+{
+    if (nq > 0) hipLaunchKernelGGL(k_frame_prep_last, dim3((nq + 255) / 256), dim3(256), 0, s, nq, valid, oct, scale, th, qr, minl, maxl);
+}
+void frame_launch_scatter_ids(hipStream_t s, int n, const int* match, const int* src, const int* status, int* mp_id)
+{
+    if (n > 0) hipLaunchKernelGGL(k_frame_scatter_ids, dim3((n + 255) / 256), dim3(256), 0, s, n, match, src, status, mp_id);
+}
+void frame_launch_pose_gather(hipStream_t s, const PoseGatherArgs& A)
+{
+    hipLaunchKernelGGL(k_frame_pose_gather, dim3(1), dim3(FB_TPB), 0, s, A);
+}
+void frame_launch_pose_scatter(hipStream_t s, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier)
+{
+    if (n > 0) hipLaunchKernelGGL(k_frame_pose_scatter, dim3((n + 255) / 256), dim3(256), 0, s, n, kof, first, outl, outlier);
+}

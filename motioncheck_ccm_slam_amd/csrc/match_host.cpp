@@ -1,6 +1,7 @@
 // match_host.cpp -- C ABI of the matcher (include/ccm_hot.h): brute-force Hamming search,
 // ORBmatcher::SearchByBoW (cslam/src/ORBmatcher.cpp:178-306, 565-698; on the device, k_bow_greedy) and the windowed matchers.
 #include "ccm_internal.h"
+#include "window_types.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -275,35 +276,16 @@ int ccm_match_bow(ccm_ctx* c, const ccm_bow_options* o, const uint8_t* desc1, co
 // (k_window_greedy: the reference's order-dependent occupancy bookkeeping resolved by claim rounds, bit-identical to the
 // sequential loop; the frame matcher's rotation histogram and its three maxima in the same kernel).  Only the
 // initialisation matcher (called once per map) keeps its acceptance loop on the host.
-struct WinGrid {
-    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
-    const float* kx; const float* ky; const int* oct; const uint8_t* desc; const int* cell_first; const int* cell_items;
-};
-void match_launch_window(hipStream_t, const WinGrid&, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
-                         const int* maxl, const uint8_t* qdesc, int cap, int* ci, int* cd, int* cn);
-
 void match_launch_window_select_batch(hipStream_t, const WinGrid* grids, const int* q_kf, int nq, const float* qx, const float* qy, const float* qr,
                                       const int* minl, const int* maxl, const uint8_t* qdesc, const float* inv_sigma2, int accept_th, int* best_idx, int* best_dist);
 void match_launch_window_select(hipStream_t, const WinGrid&, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
                                 const int* maxl, const uint8_t* qdesc, const float* inv_sigma2, int accept_th, int* best_idx, int* best_dist);
-struct GreedyArgs {
-    int nq, n, cap; const int* ci; const int* cd; const int* cn; const uint8_t* active; const int* qlevel; const int* oct; const uint8_t* qflag;
-    uint8_t* flag; float nnratio; int* out; int* status;
-    int orb_dist, check_ori; const float* q_angle; const float* f_angle; int* ev;
-    const struct GreedyKf* kfs;
-};
-struct GreedyKf { int q0, nq, f0, n; };
 int match_launch_window_greedy_batch(hipStream_t, const GreedyArgs&, int n_kf, int max_n);
 void match_launch_window_batch(hipStream_t, const WinGrid* grids, const int* q_kf, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
                                const int* maxl, const uint8_t* qdesc, int cap, int* ci, int* cd, int* cn);
-size_t match_window_greedy_lds(int n, int nq);
-int match_launch_window_greedy(hipStream_t, int mode, const GreedyArgs&);
 
 struct WindowBufs { DevBuf kx, ky, oct, desc, cfirst, citems, qx, qy, qr, minl, maxl, qdesc, ci, cd, cn, sel_i, sel_d, is2, act, qlvl, qflag, flag, out, status, qang, fang, ev,
                            grids, qkf, gkf; };
-// LDS the single-workgroup acceptance kernel may ask for (claim + flag per feature, one byte per query); larger problems take the
-// host loops below
-static const size_t kGreedyLdsMax = 150 * 1024;
 
 // mode 0: candidate lists to the host (ci / cd / cn); 1: lists stay in HBM for k_window_greedy; 2: no lists, k_window_select
 // leaves one (index, distance) per query in W.sel_i / W.sel_d
@@ -413,6 +395,77 @@ static int window_greedy(ccm_ctx* c, const ccm_frame_grid* f, int nq, const floa
     return ccm_fail(c, CCM_E_CAPACITY, "window candidate lists keep overflowing");
 }
 
+bool window_host_accept_forced()
+{
+    static const bool host_accept = getenv("CCM_WINDOW_HOST_ACCEPT") && atoi(getenv("CCM_WINDOW_HOST_ACCEPT")) != 0;   // test switch
+    return host_accept;
+}
+
+int window_accept_projection_host(int n_mp, const uint8_t* in_view, const int32_t* ci, const int32_t* cd, const int32_t* cn, int cap,
+                                  const int32_t* kp_octave, const uint8_t* mp_has_obs, uint8_t* occupied, float nnratio, int32_t* match)
+{
+    int nmatches = 0;
+    for (int m = 0; m < n_mp; m++) {
+        if (!in_view[m] || cn[m] == 0) continue;
+        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+        for (int k = 0; k < cn[m]; k++) {
+            const int idx = ci[(size_t)m * cap + k];
+            if (occupied[idx]) continue;                                       // mvpMapPoints[idx] with Observations() > 0
+            const int dist = cd[(size_t)m * cap + k];
+            if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = kp_octave[idx]; bestIdx = idx; }
+            else if (dist < bestDist2) { bestLevel2 = kp_octave[idx]; bestDist2 = dist; }
+        }
+        if (bestDist <= 100) {                                                 // TH_HIGH
+            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
+            match[bestIdx] = m;
+            occupied[bestIdx] = mp_has_obs[m];
+            nmatches++;
+        }
+    }
+    return nmatches;
+}
+
+int window_accept_frame_host(int n_last, const uint8_t* valid, const int32_t* ci, const int32_t* cd, const int32_t* cn, int cap,
+                             const uint8_t* mp_has_obs, uint8_t* occupied, int orb_dist, int check_ori, const float* last_angle,
+                             const float* cur_angle, int32_t* match)
+{
+    const int HISTO = 30;
+    std::vector<int> rot[HISTO];
+    const float factor = 1.0f / HISTO;
+    int nmatches = 0;
+    for (int i = 0; i < n_last; i++) {
+        if (!valid[i] || cn[i] == 0) continue;
+        int bestDist = 256, bestIdx2 = -1;
+        for (int k = 0; k < cn[i]; k++) {
+            const int i2 = ci[(size_t)i * cap + k];
+            if (occupied[i2]) continue;
+            const int dist = cd[(size_t)i * cap + k];
+            if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
+        }
+        if (bestDist <= orb_dist) {                                            // TH_HIGH (:1432) / ORBdist (:1556)
+            match[bestIdx2] = i;
+            occupied[bestIdx2] = mp_has_obs[i];
+            nmatches++;
+            if (check_ori) {
+                float r = last_angle[i] - cur_angle[bestIdx2];
+                if (r < 0.0) r += 360.0f;
+                int bin = (int)std::round(r * factor);
+                if (bin == HISTO) bin = 0;
+                rot[bin].push_back(bestIdx2);
+            }
+        }
+    }
+    if (check_ori) {
+        int i1, i2, i3;
+        three_maxima(rot, HISTO, i1, i2, i3);
+        for (int b = 0; b < HISTO; b++) {
+            if (b == i1 || b == i2 || b == i3) continue;
+            for (int idx : rot[b]) { match[idx] = -1; nmatches--; }
+        }
+    }
+    return nmatches;
+}
+
 void match_window_free(WindowBufs* w)
 {
     if (!w) return;
@@ -464,8 +517,7 @@ int ccm_search_by_projection(ccm_ctx* c, const ccm_frame_grid* f, const float* s
         qr[m] = r * scale_factors[level[m]];
         minl[m] = level[m] - 1; maxl[m] = level[m];
     }
-    static const bool host_accept = getenv("CCM_WINDOW_HOST_ACCEPT") && atoi(getenv("CCM_WINDOW_HOST_ACCEPT")) != 0;   // test switch
-    if (!host_accept && match_window_greedy_lds(f->n, n_mp) <= kGreedyLdsMax)
+    if (!window_host_accept_forced() && match_window_greedy_lds(f->n, n_mp) <= kGreedyLdsMax)
         return window_greedy(c, f, n_mp, proj_x, proj_y, qr.data(), minl.data(), maxl.data(), mp_desc, 0, in_view, nullptr, mp_has_obs, occupied,
                              nnratio, match, f->n);
     int cap = 64;
@@ -478,25 +530,7 @@ int ccm_search_by_projection(ccm_ctx* c, const ccm_frame_grid* f, const float* s
         if (mx <= cap) break;
         cap = mx;                                                              // rare: a denser window than expected
     }
-    int nmatches = 0;
-    for (int m = 0; m < n_mp; m++) {
-        if (!in_view[m] || cn[m] == 0) continue;
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for (int k = 0; k < cn[m]; k++) {
-            const int idx = ci[(size_t)m * cap + k];
-            if (occupied[idx]) continue;                                       // mvpMapPoints[idx] with Observations() > 0
-            const int dist = cd[(size_t)m * cap + k];
-            if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = f->kp_octave[idx]; bestIdx = idx; }
-            else if (dist < bestDist2) { bestLevel2 = f->kp_octave[idx]; bestDist2 = dist; }
-        }
-        if (bestDist <= 100) {                                                 // TH_HIGH
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-            match[bestIdx] = m;
-            occupied[bestIdx] = mp_has_obs[m];
-            nmatches++;
-        }
-    }
-    return nmatches;
+    return window_accept_projection_host(n_mp, in_view, ci.data(), cd.data(), cn.data(), cap, f->kp_octave, mp_has_obs, occupied, nnratio, match);
 }
 
 // ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, th), ORBmatcher.cpp:1350-1476
@@ -518,8 +552,7 @@ int ccm_search_by_projection_frame(ccm_ctx* c, const ccm_frame_grid* f, const fl
         qr[i] = th * scale_factors[last_octave[i]];                           // :1401
         minl[i] = last_octave[i] - 1; maxl[i] = last_octave[i] + 1;           // :1405
     }
-    static const bool host_accept = getenv("CCM_WINDOW_HOST_ACCEPT") && atoi(getenv("CCM_WINDOW_HOST_ACCEPT")) != 0;   // test switch
-    if (!host_accept && match_window_greedy_lds(f->n, n_last) <= kGreedyLdsMax)
+    if (!window_host_accept_forced() && match_window_greedy_lds(f->n, n_last) <= kGreedyLdsMax)
         return window_greedy(c, f, n_last, u, v, qr.data(), minl.data(), maxl.data(), mp_desc, 2, valid, nullptr, mp_has_obs, occupied, 0.f, match, f->n,
                              orb_dist, check_ori, last_angle, cur_angle);
     int cap = 64;
@@ -532,41 +565,8 @@ int ccm_search_by_projection_frame(ccm_ctx* c, const ccm_frame_grid* f, const fl
         if (mx <= cap) break;
         cap = mx;
     }
-    const int HISTO = 30;
-    std::vector<int> rot[HISTO];
-    const float factor = 1.0f / HISTO;
-    int nmatches = 0;
-    for (int i = 0; i < n_last; i++) {
-        if (!valid[i] || cn[i] == 0) continue;
-        int bestDist = 256, bestIdx2 = -1;
-        for (int k = 0; k < cn[i]; k++) {
-            const int i2 = ci[(size_t)i * cap + k];
-            if (occupied[i2]) continue;
-            const int dist = cd[(size_t)i * cap + k];
-            if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
-        }
-        if (bestDist <= orb_dist) {                                            // TH_HIGH (:1432) / ORBdist (:1556)
-            match[bestIdx2] = i;
-            occupied[bestIdx2] = mp_has_obs[i];
-            nmatches++;
-            if (check_ori) {
-                float r = last_angle[i] - cur_angle[bestIdx2];
-                if (r < 0.0) r += 360.0f;
-                int bin = (int)std::round(r * factor);
-                if (bin == HISTO) bin = 0;
-                rot[bin].push_back(bestIdx2);
-            }
-        }
-    }
-    if (check_ori) {
-        int i1, i2, i3;
-        three_maxima(rot, HISTO, i1, i2, i3);
-        for (int b = 0; b < HISTO; b++) {
-            if (b == i1 || b == i2 || b == i3) continue;
-            for (int idx : rot[b]) { match[idx] = -1; nmatches--; }
-        }
-    }
-    return nmatches;
+    return window_accept_frame_host(n_last, valid, ci.data(), cd.data(), cn.data(), cap, mp_has_obs, occupied, orb_dist, check_ori, last_angle,
+                                    cur_angle, match);
 }
 
 // ORBmatcher::SearchForInitialization, ORBmatcher.cpp:448-563

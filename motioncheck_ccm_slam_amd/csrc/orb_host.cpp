@@ -357,6 +357,18 @@ static int orb_check_status(ccm_ctx* c)
     return CCM_OK;
 }
 
+// The last extract's results in device memory, for ccm_frame_from_extract (frame_host.cpp): keypoints [n_images][max_per_image],
+// descriptor rows likewise, counts [n_images].  Returns CCM_E_STATE when this context has not extracted yet.
+int orb_last_result(ccm_ctx* c, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
+                    int* nlevels)
+{
+    if (!c->orb || !c->orb->have_result) return ccm_fail(c, CCM_E_STATE, "no extraction on this context yet");
+    const OrbState& S = *c->orb;
+    *kps = S.kps.as<ccm_keypoint>(); *desc = S.desc.as<uint8_t>(); *counts = S.counts.as<int32_t>();
+    *n_images = S.nframes; *max_per_image = S.max_per_image; *nlevels = S.par.nlevels;
+    return CCM_OK;
+}
+
 extern "C" {
 
 int ccm_orb_tables(const ccm_orb_params* p, float* scale, float* inv_scale, float* sigma2, float* inv_sigma2,

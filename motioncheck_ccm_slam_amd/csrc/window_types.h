@@ -1,0 +1,40 @@
+// window_types.h -- the windowed matchers' device structures and launchers (match_kernels.hip), shared by the host translation
+// units that drive them: match_host.cpp (host arrays per call) and frame_host.cpp (frame handles).  The structures must match
+// match_kernels.hip.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <hip/hip_runtime.h>
+
+struct WinGrid {
+    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
+    const float* kx; const float* ky; const int* oct; const uint8_t* desc; const int* cell_first; const int* cell_items;
+};
+void match_launch_window(hipStream_t, const WinGrid&, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
+                         const int* maxl, const uint8_t* qdesc, int cap, int* ci, int* cd, int* cn);
+
+struct GreedyArgs {
+    int nq, n, cap; const int* ci; const int* cd; const int* cn; const uint8_t* active; const int* qlevel; const int* oct; const uint8_t* qflag;
+    uint8_t* flag; float nnratio; int* out; int* status;
+    int orb_dist, check_ori; const float* q_angle; const float* f_angle; int* ev;
+    const struct GreedyKf* kfs;
+};
+struct GreedyKf { int q0, nq, f0, n; };
+size_t match_window_greedy_lds(int n, int nq);
+int match_launch_window_greedy(hipStream_t, int mode, const GreedyArgs&);
+
+// LDS the single-workgroup acceptance kernel may ask for (claim + flag per feature, one byte per query); larger problems take the
+// host loops below
+static const size_t kGreedyLdsMax = 150 * 1024;
+
+// The host acceptance loops (the round-1 path; CCM_WINDOW_HOST_ACCEPT=1 or problems above kGreedyLdsMax) on candidate lists
+// [nq][cap] with counts cn.  match[] must be pre-set to -1; occupied is updated; return nmatches.
+// SearchByProjection(Frame&, map points), ORBmatcher.cpp:71-148 (kp_octave: the frame's octaves)
+int window_accept_projection_host(int n_mp, const uint8_t* in_view, const int32_t* ci, const int32_t* cd, const int32_t* cn, int cap,
+                                  const int32_t* kp_octave, const uint8_t* mp_has_obs, uint8_t* occupied, float nnratio, int32_t* match);
+// SearchByProjection(Frame&, Frame | KeyFrame), ORBmatcher.cpp:1350-1476, :1478-1605
+int window_accept_frame_host(int n_last, const uint8_t* valid, const int32_t* ci, const int32_t* cd, const int32_t* cn, int cap,
+                             const uint8_t* mp_has_obs, uint8_t* occupied, int orb_dist, int check_ori, const float* last_angle,
+                             const float* cur_angle, int32_t* match);
+// true when CCM_WINDOW_HOST_ACCEPT=1 (test switch)
+bool window_host_accept_forced();

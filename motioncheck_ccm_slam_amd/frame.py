@@ -1,0 +1,98 @@
+"""Device-resident frames (include/ccm_hot.h "frame handles"): one `Frame`'s undistorted keypoints, descriptors, feature grid and
+map-point ids kept on the GPU for the frame's lifetime, so that the per-frame calls of Tracking (SearchByProjection twice, pose
+optimisation twice, src/Tracking.cpp:571-597 and :905-920) upload only their per-call inputs.
+
+Map points are ids into the caller's map-point table, -1 = none (`Frame::mvpMapPoints`)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .matcher import FRAME_GRID_COLS, FRAME_GRID_ROWS, FrameGridView
+
+
+class DeviceFrame:
+    """A ccm_frame handle.  Build with `DeviceFrame(view, angle, ctx=...)` from host arrays or `DeviceFrame.from_extract` from the
+    last extraction of an `ORBextractor`; release with `close()` (before the context goes)."""
+
+    def __init__(self, view: FrameGridView | None = None, angle=None, ctx: _lib.Context | None = None, _handle=None):
+        self.ctx = ctx or _lib.default_context(0)
+        self.lib = self.ctx.lib
+        if _handle is None:
+            if view is None:
+                raise ValueError("DeviceFrame needs a FrameGridView (or use DeviceFrame.from_extract)")
+            self._angle = None if angle is None else np.ascontiguousarray(angle, "f4")
+            if self._angle is not None and len(self._angle) != len(view.kx):
+                raise ValueError("angle must have one entry per feature")
+            g = view.struct()
+            h = C.c_void_p()
+            self.ctx.check(self.lib.ccm_frame_create(self.ctx.handle, C.byref(g), _lib.ptr(self._angle), C.byref(h)))
+            _handle = h.value
+        self.handle = _handle
+        self.n = self.lib.ccm_frame_size(C.c_void_p(self.handle))
+
+    @classmethod
+    def from_extract(cls, extractor, image: int = 0, kx_un=None, ky_un=None, n: int = -1, min_x=0.0, max_x=752.0, min_y=0.0, max_y=480.0,
+                     ctx: _lib.Context | None = None):
+        """Frame of image `image` of the extractor's last extract (ccm_frame_from_extract): octave, angle and descriptors stay on the
+        device; kx_un / ky_un are the undistorted coordinates (None: the extracted ones).  n = keypoint count (-1: read it)."""
+        ctx = ctx or extractor.ctx
+        lib = ctx.lib
+        kx = None if kx_un is None else np.ascontiguousarray(kx_un, "f4")
+        ky = None if ky_un is None else np.ascontiguousarray(ky_un, "f4")
+        if (kx is None) != (ky is None):
+            raise ValueError("give both undistorted coordinate arrays or neither")
+        if kx is not None:
+            if n < 0:
+                n = len(kx)
+            if len(kx) < n or len(ky) < n:
+                raise ValueError("coordinate arrays shorter than n")
+        inv_w = np.float32(FRAME_GRID_COLS) / np.float32(np.float32(max_x) - np.float32(min_x))
+        inv_h = np.float32(FRAME_GRID_ROWS) / np.float32(np.float32(max_y) - np.float32(min_y))
+        h = C.c_void_p()
+        ctx.check(lib.ccm_frame_from_extract(ctx.handle, int(image), int(n), _lib.ptr(kx), _lib.ptr(ky), float(np.float32(min_x)),
+                                             float(np.float32(min_y)), float(inv_w), float(inv_h), FRAME_GRID_COLS, FRAME_GRID_ROWS,
+                                             C.byref(h)))
+        return cls(ctx=ctx, _handle=h.value)
+
+    @property
+    def map_points(self) -> np.ndarray:
+        out = np.empty(max(self.n, 1), "i4")
+        self.ctx.check(self.lib.ccm_frame_get_map_points(C.c_void_p(self.handle), _lib.ptr(out)))
+        return out[:self.n]
+
+    @map_points.setter
+    def map_points(self, ids):
+        """None = all -1 (fill(mvpMapPoints, nullptr)); else one id per feature."""
+        a = None
+        if ids is not None:
+            a = np.ascontiguousarray(ids, "i4")
+            if a.shape != (self.n,):
+                raise ValueError("map_points needs %d ids" % self.n)
+        self.ctx.check(self.lib.ccm_frame_set_map_points(C.c_void_p(self.handle), _lib.ptr(a)))
+
+    def grid(self):
+        """(cell_first [cols*rows+1], cell_items) of the device-built grid (ccm_frame_debug_grid)."""
+        first = np.zeros(FRAME_GRID_COLS * FRAME_GRID_ROWS + 1, "i4")
+        items = np.zeros(max(self.n, 1), "i4")
+        self.ctx.check(self.lib.ccm_frame_debug_grid(C.c_void_p(self.handle), _lib.ptr(first), _lib.ptr(items)))
+        return first, items[:first[-1]]
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.ccm_frame_destroy(C.c_void_p(self.handle))
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -147,6 +147,47 @@ def _search_by_projection_frame(self, cur: FrameGridView, cur_angle, scale_facto
 ORBmatcher.SearchByProjectionFrame = _search_by_projection_frame
 
 
+def _search_by_projection_handle(self, frame, scale_factors, in_view, level, view_cos, proj_x, proj_y, mp_desc, mp_has_obs, occupied,
+                                 th: float = 1.0, query_mp_id=None):
+    """SearchByProjection(Frame&, vpMapPoints, th) with the frame side from a `frame.DeviceFrame` (ccm_frame_search_by_projection).
+    Same results as SearchByProjection; the handle's map_points become query_mp_id[q] (or q) for every newly matched feature."""
+    a = np.ascontiguousarray
+    sf = a(scale_factors, "f4"); iv = a(in_view, np.uint8); lv = a(level, "i4"); vc = a(view_cos, "f4")
+    px = a(proj_x, "f4"); py = a(proj_y, "f4"); md = a(mp_desc, np.uint8); ho = a(mp_has_obs, np.uint8)
+    qid = None if query_mp_id is None else a(query_mp_id, "i4")
+    occ = a(occupied, np.uint8).copy()
+    match = np.full(max(frame.n, 1), -1, "i4")
+    p = _lib.ptr
+    n = self.ctx.check(self.lib.ccm_frame_search_by_projection(self.ctx.handle, C.c_void_p(frame.handle), p(sf), len(iv), p(iv), p(lv), p(vc),
+                                                               p(px), p(py), p(md), p(ho), p(qid), p(occ), C.c_float(th),
+                                                               C.c_float(self.mfNNratio), p(match)))
+    return n, match[:frame.n], occ
+
+
+def _search_by_projection_frame_handle(self, cur, last, scale_factors, valid, u, v, mp_desc, mp_has_obs, occupied, th: float,
+                                       last_octave=None, last_angle=None, orb_dist: int = 100, query_mp_id=None):
+    """SearchByProjection(Current, Last | KeyFrame) with `cur` a DeviceFrame (ccm_frame_search_by_projection_frame).  last = a
+    DeviceFrame: its octaves, angles and map-point ids are used; last = None: the relocalisation form with last_octave /
+    last_angle arrays.  Returns (nmatches, match[feature of cur] = query index or -1, occupied)."""
+    a = np.ascontiguousarray
+    sf = a(scale_factors, "f4"); va = a(valid, np.uint8); uu = a(u, "f4"); vv = a(v, "f4")
+    md = a(mp_desc, np.uint8); ho = a(mp_has_obs, np.uint8)
+    lo = None if last_octave is None else a(last_octave, "i4")
+    la = None if last_angle is None else a(last_angle, "f4")
+    qid = None if query_mp_id is None else a(query_mp_id, "i4")
+    occ = a(occupied, np.uint8).copy()
+    match = np.full(max(cur.n, 1), -1, "i4")
+    p = _lib.ptr
+    n = self.ctx.check(self.lib.ccm_frame_search_by_projection_frame(
+        self.ctx.handle, C.c_void_p(cur.handle), None if last is None else C.c_void_p(last.handle), p(sf), len(va), p(va), p(uu), p(vv),
+        p(lo), p(la), p(md), p(ho), p(qid), p(occ), C.c_float(th), int(self.mbCheckOrientation), int(orb_dist), p(match)))
+    return n, match[:cur.n], occ
+
+
+ORBmatcher.SearchByProjectionHandle = _search_by_projection_handle
+ORBmatcher.SearchByProjectionFrameHandle = _search_by_projection_frame_handle
+
+
 def _search_for_initialization(self, oct1, desc1, angle1, f2: FrameGridView, angle2, prev_matched, window: int = 100):
     """ORBmatcher::SearchForInitialization (ORBmatcher.cpp:448-563).  Returns (nmatches, matches12, prev_matched)."""
     a = np.ascontiguousarray

@@ -134,6 +134,21 @@ class Optimizer:
         ctx.check(lib.ccm_pose_optimize(ctx.handle, C.byref(pb)))
         return poses, outl[:len(info)], ninl
 
+    @staticmethod
+    def PoseOptimizationFrame(frame, pose, intr, mp_xyz, inv_level_sigma2, ctx=None):
+        """Optimizer::PoseOptimizationClient(Frame&) (src/Optimizer.cpp:215-347) on a `frame.DeviceFrame`: the correspondences are its
+        features with a map point (ids into mp_xyz [n_mp][3]), obs = its undistorted keypoints, info = inv_level_sigma2[octave].
+        Returns (pose7, outlier per feature, nInliers)."""
+        ctx = ctx or frame.ctx
+        lib = _lib.load()
+        pose = np.ascontiguousarray(pose, "f8").copy(); intr = np.ascontiguousarray(intr, "f8")
+        xyz = np.ascontiguousarray(mp_xyz, "f8").reshape(-1, 3); is2 = np.ascontiguousarray(inv_level_sigma2, "f4")
+        outl = np.zeros(max(frame.n, 1), np.uint8); ninl = np.zeros(1, "i4")
+        p = _lib.ptr
+        ctx.check(lib.ccm_frame_pose_optimize(ctx.handle, C.c_void_p(frame.handle), len(xyz), p(xyz), p(is2), len(is2), p(intr), p(pose),
+                                              p(outl), p(ninl)))
+        return pose, outl[:frame.n], int(ninl[0])
+
 
     @staticmethod
     def OptimizeSim3(sim3, fix_scale, K1, K2, first, P1, P2, obs1, obs2, info1, info2, th2, ctx=None):

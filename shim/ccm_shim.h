@@ -9,18 +9,73 @@
 #pragma once
 #include <ccm_hot.h>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 namespace ccm_shim {
 
 // One context (HIP stream + workspaces) per calling thread: Tracking, LocalMapping, LoopFinder and MapMatcher each run in
-// their own thread in the reference (src/ClientHandler.cpp:140-176), and a ccm_ctx is not meant to be shared.
+// their own thread in the reference (src/ClientHandler.cpp:140-176), and a ccm_ctx is not meant to be shared.  The same
+// thread-local object caches the device-resident frames (ccm_frame) of the two Frames Tracking works on -- the current one and
+// mLastFrame -- so that the Frame-side SearchByProjection bodies upload a Frame's keypoints and descriptors once, not per call.
+// Members are destroyed in reverse order: the frames go before the context.
+struct ThreadState {
+    struct Slot { size_t id0 = ~(size_t)0, id1 = ~(size_t)0; int n = -1; ccm_frame* f = nullptr; unsigned used = 0; };
+    // a shim object built against another version of ccm_hot.h than the library would pass structures of the wrong size
+    ccm_ctx* c = ccm_abi_version() == CCM_ABI_VERSION ? ccm_create(0, 0) : nullptr;
+    Slot slot[2];
+    unsigned clock = 0;
+    ThreadState() = default;
+    ThreadState(const ThreadState&) = delete;
+    ThreadState& operator=(const ThreadState&) = delete;
+    ~ThreadState()
+    {
+        for (Slot& s : slot) ccm_frame_destroy(s.f);
+        if (c) ccm_destroy(c);
+    }
+};
+inline ThreadState& thread_state()
+{
+    static thread_local ThreadState s;
+    return s;
+}
 inline ccm_ctx* ctx()
 {
-    // a shim object built against another version of ccm_hot.h than the library would pass structures of the wrong size
-    static thread_local ccm_ctx* c = ccm_abi_version() == CCM_ABI_VERSION ? ccm_create(0, 0) : nullptr;
-    return c;                                          // nullptr: every ccm_* call returns CCM_E_ARG and the shim bodies throw
+    return thread_state().c;                           // nullptr: every ccm_* call returns CCM_E_ARG and the shim bodies throw
 }
+
+// CCM_SHIM_FRAME_HANDLES=0: the Frame-side matchers go back to uploading the Frame per call (A/B timing of the two paths)
+inline bool frame_handles_on()
+{
+    static const bool on = !(getenv("CCM_SHIM_FRAME_HANDLES") && atoi(getenv("CCM_SHIM_FRAME_HANDLES")) == 0);
+    return on;
+}
+
+#ifdef FRAME_GRID_COLS                                 // translation units that include cslam/Frame.h
+// The cached ccm_frame of Frame F, keyed on Frame::mId and checked against N (a Frame's mvKeysUn and mDescriptors never change after
+// its constructor), made on a miss in the least recently used slot; nullptr on failure.
+template <class FrameT>
+inline ccm_frame* frame_handle(const FrameT& F)
+{
+    ThreadState& S = thread_state();
+    const int N = (int)F.mvKeysUn.size();
+    S.clock++;
+    for (ThreadState::Slot& s : S.slot)
+        if (s.f && s.id0 == F.mId.first && s.id1 == F.mId.second && s.n == N) { s.used = S.clock; return s.f; }
+    ThreadState::Slot& s = S.slot[0].used <= S.slot[1].used ? S.slot[0] : S.slot[1];
+    ccm_frame_destroy(s.f);
+    s = ThreadState::Slot();
+    std::vector<float> kx(N), ky(N), angle(N); std::vector<int32_t> oct(N);
+    for (int i = 0; i < N; i++) { kx[i] = F.mvKeysUn[i].pt.x; ky[i] = F.mvKeysUn[i].pt.y; oct[i] = F.mvKeysUn[i].octave; angle[i] = F.mvKeysUn[i].angle; }
+    const auto desc = F.mDescriptors.isContinuous() ? F.mDescriptors : F.mDescriptors.clone();
+    const ccm_frame_grid g{N, kx.data(), ky.data(), oct.data(), desc.data, FrameT::mnMinX, FrameT::mnMinY, FrameT::mfGridElementWidthInv,
+                           FrameT::mfGridElementHeightInv, FRAME_GRID_COLS, FRAME_GRID_ROWS};
+    ccm_frame* f = nullptr;
+    if (ccm_frame_create(S.c, &g, angle.data(), &f)) return nullptr;
+    s.id0 = F.mId.first; s.id1 = F.mId.second; s.n = N; s.f = f; s.used = S.clock;
+    return f;
+}
+#endif
 
 // per-feature vocabulary node of a DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>), -1 = none
 template <class FeatVec>

@@ -89,8 +89,13 @@ int ORBmatcher::SearchByProjection(Frame& F, const std::vector<mpptr>& vpMapPoin
         if (!d.empty()) memcpy(&mp_desc[(size_t)m * 32], d.ptr<uint8_t>(), 32);
     }
     for (int i = 0; i < N; i++) occupied[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;   // :112-114
-    const int n = ccm_search_by_projection(ccm_shim::ctx(), &fg, F.mvScaleFactors.data(), nMP, in_view.data(), level.data(), view_cos.data(),
-                                           px.data(), py.data(), mp_desc.data(), has_obs.data(), occupied.data(), th, mfNNratio, match.data());
+    ccm_frame* h = ccm_shim::frame_handles_on() ? ccm_shim::frame_handle(F) : nullptr;     // the Frame's features stay on the device
+    if (ccm_shim::frame_handles_on() && !h) throw estd::infrastructure_ex();
+    const int n = h ? ccm_frame_search_by_projection(ccm_shim::ctx(), h, F.mvScaleFactors.data(), nMP, in_view.data(), level.data(),
+                                                     view_cos.data(), px.data(), py.data(), mp_desc.data(), has_obs.data(), nullptr,
+                                                     occupied.data(), th, mfNNratio, match.data())
+                    : ccm_search_by_projection(ccm_shim::ctx(), &fg, F.mvScaleFactors.data(), nMP, in_view.data(), level.data(), view_cos.data(),
+                                               px.data(), py.data(), mp_desc.data(), has_obs.data(), occupied.data(), th, mfNNratio, match.data());
     if (n < 0) throw estd::infrastructure_ex();
     for (int i = 0; i < N; i++) if (match[i] >= 0) F.mvpMapPoints[i] = vpMapPoints[match[i]];
     return n;
@@ -256,10 +261,20 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
         copy_desc(pMP, &desc[(size_t)i * 32]);
     }
     for (int i = 0; i < N; i++) occupied[i] = CurrentFrame.mvpMapPoints[i] && CurrentFrame.mvpMapPoints[i]->Observations() > 0;   // :1419-1421
-    const FrGrid G(CurrentFrame);
-    const int n = ccm_search_by_projection_frame(ccm_shim::ctx(), &G.g, G.angle.data(), CurrentFrame.mvScaleFactors.data(), nLast, valid.data(), u.data(),
-                                                 v.data(), last_oct.data(), last_angle.data(), desc.data(), has_obs.data(), occupied.data(), th,
+    int n;
+    if (ccm_shim::frame_handles_on()) {                  // both Frames from the thread's cache: the last one was the current one a call ago
+        ccm_frame* last = ccm_shim::frame_handle(LastFrame);
+        ccm_frame* cur = ccm_shim::frame_handle(CurrentFrame);
+        if (!cur || !last) throw estd::infrastructure_ex();
+        n = ccm_frame_search_by_projection_frame(ccm_shim::ctx(), cur, last, CurrentFrame.mvScaleFactors.data(), nLast, valid.data(), u.data(),
+                                                 v.data(), nullptr, nullptr, desc.data(), has_obs.data(), nullptr, occupied.data(), th,
                                                  mbCheckOrientation ? 1 : 0, TH_HIGH, match.data());
+    } else {
+        const FrGrid G(CurrentFrame);
+        n = ccm_search_by_projection_frame(ccm_shim::ctx(), &G.g, G.angle.data(), CurrentFrame.mvScaleFactors.data(), nLast, valid.data(), u.data(),
+                                           v.data(), last_oct.data(), last_angle.data(), desc.data(), has_obs.data(), occupied.data(), th,
+                                           mbCheckOrientation ? 1 : 0, TH_HIGH, match.data());
+    }
     if (n < 0) throw estd::infrastructure_ex();
     for (int i2 = 0; i2 < N; i2++) if (match[i2] >= 0) CurrentFrame.mvpMapPoints[i2] = LastFrame.mvpMapPoints[match[i2]];
     return n;
@@ -294,10 +309,19 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, kfptr pKF, const std::se
         copy_desc(pMP, &desc[(size_t)i * 32]);
     }
     for (int i = 0; i < N; i++) occupied[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;                 // :1547
-    const FrGrid G(CurrentFrame);
-    const int n = ccm_search_by_projection_frame(ccm_shim::ctx(), &G.g, G.angle.data(), CurrentFrame.mvScaleFactors.data(), nKF, valid.data(), u.data(),
-                                                 v.data(), level.data(), kf_angle.data(), desc.data(), has_obs.data(), occupied.data(), th,
+    int n;
+    if (ccm_shim::frame_handles_on()) {                  // the keyframe side as arrays (last = NULL), the Frame from the cache
+        ccm_frame* cur = ccm_shim::frame_handle(CurrentFrame);
+        if (!cur) throw estd::infrastructure_ex();
+        n = ccm_frame_search_by_projection_frame(ccm_shim::ctx(), cur, nullptr, CurrentFrame.mvScaleFactors.data(), nKF, valid.data(), u.data(),
+                                                 v.data(), level.data(), kf_angle.data(), desc.data(), has_obs.data(), nullptr, occupied.data(), th,
                                                  mbCheckOrientation ? 1 : 0, ORBdist, match.data());
+    } else {
+        const FrGrid G(CurrentFrame);
+        n = ccm_search_by_projection_frame(ccm_shim::ctx(), &G.g, G.angle.data(), CurrentFrame.mvScaleFactors.data(), nKF, valid.data(), u.data(),
+                                           v.data(), level.data(), kf_angle.data(), desc.data(), has_obs.data(), occupied.data(), th,
+                                           mbCheckOrientation ? 1 : 0, ORBdist, match.data());
+    }
     if (n < 0) throw estd::infrastructure_ex();
     for (int i2 = 0; i2 < N; i2++) if (match[i2] >= 0) CurrentFrame.mvpMapPoints[i2] = vpMPs[match[i2]];
     return n;
