@@ -119,14 +119,6 @@ void ba_state_free(BaState* s)
     if (s->ev_chi) (void)hipEventDestroy(s->ev_chi);
     for (hipEvent_t e : s->clock_ev) (void)hipEventDestroy(e);
     if (s->pinned) (void)hipHostFree(s->pinned);
-    DevBuf* all[] = { &s->poses, &s->Rt, &s->intr, &s->free_of, &s->pose_of_free, &s->points, &s->edge_pose, &s->edge_point,
-                      &s->obs, &s->info, &s->active, &s->err, &s->pt_first, &s->pose_first, &s->pose_edges, &s->Hpp, &s->bp, &s->Hpp2, &s->bp2,
-                      &s->Hll, &s->bl, &s->Hpl, &s->Dinv, &s->Hs, &s->bs, &s->x, &s->save_poses, &s->save_points,
-                      &s->partial, &s->scal, &s->flags, &s->info_dev, &s->tmp_ll, &s->pp_diag, &s->gather,
-                      &s->sp_cnt, &s->sp_off, &s->sp_key, &s->sp_val, &s->sp_key2, &s->sp_val2, &s->sp_map, &s->sp_id, &s->sp_tmp, &s->blk_row,
-                      &s->blk_col, &s->diag_id, &s->seg_start, &s->seg_end, &s->ent_key, &s->ent_val, &s->ent_key2, &s->ent_val2, &s->row_ptr,
-                      &s->Hb, &s->Y, &s->db, &s->Minv, &s->pcg_w, &s->pcg_pap, &s->pcg_part, &s->pcg_sc, &s->pcg_aci, &s->pcg_coarse, &s->pcg_acw, &s->pcg_svec, &s->pcg_hf, &s->pcg_ecol, &s->pcg_ca, &s->pcg_aggmap, &s->pcg_pairs, &s->ce };
-    for (DevBuf* b : all) b->release();
     delete s;
 }
 
@@ -192,14 +184,9 @@ int ccm_ba_landmark_cuts(const int32_t* edge_point, int n_edges, int n_points, i
 }
 
 static int ba_solve_impl(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res);
-// No C++ exception may cross the C ABI (std::terminate would take the host process -- a SLAM server -- down): allocation failures of
-// the host-side index vectors and anything else thrown below come back as status codes.
 int ccm_ba_solve(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res)
 {
-    try { return ba_solve_impl(c, pb, opt, res); }
-    catch (const std::bad_alloc&) { return c ? ccm_fail(c, CCM_E_NOMEM, "ccm_ba_solve: host allocation failed") : CCM_E_NOMEM; }
-    catch (const std::exception& e) { return c ? ccm_fail(c, CCM_E_DEVICE, "ccm_ba_solve: %s", e.what()) : CCM_E_DEVICE; }
-    catch (...) { return c ? ccm_fail(c, CCM_E_DEVICE, "ccm_ba_solve: unknown exception") : CCM_E_DEVICE; }
+    return ccm_guard(c, "ccm_ba_solve", [&] { return ba_solve_impl(c, pb, opt, res); });
 }
 
 static int ba_solve_impl(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res)

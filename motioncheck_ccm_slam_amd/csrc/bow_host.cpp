@@ -24,53 +24,48 @@ extern "C" {
 int ccm_voc_create(ccm_ctx* c, int k, int L, int n_nodes, const int32_t* parent, const uint8_t* descriptors, const double* weights,
                    ccm_vocabulary** out)
 {
-    if (!c || !out) return CCM_E_ARG;
-    *out = nullptr;
-    if (n_nodes < 1 || !parent || !descriptors || !weights || L < 0) return ccm_fail(c, CCM_E_ARG, "bad vocabulary arguments");
-    for (int i = 1; i < n_nodes; i++)
-        if (parent[i] < 0 || parent[i] >= i) return ccm_fail(c, CCM_E_ARG, "vocabulary node %d: parent %d must precede it", i, parent[i]);
-    CCM_HIP(c, hipSetDevice(c->device));
-    // children side by side, in the order loadFromTextFile appends them (TemplatedVocabulary.h:1385-1392)
-    std::vector<int> cnt(n_nodes, 0), first(n_nodes + 1, 0), fill(n_nodes, 0), slot_node(std::max(n_nodes - 1, 1)), word(n_nodes, 0), depth(n_nodes, 0);
-    for (int i = 1; i < n_nodes; i++) cnt[parent[i]]++;
-    for (int i = 0; i < n_nodes; i++) first[i + 1] = first[i] + cnt[i];
-    std::vector<uint8_t> slot_desc((size_t)std::max(n_nodes - 1, 1) * 32);
-    int max_depth = 0;
-    for (int i = 1; i < n_nodes; i++) {
-        const int s = first[parent[i]] + fill[parent[i]]++;
-        slot_node[s] = i;
-        std::memcpy(&slot_desc[(size_t)s * 32], descriptors + (size_t)i * 32, 32);
-        depth[i] = depth[parent[i]] + 1;
-        max_depth = std::max(max_depth, depth[i]);
-    }
-    int nw = 0;
-    for (int i = 1; i < n_nodes; i++) if (cnt[i] == 0) word[i] = nw++;            // words numbered in node order (:1408-1414)
-    ccm_vocabulary* v = new ccm_vocabulary();
-    v->ctx = c; v->k = k; v->L = L; v->n = n_nodes; v->n_words = nw; v->depth = max_depth;
-    v->weight.assign(weights, weights + n_nodes);
-    struct Up { DevBuf* b; const void* src; size_t bytes; } ups[] = {
-        { &v->node_first, first.data(), (size_t)n_nodes * 4 }, { &v->node_count, cnt.data(), (size_t)n_nodes * 4 },
-        { &v->slot_desc, slot_desc.data(), slot_desc.size() }, { &v->slot_node, slot_node.data(), slot_node.size() * 4 },
-        { &v->node_word, word.data(), (size_t)n_nodes * 4 } };
-    for (auto& u : ups) {
-        if (u.b->reserve(u.bytes) || hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-            ccm_voc_destroy(v);
-            return ccm_fail(c, CCM_E_DEVICE, "vocabulary upload failed");
+    return ccm_guard(c, "ccm_voc_create", [&]() -> int {
+        if (!c || !out) return CCM_E_ARG;
+        *out = nullptr;
+        if (n_nodes < 1 || !parent || !descriptors || !weights || L < 0) return ccm_fail(c, CCM_E_ARG, "bad vocabulary arguments");
+        for (int i = 1; i < n_nodes; i++)
+            if (parent[i] < 0 || parent[i] >= i) return ccm_fail(c, CCM_E_ARG, "vocabulary node %d: parent %d must precede it", i, parent[i]);
+        CCM_HIP(c, hipSetDevice(c->device));
+        // children side by side, in the order loadFromTextFile appends them (TemplatedVocabulary.h:1385-1392)
+        std::vector<int> cnt(n_nodes, 0), first(n_nodes + 1, 0), fill(n_nodes, 0), slot_node(std::max(n_nodes - 1, 1)), word(n_nodes, 0), depth(n_nodes, 0);
+        for (int i = 1; i < n_nodes; i++) cnt[parent[i]]++;
+        for (int i = 0; i < n_nodes; i++) first[i + 1] = first[i] + cnt[i];
+        std::vector<uint8_t> slot_desc((size_t)std::max(n_nodes - 1, 1) * 32);
+        int max_depth = 0;
+        for (int i = 1; i < n_nodes; i++) {
+            const int s = first[parent[i]] + fill[parent[i]]++;
+            slot_node[s] = i;
+            std::memcpy(&slot_desc[(size_t)s * 32], descriptors + (size_t)i * 32, 32);
+            depth[i] = depth[parent[i]] + 1;
+            max_depth = std::max(max_depth, depth[i]);
         }
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) { ccm_voc_destroy(v); return ccm_fail(c, CCM_E_DEVICE, "vocabulary upload failed"); }
-    *out = v;
-    return CCM_OK;
+        int nw = 0;
+        for (int i = 1; i < n_nodes; i++) if (cnt[i] == 0) word[i] = nw++;            // words numbered in node order (:1408-1414)
+        ccm_vocabulary* v = new ccm_vocabulary();
+        v->ctx = c; v->k = k; v->L = L; v->n = n_nodes; v->n_words = nw; v->depth = max_depth;
+        v->weight.assign(weights, weights + n_nodes);
+        struct Up { DevBuf* b; const void* src; size_t bytes; } ups[] = {
+            { &v->node_first, first.data(), (size_t)n_nodes * 4 }, { &v->node_count, cnt.data(), (size_t)n_nodes * 4 },
+            { &v->slot_desc, slot_desc.data(), slot_desc.size() }, { &v->slot_node, slot_node.data(), slot_node.size() * 4 },
+            { &v->node_word, word.data(), (size_t)n_nodes * 4 } };
+        for (auto& u : ups) {
+            if (u.b->reserve(u.bytes) || hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+                ccm_voc_destroy(v);
+                return ccm_fail(c, CCM_E_DEVICE, "vocabulary upload failed");
+            }
+        }
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { ccm_voc_destroy(v); return ccm_fail(c, CCM_E_DEVICE, "vocabulary upload failed"); }
+        *out = v;
+        return CCM_OK;
+    });
 }
 
-void ccm_voc_destroy(ccm_vocabulary* v)
-{
-    if (!v) return;
-    DevBuf* all[] = { &v->node_first, &v->node_count, &v->slot_desc, &v->slot_node, &v->node_word, &v->feat, &v->word, &v->leaf, &v->nid,
-                      &v->dd, &v->dfirst, &v->dcount, &v->dbest };
-    for (DevBuf* b : all) b->release();
-    delete v;
-}
+void ccm_voc_destroy(ccm_vocabulary* v) { delete v; }
 
 int ccm_voc_words(const ccm_vocabulary* v) { return v ? v->n_words : 0; }
 
@@ -79,24 +74,26 @@ int ccm_voc_transform_dev(ccm_vocabulary* v, const uint8_t* features_dev, int n,
 {
     if (!v) return CCM_E_ARG;
     ccm_ctx* c = v->ctx;
-    if (n < 0 || (n > 0 && (!features_dev || !word_id || !weight || !node_id))) return ccm_fail(c, CCM_E_ARG, "bad transform arguments");
-    if (n == 0) return CCM_OK;
-    if (v->n_words == 0) {                                                        // empty(): transform() returns nothing (:1133)
-        for (int i = 0; i < n; i++) { word_id[i] = 0; weight[i] = 0; node_id[i] = 0; }
+    return ccm_guard(c, "ccm_voc_transform_dev", [&]() -> int {
+        if (n < 0 || (n > 0 && (!features_dev || !word_id || !weight || !node_id))) return ccm_fail(c, CCM_E_ARG, "bad transform arguments");
+        if (n == 0) return CCM_OK;
+        if (v->n_words == 0) {                                                        // empty(): transform() returns nothing (:1133)
+            for (int i = 0; i < n; i++) { word_id[i] = 0; weight[i] = 0; node_id[i] = 0; }
+            return CCM_OK;
+        }
+        CCM_HIP(c, hipSetDevice(c->device));
+        CCM_RESERVE(c, v->word, (size_t)n * 4); CCM_RESERVE(c, v->leaf, (size_t)n * 4); CCM_RESERVE(c, v->nid, (size_t)n * 4);
+        bow_launch_transform(c->stream, features_dev, n, v->node_first.as<int>(), v->node_count.as<int>(), v->slot_desc.as<uint8_t>(),
+                             v->slot_node.as<int>(), v->node_word.as<int>(), v->L - levelsup, v->depth, v->word.as<int>(), v->leaf.as<int>(), v->nid.as<int>());
+        CCM_HIP(c, hipGetLastError());
+        std::vector<int32_t> leaf(n);
+        CCM_HIP(c, hipMemcpyAsync(word_id, v->word.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipMemcpyAsync(leaf.data(), v->leaf.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipMemcpyAsync(node_id, v->nid.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipStreamSynchronize(c->stream));
+        for (int i = 0; i < n; i++) weight[i] = v->weight[leaf[i]];                   // m_nodes[final_id].weight (:1257)
         return CCM_OK;
-    }
-    CCM_HIP(c, hipSetDevice(c->device));
-    CCM_RESERVE(c, v->word, (size_t)n * 4); CCM_RESERVE(c, v->leaf, (size_t)n * 4); CCM_RESERVE(c, v->nid, (size_t)n * 4);
-    bow_launch_transform(c->stream, features_dev, n, v->node_first.as<int>(), v->node_count.as<int>(), v->slot_desc.as<uint8_t>(),
-                         v->slot_node.as<int>(), v->node_word.as<int>(), v->L - levelsup, v->depth, v->word.as<int>(), v->leaf.as<int>(), v->nid.as<int>());
-    CCM_HIP(c, hipGetLastError());
-    std::vector<int32_t> leaf(n);
-    CCM_HIP(c, hipMemcpyAsync(word_id, v->word.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    CCM_HIP(c, hipMemcpyAsync(leaf.data(), v->leaf.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    CCM_HIP(c, hipMemcpyAsync(node_id, v->nid.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    CCM_HIP(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; i++) weight[i] = v->weight[leaf[i]];                   // m_nodes[final_id].weight (:1257)
-    return CCM_OK;
+    });
 }
 
 int ccm_voc_transform(ccm_vocabulary* v, const uint8_t* features, int n, int levelsup, int32_t* word_id, double* weight, int32_t* node_id)

@@ -2,11 +2,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <roctracer/roctx.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <new>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/ccm_hot.h"
 
@@ -44,10 +48,15 @@ struct ccm_ctx {
     FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_host.cpp)
 };
 
-// grow-only device buffer
+// grow-only device buffer; it owns its memory (freed with it), so it can be moved but not copied
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { release(); }
     int reserve(size_t bytes) {
         if (bytes <= cap) return 0;
         if (p) (void)hipFree(p);
@@ -78,6 +87,25 @@ hipStream_t ccm_aux_stream(ccm_ctx* c, int which);      // nullptr if it cannot 
             return ccm_fail((c), CCM_E_NOMEM, "%s:%d device alloc of %zu bytes failed",   \
                             __FILE__, __LINE__, (size_t)(bytes));                         \
     } while (0)
+
+// b holds at least max(bytes, 16) bytes, and the bytes from src are queued for upload on st.
+inline int ccm_upload(ccm_ctx* c, DevBuf& b, const void* src, size_t bytes, hipStream_t st)
+{
+    CCM_RESERVE(c, b, std::max<size_t>(bytes, 16));
+    if (bytes) CCM_HIP(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+    return CCM_OK;
+}
+
+// Runs body() for an entry point of the C ABI.  No C++ exception may cross the C ABI (std::terminate would take the host process --
+// a SLAM server -- down): a failed host allocation (vectors sized by the caller's counts, states created on first use) and anything
+// else thrown comes back as a status code.
+template <class F> int ccm_guard(ccm_ctx* c, const char* name, F&& body) noexcept
+{
+    try { return body(); }
+    catch (const std::bad_alloc&) { return c ? ccm_fail(c, CCM_E_NOMEM, "%s: host allocation failed", name) : CCM_E_NOMEM; }
+    catch (const std::exception& e) { return c ? ccm_fail(c, CCM_E_DEVICE, "%s: %s", name, e.what()) : CCM_E_DEVICE; }
+    catch (...) { return c ? ccm_fail(c, CCM_E_DEVICE, "%s: unknown exception", name) : CCM_E_DEVICE; }
+}
 
 // Brackets the launches issued while it is alive with two events when profiling is on.
 struct ProfScope {

@@ -29,32 +29,36 @@ int ccm_comm_unique_id(uint8_t id[CCM_COMM_ID_BYTES])
 
 int ccm_comm_init(ccm_ctx* c, const uint8_t id[CCM_COMM_ID_BYTES], int n_ranks, int rank)
 {
-    if (!c || !id || n_ranks < 1 || rank < 0 || rank >= n_ranks) return c ? ccm_fail(c, CCM_E_ARG, "bad communicator arguments") : CCM_E_ARG;
-    CCM_HIP(c, hipSetDevice(c->device));
-    comm_state_free(c);
-    c->comm = new CommState();
-    c->comm->n_ranks = n_ranks; c->comm->rank = rank;
-    // A one-rank job needs no communicator.  CCM_COMM_RCCL_SINGLE=1 creates one all the same, so that the RCCL
-    // calls of the sharded path (ncclCommInitRank, in-place ncclAllReduce on the context's stream) can be run on a
-    // machine with one GPU (tests/test_ba_gpu.py).
-    const char* single = getenv("CCM_COMM_RCCL_SINGLE");
-    if (n_ranks == 1 && !(single && single[0] == '1')) return CCM_OK;
-    ncclUniqueId u;
-    std::memcpy(&u, id, sizeof u);
-    ncclResult_t r = ncclCommInitRank(&c->comm->comm, n_ranks, u, rank);
-    if (r != ncclSuccess) { c->comm->comm = nullptr; return ccm_fail(c, CCM_E_COMM, "ncclCommInitRank: %s", ncclGetErrorString(r)); }
-    return CCM_OK;
+    return ccm_guard(c, "ccm_comm_init", [&]() -> int {
+        if (!c || !id || n_ranks < 1 || rank < 0 || rank >= n_ranks) return c ? ccm_fail(c, CCM_E_ARG, "bad communicator arguments") : CCM_E_ARG;
+        CCM_HIP(c, hipSetDevice(c->device));
+        comm_state_free(c);
+        c->comm = new CommState();
+        c->comm->n_ranks = n_ranks; c->comm->rank = rank;
+        // A one-rank job needs no communicator.  CCM_COMM_RCCL_SINGLE=1 creates one all the same, so that the RCCL
+        // calls of the sharded path (ncclCommInitRank, in-place ncclAllReduce on the context's stream) can be run on a
+        // machine with one GPU (tests/test_ba_gpu.py).
+        const char* single = getenv("CCM_COMM_RCCL_SINGLE");
+        if (n_ranks == 1 && !(single && single[0] == '1')) return CCM_OK;
+        ncclUniqueId u;
+        std::memcpy(&u, id, sizeof u);
+        ncclResult_t r = ncclCommInitRank(&c->comm->comm, n_ranks, u, rank);
+        if (r != ncclSuccess) { c->comm->comm = nullptr; return ccm_fail(c, CCM_E_COMM, "ncclCommInitRank: %s", ncclGetErrorString(r)); }
+        return CCM_OK;
+    });
 }
 
 int ccm_comm_attach(ccm_ctx* c, const ccm_comm_transport* t, int n_ranks, int rank)
 {
-    if (!c || !t || !t->allreduce_f64 || !t->allreduce_u8_max || n_ranks < 1 || rank < 0 || rank >= n_ranks)
-        return c ? ccm_fail(c, CCM_E_ARG, "bad transport arguments") : CCM_E_ARG;
-    comm_state_free(c);
-    c->comm = new CommState();
-    c->comm->n_ranks = n_ranks; c->comm->rank = rank;
-    c->comm->has_ext = true; c->comm->ext = *t;
-    return CCM_OK;
+    return ccm_guard(c, "ccm_comm_attach", [&]() -> int {
+        if (!c || !t || !t->allreduce_f64 || !t->allreduce_u8_max || n_ranks < 1 || rank < 0 || rank >= n_ranks)
+            return c ? ccm_fail(c, CCM_E_ARG, "bad transport arguments") : CCM_E_ARG;
+        comm_state_free(c);
+        c->comm = new CommState();
+        c->comm->n_ranks = n_ranks; c->comm->rank = rank;
+        c->comm->has_ext = true; c->comm->ext = *t;
+        return CCM_OK;
+    });
 }
 
 int ccm_comm_destroy(ccm_ctx* c)

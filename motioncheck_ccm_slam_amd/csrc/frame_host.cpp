@@ -86,12 +86,10 @@ void frame_state_free(ccm_ctx* c)
     FrameState* S = c->frame;
     if (!S) return;
     for (ccm_frame* f : S->live) {               // frames the caller did not destroy: memory goes, the handle stays (ccm_frame_destroy)
-        if (f->mem) { f->mem->buf.release(); delete f->mem; }
+        delete f->mem;
         *f = ccm_frame();
     }
-    for (FrameMem* m : S->pool) { m->buf.release(); delete m; }
-    DevBuf* all[] = { &S->io, &S->ci, &S->cd, &S->cn, &S->ev, &S->pts, &S->obs, &S->info, &S->err, &S->outl, &S->kof, &S->first };
-    for (DevBuf* b : all) b->release();
+    for (FrameMem* m : S->pool) delete m;
     if (S->host) (void)hipHostFree(S->host);
     if (S->host_free) (void)hipEventDestroy(S->host_free);
     delete S;
@@ -325,12 +323,6 @@ static int check_frame(ccm_ctx* c, const ccm_frame* f)
     return CCM_OK;
 }
 
-#define CCM_FRAME_GUARD(c, name, ...)                                                                                            \
-    try { __VA_ARGS__ }                                                                                                           \
-    catch (const std::bad_alloc&) { return (c) ? ccm_fail((c), CCM_E_NOMEM, name ": host allocation failed") : CCM_E_NOMEM; }   \
-    catch (const std::exception& e) { return (c) ? ccm_fail((c), CCM_E_DEVICE, name ": %s", e.what()) : CCM_E_DEVICE; }         \
-    catch (...) { return (c) ? ccm_fail((c), CCM_E_DEVICE, name ": unknown exception") : CCM_E_DEVICE; }
-
 extern "C" {
 
 int ccm_frame_create(ccm_ctx* c, const ccm_frame_grid* g, const float* angle, ccm_frame** out)
@@ -340,7 +332,7 @@ int ccm_frame_create(ccm_ctx* c, const ccm_frame_grid* g, const float* angle, cc
     if (!c || !g || !out) return CCM_E_ARG;
     if (g->n < 0 || !grid_ok(g->grid_cols, g->grid_rows) || (g->n > 0 && (!g->kp_x || !g->kp_y || !g->kp_octave || !g->desc)))
         return ccm_fail(c, CCM_E_ARG, "bad frame arguments (grid of at most 16384 cells)");
-    CCM_FRAME_GUARD(c, "ccm_frame_create", {
+    return ccm_guard(c, "ccm_frame_create", [&]() -> int {
         int max_oct = -1;
         for (int i = 0; i < g->n; i++) {
             if (g->kp_octave[i] < 0 || g->kp_octave[i] > 255) return ccm_fail(c, CCM_E_ARG, "octave of feature %d out of [0, 255]", i);
@@ -364,7 +356,7 @@ int ccm_frame_create(ccm_ctx* c, const ccm_frame_grid* g, const float* angle, cc
         if ((rc = upload(c, 0, L.upload_end, f->mem->buf.p)) || (rc = frame_build(c, f, nullptr, nullptr, 0))) { frame_release(f); return rc; }
         *out = f;
         return CCM_OK;
-    })
+    });
 }
 
 int ccm_frame_from_extract(ccm_ctx* c, int image, int n, const float* kp_x_un, const float* kp_y_un, float min_x, float min_y,
@@ -375,7 +367,7 @@ int ccm_frame_from_extract(ccm_ctx* c, int image, int n, const float* kp_x_un, c
     if (!c || !out) return CCM_E_ARG;
     if (!grid_ok(grid_cols, grid_rows) || (!kp_x_un) != (!kp_y_un) || n < -1)
         return ccm_fail(c, CCM_E_ARG, "bad frame arguments (grid of at most 16384 cells, both or neither coordinate array)");
-    CCM_FRAME_GUARD(c, "ccm_frame_from_extract", {
+    return ccm_guard(c, "ccm_frame_from_extract", [&]() -> int {
         const ccm_keypoint* kps = nullptr; const uint8_t* desc = nullptr; const int32_t* counts = nullptr;
         int n_images = 0, max_per_image = 0, nlevels = 0;
         int rc = orb_last_result(c, &kps, &desc, &counts, &n_images, &max_per_image, &nlevels);
@@ -404,7 +396,7 @@ int ccm_frame_from_extract(ccm_ctx* c, int image, int n, const float* kp_x_un, c
         }
         *out = f;
         return CCM_OK;
-    })
+    });
 }
 
 void ccm_frame_destroy(ccm_frame* f)
@@ -421,7 +413,7 @@ int ccm_frame_set_map_points(ccm_frame* f, const int32_t* mp_id)
     ccm_ctx* c = f->ctx;
     if (!c) return CCM_E_STATE;
     if (f->n == 0) return CCM_OK;
-    CCM_FRAME_GUARD(c, "ccm_frame_set_map_points", {
+    return ccm_guard(c, "ccm_frame_set_map_points", [&]() -> int {
         CCM_HIP(c, hipSetDevice(c->device));
         if (!mp_id) { CCM_HIP(c, hipMemsetAsync(f->mp_id, 0xFF, (size_t)f->n * 4, c->stream)); return CCM_OK; }
         uint8_t* h = nullptr;
@@ -429,7 +421,7 @@ int ccm_frame_set_map_points(ccm_frame* f, const int32_t* mp_id)
         if (rc) return rc;
         std::memcpy(h, mp_id, (size_t)f->n * 4);
         return upload(c, 0, (size_t)f->n * 4, f->mp_id);
-    })
+    });
 }
 
 int ccm_frame_get_map_points(ccm_frame* f, int32_t* mp_id)
@@ -469,21 +461,13 @@ int ccm_frame_search_by_projection(ccm_ctx* c, ccm_frame* f, const float* scale_
         return ccm_fail(c, CCM_E_ARG, "bad SearchByProjection arguments");
     for (int i = 0; i < f->n; i++) match[i] = -1;
     if (n_mp == 0 || f->n == 0) return 0;
-    CCM_FRAME_GUARD(c, "ccm_frame_search_by_projection", {
+    return ccm_guard(c, "ccm_frame_search_by_projection", [&]() -> int {
         CCM_HIP(c, hipSetDevice(c->device));
-        const bool bFactor = th != 1.0;                                            // as match_host.cpp
-        std::vector<float> qr(n_mp); std::vector<int32_t> minl(n_mp), maxl(n_mp);
-        for (int m = 0; m < n_mp; m++) {
-            if (!in_view[m]) { qr[m] = -1.f; minl[m] = 0; maxl[m] = 0; continue; }
-            float r = view_cos[m] > 0.998 ? 2.5f : 4.0f;                          // RadiusByViewingCos :150-156
-            if (bFactor) r *= th;
-            qr[m] = r * scale_factors[level[m]];
-            minl[m] = level[m] - 1; maxl[m] = level[m];
-        }
-        WinCall w{ 0, n_mp, proj_x, proj_y, qr.data(), minl.data(), maxl.data(), mp_desc, in_view, mp_has_obs, query_mp_id,
+        const WinQueries q = window_queries_projection(n_mp, in_view, level, view_cos, scale_factors, th);
+        WinCall w{ 0, n_mp, proj_x, proj_y, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, in_view, mp_has_obs, query_mp_id,
                    nullptr, nullptr, 0.f, nullptr, nnratio, 0, 0 };
         return frame_window(c, f, w, occupied, match);
-    })
+    });
 }
 
 // ORBmatcher::SearchByProjection(Frame& Current, const Frame& Last, th), ORBmatcher.cpp:1350-1476, and the relocalisation
@@ -506,21 +490,14 @@ int ccm_frame_search_by_projection_frame(ccm_ctx* c, ccm_frame* cur, const ccm_f
         return ccm_fail(c, CCM_E_ARG, "bad SearchByProjection(frame, frame) arguments");
     for (int i = 0; i < cur->n; i++) match[i] = -1;
     if (n_last == 0 || cur->n == 0) return 0;
-    CCM_FRAME_GUARD(c, "ccm_frame_search_by_projection_frame", {
+    return ccm_guard(c, "ccm_frame_search_by_projection_frame", [&]() -> int {
         CCM_HIP(c, hipSetDevice(c->device));
-        std::vector<float> qr; std::vector<int32_t> minl, maxl;
-        if (!last) {
-            qr.resize(n_last); minl.resize(n_last); maxl.resize(n_last);
-            for (int i = 0; i < n_last; i++) {
-                if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = 0; continue; }
-                qr[i] = th * scale_factors[last_octave[i]];                       // :1401
-                minl[i] = last_octave[i] - 1; maxl[i] = last_octave[i] + 1;       // :1405
-            }
-        }
-        WinCall w{ 2, n_last, u, v, last ? nullptr : qr.data(), last ? nullptr : minl.data(), last ? nullptr : maxl.data(), mp_desc, valid,
+        WinQueries q;                                                          // a `last` handle: set up on the device
+        if (!last) q = window_queries_frame(n_last, valid, last_octave, scale_factors, th);
+        WinCall w{ 2, n_last, u, v, last ? nullptr : q.qr.data(), last ? nullptr : q.minl.data(), last ? nullptr : q.maxl.data(), mp_desc, valid,
                    mp_has_obs, query_mp_id, last, scale_factors, th, last_angle, 0.f, orb_dist, check_ori ? 1 : 0 };
         return frame_window(c, cur, w, occupied, match);
-    })
+    });
 }
 
 // Optimizer::PoseOptimizationClient(Frame&), src/Optimizer.cpp:215-347, the frame's correspondences gathered on the device
@@ -534,7 +511,7 @@ int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp
     if (!intr || !pose7 || !n_inliers || n_mp < 0 || (n_mp > 0 && !mp_xyz) || (f->n > 0 && (!outlier || !inv_level_sigma2 || n_levels < 1)))
         return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
     if (f->n == 0) { *n_inliers = 0; return CCM_OK; }
-    CCM_FRAME_GUARD(c, "ccm_frame_pose_optimize", {
+    return ccm_guard(c, "ccm_frame_pose_optimize", [&]() -> int {
         CCM_HIP(c, hipSetDevice(c->device));
         FrameState& S = *frame_state(c);
         hipStream_t st = c->stream;
@@ -571,7 +548,7 @@ int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp
         std::memcpy(outlier, S.host + o_outl, n);
         *n_inliers = head[0];
         return CCM_OK;
-    })
+    });
 }
 
 }  // extern "C"

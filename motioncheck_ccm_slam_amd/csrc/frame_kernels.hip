@@ -18,7 +18,7 @@ struct FrameBuildArgs {                          // must match frame_host.cpp
     float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
 };
 
-// PosInGrid (src/Frame.cpp:255-266) exactly as the host build in match_host.cpp: round() in float, half away from zero; features
+// PosInGrid (src/Frame.cpp:255-266) exactly as grid_build() in match_host.cpp: round() in float, half away from zero; features
 // outside the grid get no cell.  A NaN coordinate gets none either (x86's conversion gives INT_MIN, the device's 0).
 __device__ inline int fb_cell(const FrameBuildArgs& A, float x, float y)
 {
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(FB_TPB) void k_frame_build(FrameBuildArgs A)
 }
 
 // SearchByProjection(Current, Last) query set-up (ORBmatcher.cpp:1401-1405) from the last frame's octaves in HBM: the host
-// computes the same in match_host.cpp (th * scale_factors[octave] in float; levels octave-1 .. octave+1; skipped: r = -1).
+// computes the same in window_queries_frame() (th * scale_factors[octave] in float; levels octave-1 .. octave+1; skipped: r = -1).
 __global__ void k_frame_prep_last(int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

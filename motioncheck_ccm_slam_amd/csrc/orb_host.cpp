@@ -111,9 +111,6 @@ struct OrbState {
 void orb_state_free(OrbState* s)
 {
     if (!s) return;
-    DevBuf* all[] = { &s->geom_dev, &s->cells_dev, &s->tables_dev, &s->bands_dev, &s->pyr, &s->smap, &s->slots, &s->cell_count,
-                      &s->keysA, &s->keysB, &s->sel, &s->sel_count, &s->status, &s->img0, &s->kps, &s->desc, &s->counts };
-    for (DevBuf* b : all) b->release();
     if (s->copy_done) (void)hipEventDestroy(s->copy_done);
     if (s->chunk_done) (void)hipEventDestroy(s->chunk_done);
     delete s;
@@ -405,14 +402,16 @@ int ccm_orb_extract_dev(ccm_ctx* c, const ccm_orb_params* p, const uint8_t* img_
                         size_t image_stride, int n_images, int max_per_image)
 {
     RoctxRange roctx_("ccm_orb_extract_dev");
-    if (!c || !p) return CCM_E_ARG;
-    if (n_images == 0 || w == 0 || h == 0) return CCM_OK;         // empty image: silent return (:1219-1220)
-    if (!img_dev || w < 0 || h < 0 || n_images < 0 || stride < w || (n_images > 1 && image_stride < (size_t)stride * h))
-        return ccm_fail(c, CCM_E_ARG, "bad image arguments");
-    CCM_HIP(c, hipSetDevice(c->device));
-    int rc = orb_prepare(c, p, w, h, n_images, max_per_image);
-    if (rc) return rc;
-    return orb_run(c, img_dev, stride, image_stride);
+    return ccm_guard(c, "ccm_orb_extract_dev", [&]() -> int {
+        if (!c || !p) return CCM_E_ARG;
+        if (n_images == 0 || w == 0 || h == 0) return CCM_OK;         // empty image: silent return (:1219-1220)
+        if (!img_dev || w < 0 || h < 0 || n_images < 0 || stride < w || (n_images > 1 && image_stride < (size_t)stride * h))
+            return ccm_fail(c, CCM_E_ARG, "bad image arguments");
+        CCM_HIP(c, hipSetDevice(c->device));
+        int rc = orb_prepare(c, p, w, h, n_images, max_per_image);
+        if (rc) return rc;
+        return orb_run(c, img_dev, stride, image_stride);
+    });
 }
 
 int ccm_orb_fetch(ccm_ctx* c, ccm_keypoint* kps, uint8_t* desc, int32_t* counts)
@@ -434,81 +433,83 @@ int ccm_orb_extract(ccm_ctx* c, const ccm_orb_params* p, const uint8_t* img, int
                     int max_per_image)
 {
     RoctxRange roctx_("ccm_orb_extract");
-    if (!c || !p) return CCM_E_ARG;
-    if (n_images == 0 || w == 0 || h == 0) return CCM_OK;
-    if (!img || w < 0 || h < 0 || n_images < 0 || stride < w) return ccm_fail(c, CCM_E_ARG, "bad image arguments");
-    CCM_HIP(c, hipSetDevice(c->device));
-    if (!c->orb) c->orb = new OrbState();
-    OrbState& S = *c->orb;
-    // Device layout of level 0: rows padded to 64 bytes (a strided 2-D copy), or -- when the caller's rows are 16-byte multiples, which
-    // is all the kernels' wide loads need -- the caller's own layout, so that a chunk of frames goes up as ONE linear copy.
-    // Only for batches that go up in chunks behind the extraction: a single 752 x 480 frame is extracted 26 us faster from 64-byte
-    // aligned rows (0.214 against 0.240 ms per call), which a batch hides behind its uploads.
-    static const bool force_2d = getenv("CCM_ORB_UPLOAD_2D") && atoi(getenv("CCM_ORB_UPLOAD_2D")) != 0;
-    static const int chunk_frames = getenv("CCM_ORB_CHUNK") ? std::max(1, atoi(getenv("CCM_ORB_CHUNK"))) : 64;
-    const int n_chunks = n_images >= 2 * chunk_frames ? (n_images + chunk_frames - 1) / chunk_frames : 1;
-    const bool linear = !force_2d && n_chunks > 1 && stride % 16 == 0 && image_stride % 16 == 0 && image_stride >= (size_t)stride * h;
-    const int pitch = linear ? stride : (int)align_up(w, 64);
-    const size_t plane = linear ? image_stride : (size_t)pitch * h;
-    CCM_RESERVE(c, S.img0, plane * n_images + 64);
-    int rc = orb_prepare(c, p, w, h, n_images, max_per_image);
-    if (rc) return rc;
-    // Host buffers: the frames go up in chunks on a copy stream while the previous chunk is being extracted (the
-    // upload is ~2/3 of the whole call for 752x480 frames).  Small batches go up in one piece.
-    if (n_chunks > 1 && !S.copy_stream) {
-        if (!(S.copy_stream = ccm_aux_stream(c, 0))) return ccm_fail(c, CCM_E_DEVICE, "hipStreamCreate failed");      // (the context's, shared)
-        CCM_HIP(c, hipEventCreateWithFlags(&S.copy_done, hipEventDisableTiming));
-    }
-    const bool contiguous = n_images == 1 || image_stride == (size_t)stride * h;
-    // Results: with page-locked destination buffers (hipHostMalloc / ccm_host_register) each chunk's keypoints, descriptors and counts
-    // go down on a stream of their own while the next chunk is extracted -- the two copy directions use different engines.  A copy to
-    // pageable memory holds the calling thread until it is done, which would keep it from enqueueing the next chunk: those go down
-    // in one piece at the end (ccm_orb_fetch), as before.
-    auto page_locked = [](const void* q) {
-        if (!q) return true;
-        hipPointerAttribute_t a{};
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return a.type == hipMemoryTypeHost;
-    };
-    const bool stream_down = n_chunks > 1 && (kps || desc || counts) && page_locked(kps) && page_locked(desc) && page_locked(counts);
-    if (stream_down && !S.down_stream) {
-        if (!(S.down_stream = ccm_aux_stream(c, 1))) return ccm_fail(c, CCM_E_DEVICE, "hipStreamCreate failed");
-        CCM_HIP(c, hipEventCreateWithFlags(&S.chunk_done, hipEventDisableTiming));
-    }
-    for (int ck = 0; ck < n_chunks; ck++) {
-        const int f0 = (int)((long long)n_images * ck / n_chunks), f1 = (int)((long long)n_images * (ck + 1) / n_chunks);
-        hipStream_t up = n_chunks > 1 ? S.copy_stream : c->stream;
-        if (linear) {
-            const size_t bytes = f1 < n_images ? plane * (f1 - f0) : plane * (f1 - 1 - f0) + (size_t)stride * (h - 1) + w;     // (the last image may end with its last pixel)
-            CCM_HIP(c, hipMemcpyAsync(S.img0.as<char>() + plane * f0, img + image_stride * f0, bytes, hipMemcpyHostToDevice, up));
-        } else if (contiguous) {
-            // rows of consecutive images are consecutive in both layouts (device plane == pitch * h)
-            CCM_HIP(c, hipMemcpy2DAsync(S.img0.as<char>() + plane * f0, pitch, img + image_stride * f0, stride, w, (size_t)h * (f1 - f0),
-                                        hipMemcpyHostToDevice, up));
-        } else {
-            for (int i = f0; i < f1; i++)
-                CCM_HIP(c, hipMemcpy2DAsync(S.img0.as<char>() + plane * i, pitch, img + image_stride * i, stride, w, h, hipMemcpyHostToDevice, up));
-        }
-        if (n_chunks > 1) {
-            CCM_HIP(c, hipEventRecord(S.copy_done, up));
-            CCM_HIP(c, hipStreamWaitEvent(c->stream, S.copy_done, 0));
-        }
-        rc = orb_run(c, S.img0.as<uint8_t>(), pitch, plane, f0, f1 - f0);
+    return ccm_guard(c, "ccm_orb_extract", [&]() -> int {
+        if (!c || !p) return CCM_E_ARG;
+        if (n_images == 0 || w == 0 || h == 0) return CCM_OK;
+        if (!img || w < 0 || h < 0 || n_images < 0 || stride < w) return ccm_fail(c, CCM_E_ARG, "bad image arguments");
+        CCM_HIP(c, hipSetDevice(c->device));
+        if (!c->orb) c->orb = new OrbState();
+        OrbState& S = *c->orb;
+        // Device layout of level 0: rows padded to 64 bytes (a strided 2-D copy), or -- when the caller's rows are 16-byte multiples, which
+        // is all the kernels' wide loads need -- the caller's own layout, so that a chunk of frames goes up as ONE linear copy.
+        // Only for batches that go up in chunks behind the extraction: a single 752 x 480 frame is extracted 26 us faster from 64-byte
+        // aligned rows (0.214 against 0.240 ms per call), which a batch hides behind its uploads.
+        static const bool force_2d = getenv("CCM_ORB_UPLOAD_2D") && atoi(getenv("CCM_ORB_UPLOAD_2D")) != 0;
+        static const int chunk_frames = getenv("CCM_ORB_CHUNK") ? std::max(1, atoi(getenv("CCM_ORB_CHUNK"))) : 64;
+        const int n_chunks = n_images >= 2 * chunk_frames ? (n_images + chunk_frames - 1) / chunk_frames : 1;
+        const bool linear = !force_2d && n_chunks > 1 && stride % 16 == 0 && image_stride % 16 == 0 && image_stride >= (size_t)stride * h;
+        const int pitch = linear ? stride : (int)align_up(w, 64);
+        const size_t plane = linear ? image_stride : (size_t)pitch * h;
+        CCM_RESERVE(c, S.img0, plane * n_images + 64);
+        int rc = orb_prepare(c, p, w, h, n_images, max_per_image);
         if (rc) return rc;
-        if (stream_down) {
-            const size_t m = (size_t)S.max_per_image, nf = (size_t)(f1 - f0);
-            CCM_HIP(c, hipEventRecord(S.chunk_done, c->stream));
-            CCM_HIP(c, hipStreamWaitEvent(S.down_stream, S.chunk_done, 0));
-            if (kps) CCM_HIP(c, hipMemcpyAsync(kps + f0 * m, S.kps.as<ccm_keypoint>() + f0 * m, nf * m * sizeof(ccm_keypoint), hipMemcpyDeviceToHost, S.down_stream));
-            if (desc) CCM_HIP(c, hipMemcpyAsync(desc + f0 * m * 32, S.desc.as<uint8_t>() + f0 * m * 32, nf * m * 32, hipMemcpyDeviceToHost, S.down_stream));
-            if (counts) CCM_HIP(c, hipMemcpyAsync(counts + f0, S.counts.as<int32_t>() + f0, nf * 4, hipMemcpyDeviceToHost, S.down_stream));
+        // Host buffers: the frames go up in chunks on a copy stream while the previous chunk is being extracted (the
+        // upload is ~2/3 of the whole call for 752x480 frames).  Small batches go up in one piece.
+        if (n_chunks > 1 && !S.copy_stream) {
+            if (!(S.copy_stream = ccm_aux_stream(c, 0))) return ccm_fail(c, CCM_E_DEVICE, "hipStreamCreate failed");      // (the context's, shared)
+            CCM_HIP(c, hipEventCreateWithFlags(&S.copy_done, hipEventDisableTiming));
         }
-    }
-    if (stream_down) {
-        CCM_HIP(c, hipStreamSynchronize(S.down_stream));
-        return orb_check_status(c);                          // (synchronises the context's stream and reads the kernels' status word)
-    }
-    return ccm_orb_fetch(c, kps, desc, counts);
+        const bool contiguous = n_images == 1 || image_stride == (size_t)stride * h;
+        // Results: with page-locked destination buffers (hipHostMalloc / ccm_host_register) each chunk's keypoints, descriptors and counts
+        // go down on a stream of their own while the next chunk is extracted -- the two copy directions use different engines.  A copy to
+        // pageable memory holds the calling thread until it is done, which would keep it from enqueueing the next chunk: those go down
+        // in one piece at the end (ccm_orb_fetch), as before.
+        auto page_locked = [](const void* q) {
+            if (!q) return true;
+            hipPointerAttribute_t a{};
+            if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }
+            return a.type == hipMemoryTypeHost;
+        };
+        const bool stream_down = n_chunks > 1 && (kps || desc || counts) && page_locked(kps) && page_locked(desc) && page_locked(counts);
+        if (stream_down && !S.down_stream) {
+            if (!(S.down_stream = ccm_aux_stream(c, 1))) return ccm_fail(c, CCM_E_DEVICE, "hipStreamCreate failed");
+            CCM_HIP(c, hipEventCreateWithFlags(&S.chunk_done, hipEventDisableTiming));
+        }
+        for (int ck = 0; ck < n_chunks; ck++) {
+            const int f0 = (int)((long long)n_images * ck / n_chunks), f1 = (int)((long long)n_images * (ck + 1) / n_chunks);
+            hipStream_t up = n_chunks > 1 ? S.copy_stream : c->stream;
+            if (linear) {
+                const size_t bytes = f1 < n_images ? plane * (f1 - f0) : plane * (f1 - 1 - f0) + (size_t)stride * (h - 1) + w;     // (the last image may end with its last pixel)
+                CCM_HIP(c, hipMemcpyAsync(S.img0.as<char>() + plane * f0, img + image_stride * f0, bytes, hipMemcpyHostToDevice, up));
+            } else if (contiguous) {
+                // rows of consecutive images are consecutive in both layouts (device plane == pitch * h)
+                CCM_HIP(c, hipMemcpy2DAsync(S.img0.as<char>() + plane * f0, pitch, img + image_stride * f0, stride, w, (size_t)h * (f1 - f0),
+                                            hipMemcpyHostToDevice, up));
+            } else {
+                for (int i = f0; i < f1; i++)
+                    CCM_HIP(c, hipMemcpy2DAsync(S.img0.as<char>() + plane * i, pitch, img + image_stride * i, stride, w, h, hipMemcpyHostToDevice, up));
+            }
+            if (n_chunks > 1) {
+                CCM_HIP(c, hipEventRecord(S.copy_done, up));
+                CCM_HIP(c, hipStreamWaitEvent(c->stream, S.copy_done, 0));
+            }
+            rc = orb_run(c, S.img0.as<uint8_t>(), pitch, plane, f0, f1 - f0);
+            if (rc) return rc;
+            if (stream_down) {
+                const size_t m = (size_t)S.max_per_image, nf = (size_t)(f1 - f0);
+                CCM_HIP(c, hipEventRecord(S.chunk_done, c->stream));
+                CCM_HIP(c, hipStreamWaitEvent(S.down_stream, S.chunk_done, 0));
+                if (kps) CCM_HIP(c, hipMemcpyAsync(kps + f0 * m, S.kps.as<ccm_keypoint>() + f0 * m, nf * m * sizeof(ccm_keypoint), hipMemcpyDeviceToHost, S.down_stream));
+                if (desc) CCM_HIP(c, hipMemcpyAsync(desc + f0 * m * 32, S.desc.as<uint8_t>() + f0 * m * 32, nf * m * 32, hipMemcpyDeviceToHost, S.down_stream));
+                if (counts) CCM_HIP(c, hipMemcpyAsync(counts + f0, S.counts.as<int32_t>() + f0, nf * 4, hipMemcpyDeviceToHost, S.down_stream));
+            }
+        }
+        if (stream_down) {
+            CCM_HIP(c, hipStreamSynchronize(S.down_stream));
+            return orb_check_status(c);                          // (synchronises the context's stream and reads the kernels' status word)
+        }
+        return ccm_orb_fetch(c, kps, desc, counts);
+    });
 }
 
 int ccm_orb_result_dev(ccm_ctx* c, const uint8_t** desc_dev, const int32_t** counts_dev, int* max_per_image)
@@ -533,26 +534,28 @@ int ccm_orb_debug_level(ccm_ctx* c, int image, int level, uint8_t* out, int out_
 
 int ccm_orb_debug_candidates(ccm_ctx* c, int image, int level, int32_t* xy, int32_t* score, int max)
 {
-    if (!c || !c->orb || !c->orb->have_result) return c ? ccm_fail(c, CCM_E_STATE, "no extraction yet") : CCM_E_ARG;
-    OrbState& S = *c->orb;
-    if (level < 0 || level >= S.geom.nlevels || image < 0 || image >= S.nframes) return ccm_fail(c, CCM_E_ARG, "bad level/image");
-    const OrbLevel& L = S.geom.lv[level];
-    std::vector<int> cnt(std::max(S.geom.ncells, 1));
-    std::vector<unsigned> sl(S.geom.slots_per_frame);
-    CCM_HIP(c, hipMemcpyAsync(cnt.data(), S.cell_count.as<int>() + (size_t)image * S.geom.ncells, (size_t)S.geom.ncells * 4, hipMemcpyDeviceToHost, c->stream));
-    CCM_HIP(c, hipMemcpyAsync(sl.data(), S.slots.as<unsigned>() + (size_t)image * S.geom.slots_per_frame, sl.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    CCM_HIP(c, hipStreamSynchronize(c->stream));
-    int n = 0;
-    for (int ci = L.cell_first; ci < L.cell_first + L.ncells; ci++) {
-        const OrbCell& cell = S.cells[ci];
-        for (int k = 0; k < cnt[ci]; k++, n++) {
-            if (n >= max) continue;
-            const unsigned key = sl[cell.slot_first + k];
-            if (xy) { xy[2 * n] = (int)(key & 0xFFFu); xy[2 * n + 1] = (int)((key >> 12) & 0xFFFu); }
-            if (score) score[n] = (int)(key >> 24);
+    return ccm_guard(c, "ccm_orb_debug_candidates", [&]() -> int {
+        if (!c || !c->orb || !c->orb->have_result) return c ? ccm_fail(c, CCM_E_STATE, "no extraction yet") : CCM_E_ARG;
+        OrbState& S = *c->orb;
+        if (level < 0 || level >= S.geom.nlevels || image < 0 || image >= S.nframes) return ccm_fail(c, CCM_E_ARG, "bad level/image");
+        const OrbLevel& L = S.geom.lv[level];
+        std::vector<int> cnt(std::max(S.geom.ncells, 1));
+        std::vector<unsigned> sl(S.geom.slots_per_frame);
+        CCM_HIP(c, hipMemcpyAsync(cnt.data(), S.cell_count.as<int>() + (size_t)image * S.geom.ncells, (size_t)S.geom.ncells * 4, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipMemcpyAsync(sl.data(), S.slots.as<unsigned>() + (size_t)image * S.geom.slots_per_frame, sl.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipStreamSynchronize(c->stream));
+        int n = 0;
+        for (int ci = L.cell_first; ci < L.cell_first + L.ncells; ci++) {
+            const OrbCell& cell = S.cells[ci];
+            for (int k = 0; k < cnt[ci]; k++, n++) {
+                if (n >= max) continue;
+                const unsigned key = sl[cell.slot_first + k];
+                if (xy) { xy[2 * n] = (int)(key & 0xFFFu); xy[2 * n + 1] = (int)((key >> 12) & 0xFFFu); }
+                if (score) score[n] = (int)(key >> 24);
+            }
         }
-    }
-    return n;
+        return n;
+    });
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 #include <hip/hip_runtime.h>
 
 struct WinGrid {
@@ -36,5 +37,13 @@ int window_accept_projection_host(int n_mp, const uint8_t* in_view, const int32_
 int window_accept_frame_host(int n_last, const uint8_t* valid, const int32_t* ci, const int32_t* cd, const int32_t* cn, int cap,
                              const uint8_t* mp_has_obs, uint8_t* occupied, int orb_dist, int check_ori, const float* last_angle,
                              const float* cur_angle, int32_t* match);
+// Per-query search windows (radius, r < 0 skips the query; octave range) of the host-buffer and the frame-handle entry points.
+struct WinQueries { std::vector<float> qr; std::vector<int32_t> minl, maxl; };
+// SearchByProjection(Frame&, map points), ORBmatcher.cpp:97-107: RadiusByViewingCos (* th unless th == 1) * scale[level], levels
+// level - 1 .. level; map points not in view are skipped
+WinQueries window_queries_projection(int n_mp, const uint8_t* in_view, const int32_t* level, const float* view_cos, const float* scale_factors,
+                                     float th);
+// SearchByProjection(Frame&, Frame | KeyFrame), ORBmatcher.cpp:1401-1405: th * scale[octave], levels octave - 1 .. octave + 1
+WinQueries window_queries_frame(int n_last, const uint8_t* valid, const int32_t* last_octave, const float* scale_factors, float th);
 // true when CCM_WINDOW_HOST_ACCEPT=1 (test switch)
 bool window_host_accept_forced();

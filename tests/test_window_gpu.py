@@ -4,7 +4,7 @@ extraction of a synthetic image; the map points are its own features re-projecte
 import numpy as np
 import pytest
 
-from motioncheck_ccm_slam_amd import synth
+from motioncheck_ccm_slam_amd import _lib, synth
 from motioncheck_ccm_slam_amd.matcher import FrameGridView, ORBmatcher
 from motioncheck_ccm_slam_amd.orb import ORBextractor
 
@@ -167,6 +167,36 @@ def test_fuse_select_batch_equals_keyframe_by_keyframe(ctx, oracle):
             else:
                 assert (got[k][0] == -1).all()
         assert sum(int((g[0] >= 0).sum()) for g in got) > 800
+
+
+def test_fuse_select_batch_rejects_an_empty_grid(ctx, oracle):
+    """A keyframe with grid_cols = 0 makes ccm_fuse_select_batch return CCM_E_ARG (as the SearchByProjection(kf, Scw) batch does);
+    the same context then answers a valid batch exactly."""
+    ex = ORBextractor(1000, 1.2, 8, 20, 7, ctx=ctx)
+    is2 = ex.GetInverseScaleSigmaSquares()
+    rng = np.random.default_rng(22)
+    kfs, per_kf, descs = [], [], []
+    sf = None
+    for seed in (4, 5):
+        fr, sf, kps, desc = _frame(ctx, seed)
+        src = rng.integers(0, len(fr.kx), 500)
+        mp_desc = (desc[src] ^ np.packbits(rng.random((500, 256)) < 0.05, axis=1, bitorder="little")).astype(np.uint8)
+        u = (fr.kx[src] + rng.normal(0, 1.5, 500)).astype("f4"); v = (fr.ky[src] + rng.normal(0, 1.5, 500)).astype("f4")
+        level = np.clip(fr.oct[src] + rng.integers(0, 2, 500), 0, 7).astype("i4")
+        kfs.append(fr); descs.append(desc); per_kf.append((rng.random(500) < 0.85, u, v, level, mp_desc))
+    bad = FrameGridView(kfs[1].kx, kfs[1].ky, kfs[1].oct, descs[1])
+    grid = bad.struct()
+    grid.grid_cols = 0
+    bad.struct = lambda: grid
+    m = ORBmatcher(ctx=ctx)
+    with pytest.raises(_lib.CcmError) as e:
+        m.FuseSelectBatch([kfs[0], bad], sf, is2, per_kf, 3.0, True)
+    assert e.value.code == -1                                      # CCM_E_ARG
+    got = m.FuseSelectBatch(kfs, sf, is2, per_kf, 3.0, True)
+    for k, (fr, t) in enumerate(zip(kfs, per_kf)):
+        rbi, rbd = oracle.fuse_select(fr.kx, fr.ky, fr.oct, descs[k], fr.min_x, fr.min_y, fr.inv_w, fr.inv_h, sf, is2, *t, 3.0, True)
+        assert (got[k][0] == rbi).all() and (got[k][1] == rbd).all(), k
+    assert sum(int((g[0] >= 0).sum()) for g in got) > 300
 
 
 def _noisy_points(fr, desc, rng, n_rel, n_rand, sigma=1.2, flip=0.04):
