@@ -73,6 +73,23 @@ __device__ __forceinline__ int wave_sum(int v)
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
+// Wave sums of two ints by DPP, with no LDS round trip (wave_sum's __shfl_xor is a ds_bpermute each): quad_perm swaps, the two
+// row mirrors give every lane its row's sum, row_bcast:15 / :31 carry rows 0-2 into lane 63, which is read.  The two chains
+// are interleaved, so each fills the other's wait states.  Needs all 64 lanes active.  Integer sums: any order, same result.
+__device__ __forceinline__ void wave_sum2_dpp(int& x, int& y)
+{
+#define WS2_STEP(ctrl, rows) { const int tx = __builtin_amdgcn_update_dpp(0, x, ctrl, rows, 0xf, false); \
+                               const int ty = __builtin_amdgcn_update_dpp(0, y, ctrl, rows, 0xf, false); x += tx; y += ty; }
+    WS2_STEP(0xb1, 0xf)            // quad_perm [1,0,3,2]
+    WS2_STEP(0x4e, 0xf)            // quad_perm [2,3,0,1]
+    WS2_STEP(0x141, 0xf)           // row_half_mirror
+    WS2_STEP(0x140, 0xf)           // row_mirror
+    WS2_STEP(0x142, 0xa)           // row_bcast:15 into rows 1, 3
+    WS2_STEP(0x143, 0xc)           // row_bcast:31 into rows 2, 3
+#undef WS2_STEP
+    x = __builtin_amdgcn_readlane(x, 63);
+    y = __builtin_amdgcn_readlane(y, 63);
+}
 
 // ------------------------------------------------------------------------------------------------
 // k_pyr_resize: one thread = 4 horizontally adjacent output pixels in each of RS_ROWS consecutive rows: the x tables
@@ -1215,7 +1232,8 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
 // k_orient_desc: a wave per selected keypoint (small batches) or per OD_ITEMS keypoint slots (see the kernel).
 //   IC_Angle (ORBextractor.cpp:68-95) on the un-blurred level, cv::fastAtan2;
 //   GaussianBlur 7x7 sigma 2 BORDER_REFLECT_101 (:1259; integer taps {18,34,49,55,49,34,18},
-//   SURVEY.md 12.6) evaluated only on the 37x37 neighbourhood the pattern can reach -- the sum
+//   SURVEY.md 12.6) evaluated only where the pattern reads it: the row pass on the 37 columns of the
+//   43-row patch, the column pass at the 512 sample points -- the sum
 //   sum_ij q_i q_j src is exact in integers, so it equals the reference's full-image separable
 //   blur bit for bit and the blurred pyramid is never written to HBM;
 //   computeOrbDescriptor (:100-316): bit k = I(p_2k) < I(p_2k+1) with the pattern rotated by the angle.
@@ -1249,14 +1267,12 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
     return a;
 }
 
-// Per-wave LDS: hT[37][46] u16 (horizontally blurred, transposed: column-major so the vertical pass reads
-// a column as 22 consecutive dwords; 92-byte pitch = 23 dwords is odd, hence bank-conflict free) and
-// bl[37][40] u8 (blurred neighbourhood).  bl OVERLAYS hT: the vertical pass has every column in registers
-// before its first store (one wave in lockstep, LDS operations of a wave complete in order), so the
-// workgroup needs 15 KB instead of 21 KB and 8 of them (32 waves) share a CU.
+// Per-wave LDS: hT[37][46] u16 (horizontally blurred, transposed: column-major, so the 7 tap rows of a
+// blurred pixel are 4 consecutive dwords of its column; the 92-byte pitch = 23 dwords is odd, which spreads
+// the scattered gathers of the descriptor over the banks).  The vertical pass runs at the sample points only,
+// so no blurred patch is stored (it used to overlay hT); 8 workgroups (32 waves) share a CU.
 #define OD_HT_PITCH 92
-#define OD_B_PITCH 40
-#define OD_WAVE_LDS (ORB_BLUR_D * OD_HT_PITCH)      // 3404 >= 37 * 40
+#define OD_WAVE_LDS (ORB_BLUR_D * OD_HT_PITCH)
 #define OD_WAVE_LDS_PAD ((OD_WAVE_LDS + 15) & ~15)
 
 __constant__ signed char c_pattern[1024];
@@ -1265,6 +1281,31 @@ typedef unsigned short od_us2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned od_dot2(unsigned a, unsigned w, unsigned acc)
 {
     return __builtin_amdgcn_udot2(__builtin_bit_cast(od_us2, a), __builtin_bit_cast(od_us2, w), acc, false);
+}
+// The blurred pixel (18 + dx, 18 + dy) of the patch: the 7 vertical taps {18,34,49,55,49,34,18} over hT rows 18+dy .. 24+dy of
+// column 18+dx (|dx|, |dy| <= 18), and the single rounding.  ctr points at column 18, dword 9.  Rows are packed two per dword,
+// so the taps need the 4 aligned dwords from row 18+dy rounded down to even; on an odd row v_alignbit moves the window up by one
+// halfword, so one even-row tap layout serves both.  The 4th pair's upper half (weight 0) is row 25+dy or, on odd rows, zero.
+// The taps sum to 257, so a saturated neighbourhood blurs to 257: the reference's saturation to 255 is needed (min before the shift,
+// which the compare then folds into a halfword select).
+// od_gather requests the 4 dwords and keeps the shift, od_blur_at applies the taps once they have arrived.
+#ifndef OD_BRIEF_BATCH
+#define OD_BRIEF_BATCH 2         // BRIEF rounds whose gathers are in flight together (1, 2 or 4)
+#endif
+struct OdTaps { unsigned d[4], sh; };
+__device__ __forceinline__ void od_gather(const uint8_t* ctr, int dx, int dy, OdTaps& t)
+{
+    const unsigned* p = reinterpret_cast<const unsigned*>(ctr + __mul24(dx, OD_HT_PITCH) + 4 * (dy >> 1));
+#pragma unroll
+    for (int i = 0; i < 4; i++) t.d[i] = p[i];
+    t.sh = (unsigned)dy << 4;                                       // v_alignbit / v_lshrrev read bits 4:0 = 16 * (dy & 1)
+}
+__device__ __forceinline__ unsigned od_blur_at(const OdTaps& t)
+{
+    const unsigned e0 = __builtin_amdgcn_alignbit(t.d[1], t.d[0], t.sh), e1 = __builtin_amdgcn_alignbit(t.d[2], t.d[1], t.sh);
+    const unsigned e2 = __builtin_amdgcn_alignbit(t.d[3], t.d[2], t.sh), e3 = t.d[3] >> (t.sh & 31u);
+    const unsigned v = od_dot2(e3, 18u, od_dot2(e2, 49u | (34u << 16), od_dot2(e1, 49u | (55u << 16), od_dot2(e0, 18u | (34u << 16), 32768u))));
+    return min(v, 0xFFFFFFu) >> 16;                                 // = min(v >> 16, 255)
 }
 
 #ifndef OD_WAVES
@@ -1344,7 +1385,6 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
     if (todo == 0) return;
 
     uint8_t* wl = lds[wv];
-    uint8_t* bl = wl;                                  // overlays hT, see OD_WAVE_LDS
     const float factorPI = (float)(3.14159265358979323846 / 180.f);
     auto item_of = [&](int j, OdItem& it, int& level, int& score, int& row) {
         const unsigned key = (unsigned)__builtin_amdgcn_readlane((int)key_l, j);
@@ -1378,10 +1418,12 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
                 m01 = v * (int)s1;
             }
         }
-        m10 = wave_sum(m10); m01 = wave_sum(m01);
+        wave_sum2_dpp(m10, m01);
         const float angle = fast_atan2_deg((float)m01, (float)m10);
 
-        // ---- horizontal 7 taps {18,34,49,55,49,34,18}: two v_dot4_u32_u8 per output, written transposed
+        // ---- horizontal 7 taps {18,34,49,55,49,34,18}: two v_dot4_u32_u8 per output, written transposed.  The previous
+        //      keypoint's gathers from hT completed before its ballots; the wait keeps it so whatever the compiler schedules.
+        __builtin_amdgcn_s_waitcnt(0xc07f);
         if (lane < ORB_PATCH_D) {
             const unsigned Q0 = 18u | (34u << 8) | (49u << 16) | (55u << 24), Q1 = 49u | (34u << 8) | (18u << 16);
 #pragma unroll
@@ -1403,59 +1445,33 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
-        // ---- vertical 7 taps + the single rounding.  An item is a third of a blurred column (rows 12t .. 12t+12; the
-        //      13th row of the first two thirds is also the first of the next: same value, written twice): 111 items in
-        //      two rounds of 64 lanes = 26 outputs per lane instead of 37.  Rows are packed two per dword, so four
-        //      v_dot2_u32_u16 make one output; a third starts on an even row, so the tap layout is the same for all.
-        {
-            unsigned d[2][10];
-            int wofs[2];
-#pragma unroll
-            for (int rd = 0; rd < 2; rd++) {
-                const int item = min(rd * 64 + lane, 3 * ORB_BLUR_D - 1);
-                const int c = (item * 171) >> 9, t = item - 3 * c;                 // item / 3 for item < 128
-                const unsigned* col = reinterpret_cast<const unsigned*>(wl + c * OD_HT_PITCH) + 6 * t;
-#pragma unroll
-                for (int i = 0; i < 10; i++) d[rd][i] = col[i];
-                wofs[rd] = 12 * t * OD_B_PITCH + c;
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);                // every column is in registers before bl overwrites hT
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int rd = 0; rd < 2; rd++) {
-                if (rd * 64 + lane < 3 * ORB_BLUR_D) {
-#pragma unroll
-                    for (int y = 0; y < 13; y++) {
-                        const int kk = y >> 1;
-                        unsigned v;
-                        if ((y & 1) == 0)
-                            v = od_dot2(d[rd][kk + 3], 18u, od_dot2(d[rd][kk + 2], 49u | (34u << 16), od_dot2(d[rd][kk + 1], 49u | (55u << 16), od_dot2(d[rd][kk], 18u | (34u << 16), 32768u))));
-                        else
-                            v = od_dot2(d[rd][kk + 3], 34u | (18u << 16), od_dot2(d[rd][kk + 2], 55u | (49u << 16), od_dot2(d[rd][kk + 1], 34u | (49u << 16), od_dot2(d[rd][kk], 18u << 16, 32768u))));
-                        bl[wofs[rd] + y * OD_B_PITCH] = (uint8_t)min(v >> 16, 255u);     // the rounding constant 32768 is the accumulator's start value
-                    }
-                }
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        __builtin_amdgcn_wave_barrier();
 
-        // ---- steered BRIEF: lane L evaluates pairs L, 64+L, 128+L, 192+L; a ballot is 8 descriptor bytes
+        // ---- steered BRIEF: lane L evaluates pairs L, 64+L, 128+L, 192+L; a ballot is 8 descriptor bytes.  The vertical taps are
+        //      applied at the 512 sample points only (od_blur_at), straight from hT: no blurred patch is built.
         float a, b;
         ccm_sincosf(angle * factorPI, &b, &a);
         uint8_t* drow = desc + ((long long)f * max_per_image + row_c) * 32;
-        const uint8_t* ctr = bl + 18 * OD_B_PITCH + 18;
+        const uint8_t* ctr = wl + 18 * OD_HT_PITCH + 4 * 9;          // column 18, the dword of rows 18-19 (blurred row 18's first tap)
         unsigned long long mybits = 0;
+        // OD_BRIEF_BATCH rounds' gathers are requested before the first of them is used (the scheduler, left alone, waits for each
+        // point's two reads before it requests the next point's)
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const unsigned pr = pat[r * 64 + lane];
-            const float x0 = (float)(signed char)(pr & 255u), y0 = (float)(signed char)((pr >> 8) & 255u);
-            const float x1 = (float)(signed char)((pr >> 16) & 255u), y1 = (float)(signed char)(pr >> 24);
-            const int t0 = ctr[__float2int_rn(x0 * b + y0 * a) * OD_B_PITCH + __float2int_rn(x0 * a - y0 * b)];
-            const int t1 = ctr[__float2int_rn(x1 * b + y1 * a) * OD_B_PITCH + __float2int_rn(x1 * a - y1 * b)];
-            const unsigned long long bits = __ballot(t0 < t1);
-            if (lane == r) mybits = bits;
+        for (int r0 = 0; r0 < 4; r0 += OD_BRIEF_BATCH) {
+            OdTaps tp[OD_BRIEF_BATCH][2];
+#pragma unroll
+            for (int q = 0; q < OD_BRIEF_BATCH; q++) {
+                const unsigned pr = pat[(r0 + q) * 64 + lane];
+                const float x0 = (float)(signed char)(pr & 255u), y0 = (float)(signed char)((pr >> 8) & 255u);
+                const float x1 = (float)(signed char)((pr >> 16) & 255u), y1 = (float)(signed char)(pr >> 24);
+                od_gather(ctr, __float2int_rn(x0 * a - y0 * b), __float2int_rn(x0 * b + y0 * a), tp[q][0]);
+                od_gather(ctr, __float2int_rn(x1 * a - y1 * b), __float2int_rn(x1 * b + y1 * a), tp[q][1]);
+            }
+            if (OD_BRIEF_BATCH > 1) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < OD_BRIEF_BATCH; q++) {
+                const unsigned long long bits = __ballot(od_blur_at(tp[q][0]) < od_blur_at(tp[q][1]));
+                if (lane == r0 + q) mybits = bits;
+            }
         }
         if (lane < 4) *reinterpret_cast<unsigned long long*>(drow + 8 * lane) = mybits;      // one 32-byte store
         if (lane == 0) {
@@ -1468,7 +1484,7 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
             kps[(long long)f * max_per_image + row_c] = kp;
         }
         if (!more) break;
-        // (the BRIEF reads of bl are in registers -- the ballots consumed them -- before the next horizontal pass overwrites it)
+        // (the BRIEF gathers from hT are in registers -- the ballots consumed them -- before the next horizontal pass overwrites it)
     }
 }
 
