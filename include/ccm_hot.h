@@ -111,6 +111,7 @@ int ccm_orb_level_sizes(const ccm_orb_params*, int w, int h, int32_t* level_w, i
  * keypoints and 32-byte descriptors, rows in the reference's order (level-major,
  * then DistributeOctTree list order).  kps: [n_images][max_per_image],
  * desc: [n_images][max_per_image][32], counts: [n_images].
+ * Rows past counts[i] are zero.
  * n_images == 0 or w*h == 0 -> CCM_OK with nothing written (the reference
  * returns silently on an empty image, ORBextractor.cpp:1219-1220).
  * Returns CCM_E_CAPACITY if an image yields more than max_per_image keypoints
@@ -122,7 +123,10 @@ int ccm_orb_extract(ccm_ctx*, const ccm_orb_params*, const uint8_t* img, int w, 
 /* Device-resident variant: img_dev is a device pointer; results stay on the
  * device (fetch with ccm_orb_fetch) so that ccm_hamming_match_dev can consume
  * the descriptors without a PCIe round trip.  The call is asynchronous on the
- * context's stream.  */
+ * context's stream.  An image with more than max_per_image keypoints is
+ * reported by the next ccm_orb_fetch, which returns CCM_E_CAPACITY and copies
+ * nothing; counts_dev (ccm_orb_result_dev) then holds the counts clamped to
+ * max_per_image.  */
 int ccm_orb_extract_dev(ccm_ctx*, const ccm_orb_params*, const uint8_t* img_dev, int w, int h,
                         int stride, size_t image_stride, int n_images, int max_per_image);
 /* Copy the last ccm_orb_extract_dev results to host (any pointer may be NULL). */
@@ -154,7 +158,8 @@ int ccm_descriptor_distance(const uint8_t* a, const uint8_t* b);
 int ccm_hamming_match(ccm_ctx*, const uint8_t* q, int nq, const uint8_t* t, int nt, int n_pairs,
                       const int32_t* nq_n, const int32_t* nt_n,
                       int32_t* best_idx, int32_t* best_dist, int32_t* second_dist);
-/* Same on device pointers (descriptor strides in rows), asynchronous. */
+/* Same on device pointers (descriptor strides in rows), asynchronous.  q_dev and t_dev must be 16-byte aligned and
+ * nt <= 65535 (CCM_E_ARG otherwise). */
 int ccm_hamming_match_dev(ccm_ctx*, const uint8_t* q_dev, int nq, size_t q_pair_stride,
                           const uint8_t* t_dev, int nt, size_t t_pair_stride, int n_pairs,
                           const int32_t* nq_n_dev, const int32_t* nt_n_dev,
@@ -303,7 +308,8 @@ int  ccm_voc_words(const ccm_vocabulary*);
 
 /* transform(feature, word_id, weight, nid, levelsup) (:1217-1258) for n features: the L-level k-way Hamming descent.
  * node_id = the node at level L - levelsup (0 = root when that is <= 0 or the branch ends above it).  The _dev form
- * takes descriptors resident on the device (ccm_orb_result_dev); results are host arrays. */
+ * takes descriptors resident on the device (ccm_orb_result_dev); results are host arrays.  Its features_dev must be
+ * 16-byte aligned (CCM_E_ARG otherwise), as for ccm_hamming_match_dev, and is read on the vocabulary's context's stream. */
 int ccm_voc_transform(ccm_vocabulary*, const uint8_t* features, int n, int levelsup, int32_t* word_id, double* weight, int32_t* node_id);
 int ccm_voc_transform_dev(ccm_vocabulary*, const uint8_t* features_dev, int n, int levelsup, int32_t* word_id, double* weight,
                           int32_t* node_id);

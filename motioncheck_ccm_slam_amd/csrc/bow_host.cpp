@@ -77,6 +77,7 @@ int ccm_voc_transform_dev(ccm_vocabulary* v, const uint8_t* features_dev, int n,
     return ccm_guard(c, "ccm_voc_transform_dev", [&]() -> int {
         if (n < 0 || (n > 0 && (!features_dev || !word_id || !weight || !node_id))) return ccm_fail(c, CCM_E_ARG, "bad transform arguments");
         if (n == 0) return CCM_OK;
+        if ((uintptr_t)features_dev & 15) return ccm_fail(c, CCM_E_ARG, "descriptor array must be 16-byte aligned");   // (k_voc_transform reads uint4)
         if (v->n_words == 0) {                                                        // empty(): transform() returns nothing (:1133)
             for (int i = 0; i < n; i++) { word_id[i] = 0; weight[i] = 0; node_id[i] = 0; }
             return CCM_OK;

@@ -1379,6 +1379,14 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
         counts[f] = min(tot, max_per_image);
         if (tot > max_per_image) atomicOr(status, 8);
     }
+    if (wx == 0) {                                                         // the frame's rows past its count are zero, not left from an earlier call
+        const long long r0 = (long long)f * max_per_image + min(tot, max_per_image);
+        const int npad = max_per_image - min(tot, max_per_image);
+        unsigned* kz = reinterpret_cast<unsigned*>(kps + r0);             // (7 dwords per keypoint row)
+        for (int i = threadIdx.x; i < npad * 7; i += 64 * OD_WAVES) kz[i] = 0u;
+        uint4* dz = reinterpret_cast<uint4*>(desc + r0 * 32);
+        for (int i = threadIdx.x; i < npad * 2; i += 64 * OD_WAVES) dz[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
     const bool valid_l = lane < ITEMS && slot < g.out_per_frame && slot - first_l < cnt_l && row_l < max_per_image;
     unsigned long long todo = __ballot(valid_l);
     __syncthreads();                                                       // (the weight tables)

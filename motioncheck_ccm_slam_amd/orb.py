@@ -17,7 +17,7 @@ from ._lib import KP_DTYPE, OrbParams
 
 class ORBextractor:
     def __init__(self, nfeatures: int, scaleFactor: float, nlevels: int, iniThFAST: int, minThFAST: int,
-                 ctx: _lib.Context | None = None):
+                 ctx: _lib.Context | None = None, max_per_image: int | None = None):
         self.lib = _lib.load()
         self.par = OrbParams(int(nfeatures), float(scaleFactor), int(nlevels), int(iniThFAST), int(minThFAST))
         n = self.par.nlevels
@@ -30,6 +30,8 @@ class ORBextractor:
             raise _lib.CcmError(rc, "bad ORBextractor parameters")
         self._ctx = ctx
         self.max_per_image = int(nfeatures) + 4 * n + 64      # the quadtree may overshoot each quota by up to 3
+        if max_per_image is not None:                          # a smaller cap makes the extract fail with CCM_E_CAPACITY
+            self.max_per_image = int(max_per_image)
         self._last = None
 
     # ---- getters (ORBextractor.h:120-150)
@@ -63,11 +65,17 @@ class ORBextractor:
         return kps[0, :n].copy(), desc[0, :n].copy()
 
     def extract_batch(self, images: np.ndarray, out=None):
-        """images [B,H,W] uint8 (host) -> kps [B,max], desc [B,max,32], counts [B].  `out` = (kps, desc, counts) of those shapes
+        """images [B,H,W] uint8 (host; rows may be padded and frames apart) -> kps [B,max], desc [B,max,32], counts [B].  `out` = (kps, desc, counts) of those shapes
         re-uses the caller's buffers (a server keeps its frame and result pools page-locked with Context.host_register: the results
         of a chunk of frames then go down while the next chunk is extracted)."""
-        images = np.ascontiguousarray(images, np.uint8)
+        images = np.asarray(images)
         b, h, w = images.shape
+        # the caller's own layout when rows are contiguous (as the shim passes cv::Mat::step), a packed copy otherwise
+        sb, sr, sc = images.strides
+        if not (images.dtype == np.uint8 and sc == 1 and sr >= w and (b == 1 or sb >= sr * h)):
+            images = np.ascontiguousarray(images, np.uint8)
+            sb, sr = w * h, w
+        image_stride = sb if b > 1 else 0
         m = self.max_per_image
         if out is not None:
             kps, desc, counts = out
@@ -75,8 +83,8 @@ class ORBextractor:
             assert kps.flags.c_contiguous and desc.flags.c_contiguous and counts.flags.c_contiguous
         else:
             kps = np.zeros((b, m), KP_DTYPE); desc = np.zeros((b, m, 32), np.uint8); counts = np.zeros(b, "i4")
-        self.ctx.check(self.lib.ccm_orb_extract(self.ctx.handle, C.byref(self.par), _lib.ptr(images), w, h, w,
-                                                C.c_size_t(w * h), b, _lib.ptr(kps), _lib.ptr(desc), _lib.ptr(counts), m))
+        self.ctx.check(self.lib.ccm_orb_extract(self.ctx.handle, C.byref(self.par), _lib.ptr(images), w, h, sr,
+                                                C.c_size_t(image_stride), b, _lib.ptr(kps), _lib.ptr(desc), _lib.ptr(counts), m))
         self._last = (b, w, h)
         return kps, desc, counts
 

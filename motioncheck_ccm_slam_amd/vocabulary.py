@@ -41,6 +41,14 @@ class ORBVocabulary:
         self.ctx.check(self.lib.ccm_voc_transform(self.handle, _lib.ptr(d), n, int(levelsup), _lib.ptr(wid), _lib.ptr(w), _lib.ptr(nid)))
         return wid[:n], w[:n], nid[:n]
 
+    def transform_features_dev(self, desc_ptr: int, n: int, levelsup: int = 4):
+        """transform_features of n descriptors already on the device (desc_ptr: a 16-byte aligned device address, e.g. a frame's rows
+        of ORBextractor.result_dev()).  Runs on the vocabulary's context's stream: work on another stream must be finished first."""
+        wid = np.zeros(max(n, 1), "i4"); w = np.zeros(max(n, 1), "f8"); nid = np.zeros(max(n, 1), "i4")
+        self.ctx.check(self.lib.ccm_voc_transform_dev(self.handle, C.c_void_p(desc_ptr), int(n), int(levelsup), _lib.ptr(wid),
+                                                      _lib.ptr(w), _lib.ptr(nid)))
+        return wid[:n], w[:n], nid[:n]
+
     def transform(self, desc, levelsup: int = 4):
         """transform(features, BowVector, FeatureVector, levelsup): returns (word ids, values, node per feature)."""
         wid, w, nid = self.transform_features(desc, levelsup)

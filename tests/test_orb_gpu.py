@@ -90,8 +90,8 @@ def test_empty_and_strided_inputs(ctx, oracle):
     assert len(kps) == 0
     big = np.zeros((480, 800), np.uint8)
     big[:, :752] = synth.frame(1)
-    view = big[:, :752]                                   # non-contiguous rows are copied by row, like cv::Mat ROIs
-    _same(*ex(np.ascontiguousarray(view)), oracle.orb_extract(oracle.default_params(), np.ascontiguousarray(view)))
+    view = big[:, :752]                                   # a cv::Mat ROI: rows 800 bytes apart, passed as they are (stride = step)
+    _same(*ex(view), oracle.orb_extract(oracle.default_params(), np.ascontiguousarray(view)))
 
 
 def test_full_batch_properties(ctx, oracle):
