@@ -494,6 +494,91 @@ typedef struct {
 } ccm_sim3_problem;
 int ccm_optimize_sim3(ccm_ctx*, ccm_sim3_problem*);
 
+/* ---------------------------------------------------------------- Sim3Solver (src/Sim3Solver.cpp), batched RANSAC
+ * The link in front of OptimizeSim3 in loop closing and map matching (src/LoopFinder.cpp:231-346, src/MapMatcher.cpp:238-350): one
+ * Sim3Solver per candidate keyframe, iterate(5) round-robin over the candidates.  The hypotheses of Sim3Solver::iterate (:120-191)
+ * do not depend on each other (three sampled correspondences -> ComputeSim3 :210-321 -> CheckInliers :324-348); only "running
+ * best, return at the first hypothesis that qualifies" is ordered.  ccm_sim3_solver_create evaluates ALL hypotheses of ALL solvers
+ * of a batch in one launch; ccm_sim3_solver_iterate / _find replay the ordered bookkeeping over the stored results on the host, so
+ * any calling pattern returns what the sequential code returns for the same random draws.
+ *
+ * Constructor data (:5-92), flattened by the caller as for ccm_sim3_problem: correspondence e of solver k (first[k] <= e <
+ * first[k+1], N = first[k+1] - first[k]) = one vpMatched12[i1] that passed :32-59, in i1 order.  The library computes mvP1im1 /
+ * mvP2im2 (FromCameraToImage, :389-407).
+ *
+ * SetRansacParameters (:94-118) is part of the create call, because the hypotheses are evaluated there: solver k evaluates
+ * mRansacMaxIts = ccm_sim3_ransac_iterations(N, probability, min_inliers, max_iterations) hypotheses, or none when N < min_inliers
+ * (iterate leaves at :129) or N < 3 (the reference would sample out of range; unreachable behind MatchesThres 20).
+ *
+ * Sampling (:146-161): the random source stays with the caller (DUtils::Random is not part of this library).  draws holds the raw
+ * RandomInt results: draw i of hypothesis h of solver k at draws[(k * max_iterations + h) * 3 + i], in [0, N-1-i].  The library
+ * turns them into correspondence indices by the reference's swap-with-last removal on vAvailableIndices = 0..N-1 (position randi
+ * takes the last element, :159).  Only the rows of hypotheses that are evaluated are read; one of them outside its range is
+ * CCM_E_ARG.
+ *
+ * ComputeSim3: float storage as in the reference, the 4x4 symmetric eigenproblem by cyclic Jacobi in double.  The rotation is
+ * built from the unit quaternion directly (equal to the reference's Rodrigues(2 atan2(|v|, w) v/|v|) for either sign of the
+ * eigenvector, and defined at zero rotation); cv::eigen lies outside the reference tree, so the contract is a tolerance against a
+ * float64 restatement, not bits.  CheckInliers: err1 = |p1im1 - proj(K1, T12 X2)|^2, err2 = |proj(K2, T21 X1)
+ * - p2im2|^2, inlier iff err1 < max_err1 && err2 < max_err2; non-finite errors compare false. */
+typedef struct {
+    int32_t        n_solvers;
+    const int32_t* first;        /* [n_solvers+1], first[0] = 0, non-decreasing */
+    const int32_t* n1;           /* [n_solvers] mN1 = vpMatched12.size() */
+    const int32_t* fix_scale;    /* [n_solvers] mbFixScale */
+    const float*   K1;           /* [n_solvers][4] fx, fy, cx, cy of mK1 */
+    const float*   K2;
+    const float*   X1;           /* [..][3] mvX3Dc1 = Rcw1 * X3D1w + tcw1 (camera frame of pKF1) */
+    const float*   X2;           /* [..][3] mvX3Dc2 */
+    const float*   max_err1;     /* [..] mvnMaxError1 = 9.210 * mvLevelSigma2[octave] (:67) */
+    const float*   max_err2;
+    const int32_t* indices1;     /* [..] mvnIndices1, each in [0, n1[k]) */
+    double         probability;  /* SetRansacParameters(probability, minInliers, maxIterations) */
+    int32_t        min_inliers;
+    int32_t        max_iterations;
+    const int32_t* draws;        /* [n_solvers][max_iterations][3] */
+    /* mnBestInliers at the start, [n_solvers], or NULL for 0 (the constructor's value).  SetRansacParameters resets mnIterations
+     * (:117) but not mnBestInliers: a caller that changes the parameters of a solver it has already iterated creates the new batch
+     * with the old solver's best count here and keeps its estimate until a hypothesis reaches that count. */
+    const int32_t* best_inliers;
+} ccm_sim3_ransac_problem;
+typedef struct ccm_sim3_solver ccm_sim3_solver;
+
+/* mRansacMaxIts of SetRansacParameters (:94-118): epsilon = (float)min_inliers / n; nIterations = 1 if min_inliers == n, else
+ * ceil(log(1 - probability) / log(1 - pow(epsilon, 3))); max(1, min(nIterations, max_iterations)).  For n < min_inliers (and n ==
+ * 0) the reference converts the logarithm of a non-positive number to int, which is undefined; the value is never used (iterate
+ * leaves at :129) and is defined as 1 here.  Host only. */
+int ccm_sim3_ransac_iterations(int n, double probability, int min_inliers, int max_iterations);
+/* Uploads the batch, evaluates every hypothesis in one launch, downloads the per-hypothesis counts, estimates and inlier masks and
+ * synchronises once.  Device memory is the context's (grow-only, reused by the next batch); the solver object holds host memory
+ * only.  It belongs to the thread that made it.  On an error *out is untouched. */
+int ccm_sim3_solver_create(ccm_ctx*, const ccm_sim3_ransac_problem*, ccm_sim3_solver** out);
+/* NULL is a no-op. */
+void ccm_sim3_solver_destroy(ccm_sim3_solver*);
+/* n_solvers of the batch, or CCM_E_ARG for NULL. */
+int ccm_sim3_solver_count(const ccm_sim3_solver*);
+/* Sim3Solver::iterate(nIterations, bNoMore, vbInliers, nInliers) (:120-191) of solver k, exactly: N < min_inliers -> *no_more = 1
+ * and nothing else; the running best is replaced on mnInliersi >= mnBestInliers; a Sim3 comes back only for mnInliersi >
+ * min_inliers (strict); mnIterations and mnBestInliers persist over calls, the per-call counter restarts; *no_more is set only when
+ * the loop ends without a return at mnIterations >= mRansacMaxIts.  *found = 1: T12 holds mBestT12 (4x4 row-major), *n_inliers
+ * the count and inliers[mvnIndices1[i]] = 1 for every inlier i; otherwise T12 is untouched.  inliers has n1[k] entries and is
+ * always cleared first (:123).  inliers and T12 may be NULL. */
+int ccm_sim3_solver_iterate(ccm_sim3_solver*, int k, int n_iterations, int32_t* found, int32_t* no_more, uint8_t* inliers,
+                            int32_t* n_inliers, float* T12);
+/* Sim3Solver::find (:193-197) = iterate(mRansacMaxIts) without bNoMore. */
+int ccm_sim3_solver_find(ccm_sim3_solver*, int k, int32_t* found, uint8_t* inliers, int32_t* n_inliers, float* T12);
+/* GetEstimatedRotation / Translation / Scale (:351-364): the running best, which hypotheses that did not qualify for a return
+ * update as well.  R row-major 3x3.  CCM_E_STATE while no hypothesis has become the best (the reference returns empty matrices). */
+int ccm_sim3_solver_estimate(const ccm_sim3_solver*, int k, float* R, float* t, float* s);
+/* The RANSAC state of solver k (each output may be NULL): mnIterations, mnBestInliers, the hypothesis behind the running best
+ * (-1 = none yet) and mRansacMaxIts. */
+int ccm_sim3_solver_state(const ccm_sim3_solver*, int k, int32_t* iterations, int32_t* best_inliers, int32_t* best_hypothesis,
+                          int32_t* max_iterations);
+/* Test / diagnostic tap: what the launch stored for solver k.  Returns the number of hypotheses H (>= 0) or an error; each
+ * output may be NULL: sample [H][3] correspondence indices, count [H], rts [H][13] = R (9), t (3), s, mask [H][ceil(N/64)] with
+ * correspondence i at bit i % 64 of word i / 64. */
+int ccm_sim3_solver_hypotheses(const ccm_sim3_solver*, int k, int32_t* sample, int32_t* count, float* rts, uint64_t* mask);
+
 /* The optimisation inside Optimizer::OptimizeEssentialGraphLoopClosure / OptimizeEssentialGraphMapFusion
  * (src/Optimizer.cpp:1064-1331, :1333-1574): one VertexSim3Expmap per keyframe (sim3 = Scw or the corrected Sim3,
  * :1094-1108; fixed = pLoopKF, :1110), one EdgeSim3 per loop / spanning-tree / covisibility edge built by the caller

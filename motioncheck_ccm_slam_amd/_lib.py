@@ -37,6 +37,8 @@ SYMBOLS = [
     "ccm_frame_create", "ccm_frame_from_extract", "ccm_frame_destroy", "ccm_frame_size", "ccm_frame_set_map_points",
     "ccm_frame_get_map_points", "ccm_frame_debug_grid", "ccm_frame_search_by_projection", "ccm_frame_search_by_projection_frame",
     "ccm_frame_pose_optimize",
+    "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
+    "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
 ]
 
 
@@ -78,6 +80,13 @@ class Sim3Problem(C.Structure):
     _fields_ = [("n_problems", C.c_int), ("sim3", C.c_void_p), ("fix_scale", C.c_void_p), ("K1", C.c_void_p), ("K2", C.c_void_p),
                 ("first", C.c_void_p), ("P1", C.c_void_p), ("P2", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p),
                 ("info1", C.c_void_p), ("info2", C.c_void_p), ("th2", C.c_void_p), ("inlier", C.c_void_p), ("n_inliers", C.c_void_p)]
+
+
+class Sim3RansacProblem(C.Structure):
+    _fields_ = [("n_solvers", C.c_int32), ("first", C.c_void_p), ("n1", C.c_void_p), ("fix_scale", C.c_void_p), ("K1", C.c_void_p),
+                ("K2", C.c_void_p), ("X1", C.c_void_p), ("X2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("indices1", C.c_void_p), ("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
+                ("draws", C.c_void_p), ("best_inliers", C.c_void_p)]
 
 
 class EssentialGraph(C.Structure):
@@ -189,6 +198,15 @@ def load():
     lib.ccm_frame_search_by_projection.argtypes = [vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_float, vp]
     lib.ccm_frame_search_by_projection_frame.argtypes = [vp, vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_int, C.c_int, vp]
     lib.ccm_frame_pose_optimize.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int]
+    lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]
+    lib.ccm_sim3_solver_destroy.argtypes = [vp]; lib.ccm_sim3_solver_destroy.restype = None
+    lib.ccm_sim3_solver_count.argtypes = [vp]
+    lib.ccm_sim3_solver_iterate.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.ccm_sim3_solver_find.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_sim3_solver_estimate.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.ccm_sim3_solver_state.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_sim3_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -20,6 +20,7 @@ struct BaState;
 struct CommState;
 struct PoseState;
 struct Sim3State;
+struct Sim3RansacState;
 struct EssState;
 struct FrameState;
 
@@ -44,6 +45,7 @@ struct ccm_ctx {
     CommState* comm = nullptr;
     PoseState* pose = nullptr;
     Sim3State* sim3 = nullptr;
+    Sim3RansacState* sim3_ransac = nullptr;   // batched Sim3Solver: staging and device buffers (sim3_ransac_host.cpp)
     EssState* ess = nullptr;
     FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_host.cpp)
 };
@@ -143,5 +145,6 @@ void ba_state_free(BaState*);
 void comm_state_free(ccm_ctx*);
 void pose_state_free(PoseState*);
 void sim3_state_free(Sim3State*);
+void sim3_ransac_state_free(Sim3RansacState*);
 void ess_state_free(EssState*);
 void frame_state_free(ccm_ctx*);                       // also orphans the frames still alive

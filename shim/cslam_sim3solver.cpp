@@ -1,0 +1,192 @@
+// cslam_sim3solver.cpp -- drop-in body of cslam::Sim3Solver (src/Sim3Solver.cpp): the constructor's map-side loop (:5-92) fills the
+// flat arrays of ccm_sim3_ransac_problem, the random draws of the sampling loop (:146-161) come from DUtils::Random::RandomInt as in
+// the reference, and iterate / find / GetEstimated* forward to the C ABI.  The reference's header (include/cslam/Sim3Solver.h) stays
+// untouched, so the state the class has no member for -- the flat arrays and the ccm_sim3_solver handle -- lives in a side table
+// keyed on the object.  The header declares no destructor (LoopFinder and MapMatcher never delete their solvers either); an entry
+// is reused when a new solver is constructed at the address of an old one, and ccm_shim::sim3_solver_release(this) drops it for a
+// caller that does delete.
+//
+// The RANSAC parameters are part of ccm_sim3_solver_create (every hypothesis is evaluated there, in one launch), so the batch is
+// created lazily at the first iterate / find after the last SetRansacParameters.  One Sim3Solver object is a batch of one; a caller
+// that owns the candidate loop (src/LoopFinder.cpp:251-282) gets all candidates into one launch by filling one
+// ccm_sim3_ransac_problem itself.
+#include <cslam/Sim3Solver.h>
+#include <map>
+#include <mutex>
+#include "ccm_shim.h"
+
+namespace ccm_shim {
+
+struct Sim3SolverSide {
+    std::vector<float> X1, X2, max_err1, max_err2;
+    std::vector<int32_t> indices1;
+    float K1[4], K2[4];
+    int32_t n1 = 0, fix_scale = 0, best_inliers = 0;
+    double probability = 0.99; int min_inliers = 6, max_iterations = 300;
+    ccm_sim3_solver* solver = nullptr;
+    bool have_estimate = false; float R[9], t[3], s = 1.0f;       // the running best carried over a SetRansacParameters
+    ~Sim3SolverSide() { ccm_sim3_solver_destroy(solver); }
+};
+
+static std::mutex g_side_mutex;
+static std::map<const void*, Sim3SolverSide>& side_table()
+{
+    static std::map<const void*, Sim3SolverSide> t;
+    return t;
+}
+static Sim3SolverSide& side_of(const void* self, bool fresh = false)
+{
+    std::lock_guard<std::mutex> lock(g_side_mutex);
+    if (fresh) side_table().erase(self);
+    return side_table()[self];
+}
+void sim3_solver_release(const void* self)
+{
+    std::lock_guard<std::mutex> lock(g_side_mutex);
+    side_table().erase(self);
+}
+
+// the solver of the current parameters, created on first use (one upload, one launch, one download)
+static ccm_sim3_solver* ensure(Sim3SolverSide& S)
+{
+    if (S.solver) return S.solver;
+    const int N = (int)S.indices1.size();
+    const int32_t first[2] = { 0, N };
+    std::vector<int32_t> draws((size_t)S.max_iterations * 3, 0);
+    if (N >= 3)
+        for (int h = 0; h < S.max_iterations; h++)
+            for (int i = 0; i < 3; i++) draws[3 * h + i] = DUtils::Random::RandomInt(0, N - 1 - i);       // :151
+    ccm_sim3_ransac_problem pb{};
+    pb.n_solvers = 1; pb.first = first; pb.n1 = &S.n1; pb.fix_scale = &S.fix_scale; pb.K1 = S.K1; pb.K2 = S.K2;
+    pb.X1 = S.X1.data(); pb.X2 = S.X2.data(); pb.max_err1 = S.max_err1.data(); pb.max_err2 = S.max_err2.data(); pb.indices1 = S.indices1.data();
+    pb.probability = S.probability; pb.min_inliers = S.min_inliers; pb.max_iterations = S.max_iterations;
+    pb.draws = draws.data(); pb.best_inliers = &S.best_inliers;
+    if (ccm_sim3_solver_create(ctx(), &pb, &S.solver)) throw estd::infrastructure_ex();
+    return S.solver;
+}
+
+}  // namespace ccm_shim
+
+namespace cslam {
+
+Sim3Solver::Sim3Solver(kfptr pKF1, kfptr pKF2, const vector<mpptr> &vpMatched12, const bool bFixScale):
+    mnIterations(0), mnBestInliers(0), mbFixScale(bFixScale)
+{
+    ccm_shim::Sim3SolverSide& S = ccm_shim::side_of(this, true);
+    mpKF1 = pKF1;
+    mpKF2 = pKF2;
+    const vector<mpptr> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+    mN1 = vpMatched12.size();
+    mvpMatches12 = vpMatched12;
+    const cv::Mat Rcw1 = pKF1->GetRotation(), tcw1 = pKF1->GetTranslation(), Rcw2 = pKF2->GetRotation(), tcw2 = pKF2->GetTranslation();
+    size_t idx = 0;
+    for (int i1 = 0; i1 < mN1; i1++) {                                        // :30-83
+        if (!vpMatched12[i1]) continue;
+        mpptr pMP1 = vpKeyFrameMP1[i1];
+        mpptr pMP2 = vpMatched12[i1];
+        if (!pMP1) continue;
+        if (pMP1->isBad() || pMP2->isBad()) continue;
+        const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1);
+        const int indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+        if (indexKF1 < 0 || indexKF2 < 0) continue;
+        const cv::KeyPoint &kp1 = pKF1->mvKeysUn[indexKF1];
+        const cv::KeyPoint &kp2 = pKF2->mvKeysUn[indexKF2];
+        const float sigmaSquare1 = pKF1->mvLevelSigma2[kp1.octave];
+        const float sigmaSquare2 = pKF2->mvLevelSigma2[kp2.octave];
+        // mvnMaxError1/2 are std::vector<size_t> in the header (include/cslam/Sim3Solver.h:74-75): the push_back of :67-68 drops the
+        // fraction, and CheckInliers compares the float error with that integer.  The same value goes to the library as a float.
+        mvnMaxError1.push_back(9.210 * sigmaSquare1);
+        mvnMaxError2.push_back(9.210 * sigmaSquare2);
+        S.max_err1.push_back((float)mvnMaxError1.back());
+        S.max_err2.push_back((float)mvnMaxError2.back());
+        mvpMapPoints1.push_back(pMP1);
+        mvpMapPoints2.push_back(pMP2);
+        mvnIndices1.push_back(i1);
+        S.indices1.push_back(i1);
+        const cv::Mat X1c = Rcw1 * pMP1->GetWorldPos() + tcw1, X2c = Rcw2 * pMP2->GetWorldPos() + tcw2;       // :74-78
+        mvX3Dc1.push_back(X1c);
+        mvX3Dc2.push_back(X2c);
+        for (int k = 0; k < 3; k++) { S.X1.push_back(X1c.at<float>(k)); S.X2.push_back(X2c.at<float>(k)); }
+        mvAllIndices.push_back(idx);
+        idx++;
+    }
+    mK1 = pKF1->mK;
+    mK2 = pKF2->mK;
+    S.K1[0] = mK1.at<float>(0, 0); S.K1[1] = mK1.at<float>(1, 1); S.K1[2] = mK1.at<float>(0, 2); S.K1[3] = mK1.at<float>(1, 2);
+    S.K2[0] = mK2.at<float>(0, 0); S.K2[1] = mK2.at<float>(1, 1); S.K2[2] = mK2.at<float>(0, 2); S.K2[3] = mK2.at<float>(1, 2);
+    S.n1 = mN1; S.fix_scale = bFixScale ? 1 : 0;
+    SetRansacParameters();                                                    // :91; mvP1im1 / mvP2im2 (:88-89) are formed by the library
+}
+
+void Sim3Solver::SetRansacParameters(double probability, int minInliers, int maxIterations)
+{
+    ccm_shim::Sim3SolverSide& S = ccm_shim::side_of(this);
+    if (S.solver) {                                                           // mnBestInliers and the best estimate survive (:94-118)
+        int32_t best = 0;
+        ccm_sim3_solver_state(S.solver, 0, nullptr, &best, nullptr, nullptr);
+        S.best_inliers = best;
+        if (ccm_sim3_solver_estimate(S.solver, 0, S.R, S.t, &S.s) == CCM_OK) S.have_estimate = true;
+        ccm_sim3_solver_destroy(S.solver);
+        S.solver = nullptr;
+    }
+    mRansacProb = probability;
+    mRansacMinInliers = minInliers;
+    N = mvpMapPoints1.size();
+    mRansacMaxIts = ccm_sim3_ransac_iterations(N, probability, minInliers, maxIterations);     // :104-115
+    mnIterations = 0;
+    S.probability = probability; S.min_inliers = minInliers; S.max_iterations = maxIterations < 1 ? 1 : maxIterations;
+}
+
+cv::Mat Sim3Solver::iterate(int nIterations, bool &bNoMore, vector<bool> &vbInliers, int &nInliers)
+{
+    ccm_shim::Sim3SolverSide& S = ccm_shim::side_of(this);
+    ccm_sim3_solver* solver = ccm_shim::ensure(S);
+    std::vector<uint8_t> inl(mN1 > 0 ? mN1 : 1, 0);
+    int32_t found = 0, no_more = 0, n = 0;
+    cv::Mat T12(4, 4, CV_32F);
+    if (ccm_sim3_solver_iterate(solver, 0, nIterations, &found, &no_more, inl.data(), &n, T12.ptr<float>())) throw estd::infrastructure_ex();
+    int32_t its = 0, best = 0;
+    ccm_sim3_solver_state(solver, 0, &its, &best, nullptr, nullptr);
+    mnIterations = its; mnBestInliers = best;
+    bNoMore = no_more != 0;
+    vbInliers = vector<bool>(mN1, false);
+    for (int i = 0; i < mN1; i++) vbInliers[i] = inl[i] != 0;
+    nInliers = n;
+    return found ? T12 : cv::Mat();
+}
+
+cv::Mat Sim3Solver::find(vector<bool> &vbInliers12, int &nInliers)
+{
+    bool bFlag;
+    return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers);              // :193-197
+}
+
+cv::Mat Sim3Solver::GetEstimatedRotation()
+{
+    ccm_shim::Sim3SolverSide& S = ccm_shim::side_of(this);
+    cv::Mat R(3, 3, CV_32F);
+    if (S.solver && ccm_sim3_solver_estimate(S.solver, 0, R.ptr<float>(), nullptr, nullptr) == CCM_OK) return R;
+    if (!S.have_estimate) return cv::Mat();                                   // mBestRotation before any hypothesis
+    for (int k = 0; k < 9; k++) R.ptr<float>()[k] = S.R[k];
+    return R;
+}
+
+cv::Mat Sim3Solver::GetEstimatedTranslation()
+{
+    ccm_shim::Sim3SolverSide& S = ccm_shim::side_of(this);
+    cv::Mat t(3, 1, CV_32F);
+    if (S.solver && ccm_sim3_solver_estimate(S.solver, 0, nullptr, t.ptr<float>(), nullptr) == CCM_OK) return t;
+    if (!S.have_estimate) return cv::Mat();
+    for (int k = 0; k < 3; k++) t.ptr<float>()[k] = S.t[k];
+    return t;
+}
+
+float Sim3Solver::GetEstimatedScale()
+{
+    ccm_shim::Sim3SolverSide& S = ccm_shim::side_of(this);
+    float s = S.s;
+    if (S.solver) ccm_sim3_solver_estimate(S.solver, 0, nullptr, nullptr, &s);
+    return s;
+}
+
+}  // namespace cslam
