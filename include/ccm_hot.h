@@ -158,6 +158,10 @@ int ccm_descriptor_distance(const uint8_t* a, const uint8_t* b);
 int ccm_hamming_match(ccm_ctx*, const uint8_t* q, int nq, const uint8_t* t, int nt, int n_pairs,
                       const int32_t* nq_n, const int32_t* nt_n,
                       int32_t* best_idx, int32_t* best_dist, int32_t* second_dist);
+/* Test tap of the matcher's FP4 matrix-core tile: a and b are 32 descriptors (32 x 32 bytes) each, out[32 * i + j] =
+ * row_c[i] - 4096 * (number of bits a[i] and b[j] have in common), computed by the expansion to e2m1 operands and the
+ * block-scaled matrix instructions the brute-force kernel uses.  Synchronises internally. */
+int ccm_debug_fp4_tile(ccm_ctx*, const uint8_t* a, const uint8_t* b, const float* row_c, float* out);
 /* Same on device pointers (descriptor strides in rows), asynchronous.  q_dev and t_dev must be 16-byte aligned and
  * nt <= 65535 (CCM_E_ARG otherwise). */
 int ccm_hamming_match_dev(ccm_ctx*, const uint8_t* q_dev, int nq, size_t q_pair_stride,

@@ -12,6 +12,7 @@ void match_launch_bf(hipStream_t, const uint8_t* q, long long q_pair_bytes, cons
                      unsigned* part_best, int* part_second, int* bi, int* bd, int* sd);
 void match_launch_ranges(hipStream_t, const uint8_t* d1, const uint8_t* d2, const int* order2, const int* start,
                          const int* len, const long long* off, int n1, unsigned short* dist);
+void match_launch_fp4_tile(hipStream_t, const unsigned* a, const unsigned* b, const float* c, float* out);
 struct BowDev {                                  // must match match_kernels.hip
     int n_groups, n1;
     const int* ga; const int* gae; const int* gb; const int* gbe;
@@ -80,7 +81,8 @@ int ccm_hamming_match_dev(ccm_ctx* c, const uint8_t* q_dev, int nq, size_t q_pai
         // Few pairs cannot fill 256 CUs with one workgroup each: split the train rows of a pair over several
         // workgroups (exact merge afterwards) until there are about four workgroups per CU.
         static const int env_split = getenv("CCM_BF_SPLIT") ? atoi(getenv("CCM_BF_SPLIT")) : 0;
-        // default: the matrix-core kernel (variant 3) while its per-train table fits LDS (nt <= 2048), else the VALU kernel
+        // default: the matrix-core kernel (variant 3; 4 / 5 force its int8 / FP4 form) while its per-train table fits LDS (nt <= 2048),
+        // else the VALU kernel
         static const int variant = getenv("CCM_BF_VARIANT") ? atoi(getenv("CCM_BF_VARIANT")) : 3;
         int n_split = env_split > 0 ? env_split : 1;
         if (env_split <= 0) while (n_split < 8 && (long long)n_pairs * n_split < 1024 && nt / (n_split * 2) >= 128) n_split *= 2;
@@ -123,6 +125,24 @@ int ccm_hamming_match(ccm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
         CCM_HIP(c, hipMemcpyAsync(best_idx, M.bi.p, ob, hipMemcpyDeviceToHost, c->stream));
         CCM_HIP(c, hipMemcpyAsync(best_dist, M.bd.p, ob, hipMemcpyDeviceToHost, c->stream));
         CCM_HIP(c, hipMemcpyAsync(second_dist, M.sd.p, ob, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipStreamSynchronize(c->stream));
+        return CCM_OK;
+    });
+}
+
+int ccm_debug_fp4_tile(ccm_ctx* c, const uint8_t* a, const uint8_t* b, const float* row_c, float* out)
+{
+    return ccm_guard(c, "ccm_debug_fp4_tile", [&]() -> int {
+        if (!c) return CCM_E_ARG;
+        if (!a || !b || !row_c || !out) return ccm_fail(c, CCM_E_ARG, "bad FP4 tile arguments");
+        CCM_HIP(c, hipSetDevice(c->device));
+        MatchState& M = *match_state(c);
+        int rc;
+        if ((rc = ccm_upload(c, M.q, a, 1024, c->stream)) || (rc = ccm_upload(c, M.t, b, 1024, c->stream)) || (rc = ccm_upload(c, M.bd, row_c, 128, c->stream))) return rc;
+        CCM_RESERVE(c, M.sd, 4096);
+        match_launch_fp4_tile(c->stream, M.q.as<unsigned>(), M.t.as<unsigned>(), M.bd.as<float>(), M.sd.as<float>());
+        CCM_HIP(c, hipGetLastError());
+        CCM_HIP(c, hipMemcpyAsync(out, M.sd.p, 4096, hipMemcpyDeviceToHost, c->stream));
         CCM_HIP(c, hipStreamSynchronize(c->stream));
         return CCM_OK;
     });

@@ -1,5 +1,6 @@
 // match_kernels.hip -- 256-bit Hamming matching on CDNA4.
-//   k_hamming_mfma    brute-force best / second-best per query on the matrix cores (<= 2048 train rows per pair)
+//   k_hamming_mfma    brute-force best / second-best per query on the matrix cores (<= 2048 train rows per pair): bits as FP4
+//                     operands of the block-scaled matrix instruction (ships), or as int8 (CCM_BF_VARIANT=4)
 //   k_hamming_bf      the same on the vector ALU (any size): inner loop of ORBmatcher::SearchByBoW,
 //                     cslam/src/ORBmatcher.cpp:224-245, with every feature in one vocabulary node
 //   k_hamming_ranges  distances of each side-1 feature to its vocabulary node's side-2 features
@@ -103,49 +104,76 @@ __global__ __launch_bounds__(THREADS) void k_hamming_bf(
 // ------------------------------------------------------------------------------------------------
 // k_hamming_mfma: the same best / second-best search on the matrix cores.
 //   hamming(a, b) = popc(a) + popc(b) - 2 <a, b>   with <a, b> the dot product of the 0/1 bit vectors,
-// so a 32 x 32 block of distances is eight v_mfma_i32_32x32x32_i8 (K = 256 bits) on operands whose bits are
-// expanded to bytes: train rows to 0/32, query columns to 0/-128, so that a common bit adds -4096 = -(2 << 11).
+// so a 32 x 32 block of distances is a 32 x 32 x 256 matrix product on operands whose bits are expanded to numbers the matrix
+// cores take, scaled so that a common bit adds -4096 = -(2 << 11) to the accumulator.  Two forms of the product:
+//   FP4  (ships)  four v_mfma_scale_f32_32x32x64_f8f6f4 per tile.  A bit becomes an e2m1 nibble: train rows 0 / +1.0 (0b0010),
+//                 query columns 0 / -1.0 (0b1010), both with the E8M0 block scale 2^6 (byte 133).  The accumulator is f32; every
+//                 key below is an integer under 2^24 and every product a multiple of 4096, so every partial sum is exact in
+//                 whatever order the hardware adds.  Half the matrix-core cycles, operand registers and LDS of the int8 form.
+//   int8          eight v_mfma_i32_32x32x32_i8 per tile on bytes: train rows 0 / 32, query columns 0 / -128.
 // Layout: A operand = 32 train rows, B operand = 32 query columns.  C/D puts column j = lane & 31 on the lane and
 // rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) in its 16 registers, i.e. a lane sees ONE query and 16 trains per
 // tile, so the running (best, second) of that query are two registers per lane.  The accumulator of the first k-step
 // is preloaded (C operand) with the row word ((popc(train) + HM_BIAS) << 11) | train index, so the matrix cores
-// deliver the finished signed key
+// deliver the finished key
 //   ((popc(train) - 2 <a, b> + HM_BIAS) << 11) | train index
 // -- popc(query) is constant per lane and added at the end -- and the fold is  second = med3(best, second, key);
 // best = min(best, key): two VALU instructions per distance instead of ~18, the rest is MFMA.
-// A/B fragments: lane (h = lane >> 5, r = lane & 31) supplies the 16 bytes of k-step s from bits [32 s + 16 h,
-// 32 s + 16 h + 16) of its row / column; A and B use the same k assignment, which is all the dot product needs.
-// One workgroup = 4 waves x 64 queries; the train fragments of a 32-train tile (8 KiB) are expanded once per
+// A/B fragments: lane (h = lane >> 5, r = lane & 31) supplies to k-step s the bits [128 h + 32 s, 128 h + 32 s + 32) of its row /
+// column as 32 nibbles (FP4), or the bits [32 s + 16 h, 32 s + 16 h + 16) as 16 bytes (int8); A and B use the same k assignment,
+// which is all the dot product needs.
+// One workgroup = 4 waves x 64 queries; the train fragments of a 32-train tile (4 KiB FP4, 8 KiB int8) are expanded once per
 // workgroup into LDS (double-buffered) and read back as ds_read_b128.
 typedef int hm_v4i __attribute__((ext_vector_type(4)));
+typedef int hm_v8i __attribute__((ext_vector_type(8)));
 typedef int hm_v16i __attribute__((ext_vector_type(16)));
+typedef float hm_v16f __attribute__((ext_vector_type(16)));
+// Launch geometry, measured for both forms (ms per launch at 255 pairs / at 10 k pairs, 1000 x 1000 descriptors per pair):
+//   int8  (CB, waves) at 10 k pairs: (2,4) 2.55 ms, (1,8) 2.72, (1,4) 3.09, (2,8) 3.13, (4,4) 8.94 (spills); 4 workgroups per CU 2.32, 3 -> 2.48
+//   FP4   (CB 2, 4 workgroups per CU) 0.048 / 1.49;  (CB 2, 5 per CU: 93 registers) 0.048 / 1.50;  (CB 1, 8 per CU: 59 registers) 0.059 / 1.86;
+//         (CB 2, 6 per CU) spills.  int8 on the same box: 0.083 / 2.16.  More resident waves buy nothing: both forms keep (2, 4, 4).
 #ifndef HM_CB
-#define HM_CB 2                  // 32-query column blocks per wave; measured (CB, waves) at 10 k pairs: (2,4) 2.55 ms,
-                                 // (1,8) 2.72, (1,4) 3.09, (2,8) 3.13, (4,4) 8.94 (spills)
+#define HM_CB 2                  // 32-query column blocks per wave
 #endif
 #ifndef HM_WAVES
 #define HM_WAVES 4
 #endif
 #ifndef HM_TT
-#define HM_TT 1                  // 32-train tiles staged per barrier; measured at 10 k pairs: 1 -> 2.34 ms, 2 -> 2.32, 4 (2 WG/CU) -> 2.77
+#define HM_TT 1                  // 32-train tiles staged per barrier; measured (int8) at 10 k pairs: 1 -> 2.34 ms, 2 -> 2.32, 4 (2 WG/CU) -> 2.77
 #endif
 #ifndef HM_WG_PER_CU
-#define HM_WG_PER_CU 4           // measured at 10 k pairs: 4 -> 2.32 ms, 3 -> 2.48 ms
+#define HM_WG_PER_CU 4
 #endif
 #define HM_QW (32 * HM_CB)       // queries per wave
 #define HM_TPB (64 * HM_WAVES)
-#define HM_SENT 0x3FFFFFFF       // key of "no train": larger than every real key
 #define HM_MAX_NT 2048           // train rows whose row words fit the LDS table (the launcher falls back beyond)
-
-// median of three keys.  The compiler has no integer med3 pattern for variables, but every key is a positive normal
-// float when read as one -- (hamming - popc(query) + HM_BIAS) << 11 | index with the distance field in [4096, 4864],
-// HM_SENT = 0x3FFFFFFF -- and positive floats order like their bit patterns, so v_med3_f32 returns the same register.
 #define HM_BIAS 4352
 #define HM_IDX_BITS 11           // train index field of a key (HM_MAX_NT = 2048 rows)
-__device__ __forceinline__ int hm_med3(int a, int b, int c)
-{
-    return __float_as_int(__builtin_amdgcn_fmed3f(__int_as_float(a), __int_as_float(b), __int_as_float(c)));
-}
+#define HM_SCALE 0x85858585      // E8M0 2^(133 - 127) = 64 in every byte: +1.0 * 64 * -1.0 * 64 = -(2 << HM_IDX_BITS)
+
+// What differs between the two forms: the key type (= accumulator element), the key of "no train" (larger than every real key, never
+// modified because the fragments of rows past the live count are zero) and the k-steps per tile.
+template <bool FP4> struct HmForm;
+template <> struct HmForm<false> {
+    typedef int key; typedef hm_v16i acc;
+    static constexpr int KS = 8;
+    static __device__ __forceinline__ int sent() { return 0x3FFFFFFF; }
+};
+template <> struct HmForm<true> {
+    typedef float key; typedef hm_v16f acc;
+    static constexpr int KS = 4;
+    static __device__ __forceinline__ float sent() { return 16777216.0f; }      // 2^24: the largest key is (256 + HM_BIAS) << 11 | 2047 < 2^24
+};
+
+// median of three keys.  The compiler has no integer med3 pattern for variables, but every int8 key is a positive normal
+// float when read as one -- (hamming - popc(query) + HM_BIAS) << 11 | index with the distance field in [4096, 4864],
+// sentinel 0x3FFFFFFF -- and positive floats order like their bit patterns, so v_med3_f32 returns the same register.
+// The FP4 keys are floats to begin with.
+__device__ __forceinline__ float hm_med3(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
+__device__ __forceinline__ int hm_med3(int a, int b, int c) { return __float_as_int(hm_med3(__int_as_float(a), __int_as_float(b), __int_as_float(c))); }
+// the smaller of two keys.  Floats: positive, so min(a, b) = med3(a, b, 0) -- one v_med3_f32 with an inline constant
+__device__ __forceinline__ float hm_min(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, 0.0f); }
+__device__ __forceinline__ int hm_min(int a, int b) { return min(a, b); }
 
 __device__ __forceinline__ hm_v4i hm_expand16(unsigned hw, int shift)
 {
@@ -159,23 +187,55 @@ __device__ __forceinline__ hm_v4i hm_expand16(unsigned hw, int shift)
     v.z = (int)(__umul24((hs >> 8) & nm, 0x204081u) & bm); v.w = (int)(__umul24((hs >> 12) & nm, 0x204081u) & bm);
     return v;
 }
+// 8 bits -> 8 e2m1 nibbles: bit i goes to bit 4 i in three mask-and-shift steps, then times `one`: 2 = 0b0010 = +1.0 (trains),
+// 10 = 0b1010 = -1.0 (queries)
+__device__ __forceinline__ int hm_nibbles8(unsigned b, unsigned one)
+{
+    unsigned x = (b | (b << 12)) & 0x000F000Fu;
+    x = (x | (x << 6)) & 0x03030303u;
+    x = (x | (x << 3)) & 0x11111111u;
+    return (int)(x * one);
+}
+__device__ __forceinline__ hm_v4i hm_expand32_fp4(unsigned w, unsigned one)
+{
+    hm_v4i v;
+    v.x = hm_nibbles8(w & 255u, one); v.y = hm_nibbles8((w >> 8) & 255u, one);
+    v.z = hm_nibbles8((w >> 16) & 255u, one); v.w = hm_nibbles8(w >> 24, one);
+    return v;
+}
+// one k-step of a tile: acc = A x B + c
+__device__ __forceinline__ hm_v16i hm_mfma(const hm_v4i& a, const hm_v4i& b, const hm_v16i& c)
+{
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ hm_v16f hm_mfma(const hm_v4i& a, const hm_v4i& b, const hm_v16f& c)
+{
+    // cbsz 4 / blgp 4: both operands FP4 (the low four of the eight operand registers)
+    const hm_v8i a8 = { a.x, a.y, a.z, a.w, 0, 0, 0, 0 }, b8 = { b.x, b.y, b.z, b.w, 0, 0, 0, 0 };
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, (int)HM_SCALE, 0, (int)HM_SCALE);
+}
 
 // 4 workgroups per CU (<= 128 registers per lane): 255 pairs x 4 live query blocks = 1020 workgroups fit in ONE round
+template <bool FP4>
 __global__ __launch_bounds__(HM_TPB, HM_WG_PER_CU * HM_TPB / 256) void k_hamming_mfma(
     const uint8_t* __restrict__ q, long long q_pair_bytes, const uint8_t* __restrict__ t, long long t_pair_bytes,
     int nq, int nt, const int* __restrict__ nq_n, const int* __restrict__ nt_n, int q_blocks,
     int* __restrict__ best_idx, int* __restrict__ best_dist, int* __restrict__ second_dist)
 {
-    __shared__ hm_v4i frag[2][HM_TT * 8][64];  // [buffer][sub-tile, k-step][lane]: 16 expanded bytes
-    __shared__ __attribute__((aligned(16))) int wall[HM_MAX_NT];   // per train: (popc + HM_BIAS) << 11 | index, HM_SENT past the live count
+    typedef HmForm<FP4> F;
+    typedef typename F::key key_t;
+    typedef typename F::acc acc_t;
+    constexpr int KS = F::KS;                               // k-steps per tile
+    __shared__ hm_v4i frag[2][HM_TT * KS][64];  // [buffer][sub-tile, k-step][lane]: 16 expanded bytes
+    __shared__ __attribute__((aligned(16))) key_t wall[HM_MAX_NT];   // per train: (popc + HM_BIAS) << 11 | index, the sentinel past the live count
     const int pair = blockIdx.x / q_blocks, qblk = blockIdx.x - pair * q_blocks;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, h = lane >> 5, r = lane & 31;
     const int nqp = nq_n ? min(max(nq_n[pair], 0), nq) : nq;
     const int ntp = nt_n ? min(max(nt_n[pair], 0), nt) : nt;
     const unsigned* qp = reinterpret_cast<const unsigned*>(q + (long long)pair * q_pair_bytes);
     const unsigned* tp = reinterpret_cast<const unsigned*>(t + (long long)pair * t_pair_bytes);
-    const int q0 = qblk * (HM_QW * HM_WAVES) + wv * HM_QW;              // this wave's first query
-    if (qblk * (HM_QW * HM_WAVES) >= nqp) {                              // whole block past the live queries: defaults only
+    const int q0 = qblk * (HM_QW * HM_WAVES) + wv * HM_QW;                    // this wave's first query
+    if (qblk * (HM_QW * HM_WAVES) >= nqp) {                                 // whole block past the live queries: defaults only
         for (int i = tid; i < HM_QW * HM_WAVES; i += HM_TPB) {
             const int qi = qblk * (HM_QW * HM_WAVES) + i;
             if (qi < nq) { const long long o = (long long)pair * nq + qi; best_idx[o] = -1; best_dist[o] = 256; second_dist[o] = 256; }
@@ -183,87 +243,98 @@ __global__ __launch_bounds__(HM_TPB, HM_WG_PER_CU * HM_TPB / 256) void k_hamming
         return;
     }
 
-    // ---- B fragments of the wave's 64 queries (0 / -1 bytes) and their popcounts, kept in registers
-    hm_v4i bq[HM_CB][8];
+    // ---- B fragments of the wave's queries (0 / -1.0 nibbles, or 0 / -128 bytes) and their popcounts, kept in registers
+    hm_v4i bq[HM_CB][KS];
     int pa[HM_CB];
 #pragma unroll
     for (int cb = 0; cb < HM_CB; cb++) {
         const int qi = q0 + 32 * cb + r;
-        unsigned d[8];
-        int pc = 0;
+        if constexpr (FP4) {
+            // the lane's half of the row is all it expands; the other half's popcount comes from the partner lane
+            const uint4 d = qi < nqp ? reinterpret_cast<const uint4*>(qp + 8 * (long long)qi)[h] : make_uint4(0, 0, 0, 0);
+            const int pc = __popc(d.x) + __popc(d.y) + __popc(d.z) + __popc(d.w);
+            pa[cb] = pc + __shfl_xor(pc, 32, 64);
+            bq[cb][0] = hm_expand32_fp4(d.x, 10u); bq[cb][1] = hm_expand32_fp4(d.y, 10u);
+            bq[cb][2] = hm_expand32_fp4(d.z, 10u); bq[cb][3] = hm_expand32_fp4(d.w, 10u);
+        } else {
+            unsigned d[8];
+            int pc = 0;
 #pragma unroll
-        for (int s = 0; s < 8; s++) { d[s] = qi < nqp ? qp[8 * (long long)qi + s] : 0u; pc += __popc(d[s]); }
-        pa[cb] = pc;
+            for (int s = 0; s < 8; s++) { d[s] = qi < nqp ? qp[8 * (long long)qi + s] : 0u; pc += __popc(d[s]); }
+            pa[cb] = pc;
 #pragma unroll
-        for (int s = 0; s < 8; s++) bq[cb][s] = hm_expand16((d[s] >> (16 * h)) & 0xFFFFu, 7);
+            for (int s = 0; s < 8; s++) bq[cb][s] = hm_expand16((d[s] >> (16 * h)) & 0xFFFFu, 7);
+        }
     }
-    int m1[HM_CB], m2[HM_CB];
+    key_t m1[HM_CB], m2[HM_CB];
 #pragma unroll
-    for (int cb = 0; cb < HM_CB; cb++) { m1[cb] = HM_SENT; m2[cb] = HM_SENT; }
+    for (int cb = 0; cb < HM_CB; cb++) { m1[cb] = F::sent(); m2[cb] = F::sent(); }
 
-    // ---- staging of one 32-train tile: thread p expands dword s = p >> 5 of train r = p & 31 into the two
-    //      lane-half fragments of k-step s; threads 0..31 also make the row words.  The raw words are fetched one
-    //      tile ahead (issued before the MFMAs of the current tile) so that no wave waits on a global load.
-    // fragment f of a tile (512 of them): lane half f >> 8, k-step (f >> 5) & 7, train f & 31; thread t owns
-    // fragments t, t + HM_TPB, ... (with 256 threads: both halves of one dword)
+    // ---- staging of one 32-train tile.  The raw words are fetched one tile ahead (issued before the MFMAs of the current tile) so
+    //      that no wave waits on a global load.  A tile has FR fragments of 16 bytes; thread t owns fragments t, t + HM_TPB, ...
+    //      FP4:  fragment f = dword f >> 5 of train f & 31, all of it: k-step (f >> 5) & 3 of lane half f >> 7 (one per thread and tile)
+    //      int8: fragment f = half f >> 8 of dword (f >> 5) & 7 of train f & 31: k-step = the dword (with 256 threads: both halves of one dword)
     // HM_TT tiles are staged per barrier ("group")
-    constexpr int HM_FPT = (512 * HM_TT + HM_TPB - 1) / HM_TPB;
+    constexpr int FR = 64 * KS, HM_FPT = (FR * HM_TT + HM_TPB - 1) / HM_TPB;
     struct Raw { unsigned v[HM_FPT]; };
     auto fetch = [&](int group) {
         Raw x;
 #pragma unroll
         for (int j = 0; j < HM_FPT; j++) {
-            const int fi = tid + j * HM_TPB, sub = fi >> 9, fw = fi & 511;
+            const int fi = tid + j * HM_TPB, sub = fi / FR, fw = fi % FR;
             const int tr = (group * HM_TT + sub) * 32 + (fw & 31);
-            x.v[j] = (fi < 512 * HM_TT && tr < ntp) ? tp[8 * (long long)tr + ((fw >> 5) & 7)] : 0u;
+            x.v[j] = (fi < FR * HM_TT && tr < ntp) ? tp[8 * (long long)tr + ((fw >> 5) & 7)] : 0u;
         }
         return x;
     };
     auto stage = [&](const Raw& x, int buf) {
 #pragma unroll
         for (int j = 0; j < HM_FPT; j++) {
-            const int fi = tid + j * HM_TPB, sub = fi >> 9, fw = fi & 511;
-            if (fi < 512 * HM_TT) frag[buf][8 * sub + ((fw >> 5) & 7)][32 * (fw >> 8) + (fw & 31)] = hm_expand16((x.v[j] >> (16 * (fw >> 8))) & 0xFFFFu, 5);
+            const int fi = tid + j * HM_TPB, sub = fi / FR, fw = fi % FR;
+            if (fi >= FR * HM_TT) continue;
+            if constexpr (FP4) frag[buf][KS * sub + ((fw >> 5) & 3)][32 * (fw >> 7) + (fw & 31)] = hm_expand32_fp4(x.v[j], 2u);
+            else frag[buf][KS * sub + ((fw >> 5) & 7)][32 * (fw >> 8) + (fw & 31)] = hm_expand16((x.v[j] >> (16 * (fw >> 8))) & 0xFFFFu, 5);
         }
     };
     // row words of all trains, once per workgroup
     for (int tr = tid; tr < ((ntp + 31) & ~31); tr += HM_TPB) {
-        int w = HM_SENT;
+        key_t w = F::sent();
         if (tr < ntp) {
             const uint4* d = reinterpret_cast<const uint4*>(tp + 8 * (long long)tr);
             const uint4 d0 = d[0], d1 = d[1];
             const int pb = __popc(d0.x) + __popc(d0.y) + __popc(d0.z) + __popc(d0.w) + __popc(d1.x) + __popc(d1.y) + __popc(d1.z) + __popc(d1.w);
-            w = ((pb + HM_BIAS) << HM_IDX_BITS) | tr;
+            w = (key_t)(((pb + HM_BIAS) << HM_IDX_BITS) | tr);           // (FP4: below 2^24, the conversion is exact)
         }
         wall[tr] = w;
     }
     const int ntiles = (ntp + 31) >> 5;
     const bool wave_live = q0 < nqp;                                    // waves past the live queries only help staging
-    // the sixteen matrix instructions of one tile into `acc`.  The accumulators start from the row words of the tile
+    // the matrix instructions of one tile into `acc`.  The accumulators start from the row words of the tile
     // (C operand of the first k-step: row = train, the same word in every query column), so what comes out IS the key
     //   ((popc(train) + HM_BIAS) << 11 | train) - (2 << 11) <train, query>.
-    auto mma = [&](int tile, int buf, int sub, hm_v16i (&acc)[HM_CB]) {
-        hm_v16i wc;
+    auto mma = [&](int tile, int buf, int sub, acc_t (&acc)[HM_CB]) {
+        typedef key_t key4 __attribute__((ext_vector_type(4)));
+        acc_t wc;
 #pragma unroll
         for (int g = 0; g < 4; g++) {
-            const hm_v4i w4 = *reinterpret_cast<const hm_v4i*>(&wall[32 * tile + 8 * g + 4 * h]);
+            const key4 w4 = *reinterpret_cast<const key4*>(&wall[32 * tile + 8 * g + 4 * h]);
             wc[4 * g] = w4.x; wc[4 * g + 1] = w4.y; wc[4 * g + 2] = w4.z; wc[4 * g + 3] = w4.w;
         }
 #pragma unroll
-        for (int s = 0; s < 8; s++) {
-            const hm_v4i a = frag[buf][8 * sub + s][lane];
+        for (int s = 0; s < KS; s++) {
+            const hm_v4i a = frag[buf][KS * sub + s][lane];
 #pragma unroll
-            for (int cb = 0; cb < HM_CB; cb++) acc[cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[cb][s], s == 0 ? wc : acc[cb], 0, 0, 0);
+            for (int cb = 0; cb < HM_CB; cb++) acc[cb] = hm_mfma(a, bq[cb][s], s == 0 ? wc : acc[cb]);
         }
     };
-    // (best, second) of the lane's query folded over the 16 keys it sees in `acc`: v_med3_f32 + v_min_i32 per key
-    auto fold = [&](const hm_v16i (&acc)[HM_CB]) {
+    // (best, second) of the lane's query folded over the 16 keys it sees in `acc`: v_med3_f32 + a minimum per key
+    auto fold = [&](const acc_t (&acc)[HM_CB]) {
 #pragma unroll
         for (int i = 0; i < 16; i++)
 #pragma unroll
             for (int cb = 0; cb < HM_CB; cb++) {
-                const int kx = acc[cb][i];
-                m2[cb] = hm_med3(m1[cb], m2[cb], kx); m1[cb] = min(m1[cb], kx);
+                const key_t kx = acc[cb][i];
+                m2[cb] = hm_med3(m1[cb], m2[cb], kx); m1[cb] = hm_min(m1[cb], kx);
             }
     };
     const int ngroups = (ntiles + HM_TT - 1) / HM_TT;
@@ -280,7 +351,7 @@ __global__ __launch_bounds__(HM_TPB, HM_WG_PER_CU * HM_TPB / 256) void k_hamming
             for (int sub = 0; sub < HM_TT; sub++) {
                 const int tile = grp * HM_TT + sub;
                 if (tile < ntiles) {
-                    hm_v16i acc[HM_CB];
+                    acc_t acc[HM_CB];
                     mma(tile, buf, sub, acc);
                     fold(acc);
                 }
@@ -291,20 +362,40 @@ __global__ __launch_bounds__(HM_TPB, HM_WG_PER_CU * HM_TPB / 256) void k_hamming
     // ---- the two lane halves saw disjoint trains of the same query: merge, add popc(query), write
 #pragma unroll
     for (int cb = 0; cb < HM_CB; cb++) {
-        const int o1 = __shfl_xor(m1[cb], 32, 64), o2 = __shfl_xor(m2[cb], 32, 64);
-        const int b1 = min(m1[cb], o1);
-        const int b2 = min(max(m1[cb], o1), min(m2[cb], o2));
+        const key_t o1 = __shfl_xor(m1[cb], 32, 64), o2 = __shfl_xor(m2[cb], 32, 64);
+        const key_t b1 = min(m1[cb], o1);
+        const key_t b2 = min(max(m1[cb], o1), min(m2[cb], o2));
         const int qi = q0 + 32 * cb + r;
         if (h == 0 && qi < nq) {
             const long long o = (long long)pair * nq + qi;
             const bool live = qi < nqp;
-            const bool has1 = live && b1 < HM_SENT, has2 = live && b2 < HM_SENT;
-            const int bd = has1 ? (b1 >> HM_IDX_BITS) - HM_BIAS + pa[cb] : 256;
-            best_idx[o] = bd < 256 ? (b1 & ((1 << HM_IDX_BITS) - 1)) : -1;           // the reference starts at 256 and compares with <
+            const bool has1 = live && b1 < F::sent(), has2 = live && b2 < F::sent();
+            const int k1 = (int)b1, k2 = (int)b2;                                     // (FP4: integers below 2^24, exact)
+            const int bd = has1 ? (k1 >> HM_IDX_BITS) - HM_BIAS + pa[cb] : 256;
+            best_idx[o] = bd < 256 ? (k1 & ((1 << HM_IDX_BITS) - 1)) : -1;           // the reference starts at 256 and compares with <
             best_dist[o] = bd;
-            second_dist[o] = has2 ? (b2 >> HM_IDX_BITS) - HM_BIAS + pa[cb] : 256;
+            second_dist[o] = has2 ? (k2 >> HM_IDX_BITS) - HM_BIAS + pa[cb] : 256;
         }
     }
+}
+
+// Known-answer tap of the FP4 tile (ccm_debug_fp4_tile): out[i][j] = 32 x 32 x 256 product of train rows a (32 x 32 bytes) and query
+// rows b through hm_expand32_fp4 and the four matrix instructions exactly as k_hamming_mfma issues them, on top of c[i] in every column.
+__global__ __launch_bounds__(64) void k_fp4_tile(const unsigned* __restrict__ a, const unsigned* __restrict__ b, const float* __restrict__ c,
+                                                 float* __restrict__ out)
+{
+    const int lane = threadIdx.x, h = lane >> 5, r = lane & 31;
+    hm_v16f acc;
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = c[(i & 3) + 8 * (i >> 2) + 4 * h];
+#pragma unroll
+    for (int s = 0; s < 4; s++) acc = hm_mfma(hm_expand32_fp4(a[8 * r + 4 * h + s], 2u), hm_expand32_fp4(b[8 * r + 4 * h + s], 10u), acc);
+#pragma unroll
+    for (int i = 0; i < 16; i++) out[32 * ((i & 3) + 8 * (i >> 2) + 4 * h) + r] = acc[i];
+}
+void match_launch_fp4_tile(hipStream_t s, const unsigned* a, const unsigned* b, const float* c, float* out)
+{
+    hipLaunchKernelGGL(k_fp4_tile, dim3(1), dim3(64), 0, s, a, b, c, out);
 }
 
 // Exact merge of per-split partial results over disjoint, ascending index ranges: the overall best is the
@@ -862,15 +953,21 @@ void match_launch_window_batch(hipStream_t s, const WinGrid* grids, const int* q
     if (nq > 0) hipLaunchKernelGGL(k_window_candidates<true>, dim3((nq + 3) / 4), dim3(256), 0, s, WinGrid{}, grids, q_kf, nq, qx, qy, qr, minl, maxl, qdesc, cap, ci, cd, cn);
 }
 
-// variant: 0 = 512 threads x 2 queries, 1 = 256 x 4, 2 = 1024 x 1 (tuning knob, CCM_BF_VARIANT)
+// variant (CCM_BF_VARIANT): 0 = 512 threads x 2 queries, 1 = 256 x 4, 2 = 1024 x 1 on the vector ALU; 3 = the matrix-core kernel that
+// ships (its FP4 form: faster than int8 at 255 and at 10,000 pairs), 4 = its int8 form, 5 = its FP4 form (3 to 5: up to HM_MAX_NT train
+// rows, the vector-ALU kernel beyond)
 void match_launch_bf(hipStream_t s, const uint8_t* q, long long q_pair_bytes, const uint8_t* t, long long t_pair_bytes,
                      int nq, int nt, int n_pairs, const int* nq_n, const int* nt_n, int n_split, int variant,
                      unsigned* part_best, int* part_second, int* bi, int* bd, int* sd)
 {
-    if (variant == 3 && nt <= HM_MAX_NT) {
+    if (variant >= 3 && variant <= 5 && nt <= HM_MAX_NT) {
         const int q_blocks = (nq + HM_QW * HM_WAVES - 1) / (HM_QW * HM_WAVES);
-        hipLaunchKernelGGL(k_hamming_mfma, dim3(n_pairs * q_blocks), dim3(HM_TPB), 0, s, q, q_pair_bytes, t, t_pair_bytes, nq, nt, nq_n, nt_n,
-                           q_blocks, bi, bd, sd);
+        if (variant == 4)
+            hipLaunchKernelGGL(k_hamming_mfma<false>, dim3(n_pairs * q_blocks), dim3(HM_TPB), 0, s, q, q_pair_bytes, t, t_pair_bytes, nq, nt, nq_n, nt_n,
+                               q_blocks, bi, bd, sd);
+        else
+            hipLaunchKernelGGL(k_hamming_mfma<true>, dim3(n_pairs * q_blocks), dim3(HM_TPB), 0, s, q, q_pair_bytes, t, t_pair_bytes, nq, nt, nq_n, nt_n,
+                               q_blocks, bi, bd, sd);
         return;
     }
     const dim3 grid(n_pairs * n_split);

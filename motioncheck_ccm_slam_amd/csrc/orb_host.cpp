@@ -9,11 +9,11 @@
 
 extern "C" hipError_t orb_upload_pattern();
 size_t orb_octree_lds_bytes(int list_cap);
-void orb_launch_resize(hipStream_t, const OrbGeom&, int level, int dw, int dh, int nframes);
+void orb_launch_resize(hipStream_t, const OrbGeom&, int level, int dw, int dh, int nframes, int* clear_status);
 void orb_launch_score(hipStream_t, const OrbGeom&, int ntiles, int nframes);
 void orb_launch_nms(hipStream_t, const OrbGeom&, const OrbCell*, int ncells, int nframes, unsigned* slots, int* cell_count);
 void orb_launch_fast_cells(hipStream_t, const OrbGeom&, const OrbCell*, const OrbBand*, int nbands, int nframes, size_t lds_bytes,
-                           int surv_cap, unsigned* slots, int* cell_count);
+                           int surv_cap, unsigned* slots, int* cell_count, int* clear_status);
 size_t orb_fast_cells_lds(int pitch, int bh, int surv_cap);
 void orb_launch_octree(hipStream_t, const OrbGeom&, const OrbCell*, int nlevels, int nframes, int list_cap,
                        const unsigned* slots, const int* cell_count, unsigned* keysA, unsigned* keysB,
@@ -321,12 +321,19 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
     const OrbGeom& gd = G;
     const OrbCell* cd = S.cells_dev.as<OrbCell>();
     hipStream_t st = c->stream;
-    if (frame0 == 0) CCM_HIP(c, hipMemsetAsync(S.status.p, 0, 4, st));
-    for (int l = 1; l < G.nlevels; l++) { ProfScope ps(c, CCM_PROF_RESIZE); orb_launch_resize(st, gd, l, G.lv[l].w, G.lv[l].h, nrun); }
+    // The status word is cleared by the call's first chunk only (the chunked host-buffer path accumulates it over its chunks), and by
+    // the first kernel of the chain rather than by a fill dispatch of its own: the first resize, or k_fast_cells for a one-level pyramid.
+    int* clear = frame0 == 0 ? S.status.as<int>() : nullptr;
+    for (int l = 1; l < G.nlevels; l++) {
+        ProfScope ps(c, CCM_PROF_RESIZE);
+        orb_launch_resize(st, gd, l, G.lv[l].w, G.lv[l].h, nrun, clear);
+        clear = nullptr;
+    }
     if (S.fused && !S.bands.empty()) {
         ProfScope ps(c, CCM_PROF_FAST_SCORE);
-        orb_launch_fast_cells(st, gd, cd, S.bands_dev.as<OrbBand>(), (int)S.bands.size(), nrun, S.band_lds, S.surv_cap, S.slots.as<unsigned>(), S.cell_count.as<int>());
+        orb_launch_fast_cells(st, gd, cd, S.bands_dev.as<OrbBand>(), (int)S.bands.size(), nrun, S.band_lds, S.surv_cap, S.slots.as<unsigned>(), S.cell_count.as<int>(), clear);
     } else {
+        if (clear) CCM_HIP(c, hipMemsetAsync(clear, 0, 4, st));          // (one level through the two-kernel FAST path: not worth a kernel argument)
         { ProfScope ps(c, CCM_PROF_FAST_SCORE); orb_launch_score(st, gd, G.ntiles, nrun); }
         if (G.ncells > 0) { ProfScope ps(c, CCM_PROF_CELL_NMS); orb_launch_nms(st, gd, cd, G.ncells, nrun, S.slots.as<unsigned>(), S.cell_count.as<int>()); }
     }

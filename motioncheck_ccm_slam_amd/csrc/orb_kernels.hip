@@ -105,8 +105,11 @@ __device__ __forceinline__ void wave_sum2_dpp(int& x, int& y)
 #ifndef RS_ROWS
 #define RS_ROWS 8                // rows per thread (measured: 4 -> 0.186, 8 -> 0.172, 16 -> 0.260 ms)
 #endif
-__global__ __launch_bounds__(256) void k_pyr_resize(const OrbGeom g, int level)
+// clear_status: the extractor's status word, zeroed by the first thread of the launch that opens a call (nullptr otherwise) -- stream
+// order puts that before every kernel that ORs into the word, and a fill dispatch of its own is saved.
+__global__ __launch_bounds__(256) void k_pyr_resize(const OrbGeom g, int level, int* __restrict__ clear_status)
 {
+    if (clear_status && (blockIdx.x | blockIdx.y | blockIdx.z | threadIdx.x) == 0) *clear_status = 0;
     const OrbLevel& D = g.lv[level];
     const OrbLevel& S = g.lv[level - 1];
     const int lane = threadIdx.x & 63;
@@ -506,9 +509,10 @@ template <class T>
 __device__ __forceinline__ int sel4(int ci, const T (&a)[4]) { return ci == 0 ? (int)a[0] : ci == 1 ? (int)a[1] : ci == 2 ? (int)a[2] : (int)a[3]; }
 template <bool PACKED>
 __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fast_cells(const OrbGeom g, const OrbCell* __restrict__ cells, const OrbBand* __restrict__ bands,
-                                                    unsigned* __restrict__ slots, int* __restrict__ cell_count, int unused_, int abl, int xcd_on)
+                                                    unsigned* __restrict__ slots, int* __restrict__ cell_count, int* __restrict__ clear_status, int abl, int xcd_on)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t fc_smem[];
+    if (clear_status && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) *clear_status = 0;      // as in k_pyr_resize: a one-level pyramid starts here
     int wx, wy;
     xcd_work_item(xcd_on, wx, wy);
     FC_STAMP(0);
@@ -1505,10 +1509,10 @@ extern "C" hipError_t orb_upload_pattern()
 
 size_t orb_octree_lds_bytes(int list_cap) { return (size_t)list_cap * OCT_NODE_LDS + 64 + 4 * (size_t)OCT_LDS_KEYS + 8 * (size_t)list_cap; }
 
-void orb_launch_resize(hipStream_t s, const OrbGeom& g_dev, int level, int dw, int dh, int nframes)
+void orb_launch_resize(hipStream_t s, const OrbGeom& g_dev, int level, int dw, int dh, int nframes, int* clear_status)
 {
     dim3 grid((dw + 255) / 256, (dh + 4 * RS_ROWS - 1) / (4 * RS_ROWS), nframes);
-    hipLaunchKernelGGL(k_pyr_resize, grid, dim3(256), 0, s, g_dev, level);
+    hipLaunchKernelGGL(k_pyr_resize, grid, dim3(256), 0, s, g_dev, level, clear_status);
 }
 void orb_launch_score(hipStream_t s, const OrbGeom& g_dev, int ntiles, int nframes)
 {
@@ -1520,7 +1524,7 @@ void orb_launch_nms(hipStream_t s, const OrbGeom& g_dev, const OrbCell* cells, i
     hipLaunchKernelGGL(k_cell_nms, dim3((ncells + 3) / 4, nframes), dim3(256), 0, s, g_dev, cells, slots, cell_count);
 }
 void orb_launch_fast_cells(hipStream_t s, const OrbGeom& g_dev, const OrbCell* cells, const OrbBand* bands, int nbands, int nframes,
-                           size_t lds_bytes, int surv_cap, unsigned* slots, int* cell_count)
+                           size_t lds_bytes, int surv_cap, unsigned* slots, int* cell_count, int* clear_status)
 {
     static const bool packed = !(getenv("CCM_FC_PACKED") && atoi(getenv("CCM_FC_PACKED")) == 0);
     static const int abl = getenv("CCM_FC_ABL") ? atoi(getenv("CCM_FC_ABL")) : 0;     // timing ablations only (results are wrong)
@@ -1532,8 +1536,8 @@ void orb_launch_fast_cells(hipStream_t s, const OrbGeom& g_dev, const OrbCell* c
     static const size_t lds_min = getenv("CCM_FC_LDS_MIN") ? (size_t)atol(getenv("CCM_FC_LDS_MIN")) : 0;
     if (lds_bytes < lds_min) lds_bytes = lds_min;
     (void)surv_cap;                                          // (rounds 1-2: size of the pooled survivor list)
-    if (packed) hipLaunchKernelGGL(k_fast_cells<true>, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, g_dev, cells, bands, slots, cell_count, 0, abl, xcd_on);
-    else hipLaunchKernelGGL(k_fast_cells<false>, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, g_dev, cells, bands, slots, cell_count, 0, abl, xcd_on);
+    if (packed) hipLaunchKernelGGL(k_fast_cells<true>, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, g_dev, cells, bands, slots, cell_count, clear_status, abl, xcd_on);
+    else hipLaunchKernelGGL(k_fast_cells<false>, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, g_dev, cells, bands, slots, cell_count, clear_status, abl, xcd_on);
 }
 size_t orb_fast_cells_lds(int pitch, int bh, int surv_cap) { return fc_lds_bytes(pitch, bh, surv_cap); }
 void orb_launch_octree(hipStream_t s, const OrbGeom& g_dev, const OrbCell* cells, int nlevels, int nframes, int list_cap,
