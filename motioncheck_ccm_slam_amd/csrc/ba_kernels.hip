@@ -14,6 +14,7 @@
 #include <cstdint>
 #include "ba_math.h"
 #include "ba_types.h"
+#include "ba_launch.h"
 
 __device__ __forceinline__ double wave_sum_d(double v)
 {
@@ -443,7 +444,6 @@ __global__ __launch_bounds__(256) void k_ba_deactivate(BaDev D, const uint8_t* _
 // ---- launchers
 static inline int nblk(long long n, int b) { return (int)((n + b - 1) / b); }
 void ba_launch_pose_rt(hipStream_t s, const BaDev& D) { if (D.P > 0) hipLaunchKernelGGL(k_ba_pose_rt, dim3(nblk(D.P, 256)), dim3(256), 0, s, D); }
-int ba_errors_blocks(const BaDev& D) { return nblk(D.E, 256); }
 void ba_launch_errors(hipStream_t s, const BaDev& D, double hd, double* partial, double* out)
 {
     const int nb = nblk(D.E, 256);
@@ -455,7 +455,6 @@ void ba_launch_errors(hipStream_t s, const BaDev& D, double hd, double* partial,
 #endif
 // lambda > 0: the landmarks' share of the Schur step for that lambda is computed along (MODE 1, or MODE 2 when the caller can do
 // without Hpl); landmarks_only: the rebuild of Hpl after a rejected trial of a MODE 2 iteration
-void ba_launch_lin_pose(hipStream_t s, const BaDev& D, double hd);
 void ba_launch_linearize(hipStream_t s, const BaDev& D, double hd, double lambda, bool keep_hpl, bool landmarks_only)
 {
     const dim3 grid(nblk((long long)BA_LM_LANES * D.L, 256));                                       // a zero-size grid is a launch error
@@ -539,7 +538,7 @@ void ba_launch_update(hipStream_t s, const BaDev& D, double* save_poses, double*
     const int n = D.L > D.nfree ? D.L : D.nfree;
     if (n > 0) hipLaunchKernelGGL(k_ba_update, dim3(nblk(n, 256)), dim3(256), 0, s, D, save_poses, save_points);
 }
-int ba_scale_blocks(const BaDev& D) { return nblk(6LL * D.nfree + 3LL * D.L, 256); }
+static int ba_scale_blocks(const BaDev& D) { return nblk(6LL * D.nfree + 3LL * D.L, 256); }
 // chi2 of the state after the update (-> out[0]) and the trial's gain denominator (-> out[1]); partial: room for both kernels' blocks
 void ba_launch_errors_scale(hipStream_t s, const BaDev& D, double hd, double lambda, int add_pose_lambda, double* partial, double* out)
 {
@@ -547,12 +546,6 @@ void ba_launch_errors_scale(hipStream_t s, const BaDev& D, double hd, double lam
     if (nbe > 0) hipLaunchKernelGGL(k_ba_errors, dim3(nbe), dim3(256), 0, s, D, hd, partial);
     if (nbs > 0) hipLaunchKernelGGL(k_ba_scale, dim3(nbs), dim3(256), 0, s, D, lambda, add_pose_lambda, partial + nbe);
     hipLaunchKernelGGL(k_ba_reduce2, dim3(2), dim3(256), 0, s, (const double*)partial, nbe, out, (const double*)(partial + nbe), nbs, out + 1);
-}
-void ba_launch_scale(hipStream_t s, const BaDev& D, double lambda, int add_pose_lambda, double* partial, double* out)
-{
-    const int nb = ba_scale_blocks(D);
-    if (nb > 0) hipLaunchKernelGGL(k_ba_scale, dim3(nb), dim3(256), 0, s, D, lambda, add_pose_lambda, partial);
-    hipLaunchKernelGGL(k_ba_reduce, dim3(1), dim3(256), 0, s, partial, nb, out, 0);
 }
 void ba_launch_diag(hipStream_t s, const BaDev& D, double* tmp_ll, double* pp_diag, double* out_ll_max)
 {

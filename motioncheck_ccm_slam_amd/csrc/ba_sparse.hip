@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 #include <cstdint>
 #include "ba_types.h"
+#include "ba_launch.h"
 #include "ba_math.h"
 
 // ---------------------------------------------------------------------------------------- structure
@@ -1521,6 +1522,10 @@ int pcg_coarse_agg_keyframes(int nfree) { return PCG_CL * pcg_agg_clusters(nfree
 int pcg_coarse_dim(int nfree) { return PCG_CDOF * pcg_coarse_aggregates(nfree); }
 int pcg_coarse_pitch(int nfree) { return nblk(pcg_coarse_dim(nfree), INV_B) * INV_B; }
 int pcg_coarse_parts(int nfree) { return nblk(pcg_coarse_dim(nfree), 4); }
+// rpart of k_pcg_init / k_pcg_update: PCG_RSLOTS x PCG_CDOF partials per block of PCG_UPD_TPB scalars (two blocks of slack)
+size_t pcg_coarse_rpart_doubles(int nfree) { return ((size_t)(6LL * nfree) / PCG_UPD_TPB + 2) * PCG_RSLOTS * PCG_CDOF; }
+// part: three partial sums per keyframe and per block of PCG_UPD_TPB scalars (four blocks of slack)
+size_t pcg_part_doubles(int nfree) { return ((size_t)nfree + (size_t)(6LL * nfree) / PCG_UPD_TPB + 4) * 3; }
 // Ac = P^T H P as a full (padded) matrix in `Ac`
 void pcg_launch_coarse_mark(hipStream_t s, const int* blk_row, const int* blk_col, int nb, int nfree, uint8_t* aggmap)
 {

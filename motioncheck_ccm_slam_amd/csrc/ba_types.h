@@ -24,7 +24,7 @@ struct BaDev {
     double* Hll; double* bl;       // [L][9], [L][3]
     double* Hpl;                   // [E][18] 6x3 row-major
     double* Dinv;                  // [L][9]
-    double* Hs; double* bs;        // (6 nfree)^2 row-major, upper block triangle; 6 nfree
+    double* bs;                    // [6 nfree] right-hand side of the reduced camera system
     double* x;                     // [6 nfree + 3 L]
     // per LM trial (ba_sparse.hip): Z = Hpl L^-T per edge (L L^T = Hll + lambda I), db = Dinv b_l per landmark, ce = Hpl db per edge
     double* Z; double* db; double* ce;

@@ -1,5 +1,6 @@
 // comm.cpp -- RCCL communicator attached to a context (multi-GPU global BA).
 #include "ccm_internal.h"
+#include "ba_launch.h"
 #include <rccl/rccl.h>
 
 // `ext`: a caller-supplied transport (ccm_comm_attach) used instead of RCCL
@@ -70,7 +71,7 @@ int ccm_comm_destroy(ccm_ctx* c)
 
 }  // extern "C"
 
-// used by ba_host.cpp
+// used by ba_host.cpp (declared in ba_launch.h)
 int comm_ranks(const ccm_ctx* c) { return c->comm ? c->comm->n_ranks : 1; }
 int comm_rank(const ccm_ctx* c) { return c->comm ? c->comm->rank : 0; }
 int comm_allreduce_f64(ccm_ctx* c, double* dev, size_t n, bool max_op)
