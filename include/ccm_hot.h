@@ -583,6 +583,82 @@ int ccm_sim3_solver_state(const ccm_sim3_solver*, int k, int32_t* iterations, in
  * correspondence i at bit i % 64 of word i / 64. */
 int ccm_sim3_solver_hypotheses(const ccm_sim3_solver*, int k, int32_t* sample, int32_t* count, float* rts, uint64_t* mask);
 
+/* ---- Initializer: the monocular two-view initialisation (src/Initializer.cpp, called from Tracking::MonocularInitialization,
+ * src/Tracking.cpp:293-357, between ccm_search_for_initialization and the first ccm_ba_solve).
+ * Initializer::Initialize (:40-117) evaluates mMaxIterations minimal sets of 8 matches twice -- FindHomography (:120-168) and
+ * FindFundamental (:171-219) in two threads, each hypothesis scored over all N matches -- picks a model from the score ratio
+ * (:108-114) and reconstructs the motion from it (ReconstructH :568-728, ReconstructF :466-566), testing 8 or 4 motion hypotheses
+ * with CheckRT (:794-903).  ccm_initialize does the 2 x mMaxIterations hypotheses in one launch and all CheckRT calls in a second
+ * one; the ordered parts (first strictly best score :161-166 / :212-217, the decisions :495-565 / :685-727) are replayed on the host
+ * over the stored results.
+ *
+ * Arithmetic: float storage and float per-match arithmetic in the reference's operation order (Normalize :745-791 with sums in index
+ * order over ALL keypoints of each frame, the rows of ComputeH21 / ComputeF21, CheckHomography, CheckFundamental, CheckRT).  The null
+ * vectors that the reference takes from cv::SVDecomp (9 unknowns, the rank-2 step, Triangulate, the 3x3 SVDs of the reconstruction)
+ * come from a cyclic Jacobi in double on A^T A; cv::SVDecomp, cv::Mat::inv and cv::gemm are not part of the reference tree, so the
+ * contract on H21 / H12 / F21 is a tolerance (DESIGN.md "Initializer"), while the inlier flags, scores and decisions are exact
+ * functions of the matrices the library reports.
+ *
+ * The sign conventions of cv::SVD are not defined by the reference, so the ORDER of the 8 (4) motion candidates may differ from the
+ * reference's.  It cannot change the outcome: in ReconstructF two candidates equal to maxGood make nsimilar > 1, in ReconstructH a
+ * tie makes secondBestGood = bestGood, and both reject.  The contract is on the chosen (R21, t21, points), not on a candidate index. */
+typedef struct {
+    int32_t        n1;              /* mvKeys1.size() */
+    const float*   kp1_xy;          /* [n1][2] mvKeysUn of the reference frame */
+    int32_t        n2;
+    const float*   kp2_xy;          /* [n2][2] mvKeysUn of the current frame */
+    const int32_t* matches12;       /* [n1] index into frame 2, or < 0 (vMatches12); N = number of entries >= 0 */
+    float          fx, fy, cx, cy;  /* mK */
+    float          sigma;           /* mSigma (1.0) */
+    int32_t        max_iterations;  /* mMaxIterations (200) */
+    float          min_parallax;    /* 1.0 (:112) */
+    int32_t        min_triangulated;/* 50 (:112) */
+    /* [max_iterations][8]: the raw results of DUtils::Random::RandomInt(0, vAvailableIndices.size()-1) at :85.  Draw j of a set lies in
+     * [0, N-1-j]; the library turns the draws into match indices by the swap-with-last removal of :86-91.  The random source stays
+     * with the caller (the reference seeds it with SeedRandOnce(0), :76). */
+    const int32_t* draws;
+} ccm_initializer_problem;
+/* Test / diagnostic tap of ccm_initialize; every pointer may be NULL.  `it` runs over the max_iterations sets, words = ceil(N / 64),
+ * match i (in mvMatches12 order: ascending frame-1 index) is bit i % 64 of word i / 64. */
+typedef struct {
+    float*    H21;                  /* [it][9] H21i (:156) */
+    float*    H12;                  /* [it][9] H12i (:157) */
+    float*    F21;                  /* [it][9] F21i (:208) */
+    float*    score_h;              /* [it] currentScore of FindHomography */
+    float*    score_f;              /* [it] currentScore of FindFundamental */
+    uint64_t* mask_h;               /* [it][words] vbCurrentInliers of CheckHomography */
+    uint64_t* mask_f;               /* [it][words] vbCurrentInliers of CheckFundamental */
+    int32_t*  sets;                 /* [it][8] mvSets */
+    /* the reconstruction: 8 (ReconstructH), 4 (ReconstructF) or 0 candidates (none tested: N < 8, no set scored, or the early exit
+     * d1/d2 < 1.00001 || d2/d3 < 1.00001 of :593) */
+    int32_t   n_candidates;
+    float     cand_R[8][9];
+    float     cand_t[8][3];
+    int32_t   cand_n_good[8];       /* nGood of CheckRT */
+    float     cand_parallax[8];     /* parallax of CheckRT, degrees */
+    uint8_t*  cand_flags;           /* [8][N]: bit 0 = the match counts in nGood (vP3D written), bit 1 = vbGood */
+    float*    cand_cos;             /* [8][N] cosParallax where bit 0 is set */
+    float*    cand_p3d;             /* [8][N][3] p3dC1 where bit 0 is set */
+} ccm_initializer_tap;
+typedef struct {
+    int32_t  initialized;           /* the return value of Initialize */
+    int32_t  model;                 /* 0 = ReconstructH ran, 1 = ReconstructF (RH > 0.40 is false, also for RH = NaN when both scores are 0) */
+    float    score_h, score_f;      /* SH, SF */
+    int32_t  best_h, best_f;        /* the sets behind them, -1 if no set scored > 0 */
+    int32_t  n_matches;             /* N */
+    float    R21[9], t21[3];        /* row-major; written when initialized */
+    float*   p3d;                   /* in: [n1][3] caller-allocated; out: vP3D, indexed by frame-1 keypoint */
+    uint8_t* triangulated;          /* in: [n1] caller-allocated; out: vbTriangulated.  Both arrays are cleared first and stay cleared
+                                     * when initialized == 0 */
+    ccm_initializer_tap* tap;       /* in: NULL or a tap to fill */
+} ccm_initializer_result;
+/* One Initializer::Initialize.  N < 8: returns CCM_OK with initialized = 0 and launches nothing (the reference would sample out of
+ * range; its caller guards with nmatches < 100).  A set whose score is not > 0 never becomes the best; if the chosen model has no
+ * best set, initialized = 0.  Errors (CCM_E_ARG: a NULL array, a draw outside [0, N-1-j], a matches12 entry >= n2, max_iterations <
+ * 1) leave every output untouched and name the argument in ccm_last_error.  p3d, triangulated and tap are read before anything is
+ * written, so a result object can be reused. */
+int ccm_initialize(ccm_ctx*, const ccm_initializer_problem*, ccm_initializer_result*);
+
 /* The optimisation inside Optimizer::OptimizeEssentialGraphLoopClosure / OptimizeEssentialGraphMapFusion
  * (src/Optimizer.cpp:1064-1331, :1333-1574): one VertexSim3Expmap per keyframe (sim3 = Scw or the corrected Sim3,
  * :1094-1108; fixed = pLoopKF, :1110), one EdgeSim3 per loop / spanning-tree / covisibility edge built by the caller

@@ -39,6 +39,7 @@ SYMBOLS = [
     "ccm_frame_pose_optimize",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
+    "ccm_initialize",
 ]
 
 
@@ -87,6 +88,25 @@ class Sim3RansacProblem(C.Structure):
                 ("K2", C.c_void_p), ("X1", C.c_void_p), ("X2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
                 ("indices1", C.c_void_p), ("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
                 ("draws", C.c_void_p), ("best_inliers", C.c_void_p)]
+
+
+class InitializerProblem(C.Structure):
+    _fields_ = [("n1", C.c_int32), ("kp1_xy", C.c_void_p), ("n2", C.c_int32), ("kp2_xy", C.c_void_p), ("matches12", C.c_void_p),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("sigma", C.c_float),
+                ("max_iterations", C.c_int32), ("min_parallax", C.c_float), ("min_triangulated", C.c_int32), ("draws", C.c_void_p)]
+
+
+class InitializerTap(C.Structure):
+    _fields_ = [("H21", C.c_void_p), ("H12", C.c_void_p), ("F21", C.c_void_p), ("score_h", C.c_void_p), ("score_f", C.c_void_p),
+                ("mask_h", C.c_void_p), ("mask_f", C.c_void_p), ("sets", C.c_void_p), ("n_candidates", C.c_int32),
+                ("cand_R", C.c_float * 72), ("cand_t", C.c_float * 24), ("cand_n_good", C.c_int32 * 8), ("cand_parallax", C.c_float * 8),
+                ("cand_flags", C.c_void_p), ("cand_cos", C.c_void_p), ("cand_p3d", C.c_void_p)]
+
+
+class InitializerResult(C.Structure):
+    _fields_ = [("initialized", C.c_int32), ("model", C.c_int32), ("score_h", C.c_float), ("score_f", C.c_float),
+                ("best_h", C.c_int32), ("best_f", C.c_int32), ("n_matches", C.c_int32), ("R21", C.c_float * 9), ("t21", C.c_float * 3),
+                ("p3d", C.c_void_p), ("triangulated", C.c_void_p), ("tap", C.POINTER(InitializerTap))]
 
 
 class EssentialGraph(C.Structure):
@@ -208,6 +228,7 @@ def load():
     lib.ccm_sim3_solver_estimate.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.ccm_sim3_solver_state.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_sim3_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
     _lib = lib
     return lib
 

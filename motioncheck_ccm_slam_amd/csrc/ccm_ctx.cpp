@@ -54,6 +54,7 @@ void ccm_destroy(ccm_ctx* c)
     pose_state_free(c->pose);
     sim3_state_free(c->sim3);
     sim3_ransac_state_free(c->sim3_ransac);
+    init_state_free(c->init);
     ess_state_free(c->ess);
     for (ProfLabel& L : c->prof) for (auto& e : L.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (hipStream_t& a : c->aux) if (a) { (void)hipStreamSynchronize(a); (void)hipStreamDestroy(a); a = nullptr; }

@@ -21,6 +21,7 @@ struct CommState;
 struct PoseState;
 struct Sim3State;
 struct Sim3RansacState;
+struct InitState;
 struct EssState;
 struct FrameState;
 
@@ -46,6 +47,7 @@ struct ccm_ctx {
     PoseState* pose = nullptr;
     Sim3State* sim3 = nullptr;
     Sim3RansacState* sim3_ransac = nullptr;   // batched Sim3Solver: staging and device buffers (sim3_ransac_host.cpp)
+    InitState* init = nullptr;                // monocular Initializer: staging and device buffers (init_host.cpp)
     EssState* ess = nullptr;
     FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_host.cpp)
 };
@@ -146,5 +148,6 @@ void comm_state_free(ccm_ctx*);
 void pose_state_free(PoseState*);
 void sim3_state_free(Sim3State*);
 void sim3_ransac_state_free(Sim3RansacState*);
+void init_state_free(InitState*);
 void ess_state_free(EssState*);
 void frame_state_free(ccm_ctx*);                       // also orphans the frames still alive
