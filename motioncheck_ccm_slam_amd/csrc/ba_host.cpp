@@ -5,7 +5,7 @@
 //   SparseOptimizer::optimize            cslam/thirdparty/g2o/g2o/core/sparse_optimizer.cpp:354-419
 //   OptimizationAlgorithmLevenberg::solve  .../core/optimization_algorithm_levenberg.cpp:61-189
 //   BlockSolver<6,3>::buildSystem/solve  .../core/block_solver.hpp:354-486, 502-604
-// The reduced camera system is solved by a dense inverse (in-house block Gauss-Jordan, ba_sparse.hip) for small maps and
+// The reduced camera system is solved by a dense inverse (in-house block Gauss-Jordan, ba_dense.hip) for small maps and
 // by a two-level preconditioned CG on the packed blocks for large ones, in place of LinearSolverEigen's SimplicialLDLT
 // (solvers/linear_solver_eigen.h:106-136): any SPD solve of sufficient accuracy is equivalent up to rounding.  With an RCCL communicator attached (ccm_comm_init) the landmarks are
 // sharded over the ranks and the reduced system is summed with one all-reduce per LM trial.
@@ -111,10 +111,8 @@ struct BaEnv {
     int dense_max;             // CCM_BA_DENSE_MAX: largest reduced system solved densely
     bool want_coarse;          // CCM_PCG_COARSE=0: the cluster level alone
     double pcg_tol;            // CCM_PCG_TOL: overrides ccm_ba_options.pcg_tol when > 0
-    int pipelined;             // CCM_PCG_PIPELINED: test switch, 0 / 1 force, -1 = not set
     bool no_ahead;             // CCM_BA_NO_LOOKAHEAD=1: test / A-B switch
     bool keep_hpl;             // CCM_BA_KEEP_HPL=1: test / A-B switch
-    bool no_small;             // CCM_BA_NO_SMALL_SOLVE=1: test switch
     int reject_at;             // CCM_BA_TEST_REJECT_AT=N: test switch, -1 = not set
 };
 const BaEnv& ba_env()
@@ -128,10 +126,8 @@ const BaEnv& ba_env()
         e.dense_max = num("CCM_BA_DENSE_MAX", 1536);
         e.want_coarse = num("CCM_PCG_COARSE", 1) != 0;
         e.pcg_tol = getenv("CCM_PCG_TOL") ? atof(getenv("CCM_PCG_TOL")) : 0.0;
-        e.pipelined = num("CCM_PCG_PIPELINED", -1);
         e.no_ahead = num("CCM_BA_NO_LOOKAHEAD", 0) != 0;
         e.keep_hpl = num("CCM_BA_KEEP_HPL", 0) != 0;
-        e.no_small = num("CCM_BA_NO_SMALL_SOLVE", 0) != 0;
         e.reject_at = num("CCM_BA_TEST_REJECT_AT", -1);
         return e;
     }();
@@ -489,7 +485,7 @@ int BaCall::reserve_workspace()
     return CCM_OK;
 }
 
-// ---- block-sparse structure of the reduced camera system (once per call; see ba_sparse.hip), and the PCG's buffers
+// ---- block-sparse structure of the reduced camera system (once per call; see ba_structure.hip), and the PCG's buffers
 int BaCall::build_block_structure()
 {
     int rc;
@@ -580,8 +576,8 @@ int BaCall::select_solver()
     // dense solve for small systems (exact, and cheaper than PCG start-up), PCG on the packed blocks otherwise
     use_pcg = n > env.dense_max;
     // (a system small enough for k_dense_small_solve gets its damping there)
-    small_solve = !use_pcg && !env.no_small && n <= dense_small_max();
-    // second preconditioner level (ba_sparse.hip): on for systems with at least 64 coarse unknowns
+    small_solve = !use_pcg && n <= dense_small_max();
+    // second preconditioner level (ba_pcg_precond.hip): on for systems with at least 64 coarse unknowns
     nc = nfree > 0 ? pcg_coarse_dim(nfree) : 0; ncp = nfree > 0 ? pcg_coarse_pitch(nfree) : 0;
     if (use_pcg && env.want_coarse && nc >= 64 && nc <= 2304) {      // beyond: the cubic inversion would outlast an LM trial (more than 24 576 free keyframes)
         if (!S.side) {
@@ -599,10 +595,10 @@ int BaCall::select_solver()
         PC.svec = S.pcg_svec.as<double>();
         PC.cen = PC.svec + 3 * (size_t)nfree;
     }
-    // Which iteration: the pipelined one (two kernels per iteration, ba_sparse.hip) for the tolerances a BA asks for; its recurrences
+    // Which iteration: the pipelined one (two kernels per iteration, ba_ppcg.hip) for the tolerances a BA asks for; its recurrences
     // stall near a relative residual of 1e-9, so a caller that wants more than 1e-7 gets the classic four-kernel iteration.
     pcg_tol = env.pcg_tol > 0 ? env.pcg_tol : (opt->pcg_tol > 0 ? opt->pcg_tol : 1e-6);   // relative residual (default: see ccm_hot.h)
-    pipelined = use_pcg && nfree > 0 && ppcg_supported(nfree) && (env.pipelined >= 0 ? env.pipelined != 0 : pcg_tol >= 1e-7);
+    pipelined = use_pcg && nfree > 0 && ppcg_supported(nfree) && pcg_tol >= 1e-7;
     if (pipelined) {
         CCM_RESERVE(c, S.pcg_hf, 36 * 2 * (size_t)nb * 8 + 64); CCM_RESERVE(c, S.pcg_ecol, 2 * (size_t)nb * 4 + 64);
         CCM_RESERVE(c, S.pcg_ca, ppcg_ca_doubles(nfree) * 8 + 64);
@@ -646,7 +642,7 @@ void BaCall::capture_graphs()
     if (PC.Aci && use_pcg) {
         double* Aw = S.pcg_acw.as<double>();
         if (hipStreamBeginCapture(S.side, hipStreamCaptureModeRelaxed) == hipSuccess) {
-            pcg_launch_coarse_invert(S.side, Aw, ncp, Aw + (size_t)ncp * ncp, info_dev + INFO_COARSE);
+            dense_launch_invert(S.side, Aw, ncp, Aw + (size_t)ncp * ncp, info_dev + INFO_COARSE);
             pcg_launch_coarse_mirror(S.side, Aw, ncp);
             hipError_t e1 = hipStreamEndCapture(S.side, &inv_graph);
             hipError_t e2 = e1 == hipSuccess ? hipGraphInstantiate(&inv_exec, inv_graph, nullptr, nullptr, 0) : e1;
@@ -790,7 +786,7 @@ int BaCall::start_inversion(PcgTrial& t)
     hb_in_use = true;
     if (inv_exec) CCM_HIP(c, hipGraphLaunch(inv_exec, S.side));
     else {
-        pcg_launch_coarse_invert(S.side, Aw, ncp, Aw + (size_t)ncp * ncp, info_dev + INFO_COARSE);
+        dense_launch_invert(S.side, Aw, ncp, Aw + (size_t)ncp * ncp, info_dev + INFO_COARSE);
         pcg_launch_coarse_mirror(S.side, Aw, ncp);
     }
     CCM_HIP(c, hipEventRecord(S.ev_inv, S.side));

@@ -7,7 +7,7 @@
 //   k_ba_errors       computeActiveErrors + activeRobustChi2            (sparse_optimizer.cpp:61-114)
 //   k_ba_lin_landmark linearizeOplus + constructQuadraticForm, landmark side: Hll, b_l, Hpl per edge
 //   k_ba_lin_pose     the same, pose side: Hpp, b_p (one workgroup per free pose, fixed summation order)
-//   (Schur complement and reduced solve: ba_sparse.hip)
+//   (Schur complement: ba_schur.hip; reduced solve: ba_pcg*.hip, ba_ppcg.hip, ba_dense.hip)
 //   k_ba_backsub      x_l = Dinv (b_l - Hpl^T x_p)                        (block_solver.hpp:461-481)
 //   k_ba_update       oplus on poses (exp map) and points                 (sparse_optimizer.cpp:422-435)
 #include <hip/hip_runtime.h>
@@ -442,7 +442,6 @@ __global__ __launch_bounds__(256) void k_ba_deactivate(BaDev D, const uint8_t* _
 }
 
 // ---- launchers
-static inline int nblk(long long n, int b) { return (int)((n + b - 1) / b); }
 void ba_launch_pose_rt(hipStream_t s, const BaDev& D) { if (D.P > 0) hipLaunchKernelGGL(k_ba_pose_rt, dim3(nblk(D.P, 256)), dim3(256), 0, s, D); }
 void ba_launch_errors(hipStream_t s, const BaDev& D, double hd, double* partial, double* out)
 {

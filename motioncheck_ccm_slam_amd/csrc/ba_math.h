@@ -136,7 +136,7 @@ BA_HD void ba_inv3(const double* m, double* o)
     o[6] = c02 * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
 }
 
-// ---- per-landmark pieces of the Schur step, shared by ba_sparse.hip (k_sp_dinv, k_sp_edge_y) and the fused tail of k_ba_lin_landmark:
+// ---- per-landmark pieces of the Schur step, shared by ba_schur.hip (k_sp_dinv, k_sp_edge_y) and the fused tail of k_ba_lin_landmark:
 // the same expressions in the same order, so both paths produce the same bits.
 // (ba_inv3 above = Eigen's 3 x 3 inverse by cofactors, what BlockSolver::solve uses for Hll, block_solver.hpp:396)
 // lower Cholesky factor of H + lambda I (upper half of H read): f = { 1/l00, l10, l20, 1/l11, l21, 1/l22 }.

@@ -26,11 +26,11 @@ struct BaDev {
     double* Dinv;                  // [L][9]
     double* bs;                    // [6 nfree] right-hand side of the reduced camera system
     double* x;                     // [6 nfree + 3 L]
-    // per LM trial (ba_sparse.hip): Z = Hpl L^-T per edge (L L^T = Hll + lambda I), db = Dinv b_l per landmark, ce = Hpl db per edge
+    // per LM trial (ba_schur.hip): Z = Hpl L^-T per edge (L L^T = Hll + lambda I), db = Dinv b_l per landmark, ce = Hpl db per edge
     double* Z; double* db; double* ce;
 };
 
-// coarse level of the PCG preconditioner (ba_sparse.hip); Aci == nullptr switches it off
+// coarse level of the PCG preconditioner (ba_pcg_precond.hip); Aci == nullptr switches it off
 struct PcgCoarse {
     double* Aci;                   // [nc][nc] inverse of the coarse matrix, nc = 7 per aggregate
     double* rc;                    // [blocks of k_pcg_update][4][7] block partials of the restricted residual P^T r
@@ -40,7 +40,7 @@ struct PcgCoarse {
     const double* cen;             // [aggregates][3] mean translation of an aggregate's own keyframes
 };
 
-// buffers of the pipelined PCG (ba_sparse.hip, k_ppcg_*)
+// buffers of the pipelined PCG (ba_ppcg.hip, k_ppcg_*)
 struct PpcgBufs {
     double* Hf;                    // [row entries][36] the reduced matrix with both triangles, a row's blocks side by side
     int* ecol;                     // [row entries] block column
