@@ -659,6 +659,87 @@ typedef struct {
  * written, so a result object can be reused. */
 int ccm_initialize(ccm_ctx*, const ccm_initializer_problem*, ccm_initializer_result*);
 
+/* ---- LocalMapping::CreateNewMapPoints (src/Mapping.cpp:284-469), once per keyframe: for each of up to 20 covisible neighbours
+ * SearchForTriangulation (ORBmatcher.cpp:700-852, constructed as ORBmatcher(0.6, false): no rotation histogram), then per matched
+ * pair the parallax test, the linear triangulation, the depth, reprojection and scale tests (:363-448).
+ *
+ * The loop is separable.  vbMatched2 is declared in SearchForTriangulation but never set (:721, :763) and there is no orientation
+ * filter, so the match of feature i1 against neighbour k depends on (k, i1) and on the map-point flags at entry only.  The one
+ * sequential rule -- a feature that received a point with neighbour k is skipped for the neighbours after k -- reduces to: i1 belongs
+ * to the FIRST neighbour, in order, where it has a match that passes every gate; later results for i1 are dropped.
+ * ccm_create_new_map_points matches and triangulates every (k, i1) in parallel and resolves that order on the device: three
+ * launches whatever n_kf is, one upload, one download, one synchronisation.  No candidate distance leaves the device.
+ *
+ * Arithmetic: the match (Hamming distance <= TH_LOW = 50, the epipole test :775-777, CheckDistEpipolarLine :159-176, smallest
+ * distance and the last in node order among equals) is exact: the same float operations as ccm_search_for_triangulation.
+ * Triangulation and gates: float storage in the reference's operation order; the sums of cv::Mat products, dot and norm are taken in
+ * double; the null vector of the float 4x4 comes from a cyclic Jacobi in double on A^T A (cv::SVD is not part of the reference tree),
+ * so the contract on the point is a tolerance against a float64 restatement (DESIGN.md "CreateNewMapPoints") while every gate from
+ * the depth test on is an exact function of the point the library reports.
+ * Deviation: the reference has no test for a non-finite point and would create it (every later comparison with NaN is false); here
+ * such a pair gets CCM_NP_NONFINITE and creates nothing. */
+typedef struct {
+    int32_t        n;                 /* KeyFrame::N */
+    const float*   kp_x;              /* [n] mvKeysUn[i].pt.x */
+    const float*   kp_y;
+    const int32_t* kp_octave;         /* [n] mvKeysUn[i].octave, each in [0, n_levels) */
+    const uint8_t* desc;              /* [n][32] mDescriptors */
+    const int32_t* node;              /* [n] FeatureVector node of feature i, -1 for none, as for ccm_match_bow; below 2^24 */
+    const uint8_t* has_mp;            /* [n] GetMapPoint(i) != null when CreateNewMapPoints is entered */
+    float          fx, fy, cx, cy;
+    const float*   Tcw;               /* [12] rows of [Rcw | tcw] (GetRotation, GetTranslation) */
+    const float*   Ow;                /* [3] GetCameraCenter() as the keyframe stores it */
+    const float*   scale_factors;     /* [n_levels] mvScaleFactors */
+    const float*   level_sigma2;      /* [n_levels] mvLevelSigma2 */
+    int32_t        n_levels;
+} ccm_map_keyframe;
+typedef struct {
+    const ccm_map_keyframe* current;     /* mpCurrentKeyFrame */
+    int32_t                 n_kf;
+    const ccm_map_keyframe* neighbours;  /* [n_kf] GetBestCovisibilityKeyFrames(20), in that order */
+    const float*            F12;         /* [n_kf][9] row-major ComputeF12(current, neighbour k) (Mapping.cpp:549-566) */
+    const float*            epipole;     /* [n_kf][2] ex, ey of ORBmatcher.cpp:708-714 */
+    const float*            median_depth;/* [n_kf] neighbour k's ComputeSceneMedianDepth(2), > 0 */
+} ccm_new_points_problem;
+/* What became of (neighbour k, feature i1).  The gate codes follow the order of Mapping.cpp:363-448. */
+enum {
+    CCM_NP_SKIPPED_KF = 0,    /* baseline / median depth < 0.01 (:319-328): the whole neighbour */
+    CCM_NP_HAS_MP,            /* the feature already holds a map point on entry */
+    CCM_NP_NO_MATCH,          /* no match for (k, i1) */
+    CCM_NP_LOW_PARALLAX,      /* fails cos > 0 && cos < 0.9998 (:373) */
+    CCM_NP_W_ZERO,            /* fourth component of the null vector is 0 (:387) */
+    CCM_NP_NONFINITE,         /* the point has a non-finite coordinate (deviation, see above) */
+    CCM_NP_BEHIND_1,          /* z1 <= 0 (:401) */
+    CCM_NP_BEHIND_2,          /* z2 <= 0 (:405) */
+    CCM_NP_REPROJ_1,          /* reprojection gate in the current keyframe (:418) */
+    CCM_NP_REPROJ_2,          /* reprojection gate in the neighbour (:431) */
+    CCM_NP_ZERO_DIST,         /* dist1 == 0 || dist2 == 0 (:441) */
+    CCM_NP_SCALE,             /* scale consistency (:447) */
+    CCM_NP_OK,                /* the winner for this feature: a row of the result list */
+    CCM_NP_SUPERSEDED         /* passes every gate, but an earlier neighbour already won this feature */
+};
+/* Test / diagnostic tap; every pointer may be NULL.  n1 = current->n. */
+typedef struct {
+    int32_t* match;                   /* [n_kf][n1] the independent match of (k, i1): index into neighbour k, or -1 */
+    uint8_t* status;                  /* [n_kf][n1] CCM_NP_* */
+    float*   x3d_all;                 /* [n_kf][n1][3] the point wherever one was computed (status >= CCM_NP_NONFINITE), else 0 */
+} ccm_new_points_tap;
+/* Caller-allocated arrays with room for current->n rows (a feature wins at most once); rows past n_new are not written.  The order
+ * is the reference's creation order: neighbour by neighbour, idx1 ascending inside a neighbour. */
+typedef struct {
+    int32_t  n_new;                   /* out */
+    int32_t* kf;                      /* [n_new] neighbour index */
+    int32_t* idx1;                    /* [n_new] feature of the current keyframe */
+    int32_t* idx2;                    /* [n_new] feature of neighbour kf */
+    float*   x3d;                     /* [n_new][3] */
+    int32_t* first;                   /* [n_kf+1] the new points of neighbour k are rows first[k] .. first[k+1]-1 */
+    ccm_new_points_tap* tap;          /* in: NULL (production) or a tap to fill */
+} ccm_new_points_result;
+/* Returns n_new (>= 0) or an error.  CCM_E_ARG (a null pointer, n_kf < 0, an octave outside [0, n_levels), a median_depth that is
+ * not positive, a node >= 2^24) names the argument in ccm_last_error and touches no output, the tap included.  n_kf == 0,
+ * current->n == 0 and a neighbour with n == 0 are valid: the call returns 0, or that neighbour contributes nothing. */
+int ccm_create_new_map_points(ccm_ctx*, const ccm_new_points_problem*, ccm_new_points_result*);
+
 /* The optimisation inside Optimizer::OptimizeEssentialGraphLoopClosure / OptimizeEssentialGraphMapFusion
  * (src/Optimizer.cpp:1064-1331, :1333-1574): one VertexSim3Expmap per keyframe (sim3 = Scw or the corrected Sim3,
  * :1094-1108; fixed = pLoopKF, :1110), one EdgeSim3 per loop / spanning-tree / covisibility edge built by the caller

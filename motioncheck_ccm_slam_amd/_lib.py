@@ -39,7 +39,7 @@ SYMBOLS = [
     "ccm_frame_pose_optimize",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
-    "ccm_initialize",
+    "ccm_initialize", "ccm_create_new_map_points",
 ]
 
 
@@ -107,6 +107,31 @@ class InitializerResult(C.Structure):
     _fields_ = [("initialized", C.c_int32), ("model", C.c_int32), ("score_h", C.c_float), ("score_f", C.c_float),
                 ("best_h", C.c_int32), ("best_f", C.c_int32), ("n_matches", C.c_int32), ("R21", C.c_float * 9), ("t21", C.c_float * 3),
                 ("p3d", C.c_void_p), ("triangulated", C.c_void_p), ("tap", C.POINTER(InitializerTap))]
+
+
+class MapKeyframe(C.Structure):
+    _fields_ = [("n", C.c_int32), ("kp_x", C.c_void_p), ("kp_y", C.c_void_p), ("kp_octave", C.c_void_p), ("desc", C.c_void_p),
+                ("node", C.c_void_p), ("has_mp", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("Tcw", C.c_void_p), ("Ow", C.c_void_p), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("n_levels", C.c_int32)]
+
+
+class NewPointsProblem(C.Structure):
+    _fields_ = [("current", C.POINTER(MapKeyframe)), ("n_kf", C.c_int32), ("neighbours", C.POINTER(MapKeyframe)), ("F12", C.c_void_p),
+                ("epipole", C.c_void_p), ("median_depth", C.c_void_p)]
+
+
+class NewPointsTap(C.Structure):
+    _fields_ = [("match", C.c_void_p), ("status", C.c_void_p), ("x3d_all", C.c_void_p)]
+
+
+class NewPointsResult(C.Structure):
+    _fields_ = [("n_new", C.c_int32), ("kf", C.c_void_p), ("idx1", C.c_void_p), ("idx2", C.c_void_p), ("x3d", C.c_void_p),
+                ("first", C.c_void_p), ("tap", C.POINTER(NewPointsTap))]
+
+
+# CCM_NP_* of include/ccm_hot.h: what became of (neighbour k, feature i1) in ccm_create_new_map_points
+NP_STATUS = ("SKIPPED_KF", "HAS_MP", "NO_MATCH", "LOW_PARALLAX", "W_ZERO", "NONFINITE", "BEHIND_1", "BEHIND_2", "REPROJ_1", "REPROJ_2",
+             "ZERO_DIST", "SCALE", "OK", "SUPERSEDED")
 
 
 class EssentialGraph(C.Structure):
@@ -229,6 +254,7 @@ def load():
     lib.ccm_sim3_solver_state.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_sim3_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
+    lib.ccm_create_new_map_points.argtypes = [vp, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)]
     _lib = lib
     return lib
 

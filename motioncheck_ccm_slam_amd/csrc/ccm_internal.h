@@ -22,6 +22,7 @@ struct PoseState;
 struct Sim3State;
 struct Sim3RansacState;
 struct InitState;
+struct MapState;
 struct EssState;
 struct FrameState;
 
@@ -48,6 +49,7 @@ struct ccm_ctx {
     Sim3State* sim3 = nullptr;
     Sim3RansacState* sim3_ransac = nullptr;   // batched Sim3Solver: staging and device buffers (sim3_ransac_host.cpp)
     InitState* init = nullptr;                // monocular Initializer: staging and device buffers (init_host.cpp)
+    MapState* map = nullptr;                  // CreateNewMapPoints: staging and device buffers (map_host.cpp)
     EssState* ess = nullptr;
     FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_host.cpp)
 };
@@ -149,5 +151,6 @@ void pose_state_free(PoseState*);
 void sim3_state_free(Sim3State*);
 void sim3_ransac_state_free(Sim3RansacState*);
 void init_state_free(InitState*);
+void map_state_free(MapState*);
 void ess_state_free(EssState*);
 void frame_state_free(ccm_ctx*);                       // also orphans the frames still alive
