@@ -471,6 +471,101 @@ int ccm_frame_search_by_projection_frame(ccm_ctx*, ccm_frame* cur, const ccm_fra
 int ccm_frame_pose_optimize(ccm_ctx*, ccm_frame* f, int n_mp, const double* mp_xyz, const float* inv_level_sigma2, int n_levels,
                             const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers);
 
+/* ------------------------------------------------------------------ map-point table
+ * The client's map points in device memory, one row per slot; a slot is the id the frame handles carry in mp_id.  The caller
+ * assigns slots and sends rows when the map changes (keyframe rate: creation, culling, bundle adjustment); the per-frame calls below
+ * (frame rate) then upload nothing of the map.  Columns: pos = mWorldPos, normal = mNormalVector, min_dist / max_dist = the raw
+ * mfMinDistance / mfMaxDistance (the factors 0.8 / 1.2 of GetMin/MaxDistanceInvariance, src/MapPoint.cpp, are applied on the
+ * device; PredictScale uses the raw maximum), desc = GetDescriptor(), flags = CCM_MP_*.  A fresh table holds zeros (no slot LIVE).
+ * The table also keeps one `seen` stamp per slot that only ccm_frame_search_local_points writes.
+ * Ownership as for frames: a table belongs to the context that made it (another context: CCM_E_ARG); after ccm_destroy it accepts
+ * only ccm_map_table_destroy and ccm_map_table_capacity, every other call returns CCM_E_STATE. */
+enum { CCM_MP_LIVE = 1,      /* the slot is in use */
+       CCM_MP_BAD = 2,       /* MapPoint::isBad() */
+       CCM_MP_HAS_OBS = 4 }; /* Observations() > 0 */
+typedef struct ccm_map_table ccm_map_table;
+int  ccm_map_table_create(ccm_ctx*, int capacity, ccm_map_table** out);   /* capacity >= 1 */
+void ccm_map_table_destroy(ccm_map_table*);                               /* NULL is a no-op */
+int  ccm_map_table_capacity(const ccm_map_table*);                        /* or CCM_E_ARG for NULL */
+/* Rows to write.  A NULL column keeps that column of the listed slots (bundle adjustment moves positions only, culling changes
+ * flags only).  A slot listed twice takes its last row. */
+typedef struct {
+    int32_t        n;
+    const int32_t* slot;      /* [n], each in [0, capacity) */
+    const float*   pos;       /* [n][3] or NULL */
+    const float*   normal;    /* [n][3] or NULL */
+    const float*   min_dist;  /* [n] or NULL */
+    const float*   max_dist;  /* [n] or NULL */
+    const uint8_t* desc;      /* [n][32] or NULL */
+    const uint8_t* flags;     /* [n] or NULL */
+} ccm_map_update;
+/* One page-locked staging copy and one scatter launch, asynchronous on the context's stream.  A slot outside [0, capacity) returns
+ * CCM_E_ARG with the table untouched (checked on the host before anything is queued).  n == 0 is OK. */
+int ccm_map_table_update(ccm_ctx*, ccm_map_table*, const ccm_map_update*);
+/* The order in which ccm_frame_search_local_points visits the map points: slots [n].  The reference iterates mmpMapPoints, a
+ * std::map keyed by (id, client id) (Map::GetAllMapPoints, src/Map.cpp), and SearchByProjection depends on the order; the caller
+ * sends the list again only when the set of points changes.  slots == NULL: ascending slot over all LIVE slots, what a
+ * single-client map gives (the state of a fresh table).  A duplicate or a slot outside [0, capacity) returns CCM_E_ARG and keeps
+ * the previous order. */
+int ccm_map_table_set_order(ccm_ctx*, ccm_map_table*, int n, const int32_t* slots);
+/* Test tap (synchronises): the rows of slots [n] copied to the host; every output may be NULL.  seen [n] = the slot's stamp. */
+int ccm_map_table_fetch(ccm_ctx*, ccm_map_table*, int n, const int32_t* slot, float* pos, float* normal, float* min_dist,
+                        float* max_dist, uint8_t* desc, uint8_t* flags, int32_t* seen);
+
+/* Tracking::SearchLocalPoints (src/Tracking.cpp:860-922) with Frame::isInFrustum (src/Frame.cpp:139-198), MapPoint::PredictScale
+ * (src/MapPoint.cpp:854-869) and ORBmatcher::SearchByProjection(Frame&, map points, th) (ORBmatcher.cpp:71-148) on a frame handle
+ * and a table.
+ *   First loop (:863-879): a feature whose mp_id names a BAD slot loses it (-1); the other slots the frame holds are stamped as seen
+ *   and are not projected again; occupied[i] = HAS_OBS of the slot feature i keeps.  An mp_id outside the table or naming a slot
+ *   that is not LIVE returns CCM_E_ARG with the handle's ids as they were.
+ *   Second loop (:888-908) over the table's order: entries seen in this call, BAD or not LIVE are skipped; the others are tested as
+ *   isInFrustum does, in the arithmetic of a float cv::Mat (products summed in double, stored as float):
+ *     Pc[r] = (float)((double)R[r][0] P[0] + (double)R[r][1] P[1] + (double)R[r][2] P[2] + (double)t[r]);  reject PcZ < 0
+ *     invz = 1.0f / PcZ;  u = fx * PcX * invz + cx;  v = fy * PcY * invz + cy  (float, left to right)
+ *     reject u < min_x || u > max_x, then v < min_y || v > max_y
+ *     PO = P - Ow (float);  dist = (float)sqrt(sum (double)PO^2);  reject dist < 0.8f * min_dist || dist > 1.2f * max_dist
+ *     viewCos = (float)(sum (double)PO * Pn / (double)dist);  reject viewCos < viewing_cos_limit
+ *     level = ceil(((float)log((double)(max_dist / dist))) / log_scale_factor), clamped to [0, n_levels - 1] (a NaN gives 0)
+ *   The logarithm is the double one rounded to float -- the reference's log(float) is whichever overload its compiler picks.
+ *   The entries in view, in visiting order, become the matcher's queries (radius 2.5 for viewCos > 0.998, else 4.0; times th unless
+ *   th == 1; times scale_factors[level]; levels level-1 .. level) and are matched as ccm_frame_search_by_projection matches them.
+ * Returns nmatches, or an error.  Nothing of the map is uploaded; the call synchronises twice (the in-view count, the result). */
+typedef struct {
+    float Tcw[12];             /* mRcw | mtcw, row-major 3x4 */
+    float Ow[3];               /* mOw */
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y;   /* mnMinX ... mnMaxY */
+    float viewing_cos_limit;   /* 0.5 */
+    float log_scale_factor;    /* mfLogScaleFactor */
+    int32_t n_levels;          /* mnScaleLevels, 1..CCM_MAX_LEVELS */
+    const float* scale_factors;/* [n_levels] mvScaleFactors */
+    float th;                  /* 1, or 5 right after a relocalisation (:913-918) */
+    float nnratio;             /* 0.8 */
+} ccm_slp_params;
+typedef struct {
+    int32_t  n_to_match;       /* out: nToMatch, the number of entries in view */
+    int32_t  in_view_cap;      /* in: room in in_view_slot and the taps; fewer than n_to_match: CCM_E_CAPACITY, the handle's ids as they were */
+    int32_t* in_view_slot;     /* out [n_to_match]: the slots in view, in visiting order (IncreaseVisible, mbTrackInView) */
+    float*   proj_x;           /* optional taps, one value per entry in view: mTrackProjX */
+    float*   proj_y;           /*   mTrackProjY */
+    int32_t* level;            /*   mnTrackScaleLevel */
+    float*   view_cos;         /*   mTrackViewCos */
+    int32_t* match;            /* out [N]: the slot newly assigned to feature i, or -1 */
+    int32_t* mp_id;            /* out [N]: mvpMapPoints after the call (bad ones cleared, new ones set), as the handle holds them */
+    uint8_t* occupied;         /* optional out [N]: feature i holds a map point with observations, after the call */
+} ccm_slp_result;
+int ccm_frame_search_local_points(ccm_ctx*, ccm_frame* f, ccm_map_table* table, const ccm_slp_params*, ccm_slp_result*);
+/* Diagnostic tap: host wall time in milliseconds of the last ccm_frame_search_local_points on this context that reached its first
+ * read-back.  ms[0]: from the entry to the read-back (queueing the first loop, the frustum test and the compaction); ms[1]: the
+ * read-back of the count and the slot list (the copy and the wait for those kernels); ms[2]: the rest (taps, matcher, second
+ * read-back, copies to the caller).  CCM_E_STATE before the first such call. */
+int ccm_frame_search_local_points_timing(ccm_ctx*, double ms[3]);
+/* ccm_frame_pose_optimize with the points taken from the table: pos is widened to double (Converter::toVector3d of a float cv::Mat
+ * is exact), so the results equal ccm_frame_pose_optimize given mp_xyz = (double)pos bit for bit.  An mp_id outside the table or
+ * naming a slot that is not LIVE returns CCM_E_ARG with the outputs untouched. */
+int ccm_frame_pose_optimize_table(ccm_ctx*, ccm_frame* f, ccm_map_table* table, const float* inv_level_sigma2, int n_levels,
+                                  const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers);
+
 /* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:867-1062), next row F4,
  * batched over candidate keyframe pairs: one VertexSim3Expmap, fixed points, EdgeSim3ProjectXYZ +
  * EdgeInverseSim3ProjectXYZ per correspondence with g2o's numeric Jacobians (delta 1e-9) and Huber(sqrt(th2));

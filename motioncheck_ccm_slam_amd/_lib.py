@@ -37,6 +37,8 @@ SYMBOLS = [
     "ccm_frame_create", "ccm_frame_from_extract", "ccm_frame_destroy", "ccm_frame_size", "ccm_frame_set_map_points",
     "ccm_frame_get_map_points", "ccm_frame_debug_grid", "ccm_frame_search_by_projection", "ccm_frame_search_by_projection_frame",
     "ccm_frame_pose_optimize",
+    "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
+    "ccm_map_table_fetch", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points",
@@ -132,6 +134,27 @@ class NewPointsResult(C.Structure):
 # CCM_NP_* of include/ccm_hot.h: what became of (neighbour k, feature i1) in ccm_create_new_map_points
 NP_STATUS = ("SKIPPED_KF", "HAS_MP", "NO_MATCH", "LOW_PARALLAX", "W_ZERO", "NONFINITE", "BEHIND_1", "BEHIND_2", "REPROJ_1", "REPROJ_2",
              "ZERO_DIST", "SCALE", "OK", "SUPERSEDED")
+
+
+MP_LIVE, MP_BAD, MP_HAS_OBS = 1, 2, 4          # CCM_MP_* of include/ccm_hot.h
+
+
+class MapUpdate(C.Structure):
+    _fields_ = [("n", C.c_int32), ("slot", C.c_void_p), ("pos", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p),
+                ("max_dist", C.c_void_p), ("desc", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class SlpParams(C.Structure):
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("viewing_cos_limit", C.c_float),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_void_p), ("th", C.c_float),
+                ("nnratio", C.c_float)]
+
+
+class SlpResult(C.Structure):
+    _fields_ = [("n_to_match", C.c_int32), ("in_view_cap", C.c_int32), ("in_view_slot", C.c_void_p), ("proj_x", C.c_void_p),
+                ("proj_y", C.c_void_p), ("level", C.c_void_p), ("view_cos", C.c_void_p), ("match", C.c_void_p), ("mp_id", C.c_void_p),
+                ("occupied", C.c_void_p)]
 
 
 class EssentialGraph(C.Structure):
@@ -244,6 +267,15 @@ def load():
     lib.ccm_frame_search_by_projection.argtypes = [vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_float, vp]
     lib.ccm_frame_search_by_projection_frame.argtypes = [vp, vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_int, C.c_int, vp]
     lib.ccm_frame_pose_optimize.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_map_table_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    lib.ccm_map_table_destroy.argtypes = [vp]; lib.ccm_map_table_destroy.restype = None
+    lib.ccm_map_table_capacity.argtypes = [vp]
+    lib.ccm_map_table_update.argtypes = [vp, vp, C.POINTER(MapUpdate)]
+    lib.ccm_map_table_set_order.argtypes = [vp, vp, C.c_int, vp]
+    lib.ccm_map_table_fetch.argtypes = [vp, vp, C.c_int] + [vp] * 8
+    lib.ccm_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(SlpParams), C.POINTER(SlpResult)]
+    lib.ccm_frame_search_local_points_timing.argtypes = [vp, vp]
+    lib.ccm_frame_pose_optimize_table.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int]
     lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]
     lib.ccm_sim3_solver_destroy.argtypes = [vp]; lib.ccm_sim3_solver_destroy.restype = None

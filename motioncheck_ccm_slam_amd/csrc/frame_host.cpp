@@ -6,62 +6,10 @@
 //   [ results | inputs ]   one host-to-device copy of the inputs, the kernels, one device-to-host copy of the results, one
 // stream synchronisation.  The results come first so that in/out data (the occupancy flags, the pose) sits at the seam and
 // travels both ways without a second copy.
-#include "ccm_internal.h"
-#include "window_types.h"
+#include "frame_internal.h"
 #include <algorithm>
 #include <climits>
 #include <new>
-
-struct FrameBuildArgs {                          // must match frame_kernels.hip
-    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
-    const ccm_keypoint* kps; const uint8_t* src_desc;
-    int keep_xy;
-    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
-};
-struct PoseGatherArgs {                          // must match frame_kernels.hip
-    int n; const float* kx; const float* ky; const int* oct; const int* mp_id;
-    int n_mp; const double* xyz; const float* inv_sigma2; int n_levels;
-    int* first; double* pts; double* obs; double* info; int* kof; int* status;
-};
-struct PoseDev {                                 // must match pose_kernels.hip
-    int n_frames; double* poses; const double* intr; const int* first; const double* pts; const double* obs;
-    const double* info; double* err; uint8_t* outlier; int* n_inliers;
-};
-void pose_launch(hipStream_t, const PoseDev&);
-size_t frame_build_lds(int cells);
-int frame_launch_build(hipStream_t, const FrameBuildArgs&);
-void frame_launch_prep_last(hipStream_t, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl);
-void frame_launch_scatter_ids(hipStream_t, int n, const int* match, const int* src, const int* status, int* mp_id);
-void frame_launch_pose_gather(hipStream_t, const PoseGatherArgs&);
-void frame_launch_pose_scatter(hipStream_t, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier);
-int orb_last_result(ccm_ctx*, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
-                    int* nlevels);
-
-struct FrameMem { DevBuf buf; };                 // one device block per frame, recycled through the context's pool
-
-// Device layout of a frame (one block, 64-byte aligned segments): kx, ky [n] f32 | octave [n] i32 | angle [n] f32 |
-// desc [n][32] | mp_id [n] i32 | cell_items [n] i32 | cell_first [cols*rows+1] i32.  The first five are what a host upload
-// fills, in one copy.
-struct ccm_frame {
-    ccm_ctx* ctx = nullptr;                      // nullptr once the context is gone
-    FrameMem* mem = nullptr;
-    int n = 0, cols = 0, rows = 0, n_levels = 0; // n_levels: octaves are in [0, n_levels)
-    float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;
-    bool has_angle = false;
-    float* kx = nullptr; float* ky = nullptr; int* oct = nullptr; float* angle = nullptr; uint8_t* desc = nullptr;
-    int* mp_id = nullptr; int* cell_items = nullptr; int* cell_first = nullptr;
-};
-
-struct FrameState {
-    std::vector<FrameMem*> pool;                 // free blocks
-    std::vector<ccm_frame*> live;
-    DevBuf io;                                   // per-call device staging, [results | inputs]
-    uint8_t* host = nullptr; size_t host_cap = 0;  // page-locked, same layout as io
-    hipEvent_t host_free = nullptr; bool pending = false;   // recorded behind the last upload from `host`
-    DevBuf ci, cd, cn, ev, pts, obs, info, err, outl, kof, first;
-};
-
-static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
 
 struct FrameLayout { size_t kx, ky, oct, angle, desc, upload_end, mp_id, items, first, bytes; };
 static FrameLayout frame_layout(int n, int cells)
@@ -75,7 +23,7 @@ static FrameLayout frame_layout(int n, int cells)
     return L;
 }
 
-static FrameState* frame_state(ccm_ctx* c)
+FrameState* frame_state(ccm_ctx* c)
 {
     if (!c->frame) c->frame = new FrameState();
     return c->frame;
@@ -85,6 +33,7 @@ void frame_state_free(ccm_ctx* c)
 {
     FrameState* S = c->frame;
     if (!S) return;
+    mpt_tables_orphan(S);
     for (ccm_frame* f : S->live) {               // frames the caller did not destroy: memory goes, the handle stays (ccm_frame_destroy)
         delete f->mem;
         *f = ccm_frame();
@@ -97,7 +46,7 @@ void frame_state_free(ccm_ctx* c)
 }
 
 // The page-locked staging area with at least `bytes`, free to write (the last upload from it has completed), and io as large.
-static int staging(ccm_ctx* c, size_t bytes, uint8_t** host)
+int frame_staging(ccm_ctx* c, size_t bytes, uint8_t** host)
 {
     FrameState& S = *frame_state(c);
     if (!S.host_free) CCM_HIP(c, hipEventCreateWithFlags(&S.host_free, hipEventDisableTiming));
@@ -118,7 +67,7 @@ static int staging(ccm_ctx* c, size_t bytes, uint8_t** host)
 }
 
 // host[a, b) -> dst (default: io at the same offsets), asynchronous; the staging area stays busy until the copy has run
-static int upload(ccm_ctx* c, size_t a, size_t b, void* dst = nullptr)
+int frame_upload(ccm_ctx* c, size_t a, size_t b, void* dst)
 {
     FrameState& S = *c->frame;
     if (b <= a) return CCM_OK;
@@ -129,7 +78,7 @@ static int upload(ccm_ctx* c, size_t a, size_t b, void* dst = nullptr)
 }
 
 // io[0, b) -> host[0, b), then wait for the stream
-static int download(ccm_ctx* c, size_t b)
+int frame_download(ccm_ctx* c, size_t b)
 {
     FrameState& S = *c->frame;
     CCM_HIP(c, hipMemcpyAsync(S.host, S.io.p, b, hipMemcpyDeviceToHost, c->stream));
@@ -138,7 +87,7 @@ static int download(ccm_ctx* c, size_t b)
     return CCM_OK;
 }
 
-static int fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes)   // rare paths (fallbacks, test taps)
+int frame_fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes)   // rare paths (fallbacks, test taps)
 {
     if (!bytes) return CCM_OK;
     CCM_HIP(c, hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
@@ -222,7 +171,7 @@ static int frame_window(ccm_ctx* c, ccm_frame* f, const WinCall& w, uint8_t* occ
     const size_t o_scale = seg(off, dev_prep ? (size_t)w.last->n_levels * 4 : 0);
     const size_t end = off;
     uint8_t* h = nullptr;
-    int rc = staging(c, end, &h);
+    int rc = frame_staging(c, end, &h);
     if (rc) return rc;
     std::memset(h + o_out, 0xFF, (size_t)n * 4);
     std::memcpy(h + o_flag, occupied, n);
@@ -236,20 +185,36 @@ static int frame_window(ccm_ctx* c, ccm_frame* f, const WinCall& w, uint8_t* occ
     std::memcpy(h + o_act, w.active, nq); std::memcpy(h + o_qflag, w.qflag, nq);
     if (w.qid) std::memcpy(h + o_qid, w.qid, (size_t)nq * 4);
     if (need_qang) std::memcpy(h + o_qang, w.q_angle, (size_t)nq * 4);
-    if ((rc = upload(c, o_out, end))) return rc;
+    if ((rc = frame_upload(c, o_out, end))) return rc;
 
     uint8_t* io = S.io.as<uint8_t>();
-    int* d_status = (int*)(io + o_status); int* d_out = (int*)(io + o_out); uint8_t* d_flag = io + o_flag;
-    const float* d_qx = (const float*)(io + o_qx); const float* d_qy = (const float*)(io + o_qy);
     float* d_qr = (float*)(io + o_qr); int* d_minl = (int*)(io + o_minl); int* d_maxl = (int*)(io + o_maxl);
-    const uint8_t* d_qdesc = io + o_qdesc; const uint8_t* d_act = io + o_act; const uint8_t* d_qflag = io + o_qflag;
+    const uint8_t* d_act = io + o_act;
     const int* d_qid = w.qid ? (const int*)(io + o_qid) : nullptr;
-    const float* d_qang = need_qang ? (const float*)(io + o_qang) : (w.last ? w.last->angle : nullptr);
-    const int* id_src = d_qid ? d_qid : (w.last ? w.last->mp_id : nullptr);
     if (dev_prep) {
         frame_launch_prep_last(st, nq, d_act, w.last->oct, (const float*)(io + o_scale), w.th, d_qr, d_minl, d_maxl);
         CCM_HIP(c, hipGetLastError());
     }
+    WinDevCall D{ w.mode, nq, (const float*)(io + o_qx), (const float*)(io + o_qy), d_qr, d_minl, d_maxl, io + o_qdesc, d_act, io + o_qflag,
+                  d_qid ? d_qid : (w.last ? w.last->mp_id : nullptr),
+                  need_qang ? (const float*)(io + o_qang) : (w.last ? w.last->angle : nullptr),
+                  o_status, o_out, o_flag, res_end, w.nnratio, w.orb_dist, w.check_ori, w.active, w.qflag, w.q_angle, w.last, nullptr, false };
+    return frame_window_dev(c, f, D, occupied, match);
+}
+
+int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied, int32_t* match)
+{
+    FrameState& S = *frame_state(c);
+    hipStream_t st = c->stream;
+    const int n = f->n, nq = w.nq;
+    const size_t o_status = w.o_status, o_out = w.o_out, o_flag = w.o_flag, res_end = w.res_end;
+    uint8_t* io = S.io.as<uint8_t>();
+    int* d_status = (int*)(io + o_status); int* d_out = (int*)(io + o_out); uint8_t* d_flag = io + o_flag;
+    const float* d_qx = w.qx; const float* d_qy = w.qy; const float* d_qr = w.qr; const int* d_minl = w.minl; const int* d_maxl = w.maxl;
+    const uint8_t* d_qdesc = w.qdesc; const uint8_t* d_act = w.act; const uint8_t* d_qflag = w.qflag;
+    const float* d_qang = w.qang; const int* id_src = w.id_src;
+    int rc;
+    w.host_accept = false;
     const WinGrid G{ n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
     auto lists = [&](int cap) -> int {
         CCM_RESERVE(c, S.ci, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cd, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cn, (size_t)nq * 4);
@@ -268,8 +233,9 @@ static int frame_window(ccm_ctx* c, ccm_frame* f, const WinCall& w, uint8_t* occ
             if (match_launch_window_greedy(st, w.mode, A)) return ccm_fail(c, CCM_E_DEVICE, "k_window_greedy: LDS request refused");
             CCM_HIP(c, hipGetLastError());
             frame_launch_scatter_ids(st, n, d_out, id_src, d_status, f->mp_id);
+            if (w.ids_copy) frame_launch_scatter_ids(st, n, d_out, id_src, d_status, w.ids_copy);
             CCM_HIP(c, hipGetLastError());
-            if ((rc = download(c, res_end))) return rc;
+            if ((rc = frame_download(c, res_end))) return rc;
             int status[2];
             std::memcpy(status, S.host + o_status, 8);
             if (status[0] < 0) { cap = status[1]; continue; }                  // rare: a denser window than expected
@@ -282,41 +248,51 @@ static int frame_window(ccm_ctx* c, ccm_frame* f, const WinCall& w, uint8_t* occ
 
     // host acceptance (CCM_WINDOW_HOST_ACCEPT=1, or a frame too large for the single workgroup's LDS): lists to the host, the loops
     // of match_host.cpp on the frame's octaves / angles fetched from the device, the new ids scattered on the device
+    w.host_accept = true;
+    std::vector<uint8_t> act_h, qflag_h;
+    const uint8_t* h_act = w.h_act; const uint8_t* h_qflag = w.h_qflag;
+    if (!h_act) {                                                              // queries made on the device: their flags come back too
+        act_h.resize(nq); qflag_h.resize(nq);
+        if ((rc = frame_fetch(c, act_h.data(), d_act, nq)) || (rc = frame_fetch(c, qflag_h.data(), d_qflag, nq)) ||
+            (rc = frame_fetch(c, occupied, d_flag, n))) return rc;
+        h_act = act_h.data(); h_qflag = qflag_h.data();
+        for (int i = 0; i < n; i++) match[i] = -1;
+    }
     int cap = 64;
     std::vector<int32_t> ci, cd, cn(nq);
     for (;;) {
         if ((rc = lists(cap))) return rc;
         ci.resize((size_t)nq * cap); cd.resize((size_t)nq * cap);
-        if ((rc = fetch(c, cn.data(), S.cn.p, (size_t)nq * 4))) return rc;
+        if ((rc = frame_fetch(c, cn.data(), S.cn.p, (size_t)nq * 4))) return rc;
         int mx = 0;
         for (int v : cn) mx = std::max(mx, v);
         if (mx > cap) { cap = mx; continue; }
-        if ((rc = fetch(c, ci.data(), S.ci.p, ci.size() * 4)) || (rc = fetch(c, cd.data(), S.cd.p, cd.size() * 4))) return rc;
+        if ((rc = frame_fetch(c, ci.data(), S.ci.p, ci.size() * 4)) || (rc = frame_fetch(c, cd.data(), S.cd.p, cd.size() * 4))) return rc;
         break;
     }
     int nmatches;
     if (w.mode == 0) {
         std::vector<int32_t> oct(n);
-        if ((rc = fetch(c, oct.data(), f->oct, (size_t)n * 4))) return rc;
-        nmatches = window_accept_projection_host(nq, w.active, ci.data(), cd.data(), cn.data(), cap, oct.data(), w.qflag, occupied, w.nnratio, match);
+        if ((rc = frame_fetch(c, oct.data(), f->oct, (size_t)n * 4))) return rc;
+        nmatches = window_accept_projection_host(nq, h_act, ci.data(), cd.data(), cn.data(), cap, oct.data(), h_qflag, occupied, w.nnratio, match);
     } else {
         std::vector<float> cur_angle, last_angle;
         if (w.check_ori) {
             cur_angle.resize(n);
-            if ((rc = fetch(c, cur_angle.data(), f->angle, (size_t)n * 4))) return rc;
-            if (w.last) { last_angle.resize(nq); if ((rc = fetch(c, last_angle.data(), w.last->angle, (size_t)nq * 4))) return rc; }
+            if ((rc = frame_fetch(c, cur_angle.data(), f->angle, (size_t)n * 4))) return rc;
+            if (w.last) { last_angle.resize(nq); if ((rc = frame_fetch(c, last_angle.data(), w.last->angle, (size_t)nq * 4))) return rc; }
         }
-        nmatches = window_accept_frame_host(nq, w.active, ci.data(), cd.data(), cn.data(), cap, w.qflag, occupied, w.orb_dist, w.check_ori,
-                                            w.last ? last_angle.data() : w.q_angle, cur_angle.data(), match);
+        nmatches = window_accept_frame_host(nq, h_act, ci.data(), cd.data(), cn.data(), cap, h_qflag, occupied, w.orb_dist, w.check_ori,
+                                            w.last ? last_angle.data() : w.h_qang, cur_angle.data(), match);
     }
     std::memcpy(S.host + o_out, match, (size_t)n * 4);                       // the stream is idle: the staging area is free
-    if ((rc = upload(c, o_out, o_out + (size_t)n * 4))) return rc;
+    if ((rc = frame_upload(c, o_out, o_out + (size_t)n * 4))) return rc;
     frame_launch_scatter_ids(st, n, d_out, id_src, nullptr, f->mp_id);
     CCM_HIP(c, hipGetLastError());
     return nmatches;
 }
 
-static int check_frame(ccm_ctx* c, const ccm_frame* f)
+int frame_check(ccm_ctx* c, const ccm_frame* f)
 {
     if (!f->ctx) return ccm_fail(c, CCM_E_ARG, "frame handle outlived its context");
     if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "frame handle belongs to another context");
@@ -342,7 +318,7 @@ int ccm_frame_create(ccm_ctx* c, const ccm_frame_grid* g, const float* angle, cc
         const int n = g->n;
         const FrameLayout L = frame_layout(n, g->grid_cols * g->grid_rows);
         uint8_t* h = nullptr;
-        int rc = staging(c, L.upload_end, &h);
+        int rc = frame_staging(c, L.upload_end, &h);
         if (rc) return rc;
         std::memcpy(h + L.kx, g->kp_x, (size_t)n * 4); std::memcpy(h + L.ky, g->kp_y, (size_t)n * 4);
         std::memcpy(h + L.oct, g->kp_octave, (size_t)n * 4);
@@ -353,7 +329,7 @@ int ccm_frame_create(ccm_ctx* c, const ccm_frame_grid* g, const float* angle, cc
         if ((rc = frame_alloc(c, n, g->grid_cols, g->grid_rows, &f))) return rc;
         f->n_levels = max_oct + 1; f->has_angle = angle != nullptr;
         f->min_x = g->min_x; f->min_y = g->min_y; f->inv_w = g->inv_w; f->inv_h = g->inv_h;
-        if ((rc = upload(c, 0, L.upload_end, f->mem->buf.p)) || (rc = frame_build(c, f, nullptr, nullptr, 0))) { frame_release(f); return rc; }
+        if ((rc = frame_upload(c, 0, L.upload_end, f->mem->buf.p)) || (rc = frame_build(c, f, nullptr, nullptr, 0))) { frame_release(f); return rc; }
         *out = f;
         return CCM_OK;
     });
@@ -377,20 +353,20 @@ int ccm_frame_from_extract(ccm_ctx* c, int image, int n, const float* kp_x_un, c
         CCM_HIP(c, hipSetDevice(c->device));
         if (n < 0) {
             int32_t cnt = 0;
-            if ((rc = fetch(c, &cnt, counts + image, 4))) return rc;
+            if ((rc = frame_fetch(c, &cnt, counts + image, 4))) return rc;
             n = std::min<int>(cnt, max_per_image);
         }
         const FrameLayout L = frame_layout(n, grid_cols * grid_rows);
         if (kp_x_un) {
             uint8_t* h = nullptr;
-            if ((rc = staging(c, L.oct, &h))) return rc;
+            if ((rc = frame_staging(c, L.oct, &h))) return rc;
             std::memcpy(h + L.kx, kp_x_un, (size_t)n * 4); std::memcpy(h + L.ky, kp_y_un, (size_t)n * 4);
         }
         ccm_frame* f = nullptr;
         if ((rc = frame_alloc(c, n, grid_cols, grid_rows, &f))) return rc;
         f->n_levels = nlevels; f->has_angle = true;
         f->min_x = min_x; f->min_y = min_y; f->inv_w = inv_w; f->inv_h = inv_h;
-        if ((kp_x_un && (rc = upload(c, 0, L.oct, f->mem->buf.p))) ||
+        if ((kp_x_un && (rc = frame_upload(c, 0, L.oct, f->mem->buf.p))) ||
             (rc = frame_build(c, f, kps + (size_t)image * max_per_image, desc + (size_t)image * max_per_image * 32, kp_x_un ? 1 : 0))) {
             frame_release(f); return rc;
         }
@@ -417,10 +393,10 @@ int ccm_frame_set_map_points(ccm_frame* f, const int32_t* mp_id)
         CCM_HIP(c, hipSetDevice(c->device));
         if (!mp_id) { CCM_HIP(c, hipMemsetAsync(f->mp_id, 0xFF, (size_t)f->n * 4, c->stream)); return CCM_OK; }
         uint8_t* h = nullptr;
-        int rc = staging(c, (size_t)f->n * 4, &h);
+        int rc = frame_staging(c, (size_t)f->n * 4, &h);
         if (rc) return rc;
         std::memcpy(h, mp_id, (size_t)f->n * 4);
-        return upload(c, 0, (size_t)f->n * 4, f->mp_id);
+        return frame_upload(c, 0, (size_t)f->n * 4, f->mp_id);
     });
 }
 
@@ -430,7 +406,7 @@ int ccm_frame_get_map_points(ccm_frame* f, int32_t* mp_id)
     ccm_ctx* c = f->ctx;
     if (!c) return CCM_E_STATE;
     CCM_HIP(c, hipSetDevice(c->device));
-    return fetch(c, mp_id, f->mp_id, (size_t)f->n * 4);
+    return frame_fetch(c, mp_id, f->mp_id, (size_t)f->n * 4);
 }
 
 int ccm_frame_debug_grid(ccm_frame* f, int32_t* cell_first, int32_t* cell_items)
@@ -440,10 +416,10 @@ int ccm_frame_debug_grid(ccm_frame* f, int32_t* cell_first, int32_t* cell_items)
     if (!c) return CCM_E_STATE;
     CCM_HIP(c, hipSetDevice(c->device));
     const int cells = f->cols * f->rows;
-    int rc = fetch(c, cell_first, f->cell_first, ((size_t)cells + 1) * 4);
+    int rc = frame_fetch(c, cell_first, f->cell_first, ((size_t)cells + 1) * 4);
     if (rc) return rc;
     if (cell_first[cells] < 0 || cell_first[cells] > f->n) return ccm_fail(c, CCM_E_DEVICE, "grid of %d items for %d features", cell_first[cells], f->n);
-    return fetch(c, cell_items, f->cell_items, (size_t)cell_first[cells] * 4);
+    return frame_fetch(c, cell_items, f->cell_items, (size_t)cell_first[cells] * 4);
 }
 
 // ORBmatcher::SearchByProjection(Frame&, const vector<mpptr>&, th), ORBmatcher.cpp:71-148, frame side from the handle
@@ -454,7 +430,7 @@ int ccm_frame_search_by_projection(ccm_ctx* c, ccm_frame* f, const float* scale_
 {
     RoctxRange roctx_("ccm_frame_search_by_projection");
     if (!c || !f) return CCM_E_ARG;
-    int rc = check_frame(c, f);
+    int rc = frame_check(c, f);
     if (rc) return rc;
     if (n_mp < 0 || (f->n > 0 && (!match || !occupied)) ||
         (n_mp > 0 && (!scale_factors || !in_view || !level || !view_cos || !proj_x || !proj_y || !mp_desc || !mp_has_obs)))
@@ -480,8 +456,8 @@ int ccm_frame_search_by_projection_frame(ccm_ctx* c, ccm_frame* cur, const ccm_f
 {
     RoctxRange roctx_("ccm_frame_search_by_projection_frame");
     if (!c || !cur) return CCM_E_ARG;
-    int rc = check_frame(c, cur);
-    if (rc || (last && (rc = check_frame(c, last)))) return rc;
+    int rc = frame_check(c, cur);
+    if (rc || (last && (rc = frame_check(c, last)))) return rc;
     if (n_last < 0 || (last && n_last != last->n)) return ccm_fail(c, CCM_E_ARG, "n_last must be >= 0 and equal the last frame's N");
     if (check_ori && (!cur->has_angle || (last && !last->has_angle)))
         return ccm_fail(c, CCM_E_ARG, "orientation check against a frame created without angles");
@@ -506,7 +482,7 @@ int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp
 {
     RoctxRange roctx_("ccm_frame_pose_optimize");
     if (!c || !f) return CCM_E_ARG;
-    int rc = check_frame(c, f);
+    int rc = frame_check(c, f);
     if (rc) return rc;
     if (!intr || !pose7 || !n_inliers || n_mp < 0 || (n_mp > 0 && !mp_xyz) || (f->n > 0 && (!outlier || !inv_level_sigma2 || n_levels < 1)))
         return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
@@ -522,10 +498,10 @@ int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp
         const size_t o_intr = seg(off, 32), o_is2 = seg(off, (size_t)n_levels * 4), o_xyz = seg(off, (size_t)n_mp * 24);
         const size_t end = off;
         uint8_t* h = nullptr;
-        if ((rc = staging(c, end, &h))) return rc;
+        if ((rc = frame_staging(c, end, &h))) return rc;
         std::memcpy(h + o_pose, pose7, 56); std::memcpy(h + o_intr, intr, 32);
         std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4); std::memcpy(h + o_xyz, mp_xyz, (size_t)n_mp * 24);
-        if ((rc = upload(c, o_pose, end))) return rc;
+        if ((rc = frame_upload(c, o_pose, end))) return rc;
         CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
         CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
         uint8_t* io = S.io.as<uint8_t>();
@@ -540,7 +516,7 @@ int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp
         CCM_HIP(c, hipGetLastError());
         frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
         CCM_HIP(c, hipGetLastError());
-        if ((rc = download(c, res_end))) return rc;
+        if ((rc = frame_download(c, res_end))) return rc;
         int head[2];
         std::memcpy(head, S.host + o_ninl, 8);
         if (head[1]) return ccm_fail(c, CCM_E_ARG, "a map-point id outside [0, %d) or an octave outside [0, %d)", n_mp, n_levels);

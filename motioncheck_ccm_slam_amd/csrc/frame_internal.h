@@ -1,0 +1,95 @@
+// frame_internal.h -- what the host translation units of the frame handles share: frame_host.cpp (the handles and their matchers)
+// and mpt_host.cpp (the map-point table and the calls that take a frame and a table).  The kernel argument structures must match
+// frame_kernels.hip / pose_kernels.hip.
+#pragma once
+#include "ccm_internal.h"
+#include "window_types.h"
+
+struct FrameBuildArgs {                          // must match frame_kernels.hip
+    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
+    const ccm_keypoint* kps; const uint8_t* src_desc;
+    int keep_xy;
+    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
+};
+struct PoseGatherArgs {                          // must match frame_kernels.hip
+    int n; const float* kx; const float* ky; const int* oct; const int* mp_id;
+    int n_mp; const double* xyz; const float* inv_sigma2; int n_levels;
+    int* first; double* pts; double* obs; double* info; int* kof; int* status;
+};
+struct PoseDev {                                 // must match pose_kernels.hip
+    int n_frames; double* poses; const double* intr; const int* first; const double* pts; const double* obs;
+    const double* info; double* err; uint8_t* outlier; int* n_inliers;
+};
+void pose_launch(hipStream_t, const PoseDev&);
+size_t frame_build_lds(int cells);
+int frame_launch_build(hipStream_t, const FrameBuildArgs&);
+void frame_launch_prep_last(hipStream_t, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl);
+void frame_launch_scatter_ids(hipStream_t, int n, const int* match, const int* src, const int* status, int* mp_id);
+void frame_launch_pose_gather(hipStream_t, const PoseGatherArgs&);
+void frame_launch_pose_scatter(hipStream_t, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier);
+int orb_last_result(ccm_ctx*, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
+                    int* nlevels);
+
+struct FrameMem { DevBuf buf; };                 // one device block per frame, recycled through the context's pool
+
+// Device layout of a frame (one block, 64-byte aligned segments): kx, ky [n] f32 | octave [n] i32 | angle [n] f32 |
+// desc [n][32] | mp_id [n] i32 | cell_items [n] i32 | cell_first [cols*rows+1] i32.  The first five are what a host upload
+// fills, in one copy.
+struct ccm_frame {
+    ccm_ctx* ctx = nullptr;                      // nullptr once the context is gone
+    FrameMem* mem = nullptr;
+    int n = 0, cols = 0, rows = 0, n_levels = 0; // n_levels: octaves are in [0, n_levels)
+    float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;
+    bool has_angle = false;
+    float* kx = nullptr; float* ky = nullptr; int* oct = nullptr; float* angle = nullptr; uint8_t* desc = nullptr;
+    int* mp_id = nullptr; int* cell_items = nullptr; int* cell_first = nullptr;
+};
+
+struct FrameState {
+    std::vector<FrameMem*> pool;                 // free blocks
+    std::vector<ccm_frame*> live;
+    DevBuf io;                                   // per-call device staging, [results | inputs]
+    uint8_t* host = nullptr; size_t host_cap = 0;  // page-locked, same layout as io
+    hipEvent_t host_free = nullptr; bool pending = false;   // recorded behind the last upload from `host`
+    DevBuf ci, cd, cn, ev, pts, obs, info, err, outl, kof, first;
+    std::vector<struct ccm_map_table*> tables;   // map-point tables of this context (mpt_host.cpp)
+    DevBuf slp;                                  // SearchLocalPoints: per-entry temporaries, workgroup counts and offsets
+    double slp_ms[3] = { -1, 0, 0 };             // host wall time of its last call (ccm_frame_search_local_points_timing)
+};
+
+static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
+
+// ccm_destroy: releases the device memory of the map-point tables still alive and orphans their handles (mpt_host.cpp)
+void mpt_tables_orphan(FrameState* S);
+// The context's frame state, created on first use.
+FrameState* frame_state(ccm_ctx* c);
+// The page-locked staging area with at least `bytes`, free to write (the last upload from it has completed), and io as large.
+int frame_staging(ccm_ctx* c, size_t bytes, uint8_t** host);
+// host[a, b) -> dst (default: io at the same offsets), asynchronous; the staging area stays busy until the copy has run
+int frame_upload(ccm_ctx* c, size_t a, size_t b, void* dst = nullptr);
+// io[0, b) -> host[0, b), then wait for the stream
+int frame_download(ccm_ctx* c, size_t b);
+// device -> pageable host, then wait for the stream (rare paths: fallbacks, test taps)
+int frame_fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes);
+// CCM_E_ARG for a handle of another context or one that outlived its context
+int frame_check(ccm_ctx* c, const ccm_frame* f);
+
+// One windowed-matcher call whose queries already lie in device memory: the candidate lists with their capacity retry, the
+// single-workgroup acceptance kernel (or the host acceptance loops) and the scatter of the new map-point ids into the handle.
+// status / out / flag lie in the context's io block at o_status / o_out / o_flag, inside [0, res_end): the results come back
+// with one download of that range.  out must hold -1 and flag the occupancy flags when the call is made.
+struct WinDevCall {
+    int mode, nq;
+    const float* qx; const float* qy; const float* qr; const int* minl; const int* maxl;
+    const uint8_t* qdesc; const uint8_t* act; const uint8_t* qflag;
+    const int* id_src;                           // new id of query q (nullptr: q itself)
+    const float* qang;                           // mode 2 with check_ori: the query side's angles (device)
+    size_t o_status, o_out, o_flag, res_end;
+    float nnratio; int orb_dist, check_ori;
+    // host copies for the host acceptance loops; nullptr: act / qflag / the occupancy flags are fetched from the device there
+    const uint8_t* h_act; const uint8_t* h_qflag; const float* h_qang; const ccm_frame* last;
+    int* ids_copy;                               // optional second target of the id scatter (a copy of mp_id in io), or nullptr
+    bool host_accept;                            // out: the host acceptance loops ran (nothing of [0, res_end) was downloaded)
+};
+// occupied [n] in/out and match [n] out are host arrays; returns nmatches or an error.
+int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied, int32_t* match);

@@ -1,0 +1,374 @@
+// mpt_host.cpp -- C ABI of the map-point table (include/ccm_hot.h "map-point table"): the client's map points in device memory,
+// updated by rows at keyframe rate, and the two per-frame calls of Tracking::TrackLocalMap that work on a frame handle and the
+// table: SearchLocalPoints (src/Tracking.cpp:860-922) and PoseOptimizationClient (src/Optimizer.cpp:215-347).
+//
+// The calls share the frame handles' page-locked staging area and its device twin `io` (frame_internal.h).  SearchLocalPoints
+// uploads nothing: its parameters travel as kernel arguments.  Its result block is
+//   [ status | match | occupied | mp_id | count | in-view slots | proj_x | proj_y | level | view_cos ]
+// of which the first download takes everything up to the count, and the second, behind the matcher, the first four segments again;
+// the slot list and the taps are copied at their exact length once the count is known and land with the second download.
+#include "frame_internal.h"
+#include "mpt_types.h"
+#include <chrono>
+#include <climits>
+
+struct ccm_map_table {
+    ccm_ctx* ctx = nullptr;                      // nullptr once the context is gone
+    int capacity = 0;
+    DevBuf mem;                                  // the columns, one block
+    MptTable T{};
+    DevBuf order; int n_order = 0; bool order_all = true;    // order_all: ascending slot over the LIVE slots
+    int stamp = 0;                               // per-table call counter of SearchLocalPoints: seen[slot] == stamp <=> seen in this call
+    std::vector<uint32_t> gen; std::vector<int32_t> row; uint32_t cur_gen = 0;   // host: last row of a slot within one update / order
+};
+
+void mpt_tables_orphan(FrameState* S)            // ccm_destroy: the memory goes, the handles stay for ccm_map_table_destroy
+{
+    for (ccm_map_table* t : S->tables) {
+        const int cap = t->capacity;
+        *t = ccm_map_table();
+        t->capacity = cap;
+    }
+    S->tables.clear();
+}
+
+static int check_table(ccm_ctx* c, const ccm_map_table* t)
+{
+    if (!t->ctx) return ccm_fail(c, CCM_E_STATE, "map-point table outlived its context");
+    if (t->ctx != c) return ccm_fail(c, CCM_E_ARG, "map-point table belongs to another context");
+    return CCM_OK;
+}
+
+// Marks every slot of list [n] with its last position; CCM_E_ARG for a slot outside the table.  dup: whether a slot occurs twice.
+static int mark_slots(ccm_ctx* c, ccm_map_table* t, int n, const int32_t* list, bool* dup)
+{
+    for (int r = 0; r < n; r++)
+        if (list[r] < 0 || list[r] >= t->capacity) return ccm_fail(c, CCM_E_ARG, "slot %d (entry %d) outside [0, %d)", list[r], r, t->capacity);
+    if (t->gen.empty()) { t->gen.assign(t->capacity, 0); t->row.assign(t->capacity, 0); }
+    if (++t->cur_gen == 0) { std::fill(t->gen.begin(), t->gen.end(), 0); t->cur_gen = 1; }
+    *dup = false;
+    for (int r = 0; r < n; r++) {
+        const int s = list[r];
+        if (t->gen[s] == t->cur_gen) *dup = true;
+        t->gen[s] = t->cur_gen; t->row[s] = r;
+    }
+    return CCM_OK;
+}
+
+extern "C" {
+
+int ccm_map_table_create(ccm_ctx* c, int capacity, ccm_map_table** out)
+{
+    RoctxRange roctx_("ccm_map_table_create");
+    if (out) *out = nullptr;
+    if (!c || !out) return CCM_E_ARG;
+    if (capacity < 1) return ccm_fail(c, CCM_E_ARG, "map-point table capacity %d < 1", capacity);
+    return ccm_guard(c, "ccm_map_table_create", [&]() -> int {
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        const size_t m = (size_t)capacity;
+        size_t off = 0;
+        const size_t o_pos = seg(off, m * 12), o_nrm = seg(off, m * 12), o_min = seg(off, m * 4), o_max = seg(off, m * 4);
+        const size_t o_desc = seg(off, m * 32), o_flags = seg(off, m), o_seen = seg(off, m * 4);
+        ccm_map_table* t = new ccm_map_table();
+        if (t->mem.reserve(off)) { delete t; return ccm_fail(c, CCM_E_NOMEM, "map-point table: device alloc of %zu bytes failed", off); }
+        uint8_t* b = t->mem.as<uint8_t>();
+        if (hipMemsetAsync(b, 0, off, c->stream) != hipSuccess) { (void)hipGetLastError(); delete t; return ccm_fail(c, CCM_E_DEVICE, "map-point table: clearing failed"); }
+        t->ctx = c; t->capacity = capacity;
+        t->T = MptTable{ capacity, (float*)(b + o_pos), (float*)(b + o_nrm), (float*)(b + o_min), (float*)(b + o_max), b + o_desc, b + o_flags,
+                         (int*)(b + o_seen) };
+        S.tables.push_back(t);
+        *out = t;
+        return CCM_OK;
+    });
+}
+
+void ccm_map_table_destroy(ccm_map_table* t)
+{
+    if (!t) return;
+    try {
+        if (t->ctx && t->ctx->frame) {
+            std::vector<ccm_map_table*>& v = t->ctx->frame->tables;
+            v.erase(std::remove(v.begin(), v.end(), t), v.end());
+            (void)hipSetDevice(t->ctx->device);
+        }
+        delete t;                                // hipFree waits for the work still queued on the columns
+    } catch (...) {}
+}
+
+int ccm_map_table_capacity(const ccm_map_table* t) { return t ? t->capacity : CCM_E_ARG; }
+
+int ccm_map_table_update(ccm_ctx* c, ccm_map_table* t, const ccm_map_update* u)
+{
+    RoctxRange roctx_("ccm_map_table_update");
+    if (!c || !t || !u) return CCM_E_ARG;
+    int rc = check_table(c, t);
+    if (rc) return rc;
+    if (u->n < 0 || (u->n > 0 && !u->slot)) return ccm_fail(c, CCM_E_ARG, "bad map-point update (n < 0 or no slot list)");
+    if (u->n == 0) return CCM_OK;
+    return ccm_guard(c, "ccm_map_table_update", [&]() -> int {
+        const size_t n = (size_t)u->n;
+        bool dup = false;
+        if ((rc = mark_slots(c, t, u->n, u->slot, &dup))) return rc;
+        CCM_HIP(c, hipSetDevice(c->device));
+        size_t off = 0;
+        const size_t o_slot = seg(off, n * 4), o_pos = seg(off, u->pos ? n * 12 : 0), o_nrm = seg(off, u->normal ? n * 12 : 0);
+        const size_t o_min = seg(off, u->min_dist ? n * 4 : 0), o_max = seg(off, u->max_dist ? n * 4 : 0);
+        const size_t o_desc = seg(off, u->desc ? n * 32 : 0), o_flags = seg(off, u->flags ? n : 0);
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        int32_t* hs = (int32_t*)(h + o_slot);
+        std::memcpy(hs, u->slot, n * 4);
+        if (dup) for (int r = 0; r < u->n; r++) if (t->row[u->slot[r]] != r) hs[r] = -1;      // the last row of a slot wins
+        if (u->pos) std::memcpy(h + o_pos, u->pos, n * 12);
+        if (u->normal) std::memcpy(h + o_nrm, u->normal, n * 12);
+        if (u->min_dist) std::memcpy(h + o_min, u->min_dist, n * 4);
+        if (u->max_dist) std::memcpy(h + o_max, u->max_dist, n * 4);
+        if (u->desc) std::memcpy(h + o_desc, u->desc, n * 32);
+        if (u->flags) std::memcpy(h + o_flags, u->flags, n);
+        if ((rc = frame_upload(c, 0, end))) return rc;
+        const uint8_t* io = frame_state(c)->io.as<uint8_t>();
+        mpt_launch_scatter(c->stream, t->T, u->n, (const int*)(io + o_slot), u->pos ? (const float*)(io + o_pos) : nullptr,
+                           u->normal ? (const float*)(io + o_nrm) : nullptr, u->min_dist ? (const float*)(io + o_min) : nullptr,
+                           u->max_dist ? (const float*)(io + o_max) : nullptr, u->desc ? io + o_desc : nullptr, u->flags ? io + o_flags : nullptr);
+        CCM_HIP(c, hipGetLastError());
+        return CCM_OK;
+    });
+}
+
+int ccm_map_table_set_order(ccm_ctx* c, ccm_map_table* t, int n, const int32_t* slots)
+{
+    RoctxRange roctx_("ccm_map_table_set_order");
+    if (!c || !t) return CCM_E_ARG;
+    int rc = check_table(c, t);
+    if (rc) return rc;
+    if (!slots) { t->order_all = true; t->n_order = 0; return CCM_OK; }
+    if (n < 0) return ccm_fail(c, CCM_E_ARG, "order of %d entries", n);
+    return ccm_guard(c, "ccm_map_table_set_order", [&]() -> int {
+        bool dup = false;
+        if ((rc = mark_slots(c, t, n, slots, &dup))) return rc;
+        if (dup) return ccm_fail(c, CCM_E_ARG, "a slot occurs twice in the order");
+        CCM_HIP(c, hipSetDevice(c->device));
+        if (n > 0) {
+            uint8_t* h = nullptr;
+            if ((rc = frame_staging(c, (size_t)n * 4, &h))) return rc;
+            std::memcpy(h, slots, (size_t)n * 4);
+            CCM_RESERVE(c, t->order, (size_t)n * 4);
+            if ((rc = frame_upload(c, 0, (size_t)n * 4, t->order.p))) return rc;
+        }
+        t->order_all = false; t->n_order = n;
+        return CCM_OK;
+    });
+}
+
+int ccm_map_table_fetch(ccm_ctx* c, ccm_map_table* t, int n, const int32_t* slot, float* pos, float* normal, float* min_dist,
+                        float* max_dist, uint8_t* desc, uint8_t* flags, int32_t* seen)
+{
+    if (!c || !t) return CCM_E_ARG;
+    int rc = check_table(c, t);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && !slot)) return ccm_fail(c, CCM_E_ARG, "bad fetch arguments");
+    if (n == 0) return CCM_OK;
+    return ccm_guard(c, "ccm_map_table_fetch", [&]() -> int {
+        for (int r = 0; r < n; r++)
+            if (slot[r] < 0 || slot[r] >= t->capacity) return ccm_fail(c, CCM_E_ARG, "slot %d (entry %d) outside [0, %d)", slot[r], r, t->capacity);
+        CCM_HIP(c, hipSetDevice(c->device));
+        const size_t m = (size_t)n;
+        size_t off = 0;
+        const size_t o_pos = seg(off, m * 12), o_nrm = seg(off, m * 12), o_min = seg(off, m * 4), o_max = seg(off, m * 4);
+        const size_t o_desc = seg(off, m * 32), o_flags = seg(off, m), o_seen = seg(off, m * 4);
+        const size_t res_end = off;
+        const size_t o_slot = seg(off, m * 4);
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, off, &h))) return rc;
+        std::memcpy(h + o_slot, slot, m * 4);
+        if ((rc = frame_upload(c, o_slot, off))) return rc;
+        uint8_t* io = frame_state(c)->io.as<uint8_t>();
+        mpt_launch_gather(c->stream, t->T, n, (const int*)(io + o_slot), (float*)(io + o_pos), (float*)(io + o_nrm), (float*)(io + o_min),
+                          (float*)(io + o_max), io + o_desc, io + o_flags, (int*)(io + o_seen));
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = frame_download(c, res_end))) return rc;
+        if (pos) std::memcpy(pos, h + o_pos, m * 12);
+        if (normal) std::memcpy(normal, h + o_nrm, m * 12);
+        if (min_dist) std::memcpy(min_dist, h + o_min, m * 4);
+        if (max_dist) std::memcpy(max_dist, h + o_max, m * 4);
+        if (desc) std::memcpy(desc, h + o_desc, m * 32);
+        if (flags) std::memcpy(flags, h + o_flags, m);
+        if (seen) std::memcpy(seen, h + o_seen, m * 4);
+        return CCM_OK;
+    });
+}
+
+// Tracking::SearchLocalPoints, src/Tracking.cpp:860-922
+int ccm_frame_search_local_points(ccm_ctx* c, ccm_frame* f, ccm_map_table* t, const ccm_slp_params* p, ccm_slp_result* r)
+{
+    RoctxRange roctx_("ccm_frame_search_local_points");
+    if (!c || !f || !t || !p || !r) return CCM_E_ARG;
+    int rc = frame_check(c, f);
+    if (rc || (rc = check_table(c, t))) return rc;
+    if (p->n_levels < 1 || p->n_levels > CCM_MAX_LEVELS || !p->scale_factors || r->in_view_cap < 0 || (r->in_view_cap > 0 && !r->in_view_slot) ||
+        (f->n > 0 && (!r->match || !r->mp_id)))
+        return ccm_fail(c, CCM_E_ARG, "bad SearchLocalPoints arguments (n_levels in 1..%d, match and mp_id of N entries)", CCM_MAX_LEVELS);
+    using clk = std::chrono::steady_clock;
+    const clk::time_point t_entry = clk::now();
+    clk::time_point t_before, t_after;
+    bool timed = false;
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const int ret = ccm_guard(c, "ccm_frame_search_local_points", [&]() -> int {
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        hipStream_t st = c->stream;
+        const int n = f->n, n_order = t->order_all ? t->capacity : t->n_order, n_wg = slp_workgroups(n_order);
+        const size_t m = (size_t)n_order;
+        if (t->stamp == INT_MAX) { CCM_HIP(c, hipMemsetAsync(t->T.seen, 0, (size_t)t->capacity * 4, st)); t->stamp = 0; }
+        const int stamp = ++t->stamp;
+
+        size_t off = 0;
+        const size_t o_status = seg(off, 16), o_out = seg(off, (size_t)n * 4), o_flag = seg(off, (size_t)n), o_ids = seg(off, (size_t)n * 4);
+        const size_t res_end = o_ids + (size_t)n * 4;
+        const size_t o_cnt = seg(off, 16), o_slots = seg(off, m * 4);
+        const size_t first_end = o_cnt + 16;
+        const size_t o_px = seg(off, m * 4), o_py = seg(off, m * 4), o_lvl = seg(off, m * 4), o_vc = seg(off, m * 4);
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, off, &h))) return rc;
+        size_t w = 0;                                                          // device-only work area
+        const size_t w_u = seg(w, m * 4), w_v = seg(w, m * 4), w_vc = seg(w, m * 4), w_lvl = seg(w, m * 4);
+        const size_t w_mask = seg(w, (size_t)n_wg * (SLP_TPB / 64) * 8), w_cnt = seg(w, (size_t)n_wg * 4), w_off = seg(w, (size_t)n_wg * 4);
+        const size_t w_qr = seg(w, m * 4), w_minl = seg(w, m * 4), w_maxl = seg(w, m * 4), w_qdesc = seg(w, m * 32);
+        const size_t w_act = seg(w, m), w_qflag = seg(w, m);
+        CCM_RESERVE(c, S.slp, w + 64);
+        uint8_t* io = S.io.as<uint8_t>(); uint8_t* wk = S.slp.as<uint8_t>();
+        int* d_cnt = (int*)(io + o_cnt); int* d_ids = (int*)(io + o_ids);
+
+        CCM_HIP(c, hipMemsetAsync(d_cnt, 0, 16, st));
+        slp_launch_mark(st, t->T, n, f->mp_id, stamp, d_ids, io + o_flag, (int*)(io + o_out), d_cnt);
+        CCM_HIP(c, hipGetLastError());
+        SlpArgs A{};
+        A.n_order = n_order; A.order = t->order_all ? nullptr : t->order.as<int>(); A.stamp = stamp;
+        std::memcpy(A.Tcw, p->Tcw, sizeof A.Tcw); std::memcpy(A.Ow, p->Ow, sizeof A.Ow);
+        A.fx = p->fx; A.fy = p->fy; A.cx = p->cx; A.cy = p->cy; A.min_x = p->min_x; A.max_x = p->max_x; A.min_y = p->min_y; A.max_y = p->max_y;
+        A.cos_limit = p->viewing_cos_limit; A.log_scale = p->log_scale_factor; A.n_levels = p->n_levels; A.th = p->th;
+        for (int l = 0; l < CCM_MAX_LEVELS; l++) A.scale[l] = l < p->n_levels ? p->scale_factors[l] : 0.f;
+        A.tmp_u = (float*)(wk + w_u); A.tmp_v = (float*)(wk + w_v); A.tmp_vc = (float*)(wk + w_vc); A.tmp_level = (int*)(wk + w_lvl);
+        A.mask = (unsigned long long*)(wk + w_mask); A.wg_cnt = (int*)(wk + w_cnt); A.wg_off = (int*)(wk + w_off);
+        A.qx = (float*)(io + o_px); A.qy = (float*)(io + o_py); A.qr = (float*)(wk + w_qr); A.minl = (int*)(wk + w_minl); A.maxl = (int*)(wk + w_maxl);
+        A.qdesc = wk + w_qdesc; A.qact = wk + w_act; A.qflag = wk + w_qflag; A.slots = (int*)(io + o_slots);
+        A.tap_level = (int*)(io + o_lvl); A.tap_vc = (float*)(io + o_vc);
+        slp_launch_frustum(st, A, t->T, d_cnt);
+        CCM_HIP(c, hipGetLastError());
+        t_before = clk::now();
+        if ((rc = frame_download(c, first_end))) return rc;                    // the count (16 bytes) behind the first loop's results
+        t_after = clk::now(); timed = true;
+
+        int head[2];
+        std::memcpy(head, h + o_cnt, 8);
+        const int nv = head[0];
+        if (head[1]) return ccm_fail(c, CCM_E_ARG, "the frame holds a map-point id outside [0, %d) or of a slot that is not LIVE", t->capacity);
+        if (nv < 0 || nv > n_order) return ccm_fail(c, CCM_E_DEVICE, "%d entries in view of %d", nv, n_order);
+        r->n_to_match = nv;
+        if (nv > r->in_view_cap) return ccm_fail(c, CCM_E_CAPACITY, "%d map points in view, room for %d", nv, r->in_view_cap);
+        if (n > 0) CCM_HIP(c, hipMemcpyAsync(f->mp_id, d_ids, (size_t)n * 4, hipMemcpyDeviceToDevice, st));   // the bad ones cleared
+        const bool taps = r->proj_x || r->proj_y || r->level || r->view_cos;
+        if (nv == 0 || n == 0) {                                               // :910: no matcher
+            for (int i = 0; i < n; i++) r->match[i] = -1;
+            if (n > 0) std::memcpy(r->mp_id, h + o_ids, (size_t)n * 4);
+            if (n > 0 && r->occupied) std::memcpy(r->occupied, h + o_flag, n);
+            if (nv == 0) return 0;
+            if ((rc = frame_fetch(c, h + o_slots, io + o_slots, (size_t)nv * 4))) return rc;      // an empty frame: the slot list alone
+            if (taps && (rc = frame_fetch(c, h + o_px, io + o_px, (o_vc + (size_t)nv * 4) - o_px))) return rc;
+        } else {                                                               // exact lengths; they land before the matcher's download
+            CCM_HIP(c, hipMemcpyAsync(h + o_slots, io + o_slots, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+            if (taps)
+                for (size_t o : { o_px, o_py, o_lvl, o_vc }) CCM_HIP(c, hipMemcpyAsync(h + o, io + o, (size_t)nv * 4, hipMemcpyDeviceToHost, st));
+        }
+        int nmatches = 0;
+        if (nv > 0 && n > 0) {
+            WinDevCall D{ 0, nv, A.qx, A.qy, A.qr, A.minl, A.maxl, A.qdesc, A.qact, A.qflag, A.slots, nullptr, o_status, o_out, o_flag, res_end,
+                          p->nnratio, 0, 0, nullptr, nullptr, nullptr, nullptr, d_ids, false };
+            std::vector<uint8_t> occ_tmp;
+            uint8_t* occ = r->occupied;
+            if (!occ) { occ_tmp.resize(n); occ = occ_tmp.data(); }
+            nmatches = frame_window_dev(c, f, D, occ, r->match);
+            if (nmatches < 0) return nmatches;
+            if (D.host_accept) { if ((rc = frame_fetch(c, r->mp_id, f->mp_id, (size_t)n * 4))) return rc; }
+            else std::memcpy(r->mp_id, h + o_ids, (size_t)n * 4);
+            std::memcpy(r->in_view_slot, h + o_slots, (size_t)nv * 4);
+            for (int i = 0; i < n; i++) if (r->match[i] >= 0) r->match[i] = r->in_view_slot[r->match[i]];   // query -> slot
+        }
+        if (n == 0) std::memcpy(r->in_view_slot, h + o_slots, (size_t)nv * 4);
+        if (taps) {
+            if (r->proj_x) std::memcpy(r->proj_x, h + o_px, (size_t)nv * 4);
+            if (r->proj_y) std::memcpy(r->proj_y, h + o_py, (size_t)nv * 4);
+            if (r->level) std::memcpy(r->level, h + o_lvl, (size_t)nv * 4);
+            if (r->view_cos) std::memcpy(r->view_cos, h + o_vc, (size_t)nv * 4);
+        }
+        return nmatches;
+    });
+    if (timed) {
+        double* t_ms = c->frame->slp_ms;
+        t_ms[0] = ms(t_entry, t_before); t_ms[1] = ms(t_before, t_after); t_ms[2] = ms(t_after, clk::now());
+    }
+    return ret;
+}
+
+int ccm_frame_search_local_points_timing(ccm_ctx* c, double out[3])
+{
+    if (!c || !out) return CCM_E_ARG;
+    if (!c->frame || c->frame->slp_ms[0] < 0) return ccm_fail(c, CCM_E_STATE, "no ccm_frame_search_local_points on this context yet");
+    std::memcpy(out, c->frame->slp_ms, sizeof c->frame->slp_ms);
+    return CCM_OK;
+}
+
+// Optimizer::PoseOptimizationClient(Frame&), src/Optimizer.cpp:215-347, the points read from the table
+int ccm_frame_pose_optimize_table(ccm_ctx* c, ccm_frame* f, ccm_map_table* t, const float* inv_level_sigma2, int n_levels,
+                                  const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers)
+{
+    RoctxRange roctx_("ccm_frame_pose_optimize_table");
+    if (!c || !f || !t) return CCM_E_ARG;
+    int rc = frame_check(c, f);
+    if (rc || (rc = check_table(c, t))) return rc;
+    if (!intr || !pose7 || !n_inliers || (f->n > 0 && (!outlier || !inv_level_sigma2 || n_levels < 1)))
+        return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
+    if (f->n == 0) { *n_inliers = 0; return CCM_OK; }
+    return ccm_guard(c, "ccm_frame_pose_optimize_table", [&]() -> int {
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        hipStream_t st = c->stream;
+        const int n = f->n;
+        size_t off = 0;
+        const size_t o_ninl = seg(off, 16), o_outl = seg(off, (size_t)n), o_pose = seg(off, 56);
+        const size_t res_end = o_pose + 56;
+        const size_t o_intr = seg(off, 32), o_is2 = seg(off, (size_t)n_levels * 4);
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        std::memcpy(h + o_pose, pose7, 56); std::memcpy(h + o_intr, intr, 32);
+        std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4);
+        if ((rc = frame_upload(c, o_pose, end))) return rc;
+        CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
+        CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
+        uint8_t* io = S.io.as<uint8_t>();
+        int* d_ninl = (int*)(io + o_ninl); int* d_status = d_ninl + 1;
+        MptPoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, (const float*)(io + o_is2), n_levels, S.first.as<int>(), S.pts.as<double>(),
+                             S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
+        mpt_launch_pose_gather(st, G, t->T);
+        CCM_HIP(c, hipGetLastError());
+        PoseDev D{ 1, (double*)(io + o_pose), (const double*)(io + o_intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
+                   S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
+        pose_launch(st, D);
+        CCM_HIP(c, hipGetLastError());
+        frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = frame_download(c, res_end))) return rc;
+        int head[2];
+        std::memcpy(head, S.host + o_ninl, 8);
+        if (head[1]) return ccm_fail(c, CCM_E_ARG, "a map-point id outside the table or of a slot that is not LIVE, or an octave outside [0, %d)", n_levels);
+        std::memcpy(pose7, S.host + o_pose, 56);
+        std::memcpy(outlier, S.host + o_outl, n);
+        *n_inliers = head[0];
+        return CCM_OK;
+    });
+}
+
+}  // extern "C"

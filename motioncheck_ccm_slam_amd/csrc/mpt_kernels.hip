@@ -1,0 +1,250 @@
+// mpt_kernels.hip -- device side of the map-point table (mpt_host.cpp, include/ccm_hot.h "map-point table"):
+//   k_mpt_scatter      rows of a ccm_map_update into the table's columns
+//   k_mpt_gather       test tap: rows of a slot list out of the table
+//   k_slp_mark         first loop of Tracking::SearchLocalPoints (src/Tracking.cpp:863-879), thread per frame feature
+//   k_slp_frustum      second loop (:888-908): Frame::isInFrustum (src/Frame.cpp:139-198) and MapPoint::PredictScale
+//                      (src/MapPoint.cpp:854-869), thread per entry of the order list; per-wave ballots, per-workgroup counts
+//   k_slp_scan         exclusive scan of the workgroup counts, one workgroup; the in-view count
+//   k_slp_compact      the entries in view, in list order, into the query arrays of the windowed matcher
+//   k_mpt_pose_gather  k_frame_pose_gather (frame_kernels.hip) with the points read from the table as float
+// No kernel waits for another workgroup: the compaction is three launches (ballot + count, scan, scatter).
+// Every index is checked against the table's capacity before it is used as an address.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "../../include/ccm_hot.h"
+#include "mpt_types.h"
+
+// ---------------------------------------------------------------------------------------------------------------- table rows
+__global__ void k_mpt_scatter(MptTable T, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
+                              const float* max_dist, const uint8_t* desc, const uint8_t* flags)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int s = slot[r];
+    if (s < 0 || s >= T.capacity) return;        // < 0: superseded by a later row of the same slot (the host marks them)
+    if (pos) for (int d = 0; d < 3; d++) T.pos[3 * (size_t)s + d] = pos[3 * (size_t)r + d];
+    if (normal) for (int d = 0; d < 3; d++) T.normal[3 * (size_t)s + d] = normal[3 * (size_t)r + d];
+    if (min_dist) T.min_dist[s] = min_dist[r];
+    if (max_dist) T.max_dist[s] = max_dist[r];
+    if (desc) {
+        const uint4* a = reinterpret_cast<const uint4*>(desc + (size_t)r * 32);
+        uint4* b = reinterpret_cast<uint4*>(T.desc + (size_t)s * 32);
+        b[0] = a[0]; b[1] = a[1];
+    }
+    if (flags) T.flags[s] = flags[r];
+}
+
+__global__ void k_mpt_gather(MptTable T, int n, const int* slot, float* pos, float* normal, float* min_dist, float* max_dist, uint8_t* desc,
+                             uint8_t* flags, int* seen)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int s = slot[r];
+    if (s < 0 || s >= T.capacity) return;
+    for (int d = 0; d < 3; d++) { pos[3 * (size_t)r + d] = T.pos[3 * (size_t)s + d]; normal[3 * (size_t)r + d] = T.normal[3 * (size_t)s + d]; }
+    min_dist[r] = T.min_dist[s]; max_dist[r] = T.max_dist[s];
+    const uint4* a = reinterpret_cast<const uint4*>(T.desc + (size_t)s * 32);
+    uint4* b = reinterpret_cast<uint4*>(desc + (size_t)r * 32);
+    b[0] = a[0]; b[1] = a[1];
+    flags[r] = T.flags[s]; seen[r] = T.seen[s];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- first loop
+// ids / occ / match lie in the call's result block; the handle's own mp_id is replaced by ids only once the host has seen bad == 0.
+__global__ void k_slp_mark(MptTable T, int n, const int* mp_id, int stamp, int* ids, uint8_t* occ, int* match, int* cnt)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int id = mp_id[i];
+    uint8_t o = 0;
+    if (id >= 0) {
+        const uint8_t fl = id < T.capacity ? T.flags[id] : 0;
+        if (!(fl & CCM_MP_LIVE)) cnt[1] = 1;                    // outside the table or not in use: the host reports CCM_E_ARG
+        else if (fl & CCM_MP_BAD) id = -1;                      // :868-871
+        else { T.seen[id] = stamp; o = (fl & CCM_MP_HAS_OBS) ? 1 : 0; }   // :875; several features may hold one slot: same value
+    }
+    ids[i] = id; occ[i] = o; match[i] = -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- second loop
+__device__ inline int slp_slot(const SlpArgs& A, int j) { return A.order ? A.order[j] : j; }
+
+// Frame::isInFrustum + PredictScale for one point, in the arithmetic of float cv::Mat expressions (map_math.h: the products of
+// a matrix product, dot and norm are summed in double and stored as float; everything else is float, left to right).
+__device__ inline bool slp_in_frustum(const SlpArgs& A, const MptTable& T, int s, float& u, float& v, float& view_cos, int& level)
+{
+    const float P[3] = { T.pos[3 * (size_t)s], T.pos[3 * (size_t)s + 1], T.pos[3 * (size_t)s + 2] };
+    float Pc[3];
+    for (int r = 0; r < 3; r++)
+        Pc[r] = (float)((double)A.Tcw[4 * r] * (double)P[0] + (double)A.Tcw[4 * r + 1] * (double)P[1] + (double)A.Tcw[4 * r + 2] * (double)P[2] +
+                        (double)A.Tcw[4 * r + 3]);
+    if (Pc[2] < 0.0f) return false;
+    const float invz = 1.0f / Pc[2];
+    u = A.fx * Pc[0] * invz + A.cx;
+    v = A.fy * Pc[1] * invz + A.cy;
+    if (u < A.min_x || u > A.max_x) return false;
+    if (v < A.min_y || v > A.max_y) return false;
+    const float max_d = T.max_dist[s];
+    const float PO[3] = { P[0] - A.Ow[0], P[1] - A.Ow[1], P[2] - A.Ow[2] };
+    const float dist = (float)sqrt((double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1] + (double)PO[2] * (double)PO[2]);
+    if (dist < 0.8f * T.min_dist[s] || dist > 1.2f * max_d) return false;
+    const double dot = (double)PO[0] * (double)T.normal[3 * (size_t)s] + (double)PO[1] * (double)T.normal[3 * (size_t)s + 1] +
+                       (double)PO[2] * (double)T.normal[3 * (size_t)s + 2];
+    view_cos = (float)(dot / (double)dist);
+    if (view_cos < A.cos_limit) return false;
+    const float ratio = max_d / dist;
+    const float lg = (float)log((double)ratio);
+    const float q = ceilf(lg / A.log_scale);
+    level = !(q >= 0.0f) ? 0 : (q >= (float)A.n_levels ? A.n_levels - 1 : (int)q);
+    return true;
+}
+
+// One thread per entry of the order list, SLP_TPB / 64 waves per workgroup.  mask[j / 64] = the wave's ballot, wg_cnt[b] = entries in
+// view of workgroup b; tmp_* hold the values of the entries in view at their list position.
+__global__ __launch_bounds__(SLP_TPB) void k_slp_frustum(SlpArgs A, MptTable T)
+{
+    __shared__ int s_cnt[SLP_TPB / 64];
+    const int j = blockIdx.x * SLP_TPB + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    bool keep = false;
+    if (j < A.n_order) {
+        const int s = slp_slot(A, j);
+        if (s >= 0 && s < T.capacity) {
+            const uint8_t fl = T.flags[s];
+            if ((fl & CCM_MP_LIVE) && !(fl & CCM_MP_BAD) && T.seen[s] != A.stamp) {     // :891-900
+                float u, v, vc; int level;
+                keep = slp_in_frustum(A, T, s, u, v, vc, level);
+                if (keep) { A.tmp_u[j] = u; A.tmp_v[j] = v; A.tmp_vc[j] = vc; A.tmp_level[j] = level; }
+            }
+        }
+    }
+    const unsigned long long ball = __ballot(keep);
+    if (lane == 0) {
+        s_cnt[wv] = __popcll(ball);
+        if (blockIdx.x * SLP_TPB + wv * 64 < A.n_order) A.mask[(size_t)blockIdx.x * (SLP_TPB / 64) + wv] = ball;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < SLP_TPB / 64; w++) t += s_cnt[w];
+        A.wg_cnt[blockIdx.x] = t;
+    }
+}
+
+// Exclusive scan of wg_cnt [n_wg] into wg_off, one workgroup of SCAN_TPB threads walking the array in chunks; cnt[0] = the total.
+__global__ __launch_bounds__(SCAN_TPB) void k_slp_scan(int n_wg, const int* wg_cnt, int* wg_off, int* cnt)
+{
+    __shared__ int s_v[SCAN_TPB];
+    __shared__ int s_base;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int base = 0; base < n_wg; base += SCAN_TPB) {
+        const int i = base + tid;
+        const int mine = i < n_wg ? wg_cnt[i] : 0;
+        s_v[tid] = mine;
+        __syncthreads();
+        for (int off = 1; off < SCAN_TPB; off <<= 1) {
+            const int v = tid >= off ? s_v[tid - off] : 0;
+            __syncthreads();
+            s_v[tid] += v;
+            __syncthreads();
+        }
+        if (i < n_wg) wg_off[i] = s_base + s_v[tid] - mine;
+        __syncthreads();
+        if (tid == 0) s_base += s_v[SCAN_TPB - 1];
+        __syncthreads();
+    }
+    if (tid == 0) cnt[0] = s_base;
+}
+
+// Entry j in view goes to k = wg_off[b] + (entries in view of the workgroup's earlier waves) + (earlier lanes of its wave): list order
+// is kept.  Query set-up exactly as window_queries_projection() (match_host.cpp; ORBmatcher.cpp:97-107, RadiusByViewingCos :150-156).
+__global__ __launch_bounds__(SLP_TPB) void k_slp_compact(SlpArgs A, MptTable T)
+{
+    const int j = blockIdx.x * SLP_TPB + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (j >= A.n_order) return;
+    const unsigned long long* m = A.mask + (size_t)blockIdx.x * (SLP_TPB / 64);
+    const unsigned long long mine = m[wv];
+    if (!((mine >> lane) & 1ull)) return;
+    int k = A.wg_off[blockIdx.x] + __popcll(mine & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wv; w++) k += __popcll(m[w]);
+    if (k < 0 || k >= A.n_order) return;         // cannot happen: at most n_order entries are in view
+    const int s = slp_slot(A, j);
+    const float vc = A.tmp_vc[j];
+    const int level = A.tmp_level[j];
+    float r = (double)vc > 0.998 ? 2.5f : 4.0f;
+    if (A.th != 1.0f) r *= A.th;
+    A.qx[k] = A.tmp_u[j]; A.qy[k] = A.tmp_v[j]; A.qr[k] = r * A.scale[level];
+    A.minl[k] = level - 1; A.maxl[k] = level;
+    A.qact[k] = 1; A.qflag[k] = (T.flags[s] & CCM_MP_HAS_OBS) ? 1 : 0;
+    A.slots[k] = s;
+    A.tap_level[k] = level; A.tap_vc[k] = vc;
+    const uint4* a = reinterpret_cast<const uint4*>(T.desc + (size_t)s * 32);
+    uint4* b = reinterpret_cast<uint4*>(A.qdesc + (size_t)k * 32);
+    b[0] = a[0]; b[1] = a[1];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- pose
+// k_frame_pose_gather with pos read as float and widened (Converter::toVector3d of a float cv::Mat is exact); a slot outside the
+// table or not LIVE is a bad id.  One workgroup; the features with mp_id >= 0 in feature order.
+__global__ __launch_bounds__(MPG_TPB) void k_mpt_pose_gather(MptPoseGatherArgs A, MptTable T)
+{
+    __shared__ int s_wave[MPG_TPB / 64];
+    __shared__ int s_base, s_bad;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (tid == 0) { s_base = 0; s_bad = 0; }
+    __syncthreads();
+    for (int base = 0; base < A.n; base += MPG_TPB) {
+        const int i = base + tid;
+        const int id = i < A.n ? A.mp_id[i] : -1;
+        const bool has = id >= 0;
+        const int o = has ? A.oct[i] : 0;
+        const bool bad = has && (id >= T.capacity || !(T.flags[id < T.capacity ? id : 0] & CCM_MP_LIVE) || o < 0 || o >= A.n_levels);
+        if (bad) s_bad = 1;
+        const unsigned long long ball = __ballot(has);
+        const int before = __popcll(ball & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wv] = __popcll(ball);
+        __syncthreads();
+        int off = s_base;
+        for (int w = 0; w < wv; w++) off += s_wave[w];
+        const int k = off + before;
+        if (i < A.n) A.kof[i] = has ? k : -1;
+        if (has) {
+            for (int d = 0; d < 3; d++) A.pts[3 * (size_t)k + d] = bad ? 0.0 : (double)T.pos[3 * (size_t)id + d];
+            A.obs[2 * (size_t)k] = (double)A.kx[i]; A.obs[2 * (size_t)k + 1] = (double)A.ky[i];
+            A.info[k] = bad ? 0.0 : (double)A.inv_sigma2[o];
+        }
+        __syncthreads();
+        if (tid == 0) { int t = 0; for (int w = 0; w < MPG_TPB / 64; w++) t += s_wave[w]; s_base += t; }
+        __syncthreads();
+    }
+    if (tid == 0) { A.first[0] = 0; A.first[1] = s_bad ? 0 : s_base; A.status[0] = s_bad; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- launchers
+void mpt_launch_scatter(hipStream_t s, const MptTable& T, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
+                        const float* max_dist, const uint8_t* desc, const uint8_t* flags)
+{
+    if (n > 0) hipLaunchKernelGGL(k_mpt_scatter, dim3((n + 255) / 256), dim3(256), 0, s, T, n, slot, pos, normal, min_dist, max_dist, desc, flags);
+}
+void mpt_launch_gather(hipStream_t s, const MptTable& T, int n, const int* slot, float* pos, float* normal, float* min_dist, float* max_dist,
+                       uint8_t* desc, uint8_t* flags, int* seen)
+{
+    if (n > 0) hipLaunchKernelGGL(k_mpt_gather, dim3((n + 255) / 256), dim3(256), 0, s, T, n, slot, pos, normal, min_dist, max_dist, desc, flags, seen);
+}
+void slp_launch_mark(hipStream_t s, const MptTable& T, int n, const int* mp_id, int stamp, int* ids, uint8_t* occ, int* match, int* cnt)
+{
+    if (n > 0) hipLaunchKernelGGL(k_slp_mark, dim3((n + 255) / 256), dim3(256), 0, s, T, n, mp_id, stamp, ids, occ, match, cnt);
+}
+int slp_workgroups(int n_order) { return (n_order + SLP_TPB - 1) / SLP_TPB; }
+void slp_launch_frustum(hipStream_t s, const SlpArgs& A, const MptTable& T, int* cnt)
+{
+    const int n_wg = slp_workgroups(A.n_order);
+    if (n_wg > 0) hipLaunchKernelGGL(k_slp_frustum, dim3(n_wg), dim3(SLP_TPB), 0, s, A, T);
+    hipLaunchKernelGGL(k_slp_scan, dim3(1), dim3(SCAN_TPB), 0, s, n_wg, A.wg_cnt, A.wg_off, cnt);
+    if (n_wg > 0) hipLaunchKernelGGL(k_slp_compact, dim3(n_wg), dim3(SLP_TPB), 0, s, A, T);
+}
+void mpt_launch_pose_gather(hipStream_t s, const MptPoseGatherArgs& A, const MptTable& T)
+{
+    hipLaunchKernelGGL(k_mpt_pose_gather, dim3(1), dim3(MPG_TPB), 0, s, A, T);
+}

@@ -1,0 +1,41 @@
+// mpt_types.h -- kernel argument structures and launchers of the map-point table, shared by mpt_kernels.hip and mpt_host.cpp.
+#pragma once
+#include <cstdint>
+#include <hip/hip_runtime.h>
+#include "../../include/ccm_hot.h"
+
+#define SLP_TPB 256        // k_slp_frustum / k_slp_compact: 4 waves per workgroup
+#define SCAN_TPB 1024
+#define MPG_TPB 1024
+
+struct MptTable {                                // the table's columns (device)
+    int capacity;
+    float* pos; float* normal; float* min_dist; float* max_dist; uint8_t* desc; uint8_t* flags; int* seen;
+};
+
+struct SlpArgs {
+    int n_order; const int* order;               // order == nullptr: entry j is slot j
+    int stamp;
+    float Tcw[12], Ow[3], fx, fy, cx, cy, min_x, max_x, min_y, max_y, cos_limit, log_scale;
+    int n_levels; float scale[CCM_MAX_LEVELS]; float th;
+    // per list entry (written where the entry is in view) and per wave / workgroup
+    float* tmp_u; float* tmp_v; float* tmp_vc; int* tmp_level; unsigned long long* mask; int* wg_cnt; int* wg_off;
+    // per entry in view, in list order: the matcher's queries (qx / qy are also the taps mTrackProjX / Y) and the taps
+    float* qx; float* qy; float* qr; int* minl; int* maxl; uint8_t* qdesc; uint8_t* qact; uint8_t* qflag; int* slots;
+    int* tap_level; float* tap_vc;
+};
+
+struct MptPoseGatherArgs {
+    int n; const float* kx; const float* ky; const int* oct; const int* mp_id; const float* inv_sigma2; int n_levels;
+    int* first; double* pts; double* obs; double* info; int* kof; int* status;
+};
+
+void mpt_launch_scatter(hipStream_t, const MptTable&, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
+                        const float* max_dist, const uint8_t* desc, const uint8_t* flags);
+void mpt_launch_gather(hipStream_t, const MptTable&, int n, const int* slot, float* pos, float* normal, float* min_dist, float* max_dist,
+                       uint8_t* desc, uint8_t* flags, int* seen);
+void slp_launch_mark(hipStream_t, const MptTable&, int n, const int* mp_id, int stamp, int* ids, uint8_t* occ, int* match, int* cnt);
+int  slp_workgroups(int n_order);
+// k_slp_frustum, k_slp_scan (cnt[0] = entries in view) and k_slp_compact
+void slp_launch_frustum(hipStream_t, const SlpArgs&, const MptTable&, int* cnt);
+void mpt_launch_pose_gather(hipStream_t, const MptPoseGatherArgs&, const MptTable&);

@@ -1,0 +1,145 @@
+"""Device-resident map-point table and the TrackLocalMap calls that work on it (include/ccm_hot.h "map-point table").
+
+`MapPointTable` mirrors ccm_map_table: the client's map points on the GPU, one row per slot (a slot is the id a `DeviceFrame` carries
+in `map_points`), updated by rows when the map changes.  `Tracking.SearchLocalPoints` is Tracking::SearchLocalPoints
+(src/Tracking.cpp:860-922) in one call on a frame handle and the table; `Tracking.TrackLocalMap` adds the pose optimisation and the
+inlier count of Tracking::TrackLocalMap (:623-727)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import MP_BAD, MP_HAS_OBS, MP_LIVE  # noqa: F401
+
+
+class MapPointTable:
+    """A ccm_map_table of `capacity` slots; release with `close()` (before the context goes) or use it as a context manager."""
+
+    def __init__(self, capacity: int, ctx: _lib.Context | None = None):
+        self.ctx = ctx or _lib.default_context(0)
+        self.lib = self.ctx.lib
+        h = C.c_void_p()
+        self.ctx.check(self.lib.ccm_map_table_create(self.ctx.handle, int(capacity), C.byref(h)))
+        self.handle = h.value
+        self.capacity = self.lib.ccm_map_table_capacity(C.c_void_p(self.handle))
+
+    def update(self, slot, pos=None, normal=None, min_dist=None, max_dist=None, desc=None, flags=None):
+        """Write rows (ccm_map_table_update); a column left None keeps its values."""
+        a = np.ascontiguousarray
+        slot = a(slot, "i4"); n = len(slot)
+
+        def col(v, t, shape):
+            if v is None:
+                return None
+            v = a(v, t)
+            if v.shape != shape:
+                raise ValueError("column of shape %s, expected %s" % (v.shape, shape))
+            return v
+        cols = [col(pos, "f4", (n, 3)), col(normal, "f4", (n, 3)), col(min_dist, "f4", (n,)), col(max_dist, "f4", (n,)),
+                col(desc, np.uint8, (n, 32)), col(flags, np.uint8, (n,))]
+        u = _lib.MapUpdate(n, _lib.ptr(slot), *[_lib.ptr(c) for c in cols])
+        self.ctx.check(self.lib.ccm_map_table_update(self.ctx.handle, C.c_void_p(self.handle), C.byref(u)))
+
+    def set_order(self, slots=None):
+        """The visiting order of SearchLocalPoints (ccm_map_table_set_order); None = ascending slot over the LIVE slots."""
+        s = None if slots is None else np.ascontiguousarray(slots, "i4")
+        pad = s if s is None or len(s) else np.zeros(1, "i4")          # an empty list still needs a non-NULL pointer
+        self.ctx.check(self.lib.ccm_map_table_set_order(self.ctx.handle, C.c_void_p(self.handle), 0 if s is None else len(s), _lib.ptr(pad)))
+
+    def fetch(self, slot):
+        """Rows of `slot` as a dict of arrays (test tap, synchronises)."""
+        slot = np.ascontiguousarray(slot, "i4"); n = len(slot); m = max(n, 1)
+        out = dict(pos=np.zeros((m, 3), "f4"), normal=np.zeros((m, 3), "f4"), min_dist=np.zeros(m, "f4"), max_dist=np.zeros(m, "f4"),
+                   desc=np.zeros((m, 32), np.uint8), flags=np.zeros(m, np.uint8), seen=np.zeros(m, "i4"))
+        self.ctx.check(self.lib.ccm_map_table_fetch(self.ctx.handle, C.c_void_p(self.handle), n, _lib.ptr(slot),
+                                                    *[_lib.ptr(out[k]) for k in ("pos", "normal", "min_dist", "max_dist", "desc", "flags", "seen")]))
+        return {k: v[:n] for k, v in out.items()}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.lib.ccm_map_table_destroy(C.c_void_p(self.handle))
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Tracking:
+    """The per-frame calls of Tracking::TrackLocalMap on a `frame.DeviceFrame` and a `MapPointTable`."""
+
+    @staticmethod
+    def camera(Tcw, Ow=None):
+        """(Tcw [12] float32 row-major 3x4, Ow [3] float32).  Ow = -Rcw^T tcw as a float cv::Mat expression (src/Frame.cpp:136)
+        when not given."""
+        T = np.ascontiguousarray(np.asarray(Tcw, "f4").reshape(-1)[:12].reshape(3, 4))
+        if Ow is None:
+            R = T[:, :3].astype("f8"); t = T[:, 3].astype("f8")
+            Ow = np.array([np.float32(-np.float32(R[0, r]) * t[0] - np.float32(R[1, r]) * t[1] - np.float32(R[2, r]) * t[2]) for r in range(3)], "f4")
+        return T, np.ascontiguousarray(Ow, "f4")
+
+    @staticmethod
+    def SearchLocalPoints(frame, table: MapPointTable, Tcw, intr, scale_factors, Ow=None, bounds=(0.0, 752.0, 0.0, 480.0), th=1.0, nnratio=0.8,
+                          viewing_cos_limit=0.5, log_scale_factor=None, taps=False, ctx=None):
+        """Tracking::SearchLocalPoints (ccm_frame_search_local_points).  intr = fx, fy, cx, cy; bounds = mnMinX, mnMaxX, mnMinY, mnMaxY.
+        Returns a dict: nmatches, n_to_match, in_view_slot, match [N] (slot or -1), mp_id [N], occupied [N] and, with taps,
+        proj_x / proj_y / level / view_cos per entry in view."""
+        ctx = ctx or frame.ctx
+        lib = _lib.load()
+        T, Ow = Tracking.camera(Tcw, Ow)
+        sf = np.ascontiguousarray(scale_factors, "f4")
+        if log_scale_factor is None:
+            log_scale_factor = np.float32(np.log(np.float64(sf[1]))) if len(sf) > 1 else np.float32(1.0)   # mfLogScaleFactor = log(mfScaleFactor)
+        p = _lib.SlpParams()
+        p.Tcw[:] = [float(v) for v in T.reshape(-1)]; p.Ow[:] = [float(v) for v in Ow]
+        p.fx, p.fy, p.cx, p.cy = [float(np.float32(v)) for v in intr]
+        p.min_x, p.max_x, p.min_y, p.max_y = [float(np.float32(v)) for v in bounds]
+        p.viewing_cos_limit = float(viewing_cos_limit); p.log_scale_factor = float(log_scale_factor)
+        p.n_levels = len(sf); p.scale_factors = sf.ctypes.data; p.th = float(th); p.nnratio = float(nnratio)
+        n = frame.n; m = max(n, 1); cap = table.capacity
+        out = dict(in_view_slot=np.zeros(cap, "i4"), match=np.full(m, -1, "i4"), mp_id=np.full(m, -1, "i4"), occupied=np.zeros(m, np.uint8))
+        if taps:
+            out.update(proj_x=np.zeros(cap, "f4"), proj_y=np.zeros(cap, "f4"), level=np.zeros(cap, "i4"), view_cos=np.zeros(cap, "f4"))
+        g = lambda k: _lib.ptr(out[k]) if k in out else None  # noqa: E731
+        r = _lib.SlpResult(0, cap, g("in_view_slot"), g("proj_x"), g("proj_y"), g("level"), g("view_cos"), g("match"), g("mp_id"), g("occupied"))
+        nm = ctx.check(lib.ccm_frame_search_local_points(ctx.handle, C.c_void_p(frame.handle), C.c_void_p(table.handle), C.byref(p), C.byref(r)))
+        nv = int(r.n_to_match)
+        res = dict(nmatches=nm, n_to_match=nv, match=out["match"][:n], mp_id=out["mp_id"][:n], occupied=out["occupied"][:n])
+        for k in ("in_view_slot", "proj_x", "proj_y", "level", "view_cos"):
+            if k in out:
+                res[k] = out[k][:nv]
+        return res
+
+    @staticmethod
+    def PoseOptimizationTable(frame, table: MapPointTable, pose, intr, inv_level_sigma2, ctx=None):
+        """Optimizer::PoseOptimizationClient(Frame&) with the points read from the table (ccm_frame_pose_optimize_table).
+        Returns (pose7, outlier per feature, nInliers)."""
+        ctx = ctx or frame.ctx
+        lib = _lib.load()
+        pose = np.ascontiguousarray(pose, "f8").copy(); intr = np.ascontiguousarray(intr, "f8")
+        is2 = np.ascontiguousarray(inv_level_sigma2, "f4")
+        outl = np.zeros(max(frame.n, 1), np.uint8); ninl = np.zeros(1, "i4")
+        p = _lib.ptr
+        ctx.check(lib.ccm_frame_pose_optimize_table(ctx.handle, C.c_void_p(frame.handle), C.c_void_p(table.handle), p(is2), len(is2), p(intr),
+                                                    p(pose), p(outl), p(ninl)))
+        return pose, outl[:frame.n], int(ninl[0])
+
+    @staticmethod
+    def TrackLocalMap(frame, table: MapPointTable, pose, Tcw, intr, scale_factors, inv_level_sigma2, **kw):
+        """Tracking::TrackLocalMap (src/Tracking.cpp:623-727) without the fork's disabled UpdateLocalMap: SearchLocalPoints, the pose
+        optimisation, then mnMatchesInliers = the features that hold a map point and are no outlier (:637-648).  Returns (search result,
+        pose7, outlier, mnMatchesInliers)."""
+        s = Tracking.SearchLocalPoints(frame, table, Tcw, intr, scale_factors, **kw)
+        p7, outl, _ = Tracking.PoseOptimizationTable(frame, table, pose, intr, inv_level_sigma2)
+        inliers = int(((s["mp_id"] >= 0) & (outl == 0)).sum())
+        return s, p7, outl, inliers
