@@ -447,6 +447,32 @@ int ccm_frame_get_map_points(ccm_frame*, int32_t* mp_id);
 /* Test tap (host copies, synchronises): cell_first[cols*rows+1], cell_items[cell_first[cols*rows]] with cell k = px*rows + py,
  * features of a cell in ascending index, as ccm_window_candidates builds the grid from host arrays. */
 int ccm_frame_debug_grid(ccm_frame*, int32_t* cell_first, int32_t* cell_items);
+/* KeyFrame side of a frame handle: what LocalMapping reads of a keyframe beyond the Frame data (CreateNewMapPoints, src/Mapping.cpp:
+ * 284-469, with SearchForTriangulation, ORBmatcher.cpp:700-852).  All three are optional, may come in any order and may be repeated;
+ * they are asynchronous on the context's stream and in effect for the next call.  A keyframe's features never change, so a handle is
+ * made once per keyframe; what changes later is mp_id (ccm_frame_set_map_points) and the pose.  Once bow and camera are both set the
+ * device keeps the features that have a node ordered by (node, feature index) -- the order DBoW2 fills a FeatureVector in -- with
+ * node-ordered copies of their descriptors (about 52 bytes per feature in a second pooled block).  On an error the handle keeps its
+ * previous state; on a handle that outlived its context they return CCM_E_STATE.
+ * set_bow: node[n] = FeatureVector node per feature (mFeatVec, KeyFrame::ComputeBoW), -1 = none, < 2^24 as ccm_map_keyframe.node;
+ * NULL clears it.  CCM_E_ARG names the feature whose node is >= 2^24, or n when it is above 2^20 - 1.
+ * set_camera: fx, fy, cx, cy, mvScaleFactors and mvLevelSigma2 (:292-305).  CCM_E_ARG when a table is NULL or n_levels is below the
+ * handle's own n_levels (1 + the largest octave of ccm_frame_create, the extractor's levels of ccm_frame_from_extract) or above 256.
+ * set_pose: GetRotation / GetTranslation as the rows of [Rcw | tcw], and GetCameraCenter as the keyframe stores it (:337-349). */
+int ccm_frame_set_bow(ccm_frame*, const int32_t* node);
+int ccm_frame_set_camera(ccm_frame*, float fx, float fy, float cx, float cy, const float* scale_factors, const float* level_sigma2, int n_levels);
+int ccm_frame_set_pose(ccm_frame*, const float* Tcw /* [12] rows of [Rcw|tcw] */, const float* Ow /* [3] */);
+/* Test tap (synchronises): order[n_with_node] the features that have a node by (node, index), nodes[n_nodes] the distinct nodes
+ * ascending, first[n_nodes+1] their first positions in order; returns n_nodes.  Room for n, n and n + 1 entries always suffices.
+ * CCM_E_STATE without a bow. */
+int ccm_frame_debug_bow(ccm_frame*, int32_t* order, int32_t* nodes, int32_t* first);
+/* ccm_fuse_select_batch (ORBmatcher::Fuse, ORBmatcher.cpp:854-1000, for the first loop of SearchInNeighbors, src/Mapping.cpp:
+ * 471-547) with the keyframes taken from handles: their device arrays and device-built grids are used as they are, nothing of a
+ * keyframe is uploaded or rebuilt.  Same outputs.  The handles need neither bow, camera nor pose; the same handle may appear more
+ * than once.  inv_level_sigma2 (chi2_check) holds at least the largest n_levels among the handles. */
+int ccm_fuse_select_batch_frames(ccm_ctx*, int n_kf, ccm_frame* const* kfs, const float* scale_factors, const float* inv_level_sigma2,
+                                 const int32_t* mp_first, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
+                                 const uint8_t* mp_desc, float th, int chi2_check, int accept_th, int32_t* best_idx, int32_t* best_dist);
 /* ccm_search_by_projection (ORBmatcher.cpp:71-148) with the frame side taken from the handle; same results.  occupied [N] stays
  * host in/out (the caller computes Observations() > 0).  For every newly matched feature i the handle's mp_id[i] becomes
  * query_mp_id[q], or q when query_mp_id is NULL. */
@@ -834,6 +860,24 @@ typedef struct {
  * not positive, a node >= 2^24) names the argument in ccm_last_error and touches no output, the tap included.  n_kf == 0,
  * current->n == 0 and a neighbour with n == 0 are valid: the call returns 0, or that neighbour contributes nothing. */
 int ccm_create_new_map_points(ccm_ctx*, const ccm_new_points_problem*, ccm_new_points_result*);
+/* The same call on keyframe handles (ccm_frame_set_bow / _camera / _pose, "frame handles" above): the neighbourhood of a keyframe
+ * moves slowly, so the same 20 to 30 keyframes come back call after call and nothing of them is uploaded again.  has_mp of every
+ * keyframe is mp_id[i] >= 0 as the handle holds it when the call is made; the call writes into no handle (new points get ids when the
+ * caller creates them, :451-466).  The baseline rule (:319-328) runs on the host copies of Ow the handles keep.  Per call: one staged
+ * upload whose size depends on n_kf only, three launches, one download, one synchronisation.
+ * Same result structure, tap, ordering, return value and bytes as ccm_create_new_map_points for the same data, and the same
+ * argument checks (CCM_E_ARG: a null pointer, n_kf < 0, a median_depth that is not positive, n_kf * n above 2^30, a handle of
+ * another context, current with fewer than 2 levels).  CCM_E_STATE names the keyframe and what it lacks, e.g. "neighbours[3]: no
+ * pose".  No output is touched on an error. */
+typedef struct {
+    ccm_frame*        current;
+    int32_t           n_kf;
+    ccm_frame* const* neighbours;    /* [n_kf]; the same handle may appear more than once */
+    const float*      F12;           /* as ccm_new_points_problem */
+    const float*      epipole;
+    const float*      median_depth;
+} ccm_new_points_frames;
+int ccm_create_new_map_points_frames(ccm_ctx*, const ccm_new_points_frames*, ccm_new_points_result*);
 
 /* The optimisation inside Optimizer::OptimizeEssentialGraphLoopClosure / OptimizeEssentialGraphMapFusion
  * (src/Optimizer.cpp:1064-1331, :1333-1574): one VertexSim3Expmap per keyframe (sim3 = Scw or the corrected Sim3,

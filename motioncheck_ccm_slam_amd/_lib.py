@@ -37,11 +37,12 @@ SYMBOLS = [
     "ccm_frame_create", "ccm_frame_from_extract", "ccm_frame_destroy", "ccm_frame_size", "ccm_frame_set_map_points",
     "ccm_frame_get_map_points", "ccm_frame_debug_grid", "ccm_frame_search_by_projection", "ccm_frame_search_by_projection_frame",
     "ccm_frame_pose_optimize",
+    "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
     "ccm_map_table_fetch", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
-    "ccm_initialize", "ccm_create_new_map_points",
+    "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
 ]
 
 
@@ -129,6 +130,11 @@ class NewPointsTap(C.Structure):
 class NewPointsResult(C.Structure):
     _fields_ = [("n_new", C.c_int32), ("kf", C.c_void_p), ("idx1", C.c_void_p), ("idx2", C.c_void_p), ("x3d", C.c_void_p),
                 ("first", C.c_void_p), ("tap", C.POINTER(NewPointsTap))]
+
+
+class NewPointsFrames(C.Structure):
+    _fields_ = [("current", C.c_void_p), ("n_kf", C.c_int32), ("neighbours", C.POINTER(C.c_void_p)), ("F12", C.c_void_p),
+                ("epipole", C.c_void_p), ("median_depth", C.c_void_p)]
 
 
 # CCM_NP_* of include/ccm_hot.h: what became of (neighbour k, feature i1) in ccm_create_new_map_points
@@ -267,6 +273,11 @@ def load():
     lib.ccm_frame_search_by_projection.argtypes = [vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_float, vp]
     lib.ccm_frame_search_by_projection_frame.argtypes = [vp, vp, vp, vp, C.c_int] + [vp] * 9 + [C.c_float, C.c_int, C.c_int, vp]
     lib.ccm_frame_pose_optimize.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_frame_set_bow.argtypes = [vp, vp]
+    lib.ccm_frame_set_camera.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp, C.c_int]
+    lib.ccm_frame_set_pose.argtypes = [vp, vp, vp]
+    lib.ccm_frame_debug_bow.argtypes = [vp, vp, vp, vp]
+    lib.ccm_fuse_select_batch_frames.argtypes = [vp, C.c_int, C.POINTER(vp), vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]
     lib.ccm_map_table_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.ccm_map_table_destroy.argtypes = [vp]; lib.ccm_map_table_destroy.restype = None
     lib.ccm_map_table_capacity.argtypes = [vp]
@@ -287,6 +298,7 @@ def load():
     lib.ccm_sim3_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
     lib.ccm_create_new_map_points.argtypes = [vp, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)]
+    lib.ccm_create_new_map_points_frames.argtypes = [vp, C.POINTER(NewPointsFrames), C.POINTER(NewPointsResult)]
     _lib = lib
     return lib
 

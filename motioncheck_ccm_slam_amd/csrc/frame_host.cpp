@@ -7,6 +7,7 @@
 // stream synchronisation.  The results come first so that in/out data (the occupancy flags, the pose) sits at the seam and
 // travels both ways without a second copy.
 #include "frame_internal.h"
+#include "bow_directory.h"
 #include <algorithm>
 #include <climits>
 #include <new>
@@ -36,9 +37,11 @@ void frame_state_free(ccm_ctx* c)
     mpt_tables_orphan(S);
     for (ccm_frame* f : S->live) {               // frames the caller did not destroy: memory goes, the handle stays (ccm_frame_destroy)
         delete f->mem;
+        delete f->kf_mem;
         *f = ccm_frame();
     }
     for (FrameMem* m : S->pool) delete m;
+    for (FrameMem* m : S->kf_pool) delete m;
     if (S->host) (void)hipHostFree(S->host);
     if (S->host_free) (void)hipEventDestroy(S->host_free);
     delete S;
@@ -95,19 +98,25 @@ int frame_fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes)   // r
     return CCM_OK;
 }
 
+// Best fit among the free blocks, else the largest one (the caller grows it), else a new block.
+static FrameMem* pool_take(std::vector<FrameMem*>& pool, size_t bytes)
+{
+    int pick = -1;
+    for (int i = 0; i < (int)pool.size(); i++)
+        if (pool[i]->buf.cap >= bytes && (pick < 0 || pool[i]->buf.cap < pool[pick]->buf.cap)) pick = i;
+    if (pick < 0)
+        for (int i = 0; i < (int)pool.size(); i++) if (pick < 0 || pool[i]->buf.cap > pool[pick]->buf.cap) pick = i;
+    if (pick < 0) return new FrameMem();
+    FrameMem* m = pool[pick];
+    pool.erase(pool.begin() + pick);
+    return m;
+}
+
 static int frame_alloc(ccm_ctx* c, int n, int cols, int rows, ccm_frame** out)
 {
     FrameState& S = *frame_state(c);
     const FrameLayout L = frame_layout(n, cols * rows);
-    // best fit among the free blocks, else the largest one grown, else a new block
-    int pick = -1;
-    for (int i = 0; i < (int)S.pool.size(); i++)
-        if (S.pool[i]->buf.cap >= L.bytes && (pick < 0 || S.pool[i]->buf.cap < S.pool[pick]->buf.cap)) pick = i;
-    if (pick < 0)
-        for (int i = 0; i < (int)S.pool.size(); i++) if (pick < 0 || S.pool[i]->buf.cap > S.pool[pick]->buf.cap) pick = i;
-    FrameMem* m;
-    if (pick >= 0) { m = S.pool[pick]; S.pool.erase(S.pool.begin() + pick); }
-    else m = new FrameMem();
+    FrameMem* m = pool_take(S.pool, L.bytes);
     if (m->buf.reserve(L.bytes)) {
         S.pool.push_back(m);
         return ccm_fail(c, CCM_E_NOMEM, "frame: device alloc of %zu bytes failed", L.bytes);
@@ -128,6 +137,7 @@ static void frame_release(ccm_frame* f)
         FrameState& S = *f->ctx->frame;
         S.live.erase(std::remove(S.live.begin(), S.live.end(), f), S.live.end());
         if (f->mem) S.pool.push_back(f->mem);    // stream order keeps queued work on it ahead of the next user
+        if (f->kf_mem) S.kf_pool.push_back(f->kf_mem);
     }
     delete f;
 }
@@ -292,6 +302,50 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
     return nmatches;
 }
 
+// ---- the keyframe part of a handle
+struct KfLayout { size_t node, order, nodes, first, bow_end, feat, desc, sf, sig2, cam, bytes; };
+static KfLayout kf_layout(int n)
+{
+    const size_t m = (size_t)std::max(n, 1);
+    KfLayout L; size_t off = 0;
+    L.node = seg(off, m * 4); L.order = seg(off, m * 4); L.nodes = seg(off, m * 4); L.first = seg(off, (m + 1) * 4);
+    L.bow_end = off;
+    L.feat = seg(off, m * sizeof(MapFeat)); L.desc = seg(off, m * 32);
+    L.sf = seg(off, ccm_frame::kMaxLevels * 4); L.sig2 = seg(off, ccm_frame::kMaxLevels * 4); L.cam = seg(off, sizeof(MapCam));
+    L.bytes = off;
+    return L;
+}
+
+// The handle's second block, taken from the pool of keyframe parts on the first setter.
+static int kf_block(ccm_ctx* c, ccm_frame* f)
+{
+    if (f->kf_mem) return CCM_OK;
+    FrameState& S = *frame_state(c);
+    const KfLayout L = kf_layout(f->n);
+    FrameMem* m = pool_take(S.kf_pool, L.bytes);
+    if (m->buf.reserve(L.bytes)) {
+        S.kf_pool.push_back(m);
+        return ccm_fail(c, CCM_E_NOMEM, "frame: device alloc of %zu bytes failed", L.bytes);
+    }
+    uint8_t* base = m->buf.as<uint8_t>();
+    f->kf_mem = m;
+    f->node = (int*)(base + L.node); f->order = (int*)(base + L.order); f->nodes = (int*)(base + L.nodes); f->first = (int*)(base + L.first);
+    f->feat_o = (MapFeat*)(base + L.feat); f->desc_o = base + L.desc; f->sf = (float*)(base + L.sf); f->sig2 = (float*)(base + L.sig2);
+    f->d_cam = (MapCam*)(base + L.cam);
+    return CCM_OK;
+}
+
+// The node-ordered copies, once bow and camera are both there (whichever came last)
+static int kf_gather(ccm_ctx* c, ccm_frame* f)
+{
+    if (!f->has_bow || !f->has_cam || f->n_bow == 0) return CCM_OK;
+    frame_launch_kf_gather(c->stream, KfGatherArgs{ f->n_bow, f->order, f->kx, f->ky, f->oct, f->desc, f->sf, f->sig2, f->feat_o, f->desc_o });
+    CCM_HIP(c, hipGetLastError());
+    return CCM_OK;
+}
+
+const char* frame_keyframe_lacks(const ccm_frame* f) { return !f->has_bow ? "bow" : !f->has_cam ? "camera" : !f->has_pose ? "pose" : nullptr; }
+
 int frame_check(ccm_ctx* c, const ccm_frame* f)
 {
     if (!f->ctx) return ccm_fail(c, CCM_E_ARG, "frame handle outlived its context");
@@ -420,6 +474,102 @@ int ccm_frame_debug_grid(ccm_frame* f, int32_t* cell_first, int32_t* cell_items)
     if (rc) return rc;
     if (cell_first[cells] < 0 || cell_first[cells] > f->n) return ccm_fail(c, CCM_E_DEVICE, "grid of %d items for %d features", cell_first[cells], f->n);
     return frame_fetch(c, cell_items, f->cell_items, (size_t)cell_first[cells] * 4);
+}
+
+// KeyFrame::mFeatVec as one node per feature (KeyFrame::ComputeBoW, read by SearchForTriangulation ORBmatcher.cpp:739-805)
+int ccm_frame_set_bow(ccm_frame* f, const int32_t* node)
+{
+    if (!f) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    if (!node) { f->has_bow = false; return CCM_OK; }
+    return ccm_guard(c, "ccm_frame_set_bow", [&]() -> int {
+        const int n = f->n;
+        if (n > (1 << 20) - 1) return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_bow: n = %d above %d", n, (1 << 20) - 1);
+        for (int i = 0; i < n; i++)
+            if (node[i] >= (1 << 24)) return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_bow: node[%d] = %d, not below %d", i, node[i], 1 << 24);
+        BowDirectory D;
+        bow_directory_build(node, n, D);
+        CCM_HIP(c, hipSetDevice(c->device));
+        int rc = kf_block(c, f);
+        if (rc) return rc;
+        const KfLayout L = kf_layout(n);
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, L.bow_end, &h))) return rc;
+        std::memcpy(h + L.node, node, (size_t)n * 4);
+        std::memcpy(h + L.order, D.order.data(), D.order.size() * 4);
+        std::memcpy(h + L.nodes, D.nodes.data(), D.nodes.size() * 4);
+        std::memcpy(h + L.first, D.first.data(), D.first.size() * 4);
+        // the copy is queued over the live directory before the event record that can still fail: then the handle has no bow at all
+        if ((rc = frame_upload(c, 0, L.bow_end, f->kf_mem->buf.p))) { f->has_bow = false; return rc; }
+        f->has_bow = true; f->n_bow = (int)D.order.size(); f->n_nodes = (int)D.nodes.size();
+        return kf_gather(c, f);
+    });
+}
+
+// KeyFrame::fx, fy, cx, cy, mvScaleFactors, mvLevelSigma2 (read by CreateNewMapPoints, src/Mapping.cpp:292-305, :337-349)
+int ccm_frame_set_camera(ccm_frame* f, float fx, float fy, float cx, float cy, const float* scale_factors, const float* level_sigma2, int n_levels)
+{
+    if (!f) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    return ccm_guard(c, "ccm_frame_set_camera", [&]() -> int {
+        if (!scale_factors || !level_sigma2) return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_camera: null %s", !scale_factors ? "scale_factors" : "level_sigma2");
+        if (n_levels < f->n_levels || n_levels < 1 || n_levels > ccm_frame::kMaxLevels)
+            return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_camera: n_levels = %d outside [%d, %d]", n_levels, std::max(f->n_levels, 1), ccm_frame::kMaxLevels);
+        CCM_HIP(c, hipSetDevice(c->device));
+        int rc = kf_block(c, f);
+        if (rc) return rc;
+        // staged as [sf | sig2 | cam], which are neighbours in the block too (kf_layout): one copy, so a failure leaves nothing half written
+        const size_t tab = ccm_frame::kMaxLevels * 4, end = 2 * tab + sizeof(MapCam);
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        std::memset(h, 0, 2 * tab);
+        std::memcpy(h, scale_factors, (size_t)n_levels * 4); std::memcpy(h + tab, level_sigma2, (size_t)n_levels * 4);
+        MapCam m = f->cam;
+        m.fx = fx; m.fy = fy; m.cx = cx; m.cy = cy;
+        m.invfx = 1.0f / fx; m.invfy = 1.0f / fy;                              // KeyFrame::invfx, invfy
+        std::memcpy(h + 2 * tab, &m, sizeof(MapCam));
+        if ((rc = frame_upload(c, 0, end, f->sf))) return rc;
+        f->cam = m; f->has_cam = true; f->cam_levels = n_levels; f->sf1 = n_levels > 1 ? scale_factors[1] : 0.0f;
+        return kf_gather(c, f);
+    });
+}
+
+// KeyFrame::SetPose: Tcw and Ow as the keyframe stores them (GetRotation, GetTranslation, GetCameraCenter)
+int ccm_frame_set_pose(ccm_frame* f, const float* Tcw, const float* Ow)
+{
+    if (!f) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    return ccm_guard(c, "ccm_frame_set_pose", [&]() -> int {
+        if (!Tcw || !Ow) return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_pose: null %s", !Tcw ? "Tcw" : "Ow");
+        CCM_HIP(c, hipSetDevice(c->device));
+        int rc = kf_block(c, f);
+        if (rc) return rc;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, sizeof(MapCam), &h))) return rc;
+        MapCam m = f->cam;
+        std::memcpy(m.Tcw, Tcw, 48); std::memcpy(m.Ow, Ow, 12);
+        std::memcpy(h, &m, sizeof(MapCam));
+        if ((rc = frame_upload(c, 0, sizeof(MapCam), f->d_cam))) return rc;
+        f->cam = m; f->has_pose = true;
+        return CCM_OK;
+    });
+}
+
+int ccm_frame_debug_bow(ccm_frame* f, int32_t* order, int32_t* nodes, int32_t* first)
+{
+    if (!f || !order || !nodes || !first) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    if (!f->has_bow) return ccm_fail(c, CCM_E_STATE, "ccm_frame_debug_bow: no bow");
+    CCM_HIP(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = frame_fetch(c, order, f->order, (size_t)f->n_bow * 4)) || (rc = frame_fetch(c, nodes, f->nodes, (size_t)f->n_nodes * 4)) ||
+        (rc = frame_fetch(c, first, f->first, ((size_t)f->n_nodes + 1) * 4)))
+        return rc;
+    return f->n_nodes;
 }
 
 // ORBmatcher::SearchByProjection(Frame&, const vector<mpptr>&, th), ORBmatcher.cpp:71-148, frame side from the handle

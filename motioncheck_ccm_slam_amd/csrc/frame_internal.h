@@ -4,6 +4,7 @@
 #pragma once
 #include "ccm_internal.h"
 #include "window_types.h"
+#include "map_math.h"
 
 struct FrameBuildArgs {                          // must match frame_kernels.hip
     int n, cols, rows; float min_x, min_y, inv_w, inv_h;
@@ -27,6 +28,11 @@ void frame_launch_prep_last(hipStream_t, int nq, const uint8_t* valid, const int
 void frame_launch_scatter_ids(hipStream_t, int n, const int* match, const int* src, const int* status, int* mp_id);
 void frame_launch_pose_gather(hipStream_t, const PoseGatherArgs&);
 void frame_launch_pose_scatter(hipStream_t, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier);
+struct KfGatherArgs {                            // must match frame_kernels.hip
+    int m; const int* order; const float* kx; const float* ky; const int* oct; const uint8_t* desc; const float* sf; const float* sig2;
+    MapFeat* feat_o; uint8_t* desc_o;
+};
+void frame_launch_kf_gather(hipStream_t, const KfGatherArgs&);
 int orb_last_result(ccm_ctx*, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
                     int* nlevels);
 
@@ -43,10 +49,22 @@ struct ccm_frame {
     bool has_angle = false;
     float* kx = nullptr; float* ky = nullptr; int* oct = nullptr; float* angle = nullptr; uint8_t* desc = nullptr;
     int* mp_id = nullptr; int* cell_items = nullptr; int* cell_first = nullptr;
+    // ---- the keyframe part (ccm_frame_set_bow / _camera / _pose), a second block taken on the first setter.  Layout: node [n] |
+    // order [n] | nodes [n] | first [n + 1] (one upload per set_bow) | feat_o [n] MapFeat | desc_o [n][32] (node-ordered copies,
+    // gathered on the device once bow and camera are both there) | sf, sig2 [kMaxLevels] | cam.
+    static const int kMaxLevels = 256;           // ccm_frame_create admits octaves up to 255
+    FrameMem* kf_mem = nullptr;
+    bool has_bow = false, has_cam = false, has_pose = false;
+    int n_bow = 0, n_nodes = 0, cam_levels = 0;  // features with a node; distinct nodes; n_levels of set_camera
+    float sf1 = 0;                               // scale_factors[1] (ratioFactor of CreateNewMapPoints, :307)
+    MapCam cam = {};                             // host copy of *d_cam: set_camera writes the intrinsics, set_pose Tcw and Ow
+    int* node = nullptr; int* order = nullptr; int* nodes = nullptr; int* first = nullptr;
+    MapFeat* feat_o = nullptr; uint8_t* desc_o = nullptr; float* sf = nullptr; float* sig2 = nullptr; MapCam* d_cam = nullptr;
 };
 
 struct FrameState {
     std::vector<FrameMem*> pool;                 // free blocks
+    std::vector<FrameMem*> kf_pool;              // free blocks of keyframe parts
     std::vector<ccm_frame*> live;
     DevBuf io;                                   // per-call device staging, [results | inputs]
     uint8_t* host = nullptr; size_t host_cap = 0;  // page-locked, same layout as io
@@ -73,6 +91,8 @@ int frame_download(ccm_ctx* c, size_t b);
 int frame_fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 // CCM_E_ARG for a handle of another context or one that outlived its context
 int frame_check(ccm_ctx* c, const ccm_frame* f);
+// What a handle lacks to serve as a keyframe of CreateNewMapPoints ("bow", "camera", "pose"), or nullptr
+const char* frame_keyframe_lacks(const ccm_frame* f);
 
 // One windowed-matcher call whose queries already lie in device memory: the candidate lists with their capacity retry, the
 // single-workgroup acceptance kernel (or the host acceptance loops) and the scatter of the new map-point ids into the handle.

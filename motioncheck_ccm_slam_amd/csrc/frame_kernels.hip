@@ -5,9 +5,11 @@
 //   k_frame_scatter_ids   mvpMapPoints of the newly matched features
 //   k_frame_pose_gather   the correspondences of PoseOptimizationClient in feature order (compaction, first[] on the device)
 //   k_frame_pose_scatter  mvbOutlier per feature
+//   k_frame_kf_gather     the keyframe part: node-ordered copies of the descriptors and of what the pair tests read per feature
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/ccm_hot.h"
+#include "map_math.h"
 
 #define FB_TPB 1024
 
@@ -164,6 +166,25 @@ __global__ void k_frame_pose_scatter(int n, const int* kof, const int* first, co
     outlier[i] = (k >= 0 && k < first[1]) ? outl[k] : 0;
 }
 
+struct KfGatherArgs {                            // must match frame_internal.h
+    int m; const int* order; const float* kx; const float* ky; const int* oct; const uint8_t* desc; const float* sf; const float* sig2;
+    MapFeat* feat_o; uint8_t* desc_o;
+};
+
+// Position p of the node order (ccm_frame_set_bow) holds feature order[p]: its 32-byte descriptor and MapFeat {x, y,
+// mvLevelSigma2[octave], mvScaleFactors[octave]} are copied there, so that a wave of k_cnmp_match_frames scanning a node range reads
+// contiguous 16-byte words and not a gather through the index.
+__global__ __launch_bounds__(256) void k_frame_kf_gather(KfGatherArgs A)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= A.m) return;
+    const int i = A.order[p], o = A.oct[i];
+    A.feat_o[p] = MapFeat{ A.kx[i], A.ky[i], A.sig2[o], A.sf[o] };
+    const uint4* s = reinterpret_cast<const uint4*>(A.desc + (size_t)i * 32);
+    uint4* d = reinterpret_cast<uint4*>(A.desc_o + (size_t)p * 32);
+    d[0] = s[0]; d[1] = s[1];
+}
+
 size_t frame_build_lds(int cells) { return ((size_t)2 * cells + 1) * 4; }
 
 int frame_launch_build(hipStream_t s, const FrameBuildArgs& A)
@@ -188,4 +209,8 @@ void frame_launch_pose_gather(hipStream_t s, const PoseGatherArgs& A)
 void frame_launch_pose_scatter(hipStream_t s, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier)
 {
     if (n > 0) hipLaunchKernelGGL(k_frame_pose_scatter, dim3((n + 255) / 256), dim3(256), 0, s, n, kof, first, outl, outlier);
+}
+void frame_launch_kf_gather(hipStream_t s, const KfGatherArgs& A)
+{
+    if (A.m > 0) hipLaunchKernelGGL(k_frame_kf_gather, dim3((A.m + 255) / 256), dim3(256), 0, s, A);
 }

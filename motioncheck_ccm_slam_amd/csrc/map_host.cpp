@@ -2,13 +2,16 @@
 // arguments, applies the baseline rule (:319-328), orders every neighbour's candidate features by vocabulary node with a counting
 // pass, flattens everything into one page-locked staging area (one upload), queues the three launches of map_kernels.hip and one
 // download of the result list, and synchronises once.  The tap arrays are downloaded only when a tap is given.
-#include "ccm_internal.h"
+// ccm_create_new_map_points_frames is the same call on frame handles (frame_internal.h): the keyframes already lie in device memory
+// in node order, so the staged upload holds the per-neighbour MapKf records and a table of per-keyframe device views, nothing else.
+#include "frame_internal.h"
 #include "map_types.h"
 #include <cmath>
 
 void map_match_launch(hipStream_t, const MapDev&);
 void map_triangulate_launch(hipStream_t, const MapDev&);
 void map_resolve_launch(hipStream_t, const MapDev&);
+void map_frames_launch(hipStream_t, const MapFramesDev&);
 
 // One page-locked staging area and its device twin, laid out [inputs | per-pair work arrays | result list], and the node table of the
 // counting pass: cid[node] = 1 + compact id of a node of the current keyframe, all zero between calls.
@@ -25,8 +28,6 @@ static_assert((int)MAP_SKIPPED_KF == (int)CCM_NP_SKIPPED_KF && (int)MAP_NO_MATCH
               (int)MAP_BEHIND_1 == (int)CCM_NP_BEHIND_1 && (int)MAP_SCALE == (int)CCM_NP_SCALE && (int)MAP_OK == (int)CCM_NP_OK &&
               (int)MAP_SUPERSEDED == (int)CCM_NP_SUPERSEDED,
               "MAP_* of map_math.h and CCM_NP_* of ccm_hot.h are one list");
-
-static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
 
 static const int kMaxNode = 1 << 24, kMaxFeatures = (1 << MAP_POS_BITS) - 1;
 
@@ -232,6 +233,123 @@ extern "C" int ccm_create_new_map_points(ccm_ctx* c, const ccm_new_points_proble
                         tap->match[t] = (cnode1[i] >= 0 && mpos[t] >= 0) ? hi2[mpos[t]] : -1;      // mpos is written for the features of free1 only
                     }
             }
+            if (tap->status) std::memcpy(tap->status, h + o_status, pairs);
+            if (tap->x3d_all) std::memcpy(tap->x3d_all, h + o_X, pairs * 12);
+        }
+        return n_new;
+    });
+}
+
+static MapKfView view_of(const ccm_frame* f)
+{
+    return MapKfView{ f->d_cam, f->kx, f->ky, f->oct, f->mp_id, f->desc, f->sf, f->sig2, f->node, f->order, f->nodes, f->first, f->feat_o, f->desc_o,
+                      f->n, f->n_nodes };
+}
+
+extern "C" int ccm_create_new_map_points_frames(ccm_ctx* c, const ccm_new_points_frames* pb, ccm_new_points_result* res)
+{
+    RoctxRange roctx_("ccm_create_new_map_points_frames");
+    return ccm_guard(c, "ccm_create_new_map_points_frames", [&]() -> int {
+        const char* fn = "ccm_create_new_map_points_frames";
+        if (!c) return CCM_E_ARG;
+        if (!pb || !res) return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !pb ? "problem" : "result");
+        if (!pb->current) return ccm_fail(c, CCM_E_ARG, "%s: null current", fn);
+        if (pb->n_kf < 0) return ccm_fail(c, CCM_E_ARG, "%s: n_kf = %d", fn, pb->n_kf);
+        const int n_kf = pb->n_kf;
+        if (n_kf > 0 && (!pb->neighbours || !pb->F12 || !pb->epipole || !pb->median_depth))
+            return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !pb->neighbours ? "neighbours" : !pb->F12 ? "F12" : !pb->epipole ? "epipole" : "median_depth");
+        const ccm_frame* cur = pb->current;
+        auto check_handle = [&](const ccm_frame* f, const char* who) -> int {
+            if (!f) return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, who);
+            if (!f->ctx || f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: %s %s", fn, who, !f->ctx ? "outlived its context" : "belongs to another context");
+            return CCM_OK;
+        };
+        int rc = check_handle(cur, "current");
+        if (rc) return rc;
+        const int n1 = cur->n;
+        char who[40];
+        for (int k = 0; k < n_kf; k++) {
+            snprintf(who, sizeof who, "neighbours[%d]", k);
+            if ((rc = check_handle(pb->neighbours[k], who))) return rc;
+            if (!(pb->median_depth[k] > 0.0f)) return ccm_fail(c, CCM_E_ARG, "%s: median_depth[%d] = %g is not positive", fn, k, (double)pb->median_depth[k]);
+        }
+        if (!res->first) return ccm_fail(c, CCM_E_ARG, "%s: null first", fn);
+        if (n1 > 0 && (!res->kf || !res->idx1 || !res->idx2 || !res->x3d))
+            return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !res->kf ? "kf" : !res->idx1 ? "idx1" : !res->idx2 ? "idx2" : "x3d");
+        if ((long long)n_kf * n1 > (1ll << 30)) return ccm_fail(c, CCM_E_ARG, "%s: n_kf * current.n = %lld above 2^30", fn, (long long)n_kf * n1);
+        if (n_kf == 0 || n1 == 0) {                                          // nothing to match: no device work
+            for (int k = 0; k <= n_kf; k++) res->first[k] = 0;
+            res->n_new = 0;
+            return 0;
+        }
+        if (const char* lacks = frame_keyframe_lacks(cur)) return ccm_fail(c, CCM_E_STATE, "%s: current: no %s", fn, lacks);
+        for (int k = 0; k < n_kf; k++)
+            if (const char* lacks = frame_keyframe_lacks(pb->neighbours[k])) return ccm_fail(c, CCM_E_STATE, "%s: neighbours[%d]: no %s", fn, k, lacks);
+        if (cur->cam_levels < 2) return ccm_fail(c, CCM_E_ARG, "%s: current.n_levels = %d, at least 2 needed", fn, cur->cam_levels);   // ratioFactor reads scale_factors[1]
+        ccm_new_points_tap* tap = res->tap;
+        CCM_HIP(c, hipSetDevice(c->device));
+        if (!c->map) c->map = new MapState();
+        MapState& St = *c->map;
+
+        // ---- staging: [MapKf | views] up, [per-pair work arrays] and [result list] down
+        const size_t pairs = (size_t)n_kf * n1;
+        size_t off = 0;
+        const size_t o_kf = seg(off, (size_t)n_kf * sizeof(MapKf)), o_view = seg(off, (size_t)(1 + n_kf) * sizeof(MapKfView));
+        const size_t in_end = off;
+        const size_t o_midx = seg(off, pairs * 4), o_gate = seg(off, pairs), o_status = seg(off, pairs), o_X = seg(off, pairs * 12);
+        const size_t work_end = off;
+        const size_t o_first = seg(off, (size_t)(n_kf + 1) * 4), o_okf = seg(off, (size_t)n1 * 4), o_oi1 = seg(off, (size_t)n1 * 4);
+        const size_t o_oi2 = seg(off, (size_t)n1 * 4), o_ox = seg(off, (size_t)n1 * 12);
+        const size_t end = off;
+        if (end > St.host_cap) {
+            if (St.host) (void)hipHostFree(St.host);
+            St.host = nullptr; St.host_cap = 0;
+            const size_t want = end + end / 4 + 4096;
+            if (hipHostMalloc((void**)&St.host, want, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError(); St.host = nullptr;
+                return ccm_fail(c, CCM_E_NOMEM, "page-locked staging of %zu bytes failed", want);
+            }
+            St.host_cap = want;
+        }
+        CCM_RESERVE(c, St.io, end);
+        uint8_t* h = St.host;                                                // free: every call ends with a synchronisation
+        MapKf* hkf = reinterpret_cast<MapKf*>(h + o_kf);
+        MapKfView* hv = reinterpret_cast<MapKfView*>(h + o_view);
+        hv[0] = view_of(cur);
+        for (int k = 0; k < n_kf; k++) {
+            const ccm_frame* kf = pb->neighbours[k];
+            hv[1 + k] = view_of(kf);
+            hkf[k].skipped = map_baseline_too_short(cur->cam.Ow, kf->cam.Ow, pb->median_depth[k]) ? 1 : 0;   // :319-328 on the handles' host copies
+            hkf[k].ex = pb->epipole[2 * k]; hkf[k].ey = pb->epipole[2 * k + 1];
+            std::memcpy(hkf[k].F12, pb->F12 + 9 * (size_t)k, 36);
+        }
+        hipStream_t st = c->stream;
+        uint8_t* d = St.io.as<uint8_t>();
+        CCM_HIP(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st));
+        MapFramesDev D{};
+        D.n1 = n1; D.n_kf = n_kf;
+        D.ratioFactor = 1.5f * cur->sf1;                                     // :307
+        D.kf = reinterpret_cast<const MapKf*>(d + o_kf); D.view = reinterpret_cast<const MapKfView*>(d + o_view);
+        D.midx = reinterpret_cast<int32_t*>(d + o_midx); D.gate = d + o_gate; D.status = d + o_status; D.X = reinterpret_cast<float*>(d + o_X);
+        D.first = reinterpret_cast<int32_t*>(d + o_first); D.out_kf = reinterpret_cast<int32_t*>(d + o_okf);
+        D.out_idx1 = reinterpret_cast<int32_t*>(d + o_oi1); D.out_idx2 = reinterpret_cast<int32_t*>(d + o_oi2); D.out_x3d = reinterpret_cast<float*>(d + o_ox);
+        map_frames_launch(st, D);
+        CCM_HIP(c, hipGetLastError());
+        CCM_HIP(c, hipMemcpyAsync(h + work_end, d + work_end, end - work_end, hipMemcpyDeviceToHost, st));
+        const bool want_tap = tap && (tap->match || tap->status || tap->x3d_all);
+        if (want_tap) CCM_HIP(c, hipMemcpyAsync(h + in_end, d + in_end, work_end - in_end, hipMemcpyDeviceToHost, st));
+        CCM_HIP(c, hipStreamSynchronize(st));
+
+        // ---- outputs
+        const int32_t* first = reinterpret_cast<const int32_t*>(h + o_first);
+        const int n_new = first[n_kf];
+        if (n_new < 0 || n_new > n1) return ccm_fail(c, CCM_E_DEVICE, "%s: the device reported %d new points for %d features", fn, n_new, n1);
+        std::memcpy(res->first, first, (size_t)(n_kf + 1) * 4);
+        std::memcpy(res->kf, h + o_okf, (size_t)n_new * 4); std::memcpy(res->idx1, h + o_oi1, (size_t)n_new * 4);
+        std::memcpy(res->idx2, h + o_oi2, (size_t)n_new * 4); std::memcpy(res->x3d, h + o_ox, (size_t)n_new * 12);
+        res->n_new = n_new;
+        if (want_tap) {
+            if (tap->match) std::memcpy(tap->match, h + o_midx, pairs * 4);
             if (tap->status) std::memcpy(tap->status, h + o_status, pairs);
             if (tap->x3d_all) std::memcpy(tap->x3d_all, h + o_X, pairs * 12);
         }

@@ -34,3 +34,31 @@ struct MapDev {
     int32_t* first;              // [n_kf + 1]
     int32_t* out_kf; int32_t* out_idx1; int32_t* out_idx2; float* out_x3d;
 };
+
+// ---- ccm_create_new_map_points_frames: the keyframes are frame handles (frame_internal.h) and nothing of them is flattened per call.
+// One keyframe as the three *_frames kernels read it: the handle's arrays by feature index, and its keyframe part -- the features
+// that have a node ordered by (node, index), the directory of distinct nodes, and node-ordered copies of what the match reads.
+struct MapKfView {
+    const MapCam*  cam;
+    const float*   kx; const float* ky; const int32_t* oct;    // [n]
+    const int32_t* mp_id;        // [n] >= 0: the feature holds a map point
+    const uint8_t* desc;         // [n][32]
+    const float*   sf; const float* sig2;                      // mvScaleFactors, mvLevelSigma2
+    const int32_t* node;         // [n]
+    const int32_t* order;        // [first[n_nodes]] feature index at each position of the node order
+    const int32_t* nodes;        // [n_nodes] ascending
+    const int32_t* first;        // [n_nodes + 1]
+    const MapFeat* feat_o;       // node-ordered MapFeat
+    const uint8_t* desc_o;       // node-ordered descriptors
+    int32_t n, n_nodes;
+};
+struct MapFramesDev {
+    int32_t n1, n_kf;
+    float ratioFactor;
+    const MapKf*     kf;         // [n_kf]
+    const MapKfView* view;       // [1 + n_kf]: the current keyframe, then the neighbours
+    // per (k, i1), row k * n1 + i1
+    int32_t* midx;               // the match: feature index in neighbour k, -1 = none (written for every row)
+    uint8_t* gate; uint8_t* status; float* X;
+    int32_t* first; int32_t* out_kf; int32_t* out_idx1; int32_t* out_idx2; float* out_x3d;
+};

@@ -1,7 +1,6 @@
 // match_host.cpp -- C ABI of the matcher (include/ccm_hot.h): brute-force Hamming search,
 // ORBmatcher::SearchByBoW (cslam/src/ORBmatcher.cpp:178-306, 565-698; on the device, k_bow_greedy) and the windowed matchers.
-#include "ccm_internal.h"
-#include "window_types.h"
+#include "frame_internal.h"
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -730,6 +729,42 @@ int ccm_fuse_select(ccm_ctx* c, const ccm_frame_grid* kf, const float* scale_fac
     });
 }
 
+// What ccm_fuse_select_batch and ccm_fuse_select_batch_frames share once the WinGrid table lies in W.grids: the per-query windows,
+// the uploads of the queries, the launch, the download and the rows of invalid points and empty keyframes.  kf_n[k] = features of
+// keyframe k; n_levels = entries of inv_level_sigma2 the kernel may read.
+static int fuse_batch_run(ccm_ctx* c, int n_kf, const int* kf_n, int n_levels, const float* scale_factors, const float* inv_level_sigma2,
+                          const int32_t* mp_first, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
+                          const uint8_t* mp_desc, float th, int chi2_check, int accept_th, int32_t* best_idx, int32_t* best_dist)
+{
+    WindowBufs& W = window_bufs(c);
+    const int n_mp = mp_first[n_kf];
+    std::vector<float> qr(n_mp);
+    std::vector<int32_t> lo(n_mp), hi(n_mp), qkf(n_mp);
+    for (int k = 0; k < n_kf; k++)
+        for (int m = mp_first[k]; m < mp_first[k + 1]; m++) {
+            qkf[m] = k;
+            qr[m] = (valid[m] && kf_n[k] > 0) ? th * scale_factors[level[m]] : -1.f;                  // :909 / :1068
+            lo[m] = level[m] - 1; hi[m] = level[m];                                               // :925-926
+        }
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ccm_upload(c, W.qx, u, (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qy, v, (size_t)n_mp * 4, st)) ||
+        (rc = ccm_upload(c, W.qr, qr.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.minl, lo.data(), (size_t)n_mp * 4, st)) ||
+        (rc = ccm_upload(c, W.maxl, hi.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qdesc, mp_desc, (size_t)n_mp * 32, st)) ||
+        (rc = ccm_upload(c, W.qkf, qkf.data(), (size_t)n_mp * 4, st)))
+        return rc;
+    if (chi2_check && (rc = ccm_upload(c, W.is2, inv_level_sigma2, (size_t)n_levels * 4, st))) return rc;
+    CCM_RESERVE(c, W.sel_i, (size_t)n_mp * 4); CCM_RESERVE(c, W.sel_d, (size_t)n_mp * 4);
+    match_launch_window_select_batch(st, W.grids.as<WinGrid>(), W.qkf.as<int>(), n_mp, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(),
+                                     W.maxl.as<int>(), W.qdesc.as<uint8_t>(), chi2_check ? W.is2.as<float>() : nullptr, accept_th, W.sel_i.as<int>(), W.sel_d.as<int>());
+    CCM_HIP(c, hipGetLastError());
+    CCM_HIP(c, hipMemcpyAsync(best_idx, W.sel_i.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
+    CCM_HIP(c, hipMemcpyAsync(best_dist, W.sel_d.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
+    CCM_HIP(c, hipStreamSynchronize(st));                           // (the staging vectors above, and the caller's, stay alive until here)
+    for (int m = 0; m < n_mp; m++) if (!valid[m] || kf_n[qkf[m]] == 0) { best_idx[m] = -1; best_dist[m] = 256; }
+    return CCM_OK;
+}
+
 // The selection of ccm_fuse_select for n_kf keyframes in one launch: what n_kf sequential calls return (the selection reads the map
 // points' projections and descriptors and the keyframe's features only -- what an earlier keyframe's Replace / AddObservation
 // changes is which points the CALLER still applies, src/ORBmatcher.cpp:884-886, :958-990).  Map points projected into keyframe k are
@@ -752,34 +787,49 @@ int ccm_fuse_select_batch(ccm_ctx* c, int n_kf, const ccm_frame_grid* kfs, const
         for (int m = 0; m < n_mp; m++) { best_idx[m] = -1; best_dist[m] = 256; }
         if (n_mp == 0) return CCM_OK;
         CCM_HIP(c, hipSetDevice(c->device));
-        WindowBufs& W = window_bufs(c);
         KfBatch B;
         int rc = stage_keyframes(c, n_kf, kfs, B);
         if (rc) return rc;
-        std::vector<float> qr(n_mp);
-        std::vector<int32_t> lo(n_mp), hi(n_mp), qkf(n_mp);
-        for (int k = 0; k < n_kf; k++)
-            for (int m = mp_first[k]; m < mp_first[k + 1]; m++) {
-                qkf[m] = k;
-                qr[m] = (valid[m] && kfs[k].n > 0) ? th * scale_factors[level[m]] : -1.f;              // :909 / :1068
-                lo[m] = level[m] - 1; hi[m] = level[m];                                               // :925-926
-            }
-        hipStream_t st = c->stream;
-        if ((rc = ccm_upload(c, W.qx, u, (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qy, v, (size_t)n_mp * 4, st)) ||
-            (rc = ccm_upload(c, W.qr, qr.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.minl, lo.data(), (size_t)n_mp * 4, st)) ||
-            (rc = ccm_upload(c, W.maxl, hi.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qdesc, mp_desc, (size_t)n_mp * 32, st)) ||
-            (rc = ccm_upload(c, W.qkf, qkf.data(), (size_t)n_mp * 4, st)))
-            return rc;
-        if (chi2_check && (rc = ccm_upload(c, W.is2, inv_level_sigma2, (size_t)B.n_levels * 4, st))) return rc;
-        CCM_RESERVE(c, W.sel_i, (size_t)n_mp * 4); CCM_RESERVE(c, W.sel_d, (size_t)n_mp * 4);
-        match_launch_window_select_batch(st, W.grids.as<WinGrid>(), W.qkf.as<int>(), n_mp, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(),
-                                         W.maxl.as<int>(), W.qdesc.as<uint8_t>(), chi2_check ? W.is2.as<float>() : nullptr, accept_th, W.sel_i.as<int>(), W.sel_d.as<int>());
-        CCM_HIP(c, hipGetLastError());
-        CCM_HIP(c, hipMemcpyAsync(best_idx, W.sel_i.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipMemcpyAsync(best_dist, W.sel_d.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));                       // (the staging vectors above stay alive until here)
-        for (int m = 0; m < n_mp; m++) if (!valid[m] || kfs[qkf[m]].n == 0) { best_idx[m] = -1; best_dist[m] = 256; }
-        return CCM_OK;
+        std::vector<int> kf_n(n_kf);
+        for (int k = 0; k < n_kf; k++) kf_n[k] = kfs[k].n;
+        return fuse_batch_run(c, n_kf, kf_n.data(), B.n_levels, scale_factors, inv_level_sigma2, mp_first, valid, u, v, level, mp_desc, th, chi2_check,
+                              accept_th, best_idx, best_dist);
+    });
+}
+
+// ccm_fuse_select_batch on frame handles: the WinGrid table is built from the handles' device pointers and device-built grids
+// (stage_keyframes uploads nothing).  Queries and outputs as above.
+int ccm_fuse_select_batch_frames(ccm_ctx* c, int n_kf, ccm_frame* const* kfs, const float* scale_factors, const float* inv_level_sigma2,
+                                 const int32_t* mp_first, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
+                                 const uint8_t* mp_desc, float th, int chi2_check, int accept_th, int32_t* best_idx, int32_t* best_dist)
+{
+    return ccm_guard(c, "ccm_fuse_select_batch_frames", [&]() -> int {
+        if (!c) return CCM_E_ARG;
+        if (n_kf < 0 || (n_kf > 0 && (!kfs || !mp_first))) return ccm_fail(c, CCM_E_ARG, "bad Fuse batch arguments");
+        if (n_kf == 0) return CCM_OK;
+        const int n_mp = mp_first[n_kf];
+        if (mp_first[0] != 0 || n_mp < 0 || (n_mp > 0 && (!valid || !u || !v || !level || !mp_desc || !best_idx || !best_dist || !scale_factors)) ||
+            (chi2_check && !inv_level_sigma2))
+            return ccm_fail(c, CCM_E_ARG, "bad Fuse batch arguments");
+        int n_levels = 1, rc;
+        for (int k = 0; k < n_kf; k++) {
+            if (mp_first[k + 1] < mp_first[k] || !kfs[k]) return ccm_fail(c, CCM_E_ARG, "bad Fuse batch arguments");
+            if ((rc = frame_check(c, kfs[k]))) return rc;
+            n_levels = std::max(n_levels, kfs[k]->n_levels);
+        }
+        for (int m = 0; m < n_mp; m++) { best_idx[m] = -1; best_dist[m] = 256; }
+        if (n_mp == 0) return CCM_OK;
+        CCM_HIP(c, hipSetDevice(c->device));
+        std::vector<WinGrid> grids(n_kf);
+        std::vector<int> kf_n(n_kf);
+        for (int k = 0; k < n_kf; k++) {
+            const ccm_frame* f = kfs[k];
+            grids[k] = WinGrid{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+            kf_n[k] = f->n;
+        }
+        if ((rc = ccm_upload(c, window_bufs(c).grids, grids.data(), grids.size() * sizeof(WinGrid), c->stream))) return rc;
+        return fuse_batch_run(c, n_kf, kf_n.data(), n_levels, scale_factors, inv_level_sigma2, mp_first, valid, u, v, level, mp_desc, th, chi2_check,
+                              accept_th, best_idx, best_dist);
     });
 }
 

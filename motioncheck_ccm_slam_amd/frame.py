@@ -80,6 +80,37 @@ class DeviceFrame:
         self.ctx.check(self.lib.ccm_frame_debug_grid(C.c_void_p(self.handle), _lib.ptr(first), _lib.ptr(items)))
         return first, items[:first[-1]]
 
+    # ---- the keyframe side (ccm_frame_set_bow / _camera / _pose): what LocalMapping reads of a keyframe
+    def set_bow(self, node):
+        """FeatureVector node per feature (-1 = none); None clears it."""
+        a = None
+        if node is not None:
+            a = np.ascontiguousarray(node, "i4").reshape(-1)
+            if len(a) != self.n:
+                raise ValueError("set_bow needs %d nodes" % self.n)
+            if self.n == 0:
+                a = np.full(1, -1, "i4")                       # an empty array may have no address; None would clear the bow
+        self.ctx.check(self.lib.ccm_frame_set_bow(C.c_void_p(self.handle), _lib.ptr(a)))
+
+    def set_camera(self, K, scale_factors, level_sigma2):
+        """K = (fx, fy, cx, cy); mvScaleFactors and mvLevelSigma2, as many levels each."""
+        K = np.ascontiguousarray(K, "f4").reshape(4)
+        sf = np.ascontiguousarray(scale_factors, "f4").reshape(-1); s2 = np.ascontiguousarray(level_sigma2, "f4").reshape(-1)
+        if len(sf) != len(s2):
+            raise ValueError("scale_factors and level_sigma2 differ in length")
+        self.ctx.check(self.lib.ccm_frame_set_camera(C.c_void_p(self.handle), *[float(x) for x in K], _lib.ptr(sf), _lib.ptr(s2), len(sf)))
+
+    def set_pose(self, Tcw, Ow):
+        """Tcw [3][4] = [Rcw | tcw], Ow [3] = GetCameraCenter()."""
+        T = np.ascontiguousarray(Tcw, "f4").reshape(12); O = np.ascontiguousarray(Ow, "f4").reshape(3)
+        self.ctx.check(self.lib.ccm_frame_set_pose(C.c_void_p(self.handle), _lib.ptr(T), _lib.ptr(O)))
+
+    def bow(self):
+        """(order, nodes, first) of the device-resident node directory (ccm_frame_debug_bow)."""
+        order = np.zeros(max(self.n, 1), "i4"); nodes = np.zeros(max(self.n, 1), "i4"); first = np.zeros(self.n + 1, "i4")
+        nn = self.ctx.check(self.lib.ccm_frame_debug_bow(C.c_void_p(self.handle), _lib.ptr(order), _lib.ptr(nodes), _lib.ptr(first)))
+        return order[:first[nn]], nodes[:nn], first[:nn + 1]
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.ccm_frame_destroy(C.c_void_p(self.handle))

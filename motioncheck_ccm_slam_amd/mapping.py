@@ -122,6 +122,34 @@ class LocalMapping:
                                                 x3d_all=t["x3d_all"][:n_kf * n1].reshape(n_kf, n1, 3))
         return n_new, kf[:n_new], idx1[:n_new], idx2[:n_new], x3d[:n_new], first
 
+    def CreateNewMapPointsFrames(self, current, neighbours, median_depth, F12, epipole, tap: bool = True):
+        """CreateNewMapPoints on keyframe handles (ccm_create_new_map_points_frames): current and neighbours are DeviceFrame objects
+        with bow, camera and pose set; has_mp is map_points >= 0 as the handles hold it.  F12 [n_kf][3][3] and epipole [n_kf][2] come
+        from the caller (compute_f12 / compute_epipole).  Same return tuple and tap() as CreateNewMapPoints."""
+        n_kf, n1 = len(neighbours), current.n
+        F12 = np.ascontiguousarray(F12, "f4").reshape(n_kf, 9)
+        epipole = np.ascontiguousarray(epipole, "f4").reshape(n_kf, 2)
+        md = np.ascontiguousarray(median_depth, "f4").reshape(-1)
+        if len(md) != n_kf:
+            raise ValueError("median_depth has %d entries for %d neighbours" % (len(md), n_kf))
+        p = _lib.ptr
+        nb = (C.c_void_p * max(n_kf, 1))(*[kf.handle for kf in neighbours])
+        pb = _lib.NewPointsFrames(current.handle, n_kf, nb, p(F12), p(epipole), p(md))
+        rows = max(n1, 1)
+        kf = np.zeros(rows, "i4"); idx1 = np.zeros(rows, "i4"); idx2 = np.zeros(rows, "i4"); x3d = np.zeros((rows, 3), "f4")
+        first = np.zeros(n_kf + 1, "i4")
+        res = _lib.NewPointsResult(0, p(kf), p(idx1), p(idx2), p(x3d), p(first), None)
+        t = None
+        if tap:
+            pairs = max(n_kf * n1, 1)
+            t = dict(match=np.full(pairs, -1, "i4"), status=np.zeros(pairs, "u1"), x3d_all=np.zeros((pairs, 3), "f4"))
+            tp = _lib.NewPointsTap(p(t["match"]), p(t["status"]), p(t["x3d_all"]))
+            res.tap = C.pointer(tp)
+        n_new = self.ctx.check(self.lib.ccm_create_new_map_points_frames(self.ctx.handle, C.byref(pb), C.byref(res)))
+        self._tap = None if t is None else dict(match=t["match"][:n_kf * n1].reshape(n_kf, n1), status=t["status"][:n_kf * n1].reshape(n_kf, n1),
+                                                x3d_all=t["x3d_all"][:n_kf * n1].reshape(n_kf, n1, 3))
+        return n_new, kf[:n_new], idx1[:n_new], idx2[:n_new], x3d[:n_new], first
+
     def tap(self) -> dict:
         """Per (neighbour k, feature i1) of the last call: match [n_kf][n1] (index into neighbour k or -1), status [n_kf][n1]
         (_lib.NP_STATUS), x3d_all [n_kf][n1][3]."""

@@ -10,6 +10,9 @@
 #include <ccm_hot.h>
 #include <cstdint>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 namespace ccm_shim {
@@ -76,6 +79,63 @@ inline ccm_frame* frame_handle(const FrameT& F)
     return f;
 }
 #endif
+
+// ---- keyframe handles (cslam_mapping.cpp).  LocalMapping keeps one ccm_frame per keyframe of its neighbourhood in ITS context (a
+// handle belongs to the context that made it; LoopFinder and MapMatcher run in other threads and must not use it).  A keyframe's
+// features never change; its map-point matches and its pose do, from any thread.  The hooks below are called by the reference where
+// that happens (INTEGRATION.md "Keyframe handles": KeyFrame::AddMapPoint, EraseMapPointMatch, ReplaceMapPointMatch, SetPose call
+// keyframe_touched; KeyFrame::SetBadFlag calls keyframe_dropped); the cache sends mp_id and the pose again when the stamp it saw is
+// not the current one.  A keyframe no hook has ever touched has no stamp and is sent again on every use: forgetting the hooks costs
+// 8 KB per keyframe and call, never a stale match.  Memory: the cache holds at most kMaxKeyframeHandles handles (least recently used
+// go first, about 250 KB of device memory each at 2000 features); the stamp table holds one entry per live keyframe.
+struct KeyframeStamps {
+    std::mutex m;
+    std::map<std::pair<size_t, size_t>, uint64_t> stamp;       // absent = never touched; one entry per live keyframe a hook touched
+    std::vector<std::pair<size_t, size_t>> dropped;            // SetBadFlag since LocalMapping last looked; drained by its cache
+};
+inline KeyframeStamps& keyframe_stamps()
+{
+    static KeyframeStamps s;
+    return s;
+}
+inline void keyframe_touched(size_t id0, size_t id1)
+{
+    KeyframeStamps& S = keyframe_stamps();
+    std::lock_guard<std::mutex> lock(S.m);
+    S.stamp[std::make_pair(id0, id1)]++;
+}
+// The stamp goes and the id is queued for the cache, which destroys the handle when LocalMapping next enters one of its two calls.
+inline void keyframe_dropped(size_t id0, size_t id1)
+{
+    KeyframeStamps& S = keyframe_stamps();
+    std::lock_guard<std::mutex> lock(S.m);
+    S.stamp.erase(std::make_pair(id0, id1));
+    S.dropped.push_back(std::make_pair(id0, id1));
+}
+// 0 = never touched
+inline uint64_t keyframe_stamp(size_t id0, size_t id1)
+{
+    KeyframeStamps& S = keyframe_stamps();
+    std::lock_guard<std::mutex> lock(S.m);
+    const auto it = S.stamp.find(std::make_pair(id0, id1));
+    return it == S.stamp.end() ? 0 : it->second;
+}
+// The keyframes dropped since the last call (the list is emptied)
+inline std::vector<std::pair<size_t, size_t>> keyframes_dropped()
+{
+    KeyframeStamps& S = keyframe_stamps();
+    std::lock_guard<std::mutex> lock(S.m);
+    std::vector<std::pair<size_t, size_t>> out;
+    out.swap(S.dropped);
+    return out;
+}
+static const size_t kMaxKeyframeHandles = 192;    // SearchInNeighbors names up to 20 + 20 * 5 keyframes in one call
+// CCM_SHIM_KEYFRAME_HANDLES=0: CreateNewMapPoints and SearchInNeighbors go back to uploading every keyframe per call
+inline bool keyframe_handles_on()
+{
+    static const bool on = !(getenv("CCM_SHIM_KEYFRAME_HANDLES") && atoi(getenv("CCM_SHIM_KEYFRAME_HANDLES")) == 0);
+    return on;
+}
 
 // per-feature vocabulary node of a DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>), -1 = none
 template <class FeatVec>

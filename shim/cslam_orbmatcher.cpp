@@ -14,6 +14,7 @@
 #include <climits>
 #include <set>
 #include "ccm_shim.h"
+#include "fuse_steps.h"
 
 namespace cslam {
 
@@ -118,70 +119,19 @@ struct KfGrid {                                   // a keyframe's features as cc
                            pKF->mfGridElementHeightInv, pKF->mnGridCols, pKF->mnGridRows};
     }
 };
-// :888-927 / :1029-1066: projection, image bounds, distance range, viewing angle, predicted level
-struct FuseQuery { std::vector<uint8_t> valid, desc; std::vector<float> u, v; std::vector<int32_t> level; };
-FuseQuery project_for_fuse(const ORBmatcher::kfptr& pKF, const cv::Mat& Rcw, const cv::Mat& tcw, const cv::Mat& Ow,
-                           const std::vector<ORBmatcher::mpptr>& pts, const std::vector<uint8_t>& candidate, bool invz_via_double)
-{
-    const int n = (int)pts.size();
-    FuseQuery q; q.valid.assign(n, 0); q.desc.assign((size_t)n * 32, 0); q.u.assign(n, 0.f); q.v.assign(n, 0.f); q.level.assign(n, 0);
-    const float fx = pKF->fx, fy = pKF->fy, cx = pKF->cx, cy = pKF->cy;
-    for (int i = 0; i < n; i++) {
-        if (!candidate[i]) continue;
-        const ORBmatcher::mpptr& pMP = pts[i];
-        const cv::Mat p3Dw = pMP->GetWorldPos();
-        const cv::Mat p3Dc = Rcw * p3Dw + tcw;
-        if (p3Dc.at<float>(2) < 0.0f) continue;
-        // (:899 divides in float, `1/z`; :1041 in double, `1.0/z`, and rounds the quotient to float: kept apart, the two can differ in the last bit)
-        const float invz = invz_via_double ? (float)(1.0 / p3Dc.at<float>(2)) : 1 / p3Dc.at<float>(2);
-        const float u = fx * (p3Dc.at<float>(0) * invz) + cx, v = fy * (p3Dc.at<float>(1) * invz) + cy;
-        if (!pKF->IsInImage(u, v)) continue;
-        const float maxDistance = pMP->GetMaxDistanceInvariance(), minDistance = pMP->GetMinDistanceInvariance();
-        const cv::Mat PO = p3Dw - Ow;
-        const float dist3D = cv::norm(PO);
-        if (dist3D < minDistance || dist3D > maxDistance) continue;
-        if (PO.dot(pMP->GetNormal()) < 0.5 * dist3D) continue;
-        q.level[i] = pMP->PredictScale(dist3D, pKF);
-        q.u[i] = u; q.v[i] = v; q.valid[i] = 1;
-        const cv::Mat d = pMP->GetDescriptor();
-        if (!d.empty()) memcpy(&q.desc[(size_t)i * 32], d.ptr<uint8_t>(), 32);
-    }
-    return q;
-}
 }  // namespace
 
 int ORBmatcher::Fuse(kfptr pKF, const std::vector<mpptr>& vpMapPoints, const float th)
 {
     const int nMPs = (int)vpMapPoints.size();
-    std::vector<uint8_t> candidate(nMPs);
-    for (int i = 0; i < nMPs; i++) {
-        const mpptr& pMP = vpMapPoints[i];
-        candidate[i] = pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF) && !pMP->mbDoNotReplace;      // :878-886
-    }
+    const std::vector<uint8_t> candidate = ccm_shim::fuse_candidates(pKF, vpMapPoints);           // :878-886
     const KfGrid G(pKF);
-    const FuseQuery q = project_for_fuse(pKF, pKF->GetRotation(), pKF->GetTranslation(), pKF->GetCameraCenter(), vpMapPoints, candidate, false);
+    const ccm_shim::FuseQuery q = ccm_shim::project_for_fuse(pKF, pKF->GetRotation(), pKF->GetTranslation(), pKF->GetCameraCenter(), vpMapPoints, candidate, false);
     std::vector<int32_t> best(nMPs, -1), dist(nMPs, 256);
     if (ccm_fuse_select(ccm_shim::ctx(), &G.g, pKF->mvScaleFactors.data(), pKF->mvInvLevelSigma2.data(), nMPs, q.valid.data(), q.u.data(), q.v.data(),
                         q.level.data(), q.desc.data(), th, /*chi2_check=*/1, TH_LOW, best.data(), dist.data()))
         throw estd::infrastructure_ex();
-    int nFused = 0;
-    for (int i = 0; i < nMPs; i++) {                                              // :956-990, in map-point order
-        if (best[i] < 0) continue;
-        const mpptr& pMP = vpMapPoints[i];
-        if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;                     // an earlier Replace changed this point: the reference skips it at :881
-        const mpptr pMPinKF = pKF->GetMapPoint(best[i]);
-        if (pMPinKF) {
-            if (!pMPinKF->isBad() && !pMPinKF->mbDoNotReplace) {
-                if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
-                else pMPinKF->Replace(pMP);
-            }
-        } else {
-            pMP->AddObservation(pKF, best[i]);
-            pKF->AddMapPoint(pMP, best[i]);
-        }
-        nFused++;
-    }
-    return nFused;
+    return ccm_shim::apply_fuse(pKF, vpMapPoints, best.data());
 }
 
 int ORBmatcher::Fuse(kfptr pKF, cv::Mat Scw, const std::vector<mpptr>& vpPoints, float th, std::vector<mpptr>& vpReplacePoint)
@@ -197,7 +147,7 @@ int ORBmatcher::Fuse(kfptr pKF, cv::Mat Scw, const std::vector<mpptr>& vpPoints,
     std::vector<uint8_t> candidate(nPoints);
     for (int i = 0; i < nPoints; i++) candidate[i] = !vpPoints[i]->isBad() && !spAlreadyFound.count(vpPoints[i]);     // :1022-1025
     const KfGrid G(pKF);
-    const FuseQuery q = project_for_fuse(pKF, Rcw, tcw, Ow, vpPoints, candidate, true);
+    const ccm_shim::FuseQuery q = ccm_shim::project_for_fuse(pKF, Rcw, tcw, Ow, vpPoints, candidate, true);
     std::vector<int32_t> best(nPoints, -1), dist(nPoints, 256);
     if (ccm_fuse_select(ccm_shim::ctx(), &G.g, pKF->mvScaleFactors.data(), nullptr, nPoints, q.valid.data(), q.u.data(), q.v.data(), q.level.data(),
                         q.desc.data(), th, /*chi2_check=*/0, TH_LOW, best.data(), dist.data()))
@@ -346,7 +296,7 @@ int ORBmatcher::SearchByProjection(kfptr pKF, cv::Mat Scw, const std::vector<mpp
     }
     for (int i = 0; i < N; i++) matched[i] = vpMatched[i] ? 1 : 0;
     const KfGrid G(pKF);
-    const FuseQuery q = project_for_fuse(pKF, Rcw, tcw, Ow, vpPoints, candidate, false);            // :336-377: the same tests as Fuse(pKF, Scw, ...), 1/z in float
+    const ccm_shim::FuseQuery q = ccm_shim::project_for_fuse(pKF, Rcw, tcw, Ow, vpPoints, candidate, false);            // :336-377: the same tests as Fuse(pKF, Scw, ...), 1/z in float
     std::vector<int32_t> best(std::max(nPoints, 1), -1);
     const int n = ccm_search_by_projection_sim3(ccm_shim::ctx(), &G.g, pKF->mvScaleFactors.data(), nPoints, q.valid.data(), q.u.data(), q.v.data(),
                                                 q.level.data(), q.desc.data(), observed.data(), matched.data(), (float)th, best.data());

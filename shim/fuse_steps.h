@@ -1,0 +1,81 @@
+// fuse_steps.h -- the host steps of ORBmatcher::Fuse (ORBmatcher.cpp:854-1000) around the selection on the GPU, shared by
+// cslam_orbmatcher.cpp (one keyframe per call) and cslam_mapping.cpp (the first loop of SearchInNeighbors, all target keyframes in
+// one ccm_fuse_select_batch_frames call, ccm_shim::fuse_into_targets).  Include after cslam/ORBmatcher.h, cslam/KeyFrame.h and cslam/MapPoint.h.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace ccm_shim {
+
+using cslam::ORBmatcher;
+
+// :888-927 / :1029-1066: projection, image bounds, distance range, viewing angle, predicted level
+struct FuseQuery { std::vector<uint8_t> valid, desc; std::vector<float> u, v; std::vector<int32_t> level; };
+inline FuseQuery project_for_fuse(const ORBmatcher::kfptr& pKF, const cv::Mat& Rcw, const cv::Mat& tcw, const cv::Mat& Ow,
+                           const std::vector<ORBmatcher::mpptr>& pts, const std::vector<uint8_t>& candidate, bool invz_via_double)
+{
+    const int n = (int)pts.size();
+    FuseQuery q; q.valid.assign(n, 0); q.desc.assign((size_t)n * 32, 0); q.u.assign(n, 0.f); q.v.assign(n, 0.f); q.level.assign(n, 0);
+    const float fx = pKF->fx, fy = pKF->fy, cx = pKF->cx, cy = pKF->cy;
+    for (int i = 0; i < n; i++) {
+        if (!candidate[i]) continue;
+        const ORBmatcher::mpptr& pMP = pts[i];
+        const cv::Mat p3Dw = pMP->GetWorldPos();
+        const cv::Mat p3Dc = Rcw * p3Dw + tcw;
+        if (p3Dc.at<float>(2) < 0.0f) continue;
+        // (:899 divides in float, `1/z`; :1041 in double, `1.0/z`, and rounds the quotient to float: kept apart, the two can differ in the last bit)
+        const float invz = invz_via_double ? (float)(1.0 / p3Dc.at<float>(2)) : 1 / p3Dc.at<float>(2);
+        const float u = fx * (p3Dc.at<float>(0) * invz) + cx, v = fy * (p3Dc.at<float>(1) * invz) + cy;
+        if (!pKF->IsInImage(u, v)) continue;
+        const float maxDistance = pMP->GetMaxDistanceInvariance(), minDistance = pMP->GetMinDistanceInvariance();
+        const cv::Mat PO = p3Dw - Ow;
+        const float dist3D = cv::norm(PO);
+        if (dist3D < minDistance || dist3D > maxDistance) continue;
+        if (PO.dot(pMP->GetNormal()) < 0.5 * dist3D) continue;
+        q.level[i] = pMP->PredictScale(dist3D, pKF);
+        q.u[i] = u; q.v[i] = v; q.valid[i] = 1;
+        const cv::Mat d = pMP->GetDescriptor();
+        if (!d.empty()) std::memcpy(&q.desc[(size_t)i * 32], d.ptr<uint8_t>(), 32);
+    }
+    return q;
+}
+
+// :878-886: the points Fuse looks at for keyframe pKF
+inline std::vector<uint8_t> fuse_candidates(const ORBmatcher::kfptr& pKF, const std::vector<ORBmatcher::mpptr>& pts)
+{
+    std::vector<uint8_t> candidate(pts.size());
+    for (size_t i = 0; i < pts.size(); i++) {
+        const ORBmatcher::mpptr& pMP = pts[i];
+        candidate[i] = pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF) && !pMP->mbDoNotReplace;
+    }
+    return candidate;
+}
+
+// :956-990 in map-point order: best[i] = the selected feature of pKF for point i, or -1.  Returns nFused.
+inline int apply_fuse(const ORBmatcher::kfptr& pKF, const std::vector<ORBmatcher::mpptr>& pts, const int32_t* best)
+{
+    int nFused = 0;
+    for (size_t i = 0; i < pts.size(); i++) {
+        if (best[i] < 0) continue;
+        const ORBmatcher::mpptr& pMP = pts[i];
+        if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;                     // an earlier Replace changed this point: the reference skips it at :881
+        const ORBmatcher::mpptr pMPinKF = pKF->GetMapPoint(best[i]);
+        if (pMPinKF) {
+            if (!pMPinKF->isBad() && !pMPinKF->mbDoNotReplace) {
+                if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+                else pMPinKF->Replace(pMP);
+            }
+        } else {
+            pMP->AddObservation(pKF, best[i]);
+            pKF->AddMapPoint(pMP, best[i]);
+        }
+        nFused++;
+    }
+    return nFused;
+}
+
+// The first Fuse loop of LocalMapping::SearchInNeighbors on keyframe handles (defined in cslam_mapping.cpp; LocalMapping's thread only)
+void fuse_into_targets(const std::vector<ORBmatcher::kfptr>& vpTargetKFs, const std::vector<ORBmatcher::mpptr>& vpMapPointMatches);
+
+}  // namespace ccm_shim
