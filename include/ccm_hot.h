@@ -496,6 +496,40 @@ int ccm_frame_search_by_projection_frame(ccm_ctx*, ccm_frame* cur, const ccm_fra
  * outside [0, n_mp) or an octave outside [0, n_levels) returns CCM_E_ARG with the outputs untouched. */
 int ccm_frame_pose_optimize(ccm_ctx*, ccm_frame* f, int n_mp, const double* mp_xyz, const float* inv_level_sigma2, int n_levels,
                             const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers);
+/* Tracking::TrackReferenceKeyFrame (src/Tracking.cpp:514-556) and the front of loop / map matching on handles: the three calls
+ * below replace Frame::ComputeBoW, SearchByBoW(KeyFrame, Frame) and the per-candidate SearchByBoW(KeyFrame, KeyFrame) loop for
+ * features that already lie in device memory.
+ *
+ * ccm_frame_compute_bow: Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cpp:268-275).  The vocabulary descent of
+ * ccm_voc_transform_dev runs on the handle's own descriptor rows and the node directory of ccm_frame_set_bow is built on the device
+ * (frames above 4096 features: on the host): nothing of the frame is uploaded.  A feature whose word has weight <= 0 (a stopped
+ * word, TemplatedVocabulary.h:1170-1190) gets node -1, as fv_node of ccm_bow_vector.  Afterwards the handle is in the state
+ * ccm_frame_set_bow leaves with the same nodes.  word_id / weight / node [N] are optional (all three or none): the per-feature
+ * results of ccm_voc_transform_dev with node = -1 for stopped words, which feed ccm_bow_vector for the caller's mBowVec; without them
+ * the call reads back two counters.  An empty vocabulary gives a bow with no feature in it (word 0, weight 0, node -1).
+ * CCM_E_ARG, the handle's bow as before: a vocabulary or a handle of another context, a vocabulary of 2^24 nodes or more, N above
+ * 2^20 - 1, only some of the three outputs.  CCM_E_STATE: a handle that outlived its context. */
+int ccm_frame_compute_bow(ccm_ctx*, ccm_frame* f, ccm_vocabulary* voc, int levelsup, int32_t* word_id, double* weight, int32_t* node);
+/* ccm_match_bow's Frame overload (ORBmatcher.cpp:178-306) on two handles that both have a bow (set_bow or compute_bow, in any mix):
+ * descriptors, angles and FeatureVector order are the handles', the group list is made on the device.  valid1 [N_kf] or NULL = kf's
+ * mp_id >= 0.  match [N_f] = the feature of kf matched to frame feature i, or -1 (vpMapPointMatches[idx2], :251).  Returns nmatches;
+ * if and only if that is >= min_matches (Tracking.cpp:526-529) the frame's mp_id is replaced as a whole: kf's mp_id of the matched
+ * feature, -1 elsewhere (mCurrentFrame->mvpMapPoints = vpMapPointMatches).  One upload (valid1, when given), one download.
+ * Errors leave match and mp_id untouched: CCM_E_ARG for a handle of another context, kf == f, check_ori with a handle created
+ * without angles; CCM_E_STATE for a handle without a bow or one that outlived its context. */
+int ccm_frame_search_by_bow(ccm_ctx*, const ccm_frame* kf, ccm_frame* f, const ccm_bow_options*,
+                            const uint8_t* valid1 /* [N_kf] or NULL: kf's mp_id >= 0 */,
+                            int min_matches, int32_t* match /* [N_f]: feature of kf, or -1 */);
+/* ccm_match_bow's KeyFrame-KeyFrame overload (ORBmatcher.cpp:565-698; strict_th is taken as 1) for kf1 against n_kf2 candidates in
+ * three launches, whatever n_kf2: the loop of LoopFinder::ComputeSim3 (src/LoopFinder.cpp:265) and MapMatcher (src/MapMatcher.cpp:
+ * 271) in front of the batched Sim3Solver.  valid1 [N1] or NULL = kf1's mp_id >= 0; valid2 = the candidates' masks concatenated,
+ * candidate k at first2[k] .. first2[k+1] (which must span its N), or NULL = each candidate's mp_id >= 0 (first2 may then be NULL).
+ * match12 [n_kf2][N1] and nmatches [n_kf2]: per candidate what ccm_match_bow returns for that pair.  The same handle may appear
+ * twice; n_kf2 = 0 returns CCM_OK.  Errors as ccm_frame_search_by_bow, naming kfs2[k]; the outputs stay untouched. */
+int ccm_search_by_bow_frames(ccm_ctx*, const ccm_frame* kf1, int n_kf2, ccm_frame* const* kfs2, const ccm_bow_options*,
+                             const uint8_t* valid1 /* [N1] or NULL */, const int32_t* first2 /* [n_kf2+1] */,
+                             const uint8_t* valid2 /* concatenated, or NULL: mp_id >= 0 */,
+                             int32_t* match12 /* [n_kf2][N1] */, int32_t* nmatches /* [n_kf2] */);
 
 /* ------------------------------------------------------------------ map-point table
  * The client's map points in device memory, one row per slot; a slot is the id the frame handles carry in mp_id.  The caller

@@ -43,6 +43,7 @@ SYMBOLS = [
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
+    "ccm_frame_compute_bow", "ccm_frame_search_by_bow", "ccm_search_by_bow_frames",
 ]
 
 
@@ -299,6 +300,9 @@ def load():
     lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
     lib.ccm_create_new_map_points.argtypes = [vp, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)]
     lib.ccm_create_new_map_points_frames.argtypes = [vp, C.POINTER(NewPointsFrames), C.POINTER(NewPointsResult)]
+    lib.ccm_frame_compute_bow.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
+    lib.ccm_frame_search_by_bow.argtypes = [vp, vp, vp, C.POINTER(BowOptions), vp, C.c_int, vp]
+    lib.ccm_search_by_bow_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(BowOptions), vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 

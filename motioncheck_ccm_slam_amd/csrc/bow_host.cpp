@@ -1,7 +1,7 @@
 // bow_host.cpp -- C ABI of the vocabulary-tree path (include/ccm_hot.h, row F3 of SURVEY.md section 8f):
 // DBoW2::TemplatedVocabulary::transform -> Frame::ComputeBoW, BowVector assembly / L1 score, and
 // MapPoint::ComputeDistinctiveDescriptors.
-#include "ccm_internal.h"
+#include "frame_internal.h"
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -15,9 +15,18 @@ struct ccm_vocabulary {
     int k = 0, L = 0, n = 0, n_words = 0, depth = 0;
     std::vector<double> weight;                 // per node (host): looked up for the word a feature lands in
     DevBuf node_first, node_count, slot_desc, slot_node, node_word;
+    DevBuf node_pos;                            // per node (device): weight > 0, a word that is not stopped (ccm_frame_compute_bow)
     DevBuf feat, word, leaf, nid;               // staging of ccm_voc_transform
     DevBuf dd, dfirst, dcount, dbest;           // staging of ccm_distinctive_descriptors
 };
+
+VocView voc_view(const ccm_vocabulary* v) { return VocView{ v->ctx, v->n, v->n_words, v->weight.data(), v->node_pos.as<uint8_t>() }; }
+
+void voc_launch_transform(const ccm_vocabulary* v, hipStream_t s, const uint8_t* feat_dev, int n, int levelsup, int* word, int* leaf, int* nid)
+{
+    bow_launch_transform(s, feat_dev, n, v->node_first.as<int>(), v->node_count.as<int>(), v->slot_desc.as<uint8_t>(), v->slot_node.as<int>(),
+                         v->node_word.as<int>(), v->L - levelsup, v->depth, word, leaf, nid);
+}
 
 extern "C" {
 
@@ -49,10 +58,12 @@ int ccm_voc_create(ccm_ctx* c, int k, int L, int n_nodes, const int32_t* parent,
         ccm_vocabulary* v = new ccm_vocabulary();
         v->ctx = c; v->k = k; v->L = L; v->n = n_nodes; v->n_words = nw; v->depth = max_depth;
         v->weight.assign(weights, weights + n_nodes);
+        std::vector<uint8_t> pos(n_nodes);
+        for (int i = 0; i < n_nodes; i++) pos[i] = weights[i] > 0 ? 1 : 0;
         struct Up { DevBuf* b; const void* src; size_t bytes; } ups[] = {
             { &v->node_first, first.data(), (size_t)n_nodes * 4 }, { &v->node_count, cnt.data(), (size_t)n_nodes * 4 },
             { &v->slot_desc, slot_desc.data(), slot_desc.size() }, { &v->slot_node, slot_node.data(), slot_node.size() * 4 },
-            { &v->node_word, word.data(), (size_t)n_nodes * 4 } };
+            { &v->node_word, word.data(), (size_t)n_nodes * 4 }, { &v->node_pos, pos.data(), (size_t)n_nodes } };
         for (auto& u : ups) {
             if (u.b->reserve(u.bytes) || hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
                 ccm_voc_destroy(v);

@@ -2,8 +2,10 @@
 //   k_voc_transform   DBoW2::TemplatedVocabulary::transform(feature, word, weight, nid, levelsup)
 //                     (cslam/thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1217-1258): L levels of a k-way Hamming argmin
 //   k_distinctive     MapPoint::ComputeDistinctiveDescriptors (cslam/src/MapPoint.cpp:957-988): least median distance
+//   k_bow_directory   the FeatureVector of Frame::ComputeBoW as a keyframe handle's node directory (ccm_frame_compute_bow)
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "bow_directory_dev.h"
 
 __device__ __forceinline__ int bow_ham256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1)
 {
@@ -76,6 +78,77 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint4* __restrict__ d
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) best_key = min(best_key, (unsigned)__shfl_xor((int)best_key, d, 64));
     if (lane == 0) best_out[p] = (int)(best_key & 0xFFFFu);
+}
+
+// The node directory of bow_directory.h built on the device from the transform's per-feature results: node[i] = nid[i], or -1 when
+// the word feature i landed in is stopped (pos[leaf[i]] == 0; TemplatedVocabulary::transform :1170-1190), then the features that
+// have a node ordered by (node, feature index), the distinct nodes ascending and their first positions.  One workgroup with the
+// nodes staged in LDS: rank(i) = #{node_j < node_i} + #{j < i : node_j == node_i} is the position of feature i in that stable
+// order (every lane reads the same LDS word at a time: a broadcast, no bank conflict); the heads of the node runs are then numbered
+// by a scan over per-thread chunks.  n <= kBowDirMax; larger frames take the host build.
+__global__ __launch_bounds__(1024) void k_bow_directory(BowDirArgs A)
+{
+    __shared__ __attribute__((aligned(16))) int key[kBowDirMax];
+    __shared__ int sorted[kBowDirMax];
+    __shared__ int wsum[16];
+    __shared__ int n_bow_s;
+    const int t = threadIdx.x, n = A.n, lane = t & 63, w = t >> 6;
+    const int NONE = 0x7fffffff;                                // sorts behind every node; never equal to one
+    const int n4 = (n + 3) & ~3;
+    if (t == 0) n_bow_s = 0;
+    for (int i = t; i < n4; i += 1024) {
+        int nd = -1;
+        if (i < n) {
+            if (A.leaf && A.pos[A.leaf[i]]) nd = A.nid[i];
+            A.node[i] = nd;
+            if (A.node_copy) A.node_copy[i] = nd;
+        }
+        key[i] = nd >= 0 ? nd : NONE;
+    }
+    __syncthreads();
+    int mine = 0;
+    for (int i = t; i < n; i += 1024) {
+        const int k = key[i];
+        if (k == NONE) continue;
+        int r = 0;
+        for (int j = 0; j < n4; j += 4) {
+            const int4 kj = *reinterpret_cast<const int4*>(&key[j]);
+            r += (kj.x < k || (kj.x == k && j < i)) ? 1 : 0;
+            r += (kj.y < k || (kj.y == k && j + 1 < i)) ? 1 : 0;
+            r += (kj.z < k || (kj.z == k && j + 2 < i)) ? 1 : 0;
+            r += (kj.w < k || (kj.w == k && j + 3 < i)) ? 1 : 0;
+        }
+        A.order[r] = i;
+        sorted[r] = k;
+        mine++;
+    }
+    atomicAdd(&n_bow_s, mine);
+    __syncthreads();
+    const int m = n_bow_s;
+    const int chunk = (m + 1023) / 1024, r0 = min(t * chunk, m), r1 = min(r0 + chunk, m);
+    int heads = 0;
+    for (int r = r0; r < r1; r++) heads += (r == 0 || sorted[r] != sorted[r - 1]) ? 1 : 0;
+    int incl = heads;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int u = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += u;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    int base = 0, total = 0;
+    for (int k = 0; k < 16; k++) { if (k < w) base += wsum[k]; total += wsum[k]; }
+    int idx = base + incl - heads;
+    for (int r = r0; r < r1; r++)
+        if (r == 0 || sorted[r] != sorted[r - 1]) { A.nodes[idx] = sorted[r]; A.first[idx] = r; idx++; }
+    if (t == 0) { A.first[total] = m; A.counts[0] = m; A.counts[1] = total; }
+}
+
+int bow_launch_directory(hipStream_t s, const BowDirArgs& A)
+{
+    if (A.n < 0 || A.n > kBowDirMax) return 1;
+    hipLaunchKernelGGL(k_bow_directory, dim3(1), dim3(1024), 0, s, A);
+    return 0;
 }
 
 void bow_launch_transform(hipStream_t s, const uint8_t* feat, int n, const int* node_first, const int* node_count, const uint8_t* slot_desc,

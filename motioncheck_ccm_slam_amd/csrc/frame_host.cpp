@@ -344,6 +344,32 @@ static int kf_gather(ccm_ctx* c, ccm_frame* f)
     return CCM_OK;
 }
 
+// The node directory built on the host from node[n] (bow_directory.h) and sent to the handle's keyframe block in one copy:
+// ccm_frame_set_bow, and ccm_frame_compute_bow for a frame above kBowDirMax.  On an argument error the handle keeps its bow.
+static int bow_install(ccm_ctx* c, ccm_frame* f, const int32_t* node, const char* fn)
+{
+    const int n = f->n;
+    if (n > (1 << 20) - 1) return ccm_fail(c, CCM_E_ARG, "%s: n = %d above %d", fn, n, (1 << 20) - 1);
+    for (int i = 0; i < n; i++)
+        if (node[i] >= (1 << 24)) return ccm_fail(c, CCM_E_ARG, "%s: node[%d] = %d, not below %d", fn, i, node[i], 1 << 24);
+    BowDirectory D;
+    bow_directory_build(node, n, D);
+    CCM_HIP(c, hipSetDevice(c->device));
+    int rc = kf_block(c, f);
+    if (rc) return rc;
+    const KfLayout L = kf_layout(n);
+    uint8_t* h = nullptr;
+    if ((rc = frame_staging(c, L.bow_end, &h))) return rc;
+    std::memcpy(h + L.node, node, (size_t)n * 4);
+    std::memcpy(h + L.order, D.order.data(), D.order.size() * 4);
+    std::memcpy(h + L.nodes, D.nodes.data(), D.nodes.size() * 4);
+    std::memcpy(h + L.first, D.first.data(), D.first.size() * 4);
+    // the copy is queued over the live directory before the event record that can still fail: then the handle has no bow at all
+    if ((rc = frame_upload(c, 0, L.bow_end, f->kf_mem->buf.p))) { f->has_bow = false; return rc; }
+    f->has_bow = true; f->n_bow = (int)D.order.size(); f->n_nodes = (int)D.nodes.size();
+    return kf_gather(c, f);
+}
+
 const char* frame_keyframe_lacks(const ccm_frame* f) { return !f->has_bow ? "bow" : !f->has_cam ? "camera" : !f->has_pose ? "pose" : nullptr; }
 
 int frame_check(ccm_ctx* c, const ccm_frame* f)
@@ -483,26 +509,70 @@ int ccm_frame_set_bow(ccm_frame* f, const int32_t* node)
     ccm_ctx* c = f->ctx;
     if (!c) return CCM_E_STATE;
     if (!node) { f->has_bow = false; return CCM_OK; }
-    return ccm_guard(c, "ccm_frame_set_bow", [&]() -> int {
-        const int n = f->n;
-        if (n > (1 << 20) - 1) return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_bow: n = %d above %d", n, (1 << 20) - 1);
-        for (int i = 0; i < n; i++)
-            if (node[i] >= (1 << 24)) return ccm_fail(c, CCM_E_ARG, "ccm_frame_set_bow: node[%d] = %d, not below %d", i, node[i], 1 << 24);
-        BowDirectory D;
-        bow_directory_build(node, n, D);
+    return ccm_guard(c, "ccm_frame_set_bow", [&]() -> int { return bow_install(c, f, node, "ccm_frame_set_bow"); });
+}
+
+// Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cpp:268-275) on a handle: the vocabulary descent on the handle's own descriptor
+// rows, then the node directory built where the nodes already are
+int ccm_frame_compute_bow(ccm_ctx* c, ccm_frame* f, ccm_vocabulary* voc, int levelsup, int32_t* word_id, double* weight, int32_t* node)
+{
+    RoctxRange roctx_("ccm_frame_compute_bow");
+    if (!c || !f || !voc) return CCM_E_ARG;
+    if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "ccm_frame_compute_bow: frame handle outlived its context");
+    int rc = frame_check(c, f);
+    if (rc) return rc;
+    const VocView V = voc_view(voc);
+    if (V.ctx != c) return ccm_fail(c, CCM_E_ARG, "ccm_frame_compute_bow: vocabulary belongs to another context");
+    if (V.n_nodes >= (1 << 24)) return ccm_fail(c, CCM_E_ARG, "ccm_frame_compute_bow: vocabulary of %d nodes, not below %d", V.n_nodes, 1 << 24);
+    if (f->n > (1 << 20) - 1) return ccm_fail(c, CCM_E_ARG, "ccm_frame_compute_bow: n = %d above %d", f->n, (1 << 20) - 1);
+    const bool want = word_id || weight || node;
+    if (want && (!word_id || !weight || !node)) return ccm_fail(c, CCM_E_ARG, "ccm_frame_compute_bow: word_id, weight and node come together or not at all");
+    return ccm_guard(c, "ccm_frame_compute_bow", [&]() -> int {
         CCM_HIP(c, hipSetDevice(c->device));
-        int rc = kf_block(c, f);
-        if (rc) return rc;
-        const KfLayout L = kf_layout(n);
+        FrameState& S = *frame_state(c);
+        hipStream_t st = c->stream;
+        const int n = f->n;
+        const bool empty = V.n_words == 0;                                     // empty(): transform() returns nothing (:1133)
+        size_t off = 0;
+        const size_t o_cnt = seg(off, 16), o_word = seg(off, (size_t)n * 4), o_leaf = seg(off, (size_t)n * 4), o_node = seg(off, (size_t)n * 4);
+        const size_t end = off;
         uint8_t* h = nullptr;
-        if ((rc = frame_staging(c, L.bow_end, &h))) return rc;
-        std::memcpy(h + L.node, node, (size_t)n * 4);
-        std::memcpy(h + L.order, D.order.data(), D.order.size() * 4);
-        std::memcpy(h + L.nodes, D.nodes.data(), D.nodes.size() * 4);
-        std::memcpy(h + L.first, D.first.data(), D.first.size() * 4);
-        // the copy is queued over the live directory before the event record that can still fail: then the handle has no bow at all
-        if ((rc = frame_upload(c, 0, L.bow_end, f->kf_mem->buf.p))) { f->has_bow = false; return rc; }
-        f->has_bow = true; f->n_bow = (int)D.order.size(); f->n_nodes = (int)D.nodes.size();
+        if ((rc = frame_staging(c, end, &h)) || (rc = kf_block(c, f))) return rc;
+        uint8_t* io = S.io.as<uint8_t>();
+        int* d_cnt = (int*)(io + o_cnt); int* d_word = (int*)(io + o_word); int* d_leaf = (int*)(io + o_leaf); int* d_node = (int*)(io + o_node);
+        if (!empty) {
+            voc_launch_transform(voc, st, f->desc, n, levelsup, d_word, d_leaf, d_node);
+            CCM_HIP(c, hipGetLastError());
+        }
+        const bool on_device = n <= kBowDirMax;
+        if (on_device) {
+            // the launch overwrites the live directory before a step that can still fail: until the counts are back the handle has no bow
+            f->has_bow = false;
+            const BowDirArgs A{ n, empty ? nullptr : d_leaf, d_node, V.pos_dev, f->node, want && !empty ? d_node : nullptr, f->order, f->nodes,
+                                f->first, d_cnt };
+            if (bow_launch_directory(st, A)) return ccm_fail(c, CCM_E_DEVICE, "k_bow_directory: n = %d refused", n);
+            CCM_HIP(c, hipGetLastError());
+        }
+        const bool fetch = !empty && (want || !on_device);
+        if (on_device || fetch) { if ((rc = frame_download(c, fetch ? end : 16))) return rc; }
+        const int32_t* h_word = (const int32_t*)(S.host + o_word); const int32_t* h_leaf = (const int32_t*)(S.host + o_leaf);
+        const int32_t* h_node = (const int32_t*)(S.host + o_node);
+        std::vector<int32_t> built;                                            // larger frames: the node per feature for the host build
+        if (!on_device) {
+            built.assign((size_t)std::max(n, 1), -1);
+            if (!empty) for (int i = 0; i < n; i++) if (V.weight[h_leaf[i]] > 0) built[i] = h_node[i];
+        }
+        if (want) {
+            for (int i = 0; i < n; i++) {
+                word_id[i] = empty ? 0 : h_word[i];
+                weight[i] = empty ? 0.0 : V.weight[h_leaf[i]];                 // m_nodes[final_id].weight (:1257)
+                node[i] = empty ? -1 : on_device ? h_node[i] : built[i];
+            }
+        }
+        if (!on_device) return bow_install(c, f, built.data(), "ccm_frame_compute_bow");
+        int cnt[2];
+        std::memcpy(cnt, S.host + o_cnt, 8);
+        f->has_bow = true; f->n_bow = cnt[0]; f->n_nodes = cnt[1];
         return kf_gather(c, f);
     });
 }

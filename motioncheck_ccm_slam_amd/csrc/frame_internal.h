@@ -5,6 +5,7 @@
 #include "ccm_internal.h"
 #include "window_types.h"
 #include "map_math.h"
+#include "bow_directory_dev.h"
 
 struct FrameBuildArgs {                          // must match frame_kernels.hip
     int n, cols, rows; float min_x, min_y, inv_w, inv_h;
@@ -35,6 +36,12 @@ struct KfGatherArgs {                            // must match frame_kernels.hip
 void frame_launch_kf_gather(hipStream_t, const KfGatherArgs&);
 int orb_last_result(ccm_ctx*, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
                     int* nlevels);
+
+// What ccm_frame_compute_bow needs of a vocabulary (bow_host.cpp): its context, sizes, the host weights and the device flags
+// "weight > 0" per node; and k_voc_transform on n descriptors in device memory (word, leaf, nid: device, [n] each).
+struct VocView { ccm_ctx* ctx; int n_nodes, n_words; const double* weight; const uint8_t* pos_dev; };
+VocView voc_view(const ccm_vocabulary*);
+void voc_launch_transform(const ccm_vocabulary*, hipStream_t, const uint8_t* feat_dev, int n, int levelsup, int* word, int* leaf, int* nid);
 
 struct FrameMem { DevBuf buf; };                 // one device block per frame, recycled through the context's pool
 

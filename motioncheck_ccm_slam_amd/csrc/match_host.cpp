@@ -23,6 +23,17 @@ struct BowDev {                                  // must match match_kernels.hip
     float nnratio; int th, strict_th, check_ori;
 };
 void match_launch_bow(hipStream_t, const BowDev&);
+struct BowFrameRec {                             // must match match_kernels.hip
+    BowDev B;
+    const int* nodes1; const int* first1; const int* nodes2; const int* first2;
+    int n_nodes2, n2;
+    const int* mp1; const int* mp2;
+    uint8_t* v1; uint8_t* v2;
+    int* match21;
+};
+void match_launch_bow_groups(hipStream_t, const BowFrameRec& one, const BowFrameRec* recs, int n_recs, int max_threads);
+void match_launch_bow_batch(hipStream_t, const BowFrameRec* recs, int n_recs, int n_groups);
+void match_launch_bow_invert(hipStream_t, const BowFrameRec&, int min_matches, int* mp_id2);
 
 struct WindowBufs { DevBuf kx, ky, oct, desc, cfirst, citems, qx, qy, qr, minl, maxl, qdesc, ci, cd, cn, sel_i, sel_d, is2, act, qlvl, qflag, flag, out, status, qang, fang, ev,
                            grids, qkf, gkf; };
@@ -32,6 +43,7 @@ struct MatchState {
     DevBuf part_best, part_second;              // per-split partial results
     DevBuf d1, d2, order2, start, len, off, dist; // BoW staging
     DevBuf order1, grp[4], bv1, bv2, ba1, ba2, taken, m12, binof, hist;   // device-side SearchByBoW
+    DevBuf bowf;                                // SearchByBoW on frame handles: group ranges, taken, bin_of and derived masks per pair
 };
 void match_state_free(MatchState* s) { delete s; }
 
@@ -301,6 +313,141 @@ int ccm_match_bow(ccm_ctx* c, const ccm_bow_options* o, const uint8_t* desc1, co
         CCM_HIP(c, hipMemcpyAsync(&nmatches, M.hist.as<int>() + 30, 4, hipMemcpyDeviceToHost, st));
         CCM_HIP(c, hipStreamSynchronize(st));
         return nmatches;
+    });
+}
+
+// ---- SearchByBoW on frame handles.  Both sides carry descriptors, angles, mp_id and the node directory in device memory: the group
+// list is made by k_bow_groups, k_bow_greedy / k_bow_filter run on the handles' arrays, and a call costs at most one upload (the
+// caller's masks, with the pair records of the batch), one download and one synchronisation.
+static int bow_handle_check(ccm_ctx* c, const ccm_frame* f, const char* fn, const char* who, int k, int check_ori)
+{
+    char name[48];
+    if (k >= 0) snprintf(name, sizeof name, "%s[%d]", who, k); else snprintf(name, sizeof name, "%s", who);
+    if (!f) return ccm_fail(c, CCM_E_ARG, "%s: %s is null", fn, name);
+    if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: %s outlived its context", fn, name);
+    if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: %s belongs to another context", fn, name);
+    if (!f->has_bow) return ccm_fail(c, CCM_E_STATE, "%s: %s has no bow", fn, name);
+    if (check_ori && !f->has_angle) return ccm_fail(c, CCM_E_ARG, "%s: orientation check against %s, created without angles", fn, name);
+    return CCM_OK;
+}
+
+// ORBmatcher::SearchByBoW(KeyFrame, Frame), ORBmatcher.cpp:178-306, as Tracking::TrackReferenceKeyFrame calls it (src/Tracking.cpp:514-529)
+int ccm_frame_search_by_bow(ccm_ctx* c, const ccm_frame* kf, ccm_frame* f, const ccm_bow_options* o, const uint8_t* valid1, int min_matches,
+                            int32_t* match)
+{
+    RoctxRange roctx_("ccm_frame_search_by_bow");
+    static const char* fn = "ccm_frame_search_by_bow";
+    if (!c || !o) return CCM_E_ARG;
+    int rc;
+    if ((rc = bow_handle_check(c, kf, fn, "kf", -1, o->check_ori)) || (rc = bow_handle_check(c, f, fn, "f", -1, o->check_ori))) return rc;
+    if (kf == f) return ccm_fail(c, CCM_E_ARG, "%s: kf and f are the same handle", fn);
+    if (f->n > 0 && !match) return ccm_fail(c, CCM_E_ARG, "%s: null match", fn);
+    return ccm_guard(c, fn, [&]() -> int {
+        CCM_HIP(c, hipSetDevice(c->device));
+        MatchState& M = *match_state(c);
+        hipStream_t st = c->stream;
+        const int n1 = kf->n, n2 = f->n, ng = kf->n_nodes;
+        size_t off = 0;
+        const size_t o_hist = seg(off, 32 * 4), o_m21 = seg(off, (size_t)n2 * 4);
+        const size_t res_end = o_m21 + (size_t)n2 * 4;
+        const size_t o_v1 = seg(off, valid1 ? (size_t)n1 : 0);
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        if (valid1) {
+            std::memcpy(h + o_v1, valid1, (size_t)n1);
+            if ((rc = frame_upload(c, o_v1, o_v1 + (size_t)n1))) return rc;
+        }
+        size_t t = 0;
+        const size_t t_grp = seg(t, 4 * (size_t)ng * 4), t_taken = seg(t, (size_t)n2), t_m12 = seg(t, (size_t)n1 * 4), t_bin = seg(t, (size_t)n1 * 4);
+        const size_t t_v1 = seg(t, (size_t)n1);
+        CCM_RESERVE(c, M.bowf, std::max<size_t>(t, 64));
+        uint8_t* io = frame_state(c)->io.as<uint8_t>(); uint8_t* tmp = M.bowf.as<uint8_t>();
+        int* grp = (int*)(tmp + t_grp);
+        uint8_t* v1 = valid1 ? io + o_v1 : tmp + t_v1;
+        BowFrameRec R{};
+        R.B = BowDev{ ng, n1, grp, grp + ng, grp + 2 * ng, grp + 3 * ng, kf->order, f->order, kf->desc, f->desc, v1, nullptr, kf->angle, f->angle,
+                      tmp + t_taken, (int*)(tmp + t_m12), (int*)(tmp + t_bin), (int*)(io + o_hist), o->nnratio, o->th, o->strict_th, o->check_ori };
+        R.nodes1 = kf->nodes; R.first1 = kf->first; R.nodes2 = f->nodes; R.first2 = f->first; R.n_nodes2 = f->n_nodes; R.n2 = n2;
+        R.mp1 = kf->mp_id; R.mp2 = f->mp_id; R.v1 = valid1 ? nullptr : v1; R.v2 = nullptr; R.match21 = (int*)(io + o_m21);
+        match_launch_bow_groups(st, R, nullptr, 1, std::max(std::max(ng, n1), n2));
+        match_launch_bow(st, R.B);
+        match_launch_bow_invert(st, R, min_matches, f->mp_id);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = frame_download(c, res_end))) return rc;
+        const uint8_t* host = frame_state(c)->host;
+        int nmatches = 0;
+        std::memcpy(&nmatches, host + o_hist + 30 * 4, 4);
+        if (n2 > 0) std::memcpy(match, host + o_m21, (size_t)n2 * 4);
+        return nmatches;
+    });
+}
+
+// ORBmatcher::SearchByBoW(KeyFrame, KeyFrame), ORBmatcher.cpp:565-698, for one keyframe against every candidate of
+// LoopFinder::ComputeSim3 (src/LoopFinder.cpp:265) / MapMatcher (src/MapMatcher.cpp:271) at once
+int ccm_search_by_bow_frames(ccm_ctx* c, const ccm_frame* kf1, int n_kf2, ccm_frame* const* kfs2, const ccm_bow_options* o, const uint8_t* valid1,
+                             const int32_t* first2, const uint8_t* valid2, int32_t* match12, int32_t* nmatches)
+{
+    RoctxRange roctx_("ccm_search_by_bow_frames");
+    static const char* fn = "ccm_search_by_bow_frames";
+    if (!c || !o) return CCM_E_ARG;
+    int rc;
+    if ((rc = bow_handle_check(c, kf1, fn, "kf1", -1, o->check_ori))) return rc;
+    if (n_kf2 < 0 || n_kf2 > 65535) return ccm_fail(c, CCM_E_ARG, "%s: n_kf2 = %d outside [0, 65535]", fn, n_kf2);
+    if (n_kf2 == 0) return CCM_OK;
+    if (!kfs2 || !nmatches || (kf1->n > 0 && !match12) || (valid2 && !first2)) return ccm_fail(c, CCM_E_ARG, "%s: null argument", fn);
+    for (int k = 0; k < n_kf2; k++) {
+        if ((rc = bow_handle_check(c, kfs2[k], fn, "kfs2", k, o->check_ori))) return rc;
+        if (first2 && first2[k + 1] - first2[k] != kfs2[k]->n)
+            return ccm_fail(c, CCM_E_ARG, "%s: first2[%d..] spans %d entries, kfs2[%d] has %d features", fn, k, first2[k + 1] - first2[k], k, kfs2[k]->n);
+    }
+    return ccm_guard(c, fn, [&]() -> int {
+        CCM_HIP(c, hipSetDevice(c->device));
+        MatchState& M = *match_state(c);
+        hipStream_t st = c->stream;
+        const int n1 = kf1->n, ng = kf1->n_nodes;
+        std::vector<size_t> at2((size_t)n_kf2 + 1, 0);                          // offsets of the candidates' features, concatenated
+        int max_n2 = 0;
+        for (int k = 0; k < n_kf2; k++) { at2[k + 1] = at2[k] + (size_t)kfs2[k]->n; max_n2 = std::max(max_n2, kfs2[k]->n); }
+        size_t off = 0;
+        const size_t o_hist = seg(off, (size_t)n_kf2 * 32 * 4), o_m12 = seg(off, (size_t)n_kf2 * n1 * 4);
+        const size_t res_end = o_m12 + (size_t)n_kf2 * n1 * 4;
+        const size_t o_rec = seg(off, (size_t)n_kf2 * sizeof(BowFrameRec)), o_v1 = seg(off, valid1 ? (size_t)n1 : 0);
+        const size_t o_v2 = seg(off, valid2 ? at2[n_kf2] : 0);
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        size_t t = 0;
+        const size_t t_grp = seg(t, (size_t)n_kf2 * 4 * ng * 4), t_taken = seg(t, at2[n_kf2]), t_bin = seg(t, (size_t)n_kf2 * n1 * 4);
+        const size_t t_v1 = seg(t, (size_t)n1), t_v2 = seg(t, at2[n_kf2]);
+        CCM_RESERVE(c, M.bowf, std::max<size_t>(t, 64));
+        uint8_t* io = frame_state(c)->io.as<uint8_t>(); uint8_t* tmp = M.bowf.as<uint8_t>();
+        uint8_t* v1 = valid1 ? io + o_v1 : tmp + t_v1;
+        BowFrameRec* recs = (BowFrameRec*)(h + o_rec);
+        for (int k = 0; k < n_kf2; k++) {
+            const ccm_frame* f = kfs2[k];
+            int* grp = (int*)(tmp + t_grp) + (size_t)k * 4 * ng;
+            uint8_t* v2 = valid2 ? io + o_v2 + at2[k] : tmp + t_v2 + at2[k];
+            BowFrameRec R{};
+            R.B = BowDev{ ng, n1, grp, grp + ng, grp + 2 * ng, grp + 3 * ng, kf1->order, f->order, kf1->desc, f->desc, v1, v2, kf1->angle, f->angle,
+                          tmp + t_taken + at2[k], (int*)(io + o_m12) + (size_t)k * n1, (int*)(tmp + t_bin) + (size_t)k * n1,
+                          (int*)(io + o_hist) + (size_t)k * 32, o->nnratio, o->th, 1, o->check_ori };
+            R.nodes1 = kf1->nodes; R.first1 = kf1->first; R.nodes2 = f->nodes; R.first2 = f->first; R.n_nodes2 = f->n_nodes; R.n2 = f->n;
+            R.mp1 = kf1->mp_id; R.mp2 = f->mp_id; R.v1 = valid1 ? nullptr : v1; R.v2 = valid2 ? nullptr : v2; R.match21 = nullptr;
+            std::memcpy(recs + k, &R, sizeof R);
+        }
+        if (valid1) std::memcpy(h + o_v1, valid1, (size_t)n1);
+        if (valid2) for (int k = 0; k < n_kf2; k++) std::memcpy(h + o_v2 + at2[k], valid2 + first2[k], (size_t)kfs2[k]->n);
+        if ((rc = frame_upload(c, o_rec, end))) return rc;
+        const BowFrameRec* d_recs = (const BowFrameRec*)(io + o_rec);
+        match_launch_bow_groups(st, BowFrameRec{}, d_recs, n_kf2, std::max(std::max(ng, n1), max_n2));
+        match_launch_bow_batch(st, d_recs, n_kf2, ng);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = frame_download(c, res_end))) return rc;
+        const uint8_t* host = frame_state(c)->host;
+        for (int k = 0; k < n_kf2; k++) std::memcpy(nmatches + k, host + o_hist + ((size_t)k * 32 + 30) * 4, 4);
+        if (n1 > 0) std::memcpy(match12, host + o_m12, (size_t)n_kf2 * n1 * 4);
+        return CCM_OK;
     });
 }
 

@@ -7,6 +7,7 @@
 //                     (the DescriptorDistance calls of SearchByBoW; the greedy acceptance stays on the host)
 // DescriptorDistance (:1653-1669) is popcount(a^b) over 8 dwords: v_xor_b32 + v_bcnt_u32_b32 with accumulate.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 
 #define BF_TILE 1024          // train descriptors staged per pass: 32 KiB of LDS
@@ -461,9 +462,9 @@ struct BowDev {
     uint8_t* taken; int* match12; int* bin_of; int* hist;             // hist[30] + [30] = kept count
     float nnratio; int th, strict_th, check_ori;
 };
-__global__ __launch_bounds__(256) void k_bow_greedy(BowDev B)
+// one wave, one node group: shared by k_bow_greedy and its batched form
+__device__ __forceinline__ void bow_greedy_group(const BowDev& B, int grp, int lane)
 {
-    const int grp = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (grp >= B.n_groups) return;
     const int a0 = B.ga[grp], a1 = B.gae[grp], b0 = B.gb[grp], b1 = B.gbe[grp];
     for (int a = a0; a < a1; a++) {
@@ -510,8 +511,12 @@ __global__ __launch_bounds__(256) void k_bow_greedy(BowDev B)
         }
     }
 }
+__global__ __launch_bounds__(256) void k_bow_greedy(BowDev B)
+{
+    bow_greedy_group(B, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+}
 // one workgroup: ComputeThreeMaxima on the 30 bin counts, then every match outside the kept bins is dropped
-__global__ __launch_bounds__(256) void k_bow_filter(BowDev B)
+__device__ __forceinline__ void bow_filter_block(const BowDev& B)
 {
     __shared__ int keep[3];
     __shared__ int cnt;
@@ -543,10 +548,96 @@ __global__ __launch_bounds__(256) void k_bow_filter(BowDev B)
     __syncthreads();
     if (threadIdx.x == 0) B.hist[30] = cnt;
 }
+__global__ __launch_bounds__(256) void k_bow_filter(BowDev B) { bow_filter_block(B); }
 void match_launch_bow(hipStream_t s, const BowDev& B)
 {
     if (B.n_groups > 0) hipLaunchKernelGGL(k_bow_greedy, dim3((B.n_groups + 3) / 4), dim3(256), 0, s, B);
     hipLaunchKernelGGL(k_bow_filter, dim3(1), dim3(256), 0, s, B);
+}
+
+// ------------------------------------------------------------------------------------------------
+// SearchByBoW on frame handles (ccm_frame_search_by_bow, ccm_search_by_bow_frames): both sides carry their node directory (order |
+// nodes | first, ccm_frame_set_bow / ccm_frame_compute_bow) in device memory, so the group list ccm_match_bow merges on the host
+// is made here.  One record per pair; the batched forms take the pair from blockIdx.y.
+struct BowFrameRec {
+    BowDev B;                                        // n_groups = side 1's distinct nodes; ga .. gbe, taken, match12, hist are filled by k_bow_groups
+    const int* nodes1; const int* first1;            // side 1's directory
+    const int* nodes2; const int* first2;            // side 2's
+    int n_nodes2, n2;
+    const int* mp1; const int* mp2;                  // the handles' mp_id
+    uint8_t* v1; uint8_t* v2;                        // non-null: B.valid1 / B.valid2 are these, derived here as mp_id >= 0
+    int* match21;                                    // Frame overload: [n2], cleared here and filled by k_bow_invert; else null
+};
+// One thread per distinct node of side 1 looks its node up in side 2's ascending `nodes` and writes the two position ranges
+// (both empty when side 2 lacks the node); the same launch clears taken, match12, match21 and the histogram and derives the masks.
+template <bool BATCH>
+__global__ __launch_bounds__(256) void k_bow_groups(BowFrameRec one, const BowFrameRec* __restrict__ recs)
+{
+    const BowFrameRec R = BATCH ? recs[blockIdx.y] : one;
+    const BowDev& B = R.B;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < B.n_groups) {
+        const int nd = R.nodes1[t];
+        int lo = 0, hi = R.n_nodes2;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (R.nodes2[mid] < nd) lo = mid + 1; else hi = mid;
+        }
+        const bool hit = lo < R.n_nodes2 && R.nodes2[lo] == nd;
+        const_cast<int*>(B.ga)[t] = hit ? R.first1[t] : 0; const_cast<int*>(B.gae)[t] = hit ? R.first1[t + 1] : 0;
+        const_cast<int*>(B.gb)[t] = hit ? R.first2[lo] : 0; const_cast<int*>(B.gbe)[t] = hit ? R.first2[lo + 1] : 0;
+    }
+    if (t < B.n1) {
+        B.match12[t] = -1;
+        if (R.v1 && (!BATCH || blockIdx.y == 0)) R.v1[t] = R.mp1[t] >= 0 ? 1 : 0;      // one mask of side 1 serves every pair
+    }
+    if (t < R.n2) {
+        B.taken[t] = 0;
+        if (R.v2) R.v2[t] = R.mp2[t] >= 0 ? 1 : 0;
+        if (R.match21) R.match21[t] = -1;
+    }
+    if (t < 32) B.hist[t] = 0;
+}
+__global__ __launch_bounds__(256) void k_bow_greedy_batch(const BowFrameRec* __restrict__ recs)
+{
+    const BowDev B = recs[blockIdx.y].B;
+    bow_greedy_group(B, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+}
+__global__ __launch_bounds__(256) void k_bow_filter_batch(const BowFrameRec* __restrict__ recs)
+{
+    const BowDev B = recs[blockIdx.x].B;
+    bow_filter_block(B);
+}
+// Frame overload: vpMapPointMatches[idx2] = MP(idx1) (:251) -- match12 inverted (a side-2 feature is taken at most once), and,
+// when nmatches >= min_matches, the frame's mp_id replaced as a whole (Tracking.cpp:529).  One workgroup.
+__global__ __launch_bounds__(1024) void k_bow_invert(BowFrameRec R, int min_matches, int* __restrict__ mp_id2)
+{
+    const BowDev& B = R.B;
+    for (int i1 = threadIdx.x; i1 < B.n1; i1 += 1024) {
+        const int m = B.match12[i1];
+        if (m >= 0) R.match21[m] = i1;
+    }
+    __syncthreads();
+    if (B.hist[30] < min_matches) return;
+    for (int i2 = threadIdx.x; i2 < R.n2; i2 += 1024) {
+        const int m = R.match21[i2];
+        mp_id2[i2] = m >= 0 ? R.mp1[m] : -1;
+    }
+}
+void match_launch_bow_groups(hipStream_t s, const BowFrameRec& one, const BowFrameRec* recs, int n_recs, int max_threads)
+{
+    const dim3 grid((std::max(max_threads, 32) + 255) / 256, recs ? n_recs : 1);
+    if (recs) hipLaunchKernelGGL(k_bow_groups<true>, grid, dim3(256), 0, s, one, recs);
+    else hipLaunchKernelGGL(k_bow_groups<false>, grid, dim3(256), 0, s, one, recs);
+}
+void match_launch_bow_batch(hipStream_t s, const BowFrameRec* recs, int n_recs, int n_groups)
+{
+    if (n_groups > 0) hipLaunchKernelGGL(k_bow_greedy_batch, dim3((n_groups + 3) / 4, n_recs), dim3(256), 0, s, recs);
+    hipLaunchKernelGGL(k_bow_filter_batch, dim3(n_recs), dim3(256), 0, s, recs);
+}
+void match_launch_bow_invert(hipStream_t s, const BowFrameRec& R, int min_matches, int* mp_id2)
+{
+    hipLaunchKernelGGL(k_bow_invert, dim3(1), dim3(1024), 0, s, R, min_matches, mp_id2);
 }
 
 // Frame::GetFeaturesInArea (src/Frame.cpp:200-253) + the DescriptorDistance calls of the windowed matchers

@@ -92,6 +92,20 @@ class DeviceFrame:
                 a = np.full(1, -1, "i4")                       # an empty array may have no address; None would clear the bow
         self.ctx.check(self.lib.ccm_frame_set_bow(C.c_void_p(self.handle), _lib.ptr(a)))
 
+    def compute_bow(self, voc, levelsup: int = 4, outputs: bool = True):
+        """Frame::ComputeBoW / KeyFrame::ComputeBoW on the handle (ccm_frame_compute_bow): the descent of `voc` (an ORBVocabulary)
+        on the handle's own descriptors, then the node directory built on the device -- the state set_bow leaves with the same
+        nodes.  Returns (word_id, weight, node) per feature, node -1 for a stopped word (what ccm_bow_vector takes for mBowVec), or
+        None with outputs=False (nothing but two counters is read back)."""
+        if not outputs:
+            self.ctx.check(self.lib.ccm_frame_compute_bow(self.ctx.handle, C.c_void_p(self.handle), voc.handle, int(levelsup), None, None, None))
+            return None
+        m = max(self.n, 1)
+        wid = np.zeros(m, "i4"); w = np.zeros(m, "f8"); node = np.zeros(m, "i4")
+        self.ctx.check(self.lib.ccm_frame_compute_bow(self.ctx.handle, C.c_void_p(self.handle), voc.handle, int(levelsup), _lib.ptr(wid),
+                                                      _lib.ptr(w), _lib.ptr(node)))
+        return wid[:self.n], w[:self.n], node[:self.n]
+
     def set_camera(self, K, scale_factors, level_sigma2):
         """K = (fx, fy, cx, cy); mvScaleFactors and mvLevelSigma2, as many levels each."""
         K = np.ascontiguousarray(K, "f4").reshape(4)

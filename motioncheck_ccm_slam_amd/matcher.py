@@ -184,6 +184,46 @@ def _search_by_projection_frame_handle(self, cur, last, scale_factors, valid, u,
     return n, match[:cur.n], occ
 
 
+def _search_by_bow_handle(self, kf, frame, valid1=None, min_matches: int = 15):
+    """SearchByBoW(KeyFrame, Frame) on two `frame.DeviceFrame`s that both have a bow (ccm_frame_search_by_bow).  valid1 = None: kf's
+    map_points >= 0.  Returns (nmatches, match [feature of frame] = feature of kf or -1); when nmatches >= min_matches the frame's
+    map_points become kf's of the matched features and -1 elsewhere (Tracking.cpp:526-529)."""
+    v1 = None if valid1 is None else np.ascontiguousarray(valid1, np.uint8)
+    if v1 is not None and len(v1) != kf.n:
+        raise ValueError("valid1 needs %d entries" % kf.n)
+    opt = BowOptions(self.mfNNratio, int(self.mbCheckOrientation), self.TH_LOW, 0)
+    match = np.full(max(frame.n, 1), -1, "i4")
+    n = self.ctx.check(self.lib.ccm_frame_search_by_bow(self.ctx.handle, C.c_void_p(kf.handle), C.c_void_p(frame.handle), C.byref(opt),
+                                                        _lib.ptr(v1), int(min_matches), _lib.ptr(match)))
+    return n, match[:frame.n]
+
+
+def _search_by_bow_frames(self, kf1, kfs2, valid1=None, valid2=None):
+    """SearchByBoW(KeyFrame, KeyFrame) for kf1 against every DeviceFrame of kfs2 in three launches (ccm_search_by_bow_frames).
+    valid1 / valid2 (a list, one mask per candidate) = None: the handles' map_points >= 0.  Returns (nmatches [K], match12 [K][N1])."""
+    K = len(kfs2)
+    v1 = None if valid1 is None else np.ascontiguousarray(valid1, np.uint8)
+    first2 = np.zeros(K + 1, "i4")
+    for k, f in enumerate(kfs2):
+        first2[k + 1] = first2[k] + f.n
+    v2 = None
+    if valid2 is not None:
+        v2 = np.ascontiguousarray(np.concatenate([np.asarray(v, np.uint8).reshape(-1) for v in valid2]) if K else np.zeros(0), np.uint8)
+        if len(v2) != first2[-1]:
+            raise ValueError("valid2 needs one mask per candidate, as long as the candidate")
+        if len(v2) == 0:
+            v2 = np.zeros(1, np.uint8)
+    opt = BowOptions(self.mfNNratio, int(self.mbCheckOrientation), self.TH_LOW, 1)
+    m12 = np.full((max(K, 1), max(kf1.n, 1)), -1, "i4"); nm = np.zeros(max(K, 1), "i4")
+    handles = (C.c_void_p * max(K, 1))(*[f.handle for f in kfs2])
+    p = _lib.ptr
+    self.ctx.check(self.lib.ccm_search_by_bow_frames(self.ctx.handle, C.c_void_p(kf1.handle), K, handles, C.byref(opt), p(v1), p(first2), p(v2),
+                                                     p(m12), p(nm)))
+    return nm[:K], np.ascontiguousarray(m12.reshape(-1)[:K * kf1.n].reshape(K, kf1.n))
+
+
+ORBmatcher.SearchByBoWHandle = _search_by_bow_handle
+ORBmatcher.SearchByBoWFrames = _search_by_bow_frames
 ORBmatcher.SearchByProjectionHandle = _search_by_projection_handle
 ORBmatcher.SearchByProjectionFrameHandle = _search_by_projection_frame_handle
 

@@ -135,6 +135,35 @@ class Tracking:
         return pose, outl[:frame.n], int(ninl[0])
 
     @staticmethod
+    def TrackReferenceKeyFrame(frame, kf, voc, pose, intr, mp_xyz, inv_level_sigma2, nnratio=0.7, check_ori=True, min_matches=15, levelsup=4,
+                               valid1=None, mp_has_obs=None, min_inliers=10, ctx=None):
+        """Tracking::TrackReferenceKeyFrame (src/Tracking.cpp:514-556) on two `frame.DeviceFrame`s: ComputeBoW of the current frame
+        (ccm_frame_compute_bow), SearchByBoW(reference keyframe, frame) (ccm_frame_search_by_bow; the keyframe has its bow already),
+        with fewer than min_matches matches the early `return false` (:526), else PoseOptimizationClient from `pose` (the last
+        frame's, :531) and "discard outliers" (:534-553): an outlier loses its map point.  mp_xyz [n_mp][3] = the positions behind
+        the keyframe's map_points, mp_has_obs [n_mp] = Observations() > 0 of each (None: all).  Returns a dict: ok (nmatchesMap >=
+        min_inliers, :555), nmatches, match, and after the early return nothing else; otherwise pose, outlier, n_inliers, nmatches_map and mp_id (the frame's map_points as they are left)."""
+        from .matcher import ORBmatcher
+        from .optimizer import Optimizer
+        ctx = ctx or frame.ctx
+        frame.compute_bow(voc, levelsup, outputs=False)
+        nm, match = ORBmatcher(nnratio, check_ori, ctx=ctx).SearchByBoWHandle(kf, frame, valid1, min_matches)
+        if nm < min_matches:
+            return dict(ok=False, nmatches=nm, match=match)
+        p7, outl, ninl = Optimizer.PoseOptimizationFrame(frame, pose, intr, mp_xyz, inv_level_sigma2, ctx=ctx)
+        ids = frame.map_points.copy()
+        has = ids >= 0
+        drop = has & (outl != 0)
+        if drop.any():
+            ids[drop] = -1
+            frame.map_points = ids
+        keep = has & ~drop
+        if mp_has_obs is not None:
+            keep &= np.asarray(mp_has_obs, bool)[np.maximum(ids, 0)]
+        nmap = int(keep.sum())
+        return dict(ok=nmap >= min_inliers, nmatches=nm, match=match, pose=p7, outlier=outl, n_inliers=ninl, nmatches_map=nmap, mp_id=ids)
+
+    @staticmethod
     def TrackLocalMap(frame, table: MapPointTable, pose, Tcw, intr, scale_factors, inv_level_sigma2, **kw):
         """Tracking::TrackLocalMap (src/Tracking.cpp:623-727) without the fork's disabled UpdateLocalMap: SearchLocalPoints, the pose
         optimisation, then mnMatchesInliers = the features that hold a map point and are no outlier (:637-648).  Returns (search result,

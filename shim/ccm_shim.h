@@ -26,6 +26,7 @@ struct ThreadState {
     struct Slot { size_t id0 = ~(size_t)0, id1 = ~(size_t)0; int n = -1; ccm_frame* f = nullptr; unsigned used = 0; };
     // a shim object built against another version of ccm_hot.h than the library would pass structures of the wrong size
     ccm_ctx* c = ccm_abi_version() == CCM_ABI_VERSION ? ccm_create(0, 0) : nullptr;
+    ccm_vocabulary* voc = nullptr;                     // this thread's copy of the vocabulary (vocabulary() below)
     Slot slot[2];
     unsigned clock = 0;
     ThreadState() = default;
@@ -34,6 +35,7 @@ struct ThreadState {
     ~ThreadState()
     {
         for (Slot& s : slot) ccm_frame_destroy(s.f);
+        ccm_voc_destroy(voc);
         if (c) ccm_destroy(c);
     }
 };
@@ -45,6 +47,31 @@ inline ThreadState& thread_state()
 inline ccm_ctx* ctx()
 {
     return thread_state().c;                           // nullptr: every ccm_* call returns CCM_E_ARG and the shim bodies throw
+}
+
+// ---- the vocabulary.  A ccm_vocabulary lives on one context's device, so every thread that transforms (Tracking: Frame::ComputeBoW
+// on the frame handle) makes its own from the node arrays registered once after ORBVocabulary::loadFromTextFile (INTEGRATION.md
+// "ORBVocabulary": parent, descriptor and weight of m_nodes[i], with m_k, m_L, m_weighting, m_scoring).
+struct VocabularyArrays {
+    std::mutex m;
+    int k = 0, L = 0, weighting = 0, scoring = 0;
+    std::vector<int32_t> parent; std::vector<uint8_t> desc; std::vector<double> weight;
+};
+inline VocabularyArrays& vocabulary_arrays()
+{
+    static VocabularyArrays v;
+    return v;
+}
+// This thread's vocabulary, made on first use; nullptr when none is registered or it cannot be created
+inline ccm_vocabulary* vocabulary()
+{
+    ThreadState& S = thread_state();
+    if (S.voc) return S.voc;
+    VocabularyArrays& V = vocabulary_arrays();
+    std::lock_guard<std::mutex> lock(V.m);
+    if (V.parent.empty()) return nullptr;
+    if (ccm_voc_create(S.c, V.k, V.L, (int)V.parent.size(), V.parent.data(), V.desc.data(), V.weight.data(), &S.voc)) S.voc = nullptr;
+    return S.voc;
 }
 
 // CCM_SHIM_FRAME_HANDLES=0: the Frame-side matchers go back to uploading the Frame per call (A/B timing of the two paths)

@@ -9,8 +9,12 @@
 // The RANSAC parameters are part of ccm_sim3_solver_create (every hypothesis is evaluated there, in one launch), so the batch is
 // created lazily at the first iterate / find after the last SetRansacParameters.  One Sim3Solver object is a batch of one; a caller
 // that owns the candidate loop (src/LoopFinder.cpp:251-282) gets all candidates into one launch by filling one
-// ccm_sim3_ransac_problem itself.
+// ccm_sim3_ransac_problem itself.  ccm_shim::search_by_bow_candidates below is the step in front of that batch: the
+// SearchByBoW(mpCurrentKF, pKF, ...) calls of the same loop (src/LoopFinder.cpp:265, src/MapMatcher.cpp:271) as one
+// ccm_search_by_bow_frames call over all candidates.
 #include <cslam/Sim3Solver.h>
+#include <cslam/KeyFrame.h>
+#include <cslam/MapPoint.h>
 #include <map>
 #include <mutex>
 #include "ccm_shim.h"
@@ -63,6 +67,70 @@ static ccm_sim3_solver* ensure(Sim3SolverSide& S)
     pb.draws = draws.data(); pb.best_inliers = &S.best_inliers;
     if (ccm_sim3_solver_create(ctx(), &pb, &S.solver)) throw estd::infrastructure_ex();
     return S.solver;
+}
+
+// A keyframe as a handle in the calling thread's context, with the node directory of its mFeatVec; nullptr on failure.
+static ccm_frame* candidate_handle(const cslam::Sim3Solver::kfptr& pKF)
+{
+    const int n = (int)pKF->mvKeysUn.size();
+    std::vector<float> kx(n), ky(n), angle(n); std::vector<int32_t> oct(n);
+    for (int i = 0; i < n; i++) { kx[i] = pKF->mvKeysUn[i].pt.x; ky[i] = pKF->mvKeysUn[i].pt.y; oct[i] = pKF->mvKeysUn[i].octave; angle[i] = pKF->mvKeysUn[i].angle; }
+    const cv::Mat desc = pKF->mDescriptors.isContinuous() ? pKF->mDescriptors : pKF->mDescriptors.clone();
+    const ccm_frame_grid g{n, kx.data(), ky.data(), oct.data(), desc.data, (float)pKF->mnMinX, (float)pKF->mnMinY, pKF->mfGridElementWidthInv,
+                           pKF->mfGridElementHeightInv, pKF->mnGridCols, pKF->mnGridRows};
+    const std::vector<int32_t> node = nodes_of(pKF->mFeatVec, n);
+    ccm_frame* f = nullptr;
+    if (ccm_frame_create(ctx(), &g, angle.data(), &f) || ccm_frame_set_bow(f, node.data())) { ccm_frame_destroy(f); return nullptr; }
+    return f;
+}
+
+// The first loop of LoopFinder::ComputeSim3 (src/LoopFinder.cpp:251-282) and of MapMatcher (src/MapMatcher.cpp:258-290) in one call:
+// matcher.SearchByBoW(pKF1, candidates[i], vvpMatches12[i]) for every candidate (ORBmatcher(0.75, true) there), returning nmatches per
+// candidate.  The caller keeps its own tests around it (isBad candidates are passed with skip[i] != 0 and get 0 matches) and builds
+// the Sim3Solver batch from the result.  The handles are made for this call in the calling thread's context and recycled through its
+// pool; a caller that meets the same keyframes again may keep them instead.
+std::vector<int> search_by_bow_candidates(const cslam::Sim3Solver::kfptr& pKF1, const std::vector<cslam::Sim3Solver::kfptr>& candidates,
+                                          const std::vector<uint8_t>& skip, float nnratio, bool check_ori,
+                                          std::vector<std::vector<cslam::Sim3Solver::mpptr>>& vvpMatches12)
+{
+    typedef cslam::Sim3Solver::mpptr mpptr;
+    const int K = (int)candidates.size();
+    std::vector<int> result(K, 0);
+    const std::vector<mpptr> mps1 = pKF1->GetMapPointMatches();
+    const int n1 = (int)mps1.size();
+    vvpMatches12.assign(K, std::vector<mpptr>(n1));
+    std::vector<int> live;                                                     // candidates that take part
+    for (int i = 0; i < K; i++) if (skip.empty() || !skip[i]) live.push_back(i);
+    if (live.empty()) return result;
+    struct Handles {
+        std::vector<ccm_frame*> v;
+        ~Handles() { for (ccm_frame* f : v) ccm_frame_destroy(f); }
+    } H;
+    H.v.push_back(candidate_handle(pKF1));
+    std::vector<std::vector<mpptr>> mps2(live.size());
+    std::vector<int32_t> first2(live.size() + 1, 0);
+    std::vector<uint8_t> valid1(std::max(n1, 1), 0), valid2;
+    for (int i = 0; i < n1; i++) valid1[i] = mps1[i] && !mps1[i]->isBad();
+    for (size_t j = 0; j < live.size(); j++) {
+        H.v.push_back(candidate_handle(candidates[live[j]]));
+        mps2[j] = candidates[live[j]]->GetMapPointMatches();
+        for (const mpptr& p : mps2[j]) valid2.push_back(p && !p->isBad());
+        first2[j + 1] = (int32_t)valid2.size();
+    }
+    for (ccm_frame* f : H.v) if (!f) throw estd::infrastructure_ex();
+    if (valid2.empty()) valid2.push_back(0);
+    const ccm_bow_options o{nnratio, check_ori ? 1 : 0, 50, /*strict_th=*/1};  // TH_LOW; :629 compares with <
+    std::vector<int32_t> m12(live.size() * (size_t)std::max(n1, 1), -1), nm(live.size(), 0);
+    if (ccm_search_by_bow_frames(ctx(), H.v[0], (int)live.size(), H.v.data() + 1, &o, valid1.data(), first2.data(), valid2.data(), m12.data(), nm.data()))
+        throw estd::infrastructure_ex();
+    for (size_t j = 0; j < live.size(); j++) {
+        result[live[j]] = nm[j];
+        for (int i = 0; i < n1; i++) {
+            const int32_t m = m12[j * (size_t)n1 + i];
+            if (m >= 0) vvpMatches12[live[j]][i] = mps2[j][m];
+        }
+    }
+    return result;
 }
 
 }  // namespace ccm_shim

@@ -1,9 +1,9 @@
-// cslam_tracking.cpp -- drop-in bodies of cslam::Tracking::SearchLocalPoints (src/Tracking.cpp:860-922) and
-// Tracking::TrackLocalMap (:623-727) on the device-resident map-point table (ccm_hot.h "map-point table").  The reference visits
+// cslam_tracking.cpp -- drop-in bodies of cslam::Tracking::TrackReferenceKeyFrame (src/Tracking.cpp:514-556, at the end of this file),
+// Tracking::SearchLocalPoints (:860-922) and Tracking::TrackLocalMap (:623-727) on the device-resident map-point table (ccm_hot.h "map-point table").  The reference visits
 // every map point of the client's map on every tracked image (this fork sets mvpLocalMapPoints = mpMap->GetAllMapPoints(), :924-934)
 // and calls Frame::isInFrustum on each; here the map lives in a ccm_map_table, ONE ccm_frame_search_local_points call does both loops
-// and the matcher, and ONE ccm_frame_pose_optimize_table call the pose.  Remove these two bodies from src/Tracking.cpp; the rest of
-// the file stays as it is.
+// and the matcher, and ONE ccm_frame_pose_optimize_table call the pose.  Remove these three bodies from src/Tracking.cpp; the rest
+// of the file stays as it is.
 //
 // The table is filled where the map changes, not here: INTEGRATION.md "Map-point table" lists the one-line hooks in Map::AddMapPoint
 // / EraseMapPoint and MapPoint::SetWorldPos / UpdateNormalAndDepth / ComputeDistinctiveDescriptors / SetBadFlag that call
@@ -11,6 +11,7 @@
 // (GetMinDistanceInvariance returns 0.8f * mfMinDistance, which cannot be divided back exactly).
 #include <cslam/Tracking.h>
 #include <cslam/Frame.h>
+#include <cslam/KeyFrame.h>
 #include <cslam/MapPoint.h>
 #include <cslam/Map.h>
 #include <cslam/Optimizer.h>
@@ -240,6 +241,123 @@ bool Tracking::TrackLocalMap()
     if (mnMatchesInliers < params::tracking::miTrackLocalMapInlierThres)
         return false;
     return true;
+}
+
+// ---- Tracking::TrackReferenceKeyFrame (:514-556) on handles: Frame::ComputeBoW, SearchByBoW(mpReferenceKF, Frame) and
+// PoseOptimizationClient run on the current frame's handle and a handle of the reference keyframe kept in this thread's context.
+// Map points travel as slots of the map-point table, as in TrackLocalMap.
+namespace {
+
+// The reference keyframe's handle in the tracking thread's context.  mpReferenceKF changes at keyframe rate, so one cached handle
+// serves many frames; its features and FeatureVector never change, its map-point matches are sent again on every use.
+struct ReferenceHandle {
+    idpair id{~(size_t)0, ~(size_t)0};
+    ccm_frame* f = nullptr;
+    ~ReferenceHandle() { ccm_frame_destroy(f); }
+};
+
+ccm_frame* reference_handle(const Tracking::kfptr& pKF)
+{
+    static thread_local ReferenceHandle R;
+    if (R.f && R.id == pKF->mId) return R.f;
+    ccm_frame_destroy(R.f);
+    R.f = nullptr;
+    const int n = (int)pKF->mvKeysUn.size();
+    std::vector<float> kx(n), ky(n), angle(n); std::vector<int32_t> oct(n);
+    for (int i = 0; i < n; i++) { kx[i] = pKF->mvKeysUn[i].pt.x; ky[i] = pKF->mvKeysUn[i].pt.y; oct[i] = pKF->mvKeysUn[i].octave; angle[i] = pKF->mvKeysUn[i].angle; }
+    const cv::Mat desc = pKF->mDescriptors.isContinuous() ? pKF->mDescriptors : pKF->mDescriptors.clone();
+    const ccm_frame_grid g{n, kx.data(), ky.data(), oct.data(), desc.data, (float)pKF->mnMinX, (float)pKF->mnMinY, pKF->mfGridElementWidthInv,
+                           pKF->mfGridElementHeightInv, pKF->mnGridCols, pKF->mnGridRows};
+    const std::vector<int32_t> node = ccm_shim::nodes_of(pKF->mFeatVec, n);      // KeyFrame::ComputeBoW has run in its constructor's caller
+    if (ccm_frame_create(ccm_shim::ctx(), &g, angle.data(), &R.f) || ccm_frame_set_bow(R.f, node.data())) {
+        ccm_frame_destroy(R.f);
+        R.f = nullptr;
+        return nullptr;
+    }
+    R.id = pKF->mId;
+    return R.f;
+}
+
+}  // namespace
+
+bool Tracking::TrackReferenceKeyFrame()
+{
+    Frame& F = *mCurrentFrame;
+    ccm_ctx* c = ccm_shim::ctx();
+    ccm_shim::MapTable& T = ccm_shim::MapTable::get();
+    ccm_map_table* table = T.flush();
+    ccm_vocabulary* voc = ccm_shim::vocabulary();
+    ccm_frame* h = ccm_shim::frame_handle(F);
+    ccm_frame* hk = reference_handle(mpReferenceKF);
+    if (!table || !voc || !h || !hk) throw estd::infrastructure_ex();
+
+    // mCurrentFrame->ComputeBoW() (:517, src/Frame.cpp:268-275): the descent and the FeatureVector order on the handle; the
+    // per-feature results fill the Frame's own mBowVec / mFeatVec, which relocalisation and keyframe creation read later
+    const int N = F.N;
+    std::vector<int32_t> word(std::max(N, 1)), node(std::max(N, 1));
+    std::vector<double> weight(std::max(N, 1));
+    if (ccm_frame_compute_bow(c, h, voc, 4, word.data(), weight.data(), node.data())) throw estd::infrastructure_ex();
+    if (F.mBowVec.empty()) {
+        ccm_shim::VocabularyArrays& V = ccm_shim::vocabulary_arrays();
+        std::vector<int32_t> ids(std::max(N, 1)), fv(std::max(N, 1));
+        std::vector<double> vals(std::max(N, 1));
+        const int m = ccm_bow_vector(N, word.data(), weight.data(), node.data(), V.weighting, V.scoring, ids.data(), vals.data(), fv.data());
+        if (m < 0) throw estd::infrastructure_ex();
+        for (int i = 0; i < m; i++) F.mBowVec.insert(F.mBowVec.end(), std::make_pair(ids[i], vals[i]));
+        for (int i = 0; i < N; i++) if (fv[i] >= 0) F.mFeatVec.addFeature(fv[i], i);
+    }
+
+    // SearchByBoW(mpReferenceKF, *mCurrentFrame, vpMapPointMatches) (:521-524): the keyframe's good map points as table slots
+    const std::vector<mpptr> mps = mpReferenceKF->GetMapPointMatches();
+    const int n1 = (int)mps.size();
+    std::vector<int32_t> slots(std::max(n1, 1), -1);
+    std::vector<uint8_t> valid1(std::max(n1, 1), 0);
+    for (int i = 0; i < n1; i++) {
+        if (!mps[i] || mps[i]->isBad()) continue;
+        valid1[i] = 1;
+        slots[i] = T.slot_of(mps[i]);                                         // every point of the client's map has one (Map::AddMapPoint's hook)
+    }
+    if (ccm_frame_set_map_points(hk, slots.data())) throw estd::infrastructure_ex();
+    const ccm_bow_options o{0.7f, 1, 50, /*strict_th=*/0};                     // ORBmatcher matcher(0.7, true), TH_LOW
+    std::vector<int32_t> match(std::max(N, 1), -1);
+    int nmatches = ccm_frame_search_by_bow(c, hk, h, &o, valid1.data(), params::tracking::miTrackWithRefKfInlierThresSearch, match.data());
+    if (nmatches < 0) throw estd::infrastructure_ex();
+    if (nmatches < params::tracking::miTrackWithRefKfInlierThresSearch)        // :526: the handle's mp_id is untouched too
+        return false;
+
+    for (int i = 0; i < N; i++) F.mvpMapPoints[i] = match[i] >= 0 ? mps[match[i]] : mpptr();     // :529 (the handle holds the slots already)
+    F.SetPose(mLastFrame->mTcw);
+
+    // Optimizer::PoseOptimizationClient(*mCurrentFrame) (:532) on the handle and the table
+    double pose7[7];
+    float T16[16];
+    for (int r = 0; r < 4; r++) for (int cc = 0; cc < 4; cc++) T16[4 * r + cc] = F.mTcw.at<float>(r, cc);
+    ccm_pose_from_mat4f(T16, pose7);
+    const double intr[4] = {Frame::fx, Frame::fy, Frame::cx, Frame::cy};
+    std::vector<uint8_t> outlier(std::max(N, 1));
+    int32_t n_inliers = 0;
+    if (ccm_frame_pose_optimize_table(c, h, table, F.mvInvLevelSigma2.data(), (int)F.mvInvLevelSigma2.size(), intr, pose7, outlier.data(), &n_inliers))
+        throw estd::infrastructure_ex();
+    ccm_pose_to_mat4f(pose7, T16);
+    cv::Mat Tcw(4, 4, CV_32F);
+    for (int r = 0; r < 4; r++) for (int cc = 0; cc < 4; cc++) Tcw.at<float>(r, cc) = T16[4 * r + cc];
+    F.SetPose(Tcw);
+
+    // Discard outliers (:534-553)
+    int nmatchesMap = 0;
+    for (int i = 0; i < N; i++) {
+        if (!F.mvpMapPoints[i]) continue;
+        if (outlier[i]) {
+            mpptr pMP = F.mvpMapPoints[i];
+            F.mvpMapPoints[i] = nullptr;
+            F.mvbOutlier[i] = false;
+            pMP->mbTrackInView = false;
+            pMP->mLastFrameSeen = F.mId;
+            nmatches--;
+        } else if (F.mvpMapPoints[i]->Observations() > 0)
+            nmatchesMap++;
+    }
+    return nmatchesMap >= params::tracking::miTrackWithRefKfInlierThresOpt;
 }
 
 }  // namespace cslam
