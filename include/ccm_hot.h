@@ -571,6 +571,60 @@ int ccm_map_table_set_order(ccm_ctx*, ccm_map_table*, int n, const int32_t* slot
 /* Test tap (synchronises): the rows of slots [n] copied to the host; every output may be NULL.  seen [n] = the slot's stamp. */
 int ccm_map_table_fetch(ccm_ctx*, ccm_map_table*, int n, const int32_t* slot, float* pos, float* normal, float* min_dist,
                         float* max_dist, uint8_t* desc, uint8_t* flags, int32_t* seen);
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823) for a list of
+ * map points, read from keyframe handles and written into the table: what LocalMapping calls on every point it touched after
+ * CreateNewMapPoints, after Fuse (src/Mapping.cpp:471-559) and after a bundle adjustment (src/Optimizer.cpp:203, :636, :851).  The
+ * descriptors (ccm_frame_create), the camera centres (ccm_frame_set_pose), the scale factors (ccm_frame_set_camera) and the positions
+ * already lie in device memory; the call uploads the index lists only.
+ *   Observations: point p owns entries obs_first[p] .. obs_first[p+1] of obs_kf / obs_feat: mObservations in the caller's iteration
+ *   order (the reference's std::map is ordered by pointer value, so the caller fixes the order) without the entries whose keyframe
+ *   isBad() (:803, :952).  ref_kf / ref_feat = mpRefKF and mObservations[mpRefKF], which the reference reads whether or not that
+ *   keyframe is bad; they are ignored for a point without observations.
+ *   A point without observations (both functions return early): desc, normal, min_dist and max_dist of its row stay, best = -1;
+ *   pos and flags are still written when given.
+ *   CCM_MPR_DESCRIPTOR: best[p] = what ccm_distinctive_descriptors returns for the point's descriptors in list order (the least
+ *   median of its row of Hamming distances, k = (int)(0.5 * (c - 1)), the first among equal medians), and the row's desc becomes
+ *   that observation's 32 bytes.  Without this bit best[p] = -1.
+ *   CCM_MPR_NORMAL_DEPTH, in the arithmetic of a float cv::Mat as OpenCV's expression templates evaluate :797-822, with P the row's
+ *   pos after the optional write and c the number of observations:
+ *     normal = (0, 0, 0);  for each observation in list order, Ow of its keyframe:
+ *       d = P - Ow (float);  nrm = sqrt((double)d0*d0 + (double)d1*d1 + (double)d2*d2)  (cv::norm returns a double)
+ *       a = (float)(1.0 / nrm);  normal[k] = d[k] * a + normal[k]  (cv::scaleAdd: a float multiply, then a float add, not fused)
+ *     normal[k] = normal[k] * (float)(1.0 / (double)c)   (Mat / n multiplies by the reciprocal)
+ *     PC = P - Ow_ref (float);  dist = (float)sqrt(sum (double)PC^2);  level = octave_ref[ref_feat]
+ *     max_dist = dist * sf_ref[level];  min_dist = max_dist / sf_ref[n_levels_ref - 1]  (float; n_levels of ccm_frame_set_camera)
+ *   A point that coincides with a camera centre gives NaN, as in the reference.  An OpenCV built with FMA dispatch may fuse the
+ *   multiply-add of scaleAdd; the library's reading is the unfused one.
+ *   Columns `what` does not select are left as they are.
+ * One page-locked staging copy up (index lists, optional pos / flags, one small view of device pointers per keyframe), one launch on
+ * the context's stream, ordered with the other table calls: a ccm_frame_search_local_points issued afterwards sees the new rows.
+ * result (optional, each field optional): best [n] as above; normal [n][3], min_dist [n], max_dist [n] = those columns of the listed
+ * rows after the call, whether or not this call computed them.  With result == NULL or all four fields NULL the call neither
+ * downloads nor synchronises; otherwise there is one download.
+ * Errors are found on the host before anything is queued; the table and the outputs are then untouched.  CCM_E_ARG: a NULL required
+ * array (slot, kfs, obs_first; obs_kf / obs_feat when there are observations; ref_kf / ref_feat with NORMAL_DEPTH), what == 0 or with
+ * unknown bits, a slot out of range or listed twice, obs_first not ascending from 0, a keyframe index outside [0, n_kf), a feature
+ * index outside that handle's [0, N) (the message names the point and the entry), a handle or table of another context.
+ * CCM_E_STATE: a handle or table that outlived its context; with NORMAL_DEPTH an observed handle without a pose or a reference handle
+ * without a pose or a camera (the message says which).  n == 0 returns CCM_OK. */
+enum { CCM_MPR_DESCRIPTOR = 1,      /* MapPoint::ComputeDistinctiveDescriptors */
+       CCM_MPR_NORMAL_DEPTH = 2 };  /* MapPoint::UpdateNormalAndDepth */
+typedef struct {
+    int32_t          n;          /* map points */
+    const int32_t*   slot;       /* [n], each in [0, capacity), no slot twice */
+    const float*     pos;        /* [n][3] written to the table first, or NULL: the table's pos is used */
+    const uint8_t*   flags;      /* [n] written to the table, or NULL: kept */
+    int32_t          n_kf;
+    ccm_frame* const* kfs;       /* [n_kf] the keyframes the observations name; the same handle may appear twice */
+    const int32_t*   obs_first;  /* [n+1] ascending, obs_first[0] == 0 */
+    const int32_t*   obs_kf;     /* [obs_first[n]] index into kfs */
+    const int32_t*   obs_feat;   /* [obs_first[n]] feature index in that keyframe */
+    const int32_t*   ref_kf;     /* [n] mpRefKF as an index into kfs   (needed with NORMAL_DEPTH) */
+    const int32_t*   ref_feat;   /* [n] observations[pRefKF]           (needed with NORMAL_DEPTH) */
+    int32_t          what;       /* CCM_MPR_* or'ed, not 0 */
+} ccm_map_refresh;
+typedef struct { int32_t* best; float* normal; float* min_dist; float* max_dist; } ccm_map_refresh_result;  /* each [n] / [n][3], each optional */
+int ccm_map_table_refresh(ccm_ctx*, ccm_map_table*, const ccm_map_refresh*, ccm_map_refresh_result* /* or NULL */);
 
 /* Tracking::SearchLocalPoints (src/Tracking.cpp:860-922) with Frame::isInFrustum (src/Frame.cpp:139-198), MapPoint::PredictScale
  * (src/MapPoint.cpp:854-869) and ORBmatcher::SearchByProjection(Frame&, map points, th) (ORBmatcher.cpp:71-148) on a frame handle

@@ -39,7 +39,7 @@ SYMBOLS = [
     "ccm_frame_pose_optimize",
     "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
-    "ccm_map_table_fetch", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
+    "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
@@ -149,6 +149,19 @@ MP_LIVE, MP_BAD, MP_HAS_OBS = 1, 2, 4          # CCM_MP_* of include/ccm_hot.h
 class MapUpdate(C.Structure):
     _fields_ = [("n", C.c_int32), ("slot", C.c_void_p), ("pos", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p),
                 ("max_dist", C.c_void_p), ("desc", C.c_void_p), ("flags", C.c_void_p)]
+
+
+MPR_DESCRIPTOR, MPR_NORMAL_DEPTH = 1, 2        # CCM_MPR_* of include/ccm_hot.h
+
+
+class MapRefresh(C.Structure):
+    _fields_ = [("n", C.c_int32), ("slot", C.c_void_p), ("pos", C.c_void_p), ("flags", C.c_void_p), ("n_kf", C.c_int32),
+                ("kfs", C.POINTER(C.c_void_p)), ("obs_first", C.c_void_p), ("obs_kf", C.c_void_p), ("obs_feat", C.c_void_p),
+                ("ref_kf", C.c_void_p), ("ref_feat", C.c_void_p), ("what", C.c_int32)]
+
+
+class MapRefreshResult(C.Structure):
+    _fields_ = [("best", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p)]
 
 
 class SlpParams(C.Structure):
@@ -285,6 +298,7 @@ def load():
     lib.ccm_map_table_update.argtypes = [vp, vp, C.POINTER(MapUpdate)]
     lib.ccm_map_table_set_order.argtypes = [vp, vp, C.c_int, vp]
     lib.ccm_map_table_fetch.argtypes = [vp, vp, C.c_int] + [vp] * 8
+    lib.ccm_map_table_refresh.argtypes = [vp, vp, C.POINTER(MapRefresh), C.POINTER(MapRefreshResult)]
     lib.ccm_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(SlpParams), C.POINTER(SlpResult)]
     lib.ccm_frame_search_local_points_timing.argtypes = [vp, vp]
     lib.ccm_frame_pose_optimize_table.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]

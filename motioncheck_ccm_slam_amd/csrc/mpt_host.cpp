@@ -11,6 +11,7 @@
 #include "mpt_types.h"
 #include <chrono>
 #include <climits>
+#include <cstddef>
 
 struct ccm_map_table {
     ccm_ctx* ctx = nullptr;                      // nullptr once the context is gone
@@ -196,6 +197,114 @@ int ccm_map_table_fetch(ccm_ctx* c, ccm_map_table* t, int n, const int32_t* slot
         if (desc) std::memcpy(desc, h + o_desc, m * 32);
         if (flags) std::memcpy(flags, h + o_flags, m);
         if (seen) std::memcpy(seen, h + o_seen, m * 4);
+        return CCM_OK;
+    });
+}
+
+// MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823) on keyframe
+// handles.  Staging: [ best | normal | min_dist | max_dist ] down, [ slot | obs_first | obs_kf | obs_feat | ref_kf | ref_feat | pos |
+// flags | views ] up.  Everything is checked before the staging area is touched.
+int ccm_map_table_refresh(ccm_ctx* c, ccm_map_table* t, const ccm_map_refresh* u, ccm_map_refresh_result* res)
+{
+    RoctxRange roctx_("ccm_map_table_refresh");
+    if (!c || !t || !u) return CCM_E_ARG;
+    const char* fn = "ccm_map_table_refresh";
+    int rc = check_table(c, t);
+    if (rc) return rc;
+    if (u->n < 0) return ccm_fail(c, CCM_E_ARG, "%s: n = %d", fn, u->n);
+    if (u->what == 0 || (u->what & ~(CCM_MPR_DESCRIPTOR | CCM_MPR_NORMAL_DEPTH))) return ccm_fail(c, CCM_E_ARG, "%s: what = %d", fn, u->what);
+    const bool nd = (u->what & CCM_MPR_NORMAL_DEPTH) != 0;
+    if (u->n_kf < 0 || (u->n_kf > 0 && !u->kfs)) return ccm_fail(c, CCM_E_ARG, "%s: n_kf = %d%s", fn, u->n_kf, u->n_kf > 0 ? " and null kfs" : "");
+    if (u->n > 0 && (!u->slot || !u->obs_first || (nd && (!u->ref_kf || !u->ref_feat))))
+        return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !u->slot ? "slot" : !u->obs_first ? "obs_first" : !u->ref_kf ? "ref_kf" : "ref_feat");
+    if (u->n == 0) return CCM_OK;
+    return ccm_guard(c, fn, [&]() -> int {
+        const int n = u->n, n_kf = u->n_kf;
+        if (u->obs_first[0] != 0) return ccm_fail(c, CCM_E_ARG, "%s: obs_first[0] = %d, not 0", fn, u->obs_first[0]);
+        for (int p = 0; p < n; p++)
+            if (u->obs_first[p + 1] < u->obs_first[p])
+                return ccm_fail(c, CCM_E_ARG, "%s: obs_first[%d] = %d below obs_first[%d] = %d", fn, p + 1, u->obs_first[p + 1], p, u->obs_first[p]);
+        const int n_obs = u->obs_first[n];
+        if (n_obs > 0 && (!u->obs_kf || !u->obs_feat)) return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !u->obs_kf ? "obs_kf" : "obs_feat");
+        for (int k = 0; k < n_kf; k++) {
+            const ccm_frame* f = u->kfs[k];
+            if (!f) return ccm_fail(c, CCM_E_ARG, "%s: null kfs[%d]", fn, k);
+            if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: kfs[%d] outlived its context", fn, k);
+            if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: kfs[%d] belongs to another context", fn, k);
+        }
+        std::vector<uint8_t> used((size_t)n_kf, 0);              // 1: named by an observation, 2: named as a reference keyframe
+        for (int p = 0; p < n; p++) {
+            for (int e = u->obs_first[p]; e < u->obs_first[p + 1]; e++) {
+                const int k = u->obs_kf[e];
+                if (k < 0 || k >= n_kf) return ccm_fail(c, CCM_E_ARG, "%s: point %d, entry %d: keyframe %d outside [0, %d)", fn, p, e, k, n_kf);
+                if (u->obs_feat[e] < 0 || u->obs_feat[e] >= u->kfs[k]->n)
+                    return ccm_fail(c, CCM_E_ARG, "%s: point %d, entry %d: feature %d outside [0, %d) of kfs[%d]", fn, p, e, u->obs_feat[e], u->kfs[k]->n, k);
+                used[k] |= 1;
+            }
+            if (nd && u->obs_first[p + 1] > u->obs_first[p]) {
+                const int k = u->ref_kf[p];
+                if (k < 0 || k >= n_kf) return ccm_fail(c, CCM_E_ARG, "%s: point %d: reference keyframe %d outside [0, %d)", fn, p, k, n_kf);
+                if (u->ref_feat[p] < 0 || u->ref_feat[p] >= u->kfs[k]->n)
+                    return ccm_fail(c, CCM_E_ARG, "%s: point %d: reference feature %d outside [0, %d) of kfs[%d]", fn, p, u->ref_feat[p], u->kfs[k]->n, k);
+                used[k] |= 2;
+            }
+        }
+        if (nd)
+            for (int k = 0; k < n_kf; k++) {
+                const ccm_frame* f = u->kfs[k];
+                if ((used[k] & 1) && !f->has_pose) return ccm_fail(c, CCM_E_STATE, "%s: kfs[%d] is observed and has no pose", fn, k);
+                if ((used[k] & 2) && (!f->has_pose || !f->has_cam))
+                    return ccm_fail(c, CCM_E_STATE, "%s: kfs[%d] is a reference keyframe and has no %s", fn, k, !f->has_pose ? "pose" : "camera");
+            }
+        bool dup = false;
+        if ((rc = mark_slots(c, t, n, u->slot, &dup))) return rc;
+        if (dup) return ccm_fail(c, CCM_E_ARG, "%s: a slot is listed twice", fn);
+
+        CCM_HIP(c, hipSetDevice(c->device));
+        const size_t m = (size_t)n, mo = (size_t)n_obs;
+        size_t off = 0;
+        const size_t o_best = seg(off, m * 4), o_nrm = seg(off, m * 12), o_min = seg(off, m * 4), o_max = seg(off, m * 4);
+        const size_t res_end = off;
+        const size_t o_slot = seg(off, m * 4), o_first = seg(off, (m + 1) * 4), o_okf = seg(off, mo * 4), o_ofeat = seg(off, mo * 4);
+        const size_t o_rkf = seg(off, nd ? m * 4 : 0), o_rfeat = seg(off, nd ? m * 4 : 0);
+        const size_t o_pos = seg(off, u->pos ? m * 12 : 0), o_flags = seg(off, u->flags ? m : 0);
+        const size_t o_view = seg(off, (size_t)n_kf * sizeof(MptKfView));
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        std::memcpy(h + o_slot, u->slot, m * 4); std::memcpy(h + o_first, u->obs_first, (m + 1) * 4);
+        if (mo) { std::memcpy(h + o_okf, u->obs_kf, mo * 4); std::memcpy(h + o_ofeat, u->obs_feat, mo * 4); }
+        if (nd) {
+            int32_t* rk = (int32_t*)(h + o_rkf); int32_t* rf = (int32_t*)(h + o_rfeat);
+            for (int p = 0; p < n; p++) {                        // not read for a point without observations: any value the caller left
+                const bool has = u->obs_first[p + 1] > u->obs_first[p];
+                rk[p] = has ? u->ref_kf[p] : 0; rf[p] = has ? u->ref_feat[p] : 0;
+            }
+        }
+        if (u->pos) std::memcpy(h + o_pos, u->pos, m * 12);
+        if (u->flags) std::memcpy(h + o_flags, u->flags, m);
+        MptKfView* hv = (MptKfView*)(h + o_view);
+        for (int k = 0; k < n_kf; k++) {
+            const ccm_frame* f = u->kfs[k];
+            hv[k] = MptKfView{ f->desc, f->d_cam ? (const float*)((const uint8_t*)f->d_cam + offsetof(MapCam, Ow)) : nullptr, f->oct, f->sf, f->cam_levels, 0 };
+        }
+        if ((rc = frame_upload(c, o_slot, end))) return rc;
+        uint8_t* io = frame_state(c)->io.as<uint8_t>();
+        MptRefreshArgs A{};
+        A.n = n; A.what = u->what;
+        A.slot = (const int*)(io + o_slot); A.obs_first = (const int*)(io + o_first); A.obs_kf = (const int*)(io + o_okf);
+        A.obs_feat = (const int*)(io + o_ofeat); A.ref_kf = (const int*)(io + o_rkf); A.ref_feat = (const int*)(io + o_rfeat);
+        A.pos = u->pos ? (const float*)(io + o_pos) : nullptr; A.flags = u->flags ? io + o_flags : nullptr;
+        A.view = (const MptKfView*)(io + o_view);
+        A.best = (int*)(io + o_best); A.normal = (float*)(io + o_nrm); A.min_dist = (float*)(io + o_min); A.max_dist = (float*)(io + o_max);
+        mpt_launch_refresh(c->stream, A, t->T);
+        CCM_HIP(c, hipGetLastError());
+        if (!res || (!res->best && !res->normal && !res->min_dist && !res->max_dist)) return CCM_OK;
+        if ((rc = frame_download(c, res_end))) return rc;
+        if (res->best) std::memcpy(res->best, h + o_best, m * 4);
+        if (res->normal) std::memcpy(res->normal, h + o_nrm, m * 12);
+        if (res->min_dist) std::memcpy(res->min_dist, h + o_min, m * 4);
+        if (res->max_dist) std::memcpy(res->max_dist, h + o_max, m * 4);
         return CCM_OK;
     });
 }

@@ -7,6 +7,8 @@
 //   k_slp_scan         exclusive scan of the workgroup counts, one workgroup; the in-view count
 //   k_slp_compact      the entries in view, in list order, into the query arrays of the windowed matcher
 //   k_mpt_pose_gather  k_frame_pose_gather (frame_kernels.hip) with the points read from the table as float
+//   k_mpt_refresh      MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823)
+//                      for a list of points whose observations name keyframe handles; one wave per point
 // No kernel waits for another workgroup: the compaction is three launches (ballot + count, scan, scatter).
 // Every index is checked against the table's capacity before it is used as an address.
 #include <hip/hip_runtime.h>
@@ -221,6 +223,134 @@ __global__ __launch_bounds__(MPG_TPB) void k_mpt_pose_gather(MptPoseGatherArgs A
     if (tid == 0) { A.first[0] = 0; A.first[1] = s_bad ? 0 : s_base; A.status[0] = s_bad; }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- refresh
+// One wave per listed map point, MPR_TPB / 64 points per workgroup (as k_distinctive, bow_kernels.hip).
+//   Gather: lane i fetches observation i's 32 bytes from its keyframe's descriptor rows into the wave's LDS copy -- the only scattered
+//   traffic, about one cache line per observation.  The copy holds MPR_LDS_ROWS rows; the rows of a longer list are read through the
+//   index lists from global memory wherever they are needed, so any count is handled.
+//   Median: lane i owns row i of the distance matrix (rows beyond 64 in further rounds) and bisects [0, 256] for the smallest v with
+//   #(d <= v) > k, k = (int)(0.5 * (c - 1)); all lanes read the same column at a time (an LDS broadcast).  The least (median, row)
+//   over the wave is the choice: among equal medians the first observation wins.
+//   Normal: lanes compute the unit rays of their observations in parallel; the sum is then taken strictly in list order, every lane
+//   adding the same values handed round by __shfl (a float sum depends on its order; a tree would give another result).
+// The arithmetic is that of float cv::Mat expressions (include/ccm_hot.h, ccm_map_table_refresh): norms summed in double, the
+// multiply and the add of scaleAdd rounded separately.  No atomics, no scratch; every slot is checked against the capacity.
+__device__ inline const uint4* mpr_row(const MptRefreshArgs& A, int e)
+{
+    return reinterpret_cast<const uint4*>(A.view[A.obs_kf[e]].desc + 32 * (size_t)A.obs_feat[e]);
+}
+__device__ inline int mpr_ham256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1)
+{
+    int d = __popc(a0.x ^ b0.x);
+    d += __popc(a0.y ^ b0.y); d += __popc(a0.z ^ b0.z); d += __popc(a0.w ^ b0.w);
+    d += __popc(a1.x ^ b1.x); d += __popc(a1.y ^ b1.y); d += __popc(a1.z ^ b1.z); d += __popc(a1.w ^ b1.w);
+    return d;
+}
+// cv::norm of a float 3-vector: the squares summed in double
+__device__ inline double mpr_norm(float x, float y, float z)
+{
+    return sqrt(__dadd_rn(__dadd_rn(__dmul_rn((double)x, (double)x), __dmul_rn((double)y, (double)y)), __dmul_rn((double)z, (double)z)));
+}
+
+__global__ __launch_bounds__(MPR_TPB) void k_mpt_refresh(MptRefreshArgs A, MptTable T)
+{
+    __shared__ uint4 s_desc[MPR_TPB / 64][2 * MPR_LDS_ROWS];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, p = blockIdx.x * (MPR_TPB / 64) + wv;
+    int c = 0, o0 = 0, s = -1;
+    if (p < A.n) { o0 = A.obs_first[p]; c = A.obs_first[p + 1] - o0; s = A.slot[p]; }
+    const bool in_table = s >= 0 && s < T.capacity;             // the host has checked it
+    const bool do_desc = in_table && c > 0 && (A.what & CCM_MPR_DESCRIPTOR);
+    const bool do_nd = in_table && c > 0 && (A.what & CCM_MPR_NORMAL_DEPTH);
+    const int n_lds = do_desc ? min(c, MPR_LDS_ROWS) : 0;
+    uint4* L = s_desc[wv];
+    for (int i = lane; i < n_lds; i += 64) {
+        const uint4* g = mpr_row(A, o0 + i);
+        L[2 * i] = g[0]; L[2 * i + 1] = g[1];
+    }
+    __syncthreads();                                             // every wave comes here once, whatever its point
+    if (!in_table) return;
+
+    float P0, P1, P2;
+    if (A.pos) {
+        P0 = A.pos[3 * (size_t)p]; P1 = A.pos[3 * (size_t)p + 1]; P2 = A.pos[3 * (size_t)p + 2];
+        if (lane == 0) { T.pos[3 * (size_t)s] = P0; T.pos[3 * (size_t)s + 1] = P1; T.pos[3 * (size_t)s + 2] = P2; }
+    } else {
+        P0 = T.pos[3 * (size_t)s]; P1 = T.pos[3 * (size_t)s + 1]; P2 = T.pos[3 * (size_t)s + 2];
+    }
+    if (A.flags && lane == 0) T.flags[s] = A.flags[p];
+
+    int best = -1;
+    if (do_desc) {
+        const int k = (int)(0.5 * (c - 1));
+        int med = 0x7fffffff, row = 0x7fffffff;
+        for (int i = lane; i < c; i += 64) {
+            uint4 a0, a1;
+            if (i < n_lds) { a0 = L[2 * i]; a1 = L[2 * i + 1]; }
+            else { const uint4* g = mpr_row(A, o0 + i); a0 = g[0]; a1 = g[1]; }
+            int lo = 0, hi = 256;                                // smallest v with count(d <= v) > k
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                int cnt = 0;
+                for (int j = 0; j < n_lds; j++) cnt += mpr_ham256(a0, a1, L[2 * j], L[2 * j + 1]) <= mid ? 1 : 0;
+                for (int j = n_lds; j < c; j++) {
+                    const uint4* g = mpr_row(A, o0 + j);
+                    cnt += mpr_ham256(a0, a1, g[0], g[1]) <= mid ? 1 : 0;
+                }
+                if (cnt > k) hi = mid; else lo = mid + 1;
+            }
+            if (lo < med) { med = lo; row = i; }                 // rows ascend per lane: the first of equal medians stays
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const int om = __shfl_xor(med, d, 64), orow = __shfl_xor(row, d, 64);
+            if (om < med || (om == med && orow < row)) { med = om; row = orow; }
+        }
+        best = row;
+        if (lane < 2) {
+            const uint4 v = best < n_lds ? L[2 * best + lane] : mpr_row(A, o0 + best)[lane];
+            reinterpret_cast<uint4*>(T.desc + (size_t)s * 32)[lane] = v;
+        }
+    }
+
+    float n0, n1, n2, mn, mx;
+    if (do_nd) {
+        n0 = 0.0f; n1 = 0.0f; n2 = 0.0f;
+        for (int base = 0; base < c; base += 64) {
+            const int i = base + lane;
+            float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
+            if (i < c) {
+                const float* Ow = A.view[A.obs_kf[o0 + i]].Ow;
+                const float d0 = P0 - Ow[0], d1 = P1 - Ow[1], d2 = P2 - Ow[2];
+                const float a = (float)(1.0 / mpr_norm(d0, d1, d2));
+                v0 = __fmul_rn(d0, a); v1 = __fmul_rn(d1, a); v2 = __fmul_rn(d2, a);
+            }
+            const int m = min(64, c - base);
+            for (int l = 0; l < m; l++) {                        // cv::scaleAdd, observation by observation
+                n0 = __fadd_rn(__shfl(v0, l, 64), n0); n1 = __fadd_rn(__shfl(v1, l, 64), n1); n2 = __fadd_rn(__shfl(v2, l, 64), n2);
+            }
+        }
+        const float inv = (float)(1.0 / (double)c);              // Mat / n multiplies by the reciprocal
+        n0 = __fmul_rn(n0, inv); n1 = __fmul_rn(n1, inv); n2 = __fmul_rn(n2, inv);
+        const MptKfView& R = A.view[A.ref_kf[p]];
+        const float dist = (float)mpr_norm(P0 - R.Ow[0], P1 - R.Ow[1], P2 - R.Ow[2]);
+        const int level = min(max(R.oct[A.ref_feat[p]], 0), 255);   // within the handle's n_levels; sf holds 256 entries
+        mx = __fmul_rn(dist, R.sf[level]);
+        mn = __fdiv_rn(mx, R.sf[R.n_levels - 1]);
+        if (lane == 0) {
+            T.normal[3 * (size_t)s] = n0; T.normal[3 * (size_t)s + 1] = n1; T.normal[3 * (size_t)s + 2] = n2;
+            T.min_dist[s] = mn; T.max_dist[s] = mx;
+        }
+    } else {                                                     // the result block reports the row as it stands
+        n0 = T.normal[3 * (size_t)s]; n1 = T.normal[3 * (size_t)s + 1]; n2 = T.normal[3 * (size_t)s + 2];
+        mn = T.min_dist[s]; mx = T.max_dist[s];
+    }
+    if (lane == 0) {
+        A.best[p] = best;
+        A.normal[3 * (size_t)p] = n0; A.normal[3 * (size_t)p + 1] = n1; A.normal[3 * (size_t)p + 2] = n2;
+        A.min_dist[p] = mn; A.max_dist[p] = mx;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
 void mpt_launch_scatter(hipStream_t s, const MptTable& T, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
                         const float* max_dist, const uint8_t* desc, const uint8_t* flags)
@@ -247,4 +377,8 @@ void slp_launch_frustum(hipStream_t s, const SlpArgs& A, const MptTable& T, int*
 void mpt_launch_pose_gather(hipStream_t s, const MptPoseGatherArgs& A, const MptTable& T)
 {
     hipLaunchKernelGGL(k_mpt_pose_gather, dim3(1), dim3(MPG_TPB), 0, s, A, T);
+}
+void mpt_launch_refresh(hipStream_t s, const MptRefreshArgs& A, const MptTable& T)
+{
+    if (A.n > 0) hipLaunchKernelGGL(k_mpt_refresh, dim3((A.n + MPR_TPB / 64 - 1) / (MPR_TPB / 64)), dim3(MPR_TPB), 0, s, A, T);
 }

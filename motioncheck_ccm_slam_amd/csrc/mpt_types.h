@@ -7,6 +7,8 @@
 #define SLP_TPB 256        // k_slp_frustum / k_slp_compact: 4 waves per workgroup
 #define SCAN_TPB 1024
 #define MPG_TPB 1024
+#define MPR_TPB 256        // k_mpt_refresh: one wave per map point, 4 points per workgroup
+#define MPR_LDS_ROWS 256   // descriptors a wave keeps in LDS: 8 KB per wave, 32 KB per workgroup; further rows are read from global memory
 
 struct MptTable {                                // the table's columns (device)
     int capacity;
@@ -30,6 +32,17 @@ struct MptPoseGatherArgs {
     int* first; double* pts; double* obs; double* info; int* kof; int* status;
 };
 
+// What k_mpt_refresh reads of a keyframe handle: device pointers the handle owns (Ow: d_cam->Ow; sf: kMaxLevels floats, zero-padded).
+struct MptKfView { const uint8_t* desc; const float* Ow; const int* oct; const float* sf; int n_levels; int pad_; };
+
+struct MptRefreshArgs {
+    int n, what;                                 // what: CCM_MPR_*
+    const int* slot; const int* obs_first; const int* obs_kf; const int* obs_feat; const int* ref_kf; const int* ref_feat;
+    const float* pos; const uint8_t* flags;      // optional rows written first
+    const MptKfView* view;
+    int* best; float* normal; float* min_dist; float* max_dist;      // per listed point, in the call's result block
+};
+
 void mpt_launch_scatter(hipStream_t, const MptTable&, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
                         const float* max_dist, const uint8_t* desc, const uint8_t* flags);
 void mpt_launch_gather(hipStream_t, const MptTable&, int n, const int* slot, float* pos, float* normal, float* min_dist, float* max_dist,
@@ -39,3 +52,4 @@ int  slp_workgroups(int n_order);
 // k_slp_frustum, k_slp_scan (cnt[0] = entries in view) and k_slp_compact
 void slp_launch_frustum(hipStream_t, const SlpArgs&, const MptTable&, int* cnt);
 void mpt_launch_pose_gather(hipStream_t, const MptPoseGatherArgs&, const MptTable&);
+void mpt_launch_refresh(hipStream_t, const MptRefreshArgs&, const MptTable&);

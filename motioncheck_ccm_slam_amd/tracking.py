@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import MP_BAD, MP_HAS_OBS, MP_LIVE  # noqa: F401
+from ._lib import MP_BAD, MP_HAS_OBS, MP_LIVE, MPR_DESCRIPTOR, MPR_NORMAL_DEPTH  # noqa: F401
 
 
 class MapPointTable:
@@ -55,6 +55,42 @@ class MapPointTable:
                    desc=np.zeros((m, 32), np.uint8), flags=np.zeros(m, np.uint8), seen=np.zeros(m, "i4"))
         self.ctx.check(self.lib.ccm_map_table_fetch(self.ctx.handle, C.c_void_p(self.handle), n, _lib.ptr(slot),
                                                     *[_lib.ptr(out[k]) for k in ("pos", "normal", "min_dist", "max_dist", "desc", "flags", "seen")]))
+        return {k: v[:n] for k, v in out.items()}
+
+    def refresh(self, slot, kfs, obs_first, obs_kf, obs_feat, ref_kf=None, ref_feat=None, pos=None, flags=None, what=3, fetch=True):
+        """MapPoint::ComputeDistinctiveDescriptors (what & MPR_DESCRIPTOR) and MapPoint::UpdateNormalAndDepth (what & MPR_NORMAL_DEPTH)
+        for the points in `slot`, read from the keyframe handles `kfs` (DeviceFrame) and written into the table
+        (ccm_map_table_refresh).  Point p observes feature obs_feat[e] of kfs[obs_kf[e]] for e in obs_first[p] .. obs_first[p+1], in the
+        caller's order; ref_kf / ref_feat name its reference keyframe (needed with MPR_NORMAL_DEPTH).  pos / flags, when given, are
+        written to the rows first.  Returns a dict: best [n] (the chosen observation of each list; -1 for an empty list or without
+        MPR_DESCRIPTOR) and normal, min_dist, max_dist of the rows after the call; with fetch=False nothing is read back, the call does
+        not synchronise and returns None."""
+        a = np.ascontiguousarray
+        slot = a(slot, "i4").reshape(-1); n = len(slot)
+        first = a(obs_first, "i4").reshape(-1); okf = a(obs_kf, "i4").reshape(-1); ofeat = a(obs_feat, "i4").reshape(-1)
+        if len(first) != n + 1 or len(okf) != len(ofeat) or (n and len(okf) < first[-1]):
+            raise ValueError("obs_first needs n + 1 entries and obs_kf / obs_feat obs_first[n] each")
+
+        def col(v, t, shape):
+            if v is None:
+                return None
+            v = a(v, t)
+            if v.shape != shape:
+                raise ValueError("column of shape %s, expected %s" % (v.shape, shape))
+            return v
+        rkf, rfeat = col(ref_kf, "i4", (n,)), col(ref_feat, "i4", (n,))
+        pos, flags = col(pos, "f4", (n, 3)), col(flags, np.uint8, (n,))
+        handles = (C.c_void_p * max(len(kfs), 1))(*[k.handle for k in kfs])
+        pad = lambda v: v if len(v) else np.zeros(1, v.dtype)  # noqa: E731  (an empty array may have no address)
+        u = _lib.MapRefresh(n, _lib.ptr(pad(slot)), _lib.ptr(pos), _lib.ptr(flags), len(kfs), handles, _lib.ptr(first), _lib.ptr(pad(okf)),
+                            _lib.ptr(pad(ofeat)), _lib.ptr(rkf), _lib.ptr(rfeat), int(what))
+        if not fetch:
+            self.ctx.check(self.lib.ccm_map_table_refresh(self.ctx.handle, C.c_void_p(self.handle), C.byref(u), None))
+            return None
+        m = max(n, 1)
+        out = dict(best=np.full(m, -1, "i4"), normal=np.zeros((m, 3), "f4"), min_dist=np.zeros(m, "f4"), max_dist=np.zeros(m, "f4"))
+        r = _lib.MapRefreshResult(*[_lib.ptr(out[k]) for k in ("best", "normal", "min_dist", "max_dist")])
+        self.ctx.check(self.lib.ccm_map_table_refresh(self.ctx.handle, C.c_void_p(self.handle), C.byref(u), C.byref(r)))
         return {k: v[:n] for k, v in out.items()}
 
     def close(self):

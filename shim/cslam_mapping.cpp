@@ -204,6 +204,8 @@ void LocalMapping::CreateNewMapPoints()
         if (k > 0 && CheckNewKeyFrames())                                   // :314
             return;
         kfptr pKF2 = vpNeighKFs[k];
+        std::vector<mpptr> created;
+        created.reserve(first[k + 1] - first[k]);
         for (int row = first[k]; row < first[k + 1]; row++) {
             cv::Mat x3D = (cv::Mat_<float>(3, 1) << x3d[3 * (size_t)row], x3d[3 * (size_t)row + 1], x3d[3 * (size_t)row + 2]);
             // the side effects of :451-466, in that order
@@ -215,13 +217,21 @@ void LocalMapping::CreateNewMapPoints()
             mpCurrentKeyFrame->AddMapPoint(pMP, idx1[row]);
             pKF2->AddMapPoint(pMP, idx2[row]);
 
-            pMP->ComputeDistinctiveDescriptors();
+            created.push_back(pMP);
+        }
+        // ComputeDistinctiveDescriptors and UpdateNormalAndDepth (:461-463) of this neighbour's points in one ccm_map_table_refresh on
+        // the handles used above, still in front of Map::AddMapPoint as in the reference; point by point where the table belongs to
+        // another thread's context (ccm_shim::MapTable::refresh)
+        if (!(handles && ccm_shim::refresh_map_points(created, CCM_MPR_DESCRIPTOR | CCM_MPR_NORMAL_DEPTH, &keyframe_handle))) {
+            for (const mpptr& pMP : created) {
+                pMP->ComputeDistinctiveDescriptors();
 
-            pMP->UpdateNormalAndDepth();
-
+                pMP->UpdateNormalAndDepth();
+            }
+        }
+        for (const mpptr& pMP : created) {
             mpMap->AddMapPoint(pMP);
             mlpRecentAddedMapPoints.push_back(pMP);
-
         }
     }
 }

@@ -16,9 +16,11 @@
 #include <cslam/Map.h>
 #include <cslam/Optimizer.h>
 #include <cslam/Converter.h>
+#include <cslam/ORBmatcher.h>
 #include <map>
 #include <mutex>
 #include "ccm_shim.h"
+#include "fuse_steps.h"
 
 namespace ccm_shim {
 
@@ -90,7 +92,7 @@ public:
             ccm_map_table* bigger = nullptr;
             if (ccm_map_table_create(c, std::max(2 * need, 65536), &bigger)) return nullptr;
             ccm_map_table_destroy(mTable);
-            mTable = bigger; mOrderDirty = true;
+            mTable = bigger; mCtx = c; mOrderDirty = true;
             std::vector<Row> all;
             for (int s = 0; s < need; s++) if (mPoints[s]) all.push_back(mRows[s]);     // bad points that still own a slot included
             all.insert(all.end(), mQueue.begin(), mQueue.end());                         // rows queued by other threads stay behind them
@@ -119,6 +121,93 @@ public:
         }
         return mTable;
     }
+    // MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth for pts in one ccm_map_table_refresh: the observation lists are
+    // built from GetObservations() in the map's own order without the bad keyframes (src/MapPoint.cpp:803, :952), the device reads
+    // the descriptors, camera centres and scale factors from the keyframe handles and writes the table's columns, and the one download
+    // gives what the MapPoint objects keep: MapPoint::StoreRefreshed (INTEGRATION.md "Map-point table") assigns mDescriptor,
+    // mNormalVector, mfMinDistance and mfMaxDistance at the hook position without calling put(), and the row copy kept here is brought
+    // up to date instead: no row travels a second time.  A table and its handles belong to one context, so this runs on the thread
+    // that owns the table; on any other thread it returns false and touches nothing.  Points the call cannot express stay with the
+    // reference's functions: a bad point (both return at once) and a point whose observing keyframes are all bad (normal / 0).
+    bool refresh(const std::vector<mpptr>& pts, int what, KeyframeHandleOf handle_of)
+    {
+        ccm_ctx* c = ctx();
+        {
+            std::lock_guard<std::mutex> lock(mMutex);
+            if (!mTable || mCtx != c) return false;                              // the tracking thread's first flush makes the table
+        }
+        typedef cslam::Tracking::kfptr kfptr;
+        std::vector<mpptr> use;
+        std::vector<int32_t> obs_first(1, 0), obs_kf, obs_feat, ref_kf, ref_feat;
+        std::vector<ccm_frame*> kfs;
+        std::vector<kfptr> kf_ptr;
+        std::map<cslam::idpair, int> kf_index;
+        auto index_of = [&](const kfptr& pKF) -> int {
+            const auto it = kf_index.find(pKF->mId);
+            if (it != kf_index.end()) return it->second;
+            ccm_frame* h = handle_of(pKF);
+            if (!h) return -1;
+            kf_index[pKF->mId] = (int)kfs.size(); kfs.push_back(h); kf_ptr.push_back(pKF);
+            return (int)kfs.size() - 1;
+        };
+        for (const mpptr& pMP : pts) {
+            if (!pMP || pMP->isBad()) continue;
+            const std::map<kfptr, size_t> obs = pMP->GetObservations();
+            if (obs.empty()) continue;
+            const size_t mark = obs_kf.size();
+            for (const auto& kv : obs) {
+                if (kv.first->isBad()) continue;
+                const int k = index_of(kv.first);
+                if (k < 0) return false;
+                obs_kf.push_back(k); obs_feat.push_back((int32_t)kv.second);
+            }
+            if (obs_kf.size() == mark) {                                         // every observing keyframe is bad
+                if (what & CCM_MPR_NORMAL_DEPTH) pMP->UpdateNormalAndDepth();
+                continue;
+            }
+            const kfptr pRef = pMP->GetReferenceKeyFrame();
+            const int kr = index_of(pRef);
+            if (kr < 0) return false;
+            const auto itr = obs.find(pRef);
+            ref_kf.push_back(kr); ref_feat.push_back(itr == obs.end() ? 0 : (int32_t)itr->second);   // observations[pRefKF] (:813)
+            obs_first.push_back((int32_t)obs_kf.size());
+            use.push_back(pMP);
+        }
+        const int n = (int)use.size();
+        if (n == 0) return true;
+        for (const mpptr& pMP : use) if (slot_of(pMP) < 0) put(pMP, 0.f, 0.f);  // a point not yet in the map: its slot comes first
+        ccm_map_table* table = flush();                                          // rows queued earlier must not land behind the refresh
+        if (!table) return false;
+        std::vector<int32_t> slot(n), best(n);
+        std::vector<float> pos(3 * (size_t)n), normal(3 * (size_t)n), mn(n), mx(n);
+        std::vector<uint8_t> flags(n);
+        for (int i = 0; i < n; i++) {
+            slot[i] = slot_of(use[i]);
+            const cv::Mat P = use[i]->GetWorldPos();
+            for (int k = 0; k < 3; k++) pos[3 * (size_t)i + k] = P.at<float>(k);
+            flags[i] = CCM_MP_LIVE | (use[i]->Observations() > 0 ? CCM_MP_HAS_OBS : 0);
+        }
+        const ccm_map_refresh u{n, slot.data(), pos.data(), flags.data(), (int32_t)kfs.size(), kfs.data(), obs_first.data(), obs_kf.data(),
+                                obs_feat.data(), ref_kf.data(), ref_feat.data(), what};
+        ccm_map_refresh_result r{best.data(), normal.data(), mn.data(), mx.data()};
+        if (ccm_map_table_refresh(c, table, &u, &r)) return false;
+        std::lock_guard<std::mutex> lock(mMutex);
+        for (int i = 0; i < n; i++) {
+            cv::Mat D, Nv;
+            if (what & CCM_MPR_DESCRIPTOR) {
+                const int e = obs_first[i] + best[i];
+                D = kf_ptr[obs_kf[e]]->mDescriptors.row(obs_feat[e]).clone();
+            }
+            if (what & CCM_MPR_NORMAL_DEPTH) Nv = (cv::Mat_<float>(3, 1) << normal[3 * (size_t)i], normal[3 * (size_t)i + 1], normal[3 * (size_t)i + 2]);
+            use[i]->StoreRefreshed(D, Nv, mn[i], mx[i]);                         // empty Mat: that member stays
+            Row& row = mRows[slot[i]];
+            for (int k = 0; k < 3; k++) row.pos[k] = pos[3 * (size_t)i + k];
+            row.flags = flags[i];
+            if (!D.empty()) for (int k = 0; k < 32; k++) row.desc[k] = D.at<uint8_t>(0, k);
+            if (!Nv.empty()) { for (int k = 0; k < 3; k++) row.normal[k] = normal[3 * (size_t)i + k]; row.min_dist = mn[i]; row.max_dist = mx[i]; }
+        }
+        return true;
+    }
     // The slots in view of the previous SearchLocalPoints: Frame::isInFrustum clears mbTrackInView of every point it tests, so a
     // point that was in view and is rejected now must not keep a stale `true`.
     std::vector<int32_t> mLastInView;
@@ -131,9 +220,15 @@ private:
     std::vector<int> mFree;
     std::vector<Row> mQueue, mRows;                       // mRows: the last row sent for a slot, with the raw distances
     ccm_map_table* mTable = nullptr;
+    ccm_ctx* mCtx = nullptr;                              // the context of the thread that made mTable
     bool mOrderDirty = true;
     int32_t mZero = 0;
 };
+
+bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of)
+{
+    return MapTable::get().refresh(pts, what, handle_of);
+}
 
 }  // namespace ccm_shim
 

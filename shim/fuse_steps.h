@@ -78,4 +78,12 @@ inline int apply_fuse(const ORBmatcher::kfptr& pKF, const std::vector<ORBmatcher
 // The first Fuse loop of LocalMapping::SearchInNeighbors on keyframe handles (defined in cslam_mapping.cpp; LocalMapping's thread only)
 void fuse_into_targets(const std::vector<ORBmatcher::kfptr>& vpTargetKFs, const std::vector<ORBmatcher::mpptr>& vpMapPointMatches);
 
+// MapPoint::ComputeDistinctiveDescriptors (what & CCM_MPR_DESCRIPTOR) and MapPoint::UpdateNormalAndDepth (what & CCM_MPR_NORMAL_DEPTH)
+// for all of pts in one ccm_map_table_refresh on the map-point table and the caller's keyframe handles (ccm_shim::MapTable::refresh,
+// defined in cslam_tracking.cpp).  handle_of returns the handle of a keyframe in the calling thread's context, camera and pose set.
+// false = nothing was done (the table belongs to another thread's context, or a handle is missing): the caller then runs the
+// reference's two functions point by point, whose hooks queue the rows.
+using KeyframeHandleOf = ccm_frame* (*)(const ORBmatcher::kfptr&);
+bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of);
+
 }  // namespace ccm_shim
