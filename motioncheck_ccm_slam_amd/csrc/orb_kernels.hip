@@ -464,6 +464,12 @@ __global__ __launch_bounds__(256) void k_cell_nms(const OrbGeom g, const OrbCell
 // whose start-up the dispatcher overlaps with the seven others on the CU.  Not kept.
 // NMS works on the list of scored pixels (FC_NZ entries) and the list of local maxima (FC_KEPT); a band that overflows
 // either list takes the per-cell row scan instead.
+// The kernel is bound by the dependent chain of one band (8 bands per CU, each issuing for a tenth of its life).  The first NMS pass
+// therefore requests a scored pixel's eight neighbours and its column's cell together, and a cell's count comes from the per-cell
+// counters, not from a scan of its bucket by the last wave (0.367 -> 0.354 ms with the global-address-space staging loads).
+// Measured and dropped (profiles/fc_chain_ab.txt): the rank loop reading its bucket eight entries per wait (nothing), all staging
+// trips of a thread in flight before the first store (+0.002 ms), the next rejection run's LDS dwords requested before the current
+// run's ballots (+0.012 ms, 60 registers), the column masks requested with the pixel dwords (nothing).
 #ifndef FC_NZ
 #define FC_NZ 1024
 #endif
@@ -490,13 +496,13 @@ __device__ __forceinline__ int fc_mbcnt(unsigned long long m, int base)
 {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)base));
 }
-// Diagnostic build only (-DFC_STAMPS, tools/r03_fc_stamps.sh): wave 0 of every workgroup leaves the shader clock at its phase
+// Diagnostic build only (-DFC_STAMPS, tools/r03_fc_stamps.sh): wave 0 (slots 0-7) and the last wave (slots 8-15) of every workgroup leave the shader clock at their phase
 // boundaries in a buffer no other code reads; the shipped kernel contains none of this.
 #ifdef FC_STAMPS
-#define FC_STAMP_SLOTS 8
+#define FC_STAMP_SLOTS 16
 #define FC_STAMP_WGS (1 << 17)
 __device__ unsigned long long fc_stamps[FC_STAMP_WGS * FC_STAMP_SLOTS];
-#define FC_STAMP(k) do { if (threadIdx.x == 0) { const unsigned wg__ = blockIdx.y * gridDim.x + blockIdx.x; if (wg__ < FC_STAMP_WGS) fc_stamps[wg__ * FC_STAMP_SLOTS + (k)] = __builtin_amdgcn_s_memtime(); } } while (0)
+#define FC_STAMP(k) do { if (threadIdx.x == 0 || threadIdx.x == FC_TPB - 1) { const unsigned wg__ = blockIdx.y * gridDim.x + blockIdx.x; if (wg__ < FC_STAMP_WGS) fc_stamps[wg__ * FC_STAMP_SLOTS + (threadIdx.x ? 8 : 0) + (k)] = __builtin_amdgcn_s_memtime(); } } while (0)
 extern "C" int ccm_debug_fc_stamps(unsigned long long* out, int n_wgs)
 {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(fc_stamps), (size_t)n_wgs * FC_STAMP_SLOTS * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
@@ -504,6 +510,11 @@ extern "C" int ccm_debug_fc_stamps(unsigned long long* out, int n_wgs)
 #else
 #define FC_STAMP(k) do { } while (0)
 #endif
+// image pixels in the global address space (global_load_*, not flat_load_*); fc_u32x4_a4: 16 bytes at a 4-byte-aligned address
+typedef const __attribute__((address_space(1))) uint8_t fc_gbyte;
+typedef const __attribute__((address_space(1))) unsigned fc_gu32;
+typedef unsigned fc_u32x4 __attribute__((ext_vector_type(4)));
+typedef fc_u32x4 fc_u32x4_a4 __attribute__((aligned(4)));
 // element ci (per lane) of four wave-uniform values: three selects, no memory
 template <class T>
 __device__ __forceinline__ int sel4(int ci, const T (&a)[4]) { return ci == 0 ? (int)a[0] : ci == 1 ? (int)a[1] : ci == 2 ? (int)a[2] : (int)a[3]; }
@@ -568,25 +579,28 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (diagnostic: level record and everything scalar before the pixel loads has arrived)
 #endif
     FC_STAMP(5);
+    // the image is read through global-address-space pointers: `img` is a select between a kernel argument and a field of the band
+    // record, and left generic its loads become flat_load_dword, four per 16-byte chunk
+    fc_gbyte* const gimg = (fc_gbyte*)img;
     if (dword_ok && (P & 15) == 0) {
-        // 16 bytes per lane: one global load and two ds_write_b128 (pixels, zeroed scores) per 16 pixels; the last
-        // chunks of a row are clamped dword by dword
+        // 16 bytes per lane: one global_load_dwordx4 and two ds_write_b128 (pixels, zeroed scores) per 16 pixels; the last
+        // chunks of a row are clamped dword by dword (four global_load_dword)
         const int wmax = ((Lw - 1) & ~3);
         const int PQ = P >> 4;
         const unsigned pq_inv = B.pq_inv;                          // i / PQ exact for i < 2^20 / PQ
         for (int i = tid; i < bh * PQ; i += FC_TPB) {
             const int ly = (int)(((unsigned)i * pq_inv) >> 20), lq = i - ly * PQ;
             const int gy = min(B.y0 + ly, Lh - 1), gx = B.xa + 16 * lq;
-            const uint8_t* rowp = img + (long long)gy * Lpitch;
-            uint4 v;
-            if (gx + 12 <= wmax) __builtin_memcpy(&v, rowp + gx, 16);
+            fc_gbyte* rowp = gimg + (long long)gy * Lpitch;
+            fc_u32x4 v;
+            if (gx + 12 <= wmax) v = *reinterpret_cast<const __attribute__((address_space(1))) fc_u32x4_a4*>(rowp + gx);
             else {
-                v.x = *reinterpret_cast<const unsigned*>(rowp + min(gx, wmax));
-                v.y = *reinterpret_cast<const unsigned*>(rowp + min(gx + 4, wmax));
-                v.z = *reinterpret_cast<const unsigned*>(rowp + min(gx + 8, wmax));
-                v.w = *reinterpret_cast<const unsigned*>(rowp + min(gx + 12, wmax));
+                v.x = *reinterpret_cast<fc_gu32*>(rowp + min(gx, wmax));
+                v.y = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 4, wmax));
+                v.z = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 8, wmax));
+                v.w = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 12, wmax));
             }
-            reinterpret_cast<uint4*>(T)[i] = v;
+            reinterpret_cast<fc_u32x4*>(T)[i] = v;
             reinterpret_cast<uint4*>(S)[i] = make_uint4(0u, 0u, 0u, 0u);
         }
     } else if (dword_ok) {
@@ -594,14 +608,14 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         for (int i = tid; i < bh * PW; i += FC_TPB) {
             const int ly = (int)(((unsigned)i * pw_inv) >> 20), lx = i - ly * PW;
             const int gy = min(B.y0 + ly, Lh - 1), gx = min(B.xa + 4 * lx, wmax);
-            reinterpret_cast<unsigned*>(T)[i] = *reinterpret_cast<const unsigned*>(img + (long long)gy * Lpitch + gx);
+            reinterpret_cast<unsigned*>(T)[i] = *reinterpret_cast<fc_gu32*>(gimg + (long long)gy * Lpitch + gx);
             reinterpret_cast<unsigned*>(S)[i] = 0u;
         }
     } else {
         for (int i = tid; i < bh * P; i += FC_TPB) {
             const int ly = i / P, lx = i - ly * P;
             const int gy = min(B.y0 + ly, Lh - 1), gx = min(B.xa + lx, Lw - 1);
-            T[i] = img[(long long)gy * Lpitch + gx];
+            T[i] = gimg[(long long)gy * Lpitch + gx];
             S[i] = 0;
         }
     }
@@ -740,16 +754,21 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         for (int e = tid; e < nnz; e += FC_TPB) {
             const int pos = nz[e];
             const int row = (int)__umulhi((unsigned)pos, p_inv), col = pos - row * P;
+            // the score, its eight neighbours and the column's cell are read together (one LDS round trip; the tile has a 3-pixel
+            // margin around every detection pixel) and the neighbours outside the cell's rectangle masked afterwards: no
+            // short-circuit chain of dependent LDS reads
+            const uint8_t* p = S + pos;
             const int ci = colcell[col];
+            const int sc = p[0];
+            const int nl = p[-1], nr = p[1], nul = p[-P - 1], nu = p[-P], nur = p[-P + 1], ndl = p[P - 1], nd = p[P], ndr = p[P + 1];
+            __builtin_amdgcn_sched_barrier(0);
             if (ci == 255) continue;
             const int xx = col - l_clo[ci], yy = row - 3, rw = l_cwd[ci];
-            const uint8_t* p = S + pos;
-            const int sc = p[0];
             const bool l = xx > 0, r = xx + 1 < rw, u = yy > 0, d = yy + 1 < rh;
-#define NB(c, o) ((c) ? (int)p[o] : 0)
-            const bool keep = sc > NB(l, -1) && sc > NB(r, 1) &&
-                              sc > NB(u && l, -P - 1) && sc > NB(u, -P) && sc > NB(u && r, -P + 1) &&
-                              sc > NB(d && l, P - 1) && sc > NB(d, P) && sc > NB(d && r, P + 1);
+#define NB(c, v) ((c) ? (v) : 0)
+            const bool keep = (sc > NB(l, nl)) & (sc > NB(r, nr)) &
+                              (sc > NB(u && l, nul)) & (sc > NB(u, nu)) & (sc > NB(u && r, nur)) &
+                              (sc > NB(d && l, ndl)) & (sc > NB(d, nd)) & (sc > NB(d && r, ndr));
 #undef NB
             if (keep) {
                 const int q = atomicAdd(cell_k + ci, 1);
@@ -764,6 +783,15 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         const int e1 = ck.x, e2 = e1 + ck.y, e3 = e2 + ck.z, nk = e3 + ck.w;
         listed = max(max(ck.x, ck.y), max(ck.z, ck.w)) <= cap_c;
         if (listed) {
+            // a cell's count = its local maxima at the chosen threshold.  Every bucket entry is >= minThFAST (stored scores are
+            // >= t_lo == minThFAST here) and cell_hi counts those >= iniThFAST, so the count is cell_hi where the cell has any such
+            // maximum (threshold iniThFAST) and the whole bucket otherwise (threshold minThFAST); no bucket overflowed on this path.
+            // (Until round 3 an atomic per keypoint and a barrier before the store; then one thread per cell scanning its bucket.)
+            if (tid >= FC_TPB - FC_CELLS && FC_TPB - 1 - tid < bncells) {
+                const int ci = FC_TPB - 1 - tid;
+                const int hi = cell_hi[ci];
+                cell_count[(long long)f * g.ncells + bcfirst + ci] = hi > 0 ? hi : cell_k[ci];
+            }
             for (int e = tid; e < nk; e += FC_TPB) {
                 const int ci = (e >= e1 ? 1 : 0) + (e >= e2 ? 1 : 0) + (e >= e3 ? 1 : 0);
                 const int k0 = e - (ci == 0 ? 0 : ci == 1 ? e1 : ci == 2 ? e2 : e3);
@@ -781,16 +809,6 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                     slots[(long long)f * g.slots_per_frame + l_sfirst[ci] + rank] =
                         ((me & 255u) << 24) | ((unsigned)(by0 + 3 - ORB_BORDER + (int)((me >> 14) & 63u)) << 12) |
                         (unsigned)(bxa + l_clo[ci] - ORB_BORDER + (int)((me >> 8) & 63u));
-            }
-            // a cell's count = its local maxima at the chosen threshold: one thread per cell counts its bucket (an atomic per keypoint
-            // and a barrier before the store, until round 3)
-            if (tid >= FC_TPB - FC_CELLS && FC_TPB - 1 - tid < bncells) {
-                const int ci = FC_TPB - 1 - tid;
-                const unsigned th = (unsigned)(cell_hi[ci] > 0 ? g.ini_th : g.min_th);
-                const unsigned* bucket = kept + ci * cap_c;
-                int cnt = 0;
-                for (int k = 0; k < cell_k[ci]; k++) cnt += (bucket[k] & 255u) >= th ? 1 : 0;
-                cell_count[(long long)f * g.ncells + bcfirst + ci] = cnt;
             }
             FC_STAMP(4);
             return;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run on the GPU box from the repo root: tools/r03_fc_stamps.sh TAG -- where does a band of k_fast_cells spend its ~14 us?
-# Diagnostic build (-DFC_STAMPS): s_memtime of wave 0 at the phase boundaries of every workgroup of one 256-frame launch.
+# Diagnostic build (-DFC_STAMPS): s_memtime of wave 0 (slots 0-7) and of the last wave (slots 8-15) at the phase boundaries of every workgroup of one 256-frame launch.
 tag=$1; O=gpurun_out; mkdir -p $O
 touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip
 make -s -C motioncheck_ccm_slam_amd/csrc EXTRA="-DFC_STAMPS" > $O/${tag}_stamps.build 2>&1 || { tail -5 $O/${tag}_stamps.build; exit 1; }
@@ -16,7 +16,7 @@ for _ in range(3):
     ex.extract_dev(frames.data_ptr(), 752, 480, 752, 752 * 480, 256); ctx.sync()
 lib = _lib.load()
 n = 1 << 17
-buf = np.zeros((n, 8), np.uint64)
+buf = np.zeros((n, 16), np.uint64)
 lib.ccm_debug_fc_stamps.argtypes = [C.c_void_p, C.c_int]
 assert lib.ccm_debug_fc_stamps(buf.ctypes.data, n) == 0
 ok = buf[:, 4] > 0
@@ -32,6 +32,11 @@ print("s_memtime ticks (100 MHz constant clock? or shader clock): total median %
 for nm, (a, c) in zip(names, seq):
     d = b[:, c] - b[:, a]
     print("%-46s median %7.0f  mean %7.0f  (%.1f %% of the mean total)" % (nm, np.median(d), d.mean(), 100 * d.mean() / tot.mean()))
+# the last wave (it owned the per-cell count until the count came from the counters): same boundaries, slots 8 + k
+for nm, (a, c) in zip(names, seq):
+    d = b[:, 8 + c] - b[:, 8 + a]
+    print("last wave: %-35s median %7.0f  mean %7.0f" % (nm, np.median(d), d.mean()))
+print("workgroup start (wave 0) -> last wave's end: median %.0f  mean %.0f" % (np.median(b[:, 12] - b[:, 0]), (b[:, 12] - b[:, 0]).mean()))
 PY
 cat $O/${tag}_fc_stamps.txt
 touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip; make -s -C motioncheck_ccm_slam_amd/csrc > /dev/null 2>&1
