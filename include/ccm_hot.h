@@ -680,6 +680,75 @@ int ccm_frame_search_local_points_timing(ccm_ctx*, double ms[3]);
 int ccm_frame_pose_optimize_table(ccm_ctx*, ccm_frame* f, ccm_map_table* table, const float* inv_level_sigma2, int n_levels,
                                   const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers);
 
+/* ORBmatcher::Fuse, both overloads (src/ORBmatcher.cpp:854-1000 and :1002-1122), up to and including the selection, on keyframe
+ * handles and the table: ONE list of map points is projected into EVERY keyframe, as LoopFinder::SearchAndFuse (src/LoopFinder.cpp:
+ * 806-831), MapMerger::SearchAndFuse (src/MapMerger.cpp:574-600) and the first loop of LocalMapping::SearchInNeighbors
+ * (src/Mapping.cpp:499-521) do.  The two overloads share their arithmetic; they differ in where the pose comes from, in the chi2 test
+ * (chi2_check, :929-937) and in the acceptance threshold, which the caller passes as for ccm_fuse_select_batch.  What the reference
+ * does with a selection (Replace / AddObservation / vpReplacePoint, :958-990, :1103-1117) stays with the caller.
+ *   Pair (k, j) = point slot[j] in keyframe views[k]; the outputs are [n_kf][n_points], pair (k, j) at k * n_points + j.  Gates in the
+ *   reference's order, the first that fails names the pair (gate, CCM_FG_*), with P / Pn / min_dist / max_dist the slot's row:
+ *     SKIPPED      skip[j] != 0 (a null pointer, mbDoNotReplace :880), or the slot is not LIVE, or it is BAD (isBad(), :877 / :1023)
+ *     IN_KEYFRAME  some feature of the handle holds the slot in mp_id (IsInKeyFrame :877, spAlreadyFound :1011 / :1023); an mp_id
+ *                  outside [0, capacity) names no slot and is ignored
+ *     BEHIND       Pc[r] = (float)((double)R[r][0] P[0] + (double)R[r][1] P[1] + (double)R[r][2] P[2] + (double)t[r]);  Pc[2] < 0
+ *     OUTSIDE      invz = 1.0f / Pc[2];  x = Pc[0] * invz;  y = Pc[1] * invz;  u = fx * x + cx;  v = fy * y + cy  (float, each
+ *                  operation rounded, not fused -- NOT the association of ccm_frame_search_local_points, which follows
+ *                  Frame::isInFrustum);  !(u >= min_x && u < max_x && v >= min_y && v < max_y), KeyFrame::IsInImage
+ *                  (src/KeyFrame.cpp:1236): u == max_x is outside, and so is a NaN (Pc = 0).  The second overload writes 1.0 / Pc[2]
+ *                  in double and stores a float (:1040): the same value, a quotient of two floats rounds alike both ways.
+ *     DISTANCE     PO = P - Ow (float);  dist = (float)sqrt(sum (double)PO^2);  dist < 0.8f * min_dist || dist > 1.2f * max_dist
+ *     ANGLE        sum (double)PO[i] * (double)Pn[i] < 0.5 * (double)dist, compared in double (:914, :1063)
+ *     EMPTY_KF     the pair passed all of the above and the handle has no features (GetFeaturesInArea would return nothing)
+ *     SEARCHED     level = ceil(((float)log((double)(max_dist / dist))) / log_scale_factor) clamped to [0, n_levels - 1], a NaN gives 0
+ *                  (MapPoint::PredictScale, src/MapPoint.cpp:837-852, exactly as ccm_frame_search_local_points computes it);
+ *                  radius = th * scale_factors[level], features of level - 1 .. level inside the window, with chi2_check those
+ *                  whose reprojection error e2 * inv_level_sigma2[octave] is at most 5.99; the nearest descriptor, the first of equal
+ *                  ones in GetFeaturesInArea's order.  best_dist = its distance (256: none), best_idx = its index when
+ *                  best_dist <= accept_th, else -1 -- per pair what ccm_fuse_select_batch_frames returns for valid = 1, these u / v /
+ *                  level and the slot's descriptor.
+ *   Every pair that is not SEARCHED has best_idx = -1 and best_dist = 256.  The taps u / v / level (all three or none) hold the values
+ *   above where the pair got that far, and 0 before.
+ * Traffic: one page-locked staging copy up (the views with the handles' device pointers, the slot list, skip, inv_level_sigma2) --
+ * nothing per pair, nothing of a keyframe or a map point; the projection appends the SEARCHED pairs to a query list in device memory
+ * and only those run the selection.  One download of the outputs that were asked for.  The call synchronises twice: on the number of
+ * queries (16 bytes) behind the projection, and on the download.  It is ordered on the context's stream behind
+ * ccm_frame_set_map_points, ccm_map_table_update and ccm_map_table_refresh calls made before it.
+ * Errors are found on the host before anything is queued; the outputs are then untouched.  CCM_E_ARG: a NULL required array (views,
+ * slot, scale_factors, best_idx, inv_level_sigma2 with chi2_check, a view's kf), only some of u / v / level, n_levels outside
+ * 1..CCM_MAX_LEVELS, a slot outside [0, capacity) or listed twice, a handle or table of another context.  CCM_E_STATE: a handle or table
+ * that outlived its context.  CCM_E_CAPACITY: more than 65535 keyframes or 2^24 pairs in one call.  Memory: the
+ * query list is sized for every pair surviving, 69 bytes of device memory per pair plus 4 to 21 bytes per pair (by the outputs asked
+ * for) of page-locked host and device staging, kept by the context at its high-water mark -- about 11 MB + 1.4 MB at 160,000 pairs,
+ * 1.1 GB + 0.35 GB at the cap; split a larger problem over the keyframes.  n_kf == 0 or n_points == 0
+ * returns CCM_OK with n_searched = 0. */
+enum { CCM_FG_SEARCHED = 0, CCM_FG_SKIPPED = 1, CCM_FG_IN_KEYFRAME = 2, CCM_FG_BEHIND = 3, CCM_FG_OUTSIDE = 4, CCM_FG_DISTANCE = 5,
+       CCM_FG_ANGLE = 6, CCM_FG_EMPTY_KF = 7 };
+typedef struct {
+    ccm_frame* kf;                     /* features, grid and mp_id (as table slots) are read; no bow / camera / pose needed */
+    float Tcw[12];                     /* rows of [Rcw | tcw]: GetRotation / GetTranslation (:856-857), or the caller's decomposition of Scw (:1004-1007) */
+    float Ow[3];                       /* GetCameraCenter (:864), or -Rcw^T tcw as the caller computed it (:1008) */
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y;  /* mnMinX .. mnMaxY (KeyFrame::IsInImage, src/KeyFrame.cpp:1236) */
+} ccm_fuse_view;
+typedef struct {
+    int32_t n_kf;  const ccm_fuse_view* views;       /* the same handle may appear twice, with different poses */
+    int32_t n_points;  const int32_t* slot;          /* [n_points] table slots; ONE list, projected into every keyframe */
+    const uint8_t* skip;                             /* [n_points] or NULL: 1 = never looked at (null pointer, mbDoNotReplace) */
+    float log_scale_factor;  int32_t n_levels;       /* mfLogScaleFactor, mnScaleLevels (1..CCM_MAX_LEVELS) */
+    const float* scale_factors;                      /* [n_levels] */
+    const float* inv_level_sigma2;                   /* [n_levels], needed with chi2_check */
+    float th;  int32_t chi2_check;  int32_t accept_th;   /* as ccm_fuse_select_batch */
+} ccm_fuse_table_problem;
+typedef struct {
+    int32_t* best_idx;                 /* [n_kf][n_points] feature of keyframe k selected for point j, or -1 */
+    int32_t* best_dist;                /* optional, same shape; 256 where best_idx is -1 for want of a candidate */
+    uint8_t* gate;                     /* optional tap, same shape: CCM_FG_* */
+    float* u; float* v; int32_t* level;/* optional taps, same shape; meaningful where gate == CCM_FG_SEARCHED */
+    int32_t n_searched;                /* out: pairs that passed every gate */
+} ccm_fuse_table_result;
+int ccm_fuse_select_table_frames(ccm_ctx*, ccm_map_table*, const ccm_fuse_table_problem*, ccm_fuse_table_result*);
+
 /* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:867-1062), next row F4,
  * batched over candidate keyframe pairs: one VertexSim3Expmap, fixed points, EdgeSim3ProjectXYZ +
  * EdgeInverseSim3ProjectXYZ per correspondence with g2o's numeric Jacobians (delta 1e-9) and Huber(sqrt(th2));

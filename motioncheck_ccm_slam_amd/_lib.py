@@ -40,6 +40,7 @@ SYMBOLS = [
     "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
     "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
+    "ccm_fuse_select_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
@@ -177,6 +178,25 @@ class SlpResult(C.Structure):
                 ("occupied", C.c_void_p)]
 
 
+FG_GATES = ("SEARCHED", "SKIPPED", "IN_KEYFRAME", "BEHIND", "OUTSIDE", "DISTANCE", "ANGLE", "EMPTY_KF")   # CCM_FG_* of include/ccm_hot.h
+
+
+class FuseView(C.Structure):
+    _fields_ = [("kf", C.c_void_p), ("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+class FuseTableProblem(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("views", C.POINTER(FuseView)), ("n_points", C.c_int32), ("slot", C.c_void_p), ("skip", C.c_void_p),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p),
+                ("th", C.c_float), ("chi2_check", C.c_int32), ("accept_th", C.c_int32)]
+
+
+class FuseTableResult(C.Structure):
+    _fields_ = [("best_idx", C.c_void_p), ("best_dist", C.c_void_p), ("gate", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+                ("level", C.c_void_p), ("n_searched", C.c_int32)]
+
+
 class EssentialGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int), ("sim3", C.c_void_p), ("fixed", C.c_void_p), ("fix_scale", C.c_int), ("n_edges", C.c_int),
                 ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("measurement", C.c_void_p), ("iterations", C.c_int),
@@ -302,6 +322,7 @@ def load():
     lib.ccm_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(SlpParams), C.POINTER(SlpResult)]
     lib.ccm_frame_search_local_points_timing.argtypes = [vp, vp]
     lib.ccm_frame_pose_optimize_table.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.ccm_fuse_select_table_frames.argtypes = [vp, vp, C.POINTER(FuseTableProblem), C.POINTER(FuseTableResult)]
     lib.ccm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int]
     lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]
     lib.ccm_sim3_solver_destroy.argtypes = [vp]; lib.ccm_sim3_solver_destroy.restype = None

@@ -21,7 +21,12 @@ struct ccm_map_table {
     DevBuf order; int n_order = 0; bool order_all = true;    // order_all: ascending slot over the LIVE slots
     int stamp = 0;                               // per-table call counter of SearchLocalPoints: seen[slot] == stamp <=> seen in this call
     std::vector<uint32_t> gen; std::vector<int32_t> row; uint32_t cur_gen = 0;   // host: last row of a slot within one update / order
+    DevBuf where; unsigned fuse_stamp = 0;       // ccm_fuse_select_table_frames: per slot, stamp << 32 | position in that call's slot list
 };
+
+// match_kernels.hip: k_window_select<true>, query q against grids[q_kf[q]]
+void match_launch_window_select_batch(hipStream_t, const WinGrid* grids, const int* q_kf, int nq, const float* qx, const float* qy, const float* qr,
+                                      const int* minl, const int* maxl, const uint8_t* qdesc, const float* inv_sigma2, int accept_th, int* best_idx, int* best_dist);
 
 void mpt_tables_orphan(FrameState* S)            // ccm_destroy: the memory goes, the handles stay for ccm_map_table_destroy
 {
@@ -305,6 +310,121 @@ int ccm_map_table_refresh(ccm_ctx* c, ccm_map_table* t, const ccm_map_refresh* u
         if (res->normal) std::memcpy(res->normal, h + o_nrm, m * 12);
         if (res->min_dist) std::memcpy(res->min_dist, h + o_min, m * 4);
         if (res->max_dist) std::memcpy(res->max_dist, h + o_max, m * 4);
+        return CCM_OK;
+    });
+}
+
+// what a keyframe costs in the staging copy of ccm_fuse_select_table_frames (tools/bench_fuse_table.py counts the upload with these)
+static_assert(sizeof(FuseView) == 112 && sizeof(WinGrid) == 80, "per-keyframe upload of ccm_fuse_select_table_frames");
+
+// ORBmatcher::Fuse, both overloads (src/ORBmatcher.cpp:854-1000, :1002-1122), up to the selection, for every (keyframe, point) pair.
+// Staging: [ count | best_idx | best_dist | gate | u | v | level ] down, [ views | grids | slot | skip | inv_level_sigma2 ] up; the
+// taps take room only when asked for.  The query list and the selections stay in device memory (FrameState::fuse).
+int ccm_fuse_select_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_fuse_table_problem* p, ccm_fuse_table_result* r)
+{
+    RoctxRange roctx_("ccm_fuse_select_table_frames");
+    if (!c || !t || !p || !r) return CCM_E_ARG;
+    const char* fn = "ccm_fuse_select_table_frames";
+    int rc = check_table(c, t);
+    if (rc) return rc;
+    if (p->n_kf < 0 || p->n_points < 0) return ccm_fail(c, CCM_E_ARG, "%s: n_kf = %d, n_points = %d", fn, p->n_kf, p->n_points);
+    if (p->n_kf == 0 || p->n_points == 0) { r->n_searched = 0; return CCM_OK; }
+    if (!p->views || !p->slot || !p->scale_factors || !r->best_idx || (p->chi2_check && !p->inv_level_sigma2))
+        return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !p->views ? "views" : !p->slot ? "slot" : !p->scale_factors ? "scale_factors" :
+                        !r->best_idx ? "best_idx" : "inv_level_sigma2 with chi2_check");
+    if (p->n_levels < 1 || p->n_levels > CCM_MAX_LEVELS) return ccm_fail(c, CCM_E_ARG, "%s: n_levels = %d outside 1..%d", fn, p->n_levels, CCM_MAX_LEVELS);
+    if ((r->u || r->v || r->level) && !(r->u && r->v && r->level)) return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and level come together", fn);
+    if (p->n_kf > 65535 || (size_t)p->n_kf * (size_t)p->n_points > ((size_t)1 << 24))
+        return ccm_fail(c, CCM_E_CAPACITY, "%s: %d keyframes x %d points; at most 65535 keyframes and 2^24 pairs a call", fn, p->n_kf, p->n_points);
+    return ccm_guard(c, fn, [&]() -> int {
+        const int n_kf = p->n_kf, n_pt = p->n_points;
+        int max_n = 0;
+        for (int k = 0; k < n_kf; k++) {
+            const ccm_frame* f = p->views[k].kf;
+            if (!f) return ccm_fail(c, CCM_E_ARG, "%s: null views[%d].kf", fn, k);
+            if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: views[%d].kf outlived its context", fn, k);
+            if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: views[%d].kf belongs to another context", fn, k);
+            max_n = std::max(max_n, f->n);
+        }
+        bool dup = false;
+        if ((rc = mark_slots(c, t, n_pt, p->slot, &dup))) return rc;
+        if (dup) return ccm_fail(c, CCM_E_ARG, "%s: a slot is listed twice", fn);
+
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        hipStream_t st = c->stream;
+        const size_t m = (size_t)n_kf * (size_t)n_pt;
+        const bool taps = r->u != nullptr;
+        size_t off = 0;
+        const size_t o_cnt = seg(off, 16), o_bi = seg(off, m * 4), o_bd = seg(off, r->best_dist ? m * 4 : 0), o_gate = seg(off, r->gate ? m : 0);
+        const size_t o_u = seg(off, taps ? m * 4 : 0), o_v = seg(off, taps ? m * 4 : 0), o_lvl = seg(off, taps ? m * 4 : 0);
+        const size_t res_end = off;
+        const size_t o_view = seg(off, (size_t)n_kf * sizeof(FuseView)), o_grid = seg(off, (size_t)n_kf * sizeof(WinGrid));
+        const size_t o_slot = seg(off, (size_t)n_pt * 4), o_skip = seg(off, p->skip ? (size_t)n_pt : 0);
+        const size_t o_is2 = seg(off, p->chi2_check ? CCM_MAX_LEVELS * 4 : 0);
+        const size_t end = off;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, end, &h))) return rc;
+        size_t w = 0;                                                          // device-only work area
+        const size_t w_held = seg(w, m), w_qx = seg(w, m * 4), w_qy = seg(w, m * 4), w_qr = seg(w, m * 4), w_minl = seg(w, m * 4), w_maxl = seg(w, m * 4);
+        const size_t w_qkf = seg(w, m * 4), w_qpair = seg(w, m * 4), w_qdesc = seg(w, m * 32), w_si = seg(w, m * 4), w_sd = seg(w, m * 4);
+        CCM_RESERVE(c, S.fuse, w + 64);
+        if (!t->where.p) {                                                     // first Fuse on this table: every entry older than any stamp
+            CCM_RESERVE(c, t->where, (size_t)t->capacity * 8);
+            CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st));
+            t->fuse_stamp = 0;
+        }
+        if (t->fuse_stamp == 0xffffffffu) { CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st)); t->fuse_stamp = 0; }
+        const unsigned stamp = ++t->fuse_stamp;
+
+        FuseView* hv = (FuseView*)(h + o_view); WinGrid* hg = (WinGrid*)(h + o_grid);
+        for (int k = 0; k < n_kf; k++) {
+            const ccm_fuse_view& V = p->views[k];
+            const ccm_frame* f = V.kf;
+            FuseView& D = hv[k];
+            std::memcpy(D.Tcw, V.Tcw, sizeof D.Tcw); std::memcpy(D.Ow, V.Ow, sizeof D.Ow);
+            D.fx = V.fx; D.fy = V.fy; D.cx = V.cx; D.cy = V.cy; D.min_x = V.min_x; D.max_x = V.max_x; D.min_y = V.min_y; D.max_y = V.max_y;
+            D.n = f->n; D.pad_ = 0; D.mp_id = f->mp_id;
+            hg[k] = WinGrid{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+        }
+        std::memcpy(h + o_slot, p->slot, (size_t)n_pt * 4);
+        if (p->skip) std::memcpy(h + o_skip, p->skip, (size_t)n_pt);
+        if (p->chi2_check) {
+            float* is2 = (float*)(h + o_is2);
+            for (int l = 0; l < CCM_MAX_LEVELS; l++) is2[l] = l < p->n_levels ? p->inv_level_sigma2[l] : 0.f;
+        }
+        if ((rc = frame_upload(c, o_view, end))) return rc;
+        uint8_t* io = S.io.as<uint8_t>(); uint8_t* wk = S.fuse.as<uint8_t>();
+        FuseArgs A{};
+        A.n_kf = n_kf; A.n_points = n_pt;
+        A.views = (const FuseView*)(io + o_view); A.slot = (const int*)(io + o_slot); A.skip = p->skip ? io + o_skip : nullptr;
+        A.where = t->where.as<unsigned long long>(); A.stamp = stamp; A.held = wk + w_held;
+        A.log_scale = p->log_scale_factor; A.n_levels = p->n_levels; A.th = p->th;
+        for (int l = 0; l < CCM_MAX_LEVELS; l++) A.scale[l] = l < p->n_levels ? p->scale_factors[l] : 0.f;
+        A.best_idx = (int*)(io + o_bi); A.best_dist = r->best_dist ? (int*)(io + o_bd) : nullptr; A.gate = r->gate ? io + o_gate : nullptr;
+        A.u = taps ? (float*)(io + o_u) : nullptr; A.v = taps ? (float*)(io + o_v) : nullptr; A.level = taps ? (int*)(io + o_lvl) : nullptr;
+        A.cnt = (int*)(io + o_cnt); A.qx = (float*)(wk + w_qx); A.qy = (float*)(wk + w_qy); A.qr = (float*)(wk + w_qr);
+        A.minl = (int*)(wk + w_minl); A.maxl = (int*)(wk + w_maxl); A.qkf = (int*)(wk + w_qkf); A.qpair = (int*)(wk + w_qpair); A.qdesc = wk + w_qdesc;
+        CCM_HIP(c, hipMemsetAsync(A.cnt, 0, 16, st));
+        CCM_HIP(c, hipMemsetAsync(A.held, 0, m, st));
+        fuse_launch_project(st, A, t->T, max_n);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = frame_download(c, 16))) return rc;                           // the number of queries: the first synchronisation
+        int nq = 0;
+        std::memcpy(&nq, h + o_cnt, 4);
+        if (nq < 0 || (size_t)nq > m) return ccm_fail(c, CCM_E_DEVICE, "%s: %d queries of %zu pairs", fn, nq, m);
+        if (nq > 0) {
+            match_launch_window_select_batch(st, (const WinGrid*)(io + o_grid), A.qkf, nq, A.qx, A.qy, A.qr, A.minl, A.maxl, A.qdesc,
+                                             p->chi2_check ? (const float*)(io + o_is2) : nullptr, p->accept_th, (int*)(wk + w_si), (int*)(wk + w_sd));
+            fuse_launch_scatter(st, nq, (int)m, A.qpair, (const int*)(wk + w_si), (const int*)(wk + w_sd), A.best_idx, A.best_dist);
+            CCM_HIP(c, hipGetLastError());
+        }
+        if ((rc = frame_download(c, res_end))) return rc;                      // the second
+        std::memcpy(r->best_idx, h + o_bi, m * 4);
+        if (r->best_dist) std::memcpy(r->best_dist, h + o_bd, m * 4);
+        if (r->gate) std::memcpy(r->gate, h + o_gate, m);
+        if (taps) { std::memcpy(r->u, h + o_u, m * 4); std::memcpy(r->v, h + o_v, m * 4); std::memcpy(r->level, h + o_lvl, m * 4); }
+        r->n_searched = nq;
         return CCM_OK;
     });
 }

@@ -9,6 +9,10 @@
 //   k_mpt_pose_gather  k_frame_pose_gather (frame_kernels.hip) with the points read from the table as float
 //   k_mpt_refresh      MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823)
 //                      for a list of points whose observations name keyframe handles; one wave per point
+//   k_fuse_where / k_fuse_held / k_fuse_project / k_fuse_scatter
+//                      ccm_fuse_select_table_frames: the projection and the gates of ORBmatcher::Fuse, both overloads
+//                      (src/ORBmatcher.cpp:870-920, :1018-1071), for every (keyframe, point) pair; the survivors become the
+//                      queries of k_window_select (match_kernels.hip)
 // No kernel waits for another workgroup: the compaction is three launches (ballot + count, scan, scatter).
 // Every index is checked against the table's capacity before it is used as an address.
 #include <hip/hip_runtime.h>
@@ -351,6 +355,122 @@ __global__ __launch_bounds__(MPR_TPB) void k_mpt_refresh(MptRefreshArgs A, MptTa
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- fuse
+// Membership ("keyframe k already holds point j", IsInKeyFrame :877 / spAlreadyFound :1023) without a search: where[slot] = the
+// call's stamp and the slot's position in the list, then every feature of every keyframe looks its mp_id up.  An entry of an earlier
+// call carries an older stamp and reads as "not listed"; nothing has to be cleared.
+__global__ void k_fuse_where(FuseArgs A, int capacity)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= A.n_points) return;
+    const int s = A.slot[j];
+    if (s >= 0 && s < capacity) A.where[s] = ((unsigned long long)A.stamp << 32) | (unsigned)j;
+}
+__global__ void k_fuse_held(FuseArgs A, int capacity)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    const FuseView& V = A.views[k];
+    if (i >= V.n) return;
+    const int id = V.mp_id[i];
+    if (id < 0 || id >= capacity) return;        // an id outside the table names none of the listed points
+    const unsigned long long w = A.where[id];
+    const unsigned pos = (unsigned)w;
+    if ((unsigned)(w >> 32) == A.stamp && pos < (unsigned)A.n_points) A.held[(size_t)k * A.n_points + pos] = 1;   // several features: same value
+}
+
+// MapPoint::PredictScale (src/MapPoint.cpp:837-852) with the raw mfMaxDistance, the expression slp_in_frustum ends with: the double log
+// rounded to float, ceilf, clamped; a NaN gives 0
+__device__ inline int fuse_predict_level(float max_d, float dist, float log_scale, int n_levels)
+{
+    const float ratio = max_d / dist;
+    const float lg = (float)log((double)ratio);
+    const float q = ceilf(lg / log_scale);
+    return !(q >= 0.0f) ? 0 : (q >= (float)n_levels ? n_levels - 1 : (int)q);
+}
+
+// One thread per (keyframe, point) pair; blockIdx.y = the keyframe, so the view is the same for the whole workgroup and is read
+// through scalar loads.  Arithmetic of a float cv::Mat as in slp_in_frustum (products of a matrix product, dot and norm summed in
+// double), but Fuse's own association of the projection: x = PcX * invz first, then fx * x + cx (:890-895, :1040-1045).
+// The survivors of a wave take consecutive places of the query list behind ONE atomic add; which wave comes first is not fixed, and
+// does not matter: k_window_select decides per query and k_fuse_scatter writes by pair index.
+__global__ __launch_bounds__(FUSE_TPB) void k_fuse_project(FuseArgs A, MptTable T)
+{
+    const int j = blockIdx.x * FUSE_TPB + threadIdx.x, k = blockIdx.y, lane = threadIdx.x & 63;
+    const FuseView& V = A.views[k];
+    const size_t n_pairs = (size_t)A.n_kf * A.n_points, pair = (size_t)k * A.n_points + (j < A.n_points ? j : 0);
+    bool keep = false;
+    int gate = CCM_FG_SKIPPED, level = 0, s = -1;
+    float u = 0.0f, v = 0.0f;
+    if (j < A.n_points) {
+        s = A.slot[j];
+        uint8_t fl = 0;
+        if (s >= 0 && s < T.capacity && !(A.skip && A.skip[j])) fl = T.flags[s];
+        if ((fl & CCM_MP_LIVE) && !(fl & CCM_MP_BAD)) {
+            gate = CCM_FG_IN_KEYFRAME;
+            if (!A.held[pair]) {
+                const float P[3] = { T.pos[3 * (size_t)s], T.pos[3 * (size_t)s + 1], T.pos[3 * (size_t)s + 2] };
+                float Pc[3];
+                for (int r = 0; r < 3; r++)
+                    Pc[r] = (float)((double)V.Tcw[4 * r] * (double)P[0] + (double)V.Tcw[4 * r + 1] * (double)P[1] +
+                                    (double)V.Tcw[4 * r + 2] * (double)P[2] + (double)V.Tcw[4 * r + 3]);
+                gate = CCM_FG_BEHIND;
+                if (!(Pc[2] < 0.0f)) {
+                    const float invz = __fdiv_rn(1.0f, Pc[2]);
+                    const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+                    u = __fadd_rn(__fmul_rn(V.fx, x), V.cx);
+                    v = __fadd_rn(__fmul_rn(V.fy, y), V.cy);
+                    gate = CCM_FG_OUTSIDE;
+                    if (u >= V.min_x && u < V.max_x && v >= V.min_y && v < V.max_y) {      // KeyFrame::IsInImage; a NaN is outside
+                        const float max_d = T.max_dist[s];
+                        const float PO[3] = { P[0] - V.Ow[0], P[1] - V.Ow[1], P[2] - V.Ow[2] };
+                        const float dist = (float)sqrt((double)PO[0] * (double)PO[0] + (double)PO[1] * (double)PO[1] + (double)PO[2] * (double)PO[2]);
+                        gate = CCM_FG_DISTANCE;
+                        if (!(dist < 0.8f * T.min_dist[s] || dist > 1.2f * max_d)) {
+                            const double dot = (double)PO[0] * (double)T.normal[3 * (size_t)s] + (double)PO[1] * (double)T.normal[3 * (size_t)s + 1] +
+                                               (double)PO[2] * (double)T.normal[3 * (size_t)s + 2];
+                            gate = CCM_FG_ANGLE;
+                            if (!(dot < 0.5 * (double)dist)) {
+                                level = fuse_predict_level(max_d, dist, A.log_scale, A.n_levels);
+                                gate = V.n > 0 ? CCM_FG_SEARCHED : CCM_FG_EMPTY_KF;
+                                keep = V.n > 0;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        A.best_idx[pair] = -1;
+        if (A.best_dist) A.best_dist[pair] = 256;
+        if (A.gate) A.gate[pair] = (uint8_t)gate;
+        if (A.u) { A.u[pair] = u; A.v[pair] = v; A.level[pair] = level; }
+    }
+    const unsigned long long ball = __ballot(keep);
+    if (!ball) return;
+    const int leader = __ffsll((long long)ball) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(A.cnt, __popcll(ball));
+    base = __shfl(base, leader, 64);
+    if (!keep) return;
+    const size_t q = (size_t)base + __popcll(ball & ((1ull << lane) - 1ull));
+    if (q >= n_pairs) return;                    // cannot happen: at most one query per pair
+    A.qx[q] = u; A.qy[q] = v; A.qr[q] = A.th * A.scale[level];      // :920 / :1071
+    A.minl[q] = level - 1; A.maxl[q] = level;                       // :937-938 / :1089
+    A.qkf[q] = k; A.qpair[q] = (int)pair;
+    const uint4* a = reinterpret_cast<const uint4*>(T.desc + (size_t)s * 32);
+    uint4* b = reinterpret_cast<uint4*>(A.qdesc + q * 32);
+    b[0] = a[0]; b[1] = a[1];
+}
+
+__global__ void k_fuse_scatter(int nq, int n_pairs, const int* qpair, const int* sel_i, const int* sel_d, int* best_idx, int* best_dist)
+{
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    const int pair = qpair[q];
+    if (pair < 0 || pair >= n_pairs) return;
+    best_idx[pair] = sel_i[q];
+    if (best_dist) best_dist[pair] = sel_d[q];
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
 void mpt_launch_scatter(hipStream_t s, const MptTable& T, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
                         const float* max_dist, const uint8_t* desc, const uint8_t* flags)
@@ -381,4 +501,15 @@ void mpt_launch_pose_gather(hipStream_t s, const MptPoseGatherArgs& A, const Mpt
 void mpt_launch_refresh(hipStream_t s, const MptRefreshArgs& A, const MptTable& T)
 {
     if (A.n > 0) hipLaunchKernelGGL(k_mpt_refresh, dim3((A.n + MPR_TPB / 64 - 1) / (MPR_TPB / 64)), dim3(MPR_TPB), 0, s, A, T);
+}
+void fuse_launch_project(hipStream_t s, const FuseArgs& A, const MptTable& T, int max_n)
+{
+    if (A.n_kf < 1 || A.n_points < 1) return;
+    hipLaunchKernelGGL(k_fuse_where, dim3((A.n_points + 255) / 256), dim3(256), 0, s, A, T.capacity);
+    if (max_n > 0) hipLaunchKernelGGL(k_fuse_held, dim3((max_n + 255) / 256, A.n_kf), dim3(256), 0, s, A, T.capacity);
+    hipLaunchKernelGGL(k_fuse_project, dim3((A.n_points + FUSE_TPB - 1) / FUSE_TPB, A.n_kf), dim3(FUSE_TPB), 0, s, A, T);
+}
+void fuse_launch_scatter(hipStream_t s, int nq, int n_pairs, const int* qpair, const int* sel_i, const int* sel_d, int* best_idx, int* best_dist)
+{
+    if (nq > 0) hipLaunchKernelGGL(k_fuse_scatter, dim3((nq + 255) / 256), dim3(256), 0, s, nq, n_pairs, qpair, sel_i, sel_d, best_idx, best_dist);
 }

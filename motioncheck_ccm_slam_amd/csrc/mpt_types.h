@@ -8,6 +8,7 @@
 #define SCAN_TPB 1024
 #define MPG_TPB 1024
 #define MPR_TPB 256        // k_mpt_refresh: one wave per map point, 4 points per workgroup
+#define FUSE_TPB 256       // k_fuse_project: one thread per (keyframe, point) pair, the keyframe uniform per workgroup
 #define MPR_LDS_ROWS 256   // descriptors a wave keeps in LDS: 8 KB per wave, 32 KB per workgroup; further rows are read from global memory
 
 struct MptTable {                                // the table's columns (device)
@@ -43,6 +44,21 @@ struct MptRefreshArgs {
     int* best; float* normal; float* min_dist; float* max_dist;      // per listed point, in the call's result block
 };
 
+// ccm_fuse_select_table_frames.  What k_fuse_project reads of keyframe k: the caller's pose and camera and the handle's map-point ids.
+struct FuseView { float Tcw[12], Ow[3], fx, fy, cx, cy, min_x, max_x, min_y, max_y; int n; int pad_; const int* mp_id; };
+
+struct FuseArgs {
+    int n_kf, n_points;
+    const FuseView* views; const int* slot; const uint8_t* skip;     // skip == nullptr: no point is skipped
+    unsigned long long* where; unsigned stamp;                       // per table slot: stamp << 32 | position in the slot list
+    uint8_t* held;                                                   // [n_kf][n_points] keyframe k holds point j
+    float log_scale; int n_levels; float scale[CCM_MAX_LEVELS]; float th;
+    // per pair, in the call's result block
+    int* best_idx; int* best_dist; uint8_t* gate; float* u; float* v; int* level;
+    // the pairs that passed every gate, in no particular order: the queries of k_window_select and their pair index
+    int* cnt; float* qx; float* qy; float* qr; int* minl; int* maxl; int* qkf; int* qpair; uint8_t* qdesc;
+};
+
 void mpt_launch_scatter(hipStream_t, const MptTable&, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
                         const float* max_dist, const uint8_t* desc, const uint8_t* flags);
 void mpt_launch_gather(hipStream_t, const MptTable&, int n, const int* slot, float* pos, float* normal, float* min_dist, float* max_dist,
@@ -53,3 +69,7 @@ int  slp_workgroups(int n_order);
 void slp_launch_frustum(hipStream_t, const SlpArgs&, const MptTable&, int* cnt);
 void mpt_launch_pose_gather(hipStream_t, const MptPoseGatherArgs&, const MptTable&);
 void mpt_launch_refresh(hipStream_t, const MptRefreshArgs&, const MptTable&);
+// k_fuse_where and k_fuse_held (max_n: the largest feature count among the keyframes), then k_fuse_project: gates, taps, cnt[0] queries
+void fuse_launch_project(hipStream_t, const FuseArgs&, const MptTable&, int max_n);
+// best_idx / best_dist of query q to pair qpair[q]
+void fuse_launch_scatter(hipStream_t, int nq, int n_pairs, const int* qpair, const int* sel_i, const int* sel_d, int* best_idx, int* best_dist);

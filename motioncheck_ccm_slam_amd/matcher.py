@@ -309,6 +309,48 @@ def _fuse_select_batch_frames(self, frames, scale_factors, inv_level_sigma2, per
 ORBmatcher.FuseSelectBatchFrames = _fuse_select_batch_frames
 
 
+def _fuse_select_table_frames(self, table, frames, Tcw, Ow, intr, bounds, slots, scale_factors, inv_level_sigma2=None, th: float = 3.0,
+                              chi2_check: bool = True, accept_th: int = 50, skip=None, log_scale_factor=None, taps: bool = False):
+    """ORBmatcher::Fuse up to the selection with the map points read from a `tracking.MapPointTable` and the keyframes given as
+    DeviceFrame handles (ccm_fuse_select_table_frames): the ONE list `slots` is projected into every keyframe, gated and matched on
+    the device; nothing is uploaded per pair.  Tcw [K][12] (rows of [Rcw | tcw]), Ow [K][3], intr [K][4] or [4] = fx, fy, cx, cy,
+    bounds [K][4] or [4] = mnMinX, mnMaxX, mnMinY, mnMaxY.  Returns a dict of numpy arrays, each [K][len(slots)]: best_idx, best_dist
+    and, with taps, gate (CCM_FG_*), u, v, level; plus n_searched."""
+    a = np.ascontiguousarray
+    K = len(frames)
+    slot = a(slots, "i4").reshape(-1); n = len(slot)
+    T = a(Tcw, "f4").reshape(K, 12); O = a(Ow, "f4").reshape(K, 3)
+    I = np.broadcast_to(a(intr, "f4").reshape(-1, 4), (K, 4)); B = np.broadcast_to(a(bounds, "f4").reshape(-1, 4), (K, 4))
+    sf = a(scale_factors, "f4"); s2 = None if inv_level_sigma2 is None else a(inv_level_sigma2, "f4")
+    sk = None if skip is None else a(skip, np.uint8).reshape(-1)
+    if sk is not None and len(sk) != n:
+        raise ValueError("skip needs one entry per slot")
+    if log_scale_factor is None:
+        log_scale_factor = np.float32(np.log(np.float64(sf[1]))) if len(sf) > 1 else np.float32(1.0)   # mfLogScaleFactor = log(mfScaleFactor)
+    views = (_lib.FuseView * max(K, 1))()
+    for k, f in enumerate(frames):
+        views[k].kf = f.handle
+        views[k].Tcw[:] = [float(x) for x in T[k]]; views[k].Ow[:] = [float(x) for x in O[k]]
+        views[k].fx, views[k].fy, views[k].cx, views[k].cy = [float(x) for x in I[k]]
+        views[k].min_x, views[k].max_x, views[k].min_y, views[k].max_y = [float(x) for x in B[k]]
+    pad = slot if n else np.zeros(1, "i4")
+    prob = _lib.FuseTableProblem(K, views, n, _lib.ptr(pad), _lib.ptr(sk), float(log_scale_factor), len(sf), _lib.ptr(sf), _lib.ptr(s2), float(th),
+                                 int(chi2_check), int(accept_th))
+    m = max(K * n, 1)
+    out = dict(best_idx=np.full(m, -1, "i4"), best_dist=np.full(m, 256, "i4"))
+    if taps:
+        out.update(gate=np.zeros(m, np.uint8), u=np.zeros(m, "f4"), v=np.zeros(m, "f4"), level=np.zeros(m, "i4"))
+    g = lambda k: _lib.ptr(out[k]) if k in out else None  # noqa: E731
+    res = _lib.FuseTableResult(g("best_idx"), g("best_dist"), g("gate"), g("u"), g("v"), g("level"), 0)
+    self.ctx.check(self.lib.ccm_fuse_select_table_frames(self.ctx.handle, C.c_void_p(table.handle), C.byref(prob), C.byref(res)))
+    ret = {k: v[:K * n].reshape(K, n) for k, v in out.items()}
+    ret["n_searched"] = int(res.n_searched)
+    return ret
+
+
+ORBmatcher.FuseSelectTableFrames = _fuse_select_table_frames
+
+
 def _search_by_sim3(self, kf1: FrameGridView, sf1, kf2: FrameGridView, sf2, valid1, u1, v1, level1, mp_desc1, valid2, u2, v2, level2, mp_desc2,
                     th: float):
     """ORBmatcher::SearchBySim3 (ORBmatcher.cpp:1124-1348) after the caller's projections.  Returns (nFound, match12)."""

@@ -12,7 +12,8 @@
 // ids and the pose are sent again, when the keyframe's stamp (ccm_shim.h, INTEGRATION.md "Keyframe handles") says they changed.
 // CreateNewMapPoints then calls ccm_create_new_map_points_frames.  SearchInNeighbors runs right after on the same keyframes: its
 // first Fuse loop (:499-504) becomes one call of ccm_shim::fuse_into_targets (below, declared in fuse_steps.h), which makes ONE
-// ccm_fuse_select_batch_frames; the integrator replaces that loop in src/Mapping.cpp, the rest of the function stays the reference's.
+// ccm_fuse_select_table_frames on the map-point table (or, where the table is another thread's, projects on the host and makes ONE
+// ccm_fuse_select_batch_frames); the integrator replaces that loop in src/Mapping.cpp, the rest of the function stays the reference's.
 //
 // One difference in timing, none in result: the match of a later neighbour is computed before an earlier neighbour's points exist.
 // It cannot see them anyway (ccm_hot.h "CreateNewMapPoints": vbMatched2 is never set, no orientation filter; a feature that wins with
@@ -24,6 +25,7 @@
 #include <cslam/MapPoint.h>
 #include <cslam/Map.h>
 #include <algorithm>
+#include <cstdint>
 #include <map>
 #include "ccm_shim.h"
 #include "fuse_steps.h"
@@ -102,8 +104,9 @@ void sweep_keyframe_handles()
     H.clock++;
 }
 
-// The handle of pKF with its map-point ids and pose up to date, or nullptr on failure.  ids: feature i holds a map point <=> id >= 0
-// (the value itself is not read by the two calls made here).
+// The handle of pKF with its map-point ids and pose up to date, or nullptr on failure.  ids: feature i holds a map point <=> id >= 0;
+// the value is the point's slot in the map-point table, which ccm_fuse_select_table_frames reads (IsInKeyFrame), or INT32_MAX -- an id
+// outside every table -- while the point has none.  The stamp is not kept then, so the ids are sent again once the slot exists.
 ccm_frame* keyframe_handle(const LocalMapping::kfptr& pKF)
 {
     KfHandles& H = kf_handles();
@@ -129,7 +132,13 @@ ccm_frame* keyframe_handle(const LocalMapping::kfptr& pKF)
     }
     if (fresh || now == 0 || now != e.stamp) {                                  // 0: no hook ever touched it, so nothing is known
         std::vector<int32_t> ids(n);
-        for (int i = 0; i < n; i++) ids[i] = pKF->GetMapPoint(i) ? i : -1;      // :743-747, :760-764, as the function is entered
+        bool all_slotted = true;
+        for (int i = 0; i < n; i++) {                                           // :743-747, :760-764, as the function is entered
+            const LocalMapping::mpptr pMP = pKF->GetMapPoint(i);
+            const int slot = ccm_shim::map_slot_of(pMP);
+            ids[i] = !pMP ? -1 : slot >= 0 ? slot : INT32_MAX;
+            if (pMP && slot < 0) all_slotted = false;
+        }
         const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
         float Tcw[12], Ow[3];
         for (int r = 0; r < 3; r++) {
@@ -138,7 +147,7 @@ ccm_frame* keyframe_handle(const LocalMapping::kfptr& pKF)
             Ow[r] = O.at<float>(r);
         }
         if (ccm_frame_set_map_points(e.f, ids.data()) || ccm_frame_set_pose(e.f, Tcw, Ow)) return nullptr;
-        e.stamp = now;
+        e.stamp = all_slotted ? now : 0;
     }
     return e.f;
 }
@@ -238,10 +247,13 @@ void LocalMapping::CreateNewMapPoints()
 
 }  // namespace cslam
 
-// The first Fuse loop of LocalMapping::SearchInNeighbors (src/Mapping.cpp:499-504) on keyframe handles: the current keyframe's map
-// points are projected into every target keyframe on the host (fuse_steps.h), ONE ccm_fuse_select_batch_frames selects for all of them
-// (a second-level neighbour can be listed twice, :486-493, and so can its handle), and the results are applied keyframe by keyframe in
-// the list's order with the reference's state checks repeated at application time.  With CCM_SHIM_KEYFRAME_HANDLES=0 it is the loop of
+// The first Fuse loop of LocalMapping::SearchInNeighbors (src/Mapping.cpp:499-504) on keyframe handles.  First choice: ONE
+// ccm_fuse_select_table_frames projects the current keyframe's map points into every target keyframe, gates and selects on the
+// device, reading the points from the map-point table (ccm_shim::fuse_select_on_table, fuse_steps.h).  Where that is not possible --
+// the table belongs to another thread's context, or a point has no slot yet -- the points are projected on the host and ONE
+// ccm_fuse_select_batch_frames selects for all keyframes.  Either way a second-level neighbour can be listed twice (:486-493), and so
+// can its handle, and the results are applied keyframe by keyframe in the list's order with the reference's state checks repeated at
+// application time (apply_fuse).  With CCM_SHIM_KEYFRAME_HANDLES=0 it is the loop of
 // ORBmatcher::Fuse calls.  Called from LocalMapping's thread only.
 void ccm_shim::fuse_into_targets(const std::vector<cslam::ORBmatcher::kfptr>& vpTargetKFs, const std::vector<cslam::ORBmatcher::mpptr>& vpMapPointMatches)
 {
@@ -253,6 +265,15 @@ void ccm_shim::fuse_into_targets(const std::vector<cslam::ORBmatcher::kfptr>& vp
         return;
     }
     sweep_keyframe_handles();
+    {
+        std::vector<FusePose> poses(n_t);
+        for (int k = 0; k < n_t; k++) poses[k] = FusePose{vpTargetKFs[k]->GetRotation(), vpTargetKFs[k]->GetTranslation(), vpTargetKFs[k]->GetCameraCenter()};
+        std::vector<int32_t> best;
+        if (fuse_select_on_table(vpTargetKFs, poses, vpMapPointMatches, 3.0f, /*chi2_check=*/1, ORBmatcher::TH_LOW, &keyframe_handle, best)) {
+            for (int k = 0; k < n_t; k++) apply_fuse(vpTargetKFs[k], vpMapPointMatches, best.data() + (size_t)k * nMPs);
+            return;
+        }
+    }
     std::vector<ccm_frame*> h(n_t);
     std::vector<int32_t> mp_first(n_t + 1, 0), level;
     std::vector<uint8_t> valid, desc;

@@ -208,6 +208,63 @@ public:
         }
         return true;
     }
+    // ORBmatcher::Fuse up to the selection for every (keyframe, point) pair in one ccm_fuse_select_table_frames (fuse_steps.h,
+    // fuse_select_on_table).  As refresh(): only on the thread that owns the table, rows queued earlier are flushed first, and on any
+    // failure nothing of the caller's is touched.
+    bool fuse_select(const std::vector<cslam::Tracking::kfptr>& kfs, const std::vector<FusePose>& poses, const std::vector<mpptr>& pts, float th,
+                     int chi2_check, int accept_th, KeyframeHandleOf handle_of, std::vector<int32_t>& best)
+    {
+        ccm_ctx* c = ctx();
+        {
+            std::lock_guard<std::mutex> lock(mMutex);
+            if (!mTable || mCtx != c) return false;
+        }
+        const int n_kf = (int)kfs.size(), n = (int)pts.size();
+        if (poses.size() != kfs.size()) return false;
+        std::vector<int32_t> slot, row_of(n, -1);
+        std::vector<uint8_t> skip;
+        std::map<int, int> at;                                                   // slot -> its place in the list
+        for (int i = 0; i < n; i++) {
+            const mpptr& pMP = pts[i];
+            if (!pMP) continue;                                                  // :874
+            const int s = slot_of(pMP);
+            if (s < 0) return false;
+            const auto it = at.find(s);
+            if (it != at.end()) { row_of[i] = it->second; continue; }
+            at[s] = row_of[i] = (int)slot.size();
+            slot.push_back(s);
+            skip.push_back(chi2_check && pMP->mbDoNotReplace ? 1 : 0);           // :880; commented out at :1026
+        }
+        const int m = (int)slot.size();
+        std::vector<int32_t> sel((size_t)n_kf * m, -1);
+        if (n_kf > 0 && m > 0) {
+            std::vector<ccm_fuse_view> views(n_kf);
+            for (int k = 0; k < n_kf; k++) {
+                const cslam::Tracking::kfptr& pKF = kfs[k];
+                ccm_fuse_view& V = views[k];
+                if (!(V.kf = handle_of(pKF))) return false;
+                for (int r = 0; r < 3; r++) {
+                    for (int cc = 0; cc < 3; cc++) V.Tcw[4 * r + cc] = poses[k].Rcw.at<float>(r, cc);
+                    V.Tcw[4 * r + 3] = poses[k].tcw.at<float>(r);
+                    V.Ow[r] = poses[k].Ow.at<float>(r);
+                }
+                V.fx = pKF->fx; V.fy = pKF->fy; V.cx = pKF->cx; V.cy = pKF->cy;
+                V.min_x = pKF->mnMinX; V.max_x = pKF->mnMaxX; V.min_y = pKF->mnMinY; V.max_y = pKF->mnMaxY;
+            }
+            ccm_map_table* table = flush();                                      // SetBadFlag / SetWorldPos rows queued by other threads
+            if (!table) return false;
+            const cslam::Tracking::kfptr& pKF0 = kfs[0];                         // one client's keyframes share the extractor's scale tables
+            const ccm_fuse_table_problem p{n_kf, views.data(), m, slot.data(), skip.data(), pKF0->mfLogScaleFactor, (int32_t)pKF0->mvScaleFactors.size(),
+                                           pKF0->mvScaleFactors.data(), pKF0->mvInvLevelSigma2.data(), th, chi2_check, accept_th};
+            ccm_fuse_table_result r{sel.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+            if (ccm_fuse_select_table_frames(c, table, &p, &r)) return false;
+        }
+        best.assign((size_t)n_kf * n, -1);
+        for (int k = 0; k < n_kf; k++)
+            for (int i = 0; i < n; i++)
+                if (row_of[i] >= 0) best[(size_t)k * n + i] = sel[(size_t)k * m + row_of[i]];
+        return true;
+    }
     // The slots in view of the previous SearchLocalPoints: Frame::isInFrustum clears mbTrackInView of every point it tests, so a
     // point that was in view and is rejected now must not keep a stale `true`.
     std::vector<int32_t> mLastInView;
@@ -228,6 +285,14 @@ private:
 bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of)
 {
     return MapTable::get().refresh(pts, what, handle_of);
+}
+
+int map_slot_of(const ORBmatcher::mpptr& pMP) { return pMP ? MapTable::get().slot_of(pMP) : -1; }
+
+bool fuse_select_on_table(const std::vector<ORBmatcher::kfptr>& kfs, const std::vector<FusePose>& poses, const std::vector<ORBmatcher::mpptr>& pts,
+                          float th, int chi2_check, int accept_th, KeyframeHandleOf handle_of, std::vector<int32_t>& best)
+{
+    return MapTable::get().fuse_select(kfs, poses, pts, th, chi2_check, accept_th, handle_of, best);
 }
 
 }  // namespace ccm_shim

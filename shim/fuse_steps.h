@@ -86,4 +86,21 @@ void fuse_into_targets(const std::vector<ORBmatcher::kfptr>& vpTargetKFs, const 
 using KeyframeHandleOf = ccm_frame* (*)(const ORBmatcher::kfptr&);
 bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of);
 
+// The slot of pMP in the calling process's map-point table, or -1 (ccm_shim::MapTable::slot_of, cslam_tracking.cpp).  A keyframe handle
+// that is to serve fuse_select_on_table carries these in its map-point ids.
+int map_slot_of(const ORBmatcher::mpptr& pMP);
+
+// The projection, the gates and the selection of ORBmatcher::Fuse (:870-955, :1018-1101) for every keyframe of kfs and every point of
+// pts in ONE ccm_fuse_select_table_frames on the map-point table: nothing is projected on the host and nothing is uploaded per pair.
+// poses[k] = the pose Fuse would use for kfs[k]: GetRotation / GetTranslation / GetCameraCenter (:856-864), or the decomposition of
+// Scw (:1004-1008).  chi2_check = 1, th = 3 is Fuse(pKF, vpMapPoints); chi2_check = 0, th = 4 is Fuse(pKF, Scw, ...), which does not
+// ask mbDoNotReplace (:1026), so that flag is honoured with chi2_check only.  Every distinct point travels once; a null pointer gets
+// -1 and a duplicate the row of its first occurrence (the caller's apply step re-tests IsInKeyFrame, as the reference's second visit
+// would).  best [kfs.size()][pts.size()] = the selected feature or -1.
+// false = nothing was done and best is untouched: the table belongs to another thread's context, a point has no slot yet, or a
+// handle is missing.  The caller then takes the host route (project_for_fuse and ccm_fuse_select_batch_frames).
+struct FusePose { cv::Mat Rcw, tcw, Ow; };
+bool fuse_select_on_table(const std::vector<ORBmatcher::kfptr>& kfs, const std::vector<FusePose>& poses, const std::vector<ORBmatcher::mpptr>& pts,
+                          float th, int chi2_check, int accept_th, KeyframeHandleOf handle_of, std::vector<int32_t>& best);
+
 }  // namespace ccm_shim
