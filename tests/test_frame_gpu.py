@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import optimizer_cases as C_
 from motioncheck_ccm_slam_amd import _lib, synth
 from motioncheck_ccm_slam_amd.frame import DeviceFrame
 from motioncheck_ccm_slam_amd.matcher import FRAME_GRID_COLS, FRAME_GRID_ROWS, FrameGridView, ORBmatcher
@@ -239,6 +240,25 @@ def test_handle_pose_optimize(ctx, oracle):
         with pytest.raises(_lib.CcmError) as e:
             Optimizer.PoseOptimizationFrame(h, pose, intr, table, is2)
         assert e.value.code == E_ARG
+
+
+@pytest.mark.parametrize("N", C_.FRAME_SIZES)
+def test_handle_pose_optimize_at_the_compaction_edges(ctx, N):
+    """k_frame_pose_gather is one workgroup of 1024 threads with a ballot per wave and a running base per 1024-block: frames of N
+    features at and across 1024, with every feature set, only the last plus two, wave 0 of each block empty, every second 64-group
+    empty and exactly 3 set.  Pose, per-feature flags and inlier count equal the array call on the gathered problem bit for bit."""
+    is2 = ORBextractor(1000, 1.2, 8, 20, 7, ctx=ctx).GetInverseScaleSigmaSquares()
+    desc = np.random.default_rng(N).integers(0, 256, (N, 32), dtype=np.uint8)
+    for pattern in C_.FRAME_PATTERNS:
+        fc = C_.frame_case(N, pattern)
+        has = fc["mask"]
+        pts, obs, info = C_.gathered(fc, is2)
+        rp, ro, rn = Optimizer.PoseOptimizationClient(fc["pose"][None], fc["intr"][None], np.array([0, has.sum()], "i4"), pts, obs, info, ctx=ctx)
+        with DeviceFrame(FrameGridView(fc["kx"], fc["ky"], fc["oct"], desc, *C_.FRAME_BOUNDS), None, ctx=ctx) as h:
+            h.map_points = fc["ids"]
+            p7, outl, ni = Optimizer.PoseOptimizationFrame(h, fc["pose"], fc["intr"], fc["table"], is2)
+        assert (p7 == rp[0]).all() and ni == rn[0] and (outl[has] == ro).all() and (outl[~has] == 0).all(), (N, pattern)
+        assert ni >= 3 and (p7 != fc["pose"]).any() and (has.sum() < 100 or ro.sum() >= has.sum() // 7 - 8), (N, pattern)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. chain

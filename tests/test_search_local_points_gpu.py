@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import optimizer_cases as C_
 import search_local_points_ref as R
 from motioncheck_ccm_slam_amd import _lib, synth
 from motioncheck_ccm_slam_amd.frame import DeviceFrame
@@ -325,6 +326,27 @@ def test_pose_from_table_and_track_local_map(ctx, matchable):
             rp, ro, _ = Optimizer.PoseOptimizationFrame(h2, pose, intr, xyz, S["is2"])
             assert s["nmatches"] == hn and (s["mp_id"] == h2.map_points).all()
             assert (p7 == rp).all() and (outl == ro).all() and inl == int(((h2.map_points >= 0) & (ro == 0)).sum()) and inl > 300
+
+
+def test_pose_from_table_at_the_compaction_edges(ctx):
+    """k_mpt_pose_gather across a 1024-block with every second 64-group empty (1025 features): the table form equals the array call
+    on the gathered problem bit for bit; the points are the table's float32 positions."""
+    N = 1025
+    fc = C_.frame_case(N, "alternate")
+    has = fc["mask"]
+    is2 = ORBextractor(1000, 1.2, 8, 20, 7, ctx=ctx).GetInverseScaleSigmaSquares()
+    rows = R.random_points(N, 5)
+    rows["pos"] = fc["table"].astype("f4")
+    assert (rows["pos"].astype("f8") == fc["table"]).all()           # positions already went through float32
+    pts, obs, info = C_.gathered(fc, is2)
+    rp, ro, rn = Optimizer.PoseOptimizationClient(fc["pose"][None], fc["intr"][None], np.array([0, has.sum()], "i4"), pts, obs, info, ctx=ctx)
+    desc = np.random.default_rng(N).integers(0, 256, (N, 32), dtype=np.uint8)
+    with MapPointTable(N, ctx=ctx) as t, DeviceFrame(FrameGridView(fc["kx"], fc["ky"], fc["oct"], desc, *C_.FRAME_BOUNDS), None, ctx=ctx) as h:
+        t.update(np.arange(N), **{k: rows[k] for k in COLS})
+        h.map_points = fc["ids"]
+        p7, outl, ni = Tracking.PoseOptimizationTable(h, t, fc["pose"], fc["intr"], is2)
+    assert (p7 == rp[0]).all() and ni == rn[0] and (outl[has] == ro).all() and (outl[~has] == 0).all()
+    assert has.sum() == 512 and ni > 400 and ro.sum() >= 60
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. misuse, churn

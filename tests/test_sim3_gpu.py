@@ -2,8 +2,9 @@
 import numpy as np
 import pytest
 
+import optimizer_cases as C
 from motioncheck_ccm_slam_amd.optimizer import Optimizer
-from sim3_problems import make_problem, sim3_map
+from sim3_problems import make_pose_graph, make_problem, sim3_map
 
 pytestmark = pytest.mark.gpu
 
@@ -100,3 +101,117 @@ def test_essential_graph_2000_keyframes(ctx, oracle):
     assert (again == out).all() and info2["chi2_final"] == info["chi2_final"]                  # fixed summation orders: bit-reproducible
     loop_err = oracle.sim3_log(oracle.sim3_mul(oracle.sim3_mul(meas[-1], out[ei[-1]]), oracle.sim3_inverse(out[ej[-1]])))
     assert np.abs(loop_err).max() < 0.05
+
+
+# ---------------------------------------------------------------------------------------------------------------- schedule edges
+def _sim3_batch(ctx, probs, th2):
+    first = np.concatenate([[0], np.cumsum([len(p["info1"]) for p in probs])]).astype("i4")
+    cat = lambda k: np.concatenate([p[k] for p in probs])
+    S, inl, nin = Optimizer.OptimizeSim3(np.stack([p["S0"] for p in probs]), 0, np.stack([p["K1"] for p in probs]), np.stack([p["K2"] for p in probs]),
+                                         first, cat("P1"), cat("P2"), cat("obs1"), cat("obs2"), cat("info1"), cat("info2"), np.asarray(th2, "f4"), ctx=ctx)
+    return S, [inl[first[i]:first[i + 1]] for i in range(len(probs))], nin
+
+
+def test_optimize_sim3_at_the_ten_survivor_rule(ctx, oracle):
+    """12 - nb pairs survive the first round: nb = 2 leaves exactly 10 (optimised, 10 inliers), nb = 3 leaves 9 (returns 0, the
+    estimate bit-untouched; src/Optimizer.cpp:1022-1023), with nb = 1 and nb = 4 around them and th2 10 / 20 mixed.  The same call
+    after a 300-pair problem on the same context gives the same bits (the per-pair error and flag buffers are reused)."""
+    probs = [C.sim3_survivor_problem(nb) for nb in C.SIM3_SURVIVOR_NB]
+    th2 = C.SIM3_SURVIVOR_TH2
+    S, inl, nin = _sim3_batch(ctx, probs, th2)
+    for i, p in enumerate(probs):
+        rS, rinl, rn = oracle.optimize_sim3(p["S0"], 0, p["K1"], p["K2"], p["P1"], p["P2"], p["obs1"], p["obs2"], p["info1"], p["info2"], th2[i])
+        d = float(np.abs(S[i] - rS).max())
+        print("nb = %d, th2 = %g: %d inliers, max |S - oracle| = %.3g" % (C.SIM3_SURVIVOR_NB[i], th2[i], nin[i], d))
+        assert nin[i] == rn == C.SIM3_SURVIVOR_INLIERS[i] and (inl[i] == rinl).all() and d < 1e-7, (i, d)
+        assert (S[i] == p["S0"]).all() == (rn == 0)
+    big = make_problem(np.random.default_rng(11), 300, outlier_frac=0.3)
+    _, _, nbig = _sim3_batch(ctx, [big], [10.0])
+    assert nbig[0] > 100
+    S2, inl2, nin2 = _sim3_batch(ctx, probs, th2)
+    assert (S2 == S).all() and (nin2 == nin).all() and all((a == b).all() for a, b in zip(inl, inl2))
+
+
+def _ess(ctx, oracle, sim3, fixed, ei, ej, meas, name):
+    """The GPU solve held to the oracle at the bounds of test_essential_graph_matches_oracle."""
+    out, info = Optimizer.OptimizeEssentialGraph(sim3, fixed, ei, ej, meas, False, 20, ctx=ctx)
+    ref, rinfo = oracle.essential_graph(sim3, fixed, ei, ej, meas, False, 20)
+    d = float(np.abs(out - ref).max())
+    print("%s: %d iterations, chi2 %.6g -> %.6g, max |S - oracle| = %.3g" % (name, info["iterations_done"], info["chi2_initial"], info["chi2_final"], d))
+    assert info["iterations_done"] == rinfo["iterations_done"], name
+    assert np.isclose(info["chi2_initial"], rinfo["chi2_initial"], rtol=1e-9) and np.isclose(info["chi2_final"], rinfo["chi2_final"], rtol=1e-6), name
+    assert d < 1e-6, (name, d)
+    assert (out[fixed != 0] == sim3[fixed != 0]).all(), name
+    return out, info
+
+
+@pytest.fixture(scope="module")
+def graph40(ctx, oracle):
+    sim3, fixed, ei, ej, meas, truth = make_pose_graph(oracle, np.random.default_rng(C.ESS_SEED), n=40)
+    return sim3, fixed, ei, ej, meas, _ess(ctx, oracle, sim3, fixed, ei, ej, meas, "original numbering"), truth
+
+
+def test_essential_graph_relabelled(ctx, oracle, graph40):
+    """A random vertex numbering: edges with i < j as well as i > j and a scattered fill pattern; the result is the same graph's."""
+    sim3, fixed, ei, ej, meas, (out, info), _ = graph40
+    perm = np.random.default_rng(7).permutation(40)
+    s2, f2, pi, pj = C.relabel_graph(perm, sim3, fixed, ei, ej)
+    assert 40 <= (pi < pj).sum() <= len(ei) - 40
+    out2, info2 = _ess(ctx, oracle, s2, f2, pi, pj, meas, "relabelled")
+    d = float(np.abs(out2[perm] - out).max())
+    print("relabelled vs original numbering on the GPU: %.3g" % d)
+    assert d <= 1e-9 and (out2[perm[0]] == sim3[0]).all()
+    si, sj, sm = C.swap_edges(oracle, ei, ej, meas)                                 # every edge written i < j
+    assert (si < sj).all()
+    out3, info3 = _ess(ctx, oracle, sim3, fixed, si, sj, sm, "all edges i < j")
+    assert info3["chi2_final"] < 0.05 * info3["chi2_initial"]
+
+
+def test_essential_graph_duplicate_edges(ctx, oracle, graph40):
+    """Every edge listed twice: the blocks accumulate (chi2 doubles), the solution stays."""
+    sim3, fixed, ei, ej, meas, (out, info), _ = graph40
+    out2, info2 = _ess(ctx, oracle, sim3, fixed, np.tile(ei, 2), np.tile(ej, 2), np.tile(meas, (2, 1)), "duplicate edges")
+    d = float(np.abs(out2 - out).max())
+    print("duplicate edges vs single edges on the GPU: %.3g" % d)
+    assert np.isclose(info2["chi2_initial"], 2 * info["chi2_initial"], rtol=1e-12) and d <= 1e-9
+
+
+def test_essential_graph_several_fixed_vertices(ctx, oracle, graph40):
+    sim3, fixed, ei, ej, meas, _, truth = graph40
+    fx = fixed.copy(); fx[20] = 1
+    out, info = _ess(ctx, oracle, sim3, fx, ei, ej, meas, "vertices 0 and 20 fixed")
+    assert (out[0] == sim3[0]).all() and (out[20] == sim3[20]).all() and info["chi2_final"] < info["chi2_initial"]
+    fm, ci, cj, cm = C.two_chain_graph(oracle, sim3, ei, ej, meas, truth, 20)               # the free vertices form two separate chains
+    out, info = _ess(ctx, oracle, sim3, fm, ci, cj, cm, "two chains around fixed vertex 20")
+    assert (out[20] == sim3[20]).all() and (out[:20] != sim3[:20]).any() and (out[21:] != sim3[21:]).any()
+
+
+def test_essential_graph_small_graphs(ctx, oracle, graph40):
+    s, fx, ei, ej, meas = C.two_vertex_graph()                                       # one edge, zero residual
+    out, info = _ess(ctx, oracle, s, fx, ei, ej, meas, "two vertices")
+    assert (out == s).all() and info["chi2_initial"] == 0 and info["chi2_final"] == 0
+    sim3, _, ei, ej, meas, _, _ = graph40                                            # nothing free: the input comes back
+    out, info = _ess(ctx, oracle, sim3, np.ones(40, np.uint8), ei, ej, meas, "all vertices fixed")
+    assert (out == sim3).all() and info["chi2_final"] == info["chi2_initial"] and info["iterations_done"] == 0
+
+
+@pytest.mark.parametrize("n_points", [1, 255, 256, 257, 1000])
+def test_correct_map_points_whole_array(ctx, n_points):
+    """Every point against a float64 numpy restatement of inverse(after[r]) o before[r]; about a quarter have no reference keyframe."""
+    rng = np.random.default_rng(n_points)
+    nv = 30
+    before = np.stack([C.rand_sim3(rng) for _ in range(nv)]); after = np.stack([C.rand_sim3(rng) for _ in range(nv)])
+    pts = rng.normal(0, 3, (n_points, 3))
+    refv = np.where(rng.random(n_points) < 0.25, -1, rng.integers(0, nv, n_points)).astype("i4")
+    refv[-1] = nv - 1                                                                # the last point and the last keyframe are used
+    if n_points >= 255:
+        refv[0] = -1
+        assert 0.15 < (refv < 0).mean() < 0.35
+    moved = Optimizer.CorrectMapPoints(pts, refv, before, after, ctx=ctx)
+    exp = C.correct_map_points_ref(pts, refv, before, after)
+    d = float(np.abs(moved - exp).max())
+    print("%d points: max |moved - numpy| = %.3g" % (n_points, d))
+    assert d <= 1e-12
+    assert (moved[refv < 0] == pts[refv < 0]).all() and (moved[refv >= 0] != pts[refv >= 0]).all(1).all()
+    none = Optimizer.CorrectMapPoints(pts, np.full(n_points, -1, "i4"), before, after, ctx=ctx)
+    assert (none == pts).all()
