@@ -1,4 +1,5 @@
-// bow_directory_dev.h -- arguments of k_bow_directory (bow_kernels.hip), shared with its caller (frame_host.cpp).
+// bow_directory_dev.h -- arguments of k_bow_directory and the launchers of bow_kernels.hip, shared with their callers (bow_host.cpp,
+// frame_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -17,3 +18,6 @@ struct BowDirArgs {
     int* counts;                                // out: { features with a node, distinct nodes }
 };
 int bow_launch_directory(hipStream_t, const BowDirArgs&);   // nonzero: n outside [0, kBowDirMax], nothing launched
+void bow_launch_transform(hipStream_t, const uint8_t* feat, int n, const int* node_first, const int* node_count, const uint8_t* slot_desc,
+                          const int* slot_node, const int* node_word, int nid_level, int max_depth, int* word_id, int* leaf_node, int* node_id);
+void bow_launch_distinctive(hipStream_t, const uint8_t* desc, const long long* first, const int* count, int n_points, int* best);

@@ -6,10 +6,6 @@
 #include <cmath>
 #include <map>
 
-void bow_launch_transform(hipStream_t, const uint8_t* feat, int n, const int* node_first, const int* node_count, const uint8_t* slot_desc,
-                          const int* slot_node, const int* node_word, int nid_level, int max_depth, int* word_id, int* leaf_node, int* node_id);
-void bow_launch_distinctive(hipStream_t, const uint8_t* desc, const long long* first, const int* count, int n_points, int* best);
-
 struct ccm_vocabulary {
     ccm_ctx* ctx = nullptr;
     int k = 0, L = 0, n = 0, n_words = 0, depth = 0;

@@ -9,6 +9,7 @@
 //   k_ess_chi2       sum |e|^2 in a fixed order
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "ess_types.h"
 #include "sim3_math.h"
 
 __device__ void ess_error(const double* C, const double* Si, const double* Sj, double* e)

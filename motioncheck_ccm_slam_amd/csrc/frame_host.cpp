@@ -10,6 +10,7 @@
 #include "bow_directory.h"
 #include <algorithm>
 #include <climits>
+#include <cstdarg>
 #include <new>
 
 struct FrameLayout { size_t kx, ky, oct, angle, desc, upload_end, mp_id, items, first, bytes; };
@@ -225,7 +226,7 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
     const float* d_qang = w.qang; const int* id_src = w.id_src;
     int rc;
     w.host_accept = false;
-    const WinGrid G{ n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+    const WinGrid G = frame_win_grid(f);
     auto lists = [&](int cap) -> int {
         CCM_RESERVE(c, S.ci, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cd, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cn, (size_t)nq * 4);
         match_launch_window(st, G, nq, d_qx, d_qy, d_qr, d_minl, d_maxl, d_qdesc, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>());
@@ -376,6 +377,65 @@ int frame_check(ccm_ctx* c, const ccm_frame* f)
 {
     if (!f->ctx) return ccm_fail(c, CCM_E_ARG, "frame handle outlived its context");
     if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "frame handle belongs to another context");
+    return CCM_OK;
+}
+
+int frame_named_check(ccm_ctx* c, const ccm_frame* f, const char* fn, const char* who, ...)
+{
+    char name[48];
+    va_list ap;
+    va_start(ap, who);
+    vsnprintf(name, sizeof name, who, ap);
+    va_end(ap);
+    if (!f) return ccm_fail(c, CCM_E_ARG, "%s: %s is null", fn, name);
+    if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: %s outlived its context", fn, name);
+    if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: %s belongs to another context", fn, name);
+    return CCM_OK;
+}
+
+int frame_pose_run(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp_xyz, const float* pos, const uint8_t* flags,
+                   const float* inv_level_sigma2, int n_levels, const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers,
+                   bool* bad_id)
+{
+    CCM_HIP(c, hipSetDevice(c->device));
+    FrameState& S = *frame_state(c);
+    hipStream_t st = c->stream;
+    const int n = f->n;
+    const size_t xyz_bytes = mp_xyz ? (size_t)n_mp * 24 : 0;
+    size_t off = 0;
+    const size_t o_ninl = seg(off, 16), o_outl = seg(off, (size_t)n), o_pose = seg(off, 56);
+    const size_t res_end = o_pose + 56;
+    const size_t o_intr = seg(off, 32), o_is2 = seg(off, (size_t)n_levels * 4), o_xyz = seg(off, xyz_bytes);
+    const size_t end = off;
+    uint8_t* h = nullptr;
+    int rc;
+    if ((rc = frame_staging(c, end, &h))) return rc;
+    std::memcpy(h + o_pose, pose7, 56); std::memcpy(h + o_intr, intr, 32);
+    std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4);
+    if (xyz_bytes) std::memcpy(h + o_xyz, mp_xyz, xyz_bytes);
+    if ((rc = frame_upload(c, o_pose, end))) return rc;
+    CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
+    CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
+    uint8_t* io = S.io.as<uint8_t>();
+    int* d_ninl = (int*)(io + o_ninl); int* d_status = d_ninl + 1;
+    PoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, n_mp, (const double*)(io + o_xyz), pos, flags, (const float*)(io + o_is2), n_levels,
+                      S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
+    frame_launch_pose_gather(st, G);
+    CCM_HIP(c, hipGetLastError());
+    PoseDev D{ 1, (double*)(io + o_pose), (const double*)(io + o_intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
+               S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
+    pose_launch(st, D);
+    CCM_HIP(c, hipGetLastError());
+    frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
+    CCM_HIP(c, hipGetLastError());
+    if ((rc = frame_download(c, res_end))) return rc;
+    int head[2];
+    std::memcpy(head, S.host + o_ninl, 8);
+    *bad_id = head[1] != 0;
+    if (*bad_id) return CCM_OK;
+    std::memcpy(pose7, S.host + o_pose, 56);
+    std::memcpy(outlier, S.host + o_outl, n);
+    *n_inliers = head[0];
     return CCM_OK;
 }
 
@@ -708,41 +768,9 @@ int ccm_frame_pose_optimize(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp
         return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
     if (f->n == 0) { *n_inliers = 0; return CCM_OK; }
     return ccm_guard(c, "ccm_frame_pose_optimize", [&]() -> int {
-        CCM_HIP(c, hipSetDevice(c->device));
-        FrameState& S = *frame_state(c);
-        hipStream_t st = c->stream;
-        const int n = f->n;
-        size_t off = 0;
-        const size_t o_ninl = seg(off, 16), o_outl = seg(off, (size_t)n), o_pose = seg(off, 56);
-        const size_t res_end = o_pose + 56;
-        const size_t o_intr = seg(off, 32), o_is2 = seg(off, (size_t)n_levels * 4), o_xyz = seg(off, (size_t)n_mp * 24);
-        const size_t end = off;
-        uint8_t* h = nullptr;
-        if ((rc = frame_staging(c, end, &h))) return rc;
-        std::memcpy(h + o_pose, pose7, 56); std::memcpy(h + o_intr, intr, 32);
-        std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4); std::memcpy(h + o_xyz, mp_xyz, (size_t)n_mp * 24);
-        if ((rc = frame_upload(c, o_pose, end))) return rc;
-        CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
-        CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
-        uint8_t* io = S.io.as<uint8_t>();
-        int* d_ninl = (int*)(io + o_ninl); int* d_status = d_ninl + 1;
-        PoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, n_mp, (const double*)(io + o_xyz), (const float*)(io + o_is2), n_levels,
-                          S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
-        frame_launch_pose_gather(st, G);
-        CCM_HIP(c, hipGetLastError());
-        PoseDev D{ 1, (double*)(io + o_pose), (const double*)(io + o_intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
-                   S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
-        pose_launch(st, D);
-        CCM_HIP(c, hipGetLastError());
-        frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
-        CCM_HIP(c, hipGetLastError());
-        if ((rc = frame_download(c, res_end))) return rc;
-        int head[2];
-        std::memcpy(head, S.host + o_ninl, 8);
-        if (head[1]) return ccm_fail(c, CCM_E_ARG, "a map-point id outside [0, %d) or an octave outside [0, %d)", n_mp, n_levels);
-        std::memcpy(pose7, S.host + o_pose, 56);
-        std::memcpy(outlier, S.host + o_outl, n);
-        *n_inliers = head[0];
+        bool bad_id = false;
+        if ((rc = frame_pose_run(c, f, n_mp, mp_xyz, nullptr, nullptr, inv_level_sigma2, n_levels, intr, pose7, outlier, n_inliers, &bad_id))) return rc;
+        if (bad_id) return ccm_fail(c, CCM_E_ARG, "a map-point id outside [0, %d) or an octave outside [0, %d)", n_mp, n_levels);
         return CCM_OK;
     });
 }

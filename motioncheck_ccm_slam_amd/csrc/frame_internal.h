@@ -1,39 +1,13 @@
 // frame_internal.h -- what the host translation units of the frame handles share: frame_host.cpp (the handles and their matchers)
-// and mpt_host.cpp (the map-point table and the calls that take a frame and a table).  The kernel argument structures must match
-// frame_kernels.hip / pose_kernels.hip.
+// and mpt_host.cpp (the map-point table and the calls that take a frame and a table).  The kernel argument structures and launchers
+// they use come from the kernel files' types headers.
 #pragma once
 #include "ccm_internal.h"
 #include "window_types.h"
-#include "map_math.h"
+#include "frame_types.h"
+#include "pose_types.h"
 #include "bow_directory_dev.h"
 
-struct FrameBuildArgs {                          // must match frame_kernels.hip
-    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
-    const ccm_keypoint* kps; const uint8_t* src_desc;
-    int keep_xy;
-    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
-};
-struct PoseGatherArgs {                          // must match frame_kernels.hip
-    int n; const float* kx; const float* ky; const int* oct; const int* mp_id;
-    int n_mp; const double* xyz; const float* inv_sigma2; int n_levels;
-    int* first; double* pts; double* obs; double* info; int* kof; int* status;
-};
-struct PoseDev {                                 // must match pose_kernels.hip
-    int n_frames; double* poses; const double* intr; const int* first; const double* pts; const double* obs;
-    const double* info; double* err; uint8_t* outlier; int* n_inliers;
-};
-void pose_launch(hipStream_t, const PoseDev&);
-size_t frame_build_lds(int cells);
-int frame_launch_build(hipStream_t, const FrameBuildArgs&);
-void frame_launch_prep_last(hipStream_t, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl);
-void frame_launch_scatter_ids(hipStream_t, int n, const int* match, const int* src, const int* status, int* mp_id);
-void frame_launch_pose_gather(hipStream_t, const PoseGatherArgs&);
-void frame_launch_pose_scatter(hipStream_t, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier);
-struct KfGatherArgs {                            // must match frame_kernels.hip
-    int m; const int* order; const float* kx; const float* ky; const int* oct; const uint8_t* desc; const float* sf; const float* sig2;
-    MapFeat* feat_o; uint8_t* desc_o;
-};
-void frame_launch_kf_gather(hipStream_t, const KfGatherArgs&);
 int orb_last_result(ccm_ctx*, const ccm_keypoint** kps, const uint8_t** desc, const int32_t** counts, int* n_images, int* max_per_image,
                     int* nlevels);
 
@@ -83,6 +57,12 @@ struct FrameState {
     double slp_ms[3] = { -1, 0, 0 };             // host wall time of its last call (ccm_frame_search_local_points_timing)
 };
 
+// The handle's features and grid as the windowed matchers read them
+static inline WinGrid frame_win_grid(const ccm_frame* f)
+{
+    return WinGrid{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+}
+
 static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
 
 // ccm_destroy: releases the device memory of the map-point tables still alive and orphans their handles (mpt_host.cpp)
@@ -99,6 +79,9 @@ int frame_download(ccm_ctx* c, size_t b);
 int frame_fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 // CCM_E_ARG for a handle of another context or one that outlived its context
 int frame_check(ccm_ctx* c, const ccm_frame* f);
+// A handle passed under a name of the caller's (printf-style, e.g. "kfs[%d]", k): CCM_E_ARG for a null handle or one of another
+// context, CCM_E_STATE for one that outlived its context
+int frame_named_check(ccm_ctx* c, const ccm_frame* f, const char* fn, const char* who, ...) __attribute__((format(printf, 4, 5)));
 // What a handle lacks to serve as a keyframe of CreateNewMapPoints ("bow", "camera", "pose"), or nullptr
 const char* frame_keyframe_lacks(const ccm_frame* f);
 
@@ -121,3 +104,11 @@ struct WinDevCall {
 };
 // occupied [n] in/out and match [n] out are host arrays; returns nmatches or an error.
 int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied, int32_t* match);
+
+// Optimizer::PoseOptimizationClient(Frame&) on a handle whose arguments the entry point has checked (f->n > 0): the points are
+// mp_xyz [n_mp][3] (host, uploaded with the call) or, with mp_xyz == nullptr, the device columns pos / flags of a map-point table of
+// capacity n_mp.  Staging [ n_inliers+status | outlier | pose | intr | inv_sigma2 | (xyz) ]: one upload, gather -> pose_launch ->
+// scatter, one download.  A bad id or octave sets *bad_id and leaves pose7 / outlier / n_inliers alone: the caller words the error.
+int frame_pose_run(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp_xyz, const float* pos, const uint8_t* flags,
+                   const float* inv_level_sigma2, int n_levels, const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers,
+                   bool* bad_id);

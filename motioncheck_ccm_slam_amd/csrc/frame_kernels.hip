@@ -3,22 +3,13 @@
 //                         (Frame::AssignFeaturesToGrid / PosInGrid, src/Frame.cpp:103-118, 255-266), one workgroup per frame
 //   k_frame_prep_last     query radius and level window of SearchByProjection(Current, Last) from the last frame's octaves
 //   k_frame_scatter_ids   mvpMapPoints of the newly matched features
-//   k_frame_pose_gather   the correspondences of PoseOptimizationClient in feature order (compaction, first[] on the device)
+//   k_frame_pose_gather   the correspondences of PoseOptimizationClient in feature order (compaction, first[] on the device), the
+//                         points from the caller's array or from a map-point table
 //   k_frame_pose_scatter  mvbOutlier per feature
 //   k_frame_kf_gather     the keyframe part: node-ordered copies of the descriptors and of what the pair tests read per feature
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "../../include/ccm_hot.h"
-#include "map_math.h"
-
-#define FB_TPB 1024
-
-struct FrameBuildArgs {                          // must match frame_host.cpp
-    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
-    const ccm_keypoint* kps; const uint8_t* src_desc;  // gather source (an extracted image) or nullptr: x..desc already written
-    int keep_xy;                                       // with kps: x / y were uploaded (undistorted), take only octave / angle / desc
-    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
-};
+#include "frame_types.h"
 
 // PosInGrid (src/Frame.cpp:255-266) exactly as grid_build() in match_host.cpp: round() in float, half away from zero; features
 // outside the grid get no cell.  A NaN coordinate gets none either (x86's conversion gives INT_MIN, the device's 0).
@@ -115,15 +106,11 @@ __global__ void k_frame_scatter_ids(int n, const int* match, const int* src, con
     if (q >= 0) mp_id[i] = src ? src[q] : q;
 }
 
-struct PoseGatherArgs {                          // must match frame_host.cpp
-    int n; const float* kx; const float* ky; const int* oct; const int* mp_id;
-    int n_mp; const double* xyz; const float* inv_sigma2; int n_levels;
-    int* first; double* pts; double* obs; double* info; int* kof; int* status;
-};
-
 // One workgroup: the features with mp_id >= 0, in feature order (the loop of Optimizer.cpp:244-281), compacted by a ballot scan.
 // kof[i] = the correspondence of feature i or -1.  A bad id or octave sets status[0] and leaves no correspondence (first[1] = 0),
-// so the pose kernel behind it leaves the pose alone and the host reports CCM_E_ARG.
+// so the pose kernel behind it leaves the pose alone and the host reports CCM_E_ARG.  With a table (TABLE: A.pos, A.flags) a slot that is
+// not LIVE is a bad id too; the flag of an id outside the table is read at slot 0 and not used.
+template <bool TABLE>
 __global__ __launch_bounds__(FB_TPB) void k_frame_pose_gather(PoseGatherArgs A)
 {
     __shared__ int s_wave[FB_TPB / 64];
@@ -136,7 +123,7 @@ __global__ __launch_bounds__(FB_TPB) void k_frame_pose_gather(PoseGatherArgs A)
         const int id = i < A.n ? A.mp_id[i] : -1;
         const bool has = id >= 0;
         const int o = has ? A.oct[i] : 0;
-        const bool bad = has && (id >= A.n_mp || o < 0 || o >= A.n_levels);
+        const bool bad = has && (id >= A.n_mp || (TABLE && !(A.flags[id < A.n_mp ? id : 0] & CCM_MP_LIVE)) || o < 0 || o >= A.n_levels);
         if (bad) s_bad = 1;
         const unsigned long long ball = __ballot(has);
         const int before = __popcll(ball & ((1ull << lane) - 1ull));
@@ -147,7 +134,7 @@ __global__ __launch_bounds__(FB_TPB) void k_frame_pose_gather(PoseGatherArgs A)
         const int k = off + before;
         if (i < A.n) A.kof[i] = has ? k : -1;
         if (has) {
-            for (int d = 0; d < 3; d++) A.pts[3 * (size_t)k + d] = bad ? 0.0 : A.xyz[3 * (size_t)id + d];
+            for (int d = 0; d < 3; d++) A.pts[3 * (size_t)k + d] = bad ? 0.0 : TABLE ? (double)A.pos[3 * (size_t)id + d] : A.xyz[3 * (size_t)id + d];
             A.obs[2 * (size_t)k] = (double)A.kx[i]; A.obs[2 * (size_t)k + 1] = (double)A.ky[i];
             A.info[k] = bad ? 0.0 : (double)A.inv_sigma2[o];
         }
@@ -165,11 +152,6 @@ __global__ void k_frame_pose_scatter(int n, const int* kof, const int* first, co
     const int k = kof[i];
     outlier[i] = (k >= 0 && k < first[1]) ? outl[k] : 0;
 }
-
-struct KfGatherArgs {                            // must match frame_internal.h
-    int m; const int* order; const float* kx; const float* ky; const int* oct; const uint8_t* desc; const float* sf; const float* sig2;
-    MapFeat* feat_o; uint8_t* desc_o;
-};
 
 // Position p of the node order (ccm_frame_set_bow) holds feature order[p]: its 32-byte descriptor and MapFeat {x, y,
 // mvLevelSigma2[octave], mvScaleFactors[octave]} are copied there, so that a wave of k_cnmp_match_frames scanning a node range reads
@@ -204,7 +186,7 @@ void frame_launch_scatter_ids(hipStream_t s, int n, const int* match, const int*
 }
 void frame_launch_pose_gather(hipStream_t s, const PoseGatherArgs& A)
 {
-    hipLaunchKernelGGL(k_frame_pose_gather, dim3(1), dim3(FB_TPB), 0, s, A);
+    hipLaunchKernelGGL(A.pos ? k_frame_pose_gather<true> : k_frame_pose_gather<false>, dim3(1), dim3(FB_TPB), 0, s, A);
 }
 void frame_launch_pose_scatter(hipStream_t s, int n, const int* kof, const int* first, const uint8_t* outl, uint8_t* outlier)
 {

@@ -7,9 +7,6 @@
 #include "init_math.h"
 #include <cmath>
 
-void init_hypotheses_launch(hipStream_t, const IniDev&);
-void init_check_rt_launch(hipStream_t, const IniRtDev&);
-
 // One page-locked staging area and its device twin, laid out [inputs | hypothesis outputs | CheckRT outputs].
 struct InitState { DevBuf io; uint8_t* host = nullptr; size_t host_cap = 0; };
 void init_state_free(InitState* s)

@@ -1,4 +1,4 @@
-// init_types.h -- launch arguments of k_init_hypotheses and k_init_check_rt, shared by init_host.cpp and init_kernels.hip.
+// init_types.h -- launch arguments and launchers of k_init_hypotheses and k_init_check_rt, shared by init_host.cpp and init_kernels.hip.
 #pragma once
 #include <cstdint>
 
@@ -34,3 +34,9 @@ struct IniRtDev {
     float* X;                     // [n_cand][n][3]
     IniCand cand[INI_MAX_CAND];
 };
+
+// The launchers (init_kernels.hip).  This header is also compiled without ROCm (tests/support/init_math_check.cpp), so it names the
+// stream type as <hip/hip_runtime.h> declares it and does not include it.
+typedef struct ihipStream_t* hipStream_t;
+void init_hypotheses_launch(hipStream_t, const IniDev&);
+void init_check_rt_launch(hipStream_t, const IniRtDev&);

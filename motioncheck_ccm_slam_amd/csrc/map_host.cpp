@@ -8,11 +8,6 @@
 #include "map_types.h"
 #include <cmath>
 
-void map_match_launch(hipStream_t, const MapDev&);
-void map_triangulate_launch(hipStream_t, const MapDev&);
-void map_resolve_launch(hipStream_t, const MapDev&);
-void map_frames_launch(hipStream_t, const MapFramesDev&);
-
 // One page-locked staging area and its device twin, laid out [inputs | per-pair work arrays | result list], and the node table of the
 // counting pass: cid[node] = 1 + compact id of a node of the current keyframe, all zero between calls.
 struct MapState { DevBuf io; uint8_t* host = nullptr; size_t host_cap = 0; std::vector<int32_t> cid; };

@@ -1,6 +1,7 @@
 // map_types.h -- what map_host.cpp hands to the launches of map_kernels.hip (ccm_create_new_map_points).
 #pragma once
 #include <cstdint>
+#include <hip/hip_runtime.h>
 #include "map_math.h"
 
 #define MAP_TPB 256              // threads per block of all three kernels
@@ -62,3 +63,8 @@ struct MapFramesDev {
     uint8_t* gate; uint8_t* status; float* X;
     int32_t* first; int32_t* out_kf; int32_t* out_idx1; int32_t* out_idx2; float* out_x3d;
 };
+
+void map_match_launch(hipStream_t, const MapDev&);
+void map_triangulate_launch(hipStream_t, const MapDev&);
+void map_resolve_launch(hipStream_t, const MapDev&);
+void map_frames_launch(hipStream_t, const MapFramesDev&);

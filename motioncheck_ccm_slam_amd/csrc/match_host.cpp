@@ -6,35 +6,6 @@
 #include <cmath>
 #include <numeric>
 
-void match_launch_bf(hipStream_t, const uint8_t* q, long long q_pair_bytes, const uint8_t* t, long long t_pair_bytes,
-                     int nq, int nt, int n_pairs, const int* nq_n, const int* nt_n, int n_split, int variant,
-                     unsigned* part_best, int* part_second, int* bi, int* bd, int* sd);
-void match_launch_ranges(hipStream_t, const uint8_t* d1, const uint8_t* d2, const int* order2, const int* start,
-                         const int* len, const long long* off, int n1, unsigned short* dist);
-void match_launch_fp4_tile(hipStream_t, const unsigned* a, const unsigned* b, const float* c, float* out);
-struct BowDev {                                  // must match match_kernels.hip
-    int n_groups, n1;
-    const int* ga; const int* gae; const int* gb; const int* gbe;
-    const int* ord1; const int* ord2;
-    const uint8_t* d1; const uint8_t* d2;
-    const uint8_t* valid1; const uint8_t* valid2;
-    const float* angle1; const float* angle2;
-    uint8_t* taken; int* match12; int* bin_of; int* hist;
-    float nnratio; int th, strict_th, check_ori;
-};
-void match_launch_bow(hipStream_t, const BowDev&);
-struct BowFrameRec {                             // must match match_kernels.hip
-    BowDev B;
-    const int* nodes1; const int* first1; const int* nodes2; const int* first2;
-    int n_nodes2, n2;
-    const int* mp1; const int* mp2;
-    uint8_t* v1; uint8_t* v2;
-    int* match21;
-};
-void match_launch_bow_groups(hipStream_t, const BowFrameRec& one, const BowFrameRec* recs, int n_recs, int max_threads);
-void match_launch_bow_batch(hipStream_t, const BowFrameRec* recs, int n_recs, int n_groups);
-void match_launch_bow_invert(hipStream_t, const BowFrameRec&, int min_matches, int* mp_id2);
-
 struct WindowBufs { DevBuf kx, ky, oct, desc, cfirst, citems, qx, qy, qr, minl, maxl, qdesc, ci, cd, cn, sel_i, sel_d, is2, act, qlvl, qflag, flag, out, status, qang, fang, ev,
                            grids, qkf, gkf; };
 struct MatchState {
@@ -197,6 +168,15 @@ struct RotHisto {
     }
 };
 
+// The feature indices 0 .. n-1 by (node, index): the order of a DBoW2::FeatureVector walk
+static std::vector<int> node_order(const int32_t* node, int n)
+{
+    std::vector<int> ord(n);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [node](int a, int b) { return node[a] != node[b] ? node[a] < node[b] : a < b; });
+    return ord;
+}
+
 // Side-2 candidates of every side-1 feature = the features of the same vocabulary node (DBoW2::FeatureVector walk of
 // SearchByBoW / SearchForTriangulation), with their Hamming distances from k_hamming_ranges.
 struct BowRanges {
@@ -212,11 +192,7 @@ static int bow_ranges(ccm_ctx* c, const uint8_t* desc1, const int32_t* node1, co
     std::vector<long long>& off = R.off;
     std::vector<unsigned short>& dist = R.dist;
     // FeatureVector order: node ascending, feature index ascending inside a node (DBoW2 fills it so)
-    ord1.assign(n1, 0); ord2.assign(n2, 0);
-    std::iota(ord1.begin(), ord1.end(), 0); std::iota(ord2.begin(), ord2.end(), 0);
-    auto by_node = [](const int32_t* node) { return [node](int a, int b) { return node[a] != node[b] ? node[a] < node[b] : a < b; }; };
-    std::stable_sort(ord1.begin(), ord1.end(), by_node(node1));
-    std::stable_sort(ord2.begin(), ord2.end(), by_node(node2));
+    ord1 = node_order(node1, n1); ord2 = node_order(node2, n2);
     // per side-1 feature: the slice of ord2 holding its node (features without a node have id < 0)
     start.assign(n1, 0); len.assign(n1, 0); off.assign(n1 + 1, 0);
     {
@@ -268,11 +244,7 @@ int ccm_match_bow(ccm_ctx* c, const ccm_bow_options* o, const uint8_t* desc1, co
         MatchState& M = *match_state(c);
         // FeatureVector order: node ascending, feature index ascending inside a node (DBoW2 fills it so); the merge walk of
         // :201-298 pairs the runs of equal node ids -- one group per common node
-        std::vector<int> ord1(n1), ord2(n2);
-        std::iota(ord1.begin(), ord1.end(), 0); std::iota(ord2.begin(), ord2.end(), 0);
-        auto by_node = [](const int32_t* node) { return [node](int a, int b) { return node[a] != node[b] ? node[a] < node[b] : a < b; }; };
-        std::stable_sort(ord1.begin(), ord1.end(), by_node(node1));
-        std::stable_sort(ord2.begin(), ord2.end(), by_node(node2));
+        const std::vector<int> ord1 = node_order(node1, n1), ord2 = node_order(node2, n2);
         std::vector<int> grp[4];
         {
             size_t pa = 0, pb = 0;
@@ -323,9 +295,8 @@ static int bow_handle_check(ccm_ctx* c, const ccm_frame* f, const char* fn, cons
 {
     char name[48];
     if (k >= 0) snprintf(name, sizeof name, "%s[%d]", who, k); else snprintf(name, sizeof name, "%s", who);
-    if (!f) return ccm_fail(c, CCM_E_ARG, "%s: %s is null", fn, name);
-    if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: %s outlived its context", fn, name);
-    if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: %s belongs to another context", fn, name);
+    const int rc = frame_named_check(c, f, fn, "%s", name);
+    if (rc) return rc;
     if (!f->has_bow) return ccm_fail(c, CCM_E_STATE, "%s: %s has no bow", fn, name);
     if (check_ori && !f->has_angle) return ccm_fail(c, CCM_E_ARG, "%s: orientation check against %s, created without angles", fn, name);
     return CCM_OK;
@@ -461,13 +432,6 @@ int ccm_search_by_bow_frames(ccm_ctx* c, const ccm_frame* kf1, int n_kf2, ccm_fr
 // (k_window_greedy: the reference's order-dependent occupancy bookkeeping resolved by claim rounds, bit-identical to the
 // sequential loop; the frame matcher's rotation histogram and its three maxima in the same kernel).  Only the
 // initialisation matcher (called once per map) keeps its acceptance loop on the host.
-void match_launch_window_select_batch(hipStream_t, const WinGrid* grids, const int* q_kf, int nq, const float* qx, const float* qy, const float* qr,
-                                      const int* minl, const int* maxl, const uint8_t* qdesc, const float* inv_sigma2, int accept_th, int* best_idx, int* best_dist);
-void match_launch_window_select(hipStream_t, const WinGrid&, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
-                                const int* maxl, const uint8_t* qdesc, const float* inv_sigma2, int accept_th, int* best_idx, int* best_dist);
-int match_launch_window_greedy_batch(hipStream_t, const GreedyArgs&, int n_kf, int max_n);
-void match_launch_window_batch(hipStream_t, const WinGrid* grids, const int* q_kf, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
-                               const int* maxl, const uint8_t* qdesc, int cap, int* ci, int* cd, int* cn);
 
 // Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cpp:103-118, 255-266) for one grid: mGrid[x][y] is cell x * rows + y, its
 // features cell_items[cell_first[cell] .. cell_first[cell + 1]) in index order.  cell_first has cols * rows + 1 entries, cell_items f.n.
@@ -971,7 +935,7 @@ int ccm_fuse_select_batch_frames(ccm_ctx* c, int n_kf, ccm_frame* const* kfs, co
         std::vector<int> kf_n(n_kf);
         for (int k = 0; k < n_kf; k++) {
             const ccm_frame* f = kfs[k];
-            grids[k] = WinGrid{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+            grids[k] = frame_win_grid(f);
             kf_n[k] = f->n;
         }
         if ((rc = ccm_upload(c, window_bufs(c).grids, grids.data(), grids.size() * sizeof(WinGrid), c->stream))) return rc;

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include "match_types.h"
 
 #define BF_TILE 1024          // train descriptors staged per pass: 32 KiB of LDS
 
@@ -452,16 +453,6 @@ __global__ __launch_bounds__(256) void k_hamming_ranges(
 // minimal distance in scan order, second = second smallest including duplicates.  Accepted matches mark their side-2
 // feature taken, vote in the rotation histogram (integer counts), and k_bow_filter applies ComputeThreeMaxima
 // (:1607-1648) and drops the matches of the other bins (:271-289).
-struct BowDev {
-    int n_groups, n1;
-    const int* ga; const int* gae; const int* gb; const int* gbe;     // per group: ranges in ord1 / ord2
-    const int* ord1; const int* ord2;
-    const uint8_t* d1b; const uint8_t* d2b;                           // descriptors, 16-byte aligned
-    const uint8_t* valid1; const uint8_t* valid2;                     // valid2 may be null
-    const float* angle1; const float* angle2;
-    uint8_t* taken; int* match12; int* bin_of; int* hist;             // hist[30] + [30] = kept count
-    float nnratio; int th, strict_th, check_ori;
-};
 // one wave, one node group: shared by k_bow_greedy and its batched form
 __device__ __forceinline__ void bow_greedy_group(const BowDev& B, int grp, int lane)
 {
@@ -470,7 +461,7 @@ __device__ __forceinline__ void bow_greedy_group(const BowDev& B, int grp, int l
     for (int a = a0; a < a1; a++) {
         const int i1 = B.ord1[a];
         if (!B.valid1[i1]) continue;                                 // wave-uniform
-        const uint4* D1 = reinterpret_cast<const uint4*>(B.d1b); const uint4* D2 = reinterpret_cast<const uint4*>(B.d2b);
+        const uint4* D1 = reinterpret_cast<const uint4*>(B.d1); const uint4* D2 = reinterpret_cast<const uint4*>(B.d2);
         const uint4 q0 = D1[2 * (long long)i1], q1 = D1[2 * (long long)i1 + 1];
         int bd1 = 256, bd2 = 256, bi = -1;
         for (int base = b0; base < b1; base += 64) {
@@ -559,15 +550,6 @@ void match_launch_bow(hipStream_t s, const BowDev& B)
 // SearchByBoW on frame handles (ccm_frame_search_by_bow, ccm_search_by_bow_frames): both sides carry their node directory (order |
 // nodes | first, ccm_frame_set_bow / ccm_frame_compute_bow) in device memory, so the group list ccm_match_bow merges on the host
 // is made here.  One record per pair; the batched forms take the pair from blockIdx.y.
-struct BowFrameRec {
-    BowDev B;                                        // n_groups = side 1's distinct nodes; ga .. gbe, taken, match12, hist are filled by k_bow_groups
-    const int* nodes1; const int* first1;            // side 1's directory
-    const int* nodes2; const int* first2;            // side 2's
-    int n_nodes2, n2;
-    const int* mp1; const int* mp2;                  // the handles' mp_id
-    uint8_t* v1; uint8_t* v2;                        // non-null: B.valid1 / B.valid2 are these, derived here as mp_id >= 0
-    int* match21;                                    // Frame overload: [n2], cleared here and filled by k_bow_invert; else null
-};
 // One thread per distinct node of side 1 looks its node up in side 2's ascending `nodes` and writes the two position ranges
 // (both empty when side 2 lacks the node); the same launch clears taken, match12, match21 and the histogram and derives the masks.
 template <bool BATCH>
@@ -645,12 +627,6 @@ void match_launch_bow_invert(hipStream_t s, const BowFrameRec& R, int min_matche
 // query walks the grid cells of its window in the reference's order (ix outer, iy inner, cell content in
 // feature-index order), applies the level and |dx|,|dy| < r tests in float exactly as written there, and emits
 // (feature index, Hamming distance) in that order through ballot compaction.
-struct WinGrid {
-    int n, cols, rows;
-    float min_x, min_y, inv_w, inv_h;
-    const float* kx; const float* ky; const int* oct; const uint8_t* desc;
-    const int* cell_first; const int* cell_items;
-};
 // BATCH: the queries of many keyframes in one launch, query q against grids[q_kf[q]]; the candidate indices are the keyframe's own.
 template <bool BATCH>
 __global__ __launch_bounds__(256) void k_window_candidates(WinGrid G1, const WinGrid* __restrict__ grids, const int* __restrict__ q_kf,
@@ -800,23 +776,6 @@ void match_launch_window_select_batch(hipStream_t s, const WinGrid* grids, const
 // (LDS atomicMin), decide where the claim on the wanted feature(s) is one's own, reset the claims.  With many points per feature
 // (20,000 points on a 1,000-feature keyframe) round 2's first version -- claims on ALL free candidates over the whole list, 48 rounds,
 // then one wave visiting the rest in order with two global round trips per point -- took 9.1 ms; this takes the same decisions.
-struct GreedyArgs {
-    int nq, n, cap;
-    const int* ci; const int* cd; const int* cn;      // candidate lists [nq][cap], counts
-    const uint8_t* active;                            // mbTrackInView && !isBad  /  passed the projection tests
-    const int* qlevel; const int* oct;                // predicted level per point, octave per feature
-    const uint8_t* qflag;                             // Observations() > 0  /  already observed in the keyframe
-    uint8_t* flag;                                    // in/out per feature: occupied / matched
-    float nnratio;
-    int* out;                                         // MODE 0 / 2: match[feature] = point; MODE 1: best_idx[point] = feature
-    int* status;                                      // [0] matches (or -1: a list overflowed), [1] longest list, [2] most rounds a wave needed
-    // MODE 2: acceptance threshold, rotation check and its inputs; ev[point] = accepted feature << 8 | rotation bin (or -1)
-    int orb_dist, check_ori; const float* q_angle; const float* f_angle; int* ev;
-    // batch (MODE 1, ccm_search_by_projection_sim3_batch): workgroup k works on keyframe k -- queries kfs[k].q0 .. +nq of the per-query
-    // arrays, features kfs[k].f0 .. +n of the per-feature arrays, status words 3k .. 3k+2; nullptr = one problem, as described above
-    const struct GreedyKf* kfs;
-};
-struct GreedyKf { int q0, nq, f0, n; };
 #define WG_REG_CAND 16
 #define WG_BATCH_ROUNDS 3
 template <int MODE>

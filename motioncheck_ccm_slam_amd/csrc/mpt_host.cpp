@@ -24,10 +24,6 @@ struct ccm_map_table {
     DevBuf where; unsigned fuse_stamp = 0;       // ccm_fuse_select_table_frames: per slot, stamp << 32 | position in that call's slot list
 };
 
-// match_kernels.hip: k_window_select<true>, query q against grids[q_kf[q]]
-void match_launch_window_select_batch(hipStream_t, const WinGrid* grids, const int* q_kf, int nq, const float* qx, const float* qy, const float* qr,
-                                      const int* minl, const int* maxl, const uint8_t* qdesc, const float* inv_sigma2, int accept_th, int* best_idx, int* best_dist);
-
 void mpt_tables_orphan(FrameState* S)            // ccm_destroy: the memory goes, the handles stay for ccm_map_table_destroy
 {
     for (ccm_map_table* t : S->tables) {
@@ -234,8 +230,7 @@ int ccm_map_table_refresh(ccm_ctx* c, ccm_map_table* t, const ccm_map_refresh* u
         for (int k = 0; k < n_kf; k++) {
             const ccm_frame* f = u->kfs[k];
             if (!f) return ccm_fail(c, CCM_E_ARG, "%s: null kfs[%d]", fn, k);
-            if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: kfs[%d] outlived its context", fn, k);
-            if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: kfs[%d] belongs to another context", fn, k);
+            if ((rc = frame_named_check(c, f, fn, "kfs[%d]", k))) return rc;
         }
         std::vector<uint8_t> used((size_t)n_kf, 0);              // 1: named by an observation, 2: named as a reference keyframe
         for (int p = 0; p < n; p++) {
@@ -342,8 +337,7 @@ int ccm_fuse_select_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_fuse_ta
         for (int k = 0; k < n_kf; k++) {
             const ccm_frame* f = p->views[k].kf;
             if (!f) return ccm_fail(c, CCM_E_ARG, "%s: null views[%d].kf", fn, k);
-            if (!f->ctx) return ccm_fail(c, CCM_E_STATE, "%s: views[%d].kf outlived its context", fn, k);
-            if (f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: views[%d].kf belongs to another context", fn, k);
+            if ((rc = frame_named_check(c, f, fn, "views[%d].kf", k))) return rc;
             max_n = std::max(max_n, f->n);
         }
         bool dup = false;
@@ -385,7 +379,7 @@ int ccm_fuse_select_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_fuse_ta
             std::memcpy(D.Tcw, V.Tcw, sizeof D.Tcw); std::memcpy(D.Ow, V.Ow, sizeof D.Ow);
             D.fx = V.fx; D.fy = V.fy; D.cx = V.cx; D.cy = V.cy; D.min_x = V.min_x; D.max_x = V.max_x; D.min_y = V.min_y; D.max_y = V.max_y;
             D.n = f->n; D.pad_ = 0; D.mp_id = f->mp_id;
-            hg[k] = WinGrid{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
+            hg[k] = frame_win_grid(f);
         }
         std::memcpy(h + o_slot, p->slot, (size_t)n_pt * 4);
         if (p->skip) std::memcpy(h + o_skip, p->skip, (size_t)n_pt);
@@ -561,41 +555,10 @@ int ccm_frame_pose_optimize_table(ccm_ctx* c, ccm_frame* f, ccm_map_table* t, co
         return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
     if (f->n == 0) { *n_inliers = 0; return CCM_OK; }
     return ccm_guard(c, "ccm_frame_pose_optimize_table", [&]() -> int {
-        CCM_HIP(c, hipSetDevice(c->device));
-        FrameState& S = *frame_state(c);
-        hipStream_t st = c->stream;
-        const int n = f->n;
-        size_t off = 0;
-        const size_t o_ninl = seg(off, 16), o_outl = seg(off, (size_t)n), o_pose = seg(off, 56);
-        const size_t res_end = o_pose + 56;
-        const size_t o_intr = seg(off, 32), o_is2 = seg(off, (size_t)n_levels * 4);
-        const size_t end = off;
-        uint8_t* h = nullptr;
-        if ((rc = frame_staging(c, end, &h))) return rc;
-        std::memcpy(h + o_pose, pose7, 56); std::memcpy(h + o_intr, intr, 32);
-        std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4);
-        if ((rc = frame_upload(c, o_pose, end))) return rc;
-        CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
-        CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
-        uint8_t* io = S.io.as<uint8_t>();
-        int* d_ninl = (int*)(io + o_ninl); int* d_status = d_ninl + 1;
-        MptPoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, (const float*)(io + o_is2), n_levels, S.first.as<int>(), S.pts.as<double>(),
-                             S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
-        mpt_launch_pose_gather(st, G, t->T);
-        CCM_HIP(c, hipGetLastError());
-        PoseDev D{ 1, (double*)(io + o_pose), (const double*)(io + o_intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
-                   S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
-        pose_launch(st, D);
-        CCM_HIP(c, hipGetLastError());
-        frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
-        CCM_HIP(c, hipGetLastError());
-        if ((rc = frame_download(c, res_end))) return rc;
-        int head[2];
-        std::memcpy(head, S.host + o_ninl, 8);
-        if (head[1]) return ccm_fail(c, CCM_E_ARG, "a map-point id outside the table or of a slot that is not LIVE, or an octave outside [0, %d)", n_levels);
-        std::memcpy(pose7, S.host + o_pose, 56);
-        std::memcpy(outlier, S.host + o_outl, n);
-        *n_inliers = head[0];
+        bool bad_id = false;
+        if ((rc = frame_pose_run(c, f, t->T.capacity, nullptr, t->T.pos, t->T.flags, inv_level_sigma2, n_levels, intr, pose7, outlier, n_inliers, &bad_id)))
+            return rc;
+        if (bad_id) return ccm_fail(c, CCM_E_ARG, "a map-point id outside the table or of a slot that is not LIVE, or an octave outside [0, %d)", n_levels);
         return CCM_OK;
     });
 }

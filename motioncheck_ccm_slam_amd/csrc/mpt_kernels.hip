@@ -6,7 +6,6 @@
 //                      (src/MapPoint.cpp:854-869), thread per entry of the order list; per-wave ballots, per-workgroup counts
 //   k_slp_scan         exclusive scan of the workgroup counts, one workgroup; the in-view count
 //   k_slp_compact      the entries in view, in list order, into the query arrays of the windowed matcher
-//   k_mpt_pose_gather  k_frame_pose_gather (frame_kernels.hip) with the points read from the table as float
 //   k_mpt_refresh      MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cpp:929-994) and MapPoint::UpdateNormalAndDepth (:779-823)
 //                      for a list of points whose observations name keyframe handles; one wave per point
 //   k_fuse_where / k_fuse_held / k_fuse_project / k_fuse_scatter
@@ -188,43 +187,6 @@ __global__ __launch_bounds__(SLP_TPB) void k_slp_compact(SlpArgs A, MptTable T)
     const uint4* a = reinterpret_cast<const uint4*>(T.desc + (size_t)s * 32);
     uint4* b = reinterpret_cast<uint4*>(A.qdesc + (size_t)k * 32);
     b[0] = a[0]; b[1] = a[1];
-}
-
-// ---------------------------------------------------------------------------------------------------------------- pose
-// k_frame_pose_gather with pos read as float and widened (Converter::toVector3d of a float cv::Mat is exact); a slot outside the
-// table or not LIVE is a bad id.  One workgroup; the features with mp_id >= 0 in feature order.
-__global__ __launch_bounds__(MPG_TPB) void k_mpt_pose_gather(MptPoseGatherArgs A, MptTable T)
-{
-    __shared__ int s_wave[MPG_TPB / 64];
-    __shared__ int s_base, s_bad;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) { s_base = 0; s_bad = 0; }
-    __syncthreads();
-    for (int base = 0; base < A.n; base += MPG_TPB) {
-        const int i = base + tid;
-        const int id = i < A.n ? A.mp_id[i] : -1;
-        const bool has = id >= 0;
-        const int o = has ? A.oct[i] : 0;
-        const bool bad = has && (id >= T.capacity || !(T.flags[id < T.capacity ? id : 0] & CCM_MP_LIVE) || o < 0 || o >= A.n_levels);
-        if (bad) s_bad = 1;
-        const unsigned long long ball = __ballot(has);
-        const int before = __popcll(ball & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wv] = __popcll(ball);
-        __syncthreads();
-        int off = s_base;
-        for (int w = 0; w < wv; w++) off += s_wave[w];
-        const int k = off + before;
-        if (i < A.n) A.kof[i] = has ? k : -1;
-        if (has) {
-            for (int d = 0; d < 3; d++) A.pts[3 * (size_t)k + d] = bad ? 0.0 : (double)T.pos[3 * (size_t)id + d];
-            A.obs[2 * (size_t)k] = (double)A.kx[i]; A.obs[2 * (size_t)k + 1] = (double)A.ky[i];
-            A.info[k] = bad ? 0.0 : (double)A.inv_sigma2[o];
-        }
-        __syncthreads();
-        if (tid == 0) { int t = 0; for (int w = 0; w < MPG_TPB / 64; w++) t += s_wave[w]; s_base += t; }
-        __syncthreads();
-    }
-    if (tid == 0) { A.first[0] = 0; A.first[1] = s_bad ? 0 : s_base; A.status[0] = s_bad; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- refresh
@@ -493,10 +455,6 @@ void slp_launch_frustum(hipStream_t s, const SlpArgs& A, const MptTable& T, int*
     if (n_wg > 0) hipLaunchKernelGGL(k_slp_frustum, dim3(n_wg), dim3(SLP_TPB), 0, s, A, T);
     hipLaunchKernelGGL(k_slp_scan, dim3(1), dim3(SCAN_TPB), 0, s, n_wg, A.wg_cnt, A.wg_off, cnt);
     if (n_wg > 0) hipLaunchKernelGGL(k_slp_compact, dim3(n_wg), dim3(SLP_TPB), 0, s, A, T);
-}
-void mpt_launch_pose_gather(hipStream_t s, const MptPoseGatherArgs& A, const MptTable& T)
-{
-    hipLaunchKernelGGL(k_mpt_pose_gather, dim3(1), dim3(MPG_TPB), 0, s, A, T);
 }
 void mpt_launch_refresh(hipStream_t s, const MptRefreshArgs& A, const MptTable& T)
 {

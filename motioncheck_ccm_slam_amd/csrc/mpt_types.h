@@ -6,7 +6,6 @@
 
 #define SLP_TPB 256        // k_slp_frustum / k_slp_compact: 4 waves per workgroup
 #define SCAN_TPB 1024
-#define MPG_TPB 1024
 #define MPR_TPB 256        // k_mpt_refresh: one wave per map point, 4 points per workgroup
 #define FUSE_TPB 256       // k_fuse_project: one thread per (keyframe, point) pair, the keyframe uniform per workgroup
 #define MPR_LDS_ROWS 256   // descriptors a wave keeps in LDS: 8 KB per wave, 32 KB per workgroup; further rows are read from global memory
@@ -26,11 +25,6 @@ struct SlpArgs {
     // per entry in view, in list order: the matcher's queries (qx / qy are also the taps mTrackProjX / Y) and the taps
     float* qx; float* qy; float* qr; int* minl; int* maxl; uint8_t* qdesc; uint8_t* qact; uint8_t* qflag; int* slots;
     int* tap_level; float* tap_vc;
-};
-
-struct MptPoseGatherArgs {
-    int n; const float* kx; const float* ky; const int* oct; const int* mp_id; const float* inv_sigma2; int n_levels;
-    int* first; double* pts; double* obs; double* info; int* kof; int* status;
 };
 
 // What k_mpt_refresh reads of a keyframe handle: device pointers the handle owns (Ow: d_cam->Ow; sf: kMaxLevels floats, zero-padded).
@@ -67,7 +61,6 @@ void slp_launch_mark(hipStream_t, const MptTable&, int n, const int* mp_id, int 
 int  slp_workgroups(int n_order);
 // k_slp_frustum, k_slp_scan (cnt[0] = entries in view) and k_slp_compact
 void slp_launch_frustum(hipStream_t, const SlpArgs&, const MptTable&, int* cnt);
-void mpt_launch_pose_gather(hipStream_t, const MptPoseGatherArgs&, const MptTable&);
 void mpt_launch_refresh(hipStream_t, const MptRefreshArgs&, const MptTable&);
 // k_fuse_where and k_fuse_held (max_n: the largest feature count among the keyframes), then k_fuse_project: gates, taps, cnt[0] queries
 void fuse_launch_project(hipStream_t, const FuseArgs&, const MptTable&, int max_n);

@@ -7,21 +7,6 @@
 #include <cfloat>
 #include <algorithm>
 
-extern "C" hipError_t orb_upload_pattern();
-size_t orb_octree_lds_bytes(int list_cap);
-void orb_launch_resize(hipStream_t, const OrbGeom&, int level, int dw, int dh, int nframes, int* clear_status);
-void orb_launch_score(hipStream_t, const OrbGeom&, int ntiles, int nframes);
-void orb_launch_nms(hipStream_t, const OrbGeom&, const OrbCell*, int ncells, int nframes, unsigned* slots, int* cell_count);
-void orb_launch_fast_cells(hipStream_t, const OrbGeom&, const OrbCell*, const OrbBand*, int nbands, int nframes, size_t lds_bytes,
-                           int surv_cap, unsigned* slots, int* cell_count, int* clear_status);
-size_t orb_fast_cells_lds(int pitch, int bh, int surv_cap);
-void orb_launch_octree(hipStream_t, const OrbGeom&, const OrbCell*, int nlevels, int nframes, int list_cap,
-                       const unsigned* slots, const int* cell_count, unsigned* keysA, unsigned* keysB,
-                       unsigned* out, int* out_count, int* status);
-void orb_launch_orient_desc(hipStream_t, const OrbGeom&, int out_per_frame, int nframes, const unsigned* sel,
-                            const int* sel_count, ccm_keypoint* kps, uint8_t* desc, int* counts, int max_per_image,
-                            int* status);
-
 namespace {
 
 inline int cv_round(float v) { return (int)lrintf(v); }       // cvRound: ties to even (default FP mode)

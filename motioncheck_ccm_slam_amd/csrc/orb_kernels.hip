@@ -12,7 +12,6 @@
 #include "orb_types.h"
 #include "../../include/ccm_orb_pattern.h"
 #include "../../include/ccm_sincos.h"
-#include "../../include/ccm_hot.h"
 
 #define WAVE 64
 

@@ -1,13 +1,8 @@
 // pose_host.cpp -- C ABI of the batched pose-only optimisation (Optimizer::PoseOptimizationClient,
 // src/Optimizer.cpp:215-347); the whole schedule runs in one kernel launch (pose_kernels.hip).
 #include "ccm_internal.h"
+#include "pose_types.h"
 #include <algorithm>
-
-struct PoseDev {
-    int n_frames; double* poses; const double* intr; const int* first; const double* pts; const double* obs;
-    const double* info; double* err; uint8_t* outlier; int* n_inliers;
-};
-void pose_launch(hipStream_t, const PoseDev&);
 
 struct PoseState { DevBuf poses, intr, first, pts, obs, info, err, outlier, ninl; };
 static PoseState* pose_state(ccm_ctx* c)

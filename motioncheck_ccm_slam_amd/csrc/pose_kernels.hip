@@ -9,22 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cfloat>
+#include "pose_types.h"
 #include "ba_math.h"
-
-#define PO_TPB 256
-
-struct PoseDev {
-    int n_frames;
-    double* poses;            // [n_frames][7] in/out
-    const double* intr;       // [n_frames][4]
-    const int* first;         // [n_frames+1]
-    const double* pts;        // [total][3]
-    const double* obs;        // [total][2]
-    const double* info;       // [total]
-    double* err;              // [total][2] scratch: last computed error per edge
-    uint8_t* outlier;         // [total] out
-    int* n_inliers;           // [n_frames] out
-};
 
 // fixed-order block sum of NV doubles per thread -> result broadcast to all threads via LDS
 template <int NV>

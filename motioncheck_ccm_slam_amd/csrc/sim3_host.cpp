@@ -1,14 +1,8 @@
 // sim3_host.cpp -- C ABI of the batched Optimizer::OptimizeSim3 (cslam/src/Optimizer.cpp:867-1062); the whole
 // schedule of every problem runs in one kernel launch (sim3_kernels.hip).
 #include "ccm_internal.h"
+#include "sim3_types.h"
 #include <algorithm>
-
-struct Sim3Dev {
-    int n_problems; double* sim3; const int* fix_scale; const double* K1; const double* K2; const int* first;
-    const double* P1; const double* P2; const double* obs1; const double* obs2; const double* info1; const double* info2;
-    const float* th2; double* err; uint8_t* inlier; int* n_in;
-};
-void sim3_launch(hipStream_t, const Sim3Dev&);
 
 struct Sim3State { DevBuf sim3, fix, K1, K2, first, P1, P2, o1, o2, i1, i2, th2, err, inl, nin; };
 void sim3_state_free(Sim3State* s) { delete s; }

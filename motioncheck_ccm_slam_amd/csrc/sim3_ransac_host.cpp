@@ -6,8 +6,6 @@
 #include <cmath>
 #include <memory>
 
-void sim3_ransac_launch(hipStream_t, const S3rDev&, int n_blocks);
-
 // One page-locked staging area and its device twin, laid out [inputs | outputs]: one upload, one launch, one download per batch.
 struct Sim3RansacState { DevBuf io; uint8_t* host = nullptr; size_t host_cap = 0; };
 void sim3_ransac_state_free(Sim3RansacState* s)

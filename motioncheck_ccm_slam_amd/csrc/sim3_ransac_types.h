@@ -1,6 +1,7 @@
-// sim3_ransac_types.h -- launch arguments of k_sim3_ransac, shared by sim3_ransac_host.cpp and sim3_ransac_kernels.hip.
+// sim3_ransac_types.h -- launch arguments and launcher of k_sim3_ransac, shared by sim3_ransac_host.cpp and sim3_ransac_kernels.hip.
 #pragma once
 #include <cstdint>
+#include <hip/hip_runtime.h>
 
 #define S3R_TPB  256      // threads per workgroup (4 waves)
 #define S3R_HPB  64       // hypotheses per workgroup: one lane of wave 0 each for the closed form
@@ -25,3 +26,5 @@ struct S3rDev {
     float* rts;                                       // [hypothesis][13]: R (9), t (3), s
     unsigned long long* mask;                         // inlier bits, correspondence i of a solver = bit i % 64 of word i / 64
 };
+
+void sim3_ransac_launch(hipStream_t, const S3rDev&, int n_blocks);

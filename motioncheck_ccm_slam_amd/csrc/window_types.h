@@ -1,32 +1,8 @@
-// window_types.h -- the windowed matchers' device structures and launchers (match_kernels.hip), shared by the host translation
-// units that drive them: match_host.cpp (host arrays per call) and frame_host.cpp (frame handles).  The structures must match
-// match_kernels.hip.
+// window_types.h -- the host side of the windowed matchers, shared by the host translation units that drive them: match_host.cpp
+// (host arrays per call) and frame_host.cpp / mpt_host.cpp (frame handles).  The device structures and launchers are match_types.h.
 #pragma once
-#include <cstddef>
-#include <cstdint>
 #include <vector>
-#include <hip/hip_runtime.h>
-
-struct WinGrid {
-    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
-    const float* kx; const float* ky; const int* oct; const uint8_t* desc; const int* cell_first; const int* cell_items;
-};
-void match_launch_window(hipStream_t, const WinGrid&, int nq, const float* qx, const float* qy, const float* qr, const int* minl,
-                         const int* maxl, const uint8_t* qdesc, int cap, int* ci, int* cd, int* cn);
-
-struct GreedyArgs {
-    int nq, n, cap; const int* ci; const int* cd; const int* cn; const uint8_t* active; const int* qlevel; const int* oct; const uint8_t* qflag;
-    uint8_t* flag; float nnratio; int* out; int* status;
-    int orb_dist, check_ori; const float* q_angle; const float* f_angle; int* ev;
-    const struct GreedyKf* kfs;
-};
-struct GreedyKf { int q0, nq, f0, n; };
-size_t match_window_greedy_lds(int n, int nq);
-int match_launch_window_greedy(hipStream_t, int mode, const GreedyArgs&);
-
-// LDS the single-workgroup acceptance kernel may ask for (claim + flag per feature, one byte per query); larger problems take the
-// host loops below
-static const size_t kGreedyLdsMax = 150 * 1024;
+#include "match_types.h"
 
 // The host acceptance loops (the round-1 path; CCM_WINDOW_HOST_ACCEPT=1 or problems above kGreedyLdsMax) on candidate lists
 // [nq][cap] with counts cn.  match[] must be pre-set to -1; occupied is updated; return nmatches.

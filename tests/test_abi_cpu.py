@@ -100,6 +100,21 @@ def test_product_never_imports_oracle():
                 assert "oracle_py" not in txt and "liboracle" not in txt and "orc_" not in txt, os.path.join(d, f)
 
 
+def test_every_struct_is_defined_once():
+    """A kernel argument structure is passed by value from a host translation unit to a kernel translation unit: both must see one
+    definition (the kernel file's types header), never a copy of their own.  No structure name under csrc/ is defined twice."""
+    csrc = os.path.join(ROOT, "motioncheck_ccm_slam_amd", "csrc")
+    where = {}
+    for d, _, files in os.walk(csrc):
+        for f in sorted(files):
+            if f.endswith((".h", ".hip", ".cpp")):
+                for name in re.findall(r"^struct (\w+)\s*\{", open(os.path.join(d, f)).read(), flags=re.M):
+                    where.setdefault(name, []).append(f)
+    assert where
+    twice = {name: files for name, files in where.items() if len(files) > 1}
+    assert not twice, twice
+
+
 def test_header_is_plain_c_and_links_from_c(tmp_path):
     """The boundary is a C ABI: the header must compile as C99 (and as C++11), and a C program must link against the
     library and call a host-only entry point without any C++ or HIP at the call site."""

@@ -329,7 +329,7 @@ def test_pose_from_table_and_track_local_map(ctx, matchable):
 
 
 def test_pose_from_table_at_the_compaction_edges(ctx):
-    """k_mpt_pose_gather across a 1024-block with every second 64-group empty (1025 features): the table form equals the array call
+    """k_frame_pose_gather on a table across a 1024-block with every second 64-group empty (1025 features): the table form equals the array call
     on the gathered problem bit for bit; the points are the table's float32 positions."""
     N = 1025
     fc = C_.frame_case(N, "alternate")
