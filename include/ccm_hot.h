@@ -680,6 +680,69 @@ int ccm_frame_search_local_points_timing(ccm_ctx*, double ms[3]);
 int ccm_frame_pose_optimize_table(ccm_ctx*, ccm_frame* f, ccm_map_table* table, const float* inv_level_sigma2, int n_levels,
                                   const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers);
 
+/* Tracking::TrackWithMotionModel (src/Tracking.cpp:569-621) behind UpdateLastFrame and the pose product, in one call on two frame
+ * handles and the table: ORBmatcher::SearchByProjection(Current, Last, th) (src/ORBmatcher.cpp:1350-1476, monocular), its repetition
+ * with a window twice as wide, PoseOptimizationClient and "discard outliers".  In the reference's order:
+ *   Clear (:579): cur's ids all become -1.
+ *   Project, once per call: last-frame feature i with id = last's mp_id[i] < 0, or with last_outlier[i] set, is no query.  isBad() is not
+ *     asked there, so a BAD slot is projected.  An id outside the table or naming a slot that is not LIVE returns CCM_E_ARG with cur's
+ *     ids as they were on entry.  Otherwise, with P the slot's pos, in the arithmetic of a float cv::Mat:
+ *       Pc[r] = (float)((double)R[r][0] P[0] + (double)R[r][1] P[1] + (double)R[r][2] P[2] + (double)t[r])
+ *       invz = 1.0f / Pc[2];  reject invz < 0
+ *       u = fx * PcX * invz + cx;  v = fy * PcY * invz + cy   (float, left to right, each operation rounded: the association of
+ *       ccm_frame_search_local_points, one device function for both)
+ *       reject u < min_x || u > max_x, then v < min_y || v > max_y   (both ends inside, unlike IsInImage)
+ *     One deviation: a u or v that is not finite (Pc[2] == 0 only) is rejected; the reference would pass it to GetFeaturesInArea, where
+ *     the cast is undefined.  A query takes the slot's descriptor, HAS_OBS of the slot, octave and angle from `last`; the current
+ *     feature it is matched to receives the slot as its id.
+ *   Search, per pass: radius = th * scale_factors[octave], levels octave-1 .. octave+1, window selection, the sequential acceptance of
+ *     :1411-1448 and the rotation histogram of :1453-1473 exactly as ccm_frame_search_by_projection_frame runs them for a `last` handle
+ *     (on the device, or on the host with CCM_WINDOW_HOST_ACCEPT=1 or a frame too large for the acceptance kernel's LDS).
+ *   Retry (:587-591): with n_matches < retry_below the ids are cleared again and ONE more pass runs with 2 * th; the projection is
+ *     kept, only radius and level window are made again.
+ *   No pose (:593-594): with n_matches < min_matches after the last pass, or inv_level_sigma2 == NULL, posed = 0; the handle keeps the
+ *     last pass's matches as ids (the reference does not clear them there), pose7 is untouched, outlier is 0 and n_inliers 0.
+ *   Pose: as ccm_frame_pose_optimize_table on cur from pose7, bit for bit.
+ *   Discard (:599-618): a feature with an id and outlier != 0 loses its id.  n_matches_map counts the features whose id names a slot
+ *     with HAS_OBS afterwards (without a pose: of the last pass's matches).  mp_id and the handle agree after the call.
+ * Traffic, as the code has it: one page-locked copy up of last_outlier (when given), 16 zero bytes, pose7, intr, inv_level_sigma2 and
+ * scale_factors -- 320 bytes (five 64-byte segments) without last_outlier, plus N_last rounded up to 64 with it; nothing per map point.  One read-back
+ * and stream synchronisation per search pass (status, match, occupancy flags, the bad-id word: 5 N_cur + 32 bytes and the padding),
+ * which the overflow retry of the candidate lists needs, and one more for the rest (counts, pose7, outlier, mp_id; the taps when asked
+ * for): 2 synchronisations for a call of one pass, 3 with the retry.  On the host acceptance route the candidate lists and what the
+ * loops read of both frames are fetched as well, each fetch synchronising.
+ * Errors, found before anything changes the handle.  CCM_E_ARG: a NULL ctx, cur, last, table, params, result, scale_factors, pose7 (with
+ * a pose stage), intr (with a pose stage), match or mp_id or outlier (N_cur > 0); only some of u / v / valid; n_levels outside
+ * 1..CCM_MAX_LEVELS; cur == last; a handle or table of another context; check_ori with a handle that has no angles; an octave of last
+ * that is >= n_levels, or, with a pose stage, an octave of cur that is.  CCM_E_STATE: a handle or table that outlived its context.
+ * N_last == 0 or N_cur == 0: CCM_OK with zero matches and posed = 0 (cur's ids cleared).  Returns CCM_OK or an error. */
+typedef struct {
+    float Tcw[12];                      /* CurrentFrame.mTcw = mVelocity * mLastFrame->mTcw, rows of [Rcw | tcw] */
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y;   /* mnMinX .. mnMaxY */
+    int32_t n_levels; const float* scale_factors;          /* mvScaleFactors [n_levels], 1..CCM_MAX_LEVELS */
+    float th;                           /* 7 */
+    int32_t retry_below;                /* 20: fewer matches -> ids cleared, searched again with 2 * th; 0 = never */
+    int32_t min_matches;                /* 20, miTrackWithMotionModelInlierThresSearch: fewer after the last pass -> no pose */
+    int32_t check_ori; int32_t orb_dist;/* 1, TH_HIGH = 100 */
+    const uint8_t* last_outlier;        /* [N_last] LastFrame.mvbOutlier or NULL = none */
+    /* pose stage; inv_level_sigma2 == NULL: search only */
+    const float* inv_level_sigma2; const double* intr; /* [n_levels], [4] */
+} ccm_tmm_params;
+typedef struct {
+    int32_t n_matches;     /* of the last pass, after the rotation filter: what SearchByProjection returned */
+    int32_t passes;        /* 1 or 2 */
+    int32_t posed;         /* 1 when the pose stage ran */
+    int32_t n_inliers;     /* PoseOptimizationClient's return value */
+    int32_t n_matches_map; /* :600-618: features that keep a point with HAS_OBS after the discard */
+    double  pose7[7];      /* in: Converter::toSE3Quat(mTcw) (ccm_pose_from_mat4f); out: optimised when posed */
+    int32_t* match;        /* [N_cur] last-frame feature assigned to current feature i by the last pass, or -1 */
+    int32_t* mp_id;        /* [N_cur] the handle's ids after the call */
+    uint8_t* outlier;      /* [N_cur] mvbOutlier as the pose left it, BEFORE the discard (the caller needs it for mbTrackInView / mLastFrameSeen); 0 when not posed */
+    float* u; float* v; uint8_t* valid;   /* optional taps [N_last] (all three or none): the projection; u = v = 0 where valid is 0 */
+} ccm_tmm_result;
+int ccm_frame_track_motion_model(ccm_ctx*, ccm_frame* cur, const ccm_frame* last, ccm_map_table*, const ccm_tmm_params*, ccm_tmm_result*);
+
 /* ORBmatcher::Fuse, both overloads (src/ORBmatcher.cpp:854-1000 and :1002-1122), up to and including the selection, on keyframe
  * handles and the table: ONE list of map points is projected into EVERY keyframe, as LoopFinder::SearchAndFuse (src/LoopFinder.cpp:
  * 806-831), MapMerger::SearchAndFuse (src/MapMerger.cpp:574-600) and the first loop of LocalMapping::SearchInNeighbors

@@ -40,7 +40,7 @@ SYMBOLS = [
     "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
     "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
-    "ccm_fuse_select_table_frames",
+    "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
@@ -176,6 +176,20 @@ class SlpResult(C.Structure):
     _fields_ = [("n_to_match", C.c_int32), ("in_view_cap", C.c_int32), ("in_view_slot", C.c_void_p), ("proj_x", C.c_void_p),
                 ("proj_y", C.c_void_p), ("level", C.c_void_p), ("view_cos", C.c_void_p), ("match", C.c_void_p), ("mp_id", C.c_void_p),
                 ("occupied", C.c_void_p)]
+
+
+class TmmParams(C.Structure):
+    _fields_ = [("Tcw", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factors", C.c_void_p), ("th", C.c_float), ("retry_below", C.c_int32), ("min_matches", C.c_int32),
+                ("check_ori", C.c_int32), ("orb_dist", C.c_int32), ("last_outlier", C.c_void_p), ("inv_level_sigma2", C.c_void_p),
+                ("intr", C.c_void_p)]
+
+
+class TmmResult(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("passes", C.c_int32), ("posed", C.c_int32), ("n_inliers", C.c_int32),
+                ("n_matches_map", C.c_int32), ("pose7", C.c_double * 7), ("match", C.c_void_p), ("mp_id", C.c_void_p),
+                ("outlier", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("valid", C.c_void_p)]
 
 
 FG_GATES = ("SEARCHED", "SKIPPED", "IN_KEYFRAME", "BEHIND", "OUTSIDE", "DISTANCE", "ANGLE", "EMPTY_KF")   # CCM_FG_* of include/ccm_hot.h
@@ -323,7 +337,8 @@ def load():
     lib.ccm_frame_search_local_points_timing.argtypes = [vp, vp]
     lib.ccm_frame_pose_optimize_table.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_fuse_select_table_frames.argtypes = [vp, vp, C.POINTER(FuseTableProblem), C.POINTER(FuseTableResult)]
-    lib.ccm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int]
+    lib.ccm_frame_track_motion_model.argtypes = [vp, vp, vp, vp, C.POINTER(TmmParams), C.POINTER(TmmResult)]
+    lib.ccm_sim3_ransac_iterations.argtypes =[C.c_int, C.c_double, C.c_int, C.c_int]
     lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]
     lib.ccm_sim3_solver_destroy.argtypes = [vp]; lib.ccm_sim3_solver_destroy.restype = None
     lib.ccm_sim3_solver_count.argtypes = [vp]

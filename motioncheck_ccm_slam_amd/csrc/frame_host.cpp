@@ -393,13 +393,34 @@ int frame_named_check(ccm_ctx* c, const ccm_frame* f, const char* fn, const char
     return CCM_OK;
 }
 
+int frame_pose_queue(ccm_ctx* c, ccm_frame* f, int n_mp, const float* pos, const uint8_t* flags, int n_levels, const PoseIo& o)
+{
+    FrameState& S = *frame_state(c);
+    hipStream_t st = c->stream;
+    const int n = f->n;
+    CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
+    CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
+    uint8_t* io = S.io.as<uint8_t>();
+    int* d_ninl = (int*)(io + o.ninl); int* d_status = d_ninl + 1;
+    PoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, n_mp, (const double*)(io + o.xyz), pos, flags, (const float*)(io + o.is2), n_levels,
+                      S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
+    frame_launch_pose_gather(st, G);
+    CCM_HIP(c, hipGetLastError());
+    PoseDev D{ 1, (double*)(io + o.pose), (const double*)(io + o.intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
+               S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
+    pose_launch(st, D);
+    CCM_HIP(c, hipGetLastError());
+    frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o.outl);
+    CCM_HIP(c, hipGetLastError());
+    return CCM_OK;
+}
+
 int frame_pose_run(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp_xyz, const float* pos, const uint8_t* flags,
                    const float* inv_level_sigma2, int n_levels, const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers,
                    bool* bad_id)
 {
     CCM_HIP(c, hipSetDevice(c->device));
     FrameState& S = *frame_state(c);
-    hipStream_t st = c->stream;
     const int n = f->n;
     const size_t xyz_bytes = mp_xyz ? (size_t)n_mp * 24 : 0;
     size_t off = 0;
@@ -414,20 +435,7 @@ int frame_pose_run(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp_xyz, con
     std::memcpy(h + o_is2, inv_level_sigma2, (size_t)n_levels * 4);
     if (xyz_bytes) std::memcpy(h + o_xyz, mp_xyz, xyz_bytes);
     if ((rc = frame_upload(c, o_pose, end))) return rc;
-    CCM_RESERVE(c, S.pts, (size_t)n * 24); CCM_RESERVE(c, S.obs, (size_t)n * 16); CCM_RESERVE(c, S.info, (size_t)n * 8);
-    CCM_RESERVE(c, S.err, (size_t)n * 16); CCM_RESERVE(c, S.outl, (size_t)n); CCM_RESERVE(c, S.kof, (size_t)n * 4); CCM_RESERVE(c, S.first, 16);
-    uint8_t* io = S.io.as<uint8_t>();
-    int* d_ninl = (int*)(io + o_ninl); int* d_status = d_ninl + 1;
-    PoseGatherArgs G{ n, f->kx, f->ky, f->oct, f->mp_id, n_mp, (const double*)(io + o_xyz), pos, flags, (const float*)(io + o_is2), n_levels,
-                      S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(), S.info.as<double>(), S.kof.as<int>(), d_status };
-    frame_launch_pose_gather(st, G);
-    CCM_HIP(c, hipGetLastError());
-    PoseDev D{ 1, (double*)(io + o_pose), (const double*)(io + o_intr), S.first.as<int>(), S.pts.as<double>(), S.obs.as<double>(),
-               S.info.as<double>(), S.err.as<double>(), S.outl.as<uint8_t>(), d_ninl };
-    pose_launch(st, D);
-    CCM_HIP(c, hipGetLastError());
-    frame_launch_pose_scatter(st, n, S.kof.as<int>(), S.first.as<int>(), S.outl.as<uint8_t>(), io + o_outl);
-    CCM_HIP(c, hipGetLastError());
+    if ((rc = frame_pose_queue(c, f, n_mp, pos, flags, n_levels, PoseIo{ o_ninl, o_outl, o_pose, o_intr, o_is2, o_xyz }))) return rc;
     if ((rc = frame_download(c, res_end))) return rc;
     int head[2];
     std::memcpy(head, S.host + o_ninl, 8);

@@ -54,7 +54,8 @@ struct FrameState {
     std::vector<struct ccm_map_table*> tables;   // map-point tables of this context (mpt_host.cpp)
     DevBuf slp;                                  // SearchLocalPoints: per-entry temporaries, workgroup counts and offsets
     DevBuf fuse;                                 // ccm_fuse_select_table_frames: membership flags, the compact query list, its selections
-    double slp_ms[3] = { -1, 0, 0 };             // host wall time of its last call (ccm_frame_search_local_points_timing)
+    DevBuf tmm;                                  // ccm_frame_track_motion_model: the queries made from the last frame (radius, levels, flags, descriptors)
+    double slp_ms[3] = { -1, 0, 0 };            // host wall time of its last call (ccm_frame_search_local_points_timing)
 };
 
 // The handle's features and grid as the windowed matchers read them
@@ -112,3 +113,8 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
 int frame_pose_run(ccm_ctx* c, ccm_frame* f, int n_mp, const double* mp_xyz, const float* pos, const uint8_t* flags,
                    const float* inv_level_sigma2, int n_levels, const double intr[4], double pose7[7], uint8_t* outlier, int32_t* n_inliers,
                    bool* bad_id);
+// Its device half, for a caller that keeps the pose in a staging layout of its own (ccm_frame_track_motion_model): gather -> pose_launch ->
+// scatter queued on blocks of io the caller has filled.  ninl: 16 bytes, [0] n_inliers, [1] the bad-id status; outl [n]; pose 56 bytes,
+// in/out; intr 32 bytes; is2 [n_levels] float; xyz [n_mp][3] double, read only when pos == nullptr.  Nothing is copied or awaited.
+struct PoseIo { size_t ninl, outl, pose, intr, is2, xyz; };
+int frame_pose_queue(ccm_ctx* c, ccm_frame* f, int n_mp, const float* pos, const uint8_t* flags, int n_levels, const PoseIo& o);

@@ -1,6 +1,7 @@
 // mpt_host.cpp -- C ABI of the map-point table (include/ccm_hot.h "map-point table"): the client's map points in device memory,
 // updated by rows at keyframe rate, and the two per-frame calls of Tracking::TrackLocalMap that work on a frame handle and the
-// table: SearchLocalPoints (src/Tracking.cpp:860-922) and PoseOptimizationClient (src/Optimizer.cpp:215-347).
+// table: SearchLocalPoints (src/Tracking.cpp:860-922) and PoseOptimizationClient (src/Optimizer.cpp:215-347); and
+// TrackWithMotionModel (src/Tracking.cpp:569-621) on two frame handles and the table, at the end of this file.
 //
 // The calls share the frame handles' page-locked staging area and its device twin `io` (frame_internal.h).  SearchLocalPoints
 // uploads nothing: its parameters travel as kernel arguments.  Its result block is
@@ -559,6 +560,120 @@ int ccm_frame_pose_optimize_table(ccm_ctx* c, ccm_frame* f, ccm_map_table* t, co
         if ((rc = frame_pose_run(c, f, t->T.capacity, nullptr, t->T.pos, t->T.flags, inv_level_sigma2, n_levels, intr, pose7, outlier, n_inliers, &bad_id)))
             return rc;
         if (bad_id) return ccm_fail(c, CCM_E_ARG, "a map-point id outside the table or of a slot that is not LIVE, or an octave outside [0, %d)", n_levels);
+        return CCM_OK;
+    });
+}
+
+// Tracking::TrackWithMotionModel behind the pose product, src/Tracking.cpp:579-621.  Staging, results first:
+//   [ status | match | occupied | last_outlier | head | pose7 | intr | inv_sigma2 | scale | n_inliers | outlier | mp_id | u | v | valid ]
+// One upload takes last_outlier .. scale (head as zeros); every pass downloads status .. head, the end of the call head .. mp_id, or
+// .. valid for the taps.  The queries' radius, level window, HAS_OBS flags and descriptors stay in device memory (FrameState::tmm);
+// the id a matched feature receives is read from last's own mp_id (a query's slot is its feature's id), so no id list is made.
+int ccm_frame_track_motion_model(ccm_ctx* c, ccm_frame* cur, const ccm_frame* last, ccm_map_table* t, const ccm_tmm_params* p, ccm_tmm_result* r)
+{
+    RoctxRange roctx_("ccm_frame_track_motion_model");
+    if (!c || !cur || !last || !t || !p || !r) return CCM_E_ARG;
+    const char* fn = "ccm_frame_track_motion_model";
+    int rc;
+    if ((rc = frame_named_check(c, cur, fn, "cur")) || (rc = frame_named_check(c, last, fn, "last")) || (rc = check_table(c, t))) return rc;
+    const bool pose = p->inv_level_sigma2 != nullptr, taps = r->u != nullptr;
+    if (cur == last) return ccm_fail(c, CCM_E_ARG, "%s: cur and last are the same handle", fn);
+    if (p->n_levels < 1 || p->n_levels > CCM_MAX_LEVELS) return ccm_fail(c, CCM_E_ARG, "%s: n_levels = %d outside 1..%d", fn, p->n_levels, CCM_MAX_LEVELS);
+    if (!p->scale_factors || (pose && !p->intr) || (cur->n > 0 && (!r->match || !r->mp_id || !r->outlier)))
+        return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !p->scale_factors ? "scale_factors" : pose && !p->intr ? "intr with inv_level_sigma2" :
+                        !r->match ? "match" : !r->mp_id ? "mp_id" : "outlier");
+    if ((r->u || r->v || r->valid) && !(r->u && r->v && r->valid)) return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and valid come together", fn);
+    if (p->check_ori && (!cur->has_angle || !last->has_angle)) return ccm_fail(c, CCM_E_ARG, "%s: orientation check against a frame created without angles", fn);
+    if (last->n_levels > p->n_levels || (pose && cur->n_levels > p->n_levels))
+        return ccm_fail(c, CCM_E_ARG, "%s: octaves up to %d in %s, n_levels = %d", fn, (last->n_levels > p->n_levels ? last : cur)->n_levels - 1,
+                        last->n_levels > p->n_levels ? "last" : "cur", p->n_levels);
+    return ccm_guard(c, fn, [&]() -> int {
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        hipStream_t st = c->stream;
+        const int n = cur->n, nl = last->n;
+        r->n_matches = 0; r->passes = 0; r->posed = 0; r->n_inliers = 0; r->n_matches_map = 0;
+        if (n == 0 || nl == 0) {                                               // :579 still happens; no matcher, no pose
+            if (n > 0) {
+                CCM_HIP(c, hipMemsetAsync(cur->mp_id, 0xFF, (size_t)n * 4, st));
+                for (int i = 0; i < n; i++) { r->match[i] = -1; r->mp_id[i] = -1; }
+                std::memset(r->outlier, 0, n);
+            }
+            return CCM_OK;
+        }
+        const size_t m = (size_t)nl;
+        size_t off = 0;
+        const size_t o_status = seg(off, 16), o_out = seg(off, (size_t)n * 4), o_flag = seg(off, (size_t)n);
+        const size_t o_lout = seg(off, p->last_outlier ? m : 0);
+        const size_t o_head = seg(off, 16), pass_end = o_head + 16;
+        const size_t o_pose = seg(off, 56), o_intr = seg(off, 32), o_is2 = seg(off, CCM_MAX_LEVELS * 4), o_scale = seg(off, CCM_MAX_LEVELS * 4);
+        const size_t up_end = off;
+        const size_t o_ninl = seg(off, 16), o_outl = seg(off, (size_t)n), o_ids = seg(off, (size_t)n * 4);
+        const size_t res_end = o_ids + (size_t)n * 4;
+        const size_t o_u = seg(off, m * 4), o_v = seg(off, m * 4), o_act = seg(off, m);
+        const size_t tap_end = o_act + m;
+        uint8_t* h = nullptr;
+        if ((rc = frame_staging(c, off, &h))) return rc;
+        size_t w = 0;                                                          // device-only work area
+        const size_t w_qr = seg(w, m * 4), w_minl = seg(w, m * 4), w_maxl = seg(w, m * 4), w_qflag = seg(w, m), w_qdesc = seg(w, m * 32);
+        CCM_RESERVE(c, S.tmm, w + 64);
+        uint8_t* io = S.io.as<uint8_t>(); uint8_t* wk = S.tmm.as<uint8_t>();
+
+        if (p->last_outlier) std::memcpy(h + o_lout, p->last_outlier, m);
+        std::memset(h + o_head, 0, up_end - o_head);
+        if (pose) { std::memcpy(h + o_pose, r->pose7, 56); std::memcpy(h + o_intr, p->intr, 32); std::memcpy(h + o_is2, p->inv_level_sigma2, (size_t)p->n_levels * 4); }
+        std::memcpy(h + o_scale, p->scale_factors, (size_t)p->n_levels * 4);
+        if ((rc = frame_upload(c, o_lout, up_end))) return rc;                 // 5 segments of 64 bytes, and last_outlier when given
+
+        int* d_head = (int*)(io + o_head); int* d_out = (int*)(io + o_out); uint8_t* d_flag = io + o_flag;
+        TmmArgs A{};
+        A.n_last = nl; A.last_id = last->mp_id; A.last_outlier = p->last_outlier ? io + o_lout : nullptr;
+        std::memcpy(A.Tcw, p->Tcw, sizeof A.Tcw);
+        A.fx = p->fx; A.fy = p->fy; A.cx = p->cx; A.cy = p->cy; A.min_x = p->min_x; A.max_x = p->max_x; A.min_y = p->min_y; A.max_y = p->max_y;
+        A.qx = (float*)(io + o_u); A.qy = (float*)(io + o_v); A.act = io + o_act; A.qflag = wk + w_qflag; A.qdesc = wk + w_qdesc; A.head = d_head;
+        tmm_launch_project(st, A, t->T);
+        CCM_HIP(c, hipGetLastError());
+
+        std::vector<uint8_t> occ(n);
+        int nm = 0, passes = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            const float th = pass == 0 ? p->th : 2.0f * p->th;
+            tmm_launch_clear(st, n, nl, d_head, cur->mp_id, d_out, d_flag, A.act);
+            frame_launch_prep_last(st, nl, A.act, last->oct, (const float*)(io + o_scale), th, (float*)(wk + w_qr), (int*)(wk + w_minl), (int*)(wk + w_maxl));
+            CCM_HIP(c, hipGetLastError());
+            WinDevCall D{ 2, nl, A.qx, A.qy, (const float*)(wk + w_qr), (const int*)(wk + w_minl), (const int*)(wk + w_maxl), A.qdesc, A.act, A.qflag,
+                          last->mp_id, last->angle, o_status, o_out, o_flag, pass_end, 0.f, p->orb_dist, p->check_ori ? 1 : 0,
+                          nullptr, nullptr, nullptr, last, nullptr, false };
+            nm = frame_window_dev(c, cur, D, occ.data(), r->match);
+            if (nm < 0) return nm;
+            passes = pass + 1;
+            if (pass == 0) {                                                   // the projection's verdict came back with the first pass
+                int bad = 0;
+                if (D.host_accept) { if ((rc = frame_fetch(c, &bad, d_head, 4))) return rc; }
+                else std::memcpy(&bad, h + o_head, 4);
+                if (bad) return ccm_fail(c, CCM_E_ARG, "%s: last holds a map-point id outside [0, %d) or of a slot that is not LIVE", fn, t->capacity);
+            }
+            if (!(nm < p->retry_below)) break;
+        }
+        r->n_matches = nm; r->passes = passes;
+
+        const bool posed = pose && nm >= p->min_matches;
+        if (posed && (rc = frame_pose_queue(c, cur, t->T.capacity, t->T.pos, t->T.flags, p->n_levels, PoseIo{ o_ninl, o_outl, o_pose, o_intr, o_is2, 0 })))
+            return rc;
+        tmm_launch_discard(st, n, cur->mp_id, posed ? io + o_outl : nullptr, t->T, (int*)(io + o_ids), d_head);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = frame_fetch(c, h + o_head, io + o_head, (taps ? tap_end : res_end) - o_head))) return rc;
+        int head[2], ninl[2] = { 0, 0 };
+        std::memcpy(head, h + o_head, 8);
+        if (posed) {
+            std::memcpy(ninl, h + o_ninl, 8);
+            if (ninl[1]) return ccm_fail(c, CCM_E_DEVICE, "%s: the pose stage met an id or octave it cannot use", fn);   // checked on entry and by the projection
+            std::memcpy(r->pose7, h + o_pose, 56);
+            std::memcpy(r->outlier, h + o_outl, n);
+        } else std::memset(r->outlier, 0, n);
+        std::memcpy(r->mp_id, h + o_ids, (size_t)n * 4);
+        r->posed = posed ? 1 : 0; r->n_inliers = ninl[0]; r->n_matches_map = head[1];
+        if (taps) { std::memcpy(r->u, h + o_u, m * 4); std::memcpy(r->v, h + o_v, m * 4); std::memcpy(r->valid, h + o_act, m); }
         return CCM_OK;
     });
 }

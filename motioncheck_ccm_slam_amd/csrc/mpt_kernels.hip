@@ -12,6 +12,9 @@
 //                      ccm_fuse_select_table_frames: the projection and the gates of ORBmatcher::Fuse, both overloads
 //                      (src/ORBmatcher.cpp:870-920, :1018-1071), for every (keyframe, point) pair; the survivors become the
 //                      queries of k_window_select (match_kernels.hip)
+//   k_tmm_project / k_tmm_clear / k_tmm_discard
+//                      ccm_frame_track_motion_model: the queries of SearchByProjection(Current, Last) from the last frame's ids
+//                      (src/ORBmatcher.cpp:1374-1396), the clear before each pass and "discard outliers" (src/Tracking.cpp:599-618)
 // No kernel waits for another workgroup: the compaction is three launches (ballot + count, scan, scatter).
 // Every index is checked against the table's capacity before it is used as an address.
 #include <hip/hip_runtime.h>
@@ -74,19 +77,32 @@ __global__ void k_slp_mark(MptTable T, int n, const int* mp_id, int stamp, int* 
 // ---------------------------------------------------------------------------------------------------------------- second loop
 __device__ inline int slp_slot(const SlpArgs& A, int j) { return A.order ? A.order[j] : j; }
 
+// The projection both SearchLocalPoints and TrackWithMotionModel's SearchByProjection(Current, Last) use (src/Frame.cpp:150-163,
+// src/ORBmatcher.cpp:1380-1396): Pc = Rcw P + tcw summed in double and stored as float, invz = 1 / PcZ, u = fx * PcX * invz + cx in
+// float, left to right, every operation rounded (the build's -ffp-contract=off keeps the compiler from fusing them).  What rejects a
+// point behind the camera differs between the two callers and stays with them.
+__device__ inline void mpt_to_camera(const float* Tcw, const float* P, float* Pc)
+{
+    for (int r = 0; r < 3; r++)
+        Pc[r] = (float)((double)Tcw[4 * r] * (double)P[0] + (double)Tcw[4 * r + 1] * (double)P[1] + (double)Tcw[4 * r + 2] * (double)P[2] +
+                        (double)Tcw[4 * r + 3]);
+}
+__device__ inline void mpt_pinhole(float fx, float fy, float cx, float cy, const float* Pc, float invz, float& u, float& v)
+{
+    u = fx * Pc[0] * invz + cx;
+    v = fy * Pc[1] * invz + cy;
+}
+
 // Frame::isInFrustum + PredictScale for one point, in the arithmetic of float cv::Mat expressions (map_math.h: the products of
 // a matrix product, dot and norm are summed in double and stored as float; everything else is float, left to right).
 __device__ inline bool slp_in_frustum(const SlpArgs& A, const MptTable& T, int s, float& u, float& v, float& view_cos, int& level)
 {
     const float P[3] = { T.pos[3 * (size_t)s], T.pos[3 * (size_t)s + 1], T.pos[3 * (size_t)s + 2] };
     float Pc[3];
-    for (int r = 0; r < 3; r++)
-        Pc[r] = (float)((double)A.Tcw[4 * r] * (double)P[0] + (double)A.Tcw[4 * r + 1] * (double)P[1] + (double)A.Tcw[4 * r + 2] * (double)P[2] +
-                        (double)A.Tcw[4 * r + 3]);
+    mpt_to_camera(A.Tcw, P, Pc);
     if (Pc[2] < 0.0f) return false;
     const float invz = 1.0f / Pc[2];
-    u = A.fx * Pc[0] * invz + A.cx;
-    v = A.fy * Pc[1] * invz + A.cy;
+    mpt_pinhole(A.fx, A.fy, A.cx, A.cy, Pc, invz, u, v);
     if (u < A.min_x || u > A.max_x) return false;
     if (v < A.min_y || v > A.max_y) return false;
     const float max_d = T.max_dist[s];
@@ -433,7 +449,89 @@ __global__ void k_fuse_scatter(int nq, int n_pairs, const int* qpair, const int*
     if (best_dist) best_dist[pair] = sel_d[q];
 }
 
+// ---------------------------------------------------------------------------------------------------------------- motion model
+// ccm_frame_track_motion_model.  k_tmm_project: the first half of the loop of ORBmatcher::SearchByProjection(Current, Last)
+// (src/ORBmatcher.cpp:1374-1396), one thread per feature of the last frame.  A feature without a point, or one LastFrame.mvbOutlier
+// names, is no query; isBad() is not asked there, so a BAD slot is projected.  An id outside the table or of a slot that is not LIVE
+// raises head[0] (every thread that finds one stores the same 1) and is never used as an address.  Stated deviation: a u or v that is
+// not finite (PcZ == 0) is rejected; the reference would hand it to GetFeaturesInArea.  A feature that is no query gets u = v = 0.
+__global__ __launch_bounds__(TMM_TPB) void k_tmm_project(TmmArgs A, MptTable T)
+{
+    const int i = blockIdx.x * TMM_TPB + threadIdx.x;
+    if (i >= A.n_last) return;
+    const int id = A.last_id[i];
+    float u = 0.0f, v = 0.0f;
+    bool valid = false;
+    uint8_t fl = 0;
+    if (id >= 0 && !(A.last_outlier && A.last_outlier[i])) {
+        fl = id < T.capacity ? T.flags[id] : 0;
+        if (!(fl & CCM_MP_LIVE)) A.head[0] = 1;
+        else {
+            const float P[3] = { T.pos[3 * (size_t)id], T.pos[3 * (size_t)id + 1], T.pos[3 * (size_t)id + 2] };
+            float Pc[3];
+            mpt_to_camera(A.Tcw, P, Pc);
+            const float invz = 1.0f / Pc[2];
+            if (!(invz < 0.0f)) {                                              // :1386
+                mpt_pinhole(A.fx, A.fy, A.cx, A.cy, Pc, invz, u, v);
+                valid = fabsf(u) <= 3.402823466e+38f && fabsf(v) <= 3.402823466e+38f &&      // a NaN compares false
+                        !(u < A.min_x || u > A.max_x) && !(v < A.min_y || v > A.max_y);      // :1392-1395, both ends inside
+                if (!valid) { u = 0.0f; v = 0.0f; }
+            }
+        }
+    }
+    A.qx[i] = u; A.qy[i] = v; A.act[i] = valid ? 1 : 0; A.qflag[i] = (valid && (fl & CCM_MP_HAS_OBS)) ? 1 : 0;
+    if (valid) {
+        const uint4* a = reinterpret_cast<const uint4*>(T.desc + (size_t)id * 32);
+        uint4* b = reinterpret_cast<uint4*>(A.qdesc + (size_t)i * 32);
+        b[0] = a[0]; b[1] = a[1];
+    }
+}
+
+// Before every search pass (src/Tracking.cpp:579, :589): the current frame's ids to -1, the matcher's result to -1, its occupancy flags
+// to 0.  With head[0] raised by k_tmm_project the ids stay as they are and every query is switched off instead, so that the pass
+// queued behind finds nothing and writes nothing; the host then reports CCM_E_ARG.
+__global__ void k_tmm_clear(int n_cur, int n_last, const int* head, int* mp_id, int* out, uint8_t* flag, uint8_t* act)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool bad = head[0] != 0;
+    if (i < n_cur) {
+        out[i] = -1; flag[i] = 0;
+        if (!bad) mp_id[i] = -1;
+    }
+    if (bad && i < n_last) act[i] = 0;
+}
+
+// "Discard outliers" (src/Tracking.cpp:599-618), one thread per feature of the current frame: a feature that holds a point and is an
+// outlier of the pose (outlier == nullptr: no pose ran, nothing is dropped) loses it; ids_out is the handle's copy for the download.
+// head[1] counts the features that keep a point with observations: a wave's ballot, one atomic add per wave.
+__global__ __launch_bounds__(TMM_TPB) void k_tmm_discard(int n, int* mp_id, const uint8_t* outlier, MptTable T, int* ids_out, int* head)
+{
+    const int i = blockIdx.x * TMM_TPB + threadIdx.x, lane = threadIdx.x & 63;
+    bool counts = false;
+    if (i < n) {
+        int id = mp_id[i];
+        if (id >= 0 && outlier && outlier[i]) { id = -1; mp_id[i] = -1; }
+        ids_out[i] = id;
+        counts = id >= 0 && id < T.capacity && (T.flags[id] & CCM_MP_HAS_OBS);
+    }
+    const unsigned long long ball = __ballot(counts);
+    if (ball && lane == __ffsll((long long)ball) - 1) atomicAdd(head + 1, __popcll(ball));
+}
+
 // ---------------------------------------------------------------------------------------------------------------- launchers
+void tmm_launch_project(hipStream_t s, const TmmArgs& A, const MptTable& T)
+{
+    if (A.n_last > 0) hipLaunchKernelGGL(k_tmm_project, dim3((A.n_last + TMM_TPB - 1) / TMM_TPB), dim3(TMM_TPB), 0, s, A, T);
+}
+void tmm_launch_clear(hipStream_t s, int n_cur, int n_last, const int* head, int* mp_id, int* out, uint8_t* flag, uint8_t* act)
+{
+    const int m = n_cur > n_last ? n_cur : n_last;
+    if (m > 0) hipLaunchKernelGGL(k_tmm_clear, dim3((m + 255) / 256), dim3(256), 0, s, n_cur, n_last, head, mp_id, out, flag, act);
+}
+void tmm_launch_discard(hipStream_t s, int n, int* mp_id, const uint8_t* outlier, const MptTable& T, int* ids_out, int* head)
+{
+    if (n > 0) hipLaunchKernelGGL(k_tmm_discard, dim3((n + TMM_TPB - 1) / TMM_TPB), dim3(TMM_TPB), 0, s, n, mp_id, outlier, T, ids_out, head);
+}
 void mpt_launch_scatter(hipStream_t s, const MptTable& T, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
                         const float* max_dist, const uint8_t* desc, const uint8_t* flags)
 {

@@ -8,6 +8,7 @@
 #define SCAN_TPB 1024
 #define MPR_TPB 256        // k_mpt_refresh: one wave per map point, 4 points per workgroup
 #define FUSE_TPB 256       // k_fuse_project: one thread per (keyframe, point) pair, the keyframe uniform per workgroup
+#define TMM_TPB 256        // k_tmm_project / k_tmm_discard: one thread per feature
 #define MPR_LDS_ROWS 256   // descriptors a wave keeps in LDS: 8 KB per wave, 32 KB per workgroup; further rows are read from global memory
 
 struct MptTable {                                // the table's columns (device)
@@ -53,6 +54,20 @@ struct FuseArgs {
     int* cnt; float* qx; float* qy; float* qr; int* minl; int* maxl; int* qkf; int* qpair; uint8_t* qdesc;
 };
 
+// ccm_frame_track_motion_model: what k_tmm_project reads of the last frame and the caller's camera, and the matcher's queries it writes
+struct TmmArgs {
+    int n_last; const int* last_id; const uint8_t* last_outlier;     // last_outlier == nullptr: none
+    float Tcw[12], fx, fy, cx, cy, min_x, max_x, min_y, max_y;
+    float* qx; float* qy; uint8_t* act; uint8_t* qflag; uint8_t* qdesc;   // per last-frame feature; qx / qy / act are also the taps
+    int* head;                                                       // [0]: an id outside the table or of a slot that is not LIVE
+};
+
+// k_tmm_project: the queries of SearchByProjection(Current, Last) from the last frame's ids and the table
+void tmm_launch_project(hipStream_t, const TmmArgs&, const MptTable&);
+// before a search pass: out = -1, flag = 0 [n_cur]; mp_id = -1, or with head[0] set the ids kept and act [n_last] = 0
+void tmm_launch_clear(hipStream_t, int n_cur, int n_last, const int* head, int* mp_id, int* out, uint8_t* flag, uint8_t* act);
+// the outliers (nullptr: none) lose their id; ids_out = mp_id afterwards; head[1] += features that keep a slot with HAS_OBS
+void tmm_launch_discard(hipStream_t, int n, int* mp_id, const uint8_t* outlier, const MptTable&, int* ids_out, int* head);
 void mpt_launch_scatter(hipStream_t, const MptTable&, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
                         const float* max_dist, const uint8_t* desc, const uint8_t* flags);
 void mpt_launch_gather(hipStream_t, const MptTable&, int n, const int* slot, float* pos, float* normal, float* min_dist, float* max_dist,

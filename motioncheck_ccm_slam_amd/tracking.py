@@ -3,7 +3,8 @@
 `MapPointTable` mirrors ccm_map_table: the client's map points on the GPU, one row per slot (a slot is the id a `DeviceFrame` carries
 in `map_points`), updated by rows when the map changes.  `Tracking.SearchLocalPoints` is Tracking::SearchLocalPoints
 (src/Tracking.cpp:860-922) in one call on a frame handle and the table; `Tracking.TrackLocalMap` adds the pose optimisation and the
-inlier count of Tracking::TrackLocalMap (:623-727)."""
+inlier count of Tracking::TrackLocalMap (:623-727); `Tracking.TrackWithMotionModel` is Tracking::TrackWithMotionModel (:569-621)
+behind the pose product in one call on the last and the current frame's handles and the table."""
 from __future__ import annotations
 
 import ctypes as C
@@ -111,8 +112,23 @@ class MapPointTable:
             pass
 
 
+class MotionModelResult:
+    """What `Tracking.TrackWithMotionModel` returns (ccm_tmm_result): n_matches and passes of the search, posed, n_inliers,
+    n_matches_map, pose7 (optimised when posed), match [N_cur] (feature of the last frame or -1), mp_id [N_cur] (the current frame's
+    map_points after the call), outlier [N_cur] (before the discard) and, with taps, u / v / valid [N_last].  `ok` is the function's
+    return value at :620, nmatchesMap >= 10, and False after the early return of :593."""
+    u = v = valid = None
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def ok(self):
+        return bool(self.posed) and self.n_matches_map >= 10
+
+
 class Tracking:
-    """The per-frame calls of Tracking::TrackLocalMap on a `frame.DeviceFrame` and a `MapPointTable`."""
+    """The per-frame calls of Tracking::TrackLocalMap and Tracking::TrackWithMotionModel on `frame.DeviceFrame`s and a `MapPointTable`."""
 
     @staticmethod
     def camera(Tcw, Ow=None):
@@ -198,6 +214,51 @@ class Tracking:
             keep &= np.asarray(mp_has_obs, bool)[np.maximum(ids, 0)]
         nmap = int(keep.sum())
         return dict(ok=nmap >= min_inliers, nmatches=nm, match=match, pose=p7, outlier=outl, n_inliers=ninl, nmatches_map=nmap, mp_id=ids)
+
+    @staticmethod
+    def TrackWithMotionModel(cur, last, table: MapPointTable, Tcw, pose, intr, scale_factors, inv_level_sigma2, bounds=(0.0, 752.0, 0.0, 480.0),
+                             th=7.0, retry_below=20, min_matches=20, check_ori=True, orb_dist=100, last_outlier=None, taps=False, ctx=None):
+        """Tracking::TrackWithMotionModel (src/Tracking.cpp:569-621) behind the pose product, in one call on two `frame.DeviceFrame`s
+        and the table (ccm_frame_track_motion_model): SearchByProjection(cur, last, th), once more with 2 * th when it finds fewer than
+        retry_below, then -- with at least min_matches -- the pose optimisation from `pose` and "discard outliers".  Tcw = the predicted
+        mVelocity * mLastFrame->mTcw (3x4 or 4x4), pose = the same as pose7, intr = fx, fy, cx, cy.  inv_level_sigma2 = None: the search
+        alone.  Returns a `MotionModelResult`."""
+        ctx = ctx or cur.ctx
+        lib = _lib.load()
+        T, _ = Tracking.camera(Tcw, np.zeros(3, "f4"))
+        sf = np.ascontiguousarray(scale_factors, "f4")
+        p = _lib.TmmParams()
+        p.Tcw[:] = [float(v) for v in T.reshape(-1)]
+        p.fx, p.fy, p.cx, p.cy = [float(np.float32(v)) for v in intr]
+        p.min_x, p.max_x, p.min_y, p.max_y = [float(np.float32(v)) for v in bounds]
+        p.n_levels = len(sf); p.scale_factors = sf.ctypes.data; p.th = float(th)
+        p.retry_below = int(retry_below); p.min_matches = int(min_matches); p.check_ori = int(bool(check_ori)); p.orb_dist = int(orb_dist)
+        lo = None if last_outlier is None else np.ascontiguousarray(last_outlier, np.uint8)
+        if lo is not None and lo.shape != (last.n,):
+            raise ValueError("last_outlier needs %d entries" % last.n)
+        p.last_outlier = None if lo is None or last.n == 0 else lo.ctypes.data
+        is2 = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, "f4")
+        if is2 is not None and len(is2) != len(sf):
+            raise ValueError("inv_level_sigma2 and scale_factors need one entry per level each")
+        k4 = np.ascontiguousarray(intr, "f8")
+        p.inv_level_sigma2 = None if is2 is None else is2.ctypes.data
+        p.intr = k4.ctypes.data
+        n, nl = cur.n, last.n
+        match = np.full(max(n, 1), -1, "i4"); mp_id = np.full(max(n, 1), -1, "i4"); outl = np.zeros(max(n, 1), np.uint8)
+        r = _lib.TmmResult()
+        r.pose7[:] = [float(v) for v in np.asarray(pose, "f8").reshape(-1)[:7]]
+        r.match = match.ctypes.data; r.mp_id = mp_id.ctypes.data; r.outlier = outl.ctypes.data
+        if taps:
+            u = np.zeros(max(nl, 1), "f4"); v = np.zeros(max(nl, 1), "f4"); valid = np.zeros(max(nl, 1), np.uint8)
+            r.u = u.ctypes.data; r.v = v.ctypes.data; r.valid = valid.ctypes.data
+        ctx.check(lib.ccm_frame_track_motion_model(ctx.handle, C.c_void_p(cur.handle), C.c_void_p(last.handle), C.c_void_p(table.handle),
+                                                   C.byref(p), C.byref(r)))
+        res = MotionModelResult(n_matches=int(r.n_matches), passes=int(r.passes), posed=bool(r.posed), n_inliers=int(r.n_inliers),
+                                n_matches_map=int(r.n_matches_map), pose7=np.array(r.pose7[:], "f8"), match=match[:n], mp_id=mp_id[:n],
+                                outlier=outl[:n])
+        if taps:
+            res.u, res.v, res.valid = u[:nl], v[:nl], valid[:nl]
+        return res
 
     @staticmethod
     def TrackLocalMap(frame, table: MapPointTable, pose, Tcw, intr, scale_factors, inv_level_sigma2, **kw):

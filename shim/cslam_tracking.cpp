@@ -2,7 +2,8 @@
 // Tracking::SearchLocalPoints (:860-922) and Tracking::TrackLocalMap (:623-727) on the device-resident map-point table (ccm_hot.h "map-point table").  The reference visits
 // every map point of the client's map on every tracked image (this fork sets mvpLocalMapPoints = mpMap->GetAllMapPoints(), :924-934)
 // and calls Frame::isInFrustum on each; here the map lives in a ccm_map_table, ONE ccm_frame_search_local_points call does both loops
-// and the matcher, and ONE ccm_frame_pose_optimize_table call the pose.  Remove these three bodies from src/Tracking.cpp; the rest
+// and the matcher, and ONE ccm_frame_pose_optimize_table call the pose.  Tracking::TrackWithMotionModel (:569-621) is ONE
+// ccm_frame_track_motion_model on the last and the current frame's handles.  Remove these four bodies from src/Tracking.cpp; the rest
 // of the file stays as it is.
 //
 // The table is filled where the map changes, not here: INTEGRATION.md "Map-point table" lists the one-line hooks in Map::AddMapPoint
@@ -81,6 +82,12 @@ public:
     {
         std::lock_guard<std::mutex> lock(mMutex);
         return slot >= 0 && slot < (int)mPoints.size() ? mPoints[slot] : nullptr;
+    }
+    // Whether the table lives in context c: a table and the frame handles used with it belong to one context
+    bool in_context(ccm_ctx* c)
+    {
+        std::lock_guard<std::mutex> lock(mMutex);
+        return mTable && mCtx == c;
     }
     // The tracking thread, before it searches: the queued rows and, when the set of points changed, the order.  Returns the table.
     ccm_map_table* flush()
@@ -401,6 +408,110 @@ bool Tracking::TrackLocalMap()
     if (mnMatchesInliers < params::tracking::miTrackLocalMapInlierThres)
         return false;
     return true;
+}
+
+// ---- Tracking::TrackWithMotionModel (:569-621): UpdateLastFrame and the pose product stay on the host in cv::Mat; the clear, both
+// SearchByProjection(Current, Last) passes, PoseOptimizationClient and "discard outliers" are ONE ccm_frame_track_motion_model on the
+// two frames' handles and the table.  Nothing of the map is uploaded: the last frame's points travel as slots (4 bytes a feature,
+// into its handle), the projection is made on the device from the table's rows.
+namespace {
+
+// CCM_SHIM_TRACK_MOTION_MODEL=0: back to the three calls (A/B timing of the two routes)
+bool track_motion_model_on()
+{
+    static const bool on = !(getenv("CCM_SHIM_TRACK_MOTION_MODEL") && atoi(getenv("CCM_SHIM_TRACK_MOTION_MODEL")) == 0);
+    return on;
+}
+
+}  // namespace
+
+bool Tracking::TrackWithMotionModel()
+{
+    UpdateLastFrame();
+    Frame& F = *mCurrentFrame;
+    const Frame& L = *mLastFrame;
+    F.SetPose(mVelocity * L.mTcw);
+    const int N = F.N;
+    std::fill(F.mvpMapPoints.begin(), F.mvpMapPoints.end(), mpptr());
+
+    // The route before ccm_frame_track_motion_model: the matcher drop-in (cslam_orbmatcher.cpp: the projection on the host, valid / u / v
+    // / descriptors / flags uploaded per pass), the pose drop-in, and the discard here.
+    auto three_calls = [&]() -> bool {
+        ORBmatcher matcher(0.9, true);
+        const int th = 7;
+        int nmatches = matcher.SearchByProjection(F, L, th);
+        if (nmatches < 20) {
+            std::fill(F.mvpMapPoints.begin(), F.mvpMapPoints.end(), mpptr());
+            nmatches = matcher.SearchByProjection(F, L, 2 * th);
+        }
+        if (nmatches < params::tracking::miTrackWithMotionModelInlierThresSearch) return false;
+        Optimizer::PoseOptimizationClient(F);
+        int nmatchesMap = 0;
+        for (int i = 0; i < N; i++) {
+            mpptr pMP = F.mvpMapPoints[i];
+            if (!pMP) continue;
+            if (F.mvbOutlier[i]) {
+                F.mvpMapPoints[i] = nullptr; F.mvbOutlier[i] = false;
+                pMP->mbTrackInView = false; pMP->mLastFrameSeen = F.mId;
+            } else if (pMP->Observations() > 0)
+                nmatchesMap++;
+        }
+        return nmatchesMap >= params::tracking::miTrackWithMotionModelInlierThresOpt;
+    };
+    if (!track_motion_model_on()) return three_calls();
+
+    ccm_ctx* c = ccm_shim::ctx();
+    ccm_shim::MapTable& T = ccm_shim::MapTable::get();
+    ccm_map_table* table = T.flush();
+    if (!table) throw estd::infrastructure_ex();
+    // Fallback 1: the table was made by another thread's flush and lives in that thread's context; this thread's frame handles
+    // cannot be used with it (ccm_frame_track_motion_model would return CCM_E_ARG).
+    if (!T.in_context(c)) return three_calls();
+    // Fallback 2: a point of the last frame has no slot (one that Map::AddMapPoint's hook never saw): the handle could not name it.
+    std::vector<int32_t> slots(std::max(L.N, 1), -1);
+    std::vector<uint8_t> last_outlier(std::max(L.N, 1), 0);
+    for (int i = 0; i < L.N; i++) {
+        last_outlier[i] = L.mvbOutlier[i] ? 1 : 0;
+        if (!L.mvpMapPoints[i]) continue;
+        slots[i] = T.slot_of(L.mvpMapPoints[i]);
+        if (slots[i] < 0) return three_calls();
+    }
+    ccm_frame* hc = ccm_shim::frame_handle(F);
+    ccm_frame* hl = ccm_shim::frame_handle(L);
+    if (!hc || !hl || ccm_frame_set_map_points(hl, slots.data())) throw estd::infrastructure_ex();
+
+    ccm_tmm_params p{};
+    float T16[16];
+    for (int r = 0; r < 4; r++) for (int cc = 0; cc < 4; cc++) T16[4 * r + cc] = F.mTcw.at<float>(r, cc);
+    for (int k = 0; k < 12; k++) p.Tcw[k] = T16[k];
+    p.fx = Frame::fx; p.fy = Frame::fy; p.cx = Frame::cx; p.cy = Frame::cy;
+    p.min_x = Frame::mnMinX; p.max_x = Frame::mnMaxX; p.min_y = Frame::mnMinY; p.max_y = Frame::mnMaxY;
+    p.n_levels = F.mnScaleLevels; p.scale_factors = F.mvScaleFactors.data();
+    p.th = 7.f; p.retry_below = 20; p.min_matches = params::tracking::miTrackWithMotionModelInlierThresSearch;
+    p.check_ori = 1; p.orb_dist = ORBmatcher::TH_HIGH;                         // ORBmatcher matcher(0.9, true)
+    p.last_outlier = last_outlier.data();
+    const double intr[4] = {Frame::fx, Frame::fy, Frame::cx, Frame::cy};
+    p.inv_level_sigma2 = F.mvInvLevelSigma2.data(); p.intr = intr;
+    std::vector<int32_t> match(std::max(N, 1), -1), ids(std::max(N, 1), -1);
+    std::vector<uint8_t> outlier(std::max(N, 1), 0);
+    ccm_tmm_result r{};
+    ccm_pose_from_mat4f(T16, r.pose7);
+    r.match = match.data(); r.mp_id = ids.data(); r.outlier = outlier.data();
+    if (ccm_frame_track_motion_model(c, hc, hl, table, &p, &r)) throw estd::infrastructure_ex();
+
+    for (int i = 0; i < N; i++) F.mvpMapPoints[i] = ids[i] >= 0 ? T.point(ids[i]) : mpptr();
+    if (!r.posed) return false;                                                // :593: the matches stay in mvpMapPoints
+    ccm_pose_to_mat4f(r.pose7, T16);
+    cv::Mat Tcw(4, 4, CV_32F);
+    for (int rr = 0; rr < 4; rr++) for (int cc = 0; cc < 4; cc++) Tcw.at<float>(rr, cc) = T16[4 * rr + cc];
+    F.SetPose(Tcw);
+    for (int i = 0; i < N; i++) {                                              // :605-612 for the points the device discarded
+        if (match[i] < 0) continue;
+        F.mvbOutlier[i] = false;
+        if (!outlier[i]) continue;
+        if (mpptr pMP = T.point(slots[match[i]])) { pMP->mbTrackInView = false; pMP->mLastFrameSeen = F.mId; }
+    }
+    return r.n_matches_map >= params::tracking::miTrackWithMotionModelInlierThresOpt;
 }
 
 // ---- Tracking::TrackReferenceKeyFrame (:514-556) on handles: Frame::ComputeBoW, SearchByBoW(mpReferenceKF, Frame) and
