@@ -1,0 +1,397 @@
+// orb_fast_cells.hip -- FAST of the ORB extractor in one kernel: score, per-cell threshold choice and 3x3 NMS on bands of cells whose
+// scores stay in LDS (the stages: orb_types.h; the two-kernel path of the bands that do not fit: orb_fast_tiles.hip).
+#include <hip/hip_runtime.h>
+#include "orb_types.h"
+#include "orb_device.h"
+
+// ------------------------------------------------------------------------------------------------
+// k_fast_cells: k_fast_score + k_cell_nms fused on a band = a run of cells of one cell row.  The band's pixels
+// are staged once in LDS, scored in LDS (rejection test -> survivor list -> dense scoring, in row blocks), and
+// each cell's threshold choice / 3x3 NMS / ordered compaction runs straight from the LDS score tile: the score
+// map never goes to HBM.  Bands of adjacent cell rows overlap by 6 rows, which are scored twice.
+// One band per workgroup.  Round 3 built the alternative -- a workgroup loops over 1..8 consecutive bands and requests the next
+// band's pixels (8 registers per thread, one branch-free 16-byte global load per chunk) as soon as the current band is scored, so
+// that they arrive under the NMS -- and measured it on one box against this kernel (tools/ab_orb.sh): 0.391 ms at 1 band per
+// workgroup, 0.410 / 0.421 / 0.424 / 0.436 / 0.448 at 2 / 3 / 4 / 6 / 8, against 0.368.  A round of the loop (the extra barrier, the
+// band record and the kernel arguments re-read through scalar loads, 64 registers instead of 54) costs more than a fresh workgroup,
+// whose start-up the dispatcher overlaps with the seven others on the CU.  Not kept.
+// NMS works on the list of scored pixels (FC_NZ entries) and the list of local maxima (FC_KEPT); a band that overflows
+// either list takes the per-cell row scan instead.
+// The kernel is bound by the dependent chain of one band (8 bands per CU, each issuing for a tenth of its life).  The first NMS pass
+// therefore requests a scored pixel's eight neighbours and its column's cell together, and a cell's count comes from the per-cell
+// counters, not from a scan of its bucket by the last wave (0.367 -> 0.354 ms with the global-address-space staging loads).
+// Measured and dropped (profiles/fc_chain_ab.txt): the rank loop reading its bucket eight entries per wait (nothing), all staging
+// trips of a thread in flight before the first store (+0.002 ms), the next rejection run's LDS dwords requested before the current
+// run's ballots (+0.012 ms, 60 registers), the column masks requested with the pixel dwords (nothing).
+#ifndef FC_NZ
+#define FC_NZ 1024
+#endif
+#ifndef FC_KEPT
+#define FC_KEPT 480             // + the per-cell bucket counters = the 20480 bytes of LDS that let 8 workgroups share a CU on the 4-cell bands
+#endif
+#define FC_CELLS 32
+#ifndef FC_TPB
+#define FC_TPB 256              // threads per band workgroup (measured: 192 0.56, 256 0.52, 320 0.75, 384 0.82 ms)
+#endif
+// Survivors of the rejection test wait on the wave's own stack in LDS (running count in a scalar register, no atomic) and are scored
+// 64 at a time: the stack never holds more than 63 waiting entries + the 256 pixels of one run of 64 four-pixel items.
+#define FC_WAVE_CAP 320         // wave-local stack: at most 63 waiting + the 256 pixels of one item
+__host__ __device__ inline size_t fc_lds_bytes(int pitch, int bh)
+{
+    return 2 * (size_t)pitch * bh + (size_t)FC_WAVE_CAP * (FC_TPB / 64) * 2 + 32 + FC_NZ * 2 + FC_KEPT * 4 + FC_CELLS * 16 + 64 * 8 + 256 + 64;
+}
+
+// The rejection test runs on two pixels per register with the packed 16-bit VALU (v_pk_sub_u16 / v_pk_max_u16 /
+// v_pk_min_u16): |v - n| <= t  <=>  (u16)(v + t - n) <= 2t.
+__device__ __forceinline__ unsigned fc_u(fc_us2 x) { return __builtin_bit_cast(unsigned, x); }      // (fc_pk: orb_device.h)
+__device__ __forceinline__ int fc_mbcnt(unsigned long long m, int base)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)base));
+}
+// Diagnostic build only (-DFC_STAMPS, tools/r03_fc_stamps.sh): wave 0 (slots 0-7) and the last wave (slots 8-15) of every workgroup leave the shader clock at their phase
+// boundaries in a buffer no other code reads; the shipped kernel contains none of this.
+#ifdef FC_STAMPS
+#define FC_STAMP_SLOTS 16
+#define FC_STAMP_WGS (1 << 17)
+__device__ unsigned long long fc_stamps[FC_STAMP_WGS * FC_STAMP_SLOTS];
+#define FC_STAMP(k) do { if (threadIdx.x == 0 || threadIdx.x == FC_TPB - 1) { const unsigned wg__ = blockIdx.y * gridDim.x + blockIdx.x; if (wg__ < FC_STAMP_WGS) fc_stamps[wg__ * FC_STAMP_SLOTS + (threadIdx.x ? 8 : 0) + (k)] = __builtin_amdgcn_s_memtime(); } } while (0)
+extern "C" int ccm_debug_fc_stamps(unsigned long long* out, int n_wgs)
+{
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(fc_stamps), (size_t)n_wgs * FC_STAMP_SLOTS * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#else
+#define FC_STAMP(k) do { } while (0)
+#endif
+// image pixels in the global address space (global_load_*, not flat_load_*); fc_u32x4_a4: 16 bytes at a 4-byte-aligned address
+typedef const __attribute__((address_space(1))) uint8_t fc_gbyte;
+typedef const __attribute__((address_space(1))) unsigned fc_gu32;
+typedef unsigned fc_u32x4 __attribute__((ext_vector_type(4)));
+typedef fc_u32x4 fc_u32x4_a4 __attribute__((aligned(4)));
+// element ci (per lane) of four wave-uniform values: three selects, no memory
+template <class T>
+__device__ __forceinline__ int sel4(int ci, const T (&a)[4]) { return ci == 0 ? (int)a[0] : ci == 1 ? (int)a[1] : ci == 2 ? (int)a[2] : (int)a[3]; }
+__global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fast_cells(const OrbGeom g, const OrbCell* __restrict__ cells, const OrbBand* __restrict__ bands,
+                                                    unsigned* __restrict__ slots, int* __restrict__ cell_count, int* __restrict__ clear_status, int xcd_on)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t fc_smem[];
+    if (clear_status && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) *clear_status = 0;      // as in k_pyr_resize: a one-level pyramid starts here
+    int wx, wy;
+    xcd_work_item(xcd_on, wx, wy);
+    FC_STAMP(0);
+    const OrbBand B = bands[wx];
+#ifdef FC_STAMPS
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (diagnostic: the band descriptor has arrived)
+#endif
+    FC_STAMP(6);
+    // the band's cells, held in scalar registers from here on (left to itself the compiler loads them again where the NMS uses them:
+    // another scalar-load latency in each of its two passes, +1,400 cycles per band measured)
+    int bclo[4], bcwd[4], bsfirst[4], bscap[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        bclo[i] = B.clo[i]; bcwd[i] = B.cwd[i]; bsfirst[i] = B.slot_first[i]; bscap[i] = B.slot_cap[i];
+        asm volatile("" : "+s"(bclo[i]), "+s"(bcwd[i]), "+s"(bsfirst[i]), "+s"(bscap[i]));
+    }
+    int bxa = B.xa, by0 = B.y0, bncells = B.ncells, bcfirst = B.cell_first;
+    asm volatile("" : "+s"(bxa), "+s"(by0), "+s"(bncells), "+s"(bcfirst));
+    const int f = wy + g.frame0, tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    // the level's image: from the band record, except level 0 (the caller's frames: pointer, pitch and plane are per call and sit at a
+    // fixed place of the kernel arguments -- no load that depends on the band record)
+    const bool lvl0 = B.level == 0;
+    const uint8_t* const Limg = lvl0 ? g.lv[0].img : B.img;
+    const long long Lplane = lvl0 ? g.lv[0].plane : B.plane;
+    const int Lpitch = lvl0 ? g.lv[0].pitch : B.lpitch, Lw = B.w, Lh = B.h;
+    const int P = B.pitch, bh = B.bh, PW = P >> 2;
+    uint8_t* T = fc_smem;                                   // pixels  [bh][P]
+    uint8_t* S = fc_smem + (size_t)P * bh;                  // scores  [bh][P]
+    constexpr int NW = FC_TPB / 64;
+    const int WCAP = FC_WAVE_CAP;
+    unsigned short* surv = reinterpret_cast<unsigned short*>(S + (size_t)P * bh);     // [NW][WCAP]
+    int* nsurv = reinterpret_cast<int*>(surv + NW * WCAP);   // [1] scored pixels, [2] local maxima, [4 + w] survivors of wave w in the row block
+    unsigned short* nz = reinterpret_cast<unsigned short*>(nsurv + 8);
+    unsigned* kept = reinterpret_cast<unsigned*>(nz + FC_NZ);
+    int* cell_hi = reinterpret_cast<int*>(kept + FC_KEPT);   // per cell: local maxima with score >= iniThFAST
+    int* cell_n = cell_hi + FC_CELLS;                        // per cell: keypoints written
+    int* cell_k = cell_n + FC_CELLS;                         // per cell: local maxima in the cell's bucket of `kept`
+    uint2* colmask = reinterpret_cast<uint2*>(cell_k + FC_CELLS + FC_CELLS);     // per tile dword: 16-bit lane masks of its detection columns: .x pixels 0 and 2, .y pixels 1 and 3
+    // (what the NMS needs of a cell -- its detection columns and its candidate slots -- comes with the band record: until round 3 the
+    //  cell records were loaded from global memory, first on the NMS's critical path, then in front of the pixel loads)
+    uint8_t* colcell = reinterpret_cast<uint8_t*>(colmask + 64);     // [256] cell of a tile column; 255 = no cell's detection column
+    if (tid < FC_CELLS) { cell_hi[tid] = 0; cell_n[tid] = 0; cell_k[tid] = 0; }
+    // per cell, for the NMS (indexed per lane there: an LDS read measured 0.7 % faster than three selects on the scalar registers)
+    int* l_clo = reinterpret_cast<int*>(colcell + 256); int* l_cwd = l_clo + 4; int* l_sfirst = l_cwd + 4; int* l_scap = l_sfirst + 4;
+    if (tid < 4) { l_clo[tid] = sel4(tid, bclo); l_cwd[tid] = sel4(tid, bcwd); l_sfirst[tid] = sel4(tid, bsfirst); l_scap[tid] = sel4(tid, bscap); }
+    if (tid == 0) { nsurv[1] = 0; nsurv[2] = 0; }
+    const uint8_t* img = Limg + (long long)f * Lplane;
+    // ---- stage pixels (clamped: duplicates are only read for pixels whose score is not needed), zero the scores
+    const bool dword_ok = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)Lpitch) & 3) == 0 && Lpitch >= ((Lw + 3) & ~3);
+    // i / PW by multiply-shift: exact for i < 2^20 / PW (i <= 65 * 64 here)
+    const unsigned pw_inv = B.pw_inv;
+#ifdef FC_STAMPS
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (diagnostic: level record and everything scalar before the pixel loads has arrived)
+#endif
+    FC_STAMP(5);
+    // the image is read through global-address-space pointers: `img` is a select between a kernel argument and a field of the band
+    // record, and left generic its loads become flat_load_dword, four per 16-byte chunk
+    fc_gbyte* const gimg = (fc_gbyte*)img;
+    if (dword_ok && (P & 15) == 0) {
+        // 16 bytes per lane: one global_load_dwordx4 and two ds_write_b128 (pixels, zeroed scores) per 16 pixels; the last
+        // chunks of a row are clamped dword by dword (four global_load_dword)
+        const int wmax = ((Lw - 1) & ~3);
+        const int PQ = P >> 4;
+        const unsigned pq_inv = B.pq_inv;                          // i / PQ exact for i < 2^20 / PQ
+        for (int i = tid; i < bh * PQ; i += FC_TPB) {
+            const int ly = (int)(((unsigned)i * pq_inv) >> 20), lq = i - ly * PQ;
+            const int gy = min(B.y0 + ly, Lh - 1), gx = B.xa + 16 * lq;
+            fc_gbyte* rowp = gimg + (long long)gy * Lpitch;
+            fc_u32x4 v;
+            if (gx + 12 <= wmax) v = *reinterpret_cast<const __attribute__((address_space(1))) fc_u32x4_a4*>(rowp + gx);
+            else {
+                v.x = *reinterpret_cast<fc_gu32*>(rowp + min(gx, wmax));
+                v.y = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 4, wmax));
+                v.z = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 8, wmax));
+                v.w = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 12, wmax));
+            }
+            reinterpret_cast<fc_u32x4*>(T)[i] = v;
+            reinterpret_cast<uint4*>(S)[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    } else if (dword_ok) {
+        const int wmax = ((Lw - 1) & ~3);
+        for (int i = tid; i < bh * PW; i += FC_TPB) {
+            const int ly = (int)(((unsigned)i * pw_inv) >> 20), lx = i - ly * PW;
+            const int gy = min(B.y0 + ly, Lh - 1), gx = min(B.xa + 4 * lx, wmax);
+            reinterpret_cast<unsigned*>(T)[i] = *reinterpret_cast<fc_gu32*>(gimg + (long long)gy * Lpitch + gx);
+            reinterpret_cast<unsigned*>(S)[i] = 0u;
+        }
+    } else {
+        for (int i = tid; i < bh * P; i += FC_TPB) {
+            const int ly = i / P, lx = i - ly * P;
+            const int gy = min(B.y0 + ly, Lh - 1), gx = min(B.xa + lx, Lw - 1);
+            T[i] = gimg[(long long)gy * Lpitch + gx];
+            S[i] = 0;
+        }
+    }
+#ifdef FC_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (diagnostic: this wave's pixels have arrived)
+#endif
+    FC_STAMP(7);
+    // columns of the tile that belong to some cell's detection area: [c_lo, c_hi)
+    const int c_lo = B.c_lo, c_hi = B.c_hi;
+    const int t_lo = min(g.ini_th, g.min_th);
+    // dwords that hold at least one detection column and have both neighbours inside the row
+    const int dw_lo = B.dw_lo, dw_hi = B.dw_hi;
+    if (tid < PW) {
+        unsigned mk[4];
+        for (int i = 0; i < 4; i++) mk[i] = (4 * tid + i >= c_lo && 4 * tid + i < c_hi) ? 0xFFFFu : 0u;
+        colmask[tid] = make_uint2(mk[0] | (mk[2] << 16), mk[1] | (mk[3] << 16));
+    }
+    __syncthreads();
+    FC_STAMP(1);
+    if (tid < P) {                                           // (read after the next barrier)
+        int ci = 255;
+#pragma unroll
+        for (int i = 0; i < ORB_BAND_CELLS; i++) if (i < bncells && tid >= bclo[i] && tid < bclo[i] + bcwd[i]) ci = i;
+        colcell[tid] = (uint8_t)ci;
+    }
+    unsigned short* wsurv = surv + wv * WCAP;
+    // ---- rejection + scoring, WAVE-LOCAL (round 3): a wave tests its own runs of 64 items (4 pixels per lane), pushes the survivors on
+    // its own stack in LDS, and scores them 64 at a time -- a full wave per 130-instruction score -- as soon as 64 are waiting.  No
+    // workgroup barrier until every pixel of the band is scored: round 2 pooled the survivors of a row block over the four waves
+    // (two barriers per row block, and every wave waited for the slowest at each of them).  The stack never holds more than
+    // 63 + 256 entries.  The order in which pixels are scored does not matter: the NMS below works on the set.
+    auto score_at = [&](int pos) {
+        const uint8_t* c = T + pos;
+        const int v = c[0];
+        int r[16];
+        r[0] = c[3 * P];      r[1] = c[3 * P + 1];  r[2] = c[2 * P + 2];  r[3] = c[P + 3];
+        r[4] = c[3];          r[5] = c[-P + 3];     r[6] = c[-2 * P + 2]; r[7] = c[-3 * P + 1];
+        r[8] = c[-3 * P];     r[9] = c[-3 * P - 1]; r[10] = c[-2 * P - 2]; r[11] = c[-P - 3];
+        r[12] = c[-3];        r[13] = c[P - 3];     r[14] = c[2 * P - 2]; r[15] = c[3 * P - 1];
+        const int sc = fast_score16(v, r);
+        if (sc >= t_lo && sc > 0) {
+            S[pos] = (uint8_t)sc;
+            const int q = atomicAdd(nsurv + 1, 1);
+            if (q < FC_NZ) nz[q] = (unsigned short)pos;
+        }
+    };
+    {
+        int wcnt = 0;                                          // entries on this wave's stack (wave-uniform)
+        const int items = (bh - 6) * PW;
+        constexpr int r0 = 3;
+        for (int it0 = wv * 64; it0 < items; it0 += FC_TPB) {
+            const int it = it0 + lane;
+            const int rr = (int)(((unsigned)it * pw_inv) >> 20);
+            const int dw = it - rr * PW;                        // the item: pixels px .. px + 3, px = 4 * dw, of row = r0 + rr
+            unsigned kk0 = 0, kk1 = 0;                          // 16-bit halves, .lo/.hi of kk0 = pixels 0 / 2, of kk1 = pixels 1 / 3
+            if (it < items && dw >= dw_lo && dw <= dw_hi) {
+                // P == 4 * PW: the centre dword of item `it` sits at byte r0 * P + 4 * it
+                const unsigned* crow = reinterpret_cast<const unsigned*>(T + r0 * P) + it;
+                const unsigned c0 = crow[-1], c1 = crow[0], c2 = crow[1];
+                const unsigned nn = crow[3 * PW], ss = crow[-3 * PW];
+                const unsigned ww = __builtin_amdgcn_alignbyte(c1, c0, 1);        // columns px-3 .. px
+                const unsigned ee = __builtin_amdgcn_alignbyte(c2, c1, 3);        // columns px+3 .. px+6
+                const fc_us2 tt = fc_pk((unsigned)t_lo * 0x00010001u);
+                unsigned kk[2];
+#pragma unroll
+                for (int h = 0; h < 2; h++) {                                     // h = 0: pixels 0 and 2; h = 1: pixels 1 and 3
+                    const unsigned sel = h ? 0x0c030c01u : 0x0c020c00u;           // v_perm_b32: two bytes -> two u16
+                    const fc_us2 v = fc_pk(__builtin_amdgcn_perm(0u, c1, sel));
+                    const fc_us2 n = fc_pk(__builtin_amdgcn_perm(0u, nn, sel)), sq = fc_pk(__builtin_amdgcn_perm(0u, ss, sel));
+                    const fc_us2 w = fc_pk(__builtin_amdgcn_perm(0u, ww, sel)), e = fc_pk(__builtin_amdgcn_perm(0u, ee, sel));
+                    // every 9-arc holds ring pixel k or k+8: a corner brighter (darker) than v by more than t needs the
+                    // larger (smaller) of BOTH opposite pairs beyond v + t (v - t)
+                    const fc_us2 bm = __builtin_elementwise_min(__builtin_elementwise_max(n, sq), __builtin_elementwise_max(e, w));
+                    const fc_us2 dm = __builtin_elementwise_max(__builtin_elementwise_min(n, sq), __builtin_elementwise_min(e, w));
+                    kk[h] = fc_u(__builtin_elementwise_sub_sat(bm, (fc_us2)(v + tt))) | fc_u(__builtin_elementwise_sub_sat(__builtin_elementwise_sub_sat(v, tt), dm));
+                }
+                const uint2 cm = colmask[dw];
+                kk0 = kk[0] & cm.x; kk1 = kk[1] & cm.y;
+            }
+            // survivor predicates of the lane's four pixels: one 16-bit compare each
+            const bool k0 = (kk0 & 0xFFFFu) != 0u, k1 = (kk1 & 0xFFFFu) != 0u;
+            const bool k2 = (kk0 >> 16) != 0u, k3 = (kk1 >> 16) != 0u;
+            const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1), m2 = __ballot(k2), m3 = __ballot(k3);
+            if ((m0 | m1 | m2 | m3) != 0ull) {
+                // stack slot of the lane's pixel i among the wave's survivors of this item: pixels 0 of all lanes first, then
+                // pixels 1, ...; v_mbcnt adds the count of lower lanes to the running base
+                const int b1 = wcnt + __popcll(m0), b2 = b1 + __popcll(m1), b3 = b2 + __popcll(m2);
+                const int pos0 = r0 * P + 4 * it;                  // == row * P + px, as P == 4 * PW
+                if (k0) wsurv[fc_mbcnt(m0, wcnt)] = (unsigned short)pos0;
+                if (k1) wsurv[fc_mbcnt(m1, b1)] = (unsigned short)(pos0 + 1);
+                if (k2) wsurv[fc_mbcnt(m2, b2)] = (unsigned short)(pos0 + 2);
+                if (k3) wsurv[fc_mbcnt(m3, b3)] = (unsigned short)(pos0 + 3);
+                wcnt = b3 + __popcll(m3);
+                // the LDS operations of one wave complete in order; the fence keeps the compiler from moving the pops above the pushes
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                while (wcnt >= 64) { wcnt -= 64; score_at(wsurv[wcnt + lane]); }
+            }
+        }
+        if (lane < wcnt) score_at(wsurv[lane]);
+    }
+    __syncthreads();
+    FC_STAMP(2);
+    // ---- NMS on the list of scored pixels.  With minThFAST <= iniThFAST every stored score is >= minThFAST, so
+    // "keep at threshold th" == score >= th and strictly greater than every neighbour inside the cell's rectangle.
+    const int nnz = nsurv[1];
+    const int rh = bh - 6;
+    bool listed = g.min_th <= g.ini_th && nnz <= FC_NZ && bncells <= ORB_BAND_CELLS;
+    if (listed) {
+        // the local maxima go to one bucket of `kept` per cell, so that the row-major rank of a keypoint inside its
+        // cell only scans the maxima of that cell (a fifth of the band's on the EuRoC-shaped frames)
+        const int cap_c = ((FC_KEPT / max(bncells, 1)) - 1) | 1;      // odd: the buckets start in different LDS banks
+        const unsigned p_inv = 0xFFFFFFFFu / (unsigned)P + 1u;           // pos / P == mulhi(pos, p_inv) for pos < 2^16 and every pitch 16..256 (checked exhaustively)
+        for (int e = tid; e < nnz; e += FC_TPB) {
+            const int pos = nz[e];
+            const int row = (int)__umulhi((unsigned)pos, p_inv), col = pos - row * P;
+            // the score, its eight neighbours and the column's cell are read together (one LDS round trip; the tile has a 3-pixel
+            // margin around every detection pixel) and the neighbours outside the cell's rectangle masked afterwards: no
+            // short-circuit chain of dependent LDS reads
+            const uint8_t* p = S + pos;
+            const int ci = colcell[col];
+            const int sc = p[0];
+            const int nl = p[-1], nr = p[1], nul = p[-P - 1], nu = p[-P], nur = p[-P + 1], ndl = p[P - 1], nd = p[P], ndr = p[P + 1];
+            __builtin_amdgcn_sched_barrier(0);
+            if (ci == 255) continue;
+            const int xx = col - l_clo[ci], yy = row - 3, rw = l_cwd[ci];
+            const bool l = xx > 0, r = xx + 1 < rw, u = yy > 0, d = yy + 1 < rh;
+#define NB(c, v) ((c) ? (v) : 0)
+            const bool keep = (sc > NB(l, nl)) & (sc > NB(r, nr)) &
+                              (sc > NB(u && l, nul)) & (sc > NB(u, nu)) & (sc > NB(u && r, nur)) &
+                              (sc > NB(d && l, ndl)) & (sc > NB(d, nd)) & (sc > NB(d && r, ndr));
+#undef NB
+            if (keep) {
+                const int q = atomicAdd(cell_k + ci, 1);
+                if (q < cap_c) kept[ci * cap_c + q] = ((unsigned)yy << 14) | ((unsigned)xx << 8) | (unsigned)sc;
+                if (sc >= g.ini_th) atomicAdd(cell_hi + ci, 1);
+            }
+        }
+        __syncthreads();
+        FC_STAMP(3);
+        // (cell_k of the cells the band does not have is 0)
+        const int4 ck = *reinterpret_cast<const int4*>(cell_k);
+        const int e1 = ck.x, e2 = e1 + ck.y, e3 = e2 + ck.z, nk = e3 + ck.w;
+        listed = max(max(ck.x, ck.y), max(ck.z, ck.w)) <= cap_c;
+        if (listed) {
+            // a cell's count = its local maxima at the chosen threshold.  Every bucket entry is >= minThFAST (stored scores are
+            // >= t_lo == minThFAST here) and cell_hi counts those >= iniThFAST, so the count is cell_hi where the cell has any such
+            // maximum (threshold iniThFAST) and the whole bucket otherwise (threshold minThFAST); no bucket overflowed on this path.
+            // (Until round 3 an atomic per keypoint and a barrier before the store; then one thread per cell scanning its bucket.)
+            if (tid >= FC_TPB - FC_CELLS && FC_TPB - 1 - tid < bncells) {
+                const int ci = FC_TPB - 1 - tid;
+                const int hi = cell_hi[ci];
+                cell_count[(long long)f * g.ncells + bcfirst + ci] = hi > 0 ? hi : cell_k[ci];
+            }
+            for (int e = tid; e < nk; e += FC_TPB) {
+                const int ci = (e >= e1 ? 1 : 0) + (e >= e2 ? 1 : 0) + (e >= e3 ? 1 : 0);
+                const int k0 = e - (ci == 0 ? 0 : ci == 1 ? e1 : ci == 2 ? e2 : e3);
+                const unsigned* bucket = kept + ci * cap_c;
+                const int nb = ci == 0 ? ck.x : ci == 1 ? ck.y : ci == 2 ? ck.z : ck.w;
+                const unsigned me = bucket[k0];
+                const unsigned th = (unsigned)(cell_hi[ci] > 0 ? g.ini_th : g.min_th);      // :978-984: ini first, else min
+                if ((me & 255u) < th) continue;
+                int rank = 0;                                                             // row-major order inside the cell
+                for (int k = 0; k < nb; k++) {
+                    const unsigned o = bucket[k];
+                    rank += ((o & 255u) >= th && (o >> 8) < (me >> 8)) ? 1 : 0;
+                }
+                if (rank < l_scap[ci])
+                    slots[(long long)f * g.slots_per_frame + l_sfirst[ci] + rank] =
+                        ((me & 255u) << 24) | ((unsigned)(by0 + 3 - ORB_BORDER + (int)((me >> 14) & 63u)) << 12) |
+                        (unsigned)(bxa + l_clo[ci] - ORB_BORDER + (int)((me >> 8) & 63u));
+            }
+            FC_STAMP(4);
+            return;
+        }
+    }
+    // ---- per cell: threshold choice, strict 3x3 NMS inside the cell's detection rectangle, ordered compaction
+    for (int ci = wv; ci < B.ncells; ci += FC_TPB / 64) {
+        const OrbCell c = cells[B.cell_first + ci];
+        const int rw = c.cw - 6, rh = c.ch - 6;
+        int* count_out = cell_count + (long long)f * g.ncells + B.cell_first + ci;
+        if (rw <= 0 || rh <= 0) { if (lane == 0) *count_out = 0; continue; }
+        const uint8_t* S0 = S + 3 * P + (c.x0 + 3 - B.xa);                    // score of the rectangle's first pixel
+        unsigned* out = slots + (long long)f * g.slots_per_frame + c.slot_first;
+        const int relx = c.x0 + 3 - ORB_BORDER, rely = c.y0 + 3 - ORB_BORDER;
+        const int rpi = rw <= 32 ? 2 : 1;
+        const int xx = rpi == 2 ? (lane & 31) : lane, yoff = rpi == 2 ? (lane >> 5) : 0;
+        int n = 0;
+        for (int attempt = 0; attempt < 2 && n == 0; attempt++) {
+            const int th = attempt == 0 ? g.ini_th : g.min_th;
+            for (int y0 = 0; y0 < rh; y0 += rpi) {
+                const int yy = y0 + yoff;
+                const bool in = yy < rh && xx < rw;
+                const uint8_t* p = S0 + min(yy, rh - 1) * P + min(xx, rw - 1);
+                const int s = in ? p[0] : 0;
+                if (__ballot(s >= th && s > 0) == 0ull) continue;              // most rows hold no corner
+                bool keep = false;
+                if (s >= th && s > 0) {
+                    // neighbours outside the cell's rectangle, and scores below the threshold, count as 0
+                    const bool l = xx > 0, r = xx + 1 < rw, u = yy > 0, d = yy + 1 < rh;
+#define NB(c, o) ((c) && (int)p[o] >= th ? (int)p[o] : 0)
+                    keep = s > NB(l, -1) && s > NB(r, 1) &&
+                           s > NB(u && l, -P - 1) && s > NB(u, -P) && s > NB(u && r, -P + 1) &&
+                           s > NB(d && l, P - 1) && s > NB(d, P) && s > NB(d && r, P + 1);
+#undef NB
+                }
+                const unsigned long long m = __ballot(keep);
+                if (keep) {
+                    const int pos = n + __popcll(m & lanemask_lt());
+                    if (pos < c.slot_cap)
+                        out[pos] = ((unsigned)s << 24) | ((unsigned)(rely + yy) << 12) | (unsigned)(relx + xx);
+                }
+                n += __popcll(m);
+            }
+        }
+        if (lane == 0) *count_out = n;
+    }
+}
+
+void orb_launch_fast_cells(hipStream_t s, const OrbGeom& g_dev, const OrbCell* cells, const OrbBand* bands, int nbands, int nframes,
+                           size_t lds_bytes, unsigned* slots, int* cell_count, int* clear_status)
+{
+    // default 0 for this kernel: co-locating neighbouring bands on one XCD cuts its fabric reads 2.2x (285 -> 128 MiB per launch, = the
+    // algorithmic bytes) but the kernel, which is not bandwidth-bound, runs 3-5 % slower with every co-locating order tried
+    // (profiles/r02_xcd_order.txt); k_orient_desc gains from it and uses it
+    static const int xcd_on = getenv("CCM_ORB_XCD") ? atoi(getenv("CCM_ORB_XCD")) : 0;
+    hipLaunchKernelGGL(k_fast_cells, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, g_dev, cells, bands, slots, cell_count, clear_status, xcd_on);
+}
+size_t orb_fast_cells_lds(int pitch, int bh) { return fc_lds_bytes(pitch, bh); }

@@ -82,7 +82,7 @@ struct OrbState {
     OrbTables tab{};
     OrbGeom geom{};
     std::vector<OrbCell> cells;
-    std::vector<OrbBand> bands; size_t band_lds = 0; bool fused = true; int surv_cap = 1024; hipStream_t copy_stream = nullptr; hipEvent_t copy_done = nullptr;
+    std::vector<OrbBand> bands; size_t band_lds = 0; bool fused = true; hipStream_t copy_stream = nullptr; hipEvent_t copy_done = nullptr;
     hipStream_t down_stream = nullptr; hipEvent_t chunk_done = nullptr;      // results of a chunk go down while the next chunk is extracted
     DevBuf geom_dev, cells_dev, tables_dev, bands_dev;
     DevBuf pyr, smap, slots, cell_count, keysA, keysB, sel, sel_count, status;
@@ -199,9 +199,7 @@ static int orb_prepare(ccm_ctx* c, const ccm_orb_params* p, int w, int h, int nf
     S.bands.clear(); S.band_lds = 0;
     static const bool want_fused = !(getenv("CCM_ORB_FUSED") && atoi(getenv("CCM_ORB_FUSED")) == 0);
     S.fused = want_fused;
-    static const int pcap = getenv("CCM_FC_PCAP") ? std::min(atoi(getenv("CCM_FC_PCAP")), 256) : 144;   // measured: 112 0.576, 128 0.558, 144 0.532, 160 0.574 ms      // pitch <= 256: one dword per lane
-    static const int scap = getenv("CCM_FC_SURV") ? atoi(getenv("CCM_FC_SURV")) : 3072;      // two row blocks per 30-row band (measured best)
-    S.surv_cap = scap;
+    constexpr int pcap = 144;   // largest LDS pitch of a band of several cells (measured: 112 0.576, 128 0.558, 144 0.532, 160 0.574 ms)
     for (size_t a = 0; a < S.cells.size();) {
         size_t b = a;
         const OrbCell& c0 = S.cells[a];
@@ -229,11 +227,10 @@ static int orb_prepare(ccm_ctx* c, const ccm_orb_params* p, int w, int h, int nf
             }
         }
         for (size_t k = a; k < b; k++) if (S.cells[k].ch != c0.ch) S.fused = false;      // cannot happen: one row, one height
-        S.surv_cap = std::max(S.surv_cap, pitch);                 // at least one row per block
         S.bands.push_back(band);
         a = b;
     }
-    for (const OrbBand& b : S.bands) S.band_lds = std::max(S.band_lds, orb_fast_cells_lds(b.pitch, b.bh, S.surv_cap));
+    for (const OrbBand& b : S.bands) S.band_lds = std::max(S.band_lds, orb_fast_cells_lds(b.pitch, b.bh));
     for (const OrbBand& b : S.bands) if (b.pitch > 256) S.fused = false;    // a single cell wider than the tile: two-kernel path
     if (S.band_lds > 60 * 1024) S.fused = false;                 // very large cells: keep the two-kernel path
     G.ncells = (int)S.cells.size(); G.ntiles = tile_acc;
@@ -316,7 +313,7 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
     }
     if (S.fused && !S.bands.empty()) {
         ProfScope ps(c, CCM_PROF_FAST_SCORE);
-        orb_launch_fast_cells(st, gd, cd, S.bands_dev.as<OrbBand>(), (int)S.bands.size(), nrun, S.band_lds, S.surv_cap, S.slots.as<unsigned>(), S.cell_count.as<int>(), clear);
+        orb_launch_fast_cells(st, gd, cd, S.bands_dev.as<OrbBand>(), (int)S.bands.size(), nrun, S.band_lds, S.slots.as<unsigned>(), S.cell_count.as<int>(), clear);
     } else {
         if (clear) CCM_HIP(c, hipMemsetAsync(clear, 0, 4, st));          // (one level through the two-kernel FAST path: not worth a kernel argument)
         { ProfScope ps(c, CCM_PROF_FAST_SCORE); orb_launch_score(st, gd, G.ntiles, nrun); }

@@ -1,4 +1,13 @@
-// orb_types.h -- device-visible geometry tables of the ORB pipeline and the launchers of orb_kernels.hip, shared with orb_host.cpp.
+// orb_types.h -- device-visible geometry tables of the ORB pipeline and the launchers of its CDNA4 (gfx950) kernels, shared with orb_host.cpp.
+//
+// Pipeline per batch (all frames of the batch in every launch), one file per stage:
+//   orb_pyramid.hip      k_pyr_resize  x (nlevels-1)   cv::resize INTER_LINEAR 8u                                ORBextractor.cpp:1293
+//   orb_fast_cells.hip   k_fast_cells                  FAST-9/16 score + per-cell threshold choice + 3x3 NMS,    :957-998, :978-984 (cv::FAST)
+//                                                      fused on cell-row bands (scores stay in LDS)
+//   orb_fast_tiles.hip   k_fast_score + k_cell_nms     the same in two kernels through a score map, for cells wider than one LDS tile
+//   orb_octree.hip       k_octree                      DistributeOctTree                                         :707-931
+//   orb_orient_desc.hip  k_orient_desc                 IC_Angle + 7x7 blur + rBRIEF                              :68-95, :1259, :100-316
+// orb_device.h holds the device helpers that more than one stage uses.  Wavefront = 64 everywhere; ballots are 64-bit.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -81,8 +90,8 @@ void orb_launch_resize(hipStream_t, const OrbGeom&, int level, int dw, int dh, i
 void orb_launch_score(hipStream_t, const OrbGeom&, int ntiles, int nframes);
 void orb_launch_nms(hipStream_t, const OrbGeom&, const OrbCell*, int ncells, int nframes, unsigned* slots, int* cell_count);
 void orb_launch_fast_cells(hipStream_t, const OrbGeom&, const OrbCell*, const OrbBand*, int nbands, int nframes, size_t lds_bytes,
-                           int surv_cap, unsigned* slots, int* cell_count, int* clear_status);
-size_t orb_fast_cells_lds(int pitch, int bh, int surv_cap);
+                           unsigned* slots, int* cell_count, int* clear_status);
+size_t orb_fast_cells_lds(int pitch, int bh);
 void orb_launch_octree(hipStream_t, const OrbGeom&, const OrbCell*, int nlevels, int nframes, int list_cap,
                        const unsigned* slots, const int* cell_count, unsigned* keysA, unsigned* keysB,
                        unsigned* out, int* out_count, int* status);

@@ -94,7 +94,7 @@ def _geometry(case):
 
 
 def _staging_path(base, pitch, w):
-    """The level-0 staging path k_fast_cells / k_fast_score take for a frame at `base` (orb_kernels.hip: dword_ok)."""
+    """The level-0 staging path k_fast_cells / k_fast_score take for a frame at `base` (orb_fast_cells.hip, orb_fast_tiles.hip: dword_ok)."""
     return "dword" if ((base | pitch) & 3) == 0 and pitch >= ((w + 3) & ~3) else "byte"
 
 
@@ -198,7 +198,7 @@ def test_extract_dev_layouts(ctx, oracle, case):
 
 # ------------------------------------------------------------------------------------------------- 3./4. switches in child processes
 def _od_items(ex, w, h, nframes):
-    """(workgroups, slots per wave) of k_orient_desc: its grid is out_per_frame / (4 waves * slots) x frames (orb_kernels.hip)."""
+    """(workgroups, slots per wave) of k_orient_desc: its grid is out_per_frame / (4 waves * slots) x frames (orb_orient_desc.hip)."""
     lw, lh = ex.level_sizes(w, h)
     opf = 0
     for l in range(ex.GetLevels()):

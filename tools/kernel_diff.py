@@ -5,7 +5,7 @@ usage: tools/kernel_diff.py OLD_CSRC NEW_CSRC [--map OLD_MANGLED=NEW_MANGLED ...
 
 Every .hip of each tree is compiled with the Makefile's flags, device side only.  Kernels are matched by mangled name, whichever
 file they live in (--map pairs a kernel whose template signature changed); rocPRIM's are ignored.  Prints one line per kernel --
-identical or different, with its resource metadata -- and the kernels present on one side only (the first differing lines of a
+identical or different, with its resource metadata and instruction count -- and the kernels present on one side only (the first differing lines of a
 kernel go to stderr); exits 1 on any difference."""
 import difflib
 import os
@@ -32,13 +32,20 @@ def kernels_of(src, tmp):
         entry = "  - .agpr_count:" + entry
         name = re.search(r"^\s+\.name:\s+(\S+)", entry, re.M).group(1)
         meta[name] = {k: int(re.search(r"\s" + re.escape(k) + r":\s+(\d+)", entry).group(1)) for k in META}
-    text, cur = {}, None
+    text, cur, pcrel = {}, None, 0
     for line in subprocess.check_output([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", obj], text=True).splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
         if m:
             cur = text.setdefault(m.group(1), []) if m.group(1) in meta else None
         elif cur is not None and line.strip():
-            cur.append(re.sub(r"\s*//.*$", "", line).strip())           # "// addr: <sym+off>" trailers off; addresses are in them only
+            ins = re.sub(r"\s*//.*$", "", line).strip()                  # "// addr: <sym+off>" trailers off: addresses are in them ...
+            # ... and in the distance from the kernel to a global (__constant__ table) that the two adds behind s_getpc_b64 carry:
+            # it changes with the other code of the file, not with the kernel
+            if pcrel and re.match(r"s_addc?_u32 ", ins):
+                ins, pcrel = re.sub(r",\s*\S+$", ", <pc-relative>", ins), pcrel - 1
+            else:
+                pcrel = 2 if ins.startswith("s_getpc_b64") else 0
+            cur.append(ins)
     for lines in text.values():                                          # the padding behind a file's last kernel is not its code
         while lines and lines[-1] in ("s_nop 0", "s_code_end", "..."):
             lines.pop()
@@ -72,7 +79,8 @@ def main():
         same = ta == tb and ma == mb
         differ += not same
         fmt = lambda m: " ".join("%s=%d" % (q.strip(".").replace("_count", "").replace("_segment_fixed_size", "").replace("_segment_size", "").replace("_flat_workgroup_size", "_wg"), m[q]) for q in META)
-        print("%-9s %-34s %s -> %s  %s" % ("identical" if same else "DIFFERENT", short(k), fa, fb, fmt(mb) if ma == mb else fmt(ma) + "  ->  " + fmt(mb)))
+        insts = "insts=%d" % len(tb) if len(ta) == len(tb) else "insts=%d -> %d" % (len(ta), len(tb))
+        print("%-9s %-34s %s -> %s  %s %s" % ("identical" if same else "DIFFERENT", short(k), fa, fb, fmt(mb) if ma == mb else fmt(ma) + "  ->  " + fmt(mb), insts))
         if ta != tb:
             for d in list(difflib.unified_diff(ta, tb, "old", "new", n=0, lineterm=""))[2:42]:
                 print("          " + d, file=sys.stderr)

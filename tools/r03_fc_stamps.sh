@@ -2,7 +2,7 @@
 # Run on the GPU box from the repo root: tools/r03_fc_stamps.sh TAG -- where does a band of k_fast_cells spend its ~14 us?
 # Diagnostic build (-DFC_STAMPS): s_memtime of wave 0 (slots 0-7) and of the last wave (slots 8-15) at the phase boundaries of every workgroup of one 256-frame launch.
 tag=$1; O=gpurun_out; mkdir -p $O
-touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip
+touch motioncheck_ccm_slam_amd/csrc/orb_fast_cells.hip
 make -s -C motioncheck_ccm_slam_amd/csrc EXTRA="-DFC_STAMPS" > $O/${tag}_stamps.build 2>&1 || { tail -5 $O/${tag}_stamps.build; exit 1; }
 timeout -k 10 200 python3 - > $O/${tag}_fc_stamps.txt 2>&1 <<'PY'
 import ctypes as C, numpy as np, sys, os
@@ -39,4 +39,4 @@ for nm, (a, c) in zip(names, seq):
 print("workgroup start (wave 0) -> last wave's end: median %.0f  mean %.0f" % (np.median(b[:, 12] - b[:, 0]), (b[:, 12] - b[:, 0]).mean()))
 PY
 cat $O/${tag}_fc_stamps.txt
-touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip; make -s -C motioncheck_ccm_slam_amd/csrc > /dev/null 2>&1
+touch motioncheck_ccm_slam_amd/csrc/orb_fast_cells.hip; make -s -C motioncheck_ccm_slam_amd/csrc > /dev/null 2>&1

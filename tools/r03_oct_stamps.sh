@@ -2,7 +2,7 @@
 # Run on the GPU box from the repo root: tools/r03_oct_stamps.sh -- where does the level-0 quadtree of one frame spend its ~100 us?
 # Diagnostic build (-DOCT_STAMPS): s_memtime of thread 0 of the (frame 0, level 0) workgroup at its phase boundaries, one 256-frame launch.
 O=gpurun_out; mkdir -p $O
-touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip
+touch motioncheck_ccm_slam_amd/csrc/orb_octree.hip
 make -s -C motioncheck_ccm_slam_amd/csrc EXTRA="-DOCT_STAMPS" > $O/oct_stamps.build 2>&1 || { tail -5 $O/oct_stamps.build; exit 1; }
 timeout -k 10 200 python3 - <<'PY'
 import ctypes as C, numpy as np, sys, os
@@ -28,4 +28,4 @@ while i + 2 < k:
     print("pass %d: partition %d, order %d, new list %d" % (p, t[i] - t[i - 1], t[i + 1] - t[i], t[i + 2] - t[i + 1])); i += 3; p += 1
 print("final selection %d" % (t[k - 1] - t[k - 2]))
 PY
-touch motioncheck_ccm_slam_amd/csrc/orb_kernels.hip; make -s -C motioncheck_ccm_slam_amd/csrc > /dev/null 2>&1
+touch motioncheck_ccm_slam_amd/csrc/orb_octree.hip; make -s -C motioncheck_ccm_slam_amd/csrc > /dev/null 2>&1

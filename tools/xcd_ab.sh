@@ -10,6 +10,6 @@ import json
 l=[q for q in open("$O/xcd_$x.log") if q.startswith("{")]
 j=json.loads(l[-1]); k=j["kernels"]
 f={r.split()[0]: float(r.split()[2]) for r in open("$O/xcd_fetch_$x.txt") if "FETCH_SIZE" in r}
-print("XCD=%s value=%.1f ms/step=%.4f fast_cells=%.4f ms (fetch %.0f MiB) orient_desc=%.4f ms (fetch %.0f MiB)" % ("$x", j["value"], j["ms_per_step"], k["k_fast_cells"]["ms_per_step"], f.get("k_fast_cells<true>",0)/1024, k["k_orient_desc"]["ms_per_step"], f.get("k_orient_desc",0)/1024))
+print("XCD=%s value=%.1f ms/step=%.4f fast_cells=%.4f ms (fetch %.0f MiB) orient_desc=%.4f ms (fetch %.0f MiB)" % ("$x", j["value"], j["ms_per_step"], k["k_fast_cells"]["ms_per_step"], f.get("k_fast_cells",0)/1024, k["k_orient_desc"]["ms_per_step"], f.get("k_orient_desc",0)/1024))
 PY
 done
