@@ -258,7 +258,7 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
     }
 
     // host acceptance (CCM_WINDOW_HOST_ACCEPT=1, or a frame too large for the single workgroup's LDS): lists to the host, the loops
-    // of match_host.cpp on the frame's octaves / angles fetched from the device, the new ids scattered on the device
+    // of match_window_host.cpp on the frame's octaves / angles fetched from the device, the new ids scattered on the device
     w.host_accept = true;
     std::vector<uint8_t> act_h, qflag_h;
     const uint8_t* h_act = w.h_act; const uint8_t* h_qflag = w.h_qflag;

@@ -11,7 +11,7 @@
 #include <cstdint>
 #include "frame_types.h"
 
-// PosInGrid (src/Frame.cpp:255-266) exactly as grid_build() in match_host.cpp: round() in float, half away from zero; features
+// PosInGrid (src/Frame.cpp:255-266) exactly as grid_build() in match_window_host.cpp: round() in float, half away from zero; features
 // outside the grid get no cell.  A NaN coordinate gets none either (x86's conversion gives INT_MIN, the device's 0).
 __device__ inline int fb_cell(const FrameBuildArgs& A, float x, float y)
 {

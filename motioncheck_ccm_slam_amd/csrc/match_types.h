@@ -1,12 +1,25 @@
-// match_types.h -- kernel argument structures, launch constants and launchers of match_kernels.hip, shared with the host
-// translation units that launch into it (match_host.cpp, frame_host.cpp, mpt_host.cpp; through window_types.h).
+// match_types.h -- kernel argument structures, launch constants and launchers of the matcher's CDNA4 (gfx950) kernels, shared with the
+// host translation units that launch into them (match_*_host.cpp, frame_host.cpp, mpt_host.cpp; through window_types.h).
+//
+// 256-bit Hamming matching, one file per kernel family:
+//   match_bf.hip      k_hamming_mfma    brute-force best / second-best per query on the matrix cores (<= 2048 train rows per pair):
+//                                       bits as FP4 operands of the block-scaled matrix instruction
+//                     k_hamming_bf      the same on the vector ALU (any size): inner loop of ORBmatcher::SearchByBoW,
+//                     + k_hamming_merge cslam/src/ORBmatcher.cpp:224-245, with every feature in one vocabulary node
+//                     k_hamming_ranges  distances of each side-1 feature to its vocabulary node's side-2 features (the
+//                                       DescriptorDistance calls of SearchByBoW / SearchForTriangulation; acceptance on the host)
+//   match_bow.hip     k_bow_greedy, k_bow_filter (+ _batch, k_bow_groups, k_bow_invert on frame handles)   SearchByBoW, :178-306, :565-698
+//   match_window.hip  k_window_candidates, k_window_select, k_window_greedy   Frame::GetFeaturesInArea and the acceptance of
+//                                       SearchByProjection / Fuse / SearchBySim3, :71-148 and following
+// match_device.h holds the device helpers that more than one of them uses.  The host side is split the same way (match_bf_host.cpp,
+// match_bow_host.cpp, match_window_host.cpp; shared state in match_internal.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <hip/hip_runtime.h>
 
 void match_launch_bf(hipStream_t, const uint8_t* q, long long q_pair_bytes, const uint8_t* t, long long t_pair_bytes,
-                     int nq, int nt, int n_pairs, const int* nq_n, const int* nt_n, int n_split, int variant,
+                     int nq, int nt, int n_pairs, const int* nq_n, const int* nt_n, int n_split,
                      unsigned* part_best, int* part_second, int* bi, int* bd, int* sd);
 void match_launch_ranges(hipStream_t, const uint8_t* d1, const uint8_t* d2, const int* order2, const int* start,
                          const int* len, const long long* off, int n1, unsigned short* dist);

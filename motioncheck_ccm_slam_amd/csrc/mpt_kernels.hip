@@ -11,7 +11,7 @@
 //   k_fuse_where / k_fuse_held / k_fuse_project / k_fuse_scatter
 //                      ccm_fuse_select_table_frames: the projection and the gates of ORBmatcher::Fuse, both overloads
 //                      (src/ORBmatcher.cpp:870-920, :1018-1071), for every (keyframe, point) pair; the survivors become the
-//                      queries of k_window_select (match_kernels.hip)
+//                      queries of k_window_select (match_window.hip)
 //   k_tmm_project / k_tmm_clear / k_tmm_discard
 //                      ccm_frame_track_motion_model: the queries of SearchByProjection(Current, Last) from the last frame's ids
 //                      (src/ORBmatcher.cpp:1374-1396), the clear before each pass and "discard outliers" (src/Tracking.cpp:599-618)
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(SCAN_TPB) void k_slp_scan(int n_wg, const int* wg_c
 }
 
 // Entry j in view goes to k = wg_off[b] + (entries in view of the workgroup's earlier waves) + (earlier lanes of its wave): list order
-// is kept.  Query set-up exactly as window_queries_projection() (match_host.cpp; ORBmatcher.cpp:97-107, RadiusByViewingCos :150-156).
+// is kept.  Query set-up exactly as window_queries_projection() (match_window_host.cpp; ORBmatcher.cpp:97-107, RadiusByViewingCos :150-156).
 __global__ __launch_bounds__(SLP_TPB) void k_slp_compact(SlpArgs A, MptTable T)
 {
     const int j = blockIdx.x * SLP_TPB + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

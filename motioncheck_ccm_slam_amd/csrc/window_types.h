@@ -1,4 +1,4 @@
-// window_types.h -- the host side of the windowed matchers, shared by the host translation units that drive them: match_host.cpp
+// window_types.h -- the host side of the windowed matchers, shared by the host translation units that drive them: match_window_host.cpp
 // (host arrays per call) and frame_host.cpp / mpt_host.cpp (frame handles).  The device structures and launchers are match_types.h.
 #pragma once
 #include <vector>

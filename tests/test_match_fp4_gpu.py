@@ -1,17 +1,9 @@
-"""The matrix-core Hamming matcher in both of its forms -- FP4 operands through the block-scaled matrix instruction, and int8 --
-against the CPU oracle, bit for bit, and a known-answer test of the FP4 tile itself.
-
-The form is chosen by CCM_BF_VARIANT (3 = what ships, 4 = int8, 5 = FP4), which the library reads once per process: every form runs
-`run_cases` below in a child process of its own."""
-import os
-import subprocess
-import sys
-
+"""The matrix-core Hamming matcher -- FP4 operands through the block-scaled matrix instruction -- against the CPU oracle, bit for
+bit, and a known-answer test of the FP4 tile itself."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def _bits(d):
@@ -87,12 +79,9 @@ def _check(m, oracle, q, t, nq_n=None, nt_n=None):
     return bi, bd, sd
 
 
-def run_cases():
-    """Best index, best distance and second distance EXACTLY as the oracle's hamming_match, on the library this process loaded."""
-    from motioncheck_ccm_slam_amd import _lib
+def run_cases(ctx, oracle):
+    """Best index, best distance and second distance EXACTLY as the oracle's hamming_match."""
     from motioncheck_ccm_slam_amd.matcher import ORBmatcher
-    from oracle import oracle_py as oracle
-    ctx = _lib.Context(0)
     m = ORBmatcher(ctx=ctx)
     rng = np.random.default_rng(2024)
     rand = lambda *shape: rng.integers(0, 256, shape + (32,), dtype=np.uint8)
@@ -154,16 +143,7 @@ def run_cases():
                 t[p, next(slot)] = d2
     bi, bd, sd = _check(m, oracle, q, t)
     assert (bd[:, ::3] < 40).mean() > 0.9
-    ctx.close()
-    print("ok")
 
 
-@pytest.mark.parametrize("variant", ["3", "4", "5"])
-def test_matrix_core_forms_match_oracle_exactly(variant):
-    """3 = the kernel that ships, 4 = int8 operands, 5 = FP4 operands."""
-    root = os.path.dirname(HERE)
-    code = "import sys; sys.path.insert(0, %r); import test_match_fp4_gpu as T; T.run_cases()" % HERE
-    env = dict(os.environ, PYTHONPATH=root, CCM_BF_VARIANT=variant)
-    env.pop("CCM_BF_SPLIT", None)
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr[-3000:]
+def test_matrix_core_matcher_matches_oracle_exactly(ctx, oracle):
+    run_cases(ctx, oracle)

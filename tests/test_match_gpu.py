@@ -73,6 +73,37 @@ def test_ragged_counts_below_2048_trains(ctx, oracle):
     assert (sd[2, :1] == 256).all() and (bi[4, :700] == -1).all()
 
 
+def test_vector_alu_kernel_splits_and_unsplit(ctx, oracle):
+    """One train row past the matrix-core limit (2049: the third LDS tile of k_hamming_bf holds one row) at 1024, 512 and 256
+    pairs, where the split rule gives 1 (the unsplit write path), 2 and 4 workgroups per pair; ragged counts including empty sides;
+    a query duplicated at the last live train row and at an earlier one (other tile, other split): the lower index wins and
+    second == best.  Exact against the oracle for every live row, the defaults past the live counts."""
+    m = ORBmatcher(ctx=ctx)
+    rng = np.random.default_rng(7)
+    NP, NQ, NT = 1024, 5, 2049
+    q = rng.integers(0, 256, (NP, NQ, 32), dtype=np.uint8)
+    t = rng.integers(0, 256, (NP, NT, 32), dtype=np.uint8)
+    nt_n = rng.integers(0, NT + 1, NP); nq_n = rng.integers(0, NQ + 1, NP)
+    corner = [(a, b) for a in (2049, 2048, 1025, 1, 0) for b in (5, 1, 0)]               # every pairing, inside the 256-pair slice
+    nt_n[:len(corner)] = [a for a, b in corner]; nq_n[:len(corner)] = [b for a, b in corner]
+    planted = (nt_n >= 2) & (nq_n >= 1)
+    early = (nt_n - 1) // 2
+    for p in np.flatnonzero(planted):
+        t[p, nt_n[p] - 1] = q[p, 0]; t[p, early[p]] = q[p, 0]
+    assert planted[0] and early[0] == 1024 and planted[:256].sum() > 100
+    want = [oracle.hamming_match(q[p, :nq_n[p]], t[p, :nt_n[p]]) if nq_n[p] else None for p in range(NP)]
+    for n_pairs in (1024, 512, 256):
+        bi, bd, sd = m.BruteForce(q[:n_pairs], t[:n_pairs], nq_n[:n_pairs], nt_n[:n_pairs])
+        for p in range(n_pairs):
+            n = nq_n[p]
+            if n:
+                rbi, rbd, rsd = want[p]
+                assert (bi[p, :n] == rbi).all() and (bd[p, :n] == rbd).all() and (sd[p, :n] == rsd).all(), (n_pairs, p, n, nt_n[p])
+            assert (bi[p, n:] == -1).all() and (bd[p, n:] == 256).all() and (sd[p, n:] == 256).all(), (n_pairs, p)
+        sel = planted[:n_pairs]
+        assert (bi[:n_pairs, 0][sel] == early[:n_pairs][sel]).all() and (bd[:n_pairs, 0][sel] == 0).all() and (sd[:n_pairs, 0][sel] == 0).all()
+
+
 def test_many_pairs_property(ctx, oracle):
     """A 512-pair slice of config 3 through the host-buffer entry point (ORBmatcher.BruteForce): symmetric checks on all,
     oracle on a sample.  The full 10,000 pairs are the next test."""
