@@ -3,6 +3,10 @@
 The reference ships no tests or golden vectors and cannot be built here, so these are the
 constants and identities derivable from its source, plus the committed fixtures under
 tests/golden/ (made by tools/make_golden.py from the oracle itself, to catch drift).
+
+The oracle's OpenCV primitives (FAST with its score and NMS, the cell loop, resize, blur, IC_Angle,
+rotated BRIEF) are held to their published definitions in tests/test_orb_definitions_cpu.py, against
+tests/orb_definitions_ref.py; the FAST, packing and atan2 tests below predate it.
 """
 import numpy as np
 import pytest
