@@ -61,6 +61,11 @@ def test_search_by_projection(ctx, oracle, th):
                                                    view_cos, px, py, mp_desc, has_obs, occupied, th, 0.8)
     assert nm == rn and (match == rmatch).all() and (occ == rocc).all()
     assert nm > 300
+    if th == 3.0:                                                # and the definition restated from the reference's text, beside the oracle
+        import window_matcher_ref as R
+        dn, dmatch, docc = R.search_by_projection(R.Grid(fr.kx, fr.ky, fr.oct, desc), sf, in_view, level, view_cos, px, py, mp_desc, has_obs, occupied,
+                                                  th, 0.8)
+        assert nm == dn and (match == dmatch).all() and (occ == docc).all()
     good = match >= 0
     assert (match[good] < 1200).mean() > 0.95                   # matches go to the true correspondences
     # nothing in view -> nothing matched
