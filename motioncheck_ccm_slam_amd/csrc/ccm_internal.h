@@ -51,7 +51,7 @@ struct ccm_ctx {
     InitState* init = nullptr;                // monocular Initializer: staging and device buffers (init_host.cpp)
     MapState* map = nullptr;                  // CreateNewMapPoints: staging and device buffers (map_host.cpp)
     EssState* ess = nullptr;
-    FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_host.cpp)
+    FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_internal.h)
 };
 
 // grow-only device buffer; it owns its memory (freed with it), so it can be moved but not copied

@@ -1,8 +1,8 @@
-// frame_internal.h -- what the host translation units of the frame handles share: frame_host.cpp (the handles and their matchers)
-// and mpt_host.cpp (the map-point table and the calls that take a frame and a table).  The kernel argument structures and launchers
-// they use come from the kernel files' types headers.
+// frame_internal.h -- what the host translation units of the frame handles share: frame_host.cpp (the handles), frame_window_host.cpp
+// and frame_pose_host.cpp (their matchers and pose stage) and the mpt_*_host.cpp files (the map-point table and the calls that take a
+// frame and a table).  The kernel argument structures and launchers they use come from the kernel files' types headers.
 #pragma once
-#include "ccm_internal.h"
+#include "staging.h"
 #include "window_types.h"
 #include "frame_types.h"
 #include "pose_types.h"
@@ -47,11 +47,9 @@ struct FrameState {
     std::vector<FrameMem*> pool;                 // free blocks
     std::vector<FrameMem*> kf_pool;              // free blocks of keyframe parts
     std::vector<ccm_frame*> live;
-    DevBuf io;                                   // per-call device staging, [results | inputs]
-    uint8_t* host = nullptr; size_t host_cap = 0;  // page-locked, same layout as io
-    hipEvent_t host_free = nullptr; bool pending = false;   // recorded behind the last upload from `host`
+    Staging stage{ true };                       // per-call staging of every call on handles and tables; the setters leave uploads queued
     DevBuf ci, cd, cn, ev, pts, obs, info, err, outl, kof, first;
-    std::vector<struct ccm_map_table*> tables;   // map-point tables of this context (mpt_host.cpp)
+    std::vector<struct ccm_map_table*> tables;   // map-point tables of this context (mpt_internal.h)
     DevBuf slp;                                  // SearchLocalPoints: per-entry temporaries, workgroup counts and offsets
     DevBuf fuse;                                 // ccm_fuse_select_table_frames: membership flags, the compact query list, its selections
     DevBuf tmm;                                  // ccm_frame_track_motion_model: the queries made from the last frame (radius, levels, flags, descriptors)
@@ -64,31 +62,26 @@ static inline WinGrid frame_win_grid(const ccm_frame* f)
     return WinGrid{ f->n, f->cols, f->rows, f->min_x, f->min_y, f->inv_w, f->inv_h, f->kx, f->ky, f->oct, f->desc, f->cell_first, f->cell_items };
 }
 
-static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
+// A per-level table of a kernel argument or staging segment: src [n] and zeros up to CCM_MAX_LEVELS
+static inline void fill_levels(float* dst, const float* src, int n) { for (int l = 0; l < CCM_MAX_LEVELS; l++) dst[l] = l < n ? src[l] : 0.f; }
 
 // ccm_destroy: releases the device memory of the map-point tables still alive and orphans their handles (mpt_host.cpp)
 void mpt_tables_orphan(FrameState* S);
 // The context's frame state, created on first use.
 FrameState* frame_state(ccm_ctx* c);
-// The page-locked staging area with at least `bytes`, free to write (the last upload from it has completed), and io as large.
-int frame_staging(ccm_ctx* c, size_t bytes, uint8_t** host);
-// host[a, b) -> dst (default: io at the same offsets), asynchronous; the staging area stays busy until the copy has run
-int frame_upload(ccm_ctx* c, size_t a, size_t b, void* dst = nullptr);
-// io[0, b) -> host[0, b), then wait for the stream
-int frame_download(ccm_ctx* c, size_t b);
 // device -> pageable host, then wait for the stream (rare paths: fallbacks, test taps)
 int frame_fetch(ccm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 // CCM_E_ARG for a handle of another context or one that outlived its context
 int frame_check(ccm_ctx* c, const ccm_frame* f);
-// A handle passed under a name of the caller's (printf-style, e.g. "kfs[%d]", k): CCM_E_ARG for a null handle or one of another
-// context, CCM_E_STATE for one that outlived its context
-int frame_named_check(ccm_ctx* c, const ccm_frame* f, const char* fn, const char* who, ...) __attribute__((format(printf, 4, 5)));
+// A handle passed under a name of the caller's (printf-style, e.g. "kfs[%d]", k): CCM_E_ARG for a null handle or one of another context,
+// `orphaned` (CCM_E_STATE, or CCM_E_ARG where the entry point has always answered so) for one that outlived its context
+int frame_named_check(ccm_ctx* c, const ccm_frame* f, int orphaned, const char* fn, const char* who, ...) __attribute__((format(printf, 5, 6)));
 // What a handle lacks to serve as a keyframe of CreateNewMapPoints ("bow", "camera", "pose"), or nullptr
 const char* frame_keyframe_lacks(const ccm_frame* f);
 
 // One windowed-matcher call whose queries already lie in device memory: the candidate lists with their capacity retry, the
 // single-workgroup acceptance kernel (or the host acceptance loops) and the scatter of the new map-point ids into the handle.
-// status / out / flag lie in the context's io block at o_status / o_out / o_flag, inside [0, res_end): the results come back
+// status / out / flag lie in the staging block at o_status / o_out / o_flag, inside [0, res_end): the results come back
 // with one download of that range.  out must hold -1 and flag the occupancy flags when the call is made.
 struct WinDevCall {
     int mode, nq;

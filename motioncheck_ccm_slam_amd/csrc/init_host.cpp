@@ -2,21 +2,19 @@
 // sampling of :78-93 on the host, evaluates every hypothesis in one launch (k_init_hypotheses), replays the ordered selection of
 // :144-167 / :195-218 over the stored scores, decomposes the chosen model into its 8 (ReconstructH) or 4 (ReconstructF) motion
 // hypotheses on the host, tests all of them in one launch (k_init_check_rt) and replays the decisions of :495-565 / :685-727.
-#include "ccm_internal.h"
+#include "staging.h"
 #include "init_types.h"
 #include "init_math.h"
 #include <cmath>
 
-// One page-locked staging area and its device twin, laid out [inputs | hypothesis outputs | CheckRT outputs].
-struct InitState { DevBuf io; uint8_t* host = nullptr; size_t host_cap = 0; };
+// The staging area (staging.h), laid out [inputs | hypothesis outputs | CheckRT outputs].
+struct InitState { Staging stage{ false }; };
 void init_state_free(InitState* s)
 {
     if (!s) return;
-    if (s->host) (void)hipHostFree(s->host);
+    s->stage.release();
     delete s;
 }
-
-static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
 
 // Normalize (:745-791) without the point list: sX, sY, meanX, meanY.  Float sums in index order over all keypoints.
 static void normalize(const float* xy, int n, float out[4])
@@ -253,43 +251,31 @@ extern "C" int ccm_initialize(ccm_ctx* c, const ccm_initializer_problem* pb, ccm
         const size_t end = off;
         CCM_HIP(c, hipSetDevice(c->device));
         if (!c->init) c->init = new InitState();
-        InitState& St = *c->init;
-        if (end > St.host_cap) {
-            if (St.host) (void)hipHostFree(St.host);
-            St.host = nullptr; St.host_cap = 0;
-            const size_t want = end + end / 4 + 4096;
-            if (hipHostMalloc((void**)&St.host, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); St.host = nullptr;
-                return ccm_fail(c, CCM_E_NOMEM, "page-locked staging of %zu bytes failed", want);
-            }
-            St.host_cap = want;
-        }
-        CCM_RESERVE(c, St.io, end);
-        uint8_t* h = St.host;                                               // free: every call ends with a synchronisation
-        float* hm = reinterpret_cast<float*>(h + o_m);
+        Staging& G = c->init->stage;
+        int rc;
+        if ((rc = G.reserve(c, end))) return rc;
+        float* hm = G.host<float>(o_m);
         for (int i = 0; i < N; i++) {
             hm[4 * i] = pb->kp1_xy[2 * (size_t)m1[i]]; hm[4 * i + 1] = pb->kp1_xy[2 * (size_t)m1[i] + 1];
             hm[4 * i + 2] = pb->kp2_xy[2 * (size_t)m2[i]]; hm[4 * i + 3] = pb->kp2_xy[2 * (size_t)m2[i] + 1];
         }
-        std::memcpy(h + o_sets, sets.data(), sets.size() * 4);
+        G.put(o_sets, sets.data(), sets.size() * 4);
         hipStream_t st = c->stream;
-        uint8_t* d = St.io.as<uint8_t>();
-        CCM_HIP(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st));
+        if ((rc = G.upload(c, 0, in_end))) return rc;
         IniDev D{};
-        D.m = reinterpret_cast<const float*>(d + o_m); D.sets = reinterpret_cast<const int32_t*>(d + o_sets);
+        D.m = G.dev<float>(o_m); D.sets = G.dev<int32_t>(o_sets);
         D.n = N; D.iters = iters; D.words = (int32_t)words;
         std::memcpy(D.T1, T1, 16); std::memcpy(D.T2, T2, 16);
         D.inv_sigma2 = (float)(1.0 / (double)(pb->sigma * pb->sigma));       // :331, :407
-        D.H21 = reinterpret_cast<float*>(d + o_h21); D.H12 = reinterpret_cast<float*>(d + o_h12); D.F21 = reinterpret_cast<float*>(d + o_f21);
-        D.score_h = reinterpret_cast<float*>(d + o_sh); D.score_f = reinterpret_cast<float*>(d + o_sf);
-        D.mask_h = reinterpret_cast<unsigned long long*>(d + o_mh); D.mask_f = reinterpret_cast<unsigned long long*>(d + o_mf);
+        D.H21 = G.dev<float>(o_h21); D.H12 = G.dev<float>(o_h12); D.F21 = G.dev<float>(o_f21);
+        D.score_h = G.dev<float>(o_sh); D.score_f = G.dev<float>(o_sf);
+        D.mask_h = G.dev<unsigned long long>(o_mh); D.mask_f = G.dev<unsigned long long>(o_mf);
         init_hypotheses_launch(st, D);
         CCM_HIP(c, hipGetLastError());
-        CCM_HIP(c, hipMemcpyAsync(h + in_end, d + in_end, a_end - in_end, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));
+        if ((rc = G.download(c, in_end, a_end)) || (rc = G.wait(c))) return rc;
 
         // ---- :144-167 / :195-218: the first strictly greater score wins, starting from 0.0
-        const float* sh = reinterpret_cast<const float*>(h + o_sh); const float* sf = reinterpret_cast<const float*>(h + o_sf);
+        const float* sh = G.host<float>(o_sh); const float* sf = G.host<float>(o_sf);
         float SH = 0.0f, SF = 0.0f; int best_h = -1, best_f = -1;
         for (int it = 0; it < iters; it++) {
             if (sh[it] > SH) { SH = sh[it]; best_h = it; }
@@ -301,22 +287,21 @@ extern "C" int ccm_initialize(ccm_ctx* c, const ccm_initializer_problem* pb, ccm
         IniRtDev R{};
         int n_cand = 0;
         if (best >= 0)
-            n_cand = model == 0 ? candidates_h(reinterpret_cast<const float*>(h + o_h21) + 9 * (size_t)best, K, R.cand)
-                                : candidates_f(reinterpret_cast<const float*>(h + o_f21) + 9 * (size_t)best, K, R.cand);
+            n_cand = model == 0 ? candidates_h(G.host<float>(o_h21) + 9 * (size_t)best, K, R.cand)
+                                : candidates_f(G.host<float>(o_f21) + 9 * (size_t)best, K, R.cand);
         int32_t nGood[INI_MAX_CAND] = { 0 }; float parallax[INI_MAX_CAND] = { 0 };
         int chosen = -1;
-        const uint8_t* flags = h + o_flags; const float* cosv = reinterpret_cast<const float*>(h + o_cos); const float* X = reinterpret_cast<const float*>(h + o_x);
+        const uint8_t* flags = G.host<uint8_t>(o_flags); const float* cosv = G.host<float>(o_cos); const float* X = G.host<float>(o_x);
         if (n_cand > 0) {
             R.m = D.m; R.mask = (model == 0 ? D.mask_h : D.mask_f) + (size_t)best * words;
             R.n = N; R.n_cand = n_cand;
             std::memcpy(R.K, K, 16);
             R.th2 = (float)(4.0 * (double)(pb->sigma * pb->sigma));          // 4.0 * mSigma2 (:490)
-            R.flags = d + o_flags; R.cosp = reinterpret_cast<float*>(d + o_cos); R.X = reinterpret_cast<float*>(d + o_x);
+            R.flags = G.dev<uint8_t>(o_flags); R.cosp = G.dev<float>(o_cos); R.X = G.dev<float>(o_x);
             init_check_rt_launch(st, R);
             CCM_HIP(c, hipGetLastError());
-            CCM_HIP(c, hipMemcpyAsync(h + a_end, d + a_end, end - a_end, hipMemcpyDeviceToHost, st));
-            CCM_HIP(c, hipStreamSynchronize(st));
-            const uint64_t* bm = reinterpret_cast<const uint64_t*>(h + (model == 0 ? o_mh : o_mf)) + (size_t)best * words;
+            if ((rc = G.download(c, a_end, end)) || (rc = G.wait(c))) return rc;
+            const uint64_t* bm = G.host<uint64_t>(model == 0 ? o_mh : o_mf) + (size_t)best * words;
             int n_in = 0;                                                   // N of :469-472 / :571-574
             for (size_t wd = 0; wd < words; wd++) n_in += __builtin_popcountll(bm[wd]);
             std::vector<float> cs;
@@ -344,13 +329,9 @@ extern "C" int ccm_initialize(ccm_ctx* c, const ccm_initializer_problem* pb, ccm
             }
         }
         if (tap) {
-            if (tap->H21) std::memcpy(tap->H21, h + o_h21, (size_t)iters * 36);
-            if (tap->H12) std::memcpy(tap->H12, h + o_h12, (size_t)iters * 36);
-            if (tap->F21) std::memcpy(tap->F21, h + o_f21, (size_t)iters * 36);
-            if (tap->score_h) std::memcpy(tap->score_h, sh, (size_t)iters * 4);
-            if (tap->score_f) std::memcpy(tap->score_f, sf, (size_t)iters * 4);
-            if (tap->mask_h) std::memcpy(tap->mask_h, h + o_mh, (size_t)iters * words * 8);
-            if (tap->mask_f) std::memcpy(tap->mask_f, h + o_mf, (size_t)iters * words * 8);
+            G.get(tap->H21, o_h21, (size_t)iters * 36); G.get(tap->H12, o_h12, (size_t)iters * 36); G.get(tap->F21, o_f21, (size_t)iters * 36);
+            G.get(tap->score_h, o_sh, (size_t)iters * 4); G.get(tap->score_f, o_sf, (size_t)iters * 4);
+            G.get(tap->mask_h, o_mh, (size_t)iters * words * 8); G.get(tap->mask_f, o_mf, (size_t)iters * words * 8);
             if (tap->sets) std::memcpy(tap->sets, sets.data(), sets.size() * 4);
             tap->n_candidates = n_cand;
             for (int k = 0; k < INI_MAX_CAND; k++) {

@@ -8,13 +8,13 @@
 #include "map_types.h"
 #include <cmath>
 
-// One page-locked staging area and its device twin, laid out [inputs | per-pair work arrays | result list], and the node table of the
-// counting pass: cid[node] = 1 + compact id of a node of the current keyframe, all zero between calls.
-struct MapState { DevBuf io; uint8_t* host = nullptr; size_t host_cap = 0; std::vector<int32_t> cid; };
+// The staging area (staging.h), laid out [inputs | per-pair work arrays | result list], and the node table of the counting pass:
+// cid[node] = 1 + compact id of a node of the current keyframe, all zero between calls.
+struct MapState { Staging stage{ false }; std::vector<int32_t> cid; };
 void map_state_free(MapState* s)
 {
     if (!s) return;
-    if (s->host) (void)hipHostFree(s->host);
+    s->stage.release();
     delete s;
 }
 
@@ -44,6 +44,53 @@ static int check_keyframe(ccm_ctx* c, const ccm_map_keyframe* kf, const char* wh
         if (kf->node[i] >= kMaxNode) return ccm_fail(c, CCM_E_ARG, "%s: %s.node[%d] = %d, not below %d", fn, who, i, kf->node[i], kMaxNode);
     }
     return CCM_OK;
+}
+
+// What both entry points stage behind their inputs: the per-pair work arrays (downloaded for a tap only) and the result list.
+struct MapOut { size_t in_end, match, gate, status, X, work_end, first, okf, oi1, oi2, ox, end; };
+static MapOut map_out_layout(size_t off, int n_kf, int n1)
+{
+    const size_t pairs = (size_t)n_kf * n1;
+    MapOut o;
+    o.in_end = off;
+    o.match = seg(off, pairs * 4); o.gate = seg(off, pairs); o.status = seg(off, pairs); o.X = seg(off, pairs * 12);
+    o.work_end = off;
+    o.first = seg(off, (size_t)(n_kf + 1) * 4); o.okf = seg(off, (size_t)n1 * 4); o.oi1 = seg(off, (size_t)n1 * 4);
+    o.oi2 = seg(off, (size_t)n1 * 4); o.ox = seg(off, (size_t)n1 * 12);
+    o.end = off;
+    return o;
+}
+
+// The end of both entry points, behind their launches: the result list comes down, and the work arrays with it when a tap is given;
+// one synchronisation; the outputs.  The match tap of the flattened call holds positions in its side 2 (written for the features
+// with a compact node only), translated through idx2 [positions]; the handles' call (idx2 == nullptr) holds feature indices already.
+static int map_finish(ccm_ctx* c, Staging& G, const char* fn, const MapOut& o, int n_kf, int n1, const int32_t* cnode1, const int32_t* idx2,
+                      ccm_new_points_result* res)
+{
+    const size_t pairs = (size_t)n_kf * n1;
+    ccm_new_points_tap* tap = res->tap;
+    const bool want_tap = tap && (tap->match || tap->status || tap->x3d_all);
+    int rc;
+    if ((rc = G.download(c, o.work_end, o.end)) || (want_tap && (rc = G.download(c, o.in_end, o.work_end))) || (rc = G.wait(c))) return rc;
+    const int32_t* first = G.host<int32_t>(o.first);
+    const int n_new = first[n_kf];
+    if (n_new < 0 || n_new > n1) return ccm_fail(c, CCM_E_DEVICE, "%s: the device reported %d new points for %d features", fn, n_new, n1);
+    std::memcpy(res->first, first, (size_t)(n_kf + 1) * 4);
+    G.get(res->kf, o.okf, (size_t)n_new * 4); G.get(res->idx1, o.oi1, (size_t)n_new * 4);
+    G.get(res->idx2, o.oi2, (size_t)n_new * 4); G.get(res->x3d, o.ox, (size_t)n_new * 12);
+    res->n_new = n_new;
+    if (want_tap) {
+        if (tap->match && idx2) {
+            const int32_t* mpos = G.host<int32_t>(o.match);
+            for (int k = 0; k < n_kf; k++)
+                for (int i = 0; i < n1; i++) {
+                    const size_t t = (size_t)k * n1 + i;
+                    tap->match[t] = (cnode1[i] >= 0 && mpos[t] >= 0) ? idx2[mpos[t]] : -1;
+                }
+        } else G.get(tap->match, o.match, pairs * 4);
+        G.get(tap->status, o.status, pairs); G.get(tap->x3d_all, o.X, pairs * 12);
+    }
+    return n_new;
 }
 
 static void fill_cam(const ccm_map_keyframe& kf, MapCam& m)
@@ -84,7 +131,6 @@ extern "C" int ccm_create_new_map_points(ccm_ctx* c, const ccm_new_points_proble
         if (n1 > 0 && (!res->kf || !res->idx1 || !res->idx2 || !res->x3d))
             return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !res->kf ? "kf" : !res->idx1 ? "idx1" : !res->idx2 ? "idx2" : "x3d");
         if ((long long)n_kf * n1 > (1ll << 30)) return ccm_fail(c, CCM_E_ARG, "%s: n_kf * current.n = %lld above 2^30", fn, (long long)n_kf * n1);
-        ccm_new_points_tap* tap = res->tap;
         if (n_kf == 0 || n1 == 0) {                                          // nothing to match: no device work
             for (int k = 0; k <= n_kf; k++) res->first[k] = 0;
             res->n_new = 0;
@@ -94,6 +140,7 @@ extern "C" int ccm_create_new_map_points(ccm_ctx* c, const ccm_new_points_proble
         CCM_HIP(c, hipSetDevice(c->device));
         if (!c->map) c->map = new MapState();
         MapState& St = *c->map;
+        Staging& G = St.stage;
 
         // ---- the current keyframe's nodes, compacted in order of first appearance; the table is cleared again when the call leaves
         int max_node = -1;
@@ -132,32 +179,15 @@ extern "C" int ccm_create_new_map_points(ccm_ctx* c, const ccm_new_points_proble
         }
 
         // ---- staging
-        const size_t pairs = (size_t)n_kf * n1;
         size_t off = 0;
         const size_t o_cam = seg(off, (size_t)(1 + n_kf) * sizeof(MapCam)), o_kf = seg(off, (size_t)n_kf * sizeof(MapKf));
         const size_t o_f1 = seg(off, (size_t)n1 * sizeof(MapFeat)), o_d1 = seg(off, (size_t)n1 * 32), o_cn = seg(off, (size_t)n1 * 4);
         const size_t o_free = seg(off, (size_t)n_free * 4), o_rg = seg(off, range.size() * 4);
         const size_t o_f2 = seg(off, (size_t)m2 * sizeof(MapFeat)), o_d2 = seg(off, (size_t)m2 * 32), o_i2 = seg(off, (size_t)m2 * 4);
-        const size_t in_end = off;
-        const size_t o_mpos = seg(off, pairs * 4), o_gate = seg(off, pairs), o_status = seg(off, pairs), o_X = seg(off, pairs * 12);
-        const size_t work_end = off;
-        const size_t o_first = seg(off, (size_t)(n_kf + 1) * 4), o_okf = seg(off, (size_t)n1 * 4), o_oi1 = seg(off, (size_t)n1 * 4);
-        const size_t o_oi2 = seg(off, (size_t)n1 * 4), o_ox = seg(off, (size_t)n1 * 12);
-        const size_t end = off;
-        if (end > St.host_cap) {
-            if (St.host) (void)hipHostFree(St.host);
-            St.host = nullptr; St.host_cap = 0;
-            const size_t want = end + end / 4 + 4096;
-            if (hipHostMalloc((void**)&St.host, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); St.host = nullptr;
-                return ccm_fail(c, CCM_E_NOMEM, "page-locked staging of %zu bytes failed", want);
-            }
-            St.host_cap = want;
-        }
-        CCM_RESERVE(c, St.io, end);
-        uint8_t* h = St.host;                                                // free: every call ends with a synchronisation
-        MapCam* cam = reinterpret_cast<MapCam*>(h + o_cam);
-        MapKf* hkf = reinterpret_cast<MapKf*>(h + o_kf);
+        const MapOut o = map_out_layout(off, n_kf, n1);
+        if ((rc = G.reserve(c, o.end))) return rc;
+        MapCam* cam = G.host<MapCam>(o_cam);
+        MapKf* hkf = G.host<MapKf>(o_kf);
         fill_cam(cur, cam[0]);
         for (int k = 0; k < n_kf; k++) {
             const ccm_map_keyframe& kf = pb->neighbours[k];
@@ -166,15 +196,15 @@ extern "C" int ccm_create_new_map_points(ccm_ctx* c, const ccm_new_points_proble
             hkf[k].ex = pb->epipole[2 * k]; hkf[k].ey = pb->epipole[2 * k + 1];
             std::memcpy(hkf[k].F12, pb->F12 + 9 * (size_t)k, 36);
         }
-        MapFeat* hf1 = reinterpret_cast<MapFeat*>(h + o_f1);
+        MapFeat* hf1 = G.host<MapFeat>(o_f1);
         for (int i = 0; i < n1; i++) hf1[i] = feat_of(cur, i);
-        std::memcpy(h + o_d1, cur.desc, (size_t)n1 * 32);
-        std::memcpy(h + o_cn, cnode1.data(), (size_t)n1 * 4);
-        if (n_free) std::memcpy(h + o_free, free1.data(), (size_t)n_free * 4);
-        std::memcpy(h + o_rg, range.data(), range.size() * 4);
-        MapFeat* hf2 = reinterpret_cast<MapFeat*>(h + o_f2);
-        uint8_t* hd2 = h + o_d2;
-        int32_t* hi2 = reinterpret_cast<int32_t*>(h + o_i2);
+        G.put(o_d1, cur.desc, (size_t)n1 * 32);
+        G.put(o_cn, cnode1.data(), (size_t)n1 * 4);
+        G.put(o_free, free1.data(), (size_t)n_free * 4);
+        G.put(o_rg, range.data(), range.size() * 4);
+        MapFeat* hf2 = G.host<MapFeat>(o_f2);
+        uint8_t* hd2 = G.host<uint8_t>(o_d2);
+        int32_t* hi2 = G.host<int32_t>(o_i2);
         std::vector<int32_t> fill(std::max(n_nodes, 1));
         for (int k = 0; k < n_kf && n_nodes > 0; k++) {                      // ascending index inside a node: the order DBoW2 fills a FeatureVector in
             const ccm_map_keyframe& kf = pb->neighbours[k];
@@ -190,48 +220,22 @@ extern "C" int ccm_create_new_map_points(ccm_ctx* c, const ccm_new_points_proble
             }
         }
         hipStream_t st = c->stream;
-        uint8_t* d = St.io.as<uint8_t>();
-        CCM_HIP(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st));
+        if ((rc = G.upload(c, 0, o.in_end))) return rc;
         MapDev D{};
         D.n1 = n1; D.n_kf = n_kf; D.n_free = n_free; D.n_nodes = n_nodes;
         D.ratioFactor = 1.5f * cur.scale_factors[1];                         // :307
-        D.cam = reinterpret_cast<const MapCam*>(d + o_cam); D.kf = reinterpret_cast<const MapKf*>(d + o_kf);
-        D.f1 = reinterpret_cast<const MapFeat*>(d + o_f1); D.desc1 = d + o_d1; D.cnode1 = reinterpret_cast<const int32_t*>(d + o_cn);
-        D.free1 = reinterpret_cast<const int32_t*>(d + o_free); D.range = reinterpret_cast<const int32_t*>(d + o_rg);
-        D.f2 = reinterpret_cast<const MapFeat*>(d + o_f2); D.desc2 = d + o_d2; D.idx2 = reinterpret_cast<const int32_t*>(d + o_i2);
-        D.mpos = reinterpret_cast<int32_t*>(d + o_mpos); D.gate = d + o_gate; D.status = d + o_status; D.X = reinterpret_cast<float*>(d + o_X);
-        D.first = reinterpret_cast<int32_t*>(d + o_first); D.out_kf = reinterpret_cast<int32_t*>(d + o_okf);
-        D.out_idx1 = reinterpret_cast<int32_t*>(d + o_oi1); D.out_idx2 = reinterpret_cast<int32_t*>(d + o_oi2); D.out_x3d = reinterpret_cast<float*>(d + o_ox);
+        D.cam = G.dev<MapCam>(o_cam); D.kf = G.dev<MapKf>(o_kf);
+        D.f1 = G.dev<MapFeat>(o_f1); D.desc1 = G.dev<uint8_t>(o_d1); D.cnode1 = G.dev<int32_t>(o_cn);
+        D.free1 = G.dev<int32_t>(o_free); D.range = G.dev<int32_t>(o_rg);
+        D.f2 = G.dev<MapFeat>(o_f2); D.desc2 = G.dev<uint8_t>(o_d2); D.idx2 = G.dev<int32_t>(o_i2);
+        D.mpos = G.dev<int32_t>(o.match); D.gate = G.dev<uint8_t>(o.gate); D.status = G.dev<uint8_t>(o.status); D.X = G.dev<float>(o.X);
+        D.first = G.dev<int32_t>(o.first); D.out_kf = G.dev<int32_t>(o.okf);
+        D.out_idx1 = G.dev<int32_t>(o.oi1); D.out_idx2 = G.dev<int32_t>(o.oi2); D.out_x3d = G.dev<float>(o.ox);
         map_match_launch(st, D);
         map_triangulate_launch(st, D);
         map_resolve_launch(st, D);
         CCM_HIP(c, hipGetLastError());
-        CCM_HIP(c, hipMemcpyAsync(h + work_end, d + work_end, end - work_end, hipMemcpyDeviceToHost, st));
-        const bool want_tap = tap && (tap->match || tap->status || tap->x3d_all);
-        if (want_tap) CCM_HIP(c, hipMemcpyAsync(h + in_end, d + in_end, work_end - in_end, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));
-
-        // ---- outputs
-        const int32_t* first = reinterpret_cast<const int32_t*>(h + o_first);
-        const int n_new = first[n_kf];
-        if (n_new < 0 || n_new > n1) return ccm_fail(c, CCM_E_DEVICE, "%s: the device reported %d new points for %d features", fn, n_new, n1);
-        std::memcpy(res->first, first, (size_t)(n_kf + 1) * 4);
-        std::memcpy(res->kf, h + o_okf, (size_t)n_new * 4); std::memcpy(res->idx1, h + o_oi1, (size_t)n_new * 4);
-        std::memcpy(res->idx2, h + o_oi2, (size_t)n_new * 4); std::memcpy(res->x3d, h + o_ox, (size_t)n_new * 12);
-        res->n_new = n_new;
-        if (want_tap) {
-            if (tap->match) {
-                const int32_t* mpos = reinterpret_cast<const int32_t*>(h + o_mpos);
-                for (int k = 0; k < n_kf; k++)
-                    for (int i = 0; i < n1; i++) {
-                        const size_t t = (size_t)k * n1 + i;
-                        tap->match[t] = (cnode1[i] >= 0 && mpos[t] >= 0) ? hi2[mpos[t]] : -1;      // mpos is written for the features of free1 only
-                    }
-            }
-            if (tap->status) std::memcpy(tap->status, h + o_status, pairs);
-            if (tap->x3d_all) std::memcpy(tap->x3d_all, h + o_X, pairs * 12);
-        }
-        return n_new;
+        return map_finish(c, G, fn, o, n_kf, n1, cnode1.data(), hi2, res);
     });
 }
 
@@ -254,18 +258,12 @@ extern "C" int ccm_create_new_map_points_frames(ccm_ctx* c, const ccm_new_points
         if (n_kf > 0 && (!pb->neighbours || !pb->F12 || !pb->epipole || !pb->median_depth))
             return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !pb->neighbours ? "neighbours" : !pb->F12 ? "F12" : !pb->epipole ? "epipole" : "median_depth");
         const ccm_frame* cur = pb->current;
-        auto check_handle = [&](const ccm_frame* f, const char* who) -> int {
-            if (!f) return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, who);
-            if (!f->ctx || f->ctx != c) return ccm_fail(c, CCM_E_ARG, "%s: %s %s", fn, who, !f->ctx ? "outlived its context" : "belongs to another context");
-            return CCM_OK;
-        };
-        int rc = check_handle(cur, "current");
+        int rc = frame_named_check(c, cur, CCM_E_ARG, fn, "current");       // an orphaned handle is CCM_E_ARG here, as it has always been
         if (rc) return rc;
         const int n1 = cur->n;
-        char who[40];
         for (int k = 0; k < n_kf; k++) {
-            snprintf(who, sizeof who, "neighbours[%d]", k);
-            if ((rc = check_handle(pb->neighbours[k], who))) return rc;
+            if (!pb->neighbours[k]) return ccm_fail(c, CCM_E_ARG, "%s: null neighbours[%d]", fn, k);
+            if ((rc = frame_named_check(c, pb->neighbours[k], CCM_E_ARG, fn, "neighbours[%d]", k))) return rc;
             if (!(pb->median_depth[k] > 0.0f)) return ccm_fail(c, CCM_E_ARG, "%s: median_depth[%d] = %g is not positive", fn, k, (double)pb->median_depth[k]);
         }
         if (!res->first) return ccm_fail(c, CCM_E_ARG, "%s: null first", fn);
@@ -281,35 +279,17 @@ extern "C" int ccm_create_new_map_points_frames(ccm_ctx* c, const ccm_new_points
         for (int k = 0; k < n_kf; k++)
             if (const char* lacks = frame_keyframe_lacks(pb->neighbours[k])) return ccm_fail(c, CCM_E_STATE, "%s: neighbours[%d]: no %s", fn, k, lacks);
         if (cur->cam_levels < 2) return ccm_fail(c, CCM_E_ARG, "%s: current.n_levels = %d, at least 2 needed", fn, cur->cam_levels);   // ratioFactor reads scale_factors[1]
-        ccm_new_points_tap* tap = res->tap;
         CCM_HIP(c, hipSetDevice(c->device));
         if (!c->map) c->map = new MapState();
-        MapState& St = *c->map;
+        Staging& G = c->map->stage;
 
         // ---- staging: [MapKf | views] up, [per-pair work arrays] and [result list] down
-        const size_t pairs = (size_t)n_kf * n1;
         size_t off = 0;
         const size_t o_kf = seg(off, (size_t)n_kf * sizeof(MapKf)), o_view = seg(off, (size_t)(1 + n_kf) * sizeof(MapKfView));
-        const size_t in_end = off;
-        const size_t o_midx = seg(off, pairs * 4), o_gate = seg(off, pairs), o_status = seg(off, pairs), o_X = seg(off, pairs * 12);
-        const size_t work_end = off;
-        const size_t o_first = seg(off, (size_t)(n_kf + 1) * 4), o_okf = seg(off, (size_t)n1 * 4), o_oi1 = seg(off, (size_t)n1 * 4);
-        const size_t o_oi2 = seg(off, (size_t)n1 * 4), o_ox = seg(off, (size_t)n1 * 12);
-        const size_t end = off;
-        if (end > St.host_cap) {
-            if (St.host) (void)hipHostFree(St.host);
-            St.host = nullptr; St.host_cap = 0;
-            const size_t want = end + end / 4 + 4096;
-            if (hipHostMalloc((void**)&St.host, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); St.host = nullptr;
-                return ccm_fail(c, CCM_E_NOMEM, "page-locked staging of %zu bytes failed", want);
-            }
-            St.host_cap = want;
-        }
-        CCM_RESERVE(c, St.io, end);
-        uint8_t* h = St.host;                                                // free: every call ends with a synchronisation
-        MapKf* hkf = reinterpret_cast<MapKf*>(h + o_kf);
-        MapKfView* hv = reinterpret_cast<MapKfView*>(h + o_view);
+        const MapOut o = map_out_layout(off, n_kf, n1);
+        if ((rc = G.reserve(c, o.end))) return rc;
+        MapKf* hkf = G.host<MapKf>(o_kf);
+        MapKfView* hv = G.host<MapKfView>(o_view);
         hv[0] = view_of(cur);
         for (int k = 0; k < n_kf; k++) {
             const ccm_frame* kf = pb->neighbours[k];
@@ -318,36 +298,16 @@ extern "C" int ccm_create_new_map_points_frames(ccm_ctx* c, const ccm_new_points
             hkf[k].ex = pb->epipole[2 * k]; hkf[k].ey = pb->epipole[2 * k + 1];
             std::memcpy(hkf[k].F12, pb->F12 + 9 * (size_t)k, 36);
         }
-        hipStream_t st = c->stream;
-        uint8_t* d = St.io.as<uint8_t>();
-        CCM_HIP(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st));
+        if ((rc = G.upload(c, 0, o.in_end))) return rc;
         MapFramesDev D{};
         D.n1 = n1; D.n_kf = n_kf;
         D.ratioFactor = 1.5f * cur->sf1;                                     // :307
-        D.kf = reinterpret_cast<const MapKf*>(d + o_kf); D.view = reinterpret_cast<const MapKfView*>(d + o_view);
-        D.midx = reinterpret_cast<int32_t*>(d + o_midx); D.gate = d + o_gate; D.status = d + o_status; D.X = reinterpret_cast<float*>(d + o_X);
-        D.first = reinterpret_cast<int32_t*>(d + o_first); D.out_kf = reinterpret_cast<int32_t*>(d + o_okf);
-        D.out_idx1 = reinterpret_cast<int32_t*>(d + o_oi1); D.out_idx2 = reinterpret_cast<int32_t*>(d + o_oi2); D.out_x3d = reinterpret_cast<float*>(d + o_ox);
-        map_frames_launch(st, D);
+        D.kf = G.dev<MapKf>(o_kf); D.view = G.dev<MapKfView>(o_view);
+        D.midx = G.dev<int32_t>(o.match); D.gate = G.dev<uint8_t>(o.gate); D.status = G.dev<uint8_t>(o.status); D.X = G.dev<float>(o.X);
+        D.first = G.dev<int32_t>(o.first); D.out_kf = G.dev<int32_t>(o.okf);
+        D.out_idx1 = G.dev<int32_t>(o.oi1); D.out_idx2 = G.dev<int32_t>(o.oi2); D.out_x3d = G.dev<float>(o.ox);
+        map_frames_launch(c->stream, D);
         CCM_HIP(c, hipGetLastError());
-        CCM_HIP(c, hipMemcpyAsync(h + work_end, d + work_end, end - work_end, hipMemcpyDeviceToHost, st));
-        const bool want_tap = tap && (tap->match || tap->status || tap->x3d_all);
-        if (want_tap) CCM_HIP(c, hipMemcpyAsync(h + in_end, d + in_end, work_end - in_end, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));
-
-        // ---- outputs
-        const int32_t* first = reinterpret_cast<const int32_t*>(h + o_first);
-        const int n_new = first[n_kf];
-        if (n_new < 0 || n_new > n1) return ccm_fail(c, CCM_E_DEVICE, "%s: the device reported %d new points for %d features", fn, n_new, n1);
-        std::memcpy(res->first, first, (size_t)(n_kf + 1) * 4);
-        std::memcpy(res->kf, h + o_okf, (size_t)n_new * 4); std::memcpy(res->idx1, h + o_oi1, (size_t)n_new * 4);
-        std::memcpy(res->idx2, h + o_oi2, (size_t)n_new * 4); std::memcpy(res->x3d, h + o_ox, (size_t)n_new * 12);
-        res->n_new = n_new;
-        if (want_tap) {
-            if (tap->match) std::memcpy(tap->match, h + o_midx, pairs * 4);
-            if (tap->status) std::memcpy(tap->status, h + o_status, pairs);
-            if (tap->x3d_all) std::memcpy(tap->x3d_all, h + o_X, pairs * 12);
-        }
-        return n_new;
+        return map_finish(c, G, fn, o, n_kf, n1, nullptr, nullptr, res);
     });
 }

@@ -134,7 +134,7 @@ static int bow_handle_check(ccm_ctx* c, const ccm_frame* f, const char* fn, cons
 {
     char name[48];
     if (k >= 0) snprintf(name, sizeof name, "%s[%d]", who, k); else snprintf(name, sizeof name, "%s", who);
-    const int rc = frame_named_check(c, f, fn, "%s", name);
+    const int rc = frame_named_check(c, f, CCM_E_STATE, fn, "%s", name);
     if (rc) return rc;
     if (!f->has_bow) return ccm_fail(c, CCM_E_STATE, "%s: %s has no bow", fn, name);
     if (check_ori && !f->has_angle) return ccm_fail(c, CCM_E_ARG, "%s: orientation check against %s, created without angles", fn, name);
@@ -162,33 +162,32 @@ int ccm_frame_search_by_bow(ccm_ctx* c, const ccm_frame* kf, ccm_frame* f, const
         const size_t res_end = o_m21 + (size_t)n2 * 4;
         const size_t o_v1 = seg(off, valid1 ? (size_t)n1 : 0);
         const size_t end = off;
-        uint8_t* h = nullptr;
-        if ((rc = frame_staging(c, end, &h))) return rc;
+        Staging& G = frame_state(c)->stage;
+        if ((rc = G.reserve(c, end))) return rc;
         if (valid1) {
-            std::memcpy(h + o_v1, valid1, (size_t)n1);
-            if ((rc = frame_upload(c, o_v1, o_v1 + (size_t)n1))) return rc;
+            G.put(o_v1, valid1, (size_t)n1);
+            if ((rc = G.upload(c, o_v1, o_v1 + (size_t)n1))) return rc;
         }
         size_t t = 0;
         const size_t t_grp = seg(t, 4 * (size_t)ng * 4), t_taken = seg(t, (size_t)n2), t_m12 = seg(t, (size_t)n1 * 4), t_bin = seg(t, (size_t)n1 * 4);
         const size_t t_v1 = seg(t, (size_t)n1);
         CCM_RESERVE(c, M.bowf, std::max<size_t>(t, 64));
-        uint8_t* io = frame_state(c)->io.as<uint8_t>(); uint8_t* tmp = M.bowf.as<uint8_t>();
+        uint8_t* tmp = M.bowf.as<uint8_t>();
         int* grp = (int*)(tmp + t_grp);
-        uint8_t* v1 = valid1 ? io + o_v1 : tmp + t_v1;
+        uint8_t* v1 = valid1 ? G.dev<uint8_t>(o_v1) : tmp + t_v1;
         BowFrameRec R{};
         R.B = BowDev{ ng, n1, grp, grp + ng, grp + 2 * ng, grp + 3 * ng, kf->order, f->order, kf->desc, f->desc, v1, nullptr, kf->angle, f->angle,
-                      tmp + t_taken, (int*)(tmp + t_m12), (int*)(tmp + t_bin), (int*)(io + o_hist), o->nnratio, o->th, o->strict_th, o->check_ori };
+                      tmp + t_taken, (int*)(tmp + t_m12), (int*)(tmp + t_bin), G.dev<int>(o_hist), o->nnratio, o->th, o->strict_th, o->check_ori };
         R.nodes1 = kf->nodes; R.first1 = kf->first; R.nodes2 = f->nodes; R.first2 = f->first; R.n_nodes2 = f->n_nodes; R.n2 = n2;
-        R.mp1 = kf->mp_id; R.mp2 = f->mp_id; R.v1 = valid1 ? nullptr : v1; R.v2 = nullptr; R.match21 = (int*)(io + o_m21);
+        R.mp1 = kf->mp_id; R.mp2 = f->mp_id; R.v1 = valid1 ? nullptr : v1; R.v2 = nullptr; R.match21 = G.dev<int>(o_m21);
         match_launch_bow_groups(st, R, nullptr, 1, std::max(std::max(ng, n1), n2));
         match_launch_bow(st, R.B);
         match_launch_bow_invert(st, R, min_matches, f->mp_id);
         CCM_HIP(c, hipGetLastError());
-        if ((rc = frame_download(c, res_end))) return rc;
-        const uint8_t* host = frame_state(c)->host;
+        if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;
         int nmatches = 0;
-        std::memcpy(&nmatches, host + o_hist + 30 * 4, 4);
-        if (n2 > 0) std::memcpy(match, host + o_m21, (size_t)n2 * 4);
+        G.get(&nmatches, o_hist + 30 * 4, 4);
+        G.get(match, o_m21, (size_t)n2 * 4);
         return nmatches;
     });
 }
@@ -225,38 +224,37 @@ int ccm_search_by_bow_frames(ccm_ctx* c, const ccm_frame* kf1, int n_kf2, ccm_fr
         const size_t o_rec = seg(off, (size_t)n_kf2 * sizeof(BowFrameRec)), o_v1 = seg(off, valid1 ? (size_t)n1 : 0);
         const size_t o_v2 = seg(off, valid2 ? at2[n_kf2] : 0);
         const size_t end = off;
-        uint8_t* h = nullptr;
-        if ((rc = frame_staging(c, end, &h))) return rc;
+        Staging& G = frame_state(c)->stage;
+        if ((rc = G.reserve(c, end))) return rc;
         size_t t = 0;
         const size_t t_grp = seg(t, (size_t)n_kf2 * 4 * ng * 4), t_taken = seg(t, at2[n_kf2]), t_bin = seg(t, (size_t)n_kf2 * n1 * 4);
         const size_t t_v1 = seg(t, (size_t)n1), t_v2 = seg(t, at2[n_kf2]);
         CCM_RESERVE(c, M.bowf, std::max<size_t>(t, 64));
-        uint8_t* io = frame_state(c)->io.as<uint8_t>(); uint8_t* tmp = M.bowf.as<uint8_t>();
-        uint8_t* v1 = valid1 ? io + o_v1 : tmp + t_v1;
-        BowFrameRec* recs = (BowFrameRec*)(h + o_rec);
+        uint8_t* tmp = M.bowf.as<uint8_t>();
+        uint8_t* v1 = valid1 ? G.dev<uint8_t>(o_v1) : tmp + t_v1;
+        BowFrameRec* recs = G.host<BowFrameRec>(o_rec);
         for (int k = 0; k < n_kf2; k++) {
             const ccm_frame* f = kfs2[k];
             int* grp = (int*)(tmp + t_grp) + (size_t)k * 4 * ng;
-            uint8_t* v2 = valid2 ? io + o_v2 + at2[k] : tmp + t_v2 + at2[k];
+            uint8_t* v2 = valid2 ? G.dev<uint8_t>(o_v2 + at2[k]) : tmp + t_v2 + at2[k];
             BowFrameRec R{};
             R.B = BowDev{ ng, n1, grp, grp + ng, grp + 2 * ng, grp + 3 * ng, kf1->order, f->order, kf1->desc, f->desc, v1, v2, kf1->angle, f->angle,
-                          tmp + t_taken + at2[k], (int*)(io + o_m12) + (size_t)k * n1, (int*)(tmp + t_bin) + (size_t)k * n1,
-                          (int*)(io + o_hist) + (size_t)k * 32, o->nnratio, o->th, 1, o->check_ori };
+                          tmp + t_taken + at2[k], G.dev<int>(o_m12) + (size_t)k * n1, (int*)(tmp + t_bin) + (size_t)k * n1,
+                          G.dev<int>(o_hist) + (size_t)k * 32, o->nnratio, o->th, 1, o->check_ori };
             R.nodes1 = kf1->nodes; R.first1 = kf1->first; R.nodes2 = f->nodes; R.first2 = f->first; R.n_nodes2 = f->n_nodes; R.n2 = f->n;
             R.mp1 = kf1->mp_id; R.mp2 = f->mp_id; R.v1 = valid1 ? nullptr : v1; R.v2 = valid2 ? nullptr : v2; R.match21 = nullptr;
             std::memcpy(recs + k, &R, sizeof R);
         }
-        if (valid1) std::memcpy(h + o_v1, valid1, (size_t)n1);
-        if (valid2) for (int k = 0; k < n_kf2; k++) std::memcpy(h + o_v2 + at2[k], valid2 + first2[k], (size_t)kfs2[k]->n);
-        if ((rc = frame_upload(c, o_rec, end))) return rc;
-        const BowFrameRec* d_recs = (const BowFrameRec*)(io + o_rec);
+        G.put(o_v1, valid1, (size_t)n1);
+        if (valid2) for (int k = 0; k < n_kf2; k++) G.put(o_v2 + at2[k], valid2 + first2[k], (size_t)kfs2[k]->n);
+        if ((rc = G.upload(c, o_rec, end))) return rc;
+        const BowFrameRec* d_recs = G.dev<BowFrameRec>(o_rec);
         match_launch_bow_groups(st, BowFrameRec{}, d_recs, n_kf2, std::max(std::max(ng, n1), max_n2));
         match_launch_bow_batch(st, d_recs, n_kf2, ng);
         CCM_HIP(c, hipGetLastError());
-        if ((rc = frame_download(c, res_end))) return rc;
-        const uint8_t* host = frame_state(c)->host;
-        for (int k = 0; k < n_kf2; k++) std::memcpy(nmatches + k, host + o_hist + ((size_t)k * 32 + 30) * 4, 4);
-        if (n1 > 0) std::memcpy(match12, host + o_m12, (size_t)n_kf2 * n1 * 4);
+        if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;
+        for (int k = 0; k < n_kf2; k++) G.get(nmatches + k, o_hist + ((size_t)k * 32 + 30) * 4, 4);
+        G.get(match12, o_m12, (size_t)n_kf2 * n1 * 4);
         return CCM_OK;
     });
 }

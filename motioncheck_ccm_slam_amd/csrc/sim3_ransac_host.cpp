@@ -1,17 +1,17 @@
 // sim3_ransac_host.cpp -- C ABI of the batched Sim3Solver (src/Sim3Solver.cpp): create evaluates every hypothesis of every solver in
 // one kernel launch (sim3_ransac_kernels.hip); iterate / find replay the ordered bookkeeping of Sim3Solver::iterate (:120-191) over
 // the stored per-hypothesis counts on the host.
-#include "ccm_internal.h"
+#include "staging.h"
 #include "sim3_ransac_types.h"
 #include <cmath>
 #include <memory>
 
-// One page-locked staging area and its device twin, laid out [inputs | outputs]: one upload, one launch, one download per batch.
-struct Sim3RansacState { DevBuf io; uint8_t* host = nullptr; size_t host_cap = 0; };
+// The staging area (staging.h), laid out [inputs | outputs]: one upload, one launch, one download per batch.
+struct Sim3RansacState { Staging stage{ false }; };
 void sim3_ransac_state_free(Sim3RansacState* s)
 {
     if (!s) return;
-    if (s->host) (void)hipHostFree(s->host);
+    s->stage.release();
     delete s;
 }
 
@@ -31,8 +31,6 @@ struct ccm_sim3_solver {
     std::vector<float> rts;
     std::vector<uint64_t> mask;
 };
-
-static inline size_t seg(size_t& off, size_t bytes) { const size_t o = off; off += (bytes + 63) & ~(size_t)63; return o; }
 
 extern "C" int ccm_sim3_ransac_iterations(int n, double probability, int min_inliers, int max_iterations)
 {
@@ -106,21 +104,11 @@ extern "C" int ccm_sim3_solver_create(ccm_ctx* c, const ccm_sim3_ransac_problem*
         const size_t end = off;
         CCM_HIP(c, hipSetDevice(c->device));
         if (!c->sim3_ransac) c->sim3_ransac = new Sim3RansacState();
-        Sim3RansacState& St = *c->sim3_ransac;
-        if (end > St.host_cap) {
-            if (St.host) (void)hipHostFree(St.host);
-            St.host = nullptr; St.host_cap = 0;
-            const size_t want = end + end / 4 + 4096;
-            if (hipHostMalloc((void**)&St.host, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); St.host = nullptr;
-                return ccm_fail(c, CCM_E_NOMEM, "page-locked staging of %zu bytes failed", want);
-            }
-            St.host_cap = want;
-        }
-        CCM_RESERVE(c, St.io, end);
-        uint8_t* h = St.host;                                               // free: every create ends with a synchronisation
-        S3rSolver* hs = reinterpret_cast<S3rSolver*>(h + o_solvers);
-        S3rBlock* hb = reinterpret_cast<S3rBlock*>(h + o_blocks);
+        Staging& G = c->sim3_ransac->stage;
+        int rc;
+        if ((rc = G.reserve(c, end))) return rc;
+        S3rSolver* hs = G.host<S3rSolver>(o_solvers);
+        S3rBlock* hb = G.host<S3rBlock>(o_blocks);
         size_t nb = 0;
         for (int f = 0; f < F; f++) {
             const S3rHost& k = S->k[f];
@@ -129,26 +117,20 @@ extern "C" int ccm_sim3_solver_create(ccm_ctx* c, const ccm_sim3_ransac_problem*
             s.words = k.words; s.mask_first = (int64_t)k.mask_first;
             std::memcpy(s.K1, pb->K1 + 4 * f, 16); std::memcpy(s.K2, pb->K2 + 4 * f, 16);
             for (int h0 = 0; h0 < k.n_hyp; h0 += S3R_HPB) hb[nb++] = S3rBlock{ f, h0, std::min(S3R_HPB, k.n_hyp - h0), 0 };
-            if (k.n_hyp) std::memcpy(h + o_draws + (size_t)k.hyp_first * 12, pb->draws + (size_t)f * pb->max_iterations * 3, (size_t)k.n_hyp * 12);
+            G.put(o_draws + (size_t)k.hyp_first * 12, pb->draws + (size_t)f * pb->max_iterations * 3, (size_t)k.n_hyp * 12);
         }
-        std::memcpy(h + o_x1, pb->X1, T * 12); std::memcpy(h + o_x2, pb->X2, T * 12);
-        std::memcpy(h + o_m1, pb->max_err1, T * 4); std::memcpy(h + o_m2, pb->max_err2, T * 4);
-        hipStream_t st = c->stream;
-        uint8_t* d = St.io.as<uint8_t>();
-        CCM_HIP(c, hipMemcpyAsync(d, h, in_end, hipMemcpyHostToDevice, st));
-        const S3rDev D{ reinterpret_cast<const S3rSolver*>(d + o_solvers), reinterpret_cast<const S3rBlock*>(d + o_blocks),
-                        reinterpret_cast<const float*>(d + o_x1), reinterpret_cast<const float*>(d + o_x2),
-                        reinterpret_cast<const float*>(d + o_m1), reinterpret_cast<const float*>(d + o_m2),
-                        reinterpret_cast<const int32_t*>(d + o_draws), reinterpret_cast<int32_t*>(d + o_count),
-                        reinterpret_cast<int32_t*>(d + o_sample), reinterpret_cast<float*>(d + o_rts),
-                        reinterpret_cast<unsigned long long*>(d + o_mask) };
-        sim3_ransac_launch(st, D, (int)n_blocks);
+        G.put(o_x1, pb->X1, T * 12); G.put(o_x2, pb->X2, T * 12);
+        G.put(o_m1, pb->max_err1, T * 4); G.put(o_m2, pb->max_err2, T * 4);
+        if ((rc = G.upload(c, 0, in_end))) return rc;
+        const S3rDev D{ G.dev<S3rSolver>(o_solvers), G.dev<S3rBlock>(o_blocks), G.dev<float>(o_x1), G.dev<float>(o_x2), G.dev<float>(o_m1),
+                        G.dev<float>(o_m2), G.dev<int32_t>(o_draws), G.dev<int32_t>(o_count), G.dev<int32_t>(o_sample), G.dev<float>(o_rts),
+                        G.dev<unsigned long long>(o_mask) };
+        sim3_ransac_launch(c->stream, D, (int)n_blocks);
         CCM_HIP(c, hipGetLastError());
-        CCM_HIP(c, hipMemcpyAsync(h + in_end, d + in_end, end - in_end, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));
-        const int32_t* rc = reinterpret_cast<const int32_t*>(h + o_count); const int32_t* rs = reinterpret_cast<const int32_t*>(h + o_sample);
-        const float* rr = reinterpret_cast<const float*>(h + o_rts); const uint64_t* rm = reinterpret_cast<const uint64_t*>(h + o_mask);
-        S->count.assign(rc, rc + H); S->sample.assign(rs, rs + 3 * H); S->rts.assign(rr, rr + 13 * H); S->mask.assign(rm, rm + W);
+        if ((rc = G.download(c, in_end, end)) || (rc = G.wait(c))) return rc;
+        const int32_t* rn = G.host<int32_t>(o_count); const int32_t* rs = G.host<int32_t>(o_sample);
+        const float* rr = G.host<float>(o_rts); const uint64_t* rm = G.host<uint64_t>(o_mask);
+        S->count.assign(rn, rn + H); S->sample.assign(rs, rs + 3 * H); S->rts.assign(rr, rr + 13 * H); S->mask.assign(rm, rm + W);
         *out = S.release();
         return CCM_OK;
     });

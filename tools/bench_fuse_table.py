@@ -135,7 +135,7 @@ def main():
                 route_b(); route_a()
             mismatches += not ((a_idx == b_idx).all() and (a_dist == b_dist).all())
         sa, sb = stats(t_a), stats(t_b)
-        # host-to-device bytes by the two calls' own layouts (match_window_host.cpp fuse_batch_run; mpt_host.cpp, whose static_assert pins the
+        # host-to-device bytes by the two calls' own layouts (match_window_host.cpp fuse_batch_run; mpt_fuse_host.cpp, whose static_assert pins the
         # 112-byte view and the 80-byte grid record per keyframe, every segment of the staging copy rounded up to 64 bytes)
         seg = lambda b: (b + 63) // 64 * 64  # noqa: E731
         chi2 = int(par["chi2_check"])

@@ -8,7 +8,7 @@ host clock around calls that end in a stream synchronisation, the two routes alt
        old route is charged less than it costs) -> ccm_frame_pose_optimize_table -> ccm_frame_set_map_points (outliers dropped)
   new  one ccm_frame_track_motion_model on a second pair of handles
 Every repetition's match, pose7, outlier and mp_id are compared between the routes.  The uploaded bytes are computed from the two
-staging layouts (csrc/frame_host.cpp frame_window / frame_pose_run / ccm_frame_set_map_points; csrc/mpt_host.cpp).
+staging layouts (csrc/frame_window_host.cpp frame_window, frame_pose_host.cpp frame_pose_run, frame_host.cpp ccm_frame_set_map_points; csrc/mpt_track_host.cpp).
 Output: profiles/<tag>_track_motion_model.json and one summary line.
 
     python tools/bench_track_motion_model.py [--reps 200] [--warmup 20] [--tag r05]
