@@ -812,6 +812,123 @@ typedef struct {
 } ccm_fuse_table_result;
 int ccm_fuse_select_table_frames(ccm_ctx*, ccm_map_table*, const ccm_fuse_table_problem*, ccm_fuse_table_result*);
 
+/* ---- ComputeSim3 on keyframe handles and the table: links 3 and 5 of LoopFinder::ComputeSim3 (src/LoopFinder.cpp:231-400) and
+ * MapMatcher::ComputeSim3 (src/MapMatcher.cpp:238-400), next to ccm_search_by_bow_frames, ccm_sim3_solver_*, ccm_optimize_sim3 and
+ * ccm_fuse_select_table_frames.  Both calls read the map points from the table and the features, grids and mp_id (as table slots) from
+ * the handles; nothing of a keyframe or of a map point is uploaded.  The table and every handle of a call belong to the calling context
+ * (one table serves one context, as for ccm_fuse_select_table_frames): a thread with another context keeps the array entry points
+ * ccm_search_by_sim3 and ccm_search_by_projection_sim3_batch.  Float arithmetic is unfused and rounded per operation; a "matrix
+ * product" below sums in double and stores a float, Pc[r] = (float)((double)M[r][0] P[0] + (double)M[r][1] P[1] + (double)M[r][2] P[2] +
+ * (double)M[r][3]) for a row-major [3][4] M, as for CCM_FG_BEHIND above.
+ *
+ * ORBmatcher::SearchBySim3 (src/ORBmatcher.cpp:1124-1348), complete, for n_pairs >= 0 candidate pairs in one call (the reference calls
+ * it once per candidate that survives RANSAC; the round-robin over candidates can hand over all of them).
+ *   Direction 1 -> 2, per feature i1 of kf1 with slot = kf1's mp_id[i1]; the first gate that fails names the feature (CCM_SG_*):
+ *     NO_POINT   slot < 0, slot >= capacity, or the slot is not LIVE (such an id names no point, as for Fuse)
+ *     MATCHED    matched12[i1] >= 0 (vbAlreadyMatched1, :1154-1164)
+ *     BAD        the slot is BAD (isBad(), :1177)
+ *     BEHIND     Pc1 = T1w P, Pc2 = S21 Pc1 (two matrix products, :1181-1182);  Pc2[2] < 0
+ *     OUTSIDE    invz = 1.0f / Pc2[2];  x = Pc2[0] * invz;  y = Pc2[1] * invz;  u = fx * x + cx;  v = fy * y + cy;  KeyFrame::IsInImage with
+ *                the bounds of the TARGET keyframe (bounds2 here): !(u >= min_x && u < max_x && v >= min_y && v < max_y); a NaN is outside
+ *     DISTANCE   dist3D = (float)sqrt(sum (double)Pc2^2);  dist3D < 0.8f * min_dist || dist3D > 1.2f * max_dist  (:1199-1205)
+ *     EMPTY_KF   the target handle has no features
+ *     SEARCHED   level = MapPoint::PredictScale on the target side's log_scale_factor / n_levels, the expression of CCM_FG_SEARCHED;
+ *                radius = th * scale_factors_target[level], features of level - 1 .. level in the window, the nearest descriptor, the
+ *                first of equal ones in GetFeaturesInArea's order, accepted at <= TH_HIGH (100): sel1[i1] = that feature of kf2 or -1
+ *   SearchBySim3 has no viewing-angle gate.  Direction 2 -> 1 is the same with T2w, S12, bounds1, side 1's levels, and MATCHED where
+ *   some i1 has matched12[i1] >= 0 and matched_idx2[i1] in [0, N2) naming the feature (vbAlreadyMatched2, :1160-1162; an index
+ *   outside [0, N2) is ignored).  fx, fy, cx, cy are ONE set used for BOTH directions: the reference reads pKF1's intrinsics for both
+ *   (:1127-1130, :1272), also where pKF2 has other ones -- pass pKF1's.
+ *   match12[i1] = sel1[i1] where sel2[sel1[i1]] == i1, else -1 (:1330-1345), decided on the device; n_found[p] counts them and the
+ *   function returns their sum.  All per-feature arrays of the result are flat over the pairs: pair p's side-1 entries start at
+ *   N1(0) + .. + N1(p-1), its side-2 entries at N2(0) + .. + N2(p-1).  The taps hold 0 (sel: -1) where a feature did not get that far.
+ * Traffic: one page-locked staging copy up (per pair and direction a 168-byte view with the handles' device pointers, an 80-byte grid
+ * record, and the two index lists, 8 bytes per feature of kf1); one download of match12 and of the taps asked for.  Two
+ * synchronisations: on the number of queries (16 bytes) behind the projection, and on the download.  Ordered on the context's stream
+ * behind earlier ccm_frame_set_map_points / ccm_map_table_update / ccm_map_table_refresh.
+ * Errors are found on the host before anything is queued; the outputs are then untouched.  CCM_E_ARG: a NULL required array (pairs,
+ * a pair's kf1 / kf2, matched12 / matched_idx2 of a pair with N1 > 0, scale_factors1 / 2, match12 with features on side 1, n_found),
+ * only some of u / v / level of a direction, n_levels1 / 2 outside 1..CCM_MAX_LEVELS, a handle or table of another context.
+ * CCM_E_STATE: a handle or table that outlived its context.  CCM_E_CAPACITY: more than 32767 pairs or 2^24 features in one call.
+ * n_pairs == 0 returns 0.  Memory: the query list is sized for every feature surviving, 72 bytes of device memory per feature of
+ * either side, plus 12 to 29 bytes per feature (by the taps asked for) of page-locked host and device staging, kept by the context
+ * at its high-water mark: about 0.5 MB for three pairs of 1,000 x 1,000 features. */
+enum { CCM_SG_SEARCHED = 0, CCM_SG_NO_POINT = 1, CCM_SG_MATCHED = 2, CCM_SG_BAD = 3, CCM_SG_BEHIND = 4, CCM_SG_OUTSIDE = 5,
+       CCM_SG_DISTANCE = 6, CCM_SG_EMPTY_KF = 7 };
+typedef struct {
+    ccm_frame* kf1; ccm_frame* kf2;    /* features, grid and mp_id (vpMapPoints1 / 2 as table slots) are read; may be the same handle */
+    float T1w[12], T2w[12];            /* rows of [R1w | t1w], [R2w | t2w] (:1133-1138) */
+    float S21[12], S12[12];            /* rows of [sR21 | t21] and [sR12 | t12], as the caller computed them at :1141-1143 */
+    float fx, fy, cx, cy;              /* pKF1's, used for both directions */
+    float bounds1[4], bounds2[4];      /* mnMinX, mnMaxX, mnMinY, mnMaxY of kf1 / kf2 */
+    const int32_t* matched12;          /* [N1] slot of vpMatches12[i] on entry, or -1 */
+    const int32_t* matched_idx2;       /* [N1] GetIndexInKeyFrame(pKF2) of that point, or -1 */
+} ccm_sim3_search_pair;
+typedef struct {
+    int32_t n_pairs;  const ccm_sim3_search_pair* pairs;
+    float th;                                                    /* 7.5 in ComputeSim3 */
+    float log_scale_factor1;  int32_t n_levels1;  const float* scale_factors1;   /* side 1: kf1 of every pair; [n_levels1] */
+    float log_scale_factor2;  int32_t n_levels2;  const float* scale_factors2;   /* side 2 */
+} ccm_sim3_search_problem;
+typedef struct {
+    int32_t* match12;                  /* [sum N1] feature of kf2 matched to feature i1, or -1 */
+    int32_t* n_found;                  /* [n_pairs] */
+    uint8_t* gate1; float* u1; float* v1; int32_t* level1; int32_t* sel1;   /* optional taps [sum N1]: CCM_SG_*, projection, vnMatch1 */
+    uint8_t* gate2; float* u2; float* v2; int32_t* level2; int32_t* sel2;   /* optional taps [sum N2]: direction 2 -> 1, vnMatch2 */
+} ccm_sim3_search_result;
+int ccm_search_by_sim3_table_frames(ccm_ctx*, ccm_map_table*, const ccm_sim3_search_problem*, ccm_sim3_search_result*);
+
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cpp:308-446) up to and including the acceptance:
+ * ONE list of table slots projected into n_kf views, each with its own vpMatched (the reference has one view, mpCurrentKF; the batch
+ * mirrors ccm_search_by_projection_sim3_batch).  A view is a ccm_fuse_view -- the caller decomposes Scw as at :317-321 -- plus
+ * matched_slot [N]: vpMatched on entry, the slot of the point or -1 (any value >= 0 marks the feature as matched; one outside
+ * [0, capacity) names no listed point).  Pair (k, j) at k * n_points + j.  Gates in the reference's order (CCM_LG_*):
+ *     SKIPPED        the slot is not LIVE, or it is BAD (isBad(), :335)
+ *     ALREADY_FOUND  the slot occurs in view k's matched_slot (spAlreadyFound, :324-335)
+ *     BEHIND / OUTSIDE / DISTANCE / ANGLE / EMPTY_KF / SEARCHED   exactly the arithmetic of CCM_FG_* above (:342-375 and Fuse's second
+ *                    overload are the same text); there is NO IN_KEYFRAME gate
+ *   Acceptance, in list order (:388-441): a SEARCHED point takes the nearest feature of level - 1 .. level in its window whose
+ *   vpMatched is still empty (:393), strictly nearer wins, so the first of equal ones; accepted at <= TH_LOW (50): best_idx = that
+ *   feature.  An accepted point that the keyframe already observes -- observed[k][j]: some feature of the handle holds the slot in
+ *   mp_id -- leaves vpMatched alone and is not counted (:414-435; RemapMapPointMatch stays with the caller, who reads observed to tell
+ *   which accepted points are remaps); any other accepted point sets matched_slot[best_idx] = its slot and counts in n_matches[k].
+ *   `observed` restates GetIndexInKeyFrame(pKF) != -1 (:415) from the handle's mp_id: it rests on mObservations and mvpMapPoints agreeing,
+ *   as AddObservation / AddMapPoint keep them.  The function returns the sum of n_matches.
+ * The queries stay in list order, one per pair (a gated pair has radius -1); keyframe k is worked by workgroup k of the acceptance
+ * kernel of ccm_search_by_projection_sim3_batch.  A handle with more features than that kernel's LDS admits (about 25,000) sends the
+ * call through the host acceptance loops, as ccm_frame_search_by_projection does in that case (so does CCM_WINDOW_HOST_ACCEPT=1).
+ * Traffic: one staging copy up (per view 112 + 80 + 16 bytes and 4 bytes per feature for matched_slot, the slot list); one download;
+ * ONE synchronisation (a second round only when a window holds more than 64 features).  Stream order, error handling and ownership as
+ * ccm_fuse_select_table_frames.  CCM_E_ARG: a NULL required array (views, a view's kf, matched_slot of a view with features, slot,
+ * scale_factors, best_idx, observed, n_matches, the result's matched_slot), only some of u / v / level, n_levels outside
+ * 1..CCM_MAX_LEVELS, a slot outside [0, capacity) or listed twice, a handle or table of another context.  CCM_E_STATE: a handle or table
+ * that outlived its context.  CCM_E_CAPACITY: more than 65535 views or 2^24 pairs.  n_kf == 0 or n_points == 0 returns 0 with
+ * best_idx = -1, n_matches = 0 and matched_slot copied through.  Memory: 574 bytes of device memory per pair (the candidate lists of 64
+ * entries take 512 of them) and 5 per feature, plus 5 to 22 bytes per pair (by the taps asked for) and 8 per feature of page-locked
+ * host and device staging, kept by the context at its high-water mark: 2.3 MB + 0.03 MB for 1,000 features x 4,000 points. */
+enum { CCM_LG_SEARCHED = 0, CCM_LG_SKIPPED = 1, CCM_LG_ALREADY_FOUND = 2, CCM_LG_BEHIND = 3, CCM_LG_OUTSIDE = 4, CCM_LG_DISTANCE = 5,
+       CCM_LG_ANGLE = 6, CCM_LG_EMPTY_KF = 7 };
+typedef struct {
+    ccm_fuse_view view;                /* handle, [Rcw | tcw], Ow, intrinsics and bounds, as for ccm_fuse_select_table_frames */
+    const int32_t* matched_slot;       /* [N] vpMatched on entry */
+} ccm_loop_view;
+typedef struct {
+    int32_t n_kf;  const ccm_loop_view* views;       /* the same handle may appear twice, with different poses */
+    int32_t n_points;  const int32_t* slot;          /* [n_points] table slots, visited in this order */
+    float log_scale_factor;  int32_t n_levels;       /* mfLogScaleFactor, mnScaleLevels (1..CCM_MAX_LEVELS) */
+    const float* scale_factors;                      /* [n_levels] */
+    float th;                                        /* 10 in ComputeSim3 */
+} ccm_loop_projection_problem;
+typedef struct {
+    int32_t* best_idx;                 /* [n_kf][n_points] accepted feature of view k for point j, or -1 */
+    uint8_t* observed;                 /* [n_kf][n_points] the handle already holds the slot */
+    int32_t* matched_slot;             /* views' vpMatched after the call, flat: view k's [N_k] at N_0 + .. + N_(k-1) */
+    int32_t* n_matches;                /* [n_kf] */
+    uint8_t* gate; float* u; float* v; int32_t* level;   /* optional taps [n_kf][n_points]: CCM_LG_* and the projection */
+    int32_t* best_dist;                /* optional tap: descriptor distance to best_idx, 256 where best_idx is -1 */
+} ccm_loop_projection_result;
+int ccm_search_by_projection_table_frames(ccm_ctx*, ccm_map_table*, const ccm_loop_projection_problem*, ccm_loop_projection_result*);
+
 /* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cpp:867-1062), next row F4,
  * batched over candidate keyframe pairs: one VertexSim3Expmap, fixed points, EdgeSim3ProjectXYZ +
  * EdgeInverseSim3ProjectXYZ per correspondence with g2o's numeric Jacobians (delta 1e-9) and Huber(sqrt(th2));

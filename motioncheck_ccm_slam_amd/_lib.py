@@ -41,6 +41,7 @@ SYMBOLS = [
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
     "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
     "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model",
+    "ccm_search_by_sim3_table_frames", "ccm_search_by_projection_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
@@ -211,6 +212,42 @@ class FuseTableResult(C.Structure):
                 ("level", C.c_void_p), ("n_searched", C.c_int32)]
 
 
+SG_GATES = ("SEARCHED", "NO_POINT", "MATCHED", "BAD", "BEHIND", "OUTSIDE", "DISTANCE", "EMPTY_KF")             # CCM_SG_*
+LG_GATES = ("SEARCHED", "SKIPPED", "ALREADY_FOUND", "BEHIND", "OUTSIDE", "DISTANCE", "ANGLE", "EMPTY_KF")   # CCM_LG_*
+
+
+class Sim3SearchPair(C.Structure):
+    _fields_ = [("kf1", C.c_void_p), ("kf2", C.c_void_p), ("T1w", C.c_float * 12), ("T2w", C.c_float * 12), ("S21", C.c_float * 12),
+                ("S12", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("bounds1", C.c_float * 4), ("bounds2", C.c_float * 4), ("matched12", C.c_void_p), ("matched_idx2", C.c_void_p)]
+
+
+class Sim3SearchProblem(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("pairs", C.POINTER(Sim3SearchPair)), ("th", C.c_float),
+                ("log_scale_factor1", C.c_float), ("n_levels1", C.c_int32), ("scale_factors1", C.c_void_p),
+                ("log_scale_factor2", C.c_float), ("n_levels2", C.c_int32), ("scale_factors2", C.c_void_p)]
+
+
+class Sim3SearchResult(C.Structure):
+    _fields_ = [("match12", C.c_void_p), ("n_found", C.c_void_p),
+                ("gate1", C.c_void_p), ("u1", C.c_void_p), ("v1", C.c_void_p), ("level1", C.c_void_p), ("sel1", C.c_void_p),
+                ("gate2", C.c_void_p), ("u2", C.c_void_p), ("v2", C.c_void_p), ("level2", C.c_void_p), ("sel2", C.c_void_p)]
+
+
+class LoopView(C.Structure):
+    _fields_ = [("view", FuseView), ("matched_slot", C.c_void_p)]
+
+
+class LoopProjectionProblem(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("views", C.POINTER(LoopView)), ("n_points", C.c_int32), ("slot", C.c_void_p),
+                ("log_scale_factor", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_void_p), ("th", C.c_float)]
+
+
+class LoopProjectionResult(C.Structure):
+    _fields_ = [("best_idx", C.c_void_p), ("observed", C.c_void_p), ("matched_slot", C.c_void_p), ("n_matches", C.c_void_p),
+                ("gate", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("level", C.c_void_p), ("best_dist", C.c_void_p)]
+
+
 class EssentialGraph(C.Structure):
     _fields_ = [("n_vertices", C.c_int), ("sim3", C.c_void_p), ("fixed", C.c_void_p), ("fix_scale", C.c_int), ("n_edges", C.c_int),
                 ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("measurement", C.c_void_p), ("iterations", C.c_int),
@@ -337,6 +374,8 @@ def load():
     lib.ccm_frame_search_local_points_timing.argtypes = [vp, vp]
     lib.ccm_frame_pose_optimize_table.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_fuse_select_table_frames.argtypes = [vp, vp, C.POINTER(FuseTableProblem), C.POINTER(FuseTableResult)]
+    lib.ccm_search_by_sim3_table_frames.argtypes = [vp, vp, C.POINTER(Sim3SearchProblem), C.POINTER(Sim3SearchResult)]
+    lib.ccm_search_by_projection_table_frames.argtypes = [vp, vp, C.POINTER(LoopProjectionProblem), C.POINTER(LoopProjectionResult)]
     lib.ccm_frame_track_motion_model.argtypes = [vp, vp, vp, vp, C.POINTER(TmmParams), C.POINTER(TmmResult)]
     lib.ccm_sim3_ransac_iterations.argtypes =[C.c_int, C.c_double, C.c_int, C.c_int]
     lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]

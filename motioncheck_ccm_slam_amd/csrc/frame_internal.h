@@ -51,7 +51,8 @@ struct FrameState {
     DevBuf ci, cd, cn, ev, pts, obs, info, err, outl, kof, first;
     std::vector<struct ccm_map_table*> tables;   // map-point tables of this context (mpt_internal.h)
     DevBuf slp;                                  // SearchLocalPoints: per-entry temporaries, workgroup counts and offsets
-    DevBuf fuse;                                 // ccm_fuse_select_table_frames: membership flags, the compact query list, its selections
+    DevBuf fuse;                                 // ccm_fuse_select_table_frames: membership flags, the compact query list, its selections;
+                                                 // the work area of the two calls of mpt_sim3_host.cpp as well
     DevBuf tmm;                                  // ccm_frame_track_motion_model: the queries made from the last frame (radius, levels, flags, descriptors)
     double slp_ms[3] = { -1, 0, 0 };            // host wall time of its last call (ccm_frame_search_local_points_timing)
 };

@@ -1,5 +1,5 @@
 // mpt_internal.h -- what the host translation units of the map-point table share: mpt_host.cpp (the table itself and its refresh),
-// mpt_fuse_host.cpp (Fuse on the table), mpt_track_host.cpp (SearchLocalPoints, TrackWithMotionModel) and frame_pose_host.cpp (the
+// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_track_host.cpp (SearchLocalPoints, TrackWithMotionModel) and frame_pose_host.cpp (the
 // pose on table points).  Every call stages through the frame handles' block (FrameState::stage, frame_internal.h).
 #pragma once
 #include "frame_internal.h"

@@ -565,6 +565,12 @@ void fuse_launch_project(hipStream_t s, const FuseArgs& A, const MptTable& T, in
     if (max_n > 0) hipLaunchKernelGGL(k_fuse_held, dim3((max_n + 255) / 256, A.n_kf), dim3(256), 0, s, A, T.capacity);
     hipLaunchKernelGGL(k_fuse_project, dim3((A.n_points + FUSE_TPB - 1) / FUSE_TPB, A.n_kf), dim3(FUSE_TPB), 0, s, A, T);
 }
+void fuse_launch_membership(hipStream_t s, const FuseArgs& A, const MptTable& T, int max_n)
+{
+    if (A.n_points <= 0 || A.n_kf <= 0) return;
+    hipLaunchKernelGGL(k_fuse_where, dim3((A.n_points + 255) / 256), dim3(256), 0, s, A, T.capacity);
+    if (max_n > 0) hipLaunchKernelGGL(k_fuse_held, dim3((max_n + 255) / 256, A.n_kf), dim3(256), 0, s, A, T.capacity);
+}
 void fuse_launch_scatter(hipStream_t s, int nq, int n_pairs, const int* qpair, const int* sel_i, const int* sel_d, int* best_idx, int* best_dist)
 {
     if (nq > 0) hipLaunchKernelGGL(k_fuse_scatter, dim3((nq + 255) / 256), dim3(256), 0, s, nq, n_pairs, qpair, sel_i, sel_d, best_idx, best_dist);

@@ -79,5 +79,50 @@ void slp_launch_frustum(hipStream_t, const SlpArgs&, const MptTable&, int* cnt);
 void mpt_launch_refresh(hipStream_t, const MptRefreshArgs&, const MptTable&);
 // k_fuse_where and k_fuse_held (max_n: the largest feature count among the keyframes), then k_fuse_project: gates, taps, cnt[0] queries
 void fuse_launch_project(hipStream_t, const FuseArgs&, const MptTable&, int max_n);
+// k_fuse_where and k_fuse_held alone: held [n_kf][n_points] (cleared by the caller) for the views' mp_id and the slot list
+void fuse_launch_membership(hipStream_t, const FuseArgs&, const MptTable&, int max_n);
+
+// ---- mpt_sim3_kernels.hip: ccm_search_by_sim3_table_frames and ccm_search_by_projection_table_frames
+#define SIM3_TPB 256       // k_sim3_project: one thread per (pair, direction, feature), pair and direction uniform per workgroup
+#define LOOP_TPB 256       // k_loop_project: one thread per (view, point), the view uniform per workgroup
+
+// What k_sim3_project reads of one direction of one pair: the source side's pose and ids, the Sim3 into the target, the intrinsics
+// (pKF1's for both directions), the target's bounds, feature count and levels
+struct Sim3View {
+    float Tsw[12], Sts[12], fx, fy, cx, cy, min_x, max_x, min_y, max_y;
+    int n, n_target, e0, side_t;                 // source / target feature counts; first flat entry; target side (0: kf1, 1: kf2)
+    const int* mp_id; const int* mark_i; const uint8_t* mark_b;      // MATCHED: mark_i[i] >= 0 (direction 1 -> 2) or mark_b[i] (2 -> 1)
+};
+struct Sim3Args {
+    int n_views, n_entries;                      // 2 * n_pairs; features of every side-1 handle, then of every side-2 handle
+    const Sim3View* views;
+    float log_scale[2]; int n_levels[2]; float scale[2][CCM_MAX_LEVELS]; float th;
+    int* sel; uint8_t* gate; float* u; float* v; int* level;         // per entry; gate / u / v / level may be nullptr
+    int* cnt; float* qx; float* qy; float* qr; int* minl; int* maxl; int* qview; int* qent; uint8_t* qdesc;   // the query list
+};
+// vbAlreadyMatched2 of pair p: am2[first2[p] + matched_idx2[i]] = 1 for the marked features i of side 1
+struct Sim3Pair { int n1, n2, first1, first2; };
+void sim3_launch_marks(hipStream_t, int n_pairs, int max_n1, const Sim3Pair* pairs, const int* matched12, const int* matched_idx2, uint8_t* am2);
+void sim3_launch_project(hipStream_t, const Sim3Args&, const MptTable&, int max_n);
+// match12[i1] = sel1[i1] where sel2[sel1[i1]] == i1 (sel2 = sel + n_side1)
+void sim3_launch_agree(hipStream_t, int n_pairs, int max_n1, const Sim3Pair* pairs, const int* sel, int n_side1, int* match12);
+
+struct LoopArgs {
+    int n_kf, n_points;
+    const FuseView* views; const int* slot;
+    const uint8_t* held; const uint8_t* found;   // [n_kf][n_points] from the where[] lookups
+    float log_scale; int n_levels; float scale[CCM_MAX_LEVELS]; float th;
+    // per pair, in list order: the queries of k_window_candidates / k_window_greedy and the taps
+    float* qx; float* qy; float* qr; int* none; int* qkf; int* qlevel; uint8_t* act; uint8_t* qdesc; int* out;
+    uint8_t* gate; float* u; float* v; int* level;
+};
+// per (view, feature): flag = matched_slot >= 0, oct (the views' octaves in one array), ms_out = matched_slot, found[k][position of
+// matched_slot in the list] = 1 by the stamped where[] of the table
+void loop_launch_marks(hipStream_t, int n_kf, int n_points, int max_n, const struct WinGrid* grids, const int* feat_first, const int* matched_slot,
+                       const unsigned long long* where, unsigned stamp, int capacity, uint8_t* flag, int* oct, int* ms_out, uint8_t* found);
+void loop_launch_project(hipStream_t, const LoopArgs&, const MptTable&);
+// after the acceptance: matched_slot[best_idx] = slot for the accepted points that are not observed; best_dist (optional)
+void loop_launch_finish(hipStream_t, int n_kf, int n_points, const struct WinGrid* grids, const int* feat_first, const int* slot, const int* out,
+                        const uint8_t* held, const MptTable&, int* ms_out, int* best_dist);
 // best_idx / best_dist of query q to pair qpair[q]
 void fuse_launch_scatter(hipStream_t, int nq, int n_pairs, const int* qpair, const int* sel_i, const int* sel_d, int* best_idx, int* best_dist);

@@ -351,6 +351,107 @@ def _fuse_select_table_frames(self, table, frames, Tcw, Ow, intr, bounds, slots,
 ORBmatcher.FuseSelectTableFrames = _fuse_select_table_frames
 
 
+def _log_sf(sf):
+    return np.float32(np.log(np.float64(sf[1]))) if len(sf) > 1 else np.float32(1.0)   # mfLogScaleFactor = log(mfScaleFactor)
+
+
+def _search_by_sim3_table_frames(self, table, pairs, scale_factors1, scale_factors2=None, th: float = 7.5, log_scale_factor1=None,
+                                 log_scale_factor2=None, taps: bool = False):
+    """ORBmatcher::SearchBySim3, complete, for a batch of candidate pairs with the map points read from a `tracking.MapPointTable` and
+    the keyframes given as DeviceFrame handles whose map_points are table slots (ccm_search_by_sim3_table_frames).  pairs: a list of
+    dicts kf1, kf2 (handles), T1w, T2w, S21, S12 ([12] or [3][4]: rows of [R | t], [sR21 | t21], [sR12 | t12]), intr (fx, fy, cx, cy of
+    kf1 -- used for BOTH directions, as the reference does), bounds1, bounds2 (mnMinX, mnMaxX, mnMinY, mnMaxY), and optionally
+    matched12 / matched_idx2 [N1] (default: none matched).  Returns a dict: match12 (a list of [N1] arrays), n_found (a list), total,
+    and with taps gate1 / u1 / v1 / level1 / sel1 and gate2 / ... / sel2 as lists per pair."""
+    a = np.ascontiguousarray
+    K = len(pairs)
+    sf1 = a(scale_factors1, "f4"); sf2 = sf1 if scale_factors2 is None else a(scale_factors2, "f4")
+    l1 = _log_sf(sf1) if log_scale_factor1 is None else log_scale_factor1
+    l2 = (_log_sf(sf2) if scale_factors2 is not None else l1) if log_scale_factor2 is None else log_scale_factor2
+    recs = (_lib.Sim3SearchPair * max(K, 1))()
+    keep = []
+    n1 = [p["kf1"].n for p in pairs]; n2 = [p["kf2"].n for p in pairs]
+    for k, p in enumerate(pairs):
+        R = recs[k]
+        R.kf1 = p["kf1"].handle; R.kf2 = p["kf2"].handle
+        for name in ("T1w", "T2w", "S21", "S12"):
+            getattr(R, name)[:] = [float(x) for x in a(p[name], "f4").reshape(12)]
+        R.fx, R.fy, R.cx, R.cy = [float(x) for x in p["intr"]]
+        R.bounds1[:] = [float(x) for x in p["bounds1"]]; R.bounds2[:] = [float(x) for x in p["bounds2"]]
+        m12 = a(p.get("matched12", np.full(n1[k], -1)), "i4").reshape(-1); mi2 = a(p.get("matched_idx2", np.full(n1[k], -1)), "i4").reshape(-1)
+        if len(m12) != n1[k] or len(mi2) != n1[k]:
+            raise ValueError("matched12 / matched_idx2 need one entry per feature of kf1")
+        keep += [m12, mi2]
+        R.matched12 = _lib.ptr(m12) if n1[k] else None; R.matched_idx2 = _lib.ptr(mi2) if n1[k] else None
+    prob = _lib.Sim3SearchProblem(K, recs, float(th), float(l1), len(sf1), _lib.ptr(sf1), float(l2), len(sf2), _lib.ptr(sf2))
+    s1, s2 = max(sum(n1), 1), max(sum(n2), 1)
+    out = dict(match12=np.full(s1, -1, "i4"), n_found=np.zeros(max(K, 1), "i4"))
+    if taps:
+        for d, s in (("1", s1), ("2", s2)):
+            out.update({"gate" + d: np.zeros(s, np.uint8), "u" + d: np.zeros(s, "f4"), "v" + d: np.zeros(s, "f4"), "level" + d: np.zeros(s, "i4"),
+                        "sel" + d: np.full(s, -1, "i4")})
+    g = lambda k: _lib.ptr(out[k]) if k in out else None  # noqa: E731
+    res = _lib.Sim3SearchResult(*[g(k) for k in ("match12", "n_found", "gate1", "u1", "v1", "level1", "sel1", "gate2", "u2", "v2", "level2", "sel2")])
+    total = self.ctx.check(self.lib.ccm_search_by_sim3_table_frames(self.ctx.handle, C.c_void_p(table.handle), C.byref(prob), C.byref(res)))
+    f1 = np.concatenate([[0], np.cumsum(n1)]).astype(int); f2 = np.concatenate([[0], np.cumsum(n2)]).astype(int)
+    ret = dict(total=int(total), n_found=[int(x) for x in out["n_found"][:K]])
+    for k, v in out.items():
+        if k != "n_found":
+            f = f2 if k.endswith("2") and k != "match12" else f1
+            ret[k] = [v[f[i]:f[i + 1]].copy() for i in range(K)]
+    return ret
+
+
+def _search_by_projection_table_frames(self, table, frames, Tcw, Ow, intr, bounds, slots, matched_slot, scale_factors, th: float = 10.0,
+                                       log_scale_factor=None, taps: bool = False):
+    """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) up to the acceptance with the points read from a
+    `tracking.MapPointTable` and the keyframes given as DeviceFrame handles (ccm_search_by_projection_table_frames): the ONE list
+    `slots` is projected into every view and accepted in list order.  Tcw [K][12], Ow [K][3], intr / bounds [K][4] or [4] as for
+    FuseSelectTableFrames (the caller decomposes Scw); matched_slot: per view [N_k], vpMatched on entry as slots or -1.  Returns a dict:
+    best_idx, observed ([K][n] arrays), matched_slot (a list of [N_k] arrays after the call), n_matches [K], total, and with taps gate,
+    u, v, level, best_dist ([K][n])."""
+    a = np.ascontiguousarray
+    K = len(frames)
+    slot = a(slots, "i4").reshape(-1); n = len(slot)
+    T = a(Tcw, "f4").reshape(K, 12); O = a(Ow, "f4").reshape(K, 3)
+    I = np.broadcast_to(a(intr, "f4").reshape(-1, 4), (K, 4)); B = np.broadcast_to(a(bounds, "f4").reshape(-1, 4), (K, 4))
+    sf = a(scale_factors, "f4")
+    if log_scale_factor is None:
+        log_scale_factor = _log_sf(sf)
+    views = (_lib.LoopView * max(K, 1))()
+    ms_in = [a(ms, "i4").reshape(-1) for ms in matched_slot]
+    nf = [f.n for f in frames]
+    for k, f in enumerate(frames):
+        if len(ms_in[k]) != nf[k]:
+            raise ValueError("matched_slot needs one entry per feature of the keyframe")
+        V = views[k].view
+        V.kf = f.handle
+        V.Tcw[:] = [float(x) for x in T[k]]; V.Ow[:] = [float(x) for x in O[k]]
+        V.fx, V.fy, V.cx, V.cy = [float(x) for x in I[k]]
+        V.min_x, V.max_x, V.min_y, V.max_y = [float(x) for x in B[k]]
+        views[k].matched_slot = _lib.ptr(ms_in[k]) if nf[k] else None
+    pad = slot if n else np.zeros(1, "i4")
+    prob = _lib.LoopProjectionProblem(K, views, n, _lib.ptr(pad), float(log_scale_factor), len(sf), _lib.ptr(sf), float(th))
+    m = max(K * n, 1)
+    out = dict(best_idx=np.full(m, -1, "i4"), observed=np.zeros(m, np.uint8), matched_slot=np.full(max(sum(nf), 1), -1, "i4"),
+               n_matches=np.zeros(max(K, 1), "i4"))
+    if taps:
+        out.update(gate=np.zeros(m, np.uint8), u=np.zeros(m, "f4"), v=np.zeros(m, "f4"), level=np.zeros(m, "i4"), best_dist=np.full(m, 256, "i4"))
+    g = lambda k: _lib.ptr(out[k]) if k in out else None  # noqa: E731
+    res = _lib.LoopProjectionResult(*[g(k) for k in ("best_idx", "observed", "matched_slot", "n_matches", "gate", "u", "v", "level", "best_dist")])
+    total = self.ctx.check(self.lib.ccm_search_by_projection_table_frames(self.ctx.handle, C.c_void_p(table.handle), C.byref(prob), C.byref(res)))
+    ff = np.concatenate([[0], np.cumsum(nf)]).astype(int)
+    ret = {k: v[:K * n].reshape(K, n) for k, v in out.items() if k not in ("matched_slot", "n_matches")}
+    ret["matched_slot"] = [out["matched_slot"][ff[k]:ff[k + 1]].copy() for k in range(K)]
+    ret["n_matches"] = out["n_matches"][:K].copy()
+    ret["total"] = int(total)
+    return ret
+
+
+ORBmatcher.SearchBySim3TableFrames = _search_by_sim3_table_frames
+ORBmatcher.SearchByProjectionTableFrames = _search_by_projection_table_frames
+
+
 def _search_by_sim3(self, kf1: FrameGridView, sf1, kf2: FrameGridView, sf2, valid1, u1, v1, level1, mp_desc1, valid2, u2, v2, level2, mp_desc2,
                     th: float):
     """ORBmatcher::SearchBySim3 (ORBmatcher.cpp:1124-1348) after the caller's projections.  Returns (nFound, match12)."""

@@ -11,13 +11,19 @@
 // that owns the candidate loop (src/LoopFinder.cpp:251-282) gets all candidates into one launch by filling one
 // ccm_sim3_ransac_problem itself.  ccm_shim::search_by_bow_candidates below is the step in front of that batch: the
 // SearchByBoW(mpCurrentKF, pKF, ...) calls of the same loop (src/LoopFinder.cpp:265, src/MapMatcher.cpp:271) as one
-// ccm_search_by_bow_frames call over all candidates.
+// ccm_search_by_bow_frames call over all candidates; ccm_shim::search_by_sim3_on_table and search_by_projection_on_table are the two
+// matchers behind the solver (SearchBySim3 for all candidates in one call, SearchByProjection(pKF, Scw, ...)) on keyframe handles and
+// the map-point table.  They need the table in the calling thread's context, as Fuse on the table does; elsewhere they decline and the
+// caller's ORBmatcher call takes the array route.
 #include <cslam/Sim3Solver.h>
 #include <cslam/KeyFrame.h>
 #include <cslam/MapPoint.h>
+#include <cslam/ORBmatcher.h>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include "ccm_shim.h"
+#include "fuse_steps.h"
 
 namespace ccm_shim {
 
@@ -131,6 +137,129 @@ std::vector<int> search_by_bow_candidates(const cslam::Sim3Solver::kfptr& pKF1, 
         }
     }
     return result;
+}
+
+static void rows_of(const cv::Mat& R, const cv::Mat& t, float out[12])
+{
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) out[4 * r + c] = R.at<float>(r, c);
+        out[4 * r + 3] = t.at<float>(r);
+    }
+}
+
+// Link 3 of ComputeSim3 (src/LoopFinder.cpp:300-330, src/MapMatcher.cpp:307-337): matcher.SearchBySim3(pKF1, candidates[i],
+// vvpMatches12[i], s12[i], R12[i], t12[i], th) for every candidate the caller hands over, in ONE ccm_search_by_sim3_table_frames.  The
+// keyframes travel as handles whose map-point ids are table slots (handle_of), the points are read from the table; only the entry
+// marks go up, 8 bytes a feature of pKF1.  The intrinsics are pKF1's for both directions, as in the reference (:1127-1130).
+bool search_by_sim3_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<ORBmatcher::kfptr>& candidates,
+                             std::vector<std::vector<ORBmatcher::mpptr>>& vvpMatches12, const std::vector<float>& s12, const std::vector<cv::Mat>& R12,
+                             const std::vector<cv::Mat>& t12, float th, KeyframeHandleOf handle_of, std::vector<int>& found)
+{
+    typedef ORBmatcher::mpptr mpptr;
+    const int K = (int)candidates.size();
+    if (vvpMatches12.size() != candidates.size() || s12.size() != candidates.size() || R12.size() != candidates.size() || t12.size() != candidates.size())
+        return false;
+    ccm_map_table* table = map_table_here();
+    if (!table) return false;
+    ccm_frame* h1 = handle_of(pKF1);
+    if (!h1) return false;
+    const int n1 = (int)pKF1->GetMapPointMatches().size();
+    std::vector<ccm_sim3_search_pair> pairs(K);
+    std::vector<std::vector<int32_t>> m12(K), mi2(K);
+    std::vector<std::vector<mpptr>> mps2(K);
+    const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation();
+    for (int k = 0; k < K; k++) {
+        const ORBmatcher::kfptr& pKF2 = candidates[k];
+        ccm_sim3_search_pair& P = pairs[k];
+        P.kf1 = h1;
+        if (!(P.kf2 = handle_of(pKF2)) || (int)vvpMatches12[k].size() != n1) return false;
+        mps2[k] = pKF2->GetMapPointMatches();
+        const cv::Mat sR12 = s12[k] * R12[k], sR21 = (1.0 / s12[k]) * R12[k].t(), t21 = -sR21 * t12[k];    // :1141-1143
+        rows_of(R1w, t1w, P.T1w); rows_of(pKF2->GetRotation(), pKF2->GetTranslation(), P.T2w);
+        rows_of(sR21, t21, P.S21); rows_of(sR12, t12[k], P.S12);
+        P.fx = pKF1->fx; P.fy = pKF1->fy; P.cx = pKF1->cx; P.cy = pKF1->cy;
+        P.bounds1[0] = pKF1->mnMinX; P.bounds1[1] = pKF1->mnMaxX; P.bounds1[2] = pKF1->mnMinY; P.bounds1[3] = pKF1->mnMaxY;
+        P.bounds2[0] = pKF2->mnMinX; P.bounds2[1] = pKF2->mnMaxX; P.bounds2[2] = pKF2->mnMinY; P.bounds2[3] = pKF2->mnMaxY;
+        m12[k].assign(std::max(n1, 1), -1); mi2[k].assign(std::max(n1, 1), -1);
+        for (int i = 0; i < n1; i++) {                                         // :1154-1164
+            const mpptr& pMP = vvpMatches12[k][i];
+            if (!pMP) continue;
+            const int s = map_slot_of(pMP);
+            m12[k][i] = s >= 0 ? s : 0;                                        // only "there is a point" is read
+            mi2[k][i] = pMP->GetIndexInKeyFrame(pKF2);
+        }
+        P.matched12 = m12[k].data(); P.matched_idx2 = mi2[k].data();
+    }
+    std::vector<int32_t> match12((size_t)K * std::max(n1, 1), -1), n_found(std::max(K, 1), 0);
+    if (K > 0) {
+        const ORBmatcher::kfptr& pKF2 = candidates[0];                         // one client's keyframes share the extractor's scale tables
+        const ccm_sim3_search_problem p{K, pairs.data(), th, pKF1->mfLogScaleFactor, (int32_t)pKF1->mvScaleFactors.size(), pKF1->mvScaleFactors.data(),
+                                        pKF2->mfLogScaleFactor, (int32_t)pKF2->mvScaleFactors.size(), pKF2->mvScaleFactors.data()};
+        ccm_sim3_search_result r{};
+        r.match12 = match12.data(); r.n_found = n_found.data();
+        if (ccm_search_by_sim3_table_frames(ctx(), table, &p, &r) < 0) return false;
+    }
+    found.assign(K, 0);
+    for (int k = 0; k < K; k++) {
+        found[k] = n_found[k];
+        for (int i = 0; i < n1; i++) {                                         // :1337-1342
+            const int32_t i2 = match12[(size_t)k * n1 + i];
+            if (i2 >= 0) vvpMatches12[k][i] = mps2[k][i2];
+        }
+    }
+    return true;
+}
+
+// Link 5 (src/LoopFinder.cpp:372, src/MapMatcher.cpp:380): matcher.SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints,
+// mvpCurrentMatchedPoints, 10) in ONE ccm_search_by_projection_table_frames.  Nothing is projected on the host; the loop points travel
+// as slots and vpMatched as one slot per feature.  The remap of an accepted point the keyframe already observes (:414-435) is made
+// here from best_idx and observed, in list order as the reference does.
+bool search_by_projection_on_table(const ORBmatcher::kfptr& pKF, const cv::Mat& Scw, const std::vector<ORBmatcher::mpptr>& vpPoints,
+                                   std::vector<ORBmatcher::mpptr>& vpMatched, int th, KeyframeHandleOf handle_of, int& nmatches)
+{
+    typedef ORBmatcher::mpptr mpptr;
+    ccm_map_table* table = map_table_here();
+    ccm_frame* h = table ? handle_of(pKF) : nullptr;
+    if (!table || !h) return false;
+    const int n = (int)vpPoints.size(), N = (int)vpMatched.size();
+    std::vector<int32_t> slot(std::max(n, 1), -1), ms(std::max(N, 1), -1);
+    std::map<int, int> seen;
+    for (int i = 0; i < n; i++) {
+        const int s = vpPoints[i] ? map_slot_of(vpPoints[i]) : -1;
+        if (s < 0 || !seen.emplace(s, i).second) return false;                 // a point without a slot, or listed twice: the array route
+        slot[i] = s;
+    }
+    for (int i = 0; i < N; i++)
+        if (vpMatched[i]) { const int s = map_slot_of(vpMatched[i]); if (s < 0) return false; ms[i] = s; }
+    ccm_loop_view V{};
+    V.view.kf = h;
+    cv::Mat sRcw = Scw.rowRange(0, 3).colRange(0, 3);                           // :317-321
+    const float scw = sqrt(sRcw.row(0).dot(sRcw.row(0)));
+    cv::Mat Rcw = sRcw / scw, tcw = Scw.rowRange(0, 3).col(3) / scw, Ow = -Rcw.t() * tcw;
+    rows_of(Rcw, tcw, V.view.Tcw);
+    for (int r = 0; r < 3; r++) V.view.Ow[r] = Ow.at<float>(r);
+    V.view.fx = pKF->fx; V.view.fy = pKF->fy; V.view.cx = pKF->cx; V.view.cy = pKF->cy;
+    V.view.min_x = pKF->mnMinX; V.view.max_x = pKF->mnMaxX; V.view.min_y = pKF->mnMinY; V.view.max_y = pKF->mnMaxY;
+    V.matched_slot = ms.data();
+    const ccm_loop_projection_problem p{1, &V, n, slot.data(), pKF->mfLogScaleFactor, (int32_t)pKF->mvScaleFactors.size(), pKF->mvScaleFactors.data(), (float)th};
+    std::vector<int32_t> best(std::max(n, 1), -1), ms_out(std::max(N, 1), -1);
+    std::vector<uint8_t> observed(std::max(n, 1), 0);
+    int32_t nm = 0;
+    ccm_loop_projection_result r{};
+    r.best_idx = best.data(); r.observed = observed.data(); r.matched_slot = ms_out.data(); r.n_matches = &nm;
+    if (ccm_search_by_projection_table_frames(ctx(), table, &p, &r) < 0) return false;
+    for (int i = 0; i < n; i++) {
+        if (best[i] < 0) continue;
+        const mpptr& pMP = vpPoints[i];
+        if (!observed[i]) { vpMatched[best[i]] = pMP; continue; }               // :439
+        const int existing_idx = pMP->GetIndexInKeyFrame(pKF);                  // :415-434
+        if (existing_idx == -1) continue;
+        // :420-429 recomputes DescriptorDistance(dMP, row bestIdx), which is bestDist itself, and asks whether it is smaller than
+        // bestDist: bDoNotReplace stays false
+        pKF->RemapMapPointMatch(pMP, existing_idx, best[i]);
+    }
+    nmatches = nm;
+    return true;
 }
 
 }  // namespace ccm_shim

@@ -272,6 +272,17 @@ public:
                 if (row_of[i] >= 0) best[(size_t)k * n + i] = sel[(size_t)k * m + row_of[i]];
         return true;
     }
+    // The table, flushed, when it lives in the calling thread's context; nullptr on any other thread (a table and the handles used with
+    // it belong to one context): ComputeSim3's matchers on handles (cslam_sim3solver.cpp) then take the array route.
+    ccm_map_table* here()
+    {
+        ccm_ctx* c = ctx();
+        {
+            std::lock_guard<std::mutex> lock(mMutex);
+            if (!mTable || mCtx != c) return nullptr;
+        }
+        return flush();
+    }
     // The slots in view of the previous SearchLocalPoints: Frame::isInFrustum clears mbTrackInView of every point it tests, so a
     // point that was in view and is rejected now must not keep a stale `true`.
     std::vector<int32_t> mLastInView;
@@ -295,6 +306,8 @@ bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, Key
 }
 
 int map_slot_of(const ORBmatcher::mpptr& pMP) { return pMP ? MapTable::get().slot_of(pMP) : -1; }
+
+ccm_map_table* map_table_here() { return MapTable::get().here(); }
 
 bool fuse_select_on_table(const std::vector<ORBmatcher::kfptr>& kfs, const std::vector<FusePose>& poses, const std::vector<ORBmatcher::mpptr>& pts,
                           float th, int chi2_check, int accept_th, KeyframeHandleOf handle_of, std::vector<int32_t>& best)

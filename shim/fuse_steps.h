@@ -89,6 +89,20 @@ bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, Key
 // The slot of pMP in the calling process's map-point table, or -1 (ccm_shim::MapTable::slot_of, cslam_tracking.cpp).  A keyframe handle
 // that is to serve fuse_select_on_table carries these in its map-point ids.
 int map_slot_of(const ORBmatcher::mpptr& pMP);
+// The process's map-point table with every queued row sent, when it lives in the calling thread's context; else nullptr.  One table
+// serves one context: a thread with another context takes the array routes.
+ccm_map_table* map_table_here();
+
+// ComputeSim3's two matchers on keyframe handles and the table (defined in cslam_sim3solver.cpp; INTEGRATION.md "ComputeSim3 on
+// handles").  Both return false with nothing touched when the table is not in the calling context, a point has no slot or a handle is
+// missing: the caller then makes the reference's call, which takes the array route (cslam_orbmatcher.cpp).
+// SearchBySim3(pKF1, candidates[i], vvpMatches12[i], s12[i], R12[i], t12[i], th) for every candidate in ONE call; found[i] = nFound.
+bool search_by_sim3_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<ORBmatcher::kfptr>& candidates,
+                             std::vector<std::vector<ORBmatcher::mpptr>>& vvpMatches12, const std::vector<float>& s12, const std::vector<cv::Mat>& R12,
+                             const std::vector<cv::Mat>& t12, float th, KeyframeHandleOf handle_of, std::vector<int>& found);
+// SearchByProjection(pKF, Scw, vpPoints, vpMatched, th), RemapMapPointMatch (:414-435) included; nmatches = its return value.
+bool search_by_projection_on_table(const ORBmatcher::kfptr& pKF, const cv::Mat& Scw, const std::vector<ORBmatcher::mpptr>& vpPoints,
+                                   std::vector<ORBmatcher::mpptr>& vpMatched, int th, KeyframeHandleOf handle_of, int& nmatches);
 
 // The projection, the gates and the selection of ORBmatcher::Fuse (:870-955, :1018-1101) for every keyframe of kfs and every point of
 // pts in ONE ccm_fuse_select_table_frames on the map-point table: nothing is projected on the host and nothing is uploaded per pair.
