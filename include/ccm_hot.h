@@ -122,7 +122,15 @@ int ccm_orb_extract(ccm_ctx*, const ccm_orb_params*, const uint8_t* img, int w, 
 
 /* Device-resident variant: img_dev is a device pointer; results stay on the
  * device (fetch with ccm_orb_fetch) so that ccm_hamming_match_dev can consume
- * the descriptors without a PCIe round trip.  The call is asynchronous on the
+ * the descriptors without a PCIe round trip.  The call is asynchronous and
+ * ordered on the context's stream: it starts after everything queued there
+ * before it, and whatever is queued there after it sees the whole batch.
+ * Inside the call a large batch is extracted in chunks of frames that alternate
+ * between the context's stream and one auxiliary stream of the context (forked
+ * from and joined back to the context's stream before the call returns, also
+ * when it fails), so that one chunk's quadtree kernel runs beside the other
+ * chunk's FAST or descriptor kernel.  Small batches, a single frame among them,
+ * and every call while ccm_profile_enable is on run as one chunk on the
  * context's stream.  An image with more than max_per_image keypoints is
  * reported by the next ccm_orb_fetch, which returns CCM_E_CAPACITY and copies
  * nothing; counts_dev (ccm_orb_result_dev) then holds the counts clamped to
@@ -143,6 +151,11 @@ int ccm_orb_debug_level(ccm_ctx*, int image, int level, uint8_t* out, int out_st
  * vToDistributeKeys is filled (ORBextractor.cpp:957-998): xy[2*i], xy[2*i+1]
  * relative to minBorderX/Y as there, score[i].  Returns the count (>= 0) or an error. */
 int ccm_orb_debug_candidates(ccm_ctx*, int image, int level, int32_t* xy, int32_t* score, int max);
+/* The chunks ccm_orb_extract_dev splits a batch of n_images frames into (host only, no GPU): chunk i is frames
+ * [frame0[i], frame0[i] + nrun[i]) on lane[i] (0 = the context's stream, 1 = the auxiliary stream).  out_per_frame is the
+ * geometry's number of keypoint slots per frame, lane_frames the configured frames per chunk (CCM_ORB_LANE_FRAMES; 0 = one
+ * chunk).  Writes at most max entries (any array may be NULL) and returns the number of chunks, or an error. */
+int ccm_orb_debug_lane_plan(int n_images, int out_per_frame, int lane_frames, int32_t* frame0, int32_t* nrun, int32_t* lane, int max);
 
 /* ------------------------------------------------------------------ matcher
  * ORBmatcher::DescriptorDistance (cslam/src/ORBmatcher.cpp:1653-1669): host helper. */

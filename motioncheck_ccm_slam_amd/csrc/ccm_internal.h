@@ -113,7 +113,9 @@ template <class F> int ccm_guard(ccm_ctx* c, const char* name, F&& body) noexcep
     catch (...) { return c ? ccm_fail(c, CCM_E_DEVICE, "%s: unknown exception", name) : CCM_E_DEVICE; }
 }
 
-// Brackets the launches issued while it is alive with two events when profiling is on.
+// Brackets the launches issued while it is alive with two events when profiling is on.  Both events go to c->stream, and what
+// bench.py --full sums from them into per-kernel and roofline figures are the times of kernels running ALONE: a caller that spreads
+// its launches over a second stream (the extractor's two lanes, orb_extract_lanes in orb_host.cpp) keeps to c->stream while prof_on.
 struct ProfScope {
     ccm_ctx* c; int label; hipEvent_t stop = nullptr;
     ProfScope(ccm_ctx* ctx, int lab) : c(ctx), label(lab)

@@ -73,6 +73,39 @@ void linear_tables(int ssize, int dsize, std::vector<int>& ofs, std::vector<shor
     }
 }
 
+// A chunk of the device path's two-lane schedule (orb_extract_lanes below): frames [frame0, frame0 + nrun) on lane 0 (the context's
+// stream) or lane 1 (the auxiliary stream).
+struct OrbChunk { int frame0, nrun, lane; };
+
+// The chunks of a batch of n_images frames.  Pure: no HIP call, no state (ccm_orb_debug_lane_plan exports it to a CPU test).
+//   lane_frames  the configured frames per chunk; 0 = one chunk
+//   minimum      a chunk is never smaller than the batch at which orb_launch_orient_desc switches to its eight-slots-per-wave form
+//                (out_per_frame * frames >= 4 * 8192, 30 frames of the bench geometry): below it a chunk would run the slower <1> form.
+//                Only a lane_frames below that size lowers the minimum, to lane_frames (the tests' switch).
+//   count        ceil(n_images / lane_frames) chunks, but no more than fit at the minimum size; a batch below two minimum chunks, or
+//                within one chunk of the configured size, is ONE chunk on lane 0 -- today's schedule launch for launch (the single
+//                frame Tracking extracts per call among them)
+//   sizes        the even division of the host-buffer path: chunk k is [n k / chunks, n (k + 1) / chunks), sizes differ by at most one
+//   lanes        0, 1, 0, 1, ...
+inline int orb_switch_frames(int out_per_frame) { return (4 * 8192 + std::max(out_per_frame, 1) - 1) / std::max(out_per_frame, 1); }
+
+std::vector<OrbChunk> orb_lane_plan(int n_images, int out_per_frame, int lane_frames)
+{
+    std::vector<OrbChunk> plan;
+    if (n_images <= 0) return plan;
+    int chunks = 1;
+    if (lane_frames > 0) {
+        const int min_frames = std::min(orb_switch_frames(out_per_frame), lane_frames);
+        chunks = std::min((n_images + lane_frames - 1) / lane_frames, n_images / min_frames);
+        if (chunks < 2) chunks = 1;
+    }
+    for (int k = 0; k < chunks; k++) {
+        const int f0 = (int)((long long)n_images * k / chunks), f1 = (int)((long long)n_images * (k + 1) / chunks);
+        plan.push_back(OrbChunk{ f0, f1 - f0, k & 1 });
+    }
+    return plan;
+}
+
 }  // namespace
 
 struct OrbState {
@@ -84,6 +117,9 @@ struct OrbState {
     std::vector<OrbCell> cells;
     std::vector<OrbBand> bands; size_t band_lds = 0; bool fused = true; hipStream_t copy_stream = nullptr; hipEvent_t copy_done = nullptr;
     hipStream_t down_stream = nullptr; hipEvent_t chunk_done = nullptr;      // results of a chunk go down while the next chunk is extracted
+    // the device path's second lane (orb_extract_lanes): the context's aux[1] and the events of the fork and of the join, created once
+    // and without timing
+    hipStream_t lane_stream = nullptr; hipEvent_t lane_fork = nullptr, lane_join = nullptr;
     DevBuf geom_dev, cells_dev, tables_dev, bands_dev;
     DevBuf pyr, smap, slots, cell_count, keysA, keysB, sel, sel_count, status;
     DevBuf img0;                   // staging for the host-pointer entry point
@@ -98,6 +134,7 @@ void orb_state_free(OrbState* s)
     if (!s) return;
     if (s->copy_done) (void)hipEventDestroy(s->copy_done);
     if (s->chunk_done) (void)hipEventDestroy(s->chunk_done);
+    for (hipEvent_t e : { s->lane_fork, s->lane_join }) if (e) (void)hipEventDestroy(e);
     delete s;
 }
 
@@ -291,8 +328,12 @@ static int orb_prepare(ccm_ctx* c, const ccm_orb_params* p, int w, int h, int nf
     return CCM_OK;
 }
 
-// Runs the pipeline on frames [frame0, frame0 + nrun) of the prepared batch (all of it by default).
-static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_stride, int frame0 = 0, int nrun = -1)
+// Enqueues the pipeline on frames [frame0, frame0 + nrun) of the prepared batch (all of it by default) on stream st (the context's
+// by default).  The launches of a chunk depend on each other only through stream order; everything they read or write is indexed by
+// absolute frame (see orb_extract_lanes), so chunks of different frames may run on different streams at the same time.
+// first_done, if given, is recorded behind the chunk's first kernel -- the one that clears the status word.
+static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_stride, int frame0 = 0, int nrun = -1,
+                   hipStream_t st = nullptr, hipEvent_t first_done = nullptr)
 {
     OrbState& S = *c->orb;
     OrbGeom& G = S.geom;
@@ -300,20 +341,22 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
     G.lv[0].img = img_dev; G.lv[0].pitch = stride; G.lv[0].plane = (long long)image_stride;
     G.frame0 = frame0;
     if (nrun < 0) nrun = S.nframes - frame0;
+    if (!st) st = c->stream;
     const OrbGeom& gd = G;
     const OrbCell* cd = S.cells_dev.as<OrbCell>();
-    hipStream_t st = c->stream;
-    // The status word is cleared by the call's first chunk only (the chunked host-buffer path accumulates it over its chunks), and by
+    // The status word is cleared by the call's first chunk only (the later chunks of a call accumulate into it), and by
     // the first kernel of the chain rather than by a fill dispatch of its own: the first resize, or k_fast_cells for a one-level pyramid.
     int* clear = frame0 == 0 ? S.status.as<int>() : nullptr;
     for (int l = 1; l < G.nlevels; l++) {
         ProfScope ps(c, CCM_PROF_RESIZE);
         orb_launch_resize(st, gd, l, G.lv[l].w, G.lv[l].h, nrun, clear);
         clear = nullptr;
+        if (l == 1 && first_done) CCM_HIP(c, hipEventRecord(first_done, st));
     }
     if (S.fused && !S.bands.empty()) {
         ProfScope ps(c, CCM_PROF_FAST_SCORE);
         orb_launch_fast_cells(st, gd, cd, S.bands_dev.as<OrbBand>(), (int)S.bands.size(), nrun, S.band_lds, S.slots.as<unsigned>(), S.cell_count.as<int>(), clear);
+        if (G.nlevels == 1 && first_done) CCM_HIP(c, hipEventRecord(first_done, st));
     } else {
         if (clear) CCM_HIP(c, hipMemsetAsync(clear, 0, 4, st));          // (one level through the two-kernel FAST path: not worth a kernel argument)
         { ProfScope ps(c, CCM_PROF_FAST_SCORE); orb_launch_score(st, gd, G.ntiles, nrun); }
@@ -330,6 +373,68 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
     CCM_HIP(c, hipGetLastError());
     S.have_result = true;
     return CCM_OK;
+}
+
+// The device path's schedule (ccm_orb_extract_dev): the prepared batch in the chunks of orb_lane_plan, alternating between two lanes --
+// lane 0 is the context's stream, lane 1 its auxiliary stream aux[1] (shared, default priority; no stream is created for this: see
+// ccm_ctx::aux for what a fifth stream cost).  k_octree leaves the GPU nearly empty for its whole run (the barrier chain inside one
+// (frame, level 0) workgroup, a few workgroups per CU) and cannot overlap anything of its own chunk, every kernel of which depends on
+// the one before; frames are independent, so one chunk's k_octree runs beside the other lane's k_fast_cells or k_orient_desc, and the
+// small pyramid levels, kernel tails and launch gaps of one lane beside the other lane's work.
+//   fork     lane 1's first wait is for an event recorded on the context's stream behind chunk 0's FIRST kernel: everything the
+//            caller queued before the call (the previous step's matcher still reading S.desc, readers of a frame made by
+//            ccm_frame_from_extract, the previous call's own join) and the clearing of the status word, which that kernel does, precede
+//            every kernel of either lane -- later chunks only ever atomicOr into the status word
+//   offset   none but the fork's: lane 1 starts one resize launch behind lane 0 and shares the GPU with it from there on, which leaves
+//            the lanes 40-55 us apart at their k_octree.  Measured against it and dropped (profiles/orb_lanes_ab.txt):
+//            chunk k + 1's k_fast_cells waiting for chunk k's, the fork behind a later resize, an uneven pair of chunks, 3, 4 and 8 chunks.
+//   join     the context's stream waits for lane 1's last launch before the call returns, on the error path as well: ccm_orb_fetch, the
+//            matcher on ccm_orb_result_dev, orb_last_result, the debug taps and ccm_sync see the whole batch and no lane
+// The events are created once, without timing, and every wait is enqueued after the record it means.
+// What makes concurrent chunks safe, checked kernel by kernel and launcher by launcher: all six kernels take their frame as a block
+// index plus OrbGeom::frame0 (k_pyr_resize z, k_fast_cells / k_orient_desc the remapped y, k_octree x, k_fast_score / k_cell_nms y) and
+// the geometry travels by value with each launch; pyramid levels, slots, cell_count, keysA / keysB (also beyond OCT_LDS_KEYS:
+// f * keys_per_frame + key_first), sel, sel_count, kps, desc and counts are indexed by that absolute frame; the bilinear tables, cells,
+// bands and the BRIEF pattern are read-only.  The one word shared by all frames is S.status: cleared once in front of the fork, atomicOr
+// afterwards.  The score map of the two-kernel FAST path is per frame too by its indexing, but that path has not been run on two lanes
+// and stays on one, as do calls while profiling is on: ProfScope brackets launches with events on the context's stream, and the
+// per-kernel and roofline figures of bench.py --full made from them must stay the times of kernels running alone.
+static int orb_extract_lanes(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_stride)
+{
+    OrbState& S = *c->orb;
+    // Frames per chunk: CCM_ORB_LANE_FRAMES as it is (tests, A/B timing; 0 = one lane), else 128 -- the 256 bench frames are two chunks;
+    // a k_octree takes 45 us for 64 frames and 76 us for 256, so every further chunk adds more of it than the lanes hide -- and never
+    // below the descriptor kernel's switch point.
+    static const int lane_env = getenv("CCM_ORB_LANE_FRAMES") ? std::max(0, atoi(getenv("CCM_ORB_LANE_FRAMES"))) : -1;
+    const int lane_frames = lane_env >= 0 ? lane_env : std::max(128, orb_switch_frames(S.geom.out_per_frame));
+    const bool one_lane = c->prof_on || !S.fused || S.bands.empty();
+    const std::vector<OrbChunk> plan = orb_lane_plan(S.nframes, S.geom.out_per_frame, one_lane ? 0 : lane_frames);
+    if (plan.size() < 2) return orb_run(c, img_dev, stride, image_stride);
+    if (!S.lane_join) {                                 // (created last: with it, the stream and both events exist)
+        if (!(S.lane_stream = ccm_aux_stream(c, 1))) return ccm_fail(c, CCM_E_DEVICE, "hipStreamCreate failed");
+        for (hipEvent_t* e : { &S.lane_fork, &S.lane_join })
+            if (!*e) CCM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    int rc = CCM_OK;
+    bool forked = false;
+    for (size_t k = 0; k < plan.size() && rc == CCM_OK; k++) {
+        const OrbChunk& ck = plan[k];
+        if (k == 1) {                                   // (the fork event was recorded when chunk 0 was enqueued)
+            hipError_t e = hipStreamWaitEvent(S.lane_stream, S.lane_fork, 0);
+            if (e != hipSuccess) { rc = ccm_fail(c, CCM_E_DEVICE, "hipStreamWaitEvent -> %s", hipGetErrorString(e)); break; }
+            forked = true;
+        }
+        rc = orb_run(c, img_dev, stride, image_stride, ck.frame0, ck.nrun, ck.lane ? S.lane_stream : c->stream, k == 0 ? S.lane_fork : nullptr);
+    }
+    if (forked) {                                       // whatever happened above, nothing of lane 1 runs on behind the call
+        hipError_t e = hipEventRecord(S.lane_join, S.lane_stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, S.lane_join, 0);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(S.lane_stream);  // (no event to wait for: hold the caller instead)
+            if (rc == CCM_OK) rc = ccm_fail(c, CCM_E_DEVICE, "joining the extractor's lanes -> %s", hipGetErrorString(e));
+        }
+    }
+    return rc;
 }
 
 static int orb_check_status(ccm_ctx* c)
@@ -399,7 +504,21 @@ int ccm_orb_extract_dev(ccm_ctx* c, const ccm_orb_params* p, const uint8_t* img_
         CCM_HIP(c, hipSetDevice(c->device));
         int rc = orb_prepare(c, p, w, h, n_images, max_per_image);
         if (rc) return rc;
-        return orb_run(c, img_dev, stride, image_stride);
+        return orb_extract_lanes(c, img_dev, stride, image_stride);
+    });
+}
+
+int ccm_orb_debug_lane_plan(int n_images, int out_per_frame, int lane_frames, int32_t* frame0, int32_t* nrun, int32_t* lane, int max)
+{
+    return ccm_guard(nullptr, "ccm_orb_debug_lane_plan", [&]() -> int {
+        if (n_images < 0 || out_per_frame < 1 || lane_frames < 0 || max < 0) return CCM_E_ARG;
+        const std::vector<OrbChunk> plan = orb_lane_plan(n_images, out_per_frame, lane_frames);
+        for (size_t k = 0; k < plan.size() && k < (size_t)max; k++) {
+            if (frame0) frame0[k] = plan[k].frame0;
+            if (nrun) nrun[k] = plan[k].nrun;
+            if (lane) lane[k] = plan[k].lane;
+        }
+        return (int)plan.size();
     });
 }
 

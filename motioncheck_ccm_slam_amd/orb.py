@@ -15,6 +15,18 @@ from . import _lib
 from ._lib import KP_DTYPE, OrbParams
 
 
+def lane_plan(n_images: int, out_per_frame: int, lane_frames: int):
+    """The chunks [(frame0, nrun, lane)] the device path splits a batch into (ccm_orb_debug_lane_plan; host only, no GPU)."""
+    lib = _lib.load()
+    cap = max(int(n_images), 1)
+    f0 = np.zeros(cap, "i4"); nr = np.zeros(cap, "i4"); ln = np.zeros(cap, "i4")
+    n = lib.ccm_orb_debug_lane_plan(int(n_images), int(out_per_frame), int(lane_frames), _lib.ptr(f0), _lib.ptr(nr), _lib.ptr(ln), cap)
+    if n < 0:
+        raise _lib.CcmError(n, "bad lane plan arguments")
+    assert n <= cap
+    return [(int(f0[k]), int(nr[k]), int(ln[k])) for k in range(n)]
+
+
 class ORBextractor:
     def __init__(self, nfeatures: int, scaleFactor: float, nlevels: int, iniThFAST: int, minThFAST: int,
                  ctx: _lib.Context | None = None, max_per_image: int | None = None):
