@@ -551,8 +551,27 @@ int ccm_search_by_bow_frames(ccm_ctx*, const ccm_frame* kf1, int n_kf2, ccm_fram
  * mfMinDistance / mfMaxDistance (the factors 0.8 / 1.2 of GetMin/MaxDistanceInvariance, src/MapPoint.cpp, are applied on the
  * device; PredictScale uses the raw maximum), desc = GetDescriptor(), flags = CCM_MP_*.  A fresh table holds zeros (no slot LIVE).
  * The table also keeps one `seen` stamp per slot that only ccm_frame_search_local_points writes.
- * Ownership as for frames: a table belongs to the context that made it (another context: CCM_E_ARG); after ccm_destroy it accepts
- * only ccm_map_table_destroy and ccm_map_table_capacity, every other call returns CCM_E_STATE. */
+ * Ownership as for frames: a table handle belongs to the context that made it (another context: CCM_E_ARG); after ccm_destroy it
+ * accepts only ccm_map_table_destroy, ccm_map_table_capacity and ccm_map_table_handles, every other call returns CCM_E_STATE.
+ *
+ * Table views.  The reference runs Tracking, LocalMapping, LoopFinder, MapMatcher and MapMerger on threads of their own, each with a
+ * context of its own, and all of them work on one map.  ccm_map_table_attach gives a context a handle of its own (a view) on the
+ * ROWS of an existing table; a view is used exactly like a table, with the view's context, by every call that takes a table:
+ * ccm_map_table_update, _set_order, _fetch, _refresh, ccm_frame_search_local_points, ccm_frame_pose_optimize_table,
+ * ccm_frame_track_motion_model, ccm_fuse_select_table_frames, ccm_search_by_sim3_table_frames and
+ * ccm_search_by_projection_table_frames.  The frame handles and vocabularies such a call names belong to that same context.
+ *   Shared between the handles of the same rows: the columns pos, normal, min_dist, max_dist, desc and flags, and the capacity.
+ *   Owned by each handle: the `seen` column and its stamp (ccm_map_table_fetch returns the calling handle's), the visiting order
+ *   (ccm_map_table_set_order), and the scratch of the Fuse and ComputeSim3 calls.
+ *   Visibility: rows written through one handle (ccm_map_table_update, ccm_map_table_refresh) are seen by every call through any
+ *   handle that starts after the writing call has returned, also where that call returned without synchronising (_update, and
+ *   _refresh without a result): the later call's stream is made to wait for the write.
+ *   Concurrency: calls on handles of the same rows may be made from different threads at the same time, each thread with its own
+ *   context.  A call that writes rows excludes every other call on those rows for its duration, calls that only read them overlap,
+ *   and the outcome equals that of some serial order of the calls.  Two threads still never share one context or one handle.
+ *   Lifetime: the rows live until their last handle is destroyed or orphaned.  Destroying the first table leaves its views working;
+ *   ccm_destroy of a context orphans that context's handles only.
+ * A table nobody attached to behaves and costs as before: it records no event and waits for none. */
 enum { CCM_MP_LIVE = 1,      /* the slot is in use */
        CCM_MP_BAD = 2,       /* MapPoint::isBad() */
        CCM_MP_HAS_OBS = 4 }; /* Observations() > 0 */
@@ -560,6 +579,14 @@ typedef struct ccm_map_table ccm_map_table;
 int  ccm_map_table_create(ccm_ctx*, int capacity, ccm_map_table** out);   /* capacity >= 1 */
 void ccm_map_table_destroy(ccm_map_table*);                               /* NULL is a no-op */
 int  ccm_map_table_capacity(const ccm_map_table*);                        /* or CCM_E_ARG for NULL */
+/* A further handle, owned by context c, on the ROWS of `table` (which may itself be such a handle).  c may be the context of `table`:
+ * a second handle with scratch of its own.  Called on c's thread; it touches nothing of the other context (the first attach to a
+ * table waits once for the device, so that rows written before it are seen).  CCM_E_ARG: a NULL argument, a context on another
+ * device.  CCM_E_STATE: `table` outlived its context.  On any failure *view = NULL.  Destroy a view with ccm_map_table_destroy. */
+int  ccm_map_table_attach(ccm_ctx* c, ccm_map_table* table, ccm_map_table** view);
+/* Test tap: the number of live handles that share this handle's rows (1 for a table nobody attached to); CCM_E_ARG for NULL, 0 for
+ * an orphan. */
+int  ccm_map_table_handles(const ccm_map_table*);
 /* Rows to write.  A NULL column keeps that column of the listed slots (bundle adjustment moves positions only, culling changes
  * flags only).  A slot listed twice takes its last row. */
 typedef struct {

@@ -39,7 +39,7 @@ SYMBOLS = [
     "ccm_frame_pose_optimize",
     "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
-    "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
+    "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_map_table_attach", "ccm_map_table_handles", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
     "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model",
     "ccm_search_by_sim3_table_frames", "ccm_search_by_projection_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
@@ -368,6 +368,8 @@ def load():
     lib.ccm_map_table_create.argtypes = [vp, C.c_int, C.POINTER(vp)]
     lib.ccm_map_table_destroy.argtypes = [vp]; lib.ccm_map_table_destroy.restype = None
     lib.ccm_map_table_capacity.argtypes = [vp]
+    lib.ccm_map_table_attach.argtypes = [vp, vp, C.POINTER(vp)]
+    lib.ccm_map_table_handles.argtypes = [vp]
     lib.ccm_map_table_update.argtypes = [vp, vp, C.POINTER(MapUpdate)]
     lib.ccm_map_table_set_order.argtypes = [vp, vp, C.c_int, vp]
     lib.ccm_map_table_fetch.argtypes = [vp, vp, C.c_int] + [vp] * 8

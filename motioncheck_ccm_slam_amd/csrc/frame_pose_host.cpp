@@ -88,7 +88,7 @@ int ccm_frame_pose_optimize_table(ccm_ctx* c, ccm_frame* f, ccm_map_table* t, co
     if (!intr || !pose7 || !n_inliers || (f->n > 0 && (!outlier || !inv_level_sigma2 || n_levels < 1)))
         return ccm_fail(c, CCM_E_ARG, "bad pose arguments");
     if (f->n == 0) { *n_inliers = 0; return CCM_OK; }
-    return ccm_guard(c, "ccm_frame_pose_optimize_table", [&]() -> int {
+    return table_call(c, t, false, "ccm_frame_pose_optimize_table", [&]() -> int {
         bool bad_id = false;
         if ((rc = frame_pose_run(c, f, t->T.capacity, nullptr, t->T.pos, t->T.flags, inv_level_sigma2, n_levels, intr, pose7, outlier, n_inliers, &bad_id)))
             return rc;

@@ -27,7 +27,7 @@ int ccm_fuse_select_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_fuse_ta
     if ((r->u || r->v || r->level) && !(r->u && r->v && r->level)) return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and level come together", fn);
     if (p->n_kf > 65535 || (size_t)p->n_kf * (size_t)p->n_points > ((size_t)1 << 24))
         return ccm_fail(c, CCM_E_CAPACITY, "%s: %d keyframes x %d points; at most 65535 keyframes and 2^24 pairs a call", fn, p->n_kf, p->n_points);
-    return ccm_guard(c, fn, [&]() -> int {
+    return table_call(c, t, false, fn, [&]() -> int {                          // writes the handle's own where[] only
         const int n_kf = p->n_kf, n_pt = p->n_points;
         int max_n = 0;
         for (int k = 0; k < n_kf; k++) {

@@ -3,11 +3,26 @@
 // call stages through the frame handles' block: update [ slot | the given columns ] up, fetch [ columns ] down and [ slot ] up.
 #include "mpt_internal.h"
 #include <cstddef>
+#include <memory>
+
+// The handle gives its reference to the rows back: per-handle memory goes now, the rows with their last handle.  A write of c's that
+// is still pending was waited for by the caller (ccm_destroy) or stays recorded in the rows' event (ccm_map_table_destroy).
+static void table_release(ccm_map_table* t, bool ctx_going)
+{
+    if (!t->rows) return;
+    {
+        std::unique_lock<std::shared_mutex> lk(t->rows->mu);
+        if (ctx_going && t->rows->writer == t->ctx) t->rows->writer = nullptr;     // ccm_destroy has waited for the stream
+        t->rows->handles--;
+    }
+    t->rows.reset();                             // hipFree waits for the work still queued on the columns
+}
 
 void mpt_tables_orphan(FrameState* S)            // ccm_destroy: the memory goes, the handles stay for ccm_map_table_destroy
 {
     for (ccm_map_table* t : S->tables) {
         const int cap = t->capacity;
+        table_release(t, true);
         *t = ccm_map_table();
         t->capacity = cap;
     }
@@ -29,18 +44,53 @@ int ccm_map_table_create(ccm_ctx* c, int capacity, ccm_map_table** out)
         size_t off = 0;
         const size_t o_pos = seg(off, m * 12), o_nrm = seg(off, m * 12), o_min = seg(off, m * 4), o_max = seg(off, m * 4);
         const size_t o_desc = seg(off, m * 32), o_flags = seg(off, m), o_seen = seg(off, m * 4);
-        ccm_map_table* t = new ccm_map_table();
-        if (t->mem.reserve(off)) { delete t; return ccm_fail(c, CCM_E_NOMEM, "map-point table: device alloc of %zu bytes failed", off); }
-        uint8_t* b = t->mem.as<uint8_t>();
-        if (hipMemsetAsync(b, 0, off, c->stream) != hipSuccess) { (void)hipGetLastError(); delete t; return ccm_fail(c, CCM_E_DEVICE, "map-point table: clearing failed"); }
-        t->ctx = c; t->capacity = capacity;
-        t->T = MptTable{ capacity, (float*)(b + o_pos), (float*)(b + o_nrm), (float*)(b + o_min), (float*)(b + o_max), b + o_desc, b + o_flags,
+        std::unique_ptr<ccm_map_table> t(new ccm_map_table());
+        std::shared_ptr<MptRows> R = std::make_shared<MptRows>();
+        if (R->mem.reserve(off)) return ccm_fail(c, CCM_E_NOMEM, "map-point table: device alloc of %zu bytes failed", off);
+        uint8_t* b = R->mem.as<uint8_t>();
+        if (hipMemsetAsync(b, 0, off, c->stream) != hipSuccess) { (void)hipGetLastError(); return ccm_fail(c, CCM_E_DEVICE, "map-point table: clearing failed"); }
+        R->device = c->device; R->capacity = capacity; R->handles = 1;
+        R->T = MptTable{ capacity, (float*)(b + o_pos), (float*)(b + o_nrm), (float*)(b + o_min), (float*)(b + o_max), b + o_desc, b + o_flags,
                          (int*)(b + o_seen) };
-        S.tables.push_back(t);
-        *out = t;
+        t->ctx = c; t->capacity = capacity; t->T = R->T; t->rows = std::move(R);
+        S.tables.push_back(t.get());
+        *out = t.release();
         return CCM_OK;
     });
 }
+
+// A further handle on the rows of `table`, with scratch of its own.  Called on c's thread; of the other context it reads nothing.
+int ccm_map_table_attach(ccm_ctx* c, ccm_map_table* table, ccm_map_table** view)
+{
+    RoctxRange roctx_("ccm_map_table_attach");
+    if (view) *view = nullptr;
+    if (!c || !table || !view) return CCM_E_ARG;
+    if (!table->ctx || !table->rows) return ccm_fail(c, CCM_E_STATE, "ccm_map_table_attach: the table outlived its context");
+    return ccm_guard(c, "ccm_map_table_attach", [&]() -> int {
+        std::shared_ptr<MptRows> R = table->rows;
+        if (R->device != c->device) return ccm_fail(c, CCM_E_ARG, "ccm_map_table_attach: the table lies on device %d, the context on %d", R->device, c->device);
+        CCM_HIP(c, hipSetDevice(c->device));
+        FrameState& S = *frame_state(c);
+        std::unique_ptr<ccm_map_table> t(new ccm_map_table());
+        const size_t seen_bytes = (size_t)R->capacity * 4;
+        CCM_RESERVE(c, t->seen_mem, seen_bytes);
+        CCM_HIP(c, hipMemsetAsync(t->seen_mem.p, 0, seen_bytes, c->stream));
+        t->ctx = c; t->capacity = R->capacity; t->T = R->T; t->T.seen = t->seen_mem.as<int>();
+        {
+            // Writes made while the rows had one handle recorded no event: the first further handle waits for the device once, and
+            // every write after it finds two handles (the count changes under the exclusive lock the writers hold)
+            std::unique_lock<std::shared_mutex> lk(R->mu);
+            if (R->handles.load() == 1) CCM_HIP(c, hipDeviceSynchronize());
+            R->handles++;
+        }
+        t->rows = std::move(R);
+        S.tables.push_back(t.get());
+        *view = t.release();
+        return CCM_OK;
+    });
+}
+
+int ccm_map_table_handles(const ccm_map_table* t) { return !t ? CCM_E_ARG : t->rows ? t->rows->handles.load() : 0; }
 
 void ccm_map_table_destroy(ccm_map_table* t)
 {
@@ -51,7 +101,8 @@ void ccm_map_table_destroy(ccm_map_table* t)
             v.erase(std::remove(v.begin(), v.end(), t), v.end());
             (void)hipSetDevice(t->ctx->device);
         }
-        delete t;                                // hipFree waits for the work still queued on the columns
+        table_release(t, false);
+        delete t;                                // hipFree waits for the work still queued on the handle's own columns
     } catch (...) {}
 }
 
@@ -65,7 +116,7 @@ int ccm_map_table_update(ccm_ctx* c, ccm_map_table* t, const ccm_map_update* u)
     if (rc) return rc;
     if (u->n < 0 || (u->n > 0 && !u->slot)) return ccm_fail(c, CCM_E_ARG, "bad map-point update (n < 0 or no slot list)");
     if (u->n == 0) return CCM_OK;
-    return ccm_guard(c, "ccm_map_table_update", [&]() -> int {
+    return table_call(c, t, true, "ccm_map_table_update", [&]() -> int {         // writes rows and returns with the scatter queued
         const size_t n = (size_t)u->n;
         bool dup = false;
         if ((rc = mark_slots(c, t, u->n, u->slot, &dup))) return rc;
@@ -126,7 +177,7 @@ int ccm_map_table_fetch(ccm_ctx* c, ccm_map_table* t, int n, const int32_t* slot
     if (rc) return rc;
     if (n < 0 || (n > 0 && !slot)) return ccm_fail(c, CCM_E_ARG, "bad fetch arguments");
     if (n == 0) return CCM_OK;
-    return ccm_guard(c, "ccm_map_table_fetch", [&]() -> int {
+    return table_call(c, t, false, "ccm_map_table_fetch", [&]() -> int {
         for (int r = 0; r < n; r++)
             if (slot[r] < 0 || slot[r] >= t->capacity) return ccm_fail(c, CCM_E_ARG, "slot %d (entry %d) outside [0, %d)", slot[r], r, t->capacity);
         CCM_HIP(c, hipSetDevice(c->device));
@@ -168,7 +219,8 @@ int ccm_map_table_refresh(ccm_ctx* c, ccm_map_table* t, const ccm_map_refresh* u
     if (u->n > 0 && (!u->slot || !u->obs_first || (nd && (!u->ref_kf || !u->ref_feat))))
         return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !u->slot ? "slot" : !u->obs_first ? "obs_first" : !u->ref_kf ? "ref_kf" : "ref_feat");
     if (u->n == 0) return CCM_OK;
-    return ccm_guard(c, fn, [&]() -> int {
+    bool synced = false;                                                       // writes rows; with a result it waits for them
+    return table_call(c, t, true, fn, [&]() -> int {
         const int n = u->n, n_kf = u->n_kf;
         if (u->obs_first[0] != 0) return ccm_fail(c, CCM_E_ARG, "%s: obs_first[0] = %d, not 0", fn, u->obs_first[0]);
         for (int p = 0; p < n; p++)
@@ -248,10 +300,11 @@ int ccm_map_table_refresh(ccm_ctx* c, ccm_map_table* t, const ccm_map_refresh* u
         CCM_HIP(c, hipGetLastError());
         if (!res || (!res->best && !res->normal && !res->min_dist && !res->max_dist)) return CCM_OK;
         if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;
+        synced = true;
         G.get(res->best, o_best, m * 4); G.get(res->normal, o_nrm, m * 12);
         G.get(res->min_dist, o_min, m * 4); G.get(res->max_dist, o_max, m * 4);
         return CCM_OK;
-    });
+    }, &synced);
 }
 
 }  // extern "C"

@@ -1,17 +1,42 @@
 // mpt_internal.h -- what the host translation units of the map-point table share: mpt_host.cpp (the table itself and its refresh),
-// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_track_host.cpp (SearchLocalPoints, TrackWithMotionModel) and frame_pose_host.cpp (the
-// pose on table points).  Every call stages through the frame handles' block (FrameState::stage, frame_internal.h).
+// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_track_host.cpp (SearchLocalPoints,
+// TrackWithMotionModel) and frame_pose_host.cpp (the pose on table points).  Every call stages through the frame handles' block (FrameState::stage, frame_internal.h).
 #pragma once
 #include "frame_internal.h"
 #include "mpt_types.h"
+#include <atomic>
+#include <memory>
+#include <mutex>
+#include <shared_mutex>
+
+// The rows of a table: the shared columns pos | normal | min_dist | max_dist | desc | flags (and, in the same block, the `seen` column
+// of the handle that created them).  Every handle on them (ccm_map_table_create, ccm_map_table_attach) holds one reference; the memory
+// goes with the last one.  Handles of several contexts, each on a thread of its own, may name the same rows:
+//   mu       a call whose kernels write a shared column (ccm_map_table_update, _refresh) holds it exclusively from entry to return, a
+//            call that only reads them holds it shared; the handle count changes under the exclusive lock
+//   written  "last unsynchronised write": recorded on the writer's stream when a writing call returns with its kernels still queued
+//            and the rows have more than one handle; a call of another context makes its stream wait for it before it queues anything
+//   writer   the context that recorded `written`, nullptr when nothing is pending (read under either lock, changed under the exclusive one)
+// Reading calls return synchronised (they download their result), so a writer finds no reader's work queued on the rows.
+struct MptRows {
+    int device = 0, capacity = 0;
+    DevBuf mem;                                  // the columns, one block
+    MptTable T{};                                // seen: the creating handle's column
+    std::shared_mutex mu;
+    hipEvent_t written = nullptr;
+    ccm_ctx* writer = nullptr;
+    std::atomic<int> handles{ 0 };
+    ~MptRows() { if (written) (void)hipEventDestroy(written); }
+};
 
 struct ccm_map_table {
     ccm_ctx* ctx = nullptr;                      // nullptr once the context is gone
     int capacity = 0;
-    DevBuf mem;                                  // the columns, one block
-    MptTable T{};
+    std::shared_ptr<MptRows> rows;               // empty once the context is gone
+    MptTable T{};                                // the rows' columns and this handle's seen
+    DevBuf seen_mem;                             // a view's own seen column (the creating handle's lies in the rows' block)
     DevBuf order; int n_order = 0; bool order_all = true;    // order_all: ascending slot over the LIVE slots
-    int stamp = 0;                               // per-table call counter of SearchLocalPoints: seen[slot] == stamp <=> seen in this call
+    int stamp = 0;                               // per-handle call counter of SearchLocalPoints: seen[slot] == stamp <=> seen in this call
     std::vector<uint32_t> gen; std::vector<int32_t> row; uint32_t cur_gen = 0;   // host: last row of a slot within one update / order
     DevBuf where; unsigned fuse_stamp = 0;       // ccm_fuse_select_table_frames: per slot, stamp << 32 | position in that call's slot list
 };
@@ -21,6 +46,58 @@ static inline int check_table(ccm_ctx* c, const ccm_map_table* t)
     if (!t->ctx) return ccm_fail(c, CCM_E_STATE, "map-point table outlived its context");
     if (t->ctx != c) return ccm_fail(c, CCM_E_ARG, "map-point table belongs to another context");
     return CCM_OK;
+}
+
+// The lock a table call holds on its rows, taken inside ccm_guard (a failing lock throws) and held from there to the return.  A call
+// names one table, so there is no lock order.
+struct RowsLock {
+    ccm_ctx* c; MptRows* R; const bool write; bool synced = false;       // synced stays false when the body throws
+    RowsLock(ccm_ctx* ctx, ccm_map_table* t, bool writes) : c(ctx), R(t->rows.get()), write(writes)
+    {
+        if (write) R->mu.lock(); else R->mu.lock_shared();
+    }
+    // Another context's unsynchronised write runs before whatever this call queues
+    int wait()
+    {
+        if (!R->writer || R->writer == c) return CCM_OK;
+        CCM_HIP(c, hipSetDevice(c->device));     // the body has not run yet
+        CCM_HIP(c, hipStreamWaitEvent(c->stream, R->written, 0));
+        return CCM_OK;
+    }
+    // synced: the call waited for its stream after its last launch.  A reading call always has when it succeeds; one that failed between
+    // a launch and its wait may have left work queued on the rows, which the next writer must not overtake.
+    ~RowsLock()
+    {
+        const bool shared = R->handles.load() > 1;       // an unshared table records nothing and waits for nothing
+        if (!write) {
+            if (!synced && shared) (void)hipStreamSynchronize(c->stream);
+            R->mu.unlock_shared();
+            return;
+        }
+        if (synced) R->writer = nullptr;
+        else if (shared) {
+            bool ok = R->written || hipEventCreateWithFlags(&R->written, hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipEventRecord(R->written, c->stream) == hipSuccess;
+            if (!ok) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); }      // no event: nothing may stay pending
+            R->writer = ok ? c : nullptr;
+        }
+        R->mu.unlock();
+    }
+    RowsLock(const RowsLock&) = delete; RowsLock& operator=(const RowsLock&) = delete;
+};
+
+// An entry point's body under ccm_guard and the lock on the table's rows.  write: its kernels write a shared column.  A reading body
+// returns synchronised unless it fails; a writing body sets *synced when it waited for its stream behind its last launch.
+template <class F> int table_call(ccm_ctx* c, ccm_map_table* t, bool write, const char* name, F&& body, const bool* synced = nullptr)
+{
+    return ccm_guard(c, name, [&]() -> int {
+        RowsLock L(c, t, write);
+        int rc = L.wait();
+        if (rc) return rc;
+        rc = body();
+        L.synced = rc >= 0 && (write ? synced && *synced : true);
+        return rc;
+    });
 }
 
 // Marks every slot of list [n] with its last position; CCM_E_ARG for a slot outside the table.  dup: whether a slot occurs twice.

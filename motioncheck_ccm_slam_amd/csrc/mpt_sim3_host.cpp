@@ -42,7 +42,7 @@ int ccm_search_by_sim3_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_sim3
     if (((r->u1 || r->v1 || r->level1) && !(r->u1 && r->v1 && r->level1)) || ((r->u2 || r->v2 || r->level2) && !(r->u2 && r->v2 && r->level2)))
         return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and level of a direction come together", fn);
     if (p->n_pairs > 32767) return ccm_fail(c, CCM_E_CAPACITY, "%s: %d pairs; at most 32767 a call", fn, p->n_pairs);
-    return ccm_guard(c, fn, [&]() -> int {
+    return table_call(c, t, false, fn, [&]() -> int {
         const int n_pairs = p->n_pairs, n_views = 2 * n_pairs;
         std::vector<Sim3Pair> pr(n_pairs);
         size_t sum1 = 0, sum2 = 0;
@@ -172,7 +172,7 @@ int ccm_search_by_projection_table_frames(ccm_ctx* c, ccm_map_table* t, const cc
     if ((r->u || r->v || r->level) && !(r->u && r->v && r->level)) return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and level come together", fn);
     if (p->n_kf > 65535 || (size_t)p->n_kf * (size_t)p->n_points > ((size_t)1 << 24))
         return ccm_fail(c, CCM_E_CAPACITY, "%s: %d views x %d points; at most 65535 views and 2^24 pairs a call", fn, p->n_kf, p->n_points);
-    return ccm_guard(c, fn, [&]() -> int {
+    return table_call(c, t, false, fn, [&]() -> int {                          // writes the handle's own where[] only
         const int n_kf = p->n_kf, n_pt = p->n_points;
         std::vector<int> ff(n_kf + 1, 0);
         int max_n = 0;

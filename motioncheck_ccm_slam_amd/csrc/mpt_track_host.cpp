@@ -27,7 +27,7 @@ int ccm_frame_search_local_points(ccm_ctx* c, ccm_frame* f, ccm_map_table* t, co
     clk::time_point t_before, t_after;
     bool timed = false;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const int ret = ccm_guard(c, "ccm_frame_search_local_points", [&]() -> int {
+    const int ret = table_call(c, t, false, "ccm_frame_search_local_points", [&]() -> int {    // writes the handle's own seen only
         CCM_HIP(c, hipSetDevice(c->device));
         FrameState& S = *frame_state(c);
         hipStream_t st = c->stream;
@@ -151,7 +151,7 @@ int ccm_frame_track_motion_model(ccm_ctx* c, ccm_frame* cur, const ccm_frame* la
     if (last->n_levels > p->n_levels || (pose && cur->n_levels > p->n_levels))
         return ccm_fail(c, CCM_E_ARG, "%s: octaves up to %d in %s, n_levels = %d", fn, (last->n_levels > p->n_levels ? last : cur)->n_levels - 1,
                         last->n_levels > p->n_levels ? "last" : "cur", p->n_levels);
-    return ccm_guard(c, fn, [&]() -> int {
+    return table_call(c, t, false, fn, [&]() -> int {
         CCM_HIP(c, hipSetDevice(c->device));
         FrameState& S = *frame_state(c);
         hipStream_t st = c->stream;

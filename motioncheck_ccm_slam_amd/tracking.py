@@ -26,6 +26,21 @@ class MapPointTable:
         self.handle = h.value
         self.capacity = self.lib.ccm_map_table_capacity(C.c_void_p(self.handle))
 
+    def attach(self, ctx: _lib.Context) -> "MapPointTable":
+        """A view of `ctx` on this table's rows (ccm_map_table_attach): the same methods, used with `ctx` on its own thread; the `seen`
+        stamps, the visiting order and the per-call scratch are the view's own.  `close()` destroys only that handle; the rows live as
+        long as any handle on them."""
+        h = C.c_void_p()
+        ctx.check(self.lib.ccm_map_table_attach(ctx.handle, C.c_void_p(self.handle), C.byref(h)))
+        view = MapPointTable.__new__(MapPointTable)
+        view.ctx = ctx; view.lib = ctx.lib; view.handle = h.value
+        view.capacity = view.lib.ccm_map_table_capacity(C.c_void_p(view.handle))
+        return view
+
+    def handles(self) -> int:
+        """Live handles on this table's rows (ccm_map_table_handles): 1 for a table nobody attached to, 0 once its context is gone."""
+        return self.lib.ccm_map_table_handles(C.c_void_p(self.handle))
+
     def update(self, slot, pos=None, normal=None, min_dist=None, max_dist=None, desc=None, flags=None):
         """Write rows (ccm_map_table_update); a column left None keeps its values."""
         a = np.ascontiguousarray

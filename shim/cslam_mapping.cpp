@@ -12,7 +12,7 @@
 // ids and the pose are sent again, when the keyframe's stamp (ccm_shim.h, INTEGRATION.md "Keyframe handles") says they changed.
 // CreateNewMapPoints then calls ccm_create_new_map_points_frames.  SearchInNeighbors runs right after on the same keyframes: its
 // first Fuse loop (:499-504) becomes one call of ccm_shim::fuse_into_targets (below, declared in fuse_steps.h), which makes ONE
-// ccm_fuse_select_table_frames on the map-point table (or, where the table is another thread's, projects on the host and makes ONE
+// ccm_fuse_select_table_frames on this thread's view of the map-point table (or, where that declines, projects on the host and makes ONE
 // ccm_fuse_select_batch_frames); the integrator replaces that loop in src/Mapping.cpp, the rest of the function stays the reference's.
 //
 // One difference in timing, none in result: the match of a later neighbour is computed before an earlier neighbour's points exist.
@@ -229,8 +229,8 @@ void LocalMapping::CreateNewMapPoints()
             created.push_back(pMP);
         }
         // ComputeDistinctiveDescriptors and UpdateNormalAndDepth (:461-463) of this neighbour's points in one ccm_map_table_refresh on
-        // the handles used above, still in front of Map::AddMapPoint as in the reference; point by point where the table belongs to
-        // another thread's context (ccm_shim::MapTable::refresh)
+        // the handles used above and this thread's view of the table, still in front of Map::AddMapPoint as in the reference; point by
+        // point where that declines (ccm_shim::MapTable::refresh)
         if (!(handles && ccm_shim::refresh_map_points(created, CCM_MPR_DESCRIPTOR | CCM_MPR_NORMAL_DEPTH, &keyframe_handle))) {
             for (const mpptr& pMP : created) {
                 pMP->ComputeDistinctiveDescriptors();
@@ -250,7 +250,7 @@ void LocalMapping::CreateNewMapPoints()
 // The first Fuse loop of LocalMapping::SearchInNeighbors (src/Mapping.cpp:499-504) on keyframe handles.  First choice: ONE
 // ccm_fuse_select_table_frames projects the current keyframe's map points into every target keyframe, gates and selects on the
 // device, reading the points from the map-point table (ccm_shim::fuse_select_on_table, fuse_steps.h).  Where that is not possible --
-// the table belongs to another thread's context, or a point has no slot yet -- the points are projected on the host and ONE
+// there is no table yet, the view cannot be attached, or a point has no slot yet -- the points are projected on the host and ONE
 // ccm_fuse_select_batch_frames selects for all keyframes.  Either way a second-level neighbour can be listed twice (:486-493), and so
 // can its handle, and the results are applied keyframe by keyframe in the list's order with the reference's state checks repeated at
 // application time (apply_fuse).  With CCM_SHIM_KEYFRAME_HANDLES=0 it is the loop of

@@ -13,8 +13,9 @@
 // SearchByBoW(mpCurrentKF, pKF, ...) calls of the same loop (src/LoopFinder.cpp:265, src/MapMatcher.cpp:271) as one
 // ccm_search_by_bow_frames call over all candidates; ccm_shim::search_by_sim3_on_table and search_by_projection_on_table are the two
 // matchers behind the solver (SearchBySim3 for all candidates in one call, SearchByProjection(pKF, Scw, ...)) on keyframe handles and
-// the map-point table.  They need the table in the calling thread's context, as Fuse on the table does; elsewhere they decline and the
-// caller's ORBmatcher call takes the array route.
+// the map-point table.  They take the calling thread's handle on the table (map_table_here: on LoopFinder's and MapMatcher's threads a
+// view of the rows the tracking thread's table holds), as Fuse on the table does; without one they decline and the caller's ORBmatcher
+// call takes the array route.
 #include <cslam/Sim3Solver.h>
 #include <cslam/KeyFrame.h>
 #include <cslam/MapPoint.h>

@@ -27,9 +27,15 @@ namespace ccm_shim {
 
 // The slot map of one client's map: slot <-> map point, filled where map points are created and erased.  Slots are handed out in
 // creation order and reused after an erase.  The visiting order of SearchLocalPoints is the order of Map::mmpMapPoints (a std::map
-// keyed by idpair, src/Map.cpp:416-424); it is sent again only when the set of points has changed.  One table per tracking thread:
-// the hooks run in other threads (LocalMapping, Communicator), so they only queue rows under the mutex, and the tracking thread
-// sends them with ccm_map_table_update before it searches.
+// keyed by idpair, src/Map.cpp:416-424); it is sent again only when the set of points has changed.  The hooks run in any thread
+// (LocalMapping, Communicator), so they only queue rows under the mutex; whichever thread next works on the table sends them with
+// ccm_map_table_update through its own handle before its call.
+// One table, a handle per thread: the tracking thread's first flush() makes the table (the root handle, in that thread's context).  Every
+// other thread -- LocalMapping, LoopFinder, MapMatcher, MapMerger, each with a context of its own -- works through a thread_local view
+// (ccm_map_table_attach), attached on first use.  Only the root's thread replaces the table by a bigger one; the generation number tells
+// the other threads to attach again, and the old rows live for as long as a view of them does, so nobody is stopped for the growth (a
+// call that runs on an old view meanwhile sees the map as it was before).  The visiting order belongs to a handle, so "order dirty" is
+// kept per handle, and only a thread that searches local points sends it.
 class MapTable {
 public:
     using mpptr = cslam::Tracking::mpptr;
@@ -48,7 +54,7 @@ public:
         else {
             if (!mFree.empty()) { slot = mFree.back(); mFree.pop_back(); }
             else { slot = (int)mPoints.size(); mPoints.push_back(nullptr); mRows.push_back(Row{}); }
-            mSlotOf[pMP->mId] = slot; mPoints[slot] = pMP; mOrderDirty = true;
+            mSlotOf[pMP->mId] = slot; mPoints[slot] = pMP; mOrderStamp++;
         }
         Row r;
         r.slot = slot;
@@ -70,7 +76,7 @@ public:
         r.slot = it->second; r.flags = 0;
         mQueue.push_back(r);
         mRows[it->second] = r;
-        mPoints[it->second] = nullptr; mFree.push_back(it->second); mSlotOf.erase(it); mOrderDirty = true;
+        mPoints[it->second] = nullptr; mFree.push_back(it->second); mSlotOf.erase(it); mOrderStamp++;
     }
     int slot_of(const mpptr& pMP)
     {
@@ -83,28 +89,29 @@ public:
         std::lock_guard<std::mutex> lock(mMutex);
         return slot >= 0 && slot < (int)mPoints.size() ? mPoints[slot] : nullptr;
     }
-    // Whether the table lives in context c: a table and the frame handles used with it belong to one context
-    bool in_context(ccm_ctx* c)
-    {
-        std::lock_guard<std::mutex> lock(mMutex);
-        return mTable && mCtx == c;
-    }
-    // The tracking thread, before it searches: the queued rows and, when the set of points changed, the order.  Returns the table.
-    ccm_map_table* flush()
+    // Before a call on the table: the queued rows and, with_order (SearchLocalPoints), the visiting order when the set of points changed
+    // since this thread's handle last received it.  Returns the calling thread's handle: the root on the thread whose context made the
+    // table, this thread's view elsewhere; nullptr when the table must grow and this is not the root's thread (the tracking thread's next
+    // flush replaces it), or when a call fails.
+    ccm_map_table* flush(bool with_order = false)
     {
         std::lock_guard<std::mutex> lock(mMutex);
         ccm_ctx* c = ctx();
         const int need = (int)mPoints.size();
         if (!mTable || ccm_map_table_capacity(mTable) < need) {                // grow: a new table, the last row of every live slot again
+            if (mTable && c != mCtx) return nullptr;                           // a handle is destroyed on its own context's thread
             ccm_map_table* bigger = nullptr;
             if (ccm_map_table_create(c, std::max(2 * need, 65536), &bigger)) return nullptr;
-            ccm_map_table_destroy(mTable);
-            mTable = bigger; mCtx = c; mOrderDirty = true;
+            ccm_map_table_destroy(mTable);                                     // the old rows stay until the last view of them is gone
+            mTable = bigger; mCtx = c; mGeneration++; mRootOrder = 0;
             std::vector<Row> all;
             for (int s = 0; s < need; s++) if (mPoints[s]) all.push_back(mRows[s]);     // bad points that still own a slot included
             all.insert(all.end(), mQueue.begin(), mQueue.end());                         // rows queued by other threads stay behind them
             mQueue.swap(all);
         }
+        uint64_t* order_sent = nullptr;
+        ccm_map_table* h = handle_locked(c, &order_sent);
+        if (!h) return nullptr;
         const int n = (int)mQueue.size();
         if (n > 0) {
             std::vector<int32_t> slot(n); std::vector<float> pos(3 * (size_t)n), normal(3 * (size_t)n), mn(n), mx(n);
@@ -116,33 +123,31 @@ public:
                 for (int k = 0; k < 32; k++) desc[32 * (size_t)i + k] = r.desc[k];
             }
             const ccm_map_update u{n, slot.data(), pos.data(), normal.data(), mn.data(), mx.data(), desc.data(), flags.data()};
-            if (ccm_map_table_update(c, mTable, &u)) return nullptr;
+            if (ccm_map_table_update(c, h, &u)) return nullptr;                // seen by every handle's later calls (ccm_hot.h "Table views")
             mQueue.clear();
         }
-        if (mOrderDirty) {
+        if (with_order && *order_sent != mOrderStamp) {
             std::vector<int32_t> order;
             order.reserve(mSlotOf.size());
             for (const auto& kv : mSlotOf) order.push_back(kv.second);         // ascending idpair, as mmpMapPoints
-            if (ccm_map_table_set_order(c, mTable, (int)order.size(), order.empty() ? &mZero : order.data())) return nullptr;
-            mOrderDirty = false;
+            if (ccm_map_table_set_order(c, h, (int)order.size(), order.empty() ? &mZero : order.data())) return nullptr;
+            *order_sent = mOrderStamp;
         }
-        return mTable;
+        return h;
     }
     // MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth for pts in one ccm_map_table_refresh: the observation lists are
     // built from GetObservations() in the map's own order without the bad keyframes (src/MapPoint.cpp:803, :952), the device reads
     // the descriptors, camera centres and scale factors from the keyframe handles and writes the table's columns, and the one download
     // gives what the MapPoint objects keep: MapPoint::StoreRefreshed (INTEGRATION.md "Map-point table") assigns mDescriptor,
     // mNormalVector, mfMinDistance and mfMaxDistance at the hook position without calling put(), and the row copy kept here is brought
-    // up to date instead: no row travels a second time.  A table and its handles belong to one context, so this runs on the thread
-    // that owns the table; on any other thread it returns false and touches nothing.  Points the call cannot express stay with the
-    // reference's functions: a bad point (both return at once) and a point whose observing keyframes are all bad (normal / 0).
+    // up to date instead: no row travels a second time.  It runs on any thread, through that thread's handle on the table (flush());
+    // it returns false and touches nothing before the tracking thread has made the table, when the view cannot be attached, or when a
+    // keyframe has no handle in this thread's context.  Points the call cannot express stay with the reference's functions: a bad point
+    // (both return at once) and a point whose observing keyframes are all bad (normal / 0).
     bool refresh(const std::vector<mpptr>& pts, int what, KeyframeHandleOf handle_of)
     {
         ccm_ctx* c = ctx();
-        {
-            std::lock_guard<std::mutex> lock(mMutex);
-            if (!mTable || mCtx != c) return false;                              // the tracking thread's first flush makes the table
-        }
+        if (!exists()) return false;                                             // the tracking thread's first flush makes the table
         typedef cslam::Tracking::kfptr kfptr;
         std::vector<mpptr> use;
         std::vector<int32_t> obs_first(1, 0), obs_kf, obs_feat, ref_kf, ref_feat;
@@ -216,16 +221,13 @@ public:
         return true;
     }
     // ORBmatcher::Fuse up to the selection for every (keyframe, point) pair in one ccm_fuse_select_table_frames (fuse_steps.h,
-    // fuse_select_on_table).  As refresh(): only on the thread that owns the table, rows queued earlier are flushed first, and on any
+    // fuse_select_on_table).  As refresh(): on any thread through its own handle, rows queued earlier are flushed first, and on any
     // failure nothing of the caller's is touched.
     bool fuse_select(const std::vector<cslam::Tracking::kfptr>& kfs, const std::vector<FusePose>& poses, const std::vector<mpptr>& pts, float th,
                      int chi2_check, int accept_th, KeyframeHandleOf handle_of, std::vector<int32_t>& best)
     {
         ccm_ctx* c = ctx();
-        {
-            std::lock_guard<std::mutex> lock(mMutex);
-            if (!mTable || mCtx != c) return false;
-        }
+        if (!exists()) return false;
         const int n_kf = (int)kfs.size(), n = (int)pts.size();
         if (poses.size() != kfs.size()) return false;
         std::vector<int32_t> slot, row_of(n, -1);
@@ -272,22 +274,38 @@ public:
                 if (row_of[i] >= 0) best[(size_t)k * n + i] = sel[(size_t)k * m + row_of[i]];
         return true;
     }
-    // The table, flushed, when it lives in the calling thread's context; nullptr on any other thread (a table and the handles used with
-    // it belong to one context): ComputeSim3's matchers on handles (cslam_sim3solver.cpp) then take the array route.
-    ccm_map_table* here()
-    {
-        ccm_ctx* c = ctx();
-        {
-            std::lock_guard<std::mutex> lock(mMutex);
-            if (!mTable || mCtx != c) return nullptr;
-        }
-        return flush();
-    }
+    // The calling thread's handle on the table, flushed: the root on the thread whose context made it, a thread_local view elsewhere.
+    // nullptr before the tracking thread has made the table or when the view cannot be attached: ComputeSim3's matchers on handles
+    // (cslam_sim3solver.cpp) then take the array route.
+    ccm_map_table* here() { return exists() ? flush() : nullptr; }
     // The slots in view of the previous SearchLocalPoints: Frame::isInFrustum clears mbTrackInView of every point it tests, so a
     // point that was in view and is rejected now must not keep a stale `true`.
     std::vector<int32_t> mLastInView;
 
 private:
+    // A thread's view of the table, destroyed with the thread (on an orphan too, should the thread's context have gone first)
+    struct View {
+        ccm_map_table* t = nullptr; uint64_t generation = 0, order = 0;
+        ~View() { ccm_map_table_destroy(t); }
+    };
+    bool exists()
+    {
+        std::lock_guard<std::mutex> lock(mMutex);
+        return mTable != nullptr;
+    }
+    // mMutex held.  The handle of the thread whose context is c, and where that handle's order stamp is kept.
+    ccm_map_table* handle_locked(ccm_ctx* c, uint64_t** order_sent)
+    {
+        if (c == mCtx) { *order_sent = &mRootOrder; return mTable; }
+        static thread_local View v;
+        if (v.t && v.generation != mGeneration) { ccm_map_table_destroy(v.t); v.t = nullptr; }       // the table was replaced by a bigger one
+        if (!v.t) {
+            if (ccm_map_table_attach(c, mTable, &v.t)) return nullptr;
+            v.generation = mGeneration; v.order = 0;
+        }
+        *order_sent = &v.order;
+        return v.t;
+    }
     struct Row { int slot; float pos[3], normal[3], min_dist, max_dist; uint8_t desc[32]; uint8_t flags; };
     std::mutex mMutex;
     std::map<cslam::idpair, int> mSlotOf;
@@ -295,8 +313,9 @@ private:
     std::vector<int> mFree;
     std::vector<Row> mQueue, mRows;                       // mRows: the last row sent for a slot, with the raw distances
     ccm_map_table* mTable = nullptr;
-    ccm_ctx* mCtx = nullptr;                              // the context of the thread that made mTable
-    bool mOrderDirty = true;
+    ccm_ctx* mCtx = nullptr;                              // the context of the thread that made mTable (the root handle)
+    uint64_t mGeneration = 0;                             // changes whenever flush() replaces the table by a bigger one
+    uint64_t mOrderStamp = 1, mRootOrder = 0;             // the set of points changed <=> a handle's order stamp differs from mOrderStamp
     int32_t mZero = 0;
 };
 
@@ -335,7 +354,7 @@ bool send_frame_points(ccm_frame* h, const Frame& F)
 void Tracking::SearchLocalPoints()
 {
     ccm_shim::MapTable& T = ccm_shim::MapTable::get();
-    ccm_map_table* table = T.flush();
+    ccm_map_table* table = T.flush(/*with_order=*/true);
     Frame& F = *mCurrentFrame;
     ccm_frame* h = ccm_shim::frame_handle(F);
     if (!table || !h || !send_frame_points(h, F)) throw estd::infrastructure_ex();
@@ -477,10 +496,9 @@ bool Tracking::TrackWithMotionModel()
     ccm_shim::MapTable& T = ccm_shim::MapTable::get();
     ccm_map_table* table = T.flush();
     if (!table) throw estd::infrastructure_ex();
-    // Fallback 1: the table was made by another thread's flush and lives in that thread's context; this thread's frame handles
-    // cannot be used with it (ccm_frame_track_motion_model would return CCM_E_ARG).
-    if (!T.in_context(c)) return three_calls();
-    // Fallback 2: a point of the last frame has no slot (one that Map::AddMapPoint's hook never saw): the handle could not name it.
+    // (flush() gave this thread's own handle on the table -- a view where another thread's flush made it --, so the frame handles of
+    // this thread's context can be used with it.)
+    // Fallback: a point of the last frame has no slot (one that Map::AddMapPoint's hook never saw): the handle could not name it.
     std::vector<int32_t> slots(std::max(L.N, 1), -1);
     std::vector<uint8_t> last_outlier(std::max(L.N, 1), 0);
     for (int i = 0; i < L.N; i++) {

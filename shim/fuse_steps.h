@@ -81,7 +81,8 @@ void fuse_into_targets(const std::vector<ORBmatcher::kfptr>& vpTargetKFs, const 
 // MapPoint::ComputeDistinctiveDescriptors (what & CCM_MPR_DESCRIPTOR) and MapPoint::UpdateNormalAndDepth (what & CCM_MPR_NORMAL_DEPTH)
 // for all of pts in one ccm_map_table_refresh on the map-point table and the caller's keyframe handles (ccm_shim::MapTable::refresh,
 // defined in cslam_tracking.cpp).  handle_of returns the handle of a keyframe in the calling thread's context, camera and pose set.
-// false = nothing was done (the table belongs to another thread's context, or a handle is missing): the caller then runs the
+// It works through the calling thread's own handle on the table (a view where another thread made it, ccm_map_table_attach).
+// false = nothing was done (there is no table yet, the view cannot be attached, or a handle is missing): the caller then runs the
 // reference's two functions point by point, whose hooks queue the rows.
 using KeyframeHandleOf = ccm_frame* (*)(const ORBmatcher::kfptr&);
 bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of);
@@ -89,8 +90,9 @@ bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, Key
 // The slot of pMP in the calling process's map-point table, or -1 (ccm_shim::MapTable::slot_of, cslam_tracking.cpp).  A keyframe handle
 // that is to serve fuse_select_on_table carries these in its map-point ids.
 int map_slot_of(const ORBmatcher::mpptr& pMP);
-// The process's map-point table with every queued row sent, when it lives in the calling thread's context; else nullptr.  One table
-// serves one context: a thread with another context takes the array routes.
+// The calling thread's handle on the process's map-point table with every queued row sent: the table itself on the thread whose
+// context made it, a thread_local view of its rows (ccm_map_table_attach) on any other.  nullptr before the tracking thread has made
+// the table or when the attach fails: the caller takes the array routes.
 ccm_map_table* map_table_here();
 
 // ComputeSim3's two matchers on keyframe handles and the table (defined in cslam_sim3solver.cpp; INTEGRATION.md "ComputeSim3 on
@@ -111,8 +113,8 @@ bool search_by_projection_on_table(const ORBmatcher::kfptr& pKF, const cv::Mat& 
 // ask mbDoNotReplace (:1026), so that flag is honoured with chi2_check only.  Every distinct point travels once; a null pointer gets
 // -1 and a duplicate the row of its first occurrence (the caller's apply step re-tests IsInKeyFrame, as the reference's second visit
 // would).  best [kfs.size()][pts.size()] = the selected feature or -1.
-// false = nothing was done and best is untouched: the table belongs to another thread's context, a point has no slot yet, or a
-// handle is missing.  The caller then takes the host route (project_for_fuse and ccm_fuse_select_batch_frames).
+// false = nothing was done and best is untouched: the calling thread has no handle on the table (map_table_here), a point has no
+// slot yet, or a handle is missing.  The caller then takes the host route (project_for_fuse and ccm_fuse_select_batch_frames).
 struct FusePose { cv::Mat Rcw, tcw, Ow; };
 bool fuse_select_on_table(const std::vector<ORBmatcher::kfptr>& kfs, const std::vector<FusePose>& poses, const std::vector<ORBmatcher::mpptr>& pts,
                           float th, int chi2_check, int accept_th, KeyframeHandleOf handle_of, std::vector<int32_t>& best);
