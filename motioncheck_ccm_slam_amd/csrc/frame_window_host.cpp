@@ -69,40 +69,25 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
     const int n = f->n, nq = w.nq;
     const size_t o_status = w.o_status, o_out = w.o_out, o_flag = w.o_flag, res_end = w.res_end;
     int* d_status = G.dev<int>(o_status); int* d_out = G.dev<int>(o_out); uint8_t* d_flag = G.dev<uint8_t>(o_flag);
-    const float* d_qx = w.qx; const float* d_qy = w.qy; const float* d_qr = w.qr; const int* d_minl = w.minl; const int* d_maxl = w.maxl;
-    const uint8_t* d_qdesc = w.qdesc; const uint8_t* d_act = w.act; const uint8_t* d_qflag = w.qflag;
-    const float* d_qang = w.qang; const int* id_src = w.id_src;
+    const uint8_t* d_act = w.act; const uint8_t* d_qflag = w.qflag; const int* id_src = w.id_src;
     int rc;
     w.host_accept = false;
-    const WinGrid grid = frame_win_grid(f);
-    auto lists = [&](int cap) -> int {
-        CCM_RESERVE(c, S.ci, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cd, (size_t)nq * cap * 4); CCM_RESERVE(c, S.cn, (size_t)nq * 4);
-        match_launch_window(st, grid, nq, d_qx, d_qy, d_qr, d_minl, d_maxl, d_qdesc, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>());
-        CCM_HIP(c, hipGetLastError());
-        return CCM_OK;
-    };
+    const WinLists L{ frame_win_grid(f), nullptr, nullptr, nq, w.qx, w.qy, w.qr, w.minl, w.maxl, w.qdesc, &S.ci, &S.cd, &S.cn };
 
     if (!window_host_accept_forced() && match_window_greedy_lds(n, nq) <= kGreedyLdsMax) {
-        int cap = 64;
         CCM_RESERVE(c, S.ev, std::max<size_t>((size_t)nq * 4, 16));
-        for (int attempt = 0; attempt < 3; attempt++) {
-            if ((rc = lists(cap))) return rc;
-            GreedyArgs A{ nq, n, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>(), d_act, nullptr, f->oct, d_qflag, d_flag, w.nnratio,
-                          d_out, d_status, w.orb_dist, w.check_ori, d_qang, f->angle, S.ev.as<int>(), nullptr };
-            if (match_launch_window_greedy(st, w.mode, A)) return ccm_fail(c, CCM_E_DEVICE, "k_window_greedy: LDS request refused");
-            CCM_HIP(c, hipGetLastError());
+        GreedyArgs A{ nq, n, 0, nullptr, nullptr, nullptr, d_act, nullptr, f->oct, d_qflag, d_flag, w.nnratio,
+                      d_out, d_status, w.orb_dist, w.check_ori, w.qang, f->angle, S.ev.as<int>(), nullptr };
+        auto tail = [&] {                                                      // the new ids into the handle (none from an overflowed attempt)
             frame_launch_scatter_ids(st, n, d_out, id_src, d_status, f->mp_id);
             if (w.ids_copy) frame_launch_scatter_ids(st, n, d_out, id_src, d_status, w.ids_copy);
-            CCM_HIP(c, hipGetLastError());
-            if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;
-            int status[2];
-            G.get(status, o_status, 8);
-            if (status[0] < 0) { cap = status[1]; continue; }                  // rare: a denser window than expected
-            G.get(match, o_out, (size_t)n * 4);
-            G.get(occupied, o_flag, n);
-            return status[0];
-        }
-        return ccm_fail(c, CCM_E_CAPACITY, "window candidate lists keep overflowing");
+        };
+        auto fetch = [&](const int** s) -> int { *s = G.host<int>(o_status); const int e = G.download(c, 0, res_end); return e ? e : G.wait(c); };
+        const int* status = nullptr;                                           // one workgroup sees an overflow before it writes: nothing to reset
+        if ((rc = window_greedy_drive(c, L, A, w.mode, 1, n, [] { return CCM_OK; }, tail, fetch, &status))) return rc;
+        G.get(match, o_out, (size_t)n * 4);
+        G.get(occupied, o_flag, n);
+        return status[0];
     }
 
     // host acceptance (CCM_WINDOW_HOST_ACCEPT=1, or a frame too large for the single workgroup's LDS): lists to the host, the loops
@@ -117,23 +102,13 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
         h_act = act_h.data(); h_qflag = qflag_h.data();
         for (int i = 0; i < n; i++) match[i] = -1;
     }
-    int cap = 64;
-    std::vector<int32_t> ci, cd, cn(nq);
-    for (;;) {
-        if ((rc = lists(cap))) return rc;
-        ci.resize((size_t)nq * cap); cd.resize((size_t)nq * cap);
-        if ((rc = frame_fetch(c, cn.data(), S.cn.p, (size_t)nq * 4))) return rc;
-        int mx = 0;
-        for (int v : cn) mx = std::max(mx, v);
-        if (mx > cap) { cap = mx; continue; }
-        if ((rc = frame_fetch(c, ci.data(), S.ci.p, ci.size() * 4)) || (rc = frame_fetch(c, cd.data(), S.cd.p, cd.size() * 4))) return rc;
-        break;
-    }
+    WinHostLists H{ 64 };
+    if ((rc = window_lists_host(c, L, H))) return rc;
     int nmatches;
     if (w.mode == 0) {
         std::vector<int32_t> oct(n);
         if ((rc = frame_fetch(c, oct.data(), f->oct, (size_t)n * 4))) return rc;
-        nmatches = window_accept_projection_host(nq, h_act, ci.data(), cd.data(), cn.data(), cap, oct.data(), h_qflag, occupied, w.nnratio, match);
+        nmatches = window_accept_projection_host(nq, h_act, H.ci.data(), H.cd.data(), H.cn.data(), H.cap, oct.data(), h_qflag, occupied, w.nnratio, match);
     } else {
         std::vector<float> cur_angle, last_angle;
         if (w.check_ori) {
@@ -141,7 +116,7 @@ int frame_window_dev(ccm_ctx* c, ccm_frame* f, WinDevCall& w, uint8_t* occupied,
             if ((rc = frame_fetch(c, cur_angle.data(), f->angle, (size_t)n * 4))) return rc;
             if (w.last) { last_angle.resize(nq); if ((rc = frame_fetch(c, last_angle.data(), w.last->angle, (size_t)nq * 4))) return rc; }
         }
-        nmatches = window_accept_frame_host(nq, h_act, ci.data(), cd.data(), cn.data(), cap, h_qflag, occupied, w.orb_dist, w.check_ori,
+        nmatches = window_accept_frame_host(nq, h_act, H.ci.data(), H.cd.data(), H.cn.data(), H.cap, h_qflag, occupied, w.orb_dist, w.check_ori,
                                             w.last ? last_angle.data() : w.h_qang, cur_angle.data(), match);
     }
     G.put(o_out, match, (size_t)n * 4);                                      // the stream is idle: the staging area is free

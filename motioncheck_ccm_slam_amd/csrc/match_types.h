@@ -1,5 +1,6 @@
 // match_types.h -- kernel argument structures, launch constants and launchers of the matcher's CDNA4 (gfx950) kernels, shared with the
-// host translation units that launch into them (match_*_host.cpp, frame_host.cpp, mpt_host.cpp; through window_types.h).
+// host translation units that launch into them (match_*_host.cpp; frame_window_host.cpp, mpt_fuse_host.cpp and mpt_sim3_host.cpp through
+// window_types.h).
 //
 // 256-bit Hamming matching, one file per kernel family:
 //   match_bf.hip      k_hamming_mfma    brute-force best / second-best per query on the matrix cores (<= 2048 train rows per pair):

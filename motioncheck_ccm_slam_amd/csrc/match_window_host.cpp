@@ -29,12 +29,27 @@ static void grid_build(const ccm_frame_grid& f, int* cell_first, int* cell_items
     for (int i = 0; i < n; i++) if (cell[i] >= 0) cell_items[fill[cell[i]]++] = i;
 }
 
-// mode 0: candidate lists to the host (ci / cd / cn); 1: lists stay in HBM for k_window_greedy; 2: no lists, k_window_select
-// leaves one (index, distance) per query in W.sel_i / W.sel_d
-static int window_run(ccm_ctx* c, const ccm_frame_grid* f, int nq, const float* qx, const float* qy, const float* qr,
-                      const int32_t* minl, const int32_t* maxl, const uint8_t* qdesc, int cap, int mode,
-                      std::vector<int32_t>& ci, std::vector<int32_t>& cd, std::vector<int32_t>& cn,
-                      const float* inv_sigma2 = nullptr, int n_levels = 0, int accept_th = 0)
+// The queries of a call into the context's WindowBufs.  L: the call on its lists in W.ci / cd / cn, over the one frame G or, with qkf
+// (each query's keyframe), over the batch's WinGrid table in W.grids.
+static int window_stage_queries(ccm_ctx* c, const WinGrid& G, int nq, const float* qx, const float* qy, const float* qr, const int32_t* minl,
+                                const int32_t* maxl, const uint8_t* qdesc, const int32_t* qkf, WinLists& L)
+{
+    WindowBufs& W = window_bufs(c);
+    hipStream_t st = c->stream;
+    int rc;
+    if ((rc = ccm_upload(c, W.qx, qx, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.qy, qy, (size_t)nq * 4, st)) ||
+        (rc = ccm_upload(c, W.qr, qr, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.minl, minl, (size_t)nq * 4, st)) ||
+        (rc = ccm_upload(c, W.maxl, maxl, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.qdesc, qdesc, (size_t)nq * 32, st)) ||
+        (qkf && (rc = ccm_upload(c, W.qkf, qkf, (size_t)nq * 4, st))))
+        return rc;
+    L = WinLists{ G, qkf ? W.grids.as<WinGrid>() : nullptr, W.qkf.as<int>(), nq, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(),
+                  W.maxl.as<int>(), W.qdesc.as<uint8_t>(), &W.ci, &W.cd, &W.cn };
+    return CCM_OK;
+}
+
+// A frame (its grid built here) and its queries into WindowBufs, once per call
+static int window_stage(ccm_ctx* c, const ccm_frame_grid* f, int nq, const float* qx, const float* qy, const float* qr, const int32_t* minl,
+                        const int32_t* maxl, const uint8_t* qdesc, WinLists& L)
 {
     WindowBufs& W = window_bufs(c);
     const int n = f->n;
@@ -44,90 +59,91 @@ static int window_run(ccm_ctx* c, const ccm_frame_grid* f, int nq, const float* 
     int rc;
     if ((rc = ccm_upload(c, W.kx, f->kp_x, (size_t)n * 4, st)) || (rc = ccm_upload(c, W.ky, f->kp_y, (size_t)n * 4, st)) ||
         (rc = ccm_upload(c, W.oct, f->kp_octave, (size_t)n * 4, st)) || (rc = ccm_upload(c, W.desc, f->desc, (size_t)n * 32, st)) ||
-        (rc = ccm_upload(c, W.cfirst, first.data(), first.size() * 4, st)) || (rc = ccm_upload(c, W.citems, items.data(), (size_t)n * 4, st)) ||
-        (rc = ccm_upload(c, W.qx, qx, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.qy, qy, (size_t)nq * 4, st)) ||
-        (rc = ccm_upload(c, W.qr, qr, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.minl, minl, (size_t)nq * 4, st)) ||
-        (rc = ccm_upload(c, W.maxl, maxl, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.qdesc, qdesc, (size_t)nq * 32, st)))
+        (rc = ccm_upload(c, W.cfirst, first.data(), first.size() * 4, st)) || (rc = ccm_upload(c, W.citems, items.data(), (size_t)n * 4, st)))
         return rc;
-    WinGrid G{ n, f->grid_cols, f->grid_rows, f->min_x, f->min_y, f->inv_w, f->inv_h, W.kx.as<float>(), W.ky.as<float>(), W.oct.as<int>(),
-               W.desc.as<uint8_t>(), W.cfirst.as<int>(), W.citems.as<int>() };
-    if (mode == 2) {
-        CCM_RESERVE(c, W.sel_i, (size_t)nq * 4); CCM_RESERVE(c, W.sel_d, (size_t)nq * 4);
-        if (inv_sigma2 && (rc = ccm_upload(c, W.is2, inv_sigma2, (size_t)n_levels * 4, st))) return rc;
-        match_launch_window_select(st, G, nq, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(), W.maxl.as<int>(),
-                                   W.qdesc.as<uint8_t>(), inv_sigma2 ? W.is2.as<float>() : nullptr, accept_th, W.sel_i.as<int>(), W.sel_d.as<int>());
-        CCM_HIP(c, hipGetLastError());
-        return CCM_OK;
-    }
-    CCM_RESERVE(c, W.ci, (size_t)nq * cap * 4); CCM_RESERVE(c, W.cd, (size_t)nq * cap * 4); CCM_RESERVE(c, W.cn, (size_t)nq * 4);
-    match_launch_window(st, G, nq, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(), W.maxl.as<int>(),
-                        W.qdesc.as<uint8_t>(), cap, W.ci.as<int>(), W.cd.as<int>(), W.cn.as<int>());
+    const WinGrid G{ n, f->grid_cols, f->grid_rows, f->min_x, f->min_y, f->inv_w, f->inv_h, W.kx.as<float>(), W.ky.as<float>(), W.oct.as<int>(),
+                     W.desc.as<uint8_t>(), W.cfirst.as<int>(), W.citems.as<int>() };
+    return window_stage_queries(c, G, nq, qx, qy, qr, minl, maxl, qdesc, nullptr, L);
+}
+
+int window_lists_launch(ccm_ctx* c, const WinLists& L, int cap)
+{
+    CCM_RESERVE(c, *L.ci, (size_t)L.nq * cap * 4); CCM_RESERVE(c, *L.cd, (size_t)L.nq * cap * 4); CCM_RESERVE(c, *L.cn, (size_t)L.nq * 4);
+    if (L.grids)
+        match_launch_window_batch(c->stream, L.grids, L.q_kf, L.nq, L.qx, L.qy, L.qr, L.minl, L.maxl, L.qdesc, cap, L.ci->as<int>(), L.cd->as<int>(), L.cn->as<int>());
+    else
+        match_launch_window(c->stream, L.grid, L.nq, L.qx, L.qy, L.qr, L.minl, L.maxl, L.qdesc, cap, L.ci->as<int>(), L.cd->as<int>(), L.cn->as<int>());
     CCM_HIP(c, hipGetLastError());
-    if (mode == 1) return CCM_OK;
-    ci.resize((size_t)nq * cap); cd.resize((size_t)nq * cap); cn.resize(nq);
-    CCM_HIP(c, hipMemcpyAsync(ci.data(), W.ci.p, ci.size() * 4, hipMemcpyDeviceToHost, st));
-    CCM_HIP(c, hipMemcpyAsync(cd.data(), W.cd.p, cd.size() * 4, hipMemcpyDeviceToHost, st));
-    CCM_HIP(c, hipMemcpyAsync(cn.data(), W.cn.p, cn.size() * 4, hipMemcpyDeviceToHost, st));
-    CCM_HIP(c, hipStreamSynchronize(st));
     return CCM_OK;
 }
 
-// Candidate lists on the host for the host acceptance loops, `cap` grown until every list fits (rare: a denser window than expected)
-static int window_fit(ccm_ctx* c, const ccm_frame_grid* f, int nq, const float* qx, const float* qy, const float* qr, const int32_t* minl,
-                      const int32_t* maxl, const uint8_t* qdesc, int& cap, std::vector<int32_t>& ci, std::vector<int32_t>& cd,
-                      std::vector<int32_t>& cn)
+// The lists of a launch at `cap` into host arrays of [nq][cap], [nq][cap] and [nq]
+static int window_lists_fetch(ccm_ctx* c, const WinLists& L, int cap, int32_t* ci, int32_t* cd, int32_t* cn)
 {
+    CCM_HIP(c, hipMemcpyAsync(ci, L.ci->p, (size_t)L.nq * cap * 4, hipMemcpyDeviceToHost, c->stream));
+    CCM_HIP(c, hipMemcpyAsync(cd, L.cd->p, (size_t)L.nq * cap * 4, hipMemcpyDeviceToHost, c->stream));
+    CCM_HIP(c, hipMemcpyAsync(cn, L.cn->p, (size_t)L.nq * 4, hipMemcpyDeviceToHost, c->stream));
+    CCM_HIP(c, hipStreamSynchronize(c->stream));
+    return CCM_OK;
+}
+
+int window_lists_host(ccm_ctx* c, const WinLists& L, WinHostLists& H)
+{
+    H.cn.resize(L.nq);
     for (;;) {
-        int rc = window_run(c, f, nq, qx, qy, qr, minl, maxl, qdesc, cap, 0, ci, cd, cn);
-        if (rc) return rc;
-        int mx = 0;
-        for (int v : cn) mx = std::max(mx, v);
-        if (mx <= cap) return CCM_OK;
-        cap = mx;
+        H.ci.resize((size_t)L.nq * H.cap); H.cd.resize((size_t)L.nq * H.cap);
+        int rc, mx = 0;
+        if ((rc = window_lists_launch(c, L, H.cap)) || (rc = window_lists_fetch(c, L, H.cap, H.ci.data(), H.cd.data(), H.cn.data()))) return rc;
+        for (int v : H.cn) mx = std::max(mx, v);
+        if (mx <= H.cap) return CCM_OK;
+        H.cap = mx;
     }
 }
 
-// The order-dependent acceptance on the device (k_window_greedy): candidate lists stay in HBM, in: per-query active / level / flag and
-// the per-feature flags; out: `out` (n_out ints, pre-set to -1), the updated flags, the number of matches.  Returns the match count,
-// or < 0 on error.  Lists longer than `cap` make the kernel report the needed length and the call repeats once.
-static int window_greedy(ccm_ctx* c, const ccm_frame_grid* f, int nq, const float* qx, const float* qy, const float* qr,
-                         const int32_t* minl, const int32_t* maxl, const uint8_t* qdesc, int mode, const uint8_t* active, const int32_t* qlevel,
-                         const uint8_t* qflag, uint8_t* flag, float nnratio, int32_t* out, int n_out,
-                         int orb_dist = 0, int check_ori = 0, const float* q_angle = nullptr, const float* f_angle = nullptr)
+// The order-dependent acceptance on the device (k_window_greedy) for staged queries.  in: per-query active / level / flag and the
+// n_flag per-feature flags; out: `out` (n_out ints, -1 where nothing is chosen), the updated flags and, for a batch (kfs [n_problems],
+// frames of at most max_n features), the matches of each problem in n_matches.  Returns the match count, or < 0 on error.
+static int window_greedy(ccm_ctx* c, const WinLists& L, int mode, const uint8_t* active, const int32_t* qlevel, const uint8_t* qflag, uint8_t* flag,
+                         int n_flag, float nnratio, int32_t* out, int n_out, int orb_dist = 0, int check_ori = 0, const float* q_angle = nullptr,
+                         const float* f_angle = nullptr, const std::vector<GreedyKf>* kfs = nullptr, int max_n = 0, int32_t* n_matches = nullptr)
 {
-    std::vector<int32_t> d0, d1, d2;
-    int cap = 64;
-    for (int attempt = 0; attempt < 3; attempt++) {
-        int rc = window_run(c, f, nq, qx, qy, qr, minl, maxl, qdesc, cap, 1, d0, d1, d2);
-        if (rc) return rc;
-        WindowBufs& W = window_bufs(c);
-        hipStream_t st = c->stream;
-        if ((rc = ccm_upload(c, W.act, active, (size_t)nq, st)) || (rc = ccm_upload(c, W.qflag, qflag, (size_t)nq, st)) ||
-            (rc = ccm_upload(c, W.flag, flag, (size_t)f->n, st)))
+    WindowBufs& W = window_bufs(c);
+    hipStream_t st = c->stream;
+    const int nq = L.nq, n_problems = kfs ? (int)kfs->size() : 1;
+    int rc;
+    if ((rc = ccm_upload(c, W.act, active, (size_t)nq, st)) || (rc = ccm_upload(c, W.qflag, qflag, (size_t)nq, st))) return rc;
+    if (qlevel && (rc = ccm_upload(c, W.qlvl, qlevel, (size_t)nq * 4, st))) return rc;
+    if (kfs && (rc = ccm_upload(c, W.gkf, kfs->data(), kfs->size() * sizeof(GreedyKf), st))) return rc;
+    if (mode == 2) {
+        CCM_RESERVE(c, W.ev, std::max<size_t>((size_t)nq * 4, 16));
+        if (check_ori && ((rc = ccm_upload(c, W.qang, q_angle, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.fang, f_angle, (size_t)n_flag * 4, st))))
             return rc;
-        if (qlevel && (rc = ccm_upload(c, W.qlvl, qlevel, (size_t)nq * 4, st))) return rc;
-        if (mode == 2) {
-            CCM_RESERVE(c, W.ev, std::max<size_t>((size_t)nq * 4, 16));
-            if (check_ori && ((rc = ccm_upload(c, W.qang, q_angle, (size_t)nq * 4, st)) || (rc = ccm_upload(c, W.fang, f_angle, (size_t)f->n * 4, st))))
-                return rc;
-        }
-        CCM_RESERVE(c, W.out, std::max<size_t>((size_t)n_out * 4, 16)); CCM_RESERVE(c, W.status, 16);
-        CCM_HIP(c, hipMemsetAsync(W.out.p, 0xFF, (size_t)n_out * 4, st));
-        GreedyArgs A{ nq, f->n, cap, W.ci.as<int>(), W.cd.as<int>(), W.cn.as<int>(), W.act.as<uint8_t>(), qlevel ? W.qlvl.as<int>() : nullptr,
-                      W.oct.as<int>(), W.qflag.as<uint8_t>(), W.flag.as<uint8_t>(), nnratio, W.out.as<int>(), W.status.as<int>(),
-                      orb_dist, check_ori, W.qang.as<float>(), W.fang.as<float>(), W.ev.as<int>(), nullptr };
-        if (match_launch_window_greedy(st, mode, A)) return ccm_fail(c, CCM_E_DEVICE, "k_window_greedy: LDS request refused");
-        CCM_HIP(c, hipGetLastError());
-        int status[3] = { 0, 0, 0 };
-        CCM_HIP(c, hipMemcpyAsync(status, W.status.p, 12, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));
-        if (status[0] < 0) { cap = status[1]; continue; }                        // rare: a denser window than expected
-        CCM_HIP(c, hipMemcpyAsync(out, W.out.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipMemcpyAsync(flag, W.flag.p, (size_t)f->n, hipMemcpyDeviceToHost, st));
-        CCM_HIP(c, hipStreamSynchronize(st));
-        return status[0];
     }
-    return ccm_fail(c, CCM_E_CAPACITY, "window candidate lists keep overflowing");
+    CCM_RESERVE(c, W.out, std::max<size_t>((size_t)n_out * 4, 16)); CCM_RESERVE(c, W.status, (size_t)n_problems * 12 + 16);
+    auto reset = [&]() -> int {                                                  // the flags and choices as they come in
+        if (int e = ccm_upload(c, W.flag, flag, (size_t)n_flag, st)) return e;
+        CCM_HIP(c, hipMemsetAsync(W.out.p, 0xFF, (size_t)n_out * 4, st));
+        return CCM_OK;
+    };
+    if ((rc = reset())) return rc;
+    GreedyArgs A{ kfs ? 0 : nq, kfs ? 0 : n_flag, 0, nullptr, nullptr, nullptr, W.act.as<uint8_t>(), qlevel ? W.qlvl.as<int>() : nullptr, W.oct.as<int>(),
+                  W.qflag.as<uint8_t>(), W.flag.as<uint8_t>(), nnratio, W.out.as<int>(), W.status.as<int>(), orb_dist, check_ori, W.qang.as<float>(),
+                  W.fang.as<float>(), W.ev.as<int>(), kfs ? W.gkf.as<GreedyKf>() : nullptr };
+    std::vector<int> words(3 * (size_t)n_problems);
+    const int* status = nullptr;
+    auto fetch = [&](const int** s) -> int {                                     // the status words alone; the results follow a success
+        *s = words.data();
+        CCM_HIP(c, hipMemcpyAsync(words.data(), W.status.p, words.size() * 4, hipMemcpyDeviceToHost, st));
+        CCM_HIP(c, hipStreamSynchronize(st));
+        return CCM_OK;
+    };
+    if ((rc = window_greedy_drive(c, L, A, mode, n_problems, max_n, reset, [] {}, fetch, &status))) return rc;
+    CCM_HIP(c, hipMemcpyAsync(out, W.out.p, (size_t)n_out * 4, hipMemcpyDeviceToHost, st));
+    CCM_HIP(c, hipMemcpyAsync(flag, W.flag.p, (size_t)n_flag, hipMemcpyDeviceToHost, st));
+    CCM_HIP(c, hipStreamSynchronize(st));
+    int total = 0;
+    for (int k = 0; k < n_problems; k++) { if (n_matches) n_matches[k] = status[3 * k]; total += status[3 * k]; }
+    return total;
 }
 
 // The keyframes of a batch call, concatenated: keyframe k's features are rows feat_first[k] .. feat_first[k + 1] - 1 of W.kx / ky /
@@ -258,6 +274,32 @@ int window_accept_frame_host(int n_last, const uint8_t* valid, const int32_t* ci
     return nmatches;
 }
 
+int window_accept_sim3_host(int n_mp, const uint8_t* valid, const int32_t* level, const int32_t* ci, const int32_t* cd, const int32_t* cn, int cap,
+                            const int32_t* kp_octave, const uint8_t* observed, uint8_t* matched, int32_t* best_idx, int32_t* best_dist)
+{
+    int nmatches = 0;
+    for (int m = 0; m < n_mp; m++) {                           // sequential: vpMatched grows while the points are visited
+        if (best_dist) best_dist[m] = 256;
+        if (!valid[m]) continue;
+        const int lvl = level[m];
+        int bestDist = 256, bestIdx = -1;
+        for (int k = 0; k < cn[m]; k++) {
+            const int idx = ci[(size_t)m * cap + k];
+            if (matched[idx]) continue;                                                              // :393-394
+            const int kpLevel = kp_octave[idx];
+            if (kpLevel < lvl - 1 || kpLevel > lvl) continue;
+            const int dist = cd[(size_t)m * cap + k];
+            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
+        }
+        if (bestDist <= 50) {                                                                        // TH_LOW
+            best_idx[m] = bestIdx;
+            if (best_dist) best_dist[m] = bestDist;
+            if (!observed[m]) { matched[bestIdx] = 1; nmatches++; }                                  // :436-440
+        }
+    }
+    return nmatches;
+}
+
 extern "C" {
 
 int ccm_window_candidates(ccm_ctx* c, const ccm_frame_grid* f, int nq, const float* qx, const float* qy, const float* qr,
@@ -271,11 +313,10 @@ int ccm_window_candidates(ccm_ctx* c, const ccm_frame_grid* f, int nq, const flo
             !cand_idx || !cand_dist || !cand_n || (f->n > 0 && (!f->kp_x || !f->kp_y || !f->kp_octave || !f->desc)))
             return ccm_fail(c, CCM_E_ARG, "bad window-search arguments");
         CCM_HIP(c, hipSetDevice(c->device));
-        std::vector<int32_t> ci, cd, cn;
-        int rc = window_run(c, f, nq, qx, qy, qr, min_level, max_level, qdesc, cap, 0, ci, cd, cn);
-        if (rc) return rc;
-        std::memcpy(cand_idx, ci.data(), ci.size() * 4); std::memcpy(cand_dist, cd.data(), cd.size() * 4); std::memcpy(cand_n, cn.data(), cn.size() * 4);
-        for (int q = 0; q < nq; q++) if (cn[q] > cap) return ccm_fail(c, CCM_E_CAPACITY, "query %d has %d candidates, cap %d", q, cn[q], cap);
+        WinLists L;
+        int rc = window_stage(c, f, nq, qx, qy, qr, min_level, max_level, qdesc, L);
+        if (rc || (rc = window_lists_launch(c, L, cap)) || (rc = window_lists_fetch(c, L, cap, cand_idx, cand_dist, cand_n))) return rc;   // truncated lists too
+        for (int q = 0; q < nq; q++) if (cand_n[q] > cap) return ccm_fail(c, CCM_E_CAPACITY, "query %d has %d candidates, cap %d", q, cand_n[q], cap);
         return CCM_OK;
     });
 }
@@ -295,14 +336,14 @@ int ccm_search_by_projection(ccm_ctx* c, const ccm_frame_grid* f, const float* s
         if (n_mp == 0 || f->n == 0) return 0;
         CCM_HIP(c, hipSetDevice(c->device));
         const WinQueries q = window_queries_projection(n_mp, in_view, level, view_cos, scale_factors, th);
-        if (!window_host_accept_forced() && match_window_greedy_lds(f->n, n_mp) <= kGreedyLdsMax)
-            return window_greedy(c, f, n_mp, proj_x, proj_y, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, 0, in_view, nullptr, mp_has_obs, occupied,
-                                 nnratio, match, f->n);
-        int cap = 64;
-        std::vector<int32_t> ci, cd, cn;
-        int rc = window_fit(c, f, n_mp, proj_x, proj_y, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, cap, ci, cd, cn);
+        WinLists L;
+        int rc = window_stage(c, f, n_mp, proj_x, proj_y, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, L);
         if (rc) return rc;
-        return window_accept_projection_host(n_mp, in_view, ci.data(), cd.data(), cn.data(), cap, f->kp_octave, mp_has_obs, occupied, nnratio, match);
+        if (!window_host_accept_forced() && match_window_greedy_lds(f->n, n_mp) <= kGreedyLdsMax)
+            return window_greedy(c, L, 0, in_view, nullptr, mp_has_obs, occupied, f->n, nnratio, match, f->n);
+        WinHostLists H{ 64 };
+        if ((rc = window_lists_host(c, L, H))) return rc;
+        return window_accept_projection_host(n_mp, in_view, H.ci.data(), H.cd.data(), H.cn.data(), H.cap, f->kp_octave, mp_has_obs, occupied, nnratio, match);
     });
 }
 
@@ -321,14 +362,14 @@ int ccm_search_by_projection_frame(ccm_ctx* c, const ccm_frame_grid* f, const fl
         if (n_last == 0 || f->n == 0) return 0;
         CCM_HIP(c, hipSetDevice(c->device));
         const WinQueries q = window_queries_frame(n_last, valid, last_octave, scale_factors, th);
-        if (!window_host_accept_forced() && match_window_greedy_lds(f->n, n_last) <= kGreedyLdsMax)
-            return window_greedy(c, f, n_last, u, v, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, 2, valid, nullptr, mp_has_obs, occupied, 0.f, match,
-                                 f->n, orb_dist, check_ori, last_angle, cur_angle);
-        int cap = 64;
-        std::vector<int32_t> ci, cd, cn;
-        int rc = window_fit(c, f, n_last, u, v, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, cap, ci, cd, cn);
+        WinLists L;
+        int rc = window_stage(c, f, n_last, u, v, q.qr.data(), q.minl.data(), q.maxl.data(), mp_desc, L);
         if (rc) return rc;
-        return window_accept_frame_host(n_last, valid, ci.data(), cd.data(), cn.data(), cap, mp_has_obs, occupied, orb_dist, check_ori, last_angle,
+        if (!window_host_accept_forced() && match_window_greedy_lds(f->n, n_last) <= kGreedyLdsMax)
+            return window_greedy(c, L, 2, valid, nullptr, mp_has_obs, occupied, f->n, 0.f, match, f->n, orb_dist, check_ori, last_angle, cur_angle);
+        WinHostLists H{ 64 };
+        if ((rc = window_lists_host(c, L, H))) return rc;
+        return window_accept_frame_host(n_last, valid, H.ci.data(), H.cd.data(), H.cn.data(), H.cap, mp_has_obs, occupied, orb_dist, check_ori, last_angle,
                                         cur_angle, match);
     });
 }
@@ -352,18 +393,18 @@ int ccm_search_for_initialization(ccm_ctx* c, int n1, const int32_t* oct1, const
             qr[i] = oct1[i] > 0 ? -1.f : (float)window;                             // :464-466 only level-0 features
             minl[i] = oct1[i]; maxl[i] = oct1[i];
         }
-        int cap = 128;
-        std::vector<int32_t> ci, cd, cn;
-        int rc = window_fit(c, f2, n1, qx.data(), qy.data(), qr.data(), minl.data(), maxl.data(), desc1, cap, ci, cd, cn);
-        if (rc) return rc;
+        WinLists L;
+        WinHostLists H{ 128 };
+        int rc = window_stage(c, f2, n1, qx.data(), qy.data(), qr.data(), minl.data(), maxl.data(), desc1, L);
+        if (rc || (rc = window_lists_host(c, L, H))) return rc;
         RotHisto rot;
         std::vector<int> matched_dist(f2->n, INT32_MAX), m21(f2->n, -1);
         int nmatches = 0;
         for (int i1 = 0; i1 < n1; i1++) {
-            if (oct1[i1] > 0 || cn[i1] == 0) continue;
+            if (oct1[i1] > 0 || H.cn[i1] == 0) continue;
             int bestDist = INT32_MAX, bestDist2 = INT32_MAX, bestIdx2 = -1;
-            for (int k = 0; k < cn[i1]; k++) {
-                const int i2 = ci[(size_t)i1 * cap + k], dist = cd[(size_t)i1 * cap + k];
+            for (int k = 0; k < H.cn[i1]; k++) {
+                const int i2 = H.ci[(size_t)i1 * H.cap + k], dist = H.cd[(size_t)i1 * H.cap + k];
                 if (matched_dist[i2] <= dist) continue;
                 if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; }
                 else if (dist < bestDist2) bestDist2 = dist;
@@ -406,11 +447,14 @@ int ccm_fuse_select(ccm_ctx* c, const ccm_frame_grid* kf, const float* scale_fac
         }
         for (int i = 0; i < kf->n; i++) n_levels = std::max(n_levels, kf->kp_octave[i] + 1);
         // the whole selection runs on the device (k_window_select): one (index, distance) per map point comes back, no candidate list
-        std::vector<int32_t> d0, d1, d2;
-        int rc = window_run(c, kf, n_mp, u, v, qr.data(), lo.data(), hi.data(), mp_desc, 0, 2, d0, d1, d2, chi2_check ? inv_level_sigma2 : nullptr,
-                            n_levels, accept_th);
-        if (rc) return rc;
         WindowBufs& W = window_bufs(c);
+        WinLists L;
+        int rc = window_stage(c, kf, n_mp, u, v, qr.data(), lo.data(), hi.data(), mp_desc, L);
+        if (rc || (chi2_check && (rc = ccm_upload(c, W.is2, inv_level_sigma2, (size_t)n_levels * 4, c->stream)))) return rc;
+        CCM_RESERVE(c, W.sel_i, (size_t)n_mp * 4); CCM_RESERVE(c, W.sel_d, (size_t)n_mp * 4);
+        match_launch_window_select(c->stream, L.grid, n_mp, L.qx, L.qy, L.qr, L.minl, L.maxl, L.qdesc, chi2_check ? W.is2.as<float>() : nullptr, accept_th,
+                                   W.sel_i.as<int>(), W.sel_d.as<int>());
+        CCM_HIP(c, hipGetLastError());
         CCM_HIP(c, hipMemcpyAsync(best_idx, W.sel_i.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, c->stream));
         CCM_HIP(c, hipMemcpyAsync(best_dist, W.sel_d.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, c->stream));
         CCM_HIP(c, hipStreamSynchronize(c->stream));
@@ -437,16 +481,12 @@ static int fuse_batch_run(ccm_ctx* c, int n_kf, const int* kf_n, int n_levels, c
             lo[m] = level[m] - 1; hi[m] = level[m];                                               // :925-926
         }
     hipStream_t st = c->stream;
-    int rc;
-    if ((rc = ccm_upload(c, W.qx, u, (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qy, v, (size_t)n_mp * 4, st)) ||
-        (rc = ccm_upload(c, W.qr, qr.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.minl, lo.data(), (size_t)n_mp * 4, st)) ||
-        (rc = ccm_upload(c, W.maxl, hi.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qdesc, mp_desc, (size_t)n_mp * 32, st)) ||
-        (rc = ccm_upload(c, W.qkf, qkf.data(), (size_t)n_mp * 4, st)))
-        return rc;
-    if (chi2_check && (rc = ccm_upload(c, W.is2, inv_level_sigma2, (size_t)n_levels * 4, st))) return rc;
+    WinLists L;
+    int rc = window_stage_queries(c, WinGrid{}, n_mp, u, v, qr.data(), lo.data(), hi.data(), mp_desc, qkf.data(), L);
+    if (rc || (chi2_check && (rc = ccm_upload(c, W.is2, inv_level_sigma2, (size_t)n_levels * 4, st)))) return rc;
     CCM_RESERVE(c, W.sel_i, (size_t)n_mp * 4); CCM_RESERVE(c, W.sel_d, (size_t)n_mp * 4);
-    match_launch_window_select_batch(st, W.grids.as<WinGrid>(), W.qkf.as<int>(), n_mp, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(),
-                                     W.maxl.as<int>(), W.qdesc.as<uint8_t>(), chi2_check ? W.is2.as<float>() : nullptr, accept_th, W.sel_i.as<int>(), W.sel_d.as<int>());
+    match_launch_window_select_batch(st, L.grids, L.q_kf, n_mp, L.qx, L.qy, L.qr, L.minl, L.maxl, L.qdesc, chi2_check ? W.is2.as<float>() : nullptr, accept_th,
+                                     W.sel_i.as<int>(), W.sel_d.as<int>());
     CCM_HIP(c, hipGetLastError());
     CCM_HIP(c, hipMemcpyAsync(best_idx, W.sel_i.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
     CCM_HIP(c, hipMemcpyAsync(best_dist, W.sel_d.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
@@ -570,31 +610,14 @@ int ccm_search_by_projection_sim3(ccm_ctx* c, const ccm_frame_grid* kf, const fl
         CCM_HIP(c, hipSetDevice(c->device));
         std::vector<float> qr(n_mp); std::vector<int32_t> none(n_mp, -1);
         for (int m = 0; m < n_mp; m++) qr[m] = valid[m] ? th * scale_factors[level[m]] : -1.f;       // :380
-        if (!window_host_accept_forced() && match_window_greedy_lds(kf->n, n_mp) <= kGreedyLdsMax)
-            return window_greedy(c, kf, n_mp, u, v, qr.data(), none.data(), none.data(), mp_desc, 1, valid, level, observed, matched, 0.f, best_idx, n_mp);
-        int cap = 64;
-        std::vector<int32_t> ci, cd, cn;
-        int rc = window_fit(c, kf, n_mp, u, v, qr.data(), none.data(), none.data(), mp_desc, cap, ci, cd, cn);
+        WinLists L;
+        int rc = window_stage(c, kf, n_mp, u, v, qr.data(), none.data(), none.data(), mp_desc, L);
         if (rc) return rc;
-        int nmatches = 0;
-        for (int m = 0; m < n_mp; m++) {                       // sequential: vpMatched grows while the points are visited
-            if (!valid[m]) continue;
-            const int lvl = level[m];
-            int bestDist = 256, bestIdx = -1;
-            for (int k = 0; k < cn[m]; k++) {
-                const int idx = ci[(size_t)m * cap + k];
-                if (matched[idx]) continue;                                                          // :394
-                const int kpLevel = kf->kp_octave[idx];
-                if (kpLevel < lvl - 1 || kpLevel > lvl) continue;
-                const int dist = cd[(size_t)m * cap + k];
-                if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-            }
-            if (bestDist <= 50) {                                                                    // TH_LOW
-                best_idx[m] = bestIdx;
-                if (!observed[m]) { matched[bestIdx] = 1; nmatches++; }                              // :436-440
-            }
-        }
-        return nmatches;
+        if (!window_host_accept_forced() && match_window_greedy_lds(kf->n, n_mp) <= kGreedyLdsMax)
+            return window_greedy(c, L, 1, valid, level, observed, matched, kf->n, 0.f, best_idx, n_mp);
+        WinHostLists H{ 64 };
+        if ((rc = window_lists_host(c, L, H))) return rc;
+        return window_accept_sim3_host(n_mp, valid, level, H.ci.data(), H.cd.data(), H.cn.data(), H.cap, kf->kp_octave, observed, matched, best_idx);
     });
 }
 
@@ -635,7 +658,6 @@ int ccm_search_by_projection_sim3_batch(ccm_ctx* c, int n_kf, const ccm_frame_gr
             return total;
         }
         CCM_HIP(c, hipSetDevice(c->device));
-        WindowBufs& W = window_bufs(c);
         KfBatch B;
         int rc = stage_keyframes(c, n_kf, kfs, B);
         if (rc) return rc;
@@ -649,40 +671,9 @@ int ccm_search_by_projection_sim3_batch(ccm_ctx* c, int n_kf, const ccm_frame_gr
             }
             gk[k] = GreedyKf{ mp_first[k], mp_first[k + 1] - mp_first[k], B.feat_first[k], kfs[k].n };
         }
-        hipStream_t st = c->stream;
-        if ((rc = ccm_upload(c, W.qx, u, (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qy, v, (size_t)n_mp * 4, st)) ||
-            (rc = ccm_upload(c, W.qr, qr.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.minl, none.data(), (size_t)n_mp * 4, st)) ||
-            (rc = ccm_upload(c, W.maxl, none.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.qdesc, mp_desc, (size_t)n_mp * 32, st)) ||
-            (rc = ccm_upload(c, W.qkf, qkf.data(), (size_t)n_mp * 4, st)) || (rc = ccm_upload(c, W.act, valid, (size_t)n_mp, st)) ||
-            (rc = ccm_upload(c, W.qflag, observed, (size_t)n_mp, st)) || (rc = ccm_upload(c, W.qlvl, level, (size_t)n_mp * 4, st)) ||
-            (rc = ccm_upload(c, W.gkf, gk.data(), gk.size() * sizeof(GreedyKf), st)))
-            return rc;
-        CCM_RESERVE(c, W.out, (size_t)n_mp * 4); CCM_RESERVE(c, W.status, (size_t)n_kf * 12 + 16); CCM_RESERVE(c, W.cn, (size_t)n_mp * 4);
-        std::vector<int> status(3 * (size_t)n_kf);
-        int cap = 64;
-        for (int attempt = 0; attempt < 3; attempt++) {
-            CCM_RESERVE(c, W.ci, (size_t)n_mp * cap * 4); CCM_RESERVE(c, W.cd, (size_t)n_mp * cap * 4);
-            if ((rc = ccm_upload(c, W.flag, matched, (size_t)NF, st))) return rc;  // (again on a retry: the first attempt may have set flags)
-            match_launch_window_batch(st, W.grids.as<WinGrid>(), W.qkf.as<int>(), n_mp, W.qx.as<float>(), W.qy.as<float>(), W.qr.as<float>(), W.minl.as<int>(),
-                                      W.maxl.as<int>(), W.qdesc.as<uint8_t>(), cap, W.ci.as<int>(), W.cd.as<int>(), W.cn.as<int>());
-            CCM_HIP(c, hipMemsetAsync(W.out.p, 0xFF, (size_t)n_mp * 4, st));
-            GreedyArgs A{ 0, 0, cap, W.ci.as<int>(), W.cd.as<int>(), W.cn.as<int>(), W.act.as<uint8_t>(), W.qlvl.as<int>(), W.oct.as<int>(), W.qflag.as<uint8_t>(),
-                          W.flag.as<uint8_t>(), 0.f, W.out.as<int>(), W.status.as<int>(), 0, 0, nullptr, nullptr, nullptr, W.gkf.as<GreedyKf>() };
-            if (match_launch_window_greedy_batch(st, A, n_kf, max_n)) return ccm_fail(c, CCM_E_DEVICE, "k_window_greedy: LDS request refused");
-            CCM_HIP(c, hipGetLastError());
-            CCM_HIP(c, hipMemcpyAsync(status.data(), W.status.p, status.size() * 4, hipMemcpyDeviceToHost, st));
-            CCM_HIP(c, hipStreamSynchronize(st));
-            int need = 0;
-            for (int k = 0; k < n_kf; k++) if (status[3 * k] < 0) need = std::max(need, status[3 * k + 1]);
-            if (need > 0) { cap = need; continue; }                               // rare: a denser window than expected (in any keyframe: all repeat)
-            CCM_HIP(c, hipMemcpyAsync(best_idx, W.out.p, (size_t)n_mp * 4, hipMemcpyDeviceToHost, st));
-            CCM_HIP(c, hipMemcpyAsync(matched, W.flag.p, (size_t)NF, hipMemcpyDeviceToHost, st));
-            CCM_HIP(c, hipStreamSynchronize(st));
-            int total = 0;
-            for (int k = 0; k < n_kf; k++) { n_matches[k] = status[3 * k]; total += status[3 * k]; }
-            return total;
-        }
-        return ccm_fail(c, CCM_E_CAPACITY, "window candidate lists keep overflowing");
+        WinLists L;
+        if ((rc = window_stage_queries(c, WinGrid{}, n_mp, u, v, qr.data(), none.data(), none.data(), mp_desc, qkf.data(), L))) return rc;
+        return window_greedy(c, L, 1, valid, level, observed, matched, NF, 0.f, best_idx, n_mp, 0, 0, nullptr, nullptr, &gk, max_n, n_matches);
     });
 }
 }  // extern "C"

@@ -59,23 +59,13 @@ int ccm_fuse_select_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_fuse_ta
         const size_t w_held = seg(w, m), w_qx = seg(w, m * 4), w_qy = seg(w, m * 4), w_qr = seg(w, m * 4), w_minl = seg(w, m * 4), w_maxl = seg(w, m * 4);
         const size_t w_qkf = seg(w, m * 4), w_qpair = seg(w, m * 4), w_qdesc = seg(w, m * 32), w_si = seg(w, m * 4), w_sd = seg(w, m * 4);
         CCM_RESERVE(c, S.fuse, w + 64);
-        if (!t->where.p) {                                                     // first Fuse on this table: every entry older than any stamp
-            CCM_RESERVE(c, t->where, (size_t)t->capacity * 8);
-            CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st));
-            t->fuse_stamp = 0;
-        }
-        if (t->fuse_stamp == 0xffffffffu) { CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st)); t->fuse_stamp = 0; }
-        const unsigned stamp = ++t->fuse_stamp;
+        unsigned stamp = 0;
+        if ((rc = next_where_stamp(c, t, st, &stamp))) return rc;
 
         FuseView* hv = G.host<FuseView>(o_view); WinGrid* hg = G.host<WinGrid>(o_grid);
         for (int k = 0; k < n_kf; k++) {
-            const ccm_fuse_view& V = p->views[k];
-            const ccm_frame* f = V.kf;
-            FuseView& D = hv[k];
-            std::memcpy(D.Tcw, V.Tcw, sizeof D.Tcw); std::memcpy(D.Ow, V.Ow, sizeof D.Ow);
-            D.fx = V.fx; D.fy = V.fy; D.cx = V.cx; D.cy = V.cy; D.min_x = V.min_x; D.max_x = V.max_x; D.min_y = V.min_y; D.max_y = V.max_y;
-            D.n = f->n; D.pad_ = 0; D.mp_id = f->mp_id;
-            hg[k] = frame_win_grid(f);
+            fuse_view_fill(hv[k], p->views[k]);
+            hg[k] = frame_win_grid(p->views[k].kf);
         }
         G.put(o_slot, p->slot, (size_t)n_pt * 4);
         G.put(o_skip, p->skip, (size_t)n_pt);

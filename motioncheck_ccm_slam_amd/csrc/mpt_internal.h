@@ -100,6 +100,28 @@ template <class F> int table_call(ccm_ctx* c, ccm_map_table* t, bool write, cons
     });
 }
 
+// The table's stamped where[] (per slot: stamp << 32 | position in that call's slot list): created on first use, where every entry is
+// older than any stamp, and cleared when the 32-bit stamp wraps.  Gives the stamp of this call.
+static inline int next_where_stamp(ccm_ctx* c, ccm_map_table* t, hipStream_t st, unsigned* stamp)
+{
+    if (!t->where.p) {
+        CCM_RESERVE(c, t->where, (size_t)t->capacity * 8);
+        CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st));
+        t->fuse_stamp = 0;
+    }
+    if (t->fuse_stamp == 0xffffffffu) { CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st)); t->fuse_stamp = 0; }
+    *stamp = ++t->fuse_stamp;
+    return CCM_OK;
+}
+
+// A view of the caller's as the Fuse and loop kernels read it
+static inline void fuse_view_fill(FuseView& D, const ccm_fuse_view& V)
+{
+    std::memcpy(D.Tcw, V.Tcw, sizeof D.Tcw); std::memcpy(D.Ow, V.Ow, sizeof D.Ow);
+    D.fx = V.fx; D.fy = V.fy; D.cx = V.cx; D.cy = V.cy; D.min_x = V.min_x; D.max_x = V.max_x; D.min_y = V.min_y; D.max_y = V.max_y;
+    D.n = V.kf->n; D.pad_ = 0; D.mp_id = V.kf->mp_id;
+}
+
 // Marks every slot of list [n] with its last position; CCM_E_ARG for a slot outside the table.  dup: whether a slot occurs twice.
 static inline int mark_slots(ccm_ctx* c, ccm_map_table* t, int n, const int32_t* list, bool* dup)
 {

@@ -8,19 +8,6 @@
 static_assert(sizeof(Sim3View) == 168 && sizeof(Sim3Pair) == 16 && sizeof(WinGrid) == 80, "per-pair upload of ccm_search_by_sim3_table_frames");
 static_assert(sizeof(FuseView) == 112 && sizeof(GreedyKf) == 16, "per-view upload of ccm_search_by_projection_table_frames");
 
-// The table's stamped where[]: created on first use, cleared when the 32-bit stamp wraps.  Returns the stamp of this call.
-static int next_where_stamp(ccm_ctx* c, ccm_map_table* t, hipStream_t st, unsigned* stamp)
-{
-    if (!t->where.p) {
-        CCM_RESERVE(c, t->where, (size_t)t->capacity * 8);
-        CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st));
-        t->fuse_stamp = 0;
-    }
-    if (t->fuse_stamp == 0xffffffffu) { CCM_HIP(c, hipMemsetAsync(t->where.p, 0, (size_t)t->capacity * 8, st)); t->fuse_stamp = 0; }
-    *stamp = ++t->fuse_stamp;
-    return CCM_OK;
-}
-
 extern "C" {
 
 // ORBmatcher::SearchBySim3 (src/ORBmatcher.cpp:1124-1348) for n_pairs candidate pairs.  Entries: the features of every side-1 handle,
@@ -224,12 +211,8 @@ int ccm_search_by_projection_table_frames(ccm_ctx* c, ccm_map_table* t, const cc
 
         FuseView* hv = G.host<FuseView>(o_view); WinGrid* hg = G.host<WinGrid>(o_grid); GreedyKf* gk = G.host<GreedyKf>(o_gk);
         for (int k = 0; k < n_kf; k++) {
-            const ccm_fuse_view& V = p->views[k].view;
-            const ccm_frame* f = V.kf;
-            FuseView& D = hv[k];
-            std::memcpy(D.Tcw, V.Tcw, sizeof D.Tcw); std::memcpy(D.Ow, V.Ow, sizeof D.Ow);
-            D.fx = V.fx; D.fy = V.fy; D.cx = V.cx; D.cy = V.cy; D.min_x = V.min_x; D.max_x = V.max_x; D.min_y = V.min_y; D.max_y = V.max_y;
-            D.n = f->n; D.pad_ = 0; D.mp_id = f->mp_id;
+            const ccm_frame* f = p->views[k].view.kf;
+            fuse_view_fill(hv[k], p->views[k].view);
             hg[k] = frame_win_grid(f);
             gk[k] = GreedyKf{ k * n_pt, n_pt, ff[k], f->n };
             G.put(o_msin + (size_t)ff[k] * 4, p->views[k].matched_slot, (size_t)f->n * 4);
@@ -262,12 +245,7 @@ int ccm_search_by_projection_table_frames(ccm_ctx* c, ccm_map_table* t, const cc
         A.u = taps ? G.dev<float>(o_u) : nullptr; A.v = taps ? G.dev<float>(o_v) : nullptr; A.level = taps ? G.dev<int>(o_lvl) : nullptr;
         loop_launch_project(st, A, t->T);
         CCM_HIP(c, hipGetLastError());
-        auto lists = [&](int cap) -> int {
-            CCM_RESERVE(c, S.ci, m * cap * 4); CCM_RESERVE(c, S.cd, m * cap * 4); CCM_RESERVE(c, S.cn, m * 4);
-            match_launch_window_batch(st, d_grid, A.qkf, (int)m, A.qx, A.qy, A.qr, A.none, A.none, A.qdesc, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>());
-            CCM_HIP(c, hipGetLastError());
-            return CCM_OK;
-        };
+        const WinLists L{ WinGrid{}, d_grid, A.qkf, (int)m, A.qx, A.qy, A.qr, A.none, A.none, A.qdesc, &S.ci, &S.cd, &S.cn };
         auto deliver = [&]() {
             G.get(r->best_idx, o_bi, m * 4); G.get(r->observed, o_obs, m); G.get(r->matched_slot, o_ms, NF * 4);
             G.get(r->best_dist, o_bd, m * 4); G.get(r->gate, o_gate, m);
@@ -282,46 +260,27 @@ int ccm_search_by_projection_table_frames(ccm_ctx* c, ccm_map_table* t, const cc
             return 0;
         }
         if (!window_host_accept_forced() && match_window_greedy_lds(max_n, 0) <= kGreedyLdsMax) {
-            int cap = 64;
-            for (int attempt = 0; attempt < 3; attempt++) {
-                if (attempt) {                                                 // the first attempt may have set flags and choices
-                    marks();
-                    CCM_HIP(c, hipMemsetAsync(d_out, 0xFF, m * 4, st));
-                }
-                if ((rc = lists(cap))) return rc;
-                GreedyArgs Q{ 0, 0, cap, S.ci.as<int>(), S.cd.as<int>(), S.cn.as<int>(), A.act, A.qlevel, d_oct, d_held, d_flag, 0.f, d_out, d_status,
-                              0, 0, nullptr, nullptr, nullptr, G.dev<GreedyKf>(o_gk) };
-                if (match_launch_window_greedy_batch(st, Q, n_kf, max_n)) return ccm_fail(c, CCM_E_DEVICE, "k_window_greedy: LDS request refused");
-                loop_launch_finish(st, n_kf, n_pt, d_grid, d_ff, d_slot, d_out, d_held, t->T, d_ms, r->best_dist ? G.dev<int>(o_bd) : nullptr);
-                CCM_HIP(c, hipGetLastError());
-                if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;      // the one synchronisation
-                const int* status = G.host<int>(o_status);
-                int need = 0;
-                for (int k = 0; k < n_kf; k++) if (status[3 * k] < 0) need = std::max(need, status[3 * k + 1]);
-                if (need > 0) { cap = need; continue; }                        // rare: a denser window than expected (in any view: all repeat)
-                deliver();
-                int total = 0;
-                for (int k = 0; k < n_kf; k++) { r->n_matches[k] = status[3 * k]; total += status[3 * k]; }
-                return total;
-            }
-            return ccm_fail(c, CCM_E_CAPACITY, "window candidate lists keep overflowing");
+            GreedyArgs Q{ 0, 0, 0, nullptr, nullptr, nullptr, A.act, A.qlevel, d_oct, d_held, d_flag, 0.f, d_out, d_status,
+                          0, 0, nullptr, nullptr, nullptr, G.dev<GreedyKf>(o_gk) };
+            // the first attempt may have set flags and choices in the views whose lists fitted
+            auto reset = [&]() -> int { marks(); CCM_HIP(c, hipMemsetAsync(d_out, 0xFF, m * 4, st)); return CCM_OK; };
+            auto tail = [&] { loop_launch_finish(st, n_kf, n_pt, d_grid, d_ff, d_slot, d_out, d_held, t->T, d_ms, r->best_dist ? G.dev<int>(o_bd) : nullptr); };
+            // the one synchronisation
+            auto fetch = [&](const int** s) -> int { *s = G.host<int>(o_status); const int e = G.download(c, 0, res_end); return e ? e : G.wait(c); };
+            const int* status = nullptr;
+            if ((rc = window_greedy_drive(c, L, Q, 1, n_kf, max_n, reset, tail, fetch, &status))) return rc;
+            deliver();
+            int total = 0;
+            for (int k = 0; k < n_kf; k++) { r->n_matches[k] = status[3 * k]; total += status[3 * k]; }
+            return total;
         }
 
         // host acceptance (CCM_WINDOW_HOST_ACCEPT=1, or a handle too large for the acceptance kernel's LDS): the lists, the queries' flags
-        // and the octaves come to the host, and the loop of :388-441 runs there, view by view
-        int cap = 64;
-        std::vector<int32_t> ci, cd, cn(m), qlvl(m), oct(NF);
-        std::vector<uint8_t> act(m);
-        for (;;) {
-            if ((rc = lists(cap))) return rc;
-            if ((rc = frame_fetch(c, cn.data(), S.cn.p, m * 4))) return rc;
-            int mx = 0;
-            for (int v : cn) mx = std::max(mx, v);
-            if (mx > cap) { cap = mx; continue; }
-            ci.resize(m * cap); cd.resize(m * cap);
-            if ((rc = frame_fetch(c, ci.data(), S.ci.p, ci.size() * 4)) || (rc = frame_fetch(c, cd.data(), S.cd.p, cd.size() * 4))) return rc;
-            break;
-        }
+        // and the octaves come to the host, and window_accept_sim3_host runs there, view by view
+        WinHostLists H{ 64 };
+        std::vector<int32_t> qlvl(m), oct(NF);
+        std::vector<uint8_t> act(m), matched;
+        if ((rc = window_lists_host(c, L, H))) return rc;
         if ((rc = frame_fetch(c, qlvl.data(), A.qlevel, m * 4)) || (rc = frame_fetch(c, act.data(), A.act, m)) ||
             (rc = frame_fetch(c, oct.data(), d_oct, NF * 4))) return rc;
         if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;
@@ -329,28 +288,14 @@ int ccm_search_by_projection_table_frames(ccm_ctx* c, ccm_map_table* t, const cc
         int* bd = r->best_dist ? G.host<int>(o_bd) : nullptr;
         int total = 0;
         for (int k = 0; k < n_kf; k++) {
-            int nmatches = 0;
-            for (int j = 0; j < n_pt; j++) {                                   // sequential: vpMatched grows while the points are visited
-                const size_t q = (size_t)k * n_pt + j;
-                if (bd) bd[q] = 256;
-                if (!act[q]) continue;
-                const int lvl = qlvl[q];
-                int bestDist = 256, bestIdx = -1;
-                for (int e = 0; e < cn[q]; e++) {
-                    const int idx = ci[q * cap + e];
-                    if (ms[ff[k] + idx] >= 0) continue;                        // :393
-                    const int kpLevel = oct[ff[k] + idx];
-                    if (kpLevel < lvl - 1 || kpLevel > lvl) continue;
-                    const int dist = cd[q * cap + e];
-                    if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-                }
-                if (bestDist <= 50) {                                          // TH_LOW
-                    bi[q] = bestIdx;
-                    if (bd) bd[q] = bestDist;
-                    if (!held[q]) { ms[ff[k] + bestIdx] = p->slot[j]; nmatches++; }        // :436-440
-                }
-            }
-            r->n_matches[k] = nmatches; total += nmatches;
+            const size_t q0 = (size_t)k * n_pt;
+            matched.resize(ff[k + 1] - ff[k]);                                 // vpMatched as flags ...
+            for (int i = ff[k]; i < ff[k + 1]; i++) matched[i - ff[k]] = ms[i] >= 0;
+            r->n_matches[k] = window_accept_sim3_host(n_pt, act.data() + q0, qlvl.data() + q0, H.ci.data() + q0 * H.cap, H.cd.data() + q0 * H.cap, H.cn.data() + q0, H.cap,
+                                                      oct.data() + ff[k], held + q0, matched.data(), bi + q0, bd ? bd + q0 : nullptr);
+            for (int j = 0; j < n_pt; j++)                                     // ... and the accepted, unobserved points as slots (:436-440)
+                if (bi[q0 + j] >= 0 && !held[q0 + j]) ms[ff[k] + bi[q0 + j]] = p->slot[j];
+            total += r->n_matches[k];
         }
         deliver();
         return total;

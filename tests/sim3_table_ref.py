@@ -320,6 +320,31 @@ def big_loop_scene():
 HAND_SHARED = ([(300.0, 200.0, 2, 1), (303.0, 200.0, 2, 52)], [(300.5, 200.0, 2, 3), (301.0, 200.0, 2, 0)])
 
 
+# Seventy octave-2 features on a 1-px lattice, 10 x 7, around (300, 200): every one lies inside the window of either point of
+# HAND_SHARED at th = 10 (radius 10 * 1.2^2 = 14.4 px), so their lists hold 70 > 64 candidates.  Feature 37 is at distance 7 | 10 from
+# the two points, the others at 60 or more.
+HAND_CROWDED = [(296.0 + i % 10, 197.0 + i // 10, 2, 10 if i == 37 else 63 + i) for i in range(70)]
+
+
+def retry_scene():
+    """The points of HAND_SHARED seen by two views of one table: view 0 is HAND_SHARED's (short lists, one match), view 1 the crowded
+    one, whose lists overflow the first capacity of the device route so that every view repeats."""
+    sc = hand_scene(*HAND_SHARED)
+    sc["kfs"].append(hand_scene(HAND_CROWDED, HAND_SHARED[1])["kfs"][0])
+    return sc
+
+
+def longest_lists(scene, th=10.0):
+    """Per view, the length of the longest GetFeaturesInArea list among the searched points (window_matcher_ref.features_in_area)."""
+    g = loop_views(scene)
+    out = []
+    for k, kf in enumerate(scene["kfs"]):
+        G = grid(kf, kf.get("bounds", BOUNDS))
+        out.append(max([len(W.features_in_area(G, g["u"][k][j], g["v"][k][j], F(th) * F(SCALE[g["level"][k][j]])))
+                        for j in np.flatnonzero(g["gate"][k] == LG_SEARCHED)], default=0))
+    return out
+
+
 def hand_scene(features, points, matched_slot=None, held=()):
     """Hand-built order cases under the identity camera.  features: (x, y, octave, bits) per feature; points: (x, y, octave, bits) per
     point, projected exactly onto (x, y) at depth 4 and predicting `octave`; bits = how many leading bits of the all-zero descriptor

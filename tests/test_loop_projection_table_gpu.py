@@ -190,13 +190,27 @@ def test_hand_built_order_cases(ctx):
     assert res["best_idx"][0].tolist() in ([1], [2]) and res["best_dist"][0].tolist() == [0]
 
 
+def test_capacity_retry_leaves_no_trace_of_the_first_attempt(ctx):
+    """Two views of one table (sim3_table_ref.retry_scene): the crowded view's lists hold 70 > 64 candidates, so every view repeats at
+    the longer capacity -- after the first attempt has accepted a match in the sparse view and marked its feature there
+    (test_sim3_table_cpu.py holds the scene to that).  The sparse view's result is the one-view call's, byte for byte."""
+    sc = Q.retry_scene()
+    res, g, nm = _run(ctx, sc)
+    one, _, _ = _run(ctx, Q.hand_scene(*Q.HAND_SHARED))
+    for k in OUT:
+        assert res[k][0].tobytes() == one[k][0].tobytes(), k
+    assert res["matched_slot"][0].tobytes() == one["matched_slot"][0].tobytes() and res["n_matches"][0] == one["n_matches"][0] == 1
+    assert res["best_idx"].tolist() == [[0, -1], [37, -1]] and nm.tolist() == [1, 1] and res["matched_slot"][1][37] == 0
+
+
 def test_host_acceptance_stays_exact():
     """The host acceptance loops behind the device-made queries (what a handle too large for the acceptance kernel's LDS takes): a child
-    process with CCM_WINDOW_HOST_ACCEPT=1 reruns the order cases, the empty keyframe and the 257-point block edges."""
+    process with CCM_WINDOW_HOST_ACCEPT=1 reruns the order cases, the capacity-retry scene (there: the lists grown on the host), the
+    empty keyframe and the 257-point block edges."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CCM_WINDOW_HOST_ACCEPT="1", PYTHONPATH=root)
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "-k",
-                          "hand_built or empty_keyframe or (every_block_edge and 257)"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                          "hand_built or capacity_retry or empty_keyframe or (every_block_edge and 257)"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0 and " passed" in out.stdout, out.stdout[-2000:] + out.stderr[-1000:]
 
 

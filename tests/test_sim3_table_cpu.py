@@ -211,6 +211,17 @@ def test_loop_scene_conditions():
     assert nm[0] >= 100 and (g["ambiguous"] & (g["gate"] == Q.LG_SEARCHED)).sum() <= 0.01 * (g["gate"] == Q.LG_SEARCHED).sum()
 
 
+def test_retry_scene_overflows_the_first_capacity_in_one_view_only():
+    """What test_loop_projection_table_gpu.py's capacity-retry case relies on, from the definition alone: the crowded view's lists are
+    longer than the device route's first capacity of 64, the sparse view's are not, and the sparse view accepts a match (so the first
+    attempt has written flags and a choice there before every view repeats)."""
+    sc = Q.retry_scene()
+    sparse, crowded = Q.longest_lists(sc)
+    assert crowded >= 65 and 1 <= sparse <= 64, (sparse, crowded)
+    nm, bi, ms = Q.loop_accept(sc, Q.loop_views(sc))
+    assert nm[0] >= 1 and bi[0].tolist() == [0, -1] and bi[1].tolist() == [37, -1] and ms[1][37] == 0
+
+
 def test_hand_built_order_cases_of_the_restatement():
     # two points whose windows share their nearest feature: the first in the list takes it, the second its next best
     sc = Q.hand_scene(*Q.HAND_SHARED)
