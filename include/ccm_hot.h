@@ -156,6 +156,11 @@ int ccm_orb_debug_candidates(ccm_ctx*, int image, int level, int32_t* xy, int32_
  * geometry's number of keypoint slots per frame, lane_frames the configured frames per chunk (CCM_ORB_LANE_FRAMES; 0 = one
  * chunk).  Writes at most max entries (any array may be NULL) and returns the number of chunks, or an error. */
 int ccm_orb_debug_lane_plan(int n_images, int out_per_frame, int lane_frames, int32_t* frame0, int32_t* nrun, int32_t* lane, int max);
+/* The FAST-9/16 score as the fused kernel computes it, on the CPU (host only, no GPU).  vr: n rows of 17 bytes, the centre
+ * pixel and its 16 ring pixels in ring order.  full[i] = the score by its definition (both polarities); split[i] = what the
+ * kernel stores at thresholds min(iniThFAST, minThFAST) = t_lo -- one polarity per pass, chosen by the four compass pixels --
+ * which is full[i] where full[i] >= t_lo and full[i] > 0, else -1 (nothing stored). */
+int ccm_debug_fast_score(const uint8_t* vr /* n x 17: v, ring */, int n, int t_lo, int32_t* full, int32_t* split);
 
 /* ------------------------------------------------------------------ matcher
  * ORBmatcher::DescriptorDistance (cslam/src/ORBmatcher.cpp:1653-1669): host helper. */

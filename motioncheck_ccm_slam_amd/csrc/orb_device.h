@@ -106,3 +106,72 @@ __host__ __device__ inline int fast_score16(int v, const int* r)
     }
     return max(A, -B) - 1;
 }
+
+// One polarity of that score on three-operand min/max: e[k] = ring[k] - v (brighter) or v - ring[k] (darker),
+// fast_arc16(e) = max over the 16 arcs of min(e[k .. k+8]), and fast_score16(v, r) == max(arc(r - v), arc(v - r)) - 1.
+// 16 + 16 + 8 instructions: w3[k] = min of 3 neighbours, w9[k] = min of three w3 = min of 9, a max3 fold over the sixteen w9.
+// On the device every step is one v_min3_i32 / v_max3_i32 by name: written with min() / max() the compiler shares pairs between
+// neighbouring arcs and falls back to two-operand forms (110 instructions for both polarities where 80 do).
+__host__ __device__ inline int fast_min3(int a, int b, int c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int r; asm("v_min3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
+#else
+    return std::min(a, std::min(b, c));
+#endif
+}
+__host__ __device__ inline int fast_max3(int a, int b, int c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int r; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
+#else
+    return std::max(a, std::max(b, c));
+#endif
+}
+__host__ __device__ inline int fast_mad24(int a, int b, int c)                  // a * b + c, |a|, |b| < 2^23
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int r; asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r;
+#else
+    return a * b + c;
+#endif
+}
+__host__ __device__ inline int fast_arc16(const int* e)
+{
+    int w3[16], w9[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) w3[k] = fast_min3(e[k], e[(k + 1) & 15], e[(k + 2) & 15]);
+#pragma unroll
+    for (int k = 0; k < 16; k++) w9[k] = fast_min3(w3[k], w3[(k + 3) & 15], w3[(k + 6) & 15]);
+    int m = fast_max3(w9[0], w9[1], w9[2]);
+#pragma unroll
+    for (int k = 3; k < 15; k += 2) m = fast_max3(m, w9[k], w9[k + 1]);
+    return max(m, w9[15]);
+}
+
+// What k_fast_cells stores for a pixel that passed its rejection test -- the score where `score >= t_lo && score > 0`, else
+// nothing -- from ONE polarity per pass, chosen by the four compass pixels r[0], r[4], r[8], r[12] (t_lo >= 0).
+//   can_b = min(max(r0, r8), max(r4, r12)) > v + t_lo,   can_d = max(min(r0, r8), min(r4, r12)) < v - t_lo.
+// Lemma.  Every arc of 9 contiguous ring pixels holds pixel 0 or 8 and pixel 4 or 12 (two pixels 8 apart cannot both be
+// missed by 9 of 16), so min over the arc of (r - v) <= min(max(r0, r8), max(r4, r12)) - v.  With can_b false that is <= t_lo
+// for every arc: arc(r - v) <= t_lo, the brighter polarity alone scores arc - 1 < t_lo.  Then either the full score is
+// below t_lo too (nothing stored either way), or the darker polarity is >= t_lo, is the maximum, and is the full score.
+// So a polarity whose flag is false never changes what `score >= t_lo && score > 0` stores.  Mirrored for can_d.
+// Both flags: the polarities are scored one after the other (the kernel: in two passes).  At most one of them can store,
+// since a stored score > 0 needs 9 ring pixels strictly brighter than v, or 9 strictly darker, and the ring has 16.
+// `darker`: false = choose by the flags (the brighter polarity first where both hold), true = the darker polarity only (the
+// second pass of a pixel with both flags).  Returns the arc value of the polarity scored; the caller stores arc - 1 where
+// arc > max(t_lo, 1), which is `score >= t_lo && score > 0`.  Where NEITHER flag holds the darker polarity is scored and the
+// lemma itself keeps it from storing (arc <= t_lo): no select for that case.  *again: both flags hold, the darker polarity
+// is still to be scored.
+__host__ __device__ inline int fast_arc16_split(int v, const int* r, int t_lo, bool darker, bool* again)
+{
+    const int bm = min(max(r[0], r[8]), max(r[4], r[12])), dm = max(min(r[0], r[8]), min(r[4], r[12]));
+    const bool can_b = !darker && bm > v + t_lo, can_d = darker || dm < v - t_lo;
+    *again = can_b && can_d;
+    const int s = can_b ? 1 : -1, c = can_b ? -v : v;
+    int e[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) e[k] = fast_mad24(s, r[k], c);         // r - v or v - r per lane: one instruction per ring pixel
+    return fast_arc16(e);
+}

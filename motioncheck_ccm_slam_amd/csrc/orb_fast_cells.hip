@@ -65,6 +65,7 @@ extern "C" int ccm_debug_fc_stamps(unsigned long long* out, int n_wgs)
 // image pixels in the global address space (global_load_*, not flat_load_*); fc_u32x4_a4: 16 bytes at a 4-byte-aligned address
 typedef const __attribute__((address_space(1))) uint8_t fc_gbyte;
 typedef const __attribute__((address_space(1))) unsigned fc_gu32;
+typedef const __attribute__((address_space(3))) uint8_t fc_lbyte;      // a byte of LDS by its 32-bit address
 typedef unsigned fc_u32x4 __attribute__((ext_vector_type(4)));
 typedef fc_u32x4 fc_u32x4_a4 __attribute__((aligned(4)));
 // element ci (per lane) of four wave-uniform values: three selects, no memory
@@ -194,30 +195,74 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     unsigned short* wsurv = surv + wv * WCAP;
     // ---- rejection + scoring, WAVE-LOCAL (round 3): a wave tests its own runs of 64 items (4 pixels per lane), pushes the survivors on
-    // its own stack in LDS, and scores them 64 at a time -- a full wave per 130-instruction score -- as soon as 64 are waiting.  No
+    // its own stack in LDS, and scores them 64 at a time -- a full wave per scoring pass (97 vector instructions) -- as soon as 64 are waiting.  No
     // workgroup barrier until every pixel of the band is scored: round 2 pooled the survivors of a row block over the four waves
     // (two barriers per row block, and every wave waited for the slowest at each of them).  The stack never holds more than
     // 63 + 256 entries.  The order in which pixels are scored does not matter: the NMS below works on the set.
-    auto score_at = [&](int pos) {
-        const uint8_t* c = T + pos;
-        const int v = c[0];
+    //
+    // Scoring, ONE POLARITY PER PASS.  A stack entry is the pixel's tile offset (< 2^15: the host keeps pitch * bh below that) and, in
+    // bit 15, "the darker polarity only".  A pass pops up to 64 entries and scores each in the polarity its four compass pixels allow
+    // (fast_arc16_split, orb_device.h, with the lemma: a polarity whose compass flag is false scores below t_lo and cannot change
+    // what is stored); a pixel with neither flag stores nothing.  Where both flags hold (0.1 % of the survivors on level 0, 2-6 % above)
+    // the brighter polarity is scored now and the entry goes back on the stack with bit 15 set; such an entry is scored in the darker
+    // polarity and never pushed again.  At most one of the two passes stores (a stored score > 0 needs 9 ring pixels strictly
+    // brighter than v, or 9 strictly darker, and the ring has 16), so S[pos] and the `nz` list need no maximum and no second entry.
+    // Stack bound: a pass pops n = min(wcnt, 64) entries and pushes back at most n, so the stack never grows while it is drained, and
+    // it is drained below 64 before the next run of items pushes at most 256: FC_WAVE_CAP holds as before.  The drain ends: every
+    // pass either pops an unflagged entry for good or, holding flagged entries only, pushes nothing.
+    // The ring is read from seven row bases with the column 0..6 in the ds_read_u8 offset field (the row offsets k * P are
+    // run-time values: left to itself the compiler builds sixteen addresses).
+    const unsigned t_lds = (unsigned)(uintptr_t)(fc_lbyte*)T;   // the tile's LDS address: the row bases are LDS addresses, not offsets into T
+    const int thr = max(t_lo, 1);                              // score >= t_lo && score > 0  <=>  arc = score + 1 > max(t_lo, 1)
+    int wcnt = 0;                                              // entries on this wave's stack (wave-uniform)
+    auto score_top = [&]() {
+        wcnt = __builtin_amdgcn_readfirstlane(wcnt);           // (wave-uniform by construction; this keeps the stack arithmetic scalar)
+        const int n = min(wcnt, 64);
+        wcnt -= n;
+        const bool on = lane < n;
+        const unsigned long long on_mask = n >= 64 ? ~0ull : (1ull << n) - 1ull;
+        const unsigned popped = wsurv[wcnt + lane];            // (in bounds for every lane: wcnt + 63 < FC_WAVE_CAP)
+        const unsigned ent = on ? popped : (unsigned)(3 * P + 3);
+        const int pos = (int)(ent & 0x7FFFu);
+        int rb[7];
+#pragma unroll
+        for (int k = 0; k < 7; k++) rb[k] = pos + (int)(t_lds + (unsigned)((k - 3) * P - 3));
+#define FC_PX(dx, dy) (*(fc_lbyte*)(uintptr_t)(unsigned)(rb[(dy) + 3] + ((dx) + 3)))
+        const int v = FC_PX(0, 0);
         int r[16];
-        r[0] = c[3 * P];      r[1] = c[3 * P + 1];  r[2] = c[2 * P + 2];  r[3] = c[P + 3];
-        r[4] = c[3];          r[5] = c[-P + 3];     r[6] = c[-2 * P + 2]; r[7] = c[-3 * P + 1];
-        r[8] = c[-3 * P];     r[9] = c[-3 * P - 1]; r[10] = c[-2 * P - 2]; r[11] = c[-P - 3];
-        r[12] = c[-3];        r[13] = c[P - 3];     r[14] = c[2 * P - 2]; r[15] = c[3 * P - 1];
-        const int sc = fast_score16(v, r);
-        if (sc >= t_lo && sc > 0) {
-            S[pos] = (uint8_t)sc;
-            const int q = atomicAdd(nsurv + 1, 1);
-            if (q < FC_NZ) nz[q] = (unsigned short)pos;
+        r[0] = FC_PX(0, 3);    r[1] = FC_PX(1, 3);    r[2] = FC_PX(2, 2);    r[3] = FC_PX(3, 1);
+        r[4] = FC_PX(3, 0);    r[5] = FC_PX(3, -1);   r[6] = FC_PX(2, -2);   r[7] = FC_PX(1, -3);
+        r[8] = FC_PX(0, -3);   r[9] = FC_PX(-1, -3);  r[10] = FC_PX(-2, -2); r[11] = FC_PX(-3, -1);
+        r[12] = FC_PX(-3, 0);  r[13] = FC_PX(-3, 1);  r[14] = FC_PX(-2, 2);  r[15] = FC_PX(-1, 3);
+#undef FC_PX
+        auto store = [&](bool st, int arc) {
+            if (st) {
+                S[pos] = (uint8_t)(arc - 1);
+                const int q = atomicAdd(nsurv + 1, 1);
+                if (q < FC_NZ) nz[q] = (unsigned short)pos;
+            }
+        };
+        if (t_lo < 0) {                                        // (no rejection by the compass pixels below 0: the full score)
+            const int arc = fast_score16(v, r) + 1;
+            store(on && arc > thr, arc);
+            return;
+        }
+        bool again;
+        const int arc = fast_arc16_split(v, r, t_lo, (ent >> 15) != 0u, &again);
+        store(on && arc > thr, arc);
+        const unsigned long long mb = __ballot(again) & on_mask;
+        if (mb != 0ull) {
+            if (on && again) wsurv[fc_mbcnt(mb, wcnt)] = (unsigned short)(ent | 0x8000u);
+            wcnt += __popcll(mb);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         }
     };
     {
-        int wcnt = 0;                                          // entries on this wave's stack (wave-uniform)
         const int items = (bh - 6) * PW;
         constexpr int r0 = 3;
-        for (int it0 = wv * 64; it0 < items; it0 += FC_TPB) {
+        for (int it0 = wv * 64;; it0 += FC_TPB) {
+            // (past the last run of items: one more round, in which no item is tested and the stack is emptied)
+            const bool more = it0 < items;
             const int it = it0 + lane;
             const int rr = (int)(((unsigned)it * pw_inv) >> 20);
             const int dw = it - rr * PW;                        // the item: pixels px .. px + 3, px = 4 * dw, of row = r0 + rr
@@ -262,10 +307,11 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                 wcnt = b3 + __popcll(m3);
                 // the LDS operations of one wave complete in order; the fence keeps the compiler from moving the pops above the pushes
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                while (wcnt >= 64) { wcnt -= 64; score_at(wsurv[wcnt + lane]); }
             }
+            const int leave = more ? 63 : 0;
+            while (wcnt > leave) score_top();
+            if (!more) break;
         }
-        if (lane < wcnt) score_at(wsurv[lane]);
     }
     __syncthreads();
     FC_STAMP(2);

@@ -3,6 +3,7 @@
 // Reference: cslam/src/ORBextractor.cpp (cited per function).
 #include "ccm_internal.h"
 #include "orb_types.h"
+#include "orb_device.h"
 #include <cmath>
 #include <cfloat>
 #include <algorithm>
@@ -270,6 +271,7 @@ static int orb_prepare(ccm_ctx* c, const ccm_orb_params* p, int w, int h, int nf
     for (const OrbBand& b : S.bands) S.band_lds = std::max(S.band_lds, orb_fast_cells_lds(b.pitch, b.bh));
     for (const OrbBand& b : S.bands) if (b.pitch > 256) S.fused = false;    // a single cell wider than the tile: two-kernel path
     if (S.band_lds > 60 * 1024) S.fused = false;                 // very large cells: keep the two-kernel path
+    for (const OrbBand& b : S.bands) if ((int)b.pitch * b.bh >= (1 << 15)) S.fused = false;     // (implied by the line above: bit 15 of a tile offset is k_fast_cells's flag)
     G.ncells = (int)S.cells.size(); G.ntiles = tile_acc;
     G.slots_per_frame = std::max(slot_acc, 1); G.keys_per_frame = key_acc; G.out_per_frame = out_acc;
     int list_cap = 0;
@@ -663,6 +665,27 @@ int ccm_orb_debug_candidates(ccm_ctx* c, int image, int level, int32_t* xy, int3
             }
         }
         return n;
+    });
+}
+
+int ccm_debug_fast_score(const uint8_t* vr, int n, int t_lo, int32_t* full, int32_t* split)
+{
+    return ccm_guard(nullptr, "ccm_debug_fast_score", [&]() -> int {
+        if (n < 0 || (n > 0 && (!vr || !full || !split))) return CCM_E_ARG;
+        const int thr = std::max(t_lo, 1);
+        for (int i = 0; i < n; i++) {
+            const int v = vr[17 * (size_t)i];
+            int r[16];
+            for (int k = 0; k < 16; k++) r[k] = vr[17 * (size_t)i + 1 + k];
+            full[i] = fast_score16(v, r);
+            if (t_lo < 0) { split[i] = full[i] + 1 > thr ? full[i] : -1; continue; }      // (the kernel: full score below 0)
+            // k_fast_cells's passes: the polarity the compass pixels allow, then the darker one where both flags held
+            bool again, none;
+            const int a1 = fast_arc16_split(v, r, t_lo, false, &again);
+            const int a2 = again ? fast_arc16_split(v, r, t_lo, true, &none) : 0;
+            split[i] = a1 > thr && a2 > thr ? -2 : a1 > thr ? a1 - 1 : a2 > thr ? a2 - 1 : -1;      // -2: both passes would store (cannot happen)
+        }
+        return CCM_OK;
     });
 }
 
