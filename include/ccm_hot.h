@@ -161,6 +161,12 @@ int ccm_orb_debug_lane_plan(int n_images, int out_per_frame, int lane_frames, in
  * kernel stores at thresholds min(iniThFAST, minThFAST) = t_lo -- one polarity per pass, chosen by the four compass pixels --
  * which is full[i] where full[i] >= t_lo and full[i] > 0, else -1 (nothing stored). */
 int ccm_debug_fast_score(const uint8_t* vr /* n x 17: v, ring */, int n, int t_lo, int32_t* full, int32_t* split);
+/* The items of the fused kernel's rejection test -- one dword (four pixels) of a band's LDS tile each -- in the order its waves
+ * take them, produced on the CPU by the code the kernel runs (host only, no GPU).  The band: LDS pitch in bytes (a multiple of 4,
+ * 16..256), bh rows (0..65), detection dwords dw_lo..dw_hi of a row (1 <= dw_lo, dw_hi <= pitch / 4 - 2; dw_hi < dw_lo = none).
+ * Writes at most max rows of six int32 -- run, wave, lane, row, dword, pos0 (tile offset of the item's first pixel) -- run by
+ * run, and returns the number of items (>= 0, it may exceed max) or an error. */
+int ccm_debug_fc_items(int pitch, int bh, int dw_lo, int dw_hi, int32_t* out /* max x 6 */, int max);
 
 /* ------------------------------------------------------------------ matcher
  * ORBmatcher::DescriptorDistance (cslam/src/ORBmatcher.cpp:1653-1669): host helper. */

@@ -2,6 +2,7 @@
 // Wavefront = 64 everywhere; ballots are 64-bit.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "orb_types.h"
 
 #define WAVE 64
 
@@ -174,4 +175,55 @@ __host__ __device__ inline int fast_arc16_split(int v, const int* r, int t_lo, b
 #pragma unroll
     for (int k = 0; k < 16; k++) e[k] = fast_mad24(s, r[k], c);         // r - v or v - r per lane: one instruction per ring pixel
     return fast_arc16(e);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The items of k_fast_cells's rejection test, and the order in which its waves take them (the kernel and, through
+// ccm_debug_fc_items, the host run this very code).  An item is four pixels = one dword of the band's tile that holds a detection
+// column: rows 3 .. bh - 4, dwords dw_lo .. dw_hi, numbered row-major over those n_dw = dw_hi - dw_lo + 1 dwords ONLY (before, every
+// dword of the row was numbered, and the lanes outside dw_lo .. dw_hi idled through their run: 4292 runs per 752x480 frame of 8
+// levels against 3791).  A run is 64 consecutive items, one per lane; run R goes to wave R % FC_WAVES, so the run counts of the
+// waves differ by at most one.  A lane keeps (rr, dw) = (row - 3, dword) and advances it by FC_ITEM_STRIDE = 64 * FC_WAVES items per
+// run with one add, one conditional wrap and an add with carry: the quotient and remainder of FC_ITEM_STRIDE by n_dw come with
+// the band record (FcEnum, orb_types.h), no multiply or divide in the loop.
+#define FC_WAVES 4
+#define FC_ITEM_STRIDE (64 * FC_WAVES)
+struct FcItem { int rr, dw; };         // row - 3, dword of the row
+__host__ __device__ inline FcEnum fc_enum(int dw_lo, int dw_hi)
+{
+    FcEnum e{};
+    const int n = dw_hi >= dw_lo ? dw_hi - dw_lo + 1 : 0, d = n > 0 ? n : 1;
+    e.n_dw = (short)n; e.d_step = (short)(FC_ITEM_STRIDE % d); e.r_step = (short)(FC_ITEM_STRIDE / d);
+    e.nd_inv = (1u << 20) / (unsigned)d + 1u;
+    return e;
+}
+// runs of a band of bh rows (none where bh <= 6 or no dword holds a detection column)
+__host__ __device__ inline int fc_item_runs(int bh, int n_dw) { return bh > 6 && n_dw > 0 ? ((bh - 6) * n_dw + 63) >> 6 : 0; }
+// first item of lane l of wave w: item 64 * w + l
+__host__ __device__ inline FcItem fc_item_start(int dw_lo, int n_dw, unsigned nd_inv, int w, int l)
+{
+    const int it = 64 * w + l;
+    FcItem i;
+    i.rr = (int)(((unsigned)it * nd_inv) >> 20);
+    i.dw = dw_lo + it - i.rr * n_dw;
+    return i;
+}
+// the lane's item of the wave's next run: FC_ITEM_STRIDE items on (dw_end = dw_hi + 1)
+__host__ __device__ inline void fc_item_step(FcItem& i, int dw_end, int n_dw, int d_step, int r_step)
+{
+    const int d = i.dw + d_step;
+    const bool wrap = d >= dw_end;
+    i.dw = wrap ? d - n_dw : d;
+    i.rr += r_step + (wrap ? 1 : 0);
+}
+// the item is one of the band's (a lane past the last item of the last run: no)
+__host__ __device__ inline bool fc_item_valid(const FcItem& i, int bh) { return i.rr < bh - 6; }
+// tile offset of the item's first pixel (< 2^15: the host keeps pitch * bh below that)
+__host__ __device__ inline int fc_item_pos0(const FcItem& i, int P)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __mul24(i.rr, P) + 3 * P + 4 * i.dw;        // (rr <= 58, P <= 256: a 24-bit multiply-add, not v_mul_lo_u32)
+#else
+    return (3 + i.rr) * P + 4 * i.dw;
+#endif
 }

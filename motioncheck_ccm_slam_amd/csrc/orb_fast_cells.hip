@@ -23,6 +23,11 @@
 // Measured and dropped (profiles/fc_chain_ab.txt): the rank loop reading its bucket eight entries per wait (nothing), all staging
 // trips of a thread in flight before the first store (+0.002 ms), the next rejection run's LDS dwords requested before the current
 // run's ballots (+0.012 ms, 60 registers), the column masks requested with the pixel dwords (nothing).
+// The rejection test takes its items -- one dword = four pixels each -- from the dwords dw_lo .. dw_hi that hold detection columns, not
+// from every dword of the tile (3791 runs of 64 per 752x480 frame against 4292; the dominant 4-cell band 16 runs dealt 4 / 4 / 4 / 4
+// to the waves, not 18 dealt 5 / 5 / 4 / 4), by fc_item_* of orb_device.h, which the host runs too (ccm_debug_fc_items).  A run is 71
+// vector instructions (80 before: profiles/fc_reject_static.txt): run number and stack count in scalar registers, west / east pixels
+// by one v_perm_b32 each, the wave's last run drains its stack itself.  0.328 -> 0.3125 ms (profiles/fc_reject_ab.txt).
 #ifndef FC_NZ
 #define FC_NZ 1024
 #endif
@@ -33,6 +38,7 @@
 #ifndef FC_TPB
 #define FC_TPB 256              // threads per band workgroup (measured: 192 0.56, 256 0.52, 320 0.75, 384 0.82 ms)
 #endif
+static_assert(FC_TPB == FC_ITEM_STRIDE, "the band record carries the item steps of FC_WAVES waves (fc_enum, orb_device.h)");
 // Survivors of the rejection test wait on the wave's own stack in LDS (running count in a scalar register, no atomic) and are scored
 // 64 at a time: the stack never holds more than 63 waiting entries + the 256 pixels of one run of 64 four-pixel items.
 #define FC_WAVE_CAP 320         // wave-local stack: at most 63 waiting + the 256 pixels of one item
@@ -178,8 +184,8 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     // columns of the tile that belong to some cell's detection area: [c_lo, c_hi)
     const int c_lo = B.c_lo, c_hi = B.c_hi;
     const int t_lo = min(g.ini_th, g.min_th);
-    // dwords that hold at least one detection column and have both neighbours inside the row
-    const int dw_lo = B.dw_lo, dw_hi = B.dw_hi;
+    // first of the dwords that hold at least one detection column and have both neighbours inside the row (B.items.n_dw of them)
+    const int dw_lo = B.dw_lo;
     if (tid < PW) {
         unsigned mk[4];
         for (int i = 0; i < 4; i++) mk[i] = (4 * tid + i >= c_lo && 4 * tid + i < c_hi) ? 0xFFFFu : 0u;
@@ -193,7 +199,8 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         for (int i = 0; i < ORB_BAND_CELLS; i++) if (i < bncells && tid >= bclo[i] && tid < bclo[i] + bcwd[i]) ci = i;
         colcell[tid] = (uint8_t)ci;
     }
-    unsigned short* wsurv = surv + wv * WCAP;
+    const int wvs = __builtin_amdgcn_readfirstlane(wv);        // the wave's number in a scalar register: its stack's address and its runs are scalar
+    unsigned short* wsurv = surv + wvs * WCAP;
     // ---- rejection + scoring, WAVE-LOCAL (round 3): a wave tests its own runs of 64 items (4 pixels per lane), pushes the survivors on
     // its own stack in LDS, and scores them 64 at a time -- a full wave per scoring pass (97 vector instructions) -- as soon as 64 are waiting.  No
     // workgroup barrier until every pixel of the band is scored: round 2 pooled the survivors of a row block over the four waves
@@ -258,22 +265,20 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         }
     };
     {
-        const int items = (bh - 6) * PW;
-        constexpr int r0 = 3;
-        for (int it0 = wv * 64;; it0 += FC_TPB) {
-            // (past the last run of items: one more round, in which no item is tested and the stack is emptied)
-            const bool more = it0 < items;
-            const int it = it0 + lane;
-            const int rr = (int)(((unsigned)it * pw_inv) >> 20);
-            const int dw = it - rr * PW;                        // the item: pixels px .. px + 3, px = 4 * dw, of row = r0 + rr
+        // the items: the dwords dw_lo .. dw_hi of rows 3 .. bh - 4, run R of 64 to wave R % FC_WAVES (fc_item_*, orb_device.h)
+        const int n_dw = B.items.n_dw, d_step = B.items.d_step, r_step = B.items.r_step;
+        const int runs = fc_item_runs(bh, n_dw), dw_end = dw_lo + n_dw;
+        FcItem item = fc_item_start(dw_lo, n_dw, B.items.nd_inv, wv, lane);
+        // `run` and the stack count are wave-uniform and kept in scalar registers: the bases of the v_mbcnt pairs, the sums of the
+        // ballots' bit counts and the two loop tests are scalar instructions
+        for (int run = wvs; run < runs; run += FC_WAVES) {
+            wcnt = __builtin_amdgcn_readfirstlane(wcnt);
+            const int pos0 = fc_item_pos0(item, P);             // the item: pixels pos0 .. pos0 + 3 of the tile
             unsigned kk0 = 0, kk1 = 0;                          // 16-bit halves, .lo/.hi of kk0 = pixels 0 / 2, of kk1 = pixels 1 / 3
-            if (it < items && dw >= dw_lo && dw <= dw_hi) {
-                // P == 4 * PW: the centre dword of item `it` sits at byte r0 * P + 4 * it
-                const unsigned* crow = reinterpret_cast<const unsigned*>(T + r0 * P) + it;
+            if (fc_item_valid(item, bh)) {
+                const unsigned* crow = reinterpret_cast<const unsigned*>(T + pos0);
                 const unsigned c0 = crow[-1], c1 = crow[0], c2 = crow[1];
                 const unsigned nn = crow[3 * PW], ss = crow[-3 * PW];
-                const unsigned ww = __builtin_amdgcn_alignbyte(c1, c0, 1);        // columns px-3 .. px
-                const unsigned ee = __builtin_amdgcn_alignbyte(c2, c1, 3);        // columns px+3 .. px+6
                 const fc_us2 tt = fc_pk((unsigned)t_lo * 0x00010001u);
                 unsigned kk[2];
 #pragma unroll
@@ -281,36 +286,39 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                     const unsigned sel = h ? 0x0c030c01u : 0x0c020c00u;           // v_perm_b32: two bytes -> two u16
                     const fc_us2 v = fc_pk(__builtin_amdgcn_perm(0u, c1, sel));
                     const fc_us2 n = fc_pk(__builtin_amdgcn_perm(0u, nn, sel)), sq = fc_pk(__builtin_amdgcn_perm(0u, ss, sel));
-                    const fc_us2 w = fc_pk(__builtin_amdgcn_perm(0u, ww, sel)), e = fc_pk(__builtin_amdgcn_perm(0u, ee, sel));
+                    // west = columns px - 3 + i, east = px + 3 + i of pixel i: bytes 1, 3 (h = 1: 2, 4) of c0:c1 and 3, 5 (4, 6) of c1:c2,
+                    // one v_perm_b32 over the dword pair each
+                    const fc_us2 w = fc_pk(__builtin_amdgcn_perm(c1, c0, h ? 0x0c040c02u : 0x0c030c01u));
+                    const fc_us2 e = fc_pk(__builtin_amdgcn_perm(c2, c1, h ? 0x0c060c04u : 0x0c050c03u));
                     // every 9-arc holds ring pixel k or k+8: a corner brighter (darker) than v by more than t needs the
                     // larger (smaller) of BOTH opposite pairs beyond v + t (v - t)
                     const fc_us2 bm = __builtin_elementwise_min(__builtin_elementwise_max(n, sq), __builtin_elementwise_max(e, w));
                     const fc_us2 dm = __builtin_elementwise_max(__builtin_elementwise_min(n, sq), __builtin_elementwise_min(e, w));
                     kk[h] = fc_u(__builtin_elementwise_sub_sat(bm, (fc_us2)(v + tt))) | fc_u(__builtin_elementwise_sub_sat(__builtin_elementwise_sub_sat(v, tt), dm));
                 }
-                const uint2 cm = colmask[dw];
+                const uint2 cm = colmask[item.dw];
                 kk0 = kk[0] & cm.x; kk1 = kk[1] & cm.y;
             }
+            fc_item_step(item, dw_end, n_dw, d_step, r_step);
             // survivor predicates of the lane's four pixels: one 16-bit compare each
             const bool k0 = (kk0 & 0xFFFFu) != 0u, k1 = (kk1 & 0xFFFFu) != 0u;
             const bool k2 = (kk0 >> 16) != 0u, k3 = (kk1 >> 16) != 0u;
             const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1), m2 = __ballot(k2), m3 = __ballot(k3);
             if ((m0 | m1 | m2 | m3) != 0ull) {
                 // stack slot of the lane's pixel i among the wave's survivors of this item: pixels 0 of all lanes first, then
-                // pixels 1, ...; v_mbcnt adds the count of lower lanes to the running base
+                // pixels 1, ...; v_mbcnt counts the lower lanes, and the running base goes into the scalar part of the address
                 const int b1 = wcnt + __popcll(m0), b2 = b1 + __popcll(m1), b3 = b2 + __popcll(m2);
-                const int pos0 = r0 * P + 4 * it;                  // == row * P + px, as P == 4 * PW
-                if (k0) wsurv[fc_mbcnt(m0, wcnt)] = (unsigned short)pos0;
-                if (k1) wsurv[fc_mbcnt(m1, b1)] = (unsigned short)(pos0 + 1);
-                if (k2) wsurv[fc_mbcnt(m2, b2)] = (unsigned short)(pos0 + 2);
-                if (k3) wsurv[fc_mbcnt(m3, b3)] = (unsigned short)(pos0 + 3);
+                if (k0) (wsurv + wcnt)[fc_mbcnt(m0, 0)] = (unsigned short)pos0;
+                if (k1) (wsurv + b1)[fc_mbcnt(m1, 0)] = (unsigned short)(pos0 + 1);
+                if (k2) (wsurv + b2)[fc_mbcnt(m2, 0)] = (unsigned short)(pos0 + 2);
+                if (k3) (wsurv + b3)[fc_mbcnt(m3, 0)] = (unsigned short)(pos0 + 3);
                 wcnt = b3 + __popcll(m3);
                 // the LDS operations of one wave complete in order; the fence keeps the compiler from moving the pops above the pushes
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             }
-            const int leave = more ? 63 : 0;
+            // scored 64 at a time while another run follows; the wave's last run empties the stack
+            const int leave = run + FC_WAVES < runs ? 63 : 0;
             while (wcnt > leave) score_top();
-            if (!more) break;
         }
     }
     __syncthreads();

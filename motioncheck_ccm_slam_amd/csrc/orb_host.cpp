@@ -257,6 +257,7 @@ static int orb_prepare(ccm_ctx* c, const ccm_orb_params* p, int w, int h, int nf
             band.c_lo = (short)(c0.x0 + 3 - xa); band.c_hi = (short)(cl.x0 + cl.cw - 3 - xa);
             band.dw_lo = (short)std::max(1, band.c_lo >> 2); band.dw_hi = (short)std::min(PW - 2, (band.c_hi - 1) >> 2);
             band.pw_inv = (1u << 20) / (unsigned)PW + 1u; band.pq_inv = (1u << 20) / (unsigned)PQ + 1u;
+            band.items = fc_enum(band.dw_lo, band.dw_hi);
             band.w = G.lv[c0.level].w; band.h = G.lv[c0.level].h;
             for (size_t k = a; k < b; k++) {
                 const OrbCell& ck = S.cells[k];
@@ -686,6 +687,36 @@ int ccm_debug_fast_score(const uint8_t* vr, int n, int t_lo, int32_t* full, int3
             split[i] = a1 > thr && a2 > thr ? -2 : a1 > thr ? a1 - 1 : a2 > thr ? a2 - 1 : -1;      // -2: both passes would store (cannot happen)
         }
         return CCM_OK;
+    });
+}
+
+int ccm_debug_fc_items(int pitch, int bh, int dw_lo, int dw_hi, int32_t* out, int max)
+{
+    return ccm_guard(nullptr, "ccm_debug_fc_items", [&]() -> int {
+        if (pitch < 16 || pitch > 256 || (pitch & 3) || bh < 0 || bh > 65 || dw_lo < 1 || dw_hi > pitch / 4 - 2 || max < 0 || (max > 0 && !out))
+            return CCM_E_ARG;
+        // k_fast_cells's loop: wave w takes runs w, w + FC_WAVES, ...; here the runs in their global order
+        const FcEnum e = fc_enum(dw_lo, dw_hi);
+        const int runs = fc_item_runs(bh, e.n_dw);
+        FcItem it[FC_WAVES][64];
+        for (int w = 0; w < FC_WAVES; w++)
+            for (int l = 0; l < 64; l++) it[w][l] = fc_item_start(dw_lo, e.n_dw, e.nd_inv, w, l);
+        int n = 0;
+        for (int run = 0; run < runs; run++) {
+            const int w = run % FC_WAVES;
+            for (int l = 0; l < 64; l++) {
+                FcItem& i = it[w][l];
+                if (fc_item_valid(i, bh)) {
+                    if (n < max) {
+                        int32_t* o = out + 6 * (size_t)n;
+                        o[0] = run; o[1] = w; o[2] = l; o[3] = 3 + i.rr; o[4] = i.dw; o[5] = fc_item_pos0(i, pitch);
+                    }
+                    n++;
+                }
+                fc_item_step(i, dw_lo + e.n_dw, e.n_dw, e.d_step, e.r_step);
+            }
+        }
+        return n;
     });
 }
 

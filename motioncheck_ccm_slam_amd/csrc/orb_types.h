@@ -50,6 +50,12 @@ struct OrbCell {
     int slot_first, slot_cap;           // per-frame candidate slots of this cell
 };
 
+// Constants of the order in which k_fast_cells's waves take the items of the rejection test (the functions: orb_device.h, fc_enum).
+struct FcEnum {
+    short n_dw, d_step, r_step, pad_;  // detection dwords per row (>= 0); FC_ITEM_STRIDE % n_dw, FC_ITEM_STRIDE / n_dw
+    unsigned nd_inv;                   // floor(2^20 / n_dw) + 1: i / n_dw by multiply-shift, exact for i < 2^20 / n_dw (i < FC_ITEM_STRIDE here)
+};
+
 // A band of k_fast_cells: consecutive cells of one cell row of one level, with everything the kernel needs before it can request the
 // band's pixels -- one 64-byte scalar load.  (Until round 3 the kernel loaded a 16-byte band record, THEN the level record it
 // pointed to, THEN the first and last cell records, and computed two integer reciprocals: 3,700 cycles of dependent scalar work in
@@ -66,7 +72,8 @@ struct OrbBand {
     // its (at most ORB_BAND_CELLS) cells: first detection column of the tile and number of detection columns, candidate slots of the cell
     short clo[4], cwd[4];
     int slot_first[4], slot_cap[4];
-    int pad_[4];
+    FcEnum items;                      // the rejection test's item enumeration over dwords dw_lo .. dw_hi
+    int pad_[1];
 };
 #define ORB_BAND_CELLS 4
 static_assert(sizeof(OrbBand) == 128, "two s_load_dwordx16");
