@@ -46,22 +46,36 @@ __device__ __forceinline__ void xcd_work_item(int on, int& x, int& y)
     y = (int)q; x = (int)(w - q * gx);
 }
 
-// inclusive wave prefix sum
+// Inclusive wave prefix sum by DPP, with no LDS round trip (__shfl_up is a ds_bpermute each, six of them in a chain): the row_shr
+// ladder 1, 2, 4, 8 scans every row of 16 lanes (a lane whose source lies outside its row adds 0), row_bcast:15 adds the total of
+// rows 0 / 2 to rows 1 / 3, row_bcast:31 the total of rows 0-1 to rows 2-3.  Needs all 64 lanes active: a DPP read of an inactive
+// lane returns nothing, so call it only under wave-uniform control (k_octree's loops over 64-entry chunks are).
 __device__ __forceinline__ int wave_incl_scan(int v)
 {
-    const int lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int y = __shfl_up(v, d, 64);
-        if (lane >= d) v += y;
-    }
+#define WSC_STEP(ctrl, rows) v += __builtin_amdgcn_update_dpp(0, v, ctrl, rows, 0xf, false);
+    WSC_STEP(0x111, 0xf)           // row_shr:1
+    WSC_STEP(0x112, 0xf)           // row_shr:2
+    WSC_STEP(0x114, 0xf)           // row_shr:4
+    WSC_STEP(0x118, 0xf)           // row_shr:8
+    WSC_STEP(0x142, 0xa)           // row_bcast:15 into rows 1, 3
+    WSC_STEP(0x143, 0xc)           // row_bcast:31 into rows 2, 3
+#undef WSC_STEP
     return v;
 }
+// the wave's total behind wave_incl_scan: lane 63's value, by v_readlane (a scalar; all lanes active or not)
+__device__ __forceinline__ int wave_last(int incl) { return __builtin_amdgcn_readlane(incl, 63); }
+// Wave sum by DPP (the one-value form of wave_sum2_dpp below; the same condition: all 64 lanes active).
 __device__ __forceinline__ int wave_sum(int v)
 {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
+#define WS1_STEP(ctrl, rows) v += __builtin_amdgcn_update_dpp(0, v, ctrl, rows, 0xf, false);
+    WS1_STEP(0xb1, 0xf)            // quad_perm [1,0,3,2]
+    WS1_STEP(0x4e, 0xf)            // quad_perm [2,3,0,1]
+    WS1_STEP(0x141, 0xf)           // row_half_mirror
+    WS1_STEP(0x140, 0xf)           // row_mirror
+    WS1_STEP(0x142, 0xa)           // row_bcast:15 into rows 1, 3
+    WS1_STEP(0x143, 0xc)           // row_bcast:31 into rows 2, 3
+#undef WS1_STEP
+    return __builtin_amdgcn_readlane(v, 63);
 }
 // Wave sums of two ints by DPP, with no LDS round trip (wave_sum's __shfl_xor is a ds_bpermute each): quad_perm swaps, the two
 // row mirrors give every lane its row's sum, row_bcast:15 / :31 carry rows 0-2 into lane 63, which is read.  The two chains

@@ -38,6 +38,8 @@ __device__ __forceinline__ OctNodes oct_carve(char* base, int cap)
     return n;
 }
 
+template <int V> struct OctInt { static constexpr int value = V; };
+
 __device__ __forceinline__ int key_x(unsigned k) { return (int)(k & 0xFFFu); }
 __device__ __forceinline__ int key_y(unsigned k) { return (int)((k >> 12) & 0xFFFu); }
 
@@ -53,7 +55,7 @@ __device__ __forceinline__ int oct_nonempty(const int* cc, int p)
     return (cc[4 * p] > 0) + (cc[4 * p + 1] > 0) + (cc[4 * p + 2] > 0) + (cc[4 * p + 3] > 0);
 }
 
-// Diagnostic build only (-DOCT_STAMPS, tools/r03_oct_stamps.sh): the level-0 workgroup of frame 0 leaves the shader clock at its phase
+// Diagnostic build only (-DOCT_STAMPS, tools/oct_stamps.py): the level-0 workgroup of frame 0 leaves the shader clock at its phase
 // boundaries; the shipped kernel contains none of this.
 #ifdef OCT_STAMPS
 __device__ unsigned long long oct_stamps[64];
@@ -71,6 +73,9 @@ extern "C" int ccm_debug_oct_stamps(unsigned long long* out, int* n)
 #endif
 #ifndef OCT_LDS_KEYS
 #define OCT_LDS_KEYS 2048       // candidates of a (frame, level) up to which the key-parallel form below is used (its keys and their node ids live in LDS)
+#endif
+#ifndef OCT_GATHER_CELLS
+#define OCT_GATHER_CELLS 512    // cells of a level up to which the gather takes its one-trip form (752x480: 336 at level 0, 1241x376: 440)
 #endif
 #ifndef OCT_WAVES
 #define OCT_WAVES 4             // measured: 1 -> 0.22 ms, 2 -> 0.41, 4 -> 0.135, 8 -> 0.23 ms per 256 frames
@@ -103,7 +108,7 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
     int* cbase = ord + cap;           // creation index of the first child of the k-th divided node
     int* mark = cbase + cap;          // 0 = survivor, k+1 = divided as the k-th
     int* gain = mark + cap;           // careful mode: list growth per candidate, in rank order
-    int* shared_len = gain + cap;     // one uniform word
+    int* shared_len = gain + cap;     // (16 bytes kept between the lists and the keys: lkeys stays 16-byte aligned)
 
     unsigned* kb[2] = { keysA + (long long)f * g.keys_per_frame + L.key_first,
                         keysB + (long long)f * g.keys_per_frame + L.key_first };
@@ -122,11 +127,60 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
     const int N = L.quota;
     int* ocount = out_count + (long long)f * g.nlevels + level;
 
-    // ---- gather this level's candidates in cell-major order into kb[0]: 64 cells per wave and round
+    // ---- gather this level's candidates in cell-major order (= ccm_orb_debug_candidates' order: "first key wins ties" rests on it)
     const int* ccount = cell_count + (long long)f * g.ncells + L.cell_first;
     const unsigned* fslots = slots + (long long)f * g.slots_per_frame;
+    const int tid = threadIdx.x;
+    const int R = L.roots;
+    constexpr int OCT_KPT = OCT_LDS_KEYS / (64 * OCT_WAVES);
+    unsigned mykey[OCT_KPT]; int mynode[OCT_KPT];
+#pragma unroll
+    for (int j = 0; j < OCT_KPT; j++) { mykey[j] = 0u; mynode[j] = 0; }
+    if (tid < ORB_MAX_ROOTS) cc[tid] = 0;                    // the roots' sizes, counted below (the gather's barrier comes first)
+    // ONE-TRIP FORM (all keys of the level in one global round trip; two dependent trips in all: the cells' counts, then the keys).  Every wave loads the counts of ALL cells of
+    // the level at once (OCT_GCH chunks of 64: no round waits behind another's key stores) and scans them on DPP, so every wave knows
+    // every cell's first key and the total with no barrier; a wave leaves the offsets of its own chunks (u % OCT_WAVES == wave) in
+    // LDS that is idle until the roots are made -- the two node sets: goffs[cell] = first key, gdelta[cell] = slot_first - first key.
+    // Then key k = tid + 256 j (mykey[]'s own mapping: straight to registers and lkeys, all of a thread's loads in flight together)
+    // finds its cell by a binary search over goffs -- the last cell whose first key is <= k; an empty cell shares its offset with the
+    // next one and is never the last -- and its root is counted the moment it arrives.  Taken where the level has at most
+    // OCT_GATHER_CELLS cells (and the sets hold them) and at most OCT_LDS_KEYS candidates; any other level, and the test switch
+    // reg_keys_on == 0, take the loop below (until this form: every level, 29,500 of the level-0 workgroup's 112,300 cycles).
+    constexpr int OCT_GCH = OCT_GATHER_CELLS / 64, OCT_GPW = OCT_GCH / OCT_WAVES;
+    static_assert(OCT_GCH % OCT_WAVES == 0 && OCT_GPW >= 1, "every wave leaves the offsets of OCT_GPW chunks");
+    int* goffs = reinterpret_cast<int*>(smem);               // [5 * cap]
+    int* gdelta = goffs + 5 * cap;                           // [5 * cap]
     int total = 0;
-    for (int base = 0; base < L.ncells; base += 64 * OCT_WAVES) {
+    bool gathered = false;
+    if (reg_keys_on && L.ncells <= min(OCT_GATHER_CELLS, 5 * cap)) {
+        int cnt[OCT_GCH], sf[OCT_GPW], myoff[OCT_GPW];
+#pragma unroll
+        for (int u = 0; u < OCT_GCH; u++) {
+            const int ci = 64 * u + lane;
+            cnt[u] = ci < L.ncells ? ccount[ci] : 0;
+        }
+#pragma unroll
+        for (int v = 0; v < OCT_GPW; v++) {
+            const int ci = 64 * (wv + OCT_WAVES * v) + lane;
+            sf[v] = ci < L.ncells ? cells[L.cell_first + ci].slot_first : 0;
+            myoff[v] = 0;
+        }
+#pragma unroll
+        for (int u = 0; u < OCT_GCH; u++) {
+            const int incl = wave_incl_scan(cnt[u]);
+            if (u % OCT_WAVES == wv) myoff[u / OCT_WAVES] = total + incl - cnt[u];
+            total += wave_last(incl);
+        }
+        if (total <= OCT_LDS_KEYS) {
+#pragma unroll
+            for (int v = 0; v < OCT_GPW; v++) {
+                const int ci = 64 * (wv + OCT_WAVES * v) + lane;
+                if (ci < L.ncells) { goffs[ci] = myoff[v]; gdelta[ci] = sf[v] - myoff[v]; }
+            }
+            gathered = true;
+        } else total = 0;
+    }
+    for (int base = 0; base < L.ncells && !gathered; base += 64 * OCT_WAVES) {
         int cnt[OCT_WAVES];
 #pragma unroll
         for (int u = 0; u < OCT_WAVES; u++) {
@@ -140,9 +194,8 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
         for (int u = 0; u < OCT_WAVES; u++) {
             const int incl = wave_incl_scan(cnt[u]);
             if (u == wv) { mydst = total + incl - cnt[u]; mycnt = cnt[u]; }
-            total += __shfl(incl, 63, 64);
+            total += wave_last(incl);
         }
-        OCT_STAMP();                                         // (diagnostic: counts and slot offsets known)
         const unsigned* sp = fslots + sfirst;
         // (eight loads in flight per cell -- a cell of the bench frames holds up to ~20 candidates: with four per trip this loop was
         //  five dependent global round trips, twice: 30,000 of the kernel's 115,000 cycles, tools/r03_oct_stamps.sh; sixteen cost the
@@ -159,28 +212,18 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
                 }
         }
     }
-    OCT_STAMP();                                             // (diagnostic: this wave's keys stored)
+    OCT_STAMP();                                             // 1 the cells' key offsets known (the loop: its keys stored)
     if (total > L.key_cap) { if (lane == 0) atomicOr(status, 1); total = L.key_cap; }
     const int n = total;
     if (n == 0 || N <= 0) { if (threadIdx.x == 0) *ocount = 0; return; }
     const bool small = reg_keys_on && n <= OCT_LDS_KEYS;
     wave_sync_mem();
-    OCT_STAMP();                                             // 1 candidates gathered
+    OCT_STAMP();                                             // 2 offsets (the loop: keys) visible to the block
 
     // ---- the loops over keys.  Up to OCT_LDS_KEYS candidates: the thread's keys (k = tid + 256 j) and their nodes' list positions
     //      stay in REGISTERS through all passes (unrolled: the LDS reads of a thread's eight keys are independent and in flight
     //      together).  More: the keys are read from kb[0] and the node ids live in kb[1] (thread t only ever touches the ids of its
     //      own keys, so no barrier is needed for them).
-    const int tid = threadIdx.x;
-    const int R = L.roots;
-    constexpr int OCT_KPT = OCT_LDS_KEYS / (64 * OCT_WAVES);
-    unsigned mykey[OCT_KPT]; int mynode[OCT_KPT];
-#pragma unroll
-    for (int j = 0; j < OCT_KPT; j++) { mykey[j] = 0u; mynode[j] = 0; }
-    if (small) {
-#pragma unroll
-        for (int j = 0; j < OCT_KPT; j++) { const int k = tid + 64 * OCT_WAVES * j; if (k < n) mykey[j] = lkeys[k]; }
-    }
     // fn(key, node, k); mode 0: node read, 1: node read and written, 2: node written
     auto for_keys = [&](auto&& fn, int mode) {
         if (small) {
@@ -196,34 +239,67 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
         }
     };
     // ---- roots (:711-753): every key's root from its x, the roots' sizes by LDS atomics, empty roots dropped (list order = x order)
-    if (tid < ORB_MAX_ROOTS) cc[tid] = 0;
-    __syncthreads();
-    for_keys([&](unsigned key, int& node, int) {
+    auto count_root = [&](unsigned key, int& node, int) {
         int r = (int)((float)key_x(key) / L.hx); r = min(r, R - 1);
         node = r;
         atomicAdd(&cc[r], 1);
-    }, 2);
-    __syncthreads();
-    if (tid == 0) {
-        int p = 0;
-        for (int r = 0; r < R; r++) {
-            gain[r] = p;                                       // root r's list position (an empty root has no key that would ask)
-            if (cc[r] == 0) continue;
-            cur.x0[p] = (short)(int)(L.hx * (float)r);
-            cur.x1[p] = (short)(int)(L.hx * (float)(r + 1));
-            cur.y0[p] = 0; cur.y1[p] = (short)L.bh;
-            cur.count[p] = cc[r];
-            p++;
+    };
+    if (gathered) {
+        // the keys, one global trip.  The searches of a thread's keys run step by step side by side -- one basic block, no branch: NJ
+        // independent LDS reads in flight per step, nine dependent steps in all -- then all its loads are out together.
+        auto fetch = [&](auto nj) {
+            constexpr int NJ = decltype(nj)::value;
+            int pos[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; j++) pos[j] = 0;
+#pragma unroll
+            for (int step = OCT_GATHER_CELLS / 2; step >= 1; step >>= 1) {
+#pragma unroll
+                for (int j = 0; j < NJ; j++) {
+                    const int k = tid + 64 * OCT_WAVES * j, t = pos[j] + step;         // (k >= n: some cell, never used)
+                    const int first = goffs[min(t, L.ncells - 1)];
+                    pos[j] = (t < L.ncells && first <= k) ? t : pos[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; j++) pos[j] = gdelta[pos[j]];
+#pragma unroll
+            for (int j = 0; j < NJ; j++) { const int k = tid + 64 * OCT_WAVES * j; if (k < n) mykey[j] = fslots[k + pos[j]]; }
+            // (a key's root follows from its x the moment it is loaded: no pass of its own over the keys, no barrier of its own)
+#pragma unroll
+            for (int j = 0; j < NJ; j++) {
+                const int k = tid + 64 * OCT_WAVES * j;
+                if (k < n) { lkeys[k] = mykey[j]; count_root(mykey[j], mynode[j], k); }
+            }
+        };
+        if (n <= 64 * OCT_WAVES * (OCT_KPT / 2)) fetch(OctInt<OCT_KPT / 2>()); else fetch(OctInt<OCT_KPT>());
+    } else {
+        if (small) {
+#pragma unroll
+            for (int j = 0; j < OCT_KPT; j++) { const int k = tid + 64 * OCT_WAVES * j; if (k < n) mykey[j] = lkeys[k]; }
         }
-        *shared_len = p;
+        for_keys(count_root, 2);
     }
-    __syncthreads();
-    for_keys([&](unsigned, int& node, int) { node = gain[node]; }, 1);
+    wave_sync_mem();                                         // (the offsets are dead from here: the node sets are the node sets again)
+    OCT_STAMP();                                             // 3 keys in registers, roots counted
+    // every thread numbers the non-empty roots itself -- 4 bits per root: its list position -- and root r writes its own node
+    unsigned rpos = 0u;
+    int len = 0;
+#pragma unroll
+    for (int r = 0; r < ORB_MAX_ROOTS; r++)
+        if (r < R) { rpos |= (unsigned)len << (4 * r); len += cc[r] > 0; }
+    if (tid < R && cc[tid] > 0) {
+        const int p = (int)((rpos >> (4 * tid)) & 15u);
+        cur.x0[p] = (short)(int)(L.hx * (float)tid);
+        cur.x1[p] = (short)(int)(L.hx * (float)(tid + 1));
+        cur.y0[p] = 0; cur.y1[p] = (short)L.bh;
+        cur.count[p] = cc[tid];
+    }
+    for_keys([&](unsigned, int& node, int) { node = (int)((rpos >> (4 * node)) & 15u); }, 1);
     wave_sync_mem();
-    int len = *shared_len;
 
     // ---- refinement passes
-    OCT_STAMP();                                             // 2 roots made
+    OCT_STAMP();                                             // 4 roots made
     bool finish = false, careful = false;
     int guard = 0;
     const unsigned long long lt = lanemask_lt();
@@ -261,7 +337,46 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
             const int m_c = nc;
             // (eight LDS reads in flight: one per step was 145 cycles a step, 17,500 of the kernel's 115,000 cycles; the counts in
             //  registers read back with v_readlane measured slower still)
-            for (int base = 64 * wv; base < len; base += 64 * OCT_WAVES) {
+            // PACKED FORM: count << 16 | (0xFFFF - position) per node holding more than one key, 0 for the others, written once (by
+            // every wave, as the rest of the bookkeeping: no block barrier) into `best`, idle until the final selection.  Larger
+            // count first, smaller position first among equals = larger packed key first, so a node's rank is the number of packed
+            // keys above its own: a compare and an add with carry per entry, four entries per ds_read_b128 (before: five VALU
+            // instructions per entry, one ds_read_b32 each).  Positions < cap < 2^16 (the host's 150 KB check); counts <= n, so the
+            // form holds while n < 2^15 -- checked here, where n is known (the host's bound on a level's candidates, key_cap, is the
+            // cells' slots: 75,600 for level 0 of 752x480 frames that bring 1,250); a level above that takes the loop below.
+            const bool packed = n < (1 << 15);
+            if (packed) {
+                unsigned* pk = best;
+                const int len16 = (len + 15) & ~15;                                    // <= cap: a multiple of 16
+                for (int base = 0; base < len16; base += 64) {
+                    const int p = base + lane;
+                    if (p < len16) {
+                        const int c = p < len ? cur.count[p] : 0;
+                        pk[p] = c > 1 ? ((unsigned)c << 16) | (0xFFFFu - (unsigned)p) : 0u;
+                    }
+                }
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier();
+                const uint4* pk4 = reinterpret_cast<const uint4*>(pk);
+                for (int base = 64 * wv; base < len; base += 64 * OCT_WAVES) {
+                    const int p = base + lane;
+                    const unsigned mine = p < len ? pk[p] : 0u;
+                    if (mine != 0u) {
+                        int rank = 0;
+                        for (int q0 = 0; q0 < len16; q0 += 16) {
+                            uint4 a[4];
+#pragma unroll
+                            for (int u = 0; u < 4; u++) a[u] = pk4[(q0 >> 2) + u];
+#pragma unroll
+                            for (int u = 0; u < 4; u++)
+                                rank += (a[u].x > mine) + (a[u].y > mine) + (a[u].z > mine) + (a[u].w > mine);
+                        }
+                        ord[rank] = p;
+                        gain[rank] = oct_nonempty(cc, p) - 1;
+                    }
+                }
+            }
+            for (int base = 64 * wv; base < len && !packed; base += 64 * OCT_WAVES) {
                 const int p = base + lane;
                 const int myc = p < len ? cur.count[p] : 0;
                 if (myc > 1) {
@@ -290,7 +405,7 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
                 const int incl = wave_incl_scan(gn);
                 const unsigned long long hit = __ballot(k < m_c && run + incl >= N);
                 if (hit != 0ull) { K = base + __ffsll((long long)hit) - 1; found = true; }
-                run += __shfl(incl, 63, 64);
+                run += wave_last(incl);
             }
             nd = m_c > 0 ? K + 1 : 0;
         }
@@ -302,7 +417,7 @@ __global__ __launch_bounds__(64 * OCT_WAVES) OCT_OCC void k_octree(const OrbGeom
             const int ne = k < nd ? oct_nonempty(cc, ord[k]) : 0;
             const int incl = wave_incl_scan(ne);
             if (k < nd) cbase[k] = T + incl - ne;
-            T += __shfl(incl, 63, 64);
+            T += wave_last(incl);
         }
         // every wave writes all of mark, zeros first: after the barrier each word holds its final value
         for (int base = 0; base < len; base += 64) { const int p = base + lane; if (p < len) mark[p] = 0; }

@@ -12,7 +12,7 @@ for r in $(seq $rounds); do
     CCM_HOT_LIB=$PWD/$lib timeout -k 10 120 python3 bench.py --full --no-cpu --no-gba --no-extra --steps $steps 2> "$err" | grep '^{' | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); r = d['roofline']
-print('$lib round $r: step %.4f ms  value %.1f  %s %.4f ms' % (d['ms_per_step'], d['value'], r['kernel'], r['algorithmic_bytes_per_launch'] / r['achieved'] / 1e6))
+print('$lib round $r: step %.4f ms  value %.1f  %s %.4f ms  k_octree %.4f ms' % (d['ms_per_step'], d['value'], r['kernel'], r['algorithmic_bytes_per_launch'] / r['achieved'] / 1e6, d['kernels'].get('k_octree', {}).get('ms_per_step', 0)))
 " || { tail -5 "$err"; exit 1; }
   done
 done
