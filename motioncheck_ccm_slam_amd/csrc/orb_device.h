@@ -20,11 +20,13 @@ __device__ __forceinline__ unsigned long long lanemask_lt() { return (1ull << la
 // (frame, item) pairs instead -- whole frames -- so a line is fetched once and then found in that XCD's L2.  Speed only: the
 // result does not depend on where a workgroup runs.  on == 0 keeps the natural order, 1 = one contiguous range per XCD,
 // C > 1 = chunks of C consecutive items per XCD, dealt cyclically (CCM_ORB_XCD, for A/B timing).
-__device__ __forceinline__ void xcd_work_item(int on, int& x, int& y)
+// gx, gy: the grid's sizes.  A kernel that wants its first load early passes them as explicit arguments at the front of its argument
+// block (k_fast_cells): gridDim is a load from the hidden arguments, behind everything explicit.
+__device__ __forceinline__ void xcd_work_item(int on, unsigned gx, unsigned gy, int& x, int& y)
 {
     x = (int)blockIdx.x; y = (int)blockIdx.y;
     if (!on) return;
-    const unsigned gx = gridDim.x, total = gx * gridDim.y;
+    const unsigned total = gx * gy;
     const unsigned lin = blockIdx.y * gx + blockIdx.x;
     unsigned w;
     if (on == 1) {                                                         // each XCD one contiguous eighth of the items
@@ -45,6 +47,7 @@ __device__ __forceinline__ void xcd_work_item(int on, int& x, int& y)
     if (q * gx > w) q--; else if ((q + 1u) * gx <= w) q++;
     y = (int)q; x = (int)(w - q * gx);
 }
+__device__ __forceinline__ void xcd_work_item(int on, int& x, int& y) { xcd_work_item(on, gridDim.x, gridDim.y, x, y); }
 
 // Inclusive wave prefix sum by DPP, with no LDS round trip (__shfl_up is a ds_bpermute each, six of them in a chain): the row_shr
 // ladder 1, 2, 4, 8 scans every row of 16 lanes (a lane whose source lies outside its row adds 0), row_bcast:15 adds the total of

@@ -28,6 +28,17 @@
 // to the waves, not 18 dealt 5 / 5 / 4 / 4), by fc_item_* of orb_device.h, which the host runs too (ccm_debug_fc_items).  A run is 71
 // vector instructions (80 before: profiles/fc_reject_static.txt): run number and stack count in scalar registers, west / east pixels
 // by one v_perm_b32 each, the wave's last run drains its stack itself.  0.328 -> 0.3125 ms (profiles/fc_reject_ab.txt).
+// The head: ONE scalar wait in front of the pixel loads.  There were four, each dependent on the one before (the status-word pointer,
+// tested at the top; the work-order switch and the pointer block, 2.5 KB into the arguments behind OrbGeom by value; the OrbGeom fields
+// with half of the band record; the other half behind 130 instructions of exec-mask branching on wave 0), 4,600 of a band's
+// 24,500 cycles.  Now the arguments the head needs come first and the rest is 40 bytes (FcLate), the band record is fetched whole in
+// one batch with FcLate, a thread's first 16-byte chunk is requested, and the status clear, the counters' zeroing and the NMS's tables
+// (by the last wave, from vector loads of its own) run under that trip.  0.3125 -> 0.298 ms; with the kernel-argument preload
+// (csrc/Makefile) 0.297, apart from 0.298 in every round at 200 and at 400 steps (profiles/fe_prelude_ab.txt); wave 0's "band record
+// arrived -> pixel loads can be issued" 2,640 -> 772 cycles (profiles/fe_prelude_stamps.txt).  Whether the firmware preloads the stamps
+// do not show: "start -> band record arrived" is the record's own trip, 912 / 892 / 928 cycles (parent / without / with the flag).
+// Looked at on the assembly and dropped: the scalar-register pins of the band's cells behind the pixel loads too (the demand passes
+// the 80 scalar registers of eight waves per SIMD; the spills wait on their own loads in front of the pixel loads).
 #ifndef FC_NZ
 #define FC_NZ 1024
 #endif
@@ -54,7 +65,7 @@ __device__ __forceinline__ int fc_mbcnt(unsigned long long m, int base)
 {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, (unsigned)base));
 }
-// Diagnostic build only (-DFC_STAMPS, tools/r03_fc_stamps.sh): wave 0 (slots 0-7) and the last wave (slots 8-15) of every workgroup leave the shader clock at their phase
+// Diagnostic build only (-DFC_STAMPS, tools/fc_stamps.py): wave 0 (slots 0-7) and the last wave (slots 8-15) of every workgroup leave the shader clock at their phase
 // boundaries in a buffer no other code reads; the shipped kernel contains none of this.
 #ifdef FC_STAMPS
 #define FC_STAMP_SLOTS 16
@@ -74,16 +85,24 @@ typedef const __attribute__((address_space(1))) unsigned fc_gu32;
 typedef const __attribute__((address_space(3))) uint8_t fc_lbyte;      // a byte of LDS by its 32-bit address
 typedef unsigned fc_u32x4 __attribute__((ext_vector_type(4)));
 typedef fc_u32x4 fc_u32x4_a4 __attribute__((aligned(4)));
-// element ci (per lane) of four wave-uniform values: three selects, no memory
-template <class T>
-__device__ __forceinline__ int sel4(int ci, const T (&a)[4]) { return ci == 0 ? (int)a[0] : ci == 1 ? (int)a[1] : ci == 2 ? (int)a[2] : (int)a[3]; }
-__global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fast_cells(const OrbGeom g, const OrbCell* __restrict__ cells, const OrbBand* __restrict__ bands,
-                                                    unsigned* __restrict__ slots, int* __restrict__ cell_count, int* __restrict__ clear_status, int xcd_on)
+// Argument order: everything that stands in front of the pixel loads comes first -- the band table, the work-order switch and the grid
+// sizes it needs (explicit: gridDim is a load from the hidden arguments, behind everything else), the call's first frame and level 0's
+// image (the caller's: per call) -- 11 dwords, which arrive in scalar registers with the wave where the firmware preloads kernel
+// arguments (csrc/Makefile) and in one scalar load where it does not.  The band record's loads are then the kernel's first or second
+// batch, and the only wait in front of the pixel loads is theirs.  What is used behind them follows as FcLate: the few fields of
+// OrbGeom that the kernel reads (the geometry itself, 2.5 KB by value, stood FIRST until the head was cut: every pointer the head
+// needs 2.5 KB into the argument block, no preload possible), the outputs and the status word.
+struct FcLate {
+    int ini_th, min_th, ncells, slots_per_frame;      // of OrbGeom
+    const OrbCell* cells; unsigned* slots; int* cell_count;
+    int* clear_status;                                // the extractor's status word where this launch opens a call, else nullptr
+};
+__global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fast_cells(const OrbBand* __restrict__ bands, int xcd_on, unsigned grid_x, unsigned grid_y, int frame0,
+                                                    const uint8_t* __restrict__ img0, long long plane0, int pitch0, const FcLate g)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t fc_smem[];
-    if (clear_status && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) *clear_status = 0;      // as in k_pyr_resize: a one-level pyramid starts here
     int wx, wy;
-    xcd_work_item(xcd_on, wx, wy);
+    xcd_work_item(xcd_on, grid_x, grid_y, wx, wy);
     FC_STAMP(0);
     const OrbBand B = bands[wx];
 #ifdef FC_STAMPS
@@ -91,7 +110,11 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #endif
     FC_STAMP(6);
     // the band's cells, held in scalar registers from here on (left to itself the compiler loads them again where the NMS uses them:
-    // another scalar-load latency in each of its two passes, +1,400 cycles per band measured)
+    // another scalar-load latency in each of its two passes, +1,400 cycles per band measured).  The pins also make the compiler fetch
+    // the WHOLE record here, in one batch with one wait: it used to leave four of the eight loads behind the first wait, and a field
+    // that is not pinned (the reciprocals, before they were) gets a scalar load and a wait of its own on the staging path.  They cost
+    // a dozen scalar instructions in front of the pixel loads; moved behind them they raised the scalar-register demand past the 80
+    // that eight waves per SIMD allow, and the spills put waits of their own in front of the loads.
     int bclo[4], bcwd[4], bsfirst[4], bscap[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -100,13 +123,16 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     int bxa = B.xa, by0 = B.y0, bncells = B.ncells, bcfirst = B.cell_first;
     asm volatile("" : "+s"(bxa), "+s"(by0), "+s"(bncells), "+s"(bcfirst));
-    const int f = wy + g.frame0, tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    // i / PW and i / PQ by multiply-shift: exact for i < 2^20 / PW (i <= 65 * 64 here)
+    unsigned pw_inv = B.pw_inv, pq_inv = B.pq_inv;
+    asm volatile("" : "+s"(pw_inv), "+s"(pq_inv));
+    const int f = wy + frame0, tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
     // the level's image: from the band record, except level 0 (the caller's frames: pointer, pitch and plane are per call and sit at a
-    // fixed place of the kernel arguments -- no load that depends on the band record)
+    // fixed place at the front of the kernel arguments -- no load that depends on the band record)
     const bool lvl0 = B.level == 0;
-    const uint8_t* const Limg = lvl0 ? g.lv[0].img : B.img;
-    const long long Lplane = lvl0 ? g.lv[0].plane : B.plane;
-    const int Lpitch = lvl0 ? g.lv[0].pitch : B.lpitch, Lw = B.w, Lh = B.h;
+    const uint8_t* const Limg = lvl0 ? img0 : B.img;
+    const long long Lplane = lvl0 ? plane0 : B.plane;
+    const int Lpitch = lvl0 ? pitch0 : B.lpitch, Lw = B.w, Lh = B.h;
     const int P = B.pitch, bh = B.bh, PW = P >> 2;
     uint8_t* T = fc_smem;                                   // pixels  [bh][P]
     uint8_t* S = fc_smem + (size_t)P * bh;                  // scores  [bh][P]
@@ -123,16 +149,12 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     // (what the NMS needs of a cell -- its detection columns and its candidate slots -- comes with the band record: until round 3 the
     //  cell records were loaded from global memory, first on the NMS's critical path, then in front of the pixel loads)
     uint8_t* colcell = reinterpret_cast<uint8_t*>(colmask + 64);     // [256] cell of a tile column; 255 = no cell's detection column
-    if (tid < FC_CELLS) { cell_hi[tid] = 0; cell_n[tid] = 0; cell_k[tid] = 0; }
     // per cell, for the NMS (indexed per lane there: an LDS read measured 0.7 % faster than three selects on the scalar registers)
     int* l_clo = reinterpret_cast<int*>(colcell + 256); int* l_cwd = l_clo + 4; int* l_sfirst = l_cwd + 4; int* l_scap = l_sfirst + 4;
-    if (tid < 4) { l_clo[tid] = sel4(tid, bclo); l_cwd[tid] = sel4(tid, bcwd); l_sfirst[tid] = sel4(tid, bsfirst); l_scap[tid] = sel4(tid, bscap); }
-    if (tid == 0) { nsurv[1] = 0; nsurv[2] = 0; }
+    // (the counters and these tables are written behind the pixel loads, by the last wave: see there)
     const uint8_t* img = Limg + (long long)f * Lplane;
     // ---- stage pixels (clamped: duplicates are only read for pixels whose score is not needed), zero the scores
     const bool dword_ok = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)Lpitch) & 3) == 0 && Lpitch >= ((Lw + 3) & ~3);
-    // i / PW by multiply-shift: exact for i < 2^20 / PW (i <= 65 * 64 here)
-    const unsigned pw_inv = B.pw_inv;
 #ifdef FC_STAMPS
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (diagnostic: level record and everything scalar before the pixel loads has arrived)
 #endif
@@ -140,13 +162,30 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     // the image is read through global-address-space pointers: `img` is a select between a kernel argument and a field of the band
     // record, and left generic its loads become flat_load_dword, four per 16-byte chunk
     fc_gbyte* const gimg = (fc_gbyte*)img;
+    // ---- What the pixel addresses do not need runs under the pixel loads' trip: under_trip() stands between a thread's first load and
+    // the store of what it returns on the 16-byte path, behind the loop on the two others.
+    const OrbBand* const brec = bands + wx;
+    auto under_trip = [&]() {
+        // The status word: zeroed by the first thread of the launch that opens a call (a one-level pyramid starts here; nullptr
+        // otherwise).  This kernel never ORs into the word, and stream order still puts the store before every kernel that does.
+        if (g.clear_status && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) *g.clear_status = 0;
+        // The NMS counters and its per-cell tables, by the LAST wave (one staging trip on the dominant band where wave 0 has two): lane
+        // FC_TPB - 1 - k writes entry k, and takes its table entries from the band record by vector loads of its own.  (Until the head
+        // was cut, three blocks `if (tid < ..)` on wave 0 IN FRONT of its pixel loads, the table entries picked from the scalar
+        // registers by three selects each: about 100 instructions of exec-mask branching on the path to the loads.)
+        const int k = FC_TPB - 1 - tid;
+        if (k < FC_CELLS) {
+            cell_hi[k] = 0; cell_n[k] = 0; cell_k[k] = 0;
+            if (k < 2) nsurv[1 + k] = 0;
+            if (k < ORB_BAND_CELLS) { l_clo[k] = brec->clo[k]; l_cwd[k] = brec->cwd[k]; l_sfirst[k] = brec->slot_first[k]; l_scap[k] = brec->slot_cap[k]; }
+        }
+    };
     if (dword_ok && (P & 15) == 0) {
         // 16 bytes per lane: one global_load_dwordx4 and two ds_write_b128 (pixels, zeroed scores) per 16 pixels; the last
         // chunks of a row are clamped dword by dword (four global_load_dword)
         const int wmax = ((Lw - 1) & ~3);
-        const int PQ = P >> 4;
-        const unsigned pq_inv = B.pq_inv;                          // i / PQ exact for i < 2^20 / PQ
-        for (int i = tid; i < bh * PQ; i += FC_TPB) {
+        const int PQ = P >> 4, nq = bh * PQ;
+        auto chunk = [&](int i) {
             const int ly = (int)(((unsigned)i * pq_inv) >> 20), lq = i - ly * PQ;
             const int gy = min(B.y0 + ly, Lh - 1), gx = B.xa + 16 * lq;
             fc_gbyte* rowp = gimg + (long long)gy * Lpitch;
@@ -158,6 +197,19 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                 v.z = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 8, wmax));
                 v.w = *reinterpret_cast<fc_gu32*>(rowp + min(gx + 12, wmax));
             }
+            return v;
+        };
+        // the thread's first chunk is requested, the set-up runs, and only then is the chunk waited for and stored
+        fc_u32x4 v0 = { 0u, 0u, 0u, 0u };
+        if (tid < nq) v0 = chunk(tid);
+        asm volatile("" ::: "memory");                             // (the request stays in front of the set-up's stores)
+        under_trip();
+        if (tid < nq) {
+            reinterpret_cast<fc_u32x4*>(T)[tid] = v0;
+            reinterpret_cast<uint4*>(S)[tid] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        for (int i = tid + FC_TPB; i < nq; i += FC_TPB) {
+            const fc_u32x4 v = chunk(i);
             reinterpret_cast<fc_u32x4*>(T)[i] = v;
             reinterpret_cast<uint4*>(S)[i] = make_uint4(0u, 0u, 0u, 0u);
         }
@@ -169,6 +221,7 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             reinterpret_cast<unsigned*>(T)[i] = *reinterpret_cast<fc_gu32*>(gimg + (long long)gy * Lpitch + gx);
             reinterpret_cast<unsigned*>(S)[i] = 0u;
         }
+        under_trip();
     } else {
         for (int i = tid; i < bh * P; i += FC_TPB) {
             const int ly = i / P, lx = i - ly * P;
@@ -176,6 +229,7 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             T[i] = gimg[(long long)gy * Lpitch + gx];
             S[i] = 0;
         }
+        under_trip();
     }
 #ifdef FC_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (diagnostic: this wave's pixels have arrived)
@@ -372,7 +426,7 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             if (tid >= FC_TPB - FC_CELLS && FC_TPB - 1 - tid < bncells) {
                 const int ci = FC_TPB - 1 - tid;
                 const int hi = cell_hi[ci];
-                cell_count[(long long)f * g.ncells + bcfirst + ci] = hi > 0 ? hi : cell_k[ci];
+                g.cell_count[(long long)f * g.ncells + bcfirst + ci] = hi > 0 ? hi : cell_k[ci];
             }
             for (int e = tid; e < nk; e += FC_TPB) {
                 const int ci = (e >= e1 ? 1 : 0) + (e >= e2 ? 1 : 0) + (e >= e3 ? 1 : 0);
@@ -388,7 +442,7 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                     rank += ((o & 255u) >= th && (o >> 8) < (me >> 8)) ? 1 : 0;
                 }
                 if (rank < l_scap[ci])
-                    slots[(long long)f * g.slots_per_frame + l_sfirst[ci] + rank] =
+                    g.slots[(long long)f * g.slots_per_frame + l_sfirst[ci] + rank] =
                         ((me & 255u) << 24) | ((unsigned)(by0 + 3 - ORB_BORDER + (int)((me >> 14) & 63u)) << 12) |
                         (unsigned)(bxa + l_clo[ci] - ORB_BORDER + (int)((me >> 8) & 63u));
             }
@@ -398,12 +452,12 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     }
     // ---- per cell: threshold choice, strict 3x3 NMS inside the cell's detection rectangle, ordered compaction
     for (int ci = wv; ci < B.ncells; ci += FC_TPB / 64) {
-        const OrbCell c = cells[B.cell_first + ci];
+        const OrbCell c = g.cells[B.cell_first + ci];
         const int rw = c.cw - 6, rh = c.ch - 6;
-        int* count_out = cell_count + (long long)f * g.ncells + B.cell_first + ci;
+        int* count_out = g.cell_count + (long long)f * g.ncells + B.cell_first + ci;
         if (rw <= 0 || rh <= 0) { if (lane == 0) *count_out = 0; continue; }
         const uint8_t* S0 = S + 3 * P + (c.x0 + 3 - B.xa);                    // score of the rectangle's first pixel
-        unsigned* out = slots + (long long)f * g.slots_per_frame + c.slot_first;
+        unsigned* out = g.slots + (long long)f * g.slots_per_frame + c.slot_first;
         const int relx = c.x0 + 3 - ORB_BORDER, rely = c.y0 + 3 - ORB_BORDER;
         const int rpi = rw <= 32 ? 2 : 1;
         const int xx = rpi == 2 ? (lane & 31) : lane, yoff = rpi == 2 ? (lane >> 5) : 0;
@@ -446,6 +500,8 @@ void orb_launch_fast_cells(hipStream_t s, const OrbGeom& g_dev, const OrbCell* c
     // algorithmic bytes) but the kernel, which is not bandwidth-bound, runs 3-5 % slower with every co-locating order tried
     // (profiles/r02_xcd_order.txt); k_orient_desc gains from it and uses it
     static const int xcd_on = getenv("CCM_ORB_XCD") ? atoi(getenv("CCM_ORB_XCD")) : 0;
-    hipLaunchKernelGGL(k_fast_cells, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, g_dev, cells, bands, slots, cell_count, clear_status, xcd_on);
+    const FcLate late = { g_dev.ini_th, g_dev.min_th, g_dev.ncells, g_dev.slots_per_frame, cells, slots, cell_count, clear_status };
+    hipLaunchKernelGGL(k_fast_cells, dim3(nbands, nframes), dim3(FC_TPB), lds_bytes, s, bands, xcd_on, (unsigned)nbands, (unsigned)nframes, g_dev.frame0,
+                       g_dev.lv[0].img, g_dev.lv[0].plane, g_dev.lv[0].pitch, late);
 }
 size_t orb_fast_cells_lds(int pitch, int bh) { return fc_lds_bytes(pitch, bh); }

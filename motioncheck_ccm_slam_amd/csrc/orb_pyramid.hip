@@ -14,6 +14,12 @@
 // requested ahead), keeps its horizontal pass for the two output rows that need it (3.6 instead of 6 loaded dwords per output row) --
 // bit-exact, and slower: 0.270 against 0.173 ms for the seven levels.  Its serial row loop needs selects, moves and address arithmetic
 // that the fully unrolled kernel below does not (18 against 14 vector instructions per pixel), and a quarter of the waves.  Not kept.
+// Built, measured and dropped (profiles/fe_prelude_ab.txt): the head on a flat argument block -- what the kernel uses of the two level
+// records as 16 scalars and pointers instead of OrbGeom by value and a level index (g.lv[level] is a scalar load whose address depends
+// on another: four dependent scalar waits stand in front of the y-table loads), the first 14 dwords preloaded, the x tables requested
+// with the y tables instead of behind the v_readlane broadcasts, the status clear last.  Bit-exact, but 65 VGPRs where this kernel has
+// 64 (seven waves per SIMD; held to eight it spills), and 0.1723-0.1739 against 0.1704-0.1730 ms, step 0.7800-0.7844 against
+// 0.7775-0.7801 ms.  The head of this kernel has not been stamped.
 #ifndef RS_ROWS
 #define RS_ROWS 8                // rows per thread (measured: 4 -> 0.186, 8 -> 0.172, 16 -> 0.260 ms)
 #endif
