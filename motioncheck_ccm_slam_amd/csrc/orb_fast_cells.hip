@@ -39,6 +39,19 @@
 // do not show: "start -> band record arrived" is the record's own trip, 912 / 892 / 928 cycles (parent / without / with the flag).
 // Looked at on the assembly and dropped: the scalar-register pins of the band's cells behind the pixel loads too (the demand passes
 // the 80 scalar registers of eight waves per SIMD; the spills wait on their own loads in front of the pixel loads).
+// The NMS's first pass: THREE LDS trips per iteration, not five (profiles/fc_nms_static.txt).  The count of scored pixels and the thread's
+// first list entry are one batch (pinned: the compiler moves the entry's read behind the test of the count); the colcell byte carries
+// "left / right neighbour inside the cell's rectangle", so the cell's first column and width are not read; a `kept` entry packs the
+// tile column, so the second pass does not read the first column either and takes a cell's slots in one 8-byte read; row = pos / pitch
+// by the band record's reciprocal and the bucket capacity by selects -- two integer divisions stood between the list's read and the
+// neighbours'.  0.2965-0.2973 -> 0.2948-0.2960 ms, apart in the kernel's own time, not in the step (profiles/fc_nms_ab.txt).
+// Measured and dropped there: the second pass with A WAVE PER CELL (cell_k, cell_hi and the wave's bucket, one entry per lane, in one batch
+// of reads; the slots from the scalar pins; the rank of a bucket of up to 64 from v_readlane, no LDS access in the loop).  Its tail is
+// shorter on the stamps (wave 0's "local maxima -> written" 2,372 -> 1,908 cycles) and the kernel is SLOWER: 0.3176-0.3182 ms with a
+// rank loop of 11 instructions per entry, 0.3086-0.3093 with 5, 0.3067-0.3076 with the slots from the LDS table (the eight pins live
+// across the kernel cost 5 scalar registers more).  Every phase of the band got longer, the untouched rejection + scoring too (9,664 ->
+// 10,276 cycles): four waves now run the tail's address arithmetic and a rank loop over their own cell where one wave ranked all cells
+// lane-parallel in max(bucket) rounds and three waves left; those instructions are issued beside the seven other bands of the CU.
 #ifndef FC_NZ
 #define FC_NZ 1024
 #endif
@@ -148,10 +161,15 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     uint2* colmask = reinterpret_cast<uint2*>(cell_k + FC_CELLS + FC_CELLS);     // per tile dword: 16-bit lane masks of its detection columns: .x pixels 0 and 2, .y pixels 1 and 3
     // (what the NMS needs of a cell -- its detection columns and its candidate slots -- comes with the band record: until round 3 the
     //  cell records were loaded from global memory, first on the NMS's critical path, then in front of the pixel loads)
-    uint8_t* colcell = reinterpret_cast<uint8_t*>(colmask + 64);     // [256] cell of a tile column; 255 = no cell's detection column
-    // per cell, for the NMS (indexed per lane there: an LDS read measured 0.7 % faster than three selects on the scalar registers)
-    int* l_clo = reinterpret_cast<int*>(colcell + 256); int* l_cwd = l_clo + 4; int* l_sfirst = l_cwd + 4; int* l_scap = l_sfirst + 4;
-    // (the counters and these tables are written behind the pixel loads, by the last wave: see there)
+    // [256] per tile column: its cell (bits 0-1), "has a left neighbour inside the cell's rectangle" (bit 2), "has a right one" (bit 3);
+    // 255 = no cell's detection column (a cell's byte is <= 15)
+    uint8_t* colcell = reinterpret_cast<uint8_t*>(colmask + 64);
+    // per cell, for the NMS's second pass: first candidate slot and number of slots, one 8-byte read (indexed per lane there: an LDS read
+    // measured 0.7 % faster than three selects on the scalar registers).  The cell's first column and width stood here too until the
+    // colcell byte took the edge flags and a `kept` entry the tile column.
+    int2* l_slot = reinterpret_cast<int2*>(colcell + 256);
+    // (the counters and this table are written behind the pixel loads, by the last wave: see there)
+    const OrbBand* const brec = bands + wx;
     const uint8_t* img = Limg + (long long)f * Lplane;
     // ---- stage pixels (clamped: duplicates are only read for pixels whose score is not needed), zero the scores
     const bool dword_ok = ((reinterpret_cast<uintptr_t>(img) | (uintptr_t)Lpitch) & 3) == 0 && Lpitch >= ((Lw + 3) & ~3);
@@ -164,20 +182,19 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     fc_gbyte* const gimg = (fc_gbyte*)img;
     // ---- What the pixel addresses do not need runs under the pixel loads' trip: under_trip() stands between a thread's first load and
     // the store of what it returns on the 16-byte path, behind the loop on the two others.
-    const OrbBand* const brec = bands + wx;
     auto under_trip = [&]() {
         // The status word: zeroed by the first thread of the launch that opens a call (a one-level pyramid starts here; nullptr
         // otherwise).  This kernel never ORs into the word, and stream order still puts the store before every kernel that does.
         if (g.clear_status && (blockIdx.x | blockIdx.y | threadIdx.x) == 0) *g.clear_status = 0;
-        // The NMS counters and its per-cell tables, by the LAST wave (one staging trip on the dominant band where wave 0 has two): lane
-        // FC_TPB - 1 - k writes entry k, and takes its table entries from the band record by vector loads of its own.  (Until the head
+        // The NMS counters and its per-cell slot table, by the LAST wave (one staging trip on the dominant band where wave 0 has two): lane
+        // FC_TPB - 1 - k writes entry k, and takes its table entry from the band record by vector loads of its own.  (Until the head
         // was cut, three blocks `if (tid < ..)` on wave 0 IN FRONT of its pixel loads, the table entries picked from the scalar
         // registers by three selects each: about 100 instructions of exec-mask branching on the path to the loads.)
         const int k = FC_TPB - 1 - tid;
         if (k < FC_CELLS) {
             cell_hi[k] = 0; cell_n[k] = 0; cell_k[k] = 0;
             if (k < 2) nsurv[1 + k] = 0;
-            if (k < ORB_BAND_CELLS) { l_clo[k] = brec->clo[k]; l_cwd[k] = brec->cwd[k]; l_sfirst[k] = brec->slot_first[k]; l_scap[k] = brec->slot_cap[k]; }
+            if (k < ORB_BAND_CELLS) l_slot[k] = make_int2(brec->slot_first[k], brec->slot_cap[k]);
         }
     };
     if (dword_ok && (P & 15) == 0) {
@@ -248,10 +265,14 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     __syncthreads();
     FC_STAMP(1);
     if (tid < P) {                                           // (read after the next barrier)
-        int ci = 255;
+        int ci = 255, lo = 0, hi = 0;
 #pragma unroll
-        for (int i = 0; i < ORB_BAND_CELLS; i++) if (i < bncells && tid >= bclo[i] && tid < bclo[i] + bcwd[i]) ci = i;
-        colcell[tid] = (uint8_t)ci;
+        for (int i = 0; i < ORB_BAND_CELLS; i++) {
+            const bool in = i < bncells && tid >= bclo[i] && tid < bclo[i] + bcwd[i];
+            ci = in ? i : ci; lo = in ? bclo[i] : lo; hi = in ? bclo[i] + bcwd[i] : hi;
+        }
+        // xx = tid - lo: a left neighbour where xx > 0, a right one where xx + 1 < cwd (both 0 outside the cells: 255 stays 255)
+        colcell[tid] = (uint8_t)(ci | (tid > lo && tid < hi ? 4 : 0) | (tid + 1 < hi ? 8 : 0));
     }
     const int wvs = __builtin_amdgcn_readfirstlane(wv);        // the wave's number in a scalar register: its stack's address and its runs are scalar
     unsigned short* wsurv = surv + wvs * WCAP;
@@ -379,28 +400,38 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     FC_STAMP(2);
     // ---- NMS on the list of scored pixels.  With minThFAST <= iniThFAST every stored score is >= minThFAST, so
     // "keep at threshold th" == score >= th and strictly greater than every neighbour inside the cell's rectangle.
+    // The count of scored pixels and the thread's first list entry are requested together: nz[tid] is inside the list for every thread
+    // and is used only where tid < nnz.
+    static_assert(FC_TPB <= FC_NZ, "nz[tid] is read before nnz is known");
     const int nnz = nsurv[1];
+    int nz0 = nz[tid];
+    asm volatile("" : "+v"(nz0));                            // (left to itself the compiler moves the read behind the test of nnz: a trip of its own)
     const int rh = bh - 6;
     bool listed = g.min_th <= g.ini_th && nnz <= FC_NZ && bncells <= ORB_BAND_CELLS;
     if (listed) {
         // the local maxima go to one bucket of `kept` per cell, so that the row-major rank of a keypoint inside its
         // cell only scans the maxima of that cell (a fifth of the band's on the EuRoC-shaped frames)
-        const int cap_c = ((FC_KEPT / max(bncells, 1)) - 1) | 1;      // odd: the buckets start in different LDS banks
-        const unsigned p_inv = 0xFFFFFFFFu / (unsigned)P + 1u;           // pos / P == mulhi(pos, p_inv) for pos < 2^16 and every pitch 16..256 (checked exhaustively)
+        // ((FC_KEPT / bncells) - 1) | 1, odd: the buckets start in different LDS banks.  By selects on the scalar cell count (1..4 here): the
+        // division, and the reciprocal of the pitch that used to follow it, stood between the list's first read and the neighbours' reads
+        static_assert(ORB_BAND_CELLS == 4, "cap_c by cell count");
+#define FC_CAP(n) (((FC_KEPT / (n)) - 1) | 1)
+        const int cap_c = bncells <= 1 ? FC_CAP(1) : bncells == 2 ? FC_CAP(2) : bncells == 3 ? FC_CAP(3) : FC_CAP(4);
+#undef FC_CAP
         for (int e = tid; e < nnz; e += FC_TPB) {
-            const int pos = nz[e];
-            const int row = (int)__umulhi((unsigned)pos, p_inv), col = pos - row * P;
+            const int pos = e == tid ? nz0 : nz[e];
+            // pos / P == (pos / 4) / PW by the band record's multiply-shift: pos / 4 < bh * PW, the staging loop's own range
+            const int row = (int)(((unsigned)(pos >> 2) * pw_inv) >> 20), col = pos - row * P;
             // the score, its eight neighbours and the column's cell are read together (one LDS round trip; the tile has a 3-pixel
             // margin around every detection pixel) and the neighbours outside the cell's rectangle masked afterwards: no
             // short-circuit chain of dependent LDS reads
             const uint8_t* p = S + pos;
-            const int ci = colcell[col];
+            const int cc = colcell[col];
             const int sc = p[0];
             const int nl = p[-1], nr = p[1], nul = p[-P - 1], nu = p[-P], nur = p[-P + 1], ndl = p[P - 1], nd = p[P], ndr = p[P + 1];
             __builtin_amdgcn_sched_barrier(0);
-            if (ci == 255) continue;
-            const int xx = col - l_clo[ci], yy = row - 3, rw = l_cwd[ci];
-            const bool l = xx > 0, r = xx + 1 < rw, u = yy > 0, d = yy + 1 < rh;
+            if (cc == 255) continue;
+            const int ci = cc & 3, yy = row - 3;
+            const bool l = (cc & 4) != 0, r = (cc & 8) != 0, u = yy > 0, d = yy + 1 < rh;
 #define NB(c, v) ((c) ? (v) : 0)
             const bool keep = (sc > NB(l, nl)) & (sc > NB(r, nr)) &
                               (sc > NB(u && l, nul)) & (sc > NB(u, nu)) & (sc > NB(u && r, nur)) &
@@ -408,7 +439,10 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #undef NB
             if (keep) {
                 const int q = atomicAdd(cell_k + ci, 1);
-                if (q < cap_c) kept[ci * cap_c + q] = ((unsigned)yy << 14) | ((unsigned)xx << 8) | (unsigned)sc;
+                // yy << 16 | tile column << 8 | score: col < 256 (the colcell table holds every column of the tile), yy <= 58 (the
+                // largest band the reciprocals allow has 65 rows), score <= 255.  The row-major order inside a cell is that of
+                // (yy, xx): col = clo + xx with one clo per cell.
+                if (q < cap_c) kept[ci * cap_c + q] = ((unsigned)yy << 16) | ((unsigned)col << 8) | (unsigned)sc;
                 if (sc >= g.ini_th) atomicAdd(cell_hi + ci, 1);
             }
         }
@@ -441,10 +475,11 @@ __global__ __launch_bounds__(FC_TPB) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                     const unsigned o = bucket[k];
                     rank += ((o & 255u) >= th && (o >> 8) < (me >> 8)) ? 1 : 0;
                 }
-                if (rank < l_scap[ci])
-                    g.slots[(long long)f * g.slots_per_frame + l_sfirst[ci] + rank] =
-                        ((me & 255u) << 24) | ((unsigned)(by0 + 3 - ORB_BORDER + (int)((me >> 14) & 63u)) << 12) |
-                        (unsigned)(bxa + l_clo[ci] - ORB_BORDER + (int)((me >> 8) & 63u));
+                const int2 sl = l_slot[ci];                                               // (first slot, slots: one read, one trip)
+                if (rank < sl.y)
+                    g.slots[(long long)f * g.slots_per_frame + sl.x + rank] =
+                        ((me & 255u) << 24) | ((unsigned)(by0 + 3 - ORB_BORDER + (int)((me >> 16) & 63u)) << 12) |
+                        (unsigned)(bxa - ORB_BORDER + (int)((me >> 8) & 255u));
             }
             FC_STAMP(4);
             return;

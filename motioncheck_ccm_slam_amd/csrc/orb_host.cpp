@@ -74,8 +74,8 @@ void linear_tables(int ssize, int dsize, std::vector<int>& ofs, std::vector<shor
     }
 }
 
-// A chunk of the device path's two-lane schedule (orb_extract_lanes below): frames [frame0, frame0 + nrun) on lane 0 (the context's
-// stream) or lane 1 (the auxiliary stream).
+// A chunk of the device path's two-lane schedule (orb_extract_lanes below): frames [frame0, frame0 + nrun) on lane 0 or lane 1 of the
+// plan.  Which of the two streams carries a lane is orb_extract_lanes' decision: the lane of the plan's last chunk runs on the context's.
 struct OrbChunk { int frame0, nrun, lane; };
 
 // The chunks of a batch of n_images frames.  Pure: no HIP call, no state (ccm_orb_debug_lane_plan exports it to a CPU test).
@@ -334,9 +334,10 @@ static int orb_prepare(ccm_ctx* c, const ccm_orb_params* p, int w, int h, int nf
 // Enqueues the pipeline on frames [frame0, frame0 + nrun) of the prepared batch (all of it by default) on stream st (the context's
 // by default).  The launches of a chunk depend on each other only through stream order; everything they read or write is indexed by
 // absolute frame (see orb_extract_lanes), so chunks of different frames may run on different streams at the same time.
-// first_done, if given, is recorded behind the chunk's first kernel -- the one that clears the status word.
+// first_done, if given, is recorded behind the chunk's first kernel -- the one that clears the status word.  rest, if given with it
+// and different from st, takes every launch behind that kernel: it waits for first_done and the chunk goes on there.
 static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_stride, int frame0 = 0, int nrun = -1,
-                   hipStream_t st = nullptr, hipEvent_t first_done = nullptr)
+                   hipStream_t st = nullptr, hipEvent_t first_done = nullptr, hipStream_t rest = nullptr)
 {
     OrbState& S = *c->orb;
     OrbGeom& G = S.geom;
@@ -345,6 +346,7 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
     G.frame0 = frame0;
     if (nrun < 0) nrun = S.nframes - frame0;
     if (!st) st = c->stream;
+    if (!rest || !first_done) rest = st;
     const OrbGeom& gd = G;
     const OrbCell* cd = S.cells_dev.as<OrbCell>();
     // The status word is cleared by the call's first chunk only (the later chunks of a call accumulate into it), and by
@@ -354,12 +356,18 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
         ProfScope ps(c, CCM_PROF_RESIZE);
         orb_launch_resize(st, gd, l, G.lv[l].w, G.lv[l].h, nrun, clear);
         clear = nullptr;
-        if (l == 1 && first_done) CCM_HIP(c, hipEventRecord(first_done, st));
+        if (l == 1 && first_done) {
+            CCM_HIP(c, hipEventRecord(first_done, st));
+            if (rest != st) { CCM_HIP(c, hipStreamWaitEvent(rest, first_done, 0)); st = rest; }
+        }
     }
     if (S.fused && !S.bands.empty()) {
         ProfScope ps(c, CCM_PROF_FAST_SCORE);
         orb_launch_fast_cells(st, gd, cd, S.bands_dev.as<OrbBand>(), (int)S.bands.size(), nrun, S.band_lds, S.slots.as<unsigned>(), S.cell_count.as<int>(), clear);
-        if (G.nlevels == 1 && first_done) CCM_HIP(c, hipEventRecord(first_done, st));
+        if (G.nlevels == 1 && first_done) {
+            CCM_HIP(c, hipEventRecord(first_done, st));
+            if (rest != st) { CCM_HIP(c, hipStreamWaitEvent(rest, first_done, 0)); st = rest; }
+        }
     } else {
         if (clear) CCM_HIP(c, hipMemsetAsync(clear, 0, 4, st));          // (one level through the two-kernel FAST path: not worth a kernel argument)
         { ProfScope ps(c, CCM_PROF_FAST_SCORE); orb_launch_score(st, gd, G.ntiles, nrun); }
@@ -378,20 +386,26 @@ static int orb_run(ccm_ctx* c, const uint8_t* img_dev, int stride, size_t image_
     return CCM_OK;
 }
 
-// The device path's schedule (ccm_orb_extract_dev): the prepared batch in the chunks of orb_lane_plan, alternating between two lanes --
-// lane 0 is the context's stream, lane 1 its auxiliary stream aux[1] (shared, default priority; no stream is created for this: see
-// ccm_ctx::aux for what a fifth stream cost).  k_octree leaves the GPU nearly empty for its whole run (the barrier chain inside one
+// The device path's schedule (ccm_orb_extract_dev): the prepared batch in the chunks of orb_lane_plan, alternating between two streams --
+// the context's and its auxiliary stream aux[1] (shared, default priority; no stream is created for this: see ccm_ctx::aux for what a
+// fifth stream cost).  THE PLAN'S LAST CHUNK RUNS ON THE CONTEXT'S STREAM and the chunks before it alternate backwards (two chunks: the
+// context's stream carries chunk 0's first kernel, then all of chunk 1; the auxiliary stream the rest of chunk 0), so that the chunk
+// that ends last is the context's own and the join's wait is already satisfied when the stream reaches it: with chunk 0 on the
+// context's stream the trace showed 12 us of idle context stream in front of every matcher, waiting for the other stream's last
+// k_orient_desc (profiles/lanes_join_trace.txt).  k_octree leaves the GPU nearly empty for its whole run (the barrier chain inside one
 // (frame, level 0) workgroup, a few workgroups per CU) and cannot overlap anything of its own chunk, every kernel of which depends on
 // the one before; frames are independent, so one chunk's k_octree runs beside the other lane's k_fast_cells or k_orient_desc, and the
 // small pyramid levels, kernel tails and launch gaps of one lane beside the other lane's work.
-//   fork     lane 1's first wait is for an event recorded on the context's stream behind chunk 0's FIRST kernel: everything the
+//   fork     chunk 0's FIRST kernel runs on the context's stream whichever stream carries the rest of chunk 0, and the auxiliary
+//            stream's first wait is for an event recorded on the context's stream behind that kernel: everything the
 //            caller queued before the call (the previous step's matcher still reading S.desc, readers of a frame made by
 //            ccm_frame_from_extract, the previous call's own join) and the clearing of the status word, which that kernel does, precede
-//            every kernel of either lane -- later chunks only ever atomicOr into the status word
-//   offset   none but the fork's: lane 1 starts one resize launch behind lane 0 and shares the GPU with it from there on, which leaves
-//            the lanes 40-55 us apart at their k_octree.  Measured against it and dropped (profiles/orb_lanes_ab.txt):
+//            every kernel of either lane -- later chunks only ever atomicOr into the status word.  Where chunk 0 is the auxiliary
+//            stream's (an even number of chunks), orb_run moves to that stream behind the first kernel and enqueues the wait itself.
+//   offset   none but the fork's: the second chunk starts one resize launch behind the first and shares the GPU with it from there on,
+//            which leaves the lanes 40-55 us apart at their k_octree.  Measured against it and dropped (profiles/orb_lanes_ab.txt):
 //            chunk k + 1's k_fast_cells waiting for chunk k's, the fork behind a later resize, an uneven pair of chunks, 3, 4 and 8 chunks.
-//   join     the context's stream waits for lane 1's last launch before the call returns, on the error path as well: ccm_orb_fetch, the
+//   join     the context's stream waits for the auxiliary stream's last launch before the call returns, on the error path as well: ccm_orb_fetch, the
 //            matcher on ccm_orb_result_dev, orb_last_result, the debug taps and ccm_sync see the whole batch and no lane
 // The events are created once, without timing, and every wait is enqueued after the record it means.
 // What makes concurrent chunks safe, checked kernel by kernel and launcher by launcher: all six kernels take their frame as a block
@@ -419,17 +433,23 @@ static int orb_extract_lanes(ccm_ctx* c, const uint8_t* img_dev, int stride, siz
             if (!*e) CCM_HIP(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     int rc = CCM_OK;
-    bool forked = false;
+    bool forked = false;                                // the auxiliary stream may hold work of this call
     for (size_t k = 0; k < plan.size() && rc == CCM_OK; k++) {
         const OrbChunk& ck = plan[k];
-        if (k == 1) {                                   // (the fork event was recorded when chunk 0 was enqueued)
+        hipStream_t st = ((plan.size() - 1 - k) & 1) ? S.lane_stream : c->stream;      // the last chunk on the context's stream
+        if (k == 0) {                                   // (first kernel on the context's stream, the fork event behind it, the rest on st)
+            forked = st != c->stream;
+            rc = orb_run(c, img_dev, stride, image_stride, ck.frame0, ck.nrun, c->stream, S.lane_fork, st);
+            continue;
+        }
+        if (st != c->stream && !forked) {               // (the fork event was recorded when chunk 0 was enqueued)
             hipError_t e = hipStreamWaitEvent(S.lane_stream, S.lane_fork, 0);
             if (e != hipSuccess) { rc = ccm_fail(c, CCM_E_DEVICE, "hipStreamWaitEvent -> %s", hipGetErrorString(e)); break; }
             forked = true;
         }
-        rc = orb_run(c, img_dev, stride, image_stride, ck.frame0, ck.nrun, ck.lane ? S.lane_stream : c->stream, k == 0 ? S.lane_fork : nullptr);
+        rc = orb_run(c, img_dev, stride, image_stride, ck.frame0, ck.nrun, st);
     }
-    if (forked) {                                       // whatever happened above, nothing of lane 1 runs on behind the call
+    if (forked) {                                       // whatever happened above, nothing of the auxiliary stream runs on behind the call
         hipError_t e = hipEventRecord(S.lane_join, S.lane_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, S.lane_join, 0);
         if (e != hipSuccess) {
