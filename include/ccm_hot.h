@@ -460,6 +460,48 @@ int ccm_frame_create(ccm_ctx*, const ccm_frame_grid* g, const float* angle, ccm_
  * CCM_E_ARG: image out of range, n above the extract's max_per_image. */
 int ccm_frame_from_extract(ccm_ctx*, int image, int n, const float* kp_x_un, const float* kp_y_un, float min_x, float min_y,
                            float inv_w, float inv_h, int grid_cols, int grid_rows, ccm_frame** out);
+/* The camera of a Frame: mK (fx, fy, cx, cy) and mDistCoef (k1, k2, p1, p2 and k3, the fifth coefficient that src/Tracking.cpp:53-58
+ * appends only when it is not zero: 0 here when absent), as the float values the reference stores. */
+typedef struct {
+    float fx, fy, cx, cy;
+    float k1, k2, p1, p2, k3;
+} ccm_camera;
+/* Frame::mnMinX, mnMaxX, mnMinY, mnMaxY, mfGridElementWidthInv, mfGridElementHeightInv (src/Frame.cpp:87-88, :309-337). */
+typedef struct {
+    float min_x, max_x, min_y, max_y;
+    float inv_w, inv_h;
+} ccm_frame_bounds;
+/* Frame::UndistortKeyPoints (src/Frame.cpp:277-307) on n points; host only, no context, no GPU.  cv::undistortPoints as Frame.cpp:295
+ * calls it (R empty, P = mK) in its classic fixed-count form: with the float camera values and the float point widened to double,
+ *   x0 = x = (u - cx) * (1 / fx), y0 = y = (v - cy) * (1 / fy); exactly 5 times { r2 = x*x + y*y;
+ *   icdist = 1 / (1 + ((k3*r2 + k2)*r2 + k1)*r2); dx = ((2*p1)*x)*y + p2*(r2 + (2*x)*x); dy = p1*(r2 + (2*y)*y) + ((2*p2)*x)*y;
+ *   x = (x0 - dx)*icdist; y = (y0 - dy)*icdist }; u' = (float)(fx*x + cx), v' = (float)(fy*y + cy),
+ * every operation one IEEE double operation in that order.  Five iterations are not converged (up to 0.56 px from the fixed point for
+ * the EuRoC camera): the count is part of the definition.  k1 == 0 copies the input whatever the other coefficients are (the early
+ * return of :279-283).  x_un / y_un may be x / y.  CCM_E_ARG: a NULL pointer with n > 0, n < 0, fx == 0 or fy == 0. */
+int ccm_undistort_points(const ccm_camera* cam, int n, const float* x, const float* y, float* x_un, float* y_un);
+/* Frame::ComputeImageBounds (src/Frame.cpp:309-337) with the grid element sizes of :87-88; host only.  The four corners (0,0),
+ * (width,0), (0,height), (width,height) undistorted as above: min_x = min(x0, x2), max_x = max(x1, x3), min_y = min(y0, y1),
+ * max_y = max(y2, y3); with k1 == 0 the bounds are 0, width, 0, height.  inv_w = (float)grid_cols / (max_x - min_x) and inv_h likewise,
+ * in float.  CCM_E_ARG: a NULL pointer, width, height, grid_cols or grid_rows < 1, a zero focal length. */
+int ccm_image_bounds(const ccm_camera* cam, int width, int height, int grid_cols, int grid_rows, ccm_frame_bounds* out);
+/* ccm_frame_from_extract with Frame::UndistortKeyPoints (src/Frame.cpp:277-307) done on the device from the extract's own keypoints,
+ * in the kernel that builds the handle: nothing is uploaded apart from the kernel arguments, and the handle equals the one
+ * ccm_frame_from_extract makes from ccm_undistort_points' output and the same bounds.  cam == NULL or cam->k1 == 0: the extracted
+ * coordinates.  b gives min_x, min_y, inv_w, inv_h of the grid (ccm_image_bounds; max_x / max_y are not read).  Errors as
+ * ccm_frame_from_extract; CCM_E_ARG also for b == NULL or a zero focal length. */
+int ccm_frame_from_extract_camera(ccm_ctx*, int image, int n, const ccm_camera* cam, const ccm_frame_bounds* b, int grid_cols,
+                                  int grid_rows, ccm_frame** out);
+/* The Frame constructors (src/Frame.cpp:80-118 with :277-307) of n_images consecutive images of the last extract, first_image
+ * onwards: one read-back of their counts (synchronises), one staged upload of the per-frame records and one launch, a workgroup per
+ * frame.  cam may be NULL (the batched form of ccm_frame_from_extract without coordinate arrays).  All or nothing: on any error every
+ * handle made so far is released and out[] is all NULL.  n_images == 0 is CCM_OK.  CCM_E_STATE: no extract on this context yet;
+ * CCM_E_ARG: the range leaves the extract's images, b == NULL, a zero focal length. */
+int ccm_frames_from_extract_camera(ccm_ctx*, int first_image, int n_images, const ccm_camera* cam, const ccm_frame_bounds* b,
+                                   int grid_cols, int grid_rows, ccm_frame** out /* [n_images] */);
+/* Frame::mvKeysUn[i].pt (src/Frame.cpp:297-306) read back from the handle: kx, ky [N], either may be NULL.  Synchronises.
+ * CCM_E_STATE on a handle that outlived its context. */
+int ccm_frame_get_keypoints(ccm_frame*, float* kx, float* ky);
 /* NULL is a no-op. */
 void ccm_frame_destroy(ccm_frame*);
 /* Frame::N, or CCM_E_ARG for NULL. */

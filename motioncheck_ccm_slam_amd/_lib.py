@@ -46,6 +46,7 @@ SYMBOLS = [
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
     "ccm_frame_compute_bow", "ccm_frame_search_by_bow", "ccm_search_by_bow_frames",
+    "ccm_undistort_points", "ccm_image_bounds", "ccm_frame_from_extract_camera", "ccm_frames_from_extract_camera", "ccm_frame_get_keypoints",
 ]
 
 
@@ -68,6 +69,14 @@ class FrameGrid(C.Structure):
     _fields_ = [("n", C.c_int), ("kp_x", C.c_void_p), ("kp_y", C.c_void_p), ("kp_octave", C.c_void_p), ("desc", C.c_void_p),
                 ("min_x", C.c_float), ("min_y", C.c_float), ("inv_w", C.c_float), ("inv_h", C.c_float),
                 ("grid_cols", C.c_int), ("grid_rows", C.c_int)]
+
+
+class CameraStruct(C.Structure):                      # ccm_camera
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+class FrameBounds(C.Structure):                       # ccm_frame_bounds
+    _fields_ = [(k, C.c_float) for k in ("min_x", "max_x", "min_y", "max_y", "inv_w", "inv_h")]
 
 
 class BaProblem(C.Structure):
@@ -356,6 +365,13 @@ def load():
     lib.ccm_frame_create.argtypes = [vp, C.POINTER(FrameGrid), vp, C.POINTER(vp)]
     lib.ccm_frame_from_extract.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                                            C.POINTER(vp)]
+    lib.ccm_undistort_points.argtypes = [C.POINTER(CameraStruct), C.c_int, vp, vp, vp, vp]
+    lib.ccm_image_bounds.argtypes = [C.POINTER(CameraStruct), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FrameBounds)]
+    lib.ccm_frame_from_extract_camera.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CameraStruct), C.POINTER(FrameBounds), C.c_int, C.c_int,
+                                                  C.POINTER(vp)]
+    lib.ccm_frames_from_extract_camera.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CameraStruct), C.POINTER(FrameBounds), C.c_int, C.c_int,
+                                                   C.POINTER(vp)]
+    lib.ccm_frame_get_keypoints.argtypes = [vp, vp, vp]
     lib.ccm_frame_destroy.argtypes = [vp]; lib.ccm_frame_destroy.restype = None
     lib.ccm_frame_size.argtypes = [vp]
     lib.ccm_frame_set_map_points.argtypes = [vp, vp]

@@ -2,7 +2,9 @@
 // map-point ids in device memory, reused by the per-frame matchers (frame_window_host.cpp) and the pose optimisation
 // (frame_pose_host.cpp) of Tracking.  Here: the handles' lifetime and block pools, the setters, the keyframe part, ComputeBoW and the
 // debug taps.  Every setter stages its arrays in the context's block (staging.h) in the layout of their destination and sends them
-// with one copy; ComputeBoW stages [ counts | word | leaf | node ] down and uploads nothing.
+// with one copy; ComputeBoW stages [ counts | word | leaf | node ] down and uploads nothing.  The camera calls (Frame::UndistortKeyPoints,
+// Frame::ComputeImageBounds on the host from undistort.h; the handles of one or many extracted images with the undistortion done in
+// k_frame_build_batch) stage one record per frame.
 #include "frame_internal.h"
 #include "bow_directory.h"
 #include <algorithm>
@@ -271,6 +273,121 @@ int ccm_frame_from_extract(ccm_ctx* c, int image, int n, const float* kp_x_un, c
         *out = f;
         return CCM_OK;
     });
+}
+
+int ccm_undistort_points(const ccm_camera* cam, int n, const float* x, const float* y, float* x_un, float* y_un)
+{
+    if (!cam || n < 0 || (n > 0 && (!x || !y || !x_un || !y_un)) || cam->fx == 0.0f || cam->fy == 0.0f) return CCM_E_ARG;
+    if (cam->k1 == 0.0f) {                                                       // mvKeysUn = mvKeys (:279-283)
+        if (n && x_un != x) std::memmove(x_un, x, (size_t)n * 4);
+        if (n && y_un != y) std::memmove(y_un, y, (size_t)n * 4);
+        return CCM_OK;
+    }
+    const UndistortCam U = undistort_cam(*cam);
+    for (int i = 0; i < n; i++) undistort_point(U, x[i], y[i], &x_un[i], &y_un[i]);
+    return CCM_OK;
+}
+
+int ccm_image_bounds(const ccm_camera* cam, int width, int height, int grid_cols, int grid_rows, ccm_frame_bounds* out)
+{
+    if (!cam || !out || width < 1 || height < 1 || grid_cols < 1 || grid_rows < 1 || cam->fx == 0.0f || cam->fy == 0.0f) return CCM_E_ARG;
+    ccm_frame_bounds b;
+    if (cam->k1 != 0.0f) {                                                       // the corners in the order of :314-317
+        float cx[4] = { 0.0f, (float)width, 0.0f, (float)width }, cy[4] = { 0.0f, 0.0f, (float)height, (float)height };
+        const UndistortCam U = undistort_cam(*cam);
+        for (int i = 0; i < 4; i++) undistort_point(U, cx[i], cy[i], &cx[i], &cy[i]);
+        b.min_x = std::min(cx[0], cx[2]); b.max_x = std::max(cx[1], cx[3]);
+        b.min_y = std::min(cy[0], cy[1]); b.max_y = std::max(cy[2], cy[3]);
+    } else {
+        b.min_x = 0.0f; b.max_x = (float)width; b.min_y = 0.0f; b.max_y = (float)height;
+    }
+    b.inv_w = (float)grid_cols / (b.max_x - b.min_x);                            // :87-88
+    b.inv_h = (float)grid_rows / (b.max_y - b.min_y);
+    *out = b;
+    return CCM_OK;
+}
+
+// The two calls below: n_images handles from consecutive images of the last extract through one launch of k_frame_build_batch.
+// n >= 0 is the caller's count of a single image; n < 0 reads the counts of the range with one fetch.
+static int frames_from_extract(ccm_ctx* c, const char* fn, int first_image, int n_images, int n, const ccm_camera* cam,
+                               const ccm_frame_bounds* b, int grid_cols, int grid_rows, ccm_frame** out)
+{
+    if (!b || !grid_ok(grid_cols, grid_rows)) return ccm_fail(c, CCM_E_ARG, "%s: bad frame arguments (bounds, grid of at most 16384 cells)", fn);
+    if (cam && (cam->fx == 0.0f || cam->fy == 0.0f)) return ccm_fail(c, CCM_E_ARG, "%s: zero focal length", fn);
+    std::vector<ccm_frame*> made;
+    const int rc = ccm_guard(c, fn, [&]() -> int {
+        const ccm_keypoint* kps = nullptr; const uint8_t* desc = nullptr; const int32_t* counts = nullptr;
+        int have = 0, max_per_image = 0, nlevels = 0;
+        int rc = orb_last_result(c, &kps, &desc, &counts, &have, &max_per_image, &nlevels);
+        if (rc) return rc;
+        if (first_image < 0 || n_images < 0 || first_image > have || n_images > have - first_image || (n >= 0 && first_image >= have))
+            return ccm_fail(c, CCM_E_ARG, "%s: images [%d, %d + %d) out of range [0, %d)", fn, first_image, first_image, n_images, have);
+        if (n > max_per_image) return ccm_fail(c, CCM_E_ARG, "%s: n %d above the extract's max_per_image %d", fn, n, max_per_image);
+        if (n_images == 0) return CCM_OK;
+        CCM_HIP(c, hipSetDevice(c->device));
+        std::vector<int32_t> cnt((size_t)n_images, n);
+        if (n < 0) {
+            if ((rc = frame_fetch(c, cnt.data(), counts + first_image, (size_t)n_images * 4))) return rc;
+            for (int32_t& v : cnt) v = std::max(0, std::min<int>(v, max_per_image));
+        }
+        Staging& G = frame_state(c)->stage;
+        const size_t end = (size_t)n_images * sizeof(FrameBatchRec);
+        if ((rc = G.reserve(c, end))) return rc;
+        FrameBatchRec* rec = G.host<FrameBatchRec>(0);
+        made.reserve((size_t)n_images);
+        for (int k = 0; k < n_images; k++) {
+            ccm_frame* f = nullptr;
+            if ((rc = frame_alloc(c, cnt[k], grid_cols, grid_rows, &f))) return rc;
+            made.push_back(f);
+            f->n_levels = nlevels; f->has_angle = true;
+            f->min_x = b->min_x; f->min_y = b->min_y; f->inv_w = b->inv_w; f->inv_h = b->inv_h;
+            const size_t row = (size_t)(first_image + k) * max_per_image;
+            rec[k] = FrameBatchRec{ kps + row, desc + row * 32, f->n, 0, f->kx, f->ky, f->oct, f->angle, f->desc, f->cell_first, f->cell_items,
+                                    f->mp_id };
+        }
+        if ((rc = G.upload(c, 0, end))) return rc;
+        FrameBatchArgs A{};
+        A.rec = G.dev<FrameBatchRec>(0);
+        A.cols = grid_cols; A.rows = grid_rows; A.min_x = b->min_x; A.min_y = b->min_y; A.inv_w = b->inv_w; A.inv_h = b->inv_h;
+        A.undistort = cam && cam->k1 != 0.0f;                                  // the early return of :279-283
+        if (A.undistort) A.cam = undistort_cam(*cam);
+        if (frame_launch_build_batch(c->stream, n_images, A)) return ccm_fail(c, CCM_E_DEVICE, "k_frame_build_batch: LDS request refused");
+        CCM_HIP(c, hipGetLastError());
+        return CCM_OK;
+    });
+    if (rc) { for (ccm_frame* f : made) frame_release(f); return rc; }
+    for (size_t k = 0; k < made.size(); k++) out[k] = made[k];
+    return CCM_OK;
+}
+
+int ccm_frame_from_extract_camera(ccm_ctx* c, int image, int n, const ccm_camera* cam, const ccm_frame_bounds* b, int grid_cols,
+                                  int grid_rows, ccm_frame** out)
+{
+    RoctxRange roctx_("ccm_frame_from_extract_camera");
+    if (out) *out = nullptr;
+    if (!c || !out) return CCM_E_ARG;
+    if (n < -1) return ccm_fail(c, CCM_E_ARG, "ccm_frame_from_extract_camera: n = %d", n);
+    return frames_from_extract(c, "ccm_frame_from_extract_camera", image, 1, n, cam, b, grid_cols, grid_rows, out);
+}
+
+int ccm_frames_from_extract_camera(ccm_ctx* c, int first_image, int n_images, const ccm_camera* cam, const ccm_frame_bounds* b,
+                                   int grid_cols, int grid_rows, ccm_frame** out)
+{
+    RoctxRange roctx_("ccm_frames_from_extract_camera");
+    if (out) for (int k = 0; k < n_images; k++) out[k] = nullptr;
+    if (!c || (!out && n_images != 0)) return CCM_E_ARG;
+    return frames_from_extract(c, "ccm_frames_from_extract_camera", first_image, n_images, -1, cam, b, grid_cols, grid_rows, out);
+}
+
+int ccm_frame_get_keypoints(ccm_frame* f, float* kx, float* ky)
+{
+    if (!f) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    CCM_HIP(c, hipSetDevice(c->device));
+    int rc = kx ? frame_fetch(c, kx, f->kx, (size_t)f->n * 4) : CCM_OK;
+    if (rc || !ky) return rc;
+    return frame_fetch(c, ky, f->ky, (size_t)f->n * 4);
 }
 
 void ccm_frame_destroy(ccm_frame* f)

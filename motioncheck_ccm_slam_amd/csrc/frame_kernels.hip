@@ -1,6 +1,8 @@
 // frame_kernels.hip -- device side of the frame handles (frame_host.cpp, include/ccm_hot.h "frame handles"):
 //   k_frame_build         gather of an extracted image's keypoints / descriptors (ccm_frame_from_extract) and the feature grid
 //                         (Frame::AssignFeaturesToGrid / PosInGrid, src/Frame.cpp:103-118, 255-266), one workgroup per frame
+//   k_frame_build_batch   the same for many extracted images in one launch, a workgroup per frame, with Frame::UndistortKeyPoints
+//                         (src/Frame.cpp:277-307) fused into the gather (ccm_frame_from_extract_camera, ccm_frames_from_extract_camera)
 //   k_frame_prep_last     query radius and level window of SearchByProjection(Current, Last) from the last frame's octaves
 //   k_frame_scatter_ids   mvpMapPoints of the newly matched features
 //   k_frame_pose_gather   the correspondences of PoseOptimizationClient in feature order (compaction, first[] on the device), the
@@ -13,7 +15,9 @@
 
 // PosInGrid (src/Frame.cpp:255-266) exactly as grid_build() in match_window_host.cpp: round() in float, half away from zero; features
 // outside the grid get no cell.  A NaN coordinate gets none either (x86's conversion gives INT_MIN, the device's 0).
-__device__ inline int fb_cell(const FrameBuildArgs& A, float x, float y)
+// G: what a build kernel knows of its frame's grid (FrameBuildArgs, FbFrame): n, cols, rows, min_x, min_y, inv_w, inv_h, kx, ky,
+// cell_first, cell_items.
+template <class G> __device__ inline int fb_cell(const G& A, float x, float y)
 {
     const float fx = roundf((x - A.min_x) * A.inv_w), fy = roundf((y - A.min_y) * A.inv_h);
     if (fx != fx || fy != fy) return -1;
@@ -21,29 +25,13 @@ __device__ inline int fb_cell(const FrameBuildArgs& A, float x, float y)
     return (px < 0 || px >= A.cols || py < 0 || py >= A.rows) ? -1 : px * A.rows + py;
 }
 
-// One workgroup.  LDS: first[cells + 1] and fill[cells] counters.  Cell counts by LDS atomics, an exclusive scan, atomic placement,
-// then each cell's items sorted by feature index (a cell holds a handful of features): the order the host build's index-order
-// fill gives.
-__global__ __launch_bounds__(FB_TPB) void k_frame_build(FrameBuildArgs A)
+// Frame::AssignFeaturesToGrid (src/Frame.cpp:103-118) by one workgroup, on the coordinates A.kx / A.ky the workgroup has written: the
+// stages the build kernels share.  LDS: s_first[cells + 1] and s_fill[cells] counters, s_part[FB_TPB].  A build kernel clears s_fill,
+// calls fb_count_scan (cell counts by LDS atomics, then their exclusive scan into s_first), publishes s_first as cell_first and as the
+// fill positions, and calls fb_place_sort (atomic placement, then each cell's items sorted by feature index -- a cell holds a handful
+// of features: the order the host build's index-order fill gives).
+template <class G> __device__ __forceinline__ void fb_count_scan(const G& A, const int cells, const int tid, int* s_first, int* s_fill, int* s_part)
 {
-    extern __shared__ int fb_lds[];
-    const int cells = A.cols * A.rows, tid = threadIdx.x;
-    int* s_first = fb_lds;                 // [cells + 1]
-    int* s_fill = fb_lds + cells + 1;      // [cells]
-    __shared__ int s_part[FB_TPB];
-    if (A.kps) {
-        for (int i = tid; i < A.n; i += FB_TPB) {
-            const ccm_keypoint k = A.kps[i];
-            if (!A.keep_xy) { A.kx[i] = k.x; A.ky[i] = k.y; }
-            A.oct[i] = k.octave; A.angle[i] = k.angle;
-            const uint4* s = reinterpret_cast<const uint4*>(A.src_desc + (size_t)i * 32);
-            uint4* d = reinterpret_cast<uint4*>(A.desc + (size_t)i * 32);
-            d[0] = s[0]; d[1] = s[1];
-        }
-    }
-    for (int i = tid; i < A.n; i += FB_TPB) A.mp_id[i] = -1;
-    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = 0;
-    __syncthreads();
     for (int i = tid; i < A.n; i += FB_TPB) {
         const int c = fb_cell(A, A.kx[i], A.ky[i]);
         if (c >= 0) atomicAdd(&s_fill[c], 1);
@@ -65,9 +53,10 @@ __global__ __launch_bounds__(FB_TPB) void k_frame_build(FrameBuildArgs A)
     for (int k = lo; k < hi; k++) { const int cnt = s_fill[k]; s_first[k] = run; run += cnt; }
     if (tid == FB_TPB - 1) s_first[cells] = s_part[FB_TPB - 1];
     __syncthreads();
-    for (int k = tid; k <= cells; k += FB_TPB) A.cell_first[k] = s_first[k];
-    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = s_first[k];
-    __syncthreads();
+}
+
+template <class G> __device__ __forceinline__ void fb_place_sort(const G& A, const int cells, const int tid, int* s_first, int* s_fill)
+{
     for (int i = tid; i < A.n; i += FB_TPB) {
         const int c = fb_cell(A, A.kx[i], A.ky[i]);
         if (c >= 0) A.cell_items[atomicAdd(&s_fill[c], 1)] = i;
@@ -82,6 +71,90 @@ __global__ __launch_bounds__(FB_TPB) void k_frame_build(FrameBuildArgs A)
             A.cell_items[q + 1] = v;
         }
     }
+}
+
+// One workgroup: the gather of an extracted image (or nothing: the host uploaded x .. desc), mp_id = -1, then the grid.
+__global__ __launch_bounds__(FB_TPB) void k_frame_build(FrameBuildArgs A)
+{
+    extern __shared__ int fb_lds[];
+    const int cells = A.cols * A.rows, tid = threadIdx.x;
+    int* s_first = fb_lds;                 // [cells + 1]
+    int* s_fill = fb_lds + cells + 1;      // [cells]
+    __shared__ int s_part[FB_TPB];
+    if (A.kps) {
+        for (int i = tid; i < A.n; i += FB_TPB) {
+            const ccm_keypoint k = A.kps[i];
+            if (!A.keep_xy) { A.kx[i] = k.x; A.ky[i] = k.y; }
+            A.oct[i] = k.octave; A.angle[i] = k.angle;
+            const uint4* s = reinterpret_cast<const uint4*>(A.src_desc + (size_t)i * 32);
+            uint4* d = reinterpret_cast<uint4*>(A.desc + (size_t)i * 32);
+            d[0] = s[0]; d[1] = s[1];
+        }
+    }
+    for (int i = tid; i < A.n; i += FB_TPB) A.mp_id[i] = -1;
+    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = 0;
+    __syncthreads();
+    fb_count_scan(A, cells, tid, s_first, s_fill, s_part);
+    for (int k = tid; k <= cells; k += FB_TPB) A.cell_first[k] = s_first[k];
+    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = s_first[k];
+    __syncthreads();
+    fb_place_sort(A, cells, tid, s_first, s_fill);
+}
+
+// The Frame constructors of a batch of extracted images (ccm_frames_from_extract_camera; the single call is the batch of one): one
+// workgroup per frame, blockIdx.x = frame, its record in device memory.  The gather undistorts each keypoint as it is read
+// (Frame::UndistortKeyPoints, undistort.h): a thread first issues the loads of up to FB_GATHER keypoints, then
+// runs their iterations, so that the FP64 chains (one division per iteration) start on data that arrived together.
+// The record's pointers are read from memory, so the compiler cannot know that they point to global memory: they are cast to that
+// address space once, which keeps the gather and the shared stages on global (not flat) loads and stores, as in k_frame_build.
+#define FB_GATHER 4
+#define FB_GLOBAL __attribute__((address_space(1)))
+typedef unsigned fb_u32x4 __attribute__((ext_vector_type(4)));    // 16 bytes of a descriptor row
+struct FbFrame {                           // the G of the shared stages for one record
+    int n, cols, rows; float min_x, min_y, inv_w, inv_h;
+    const FB_GLOBAL float* kx; const FB_GLOBAL float* ky; FB_GLOBAL int* cell_first; FB_GLOBAL int* cell_items;
+};
+__global__ __launch_bounds__(FB_TPB) void k_frame_build_batch(FrameBatchArgs A)
+{
+    extern __shared__ int fb_lds[];
+    const int cells = A.cols * A.rows, tid = threadIdx.x;
+    int* s_first = fb_lds;                 // [cells + 1]
+    int* s_fill = fb_lds + cells + 1;      // [cells]
+    __shared__ int s_part[FB_TPB];
+    const FrameBatchRec* R = A.rec + blockIdx.x;
+    const int n = R->n;
+    const FB_GLOBAL ccm_keypoint* kps = (const FB_GLOBAL ccm_keypoint*)R->kps;
+    const FB_GLOBAL fb_u32x4* src_desc = (const FB_GLOBAL fb_u32x4*)R->src_desc;
+    FB_GLOBAL float* kx = (FB_GLOBAL float*)R->kx; FB_GLOBAL float* ky = (FB_GLOBAL float*)R->ky;
+    FB_GLOBAL int* oct = (FB_GLOBAL int*)R->oct; FB_GLOBAL float* angle = (FB_GLOBAL float*)R->angle;
+    FB_GLOBAL fb_u32x4* desc = (FB_GLOBAL fb_u32x4*)R->desc; FB_GLOBAL int* mp_id = (FB_GLOBAL int*)R->mp_id;
+    for (int k = tid; k < 2 * n; k += FB_TPB) desc[k] = src_desc[k];      // the descriptor rows, 16 bytes per lane
+    for (int base = tid; base < n; base += FB_TPB * FB_GATHER) {
+        float x[FB_GATHER], y[FB_GATHER], ang[FB_GATHER]; int o[FB_GATHER];
+#pragma unroll
+        for (int j = 0; j < FB_GATHER; j++) {
+            const int i = min(base + j * FB_TPB, n - 1);           // past the end: the last row again, not written below
+            x[j] = kps[i].x; y[j] = kps[i].y; ang[j] = kps[i].angle; o[j] = kps[i].octave;
+        }
+#pragma unroll
+        for (int j = 0; j < FB_GATHER; j++) {
+            const int i = base + j * FB_TPB;
+            if (i < n) {
+                float ux = x[j], uy = y[j];
+                if (A.undistort) undistort_point(A.cam, x[j], y[j], &ux, &uy);
+                kx[i] = ux; ky[i] = uy; oct[i] = o[j]; angle[i] = ang[j];
+            }
+        }
+    }
+    for (int i = tid; i < n; i += FB_TPB) mp_id[i] = -1;
+    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = 0;
+    __syncthreads();                       // also: the gather's coordinates are visible to the workgroup
+    const FbFrame F{ n, A.cols, A.rows, A.min_x, A.min_y, A.inv_w, A.inv_h, kx, ky, (FB_GLOBAL int*)R->cell_first, (FB_GLOBAL int*)R->cell_items };
+    fb_count_scan(F, cells, tid, s_first, s_fill, s_part);
+    for (int k = tid; k <= cells; k += FB_TPB) F.cell_first[k] = s_first[k];
+    for (int k = tid; k < cells; k += FB_TPB) s_fill[k] = s_first[k];
+    __syncthreads();
+    fb_place_sort(F, cells, tid, s_first, s_fill);
 }
 
 // SearchByProjection(Current, Last) query set-up (ORBmatcher.cpp:1401-1405) from the last frame's octaves in HBM: the host
@@ -174,6 +247,14 @@ int frame_launch_build(hipStream_t s, const FrameBuildArgs& A)
     const size_t lds = frame_build_lds(A.cols * A.rows);
     if (hipFuncSetAttribute((const void*)k_frame_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
     hipLaunchKernelGGL(k_frame_build, dim3(1), dim3(FB_TPB), lds, s, A);
+    return 0;
+}
+int frame_launch_build_batch(hipStream_t s, int n_frames, const FrameBatchArgs& A)
+{
+    if (n_frames <= 0) return 0;
+    const size_t lds = frame_build_lds(A.cols * A.rows);
+    if (hipFuncSetAttribute((const void*)k_frame_build_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_frame_build_batch, dim3(n_frames), dim3(FB_TPB), lds, s, A);
     return 0;
 }
 void frame_launch_prep_last(hipStream_t s, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl)

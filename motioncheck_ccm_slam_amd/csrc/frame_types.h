@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/ccm_hot.h"
 #include "map_math.h"
+#include "undistort.h"
 
 #define FB_TPB 1024
 
@@ -14,6 +15,18 @@ struct FrameBuildArgs {
     const ccm_keypoint* kps; const uint8_t* src_desc;  // gather source (an extracted image) or nullptr: x..desc already written
     int keep_xy;                                       // with kps: x / y were uploaded (undistorted), take only octave / angle / desc
     float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
+};
+// k_frame_build_batch: one record per frame in device memory (the frame's source rows of the extract, its count and the pointers into
+// its block); what the frames of a call share travels in the kernel arguments.
+struct FrameBatchRec {
+    const ccm_keypoint* kps; const uint8_t* src_desc; int n, pad_;
+    float* kx; float* ky; int* oct; float* angle; uint8_t* desc; int* cell_first; int* cell_items; int* mp_id;
+};
+struct FrameBatchArgs {
+    const FrameBatchRec* rec;                          // [gridDim.x]
+    int cols, rows; float min_x, min_y, inv_w, inv_h;
+    int undistort;                                     // 0: the extracted coordinates (cam == NULL or k1 == 0), cam is not read
+    UndistortCam cam;
 };
 // The points of the handle's map-point ids: xyz [n_mp][3] (the caller's array; pos and flags null), or the columns of a map-point
 // table of capacity n_mp: pos [n_mp][3] float, widened (Converter::toVector3d of a float cv::Mat is exact), and flags, where a slot
@@ -30,6 +43,7 @@ struct KfGatherArgs {
 
 size_t frame_build_lds(int cells);
 int frame_launch_build(hipStream_t, const FrameBuildArgs&);
+int frame_launch_build_batch(hipStream_t, int n_frames, const FrameBatchArgs&);
 void frame_launch_prep_last(hipStream_t, int nq, const uint8_t* valid, const int* oct, const float* scale, float th, float* qr, int* minl, int* maxl);
 void frame_launch_scatter_ids(hipStream_t, int n, const int* match, const int* src, const int* status, int* mp_id);
 void frame_launch_pose_gather(hipStream_t, const PoseGatherArgs&);

@@ -13,6 +13,49 @@ from . import _lib
 from .matcher import FRAME_GRID_COLS, FRAME_GRID_ROWS, FrameGridView
 
 
+class Camera:
+    """ccm_camera: mK and mDistCoef of a Frame as the float values the reference stores (k3 = 0 when the settings file has none,
+    src/Tracking.cpp:53-58).  `undistort` is Frame::UndistortKeyPoints (ccm_undistort_points), `image_bounds`
+    Frame::ComputeImageBounds with the grid element sizes (ccm_image_bounds); both run on the host."""
+
+    FIELDS = ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")
+
+    def __init__(self, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+        vals = np.array([fx, fy, cx, cy, k1, k2, p1, p2, k3], "f4")            # the float rounding of the nine values
+        for name, v in zip(self.FIELDS, vals):
+            setattr(self, name, float(v))
+        self.struct = _lib.CameraStruct(*[float(v) for v in vals])
+
+    def undistort(self, x, y):
+        """(x_un, y_un) float32 of the float32 points (x, y)."""
+        x = np.ascontiguousarray(x, "f4").reshape(-1); y = np.ascontiguousarray(y, "f4").reshape(-1)
+        if len(x) != len(y):
+            raise ValueError("x and y differ in length")
+        xo = np.empty(max(len(x), 1), "f4"); yo = np.empty(max(len(x), 1), "f4")
+        rc = _lib.load().ccm_undistort_points(C.byref(self.struct), len(x), _lib.ptr(x), _lib.ptr(y), _lib.ptr(xo), _lib.ptr(yo))
+        if rc:
+            raise _lib.CcmError(rc, "ccm_undistort_points")
+        return xo[:len(x)], yo[:len(x)]
+
+    def image_bounds(self, width, height, grid_cols=FRAME_GRID_COLS, grid_rows=FRAME_GRID_ROWS):
+        """The _lib.FrameBounds (min_x, max_x, min_y, max_y, inv_w, inv_h) of a width x height image."""
+        b = _lib.FrameBounds()
+        rc = _lib.load().ccm_image_bounds(C.byref(self.struct), int(width), int(height), int(grid_cols), int(grid_rows), C.byref(b))
+        if rc:
+            raise _lib.CcmError(rc, "ccm_image_bounds")
+        return b
+
+
+def _bounds_struct(bounds, min_x, max_x, min_y, max_y):
+    """bounds as a _lib.FrameBounds: given, or made from the four limits the way from_extract always has."""
+    if bounds is not None:
+        return bounds
+    inv_w = np.float32(FRAME_GRID_COLS) / np.float32(np.float32(max_x) - np.float32(min_x))
+    inv_h = np.float32(FRAME_GRID_ROWS) / np.float32(np.float32(max_y) - np.float32(min_y))
+    return _lib.FrameBounds(float(np.float32(min_x)), float(np.float32(max_x)), float(np.float32(min_y)), float(np.float32(max_y)),
+                            float(inv_w), float(inv_h))
+
+
 class DeviceFrame:
     """A ccm_frame handle.  Build with `DeviceFrame(view, angle, ctx=...)` from host arrays or `DeviceFrame.from_extract` from the
     last extraction of an `ORBextractor`; release with `close()` (before the context goes)."""
@@ -35,11 +78,21 @@ class DeviceFrame:
 
     @classmethod
     def from_extract(cls, extractor, image: int = 0, kx_un=None, ky_un=None, n: int = -1, min_x=0.0, max_x=752.0, min_y=0.0, max_y=480.0,
-                     ctx: _lib.Context | None = None):
+                     ctx: _lib.Context | None = None, camera: Camera | None = None, bounds=None):
         """Frame of image `image` of the extractor's last extract (ccm_frame_from_extract): octave, angle and descriptors stay on the
-        device; kx_un / ky_un are the undistorted coordinates (None: the extracted ones).  n = keypoint count (-1: read it)."""
+        device; kx_un / ky_un are the undistorted coordinates (None: the extracted ones).  n = keypoint count (-1: read it).
+        With `camera` (a Camera) and / or `bounds` (Camera.image_bounds) the keypoints are undistorted on the device as the handle
+        is built (ccm_frame_from_extract_camera) and no coordinates are passed; bounds=None then takes min_x .. max_y."""
         ctx = ctx or extractor.ctx
         lib = ctx.lib
+        if camera is not None or bounds is not None:
+            if kx_un is not None or ky_un is not None:
+                raise ValueError("coordinate arrays and a camera exclude each other")
+            b = _bounds_struct(bounds, min_x, max_x, min_y, max_y)
+            h = C.c_void_p()
+            ctx.check(lib.ccm_frame_from_extract_camera(ctx.handle, int(image), int(n), None if camera is None else C.byref(camera.struct),
+                                                        C.byref(b), FRAME_GRID_COLS, FRAME_GRID_ROWS, C.byref(h)))
+            return cls(ctx=ctx, _handle=h.value)
         kx = None if kx_un is None else np.ascontiguousarray(kx_un, "f4")
         ky = None if ky_un is None else np.ascontiguousarray(ky_un, "f4")
         if (kx is None) != (ky is None):
@@ -56,6 +109,24 @@ class DeviceFrame:
                                              float(np.float32(min_y)), float(inv_w), float(inv_h), FRAME_GRID_COLS, FRAME_GRID_ROWS,
                                              C.byref(h)))
         return cls(ctx=ctx, _handle=h.value)
+
+    @classmethod
+    def batch_from_extract(cls, extractor, first: int, count: int, camera: Camera | None = None, bounds=None, min_x=0.0, max_x=752.0,
+                           min_y=0.0, max_y=480.0, ctx: _lib.Context | None = None):
+        """The handles of images first .. first + count - 1 of the extractor's last extract, made by one call and one launch
+        (ccm_frames_from_extract_camera); camera=None keeps the extracted coordinates.  All or nothing."""
+        ctx = ctx or extractor.ctx
+        b = _bounds_struct(bounds, min_x, max_x, min_y, max_y)
+        hs = (C.c_void_p * max(int(count), 1))()
+        ctx.check(ctx.lib.ccm_frames_from_extract_camera(ctx.handle, int(first), int(count), None if camera is None else C.byref(camera.struct),
+                                                         C.byref(b), FRAME_GRID_COLS, FRAME_GRID_ROWS, hs))
+        return [cls(ctx=ctx, _handle=hs[k]) for k in range(int(count))]
+
+    def keypoints(self):
+        """(kx, ky) float32: the handle's coordinates, mvKeysUn[i].pt (ccm_frame_get_keypoints)."""
+        kx = np.empty(max(self.n, 1), "f4"); ky = np.empty(max(self.n, 1), "f4")
+        self.ctx.check(self.lib.ccm_frame_get_keypoints(C.c_void_p(self.handle), _lib.ptr(kx), _lib.ptr(ky)))
+        return kx[:self.n], ky[:self.n]
 
     @property
     def map_points(self) -> np.ndarray:

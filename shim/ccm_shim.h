@@ -105,6 +105,18 @@ inline ccm_frame* frame_handle(const FrameT& F)
     s.id0 = F.mId.first; s.id1 = F.mId.second; s.n = N; s.f = f; s.used = S.clock;
     return f;
 }
+// A handle made elsewhere for Frame F (the constructor's device route, cslam_frame.cpp: ccm_frame_from_extract_camera) goes into the
+// least recently used slot, so that frame_handle(F) finds it and nothing of F is uploaded.  The cache owns f from here on.
+template <class FrameT>
+inline void frame_handle_put(const FrameT& F, ccm_frame* f)
+{
+    ThreadState& S = thread_state();
+    S.clock++;
+    ThreadState::Slot& s = S.slot[0].used <= S.slot[1].used ? S.slot[0] : S.slot[1];
+    ccm_frame_destroy(s.f);
+    s = ThreadState::Slot();
+    s.id0 = F.mId.first; s.id1 = F.mId.second; s.n = ccm_frame_size(f); s.f = f; s.used = S.clock;
+}
 #endif
 
 // ---- keyframe handles (cslam_mapping.cpp).  LocalMapping keeps one ccm_frame per keyframe of its neighbourhood in ITS context (a

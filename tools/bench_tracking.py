@@ -6,6 +6,10 @@ synchronised call, the two paths alternating inside one process after a warm-up:
   (b) SearchByProjection(Current, Last, 7)          TrackWithMotionModel (:571-597)
   (c) PoseOptimizationClient of one frame
   (d) the chain: extract of one frame from host buffers -> frame (handle) -> (b) -> pose -> drop the outliers -> (a) -> pose
+  (e) a camera with distortion (the EuRoC one, k1 = -0.2834): extract on the device -> handle -> (b) -> pose, two ways.  Today's
+      route: read back the count and the keypoints, Frame::UndistortKeyPoints on the host (ccm_undistort_points), ccm_frame_from_extract
+      with the two coordinate arrays.  New route: ccm_frame_from_extract_camera, the undistortion done in the build kernel.
+  (f) the handles of 256 images of one extract: 256 calls of ccm_frame_from_extract_camera against one ccm_frames_from_extract_camera
 Every repetition's results are compared between the paths.  Output: profiles/<tag>_tracking_chain.json and one summary line.
 
     python tools/bench_tracking.py [--reps 300] [--warmup 30] [--tag r04]
@@ -22,7 +26,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from motioncheck_ccm_slam_amd import _lib, synth  # noqa: E402
-from motioncheck_ccm_slam_amd.frame import DeviceFrame  # noqa: E402
+from motioncheck_ccm_slam_amd.frame import Camera, DeviceFrame  # noqa: E402
 from motioncheck_ccm_slam_amd.matcher import FrameGridView, ORBmatcher  # noqa: E402
 from motioncheck_ccm_slam_amd.optimizer import Optimizer  # noqa: E402
 from motioncheck_ccm_slam_amd.orb import ORBextractor  # noqa: E402
@@ -111,6 +115,70 @@ def chain_handle(W, m_f, m_l, last):
     return nb, mb, pose, outl, na, ma, pose2, outl2, ni2
 
 
+# cslam/conf/vi_euroc.yaml: the 752 x 480 camera with distortion
+EUROC = dict(fx=458.654, fy=457.296, cx=367.215, cy=248.375, k1=-0.28340811, k2=0.07395907, p1=0.00019359, p2=1.76187114e-05)
+N_BATCH = 256
+
+
+def setup_distorted(W, ctx, torch):
+    """The inputs of (e) and (f): the current image and a batch of 256 in device memory, the last frame's handle with undistorted
+    coordinates and a map made from them."""
+    cam = Camera(**EUROC)
+    b = cam.image_bounds(752, 480)
+    ex = W["ex"]
+    last_img = np.roll(W["cur_img"], (-SHIFT[0], -SHIFT[1]), axis=(0, 1))
+    kl, dl = ex(last_img)
+    last = DeviceFrame.from_extract(ex, 0, camera=cam, bounds=b, ctx=ctx)
+    lx, ly = last.keypoints()
+    rng = np.random.default_rng(2)
+    nl = len(kl)
+    z = rng.uniform(2, 10, nl)
+    xyz = np.stack([(lx - INTR[2]) / INTR[0] * z, (ly - INTR[3]) / INTR[1] * z, z], 1).astype(np.float32).astype(np.float64)
+    ids = np.where(rng.random(nl) < 0.9, np.arange(nl), -1).astype("i4")
+    last.map_points = ids
+    u = (lx + SHIFT[1]).astype("f4"); v = (ly + SHIFT[0]).astype("f4")
+    valid = (ids >= 0) & (u >= b.min_x) & (u < b.max_x) & (v >= b.min_y) & (v < b.max_y)
+    dev_cur = torch.from_numpy(W["cur_img"][None].copy()).cuda()
+    batch = np.stack([np.roll(W["cur_img"], (k % 16, -(k // 16)), axis=(0, 1)) for k in range(N_BATCH)])
+    dev_batch = torch.from_numpy(batch).cuda()
+    torch.cuda.synchronize()
+    return dict(cam=cam, b=b, last=last, ids=ids, xyz=xyz, args=(valid, u, v, dl, np.ones(nl, bool)), dev_cur=dev_cur, dev_batch=dev_batch)
+
+
+def distorted_chain(W, D, m_f, ctx, new_route):
+    ex, cam, b = W["ex"], D["cam"], D["b"]
+    ex.extract_dev(D["dev_cur"].data_ptr(), 752, 480, 752, 752 * 480, 1)
+    if new_route:
+        cur = DeviceFrame.from_extract(ex, 0, camera=cam, bounds=b, ctx=ctx)
+    else:
+        kps = np.zeros((1, ex.max_per_image), _lib.KP_DTYPE); cnt = np.zeros(1, "i4")
+        ctx.check(ctx.lib.ccm_orb_fetch(ctx.handle, _lib.ptr(kps), None, _lib.ptr(cnt)))      # count and keypoints, no descriptors
+        n = int(cnt[0])
+        kxu, kyu = cam.undistort(kps[0, :n]["x"], kps[0, :n]["y"])
+        cur = DeviceFrame.from_extract(ex, 0, kxu, kyu, n=n, min_x=b.min_x, max_x=b.max_x, min_y=b.min_y, max_y=b.max_y, ctx=ctx)
+    with cur:
+        valid, u, v, md, ho = D["args"]
+        nb, mb, _ = m_f.SearchByProjectionFrameHandle(cur, D["last"], W["sf"], valid, u, v, md, ho, np.zeros(cur.n, bool), 7.0)
+        pose, outl, ni = Optimizer.PoseOptimizationFrame(cur, np.array([0, 0, 0, 1, 0, 0, 0.0]), INTR, D["xyz"], W["is2"])
+    return nb, mb, pose, outl, ni
+
+
+def build_handles(W, D, ctx, batched):
+    """(f): the timed part makes the 256 handles and waits for the device; the check and the release are outside it."""
+    ex, cam, b = W["ex"], D["cam"], D["b"]
+    t0 = time.perf_counter()
+    if batched:
+        hs = DeviceFrame.batch_from_extract(ex, 0, N_BATCH, cam, b, ctx=ctx)
+    else:
+        hs = [DeviceFrame.from_extract(ex, k, camera=cam, bounds=b, ctx=ctx) for k in range(N_BATCH)]
+    ctx.sync()
+    dt = time.perf_counter() - t0
+    res = tuple(x for k in (0, 17, N_BATCH - 1) for x in hs[k].keypoints() + hs[k].grid()) + (sum(h.n for h in hs),)
+    for h in hs:
+        h.close()
+    return dt, res
+
+
 def same(a, b):
     if isinstance(a, tuple):
         return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
@@ -124,6 +192,8 @@ def stats(ts):
 
 
 def main():
+    import torch                                                   # before the library is loaded: both then share one HIP runtime
+    torch.cuda.init()
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
@@ -161,6 +231,10 @@ def main():
             lambda: chain_host(W, m_f, m_l, ctx),
             lambda: chain_handle(W, m_f, m_l, last)),
     }
+    D = setup_distorted(W, ctx, torch)
+    cases["e_distorted_extract_handle_match_pose"] = (
+        lambda: distorted_chain(W, D, m_f, ctx, False),
+        lambda: distorted_chain(W, D, m_f, ctx, True))
     cur.map_points = ids_b
     cur_pose.map_points = ids_b
     result = {"workload": {"image": [752, 480], "features": n, "local_map_points": len(W["xyz"]), "reps": a.reps, "warmup": a.warmup},
@@ -178,16 +252,38 @@ def main():
                 if which == 0: ro = res
                 else: rn = res
             mismatches += not same(tuple(ro), tuple(rn))
-        result["cases"][name] = {"host_buffers": stats(t_old), "handle": stats(t_new), "mismatching_reps": mismatches}
-        print("%-42s host %.4f ms [%.4f, %.4f]   handle %.4f ms [%.4f, %.4f]   mismatches %d" % (
-            name, *(result["cases"][name]["host_buffers"][k] for k in ("median_ms", "p10_ms", "p90_ms")),
-            *(result["cases"][name]["handle"][k] for k in ("median_ms", "p10_ms", "p90_ms")), mismatches), flush=True)
-    last.close(); cur.close(); cur_pose.close()
+        ko, kn = ("todays_route", "new_route") if name.startswith("e_") else ("host_buffers", "handle")
+        result["cases"][name] = {ko: stats(t_old), kn: stats(t_new), "mismatching_reps": mismatches}
+        print("%-42s %s %.4f ms [%.4f, %.4f]   %s %.4f ms [%.4f, %.4f]   mismatches %d" % (
+            name, ko, *(result["cases"][name][ko][k] for k in ("median_ms", "p10_ms", "p90_ms")),
+            kn, *(result["cases"][name][kn][k] for k in ("median_ms", "p10_ms", "p90_ms")), mismatches), flush=True)
+    result["cases"]["e_distorted_extract_handle_match_pose"]["matches"] = int(distorted_chain(W, D, m_f, ctx, True)[0])
+    # (f) 256 handles of one extract: 256 calls against one batched call, alternating; the time is taken inside build_handles
+    W["ex"].extract_dev(D["dev_batch"].data_ptr(), 752, 480, 752, 752 * 480, N_BATCH)
+    ctx.sync()
+    reps_f = max(20, a.reps // 10)
+    for _ in range(3):
+        build_handles(W, D, ctx, False); build_handles(W, D, ctx, True)
+    t_old, t_new, mismatches = [], [], 0
+    for r in range(reps_f):
+        for which in ((0, 1) if r % 2 == 0 else (1, 0)):
+            dt, res = build_handles(W, D, ctx, which == 1)
+            (t_old if which == 0 else t_new).append(dt)
+            if which == 0: ro = res
+            else: rn = res
+        mismatches += not same(ro, rn)
+    name = "f_build_256_handles"
+    result["cases"][name] = {"calls_256": stats(t_old), "one_batched_call": stats(t_new), "mismatching_reps": mismatches,
+                             "features_total": int(ro[-1])}
+    print("%-42s 256 calls %.4f ms [%.4f, %.4f]   batched %.4f ms [%.4f, %.4f]   mismatches %d" % (
+        name, *(result["cases"][name]["calls_256"][k] for k in ("median_ms", "p10_ms", "p90_ms")),
+        *(result["cases"][name]["one_batched_call"][k] for k in ("median_ms", "p10_ms", "p90_ms")), mismatches), flush=True)
+    last.close(); cur.close(); cur_pose.close(); D["last"].close()
     out = a.out or os.path.join(ROOT, "profiles", "%s_tracking_chain.json" % a.tag)
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
-    print(json.dumps({k: (v["host_buffers"]["median_ms"], v["handle"]["median_ms"], v["mismatching_reps"]) for k, v in result["cases"].items()}))
+    print(json.dumps({k: tuple(x["median_ms"] if isinstance(x, dict) else x for x in list(v.values())[:3]) for k, v in result["cases"].items()}))
     bad = sum(v["mismatching_reps"] for v in result["cases"].values())
     return 1 if bad else 0
 
