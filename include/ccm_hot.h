@@ -1339,6 +1339,61 @@ int ccm_optimize_essential_graph(ccm_ctx*, ccm_essential_graph*);
 int ccm_correct_map_points(ccm_ctx*, int n_points, double* points, const int32_t* ref_vertex, int n_vertices, const double* sim3_before,
                            const double* sim3_after);
 
+/* ---------------------------------------------------------------- local BA on the table
+ * Optimizer::LocalBundleAdjustmentClient (src/Optimizer.cpp:349-644) on keyframe handles and the map-point table: ccm_ba_solve
+ * whose observations (mvKeysUn[..].pt), information values (mvInvLevelSigma2[octave]) and points (GetWorldPos) are read where they
+ * already lie in device memory, and whose results are written back there.
+ *   Graph: keyframe k = handle kfs[k] with poses / fixed / intr as in ccm_ba_problem; point p = table slot slot[p]; point p owns
+ *   entries obs_first[p] .. obs_first[p+1] of obs_kf / obs_feat (the three lists of ccm_map_refresh).  Edge e of the graph is entry e
+ *   of those lists, point-major: the order of vpEdgesMono.  ccm_ba_result.edge_outlier, when given, is in that order.
+ *   Contract: the call returns what ccm_ba_solve returns -- poses, every field of ccm_ba_result and edge_outlier, bit for bit -- for
+ *   the array problem built from the same data by widening:
+ *     obs[e] = ((double)kx[f], (double)ky[f]), f = obs_feat[e], of handle kfs[obs_kf[e]];  info[e] = (double)inv_level_sigma2[oct[f]];
+ *     points[p][k] = (double)pos[slot[p]][k];  edge_pose = obs_kf, edge_point = the point index;  poses, fixed, intr, options passed on.
+ *   This holds for every graph the array route accepts: a point seen once, a keyframe without observations, a point with an empty
+ *   list (a vertex without edges).
+ *   Afterwards the device writes, and nothing of this is uploaded again:
+ *     pos[slot[p]][k] = (float)points[p][k] (the cast of Converter::toCvMat) for every listed point; the same values go to pos_out.
+ *     The other columns, the rows of other slots and the seen stamps are untouched; flags is neither read nor written.
+ *     For publish[k] != 0 the handle's Tcw / Ow (what ccm_frame_set_pose sets) become ccm_pose_to_camera(poses[k]), on the device and
+ *     in the handle's host copy; a handle without a keyframe block gets one, as ccm_frame_set_pose would give it.
+ *   When the solve made no LM iteration because the stop flag was up on entry (:531-533 returns before writing anything), table and
+ *   handles are left exactly as they were; pos_out then holds the table's values.
+ * ccm_pose_to_camera (host only, no context): Tcw = rows 0-2 of what ccm_pose_to_mat4f gives;
+ *   Ow[r] = (float)(((-(double)R[0][r]) * t0 - (double)R[1][r] * t1) - (double)R[2][r] * t2), R and t the float entries of Tcw widened
+ *   (-Rwc * tcw of KeyFrame::SetPose, src/KeyFrame.cpp:299-302).  One definition serves host and device (csrc/pose_camera.h).
+ * The call is a writer of the table's rows (a view on another thread sees the new positions in any call that starts after this one
+ * returns) and is ordered on the context's stream behind earlier ccm_frame_set_* / ccm_map_table_update / _refresh calls.  One
+ * page-locked staging copy goes up (pose7, intr, slots, the feature indices in the device's edge order, one small view of device
+ * pointers per keyframe, the level table, publish) beside the index arrays ccm_ba_solve uploads for any problem: nothing per edge or
+ * per point beyond 4-byte indices.  One download: pose7, the outlier bytes, pos_out.  No synchronisation beyond those of the LM loop
+ * and the final one.
+ * Errors are found on the host before anything is queued; table, handles and outputs are then untouched.  CCM_E_ARG: a NULL required
+ * array (kfs, poses, fixed, intr, inv_level_sigma2; slot, obs_first with points; obs_kf, obs_feat with observations), n_kf <= 0, a
+ * handle listed twice, a slot out of range or listed twice, obs_first not ascending from 0, a keyframe index outside [0, n_kf), a
+ * feature index outside that handle's [0, N) (the message names the point and the entry), n_levels below a listed handle's own
+ * n_levels or outside 1..CCM_MAX_LEVELS, a handle or table of another context.  CCM_E_STATE: a handle or table that outlived its
+ * context; a context with a communicator of more than one rank (the table route is unsharded). */
+typedef struct {
+    int32_t           n_kf;
+    ccm_frame* const* kfs;         /* [n_kf] keyframe handles, no handle twice */
+    double*           poses;       /* [n_kf][7] in/out, as ccm_ba_problem.poses */
+    const uint8_t*    fixed;       /* [n_kf] */
+    const double*     intr;        /* [n_kf][4] */
+    const uint8_t*    publish;     /* [n_kf] or NULL: write the optimised pose into this handle */
+    int32_t           n_points;
+    const int32_t*    slot;        /* [n_points] table slots, none twice */
+    const int32_t*    obs_first;   /* [n_points+1] ascending from 0 */
+    const int32_t*    obs_kf;      /* [obs_first[n_points]] index into kfs */
+    const int32_t*    obs_feat;    /* [obs_first[n_points]] feature index in that keyframe */
+    const float*      inv_level_sigma2; int32_t n_levels;   /* mvInvLevelSigma2 */
+    float*            pos_out;     /* optional [n_points][3]: the positions written to the table */
+} ccm_ba_table_problem;
+int ccm_ba_solve_table_frames(ccm_ctx*, ccm_map_table*, ccm_ba_table_problem*, const ccm_ba_options*, ccm_ba_result*);
+int ccm_pose_to_camera(const double* pose7, float* Tcw12, float* Ow3);
+/* Test tap: Tcw [12] and Ow [3] as the DEVICE copy of the handle holds them; synchronises.  CCM_E_STATE without a pose. */
+int ccm_frame_get_pose(ccm_frame*, float* Tcw12, float* Ow3);
+
 /* Multi-GPU GBA: every rank calls ccm_ba_solve with the
  * SAME poses and ITS OWN landmark partition (points + their edges); the reduced
  * camera system is summed with one RCCL all-reduce per LM trial.  One rank

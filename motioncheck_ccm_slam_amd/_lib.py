@@ -34,6 +34,7 @@ SYMBOLS = [
     "ccm_bow_vector", "ccm_bow_score_l1", "ccm_distinctive_descriptors", "ccm_optimize_sim3", "ccm_optimize_essential_graph", "ccm_correct_map_points",
     "ccm_ba_solve", "ccm_ba_landmark_cuts", "ccm_pose_optimize", "ccm_comm_unique_id", "ccm_comm_init", "ccm_comm_attach", "ccm_comm_destroy",
     "ccm_pose_from_mat4f", "ccm_pose_to_mat4f",
+    "ccm_ba_solve_table_frames", "ccm_pose_to_camera", "ccm_frame_get_pose",
     "ccm_frame_create", "ccm_frame_from_extract", "ccm_frame_destroy", "ccm_frame_size", "ccm_frame_set_map_points",
     "ccm_frame_get_map_points", "ccm_frame_debug_grid", "ccm_frame_search_by_projection", "ccm_frame_search_by_projection_frame",
     "ccm_frame_pose_optimize",
@@ -84,6 +85,12 @@ class BaProblem(C.Structure):
                 ("n_points", C.c_int), ("points", C.c_void_p),
                 ("n_edges", C.c_int), ("edge_pose", C.c_void_p), ("edge_point", C.c_void_p),
                 ("obs", C.c_void_p), ("info", C.c_void_p)]
+
+
+class BaTableProblem(C.Structure):                    # ccm_ba_table_problem
+    _fields_ = [("n_kf", C.c_int32), ("kfs", C.POINTER(C.c_void_p)), ("poses", C.c_void_p), ("fixed", C.c_void_p), ("intr", C.c_void_p),
+                ("publish", C.c_void_p), ("n_points", C.c_int32), ("slot", C.c_void_p), ("obs_first", C.c_void_p), ("obs_kf", C.c_void_p),
+                ("obs_feat", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("n_levels", C.c_int32), ("pos_out", C.c_void_p)]
 
 
 class PoseProblem(C.Structure):
@@ -362,6 +369,10 @@ def load():
     lib.ccm_comm_destroy.argtypes = [vp]
     lib.ccm_pose_from_mat4f.argtypes = [vp, vp]
     lib.ccm_pose_to_mat4f.argtypes = [vp, vp]
+    if hasattr(lib, "ccm_ba_solve_table_frames"):      # (an older build timed through CCM_HOT_LIB has no table route)
+        lib.ccm_ba_solve_table_frames.argtypes = [vp, vp, C.POINTER(BaTableProblem), C.POINTER(BaOptions), C.POINTER(BaResult)]
+        lib.ccm_pose_to_camera.argtypes = [vp, vp, vp]
+        lib.ccm_frame_get_pose.argtypes = [vp, vp, vp]
     lib.ccm_frame_create.argtypes = [vp, C.POINTER(FrameGrid), vp, C.POINTER(vp)]
     lib.ccm_frame_from_extract.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                                            C.POINTER(vp)]

@@ -14,6 +14,7 @@
 #include "ba_math.h"
 #include "ba_launch.h"
 #include "ba_index.h"
+#include "ba_table.h"
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -198,6 +199,7 @@ struct BaCall {
     ccm_ba_result local_res{};
     ccm_ba_result* res;
     uint8_t* outlier_out;
+    BaTableRoute* const route;             // nullptr: the caller's arrays are source and sink
     const hipStream_t st;
     const int ranks, rank;
     const BaEnv& env = ba_env();
@@ -239,8 +241,8 @@ struct BaCall {
     double* bp_alt = nullptr;
     std::vector<int> clock_phase;          // phase the interval ENDING at event i belongs to (-1: none)
 
-    BaCall(ccm_ctx* ctx, ccm_ba_problem* problem, const ccm_ba_options* options, ccm_ba_result* result)
-        : c(ctx), S(*ctx->ba), pb(problem), opt(options), res(result ? result : &local_res), outlier_out(res->edge_outlier), st(ctx->stream),
+    BaCall(ccm_ctx* ctx, ccm_ba_problem* problem, const ccm_ba_options* options, ccm_ba_result* result, BaTableRoute* table_route)
+        : c(ctx), S(*ctx->ba), pb(problem), opt(options), res(result ? result : &local_res), outlier_out(res->edge_outlier), route(table_route), st(ctx->stream),
           ranks(comm_ranks(ctx)), rank(comm_rank(ctx)), P(problem->n_poses), Lall(problem->n_points), Eall(problem->n_edges)
     {
         *res = ccm_ba_result{};
@@ -270,6 +272,7 @@ struct BaCall {
     int index_on_device();
     int index_on_host();
     int upload_problem();
+    int gather_problem();
     int reserve_workspace();
     int build_block_structure();
     int select_solver();
@@ -292,6 +295,7 @@ struct BaCall {
     // results
     int read_phase_timers();
     int download();
+    int publish();
 };
 
 void BaCall::lap(const char* what)
@@ -315,11 +319,11 @@ void BaCall::tick(int phase)
 }
 
 // argument checks; the context's BA state, created on first use
-int ba_begin(ccm_ctx* c, const ccm_ba_problem* pb, const ccm_ba_options* opt)
+int ba_begin(ccm_ctx* c, const ccm_ba_problem* pb, const ccm_ba_options* opt, bool values_on_device)
 {
     if (!c || !pb || !opt) return CCM_E_ARG;
-    if (pb->n_poses <= 0 || pb->n_points < 0 || pb->n_edges < 0 || !pb->poses || !pb->intr ||
-        (pb->n_points > 0 && !pb->points) || (pb->n_edges > 0 && (!pb->edge_pose || !pb->edge_point || !pb->obs || !pb->info)))
+    if (pb->n_poses <= 0 || pb->n_points < 0 || pb->n_edges < 0 || !pb->poses || !pb->intr || (pb->n_edges > 0 && (!pb->edge_pose || !pb->edge_point)) ||
+        (!values_on_device && ((pb->n_points > 0 && !pb->points) || (pb->n_edges > 0 && (!pb->obs || !pb->info)))))
         return ccm_fail(c, CCM_E_ARG, "bad BA problem");
     // (every edge's vertex indices are range-checked by the first pass over the edge list, before anything indexes with them)
     CCM_HIP(c, hipSetDevice(c->device));
@@ -360,7 +364,7 @@ int BaCall::vertex_maps_and_shard()
 int BaCall::index_on_device()
 {
     int rc;
-    if (!(ranks == 1 && Eall >= 400000 && nfree > 0 && Lall > 0 && !env.host_index_only)) return CCM_OK;
+    if (!(ranks == 1 && Eall >= 400000 && nfree > 0 && Lall > 0 && !env.host_index_only) || route) return CCM_OK;
     st_reads_host = true;
     if ((rc = upload(S.free_of, free_of.data(), P))) return rc;
     if ((rc = upload(S.edge_pose, pb->edge_pose, Eall))) return rc;
@@ -409,6 +413,7 @@ int BaCall::index_on_host()
 int BaCall::upload_problem()
 {
     int rc;
+    if (route) return gather_problem();
     st_reads_host = true;                                      // until reserve_workspace has synchronised
     if ((rc = upload(S.poses, pb->poses, 7 * (size_t)P))) return rc;
     if ((rc = upload(S.intr, pb->intr, 4 * (size_t)P))) return rc;
@@ -442,6 +447,37 @@ int BaCall::upload_problem()
         if ((rc = upload(S.pose_first, ix.pose_first.data(), nfree + 1))) return rc;
         if ((rc = upload(S.pose_edges, ix.pose_edges.get(), ix.n_pose_edges))) return rc;
     }
+    return CCM_OK;
+}
+
+// The table route's upload_problem: poses, intrinsics and the route's lists go up in its one staging copy, the index goes up as above,
+// and observations, information values and points are gathered on the device (k_ba_gather_table) where the array route uploads them.
+int BaCall::gather_problem()
+{
+    int rc;
+    Staging& G = *route->G;
+    BaTableArgs& A = route->A;
+    int32_t* feat = G.host<int32_t>(route->o_feat);
+    for (int k = 0; k < E; k++) feat[k] = route->obs_feat[ix.edge_id(k)];      // the device's edge order
+    if ((rc = G.upload(c, route->in_begin, route->in_end))) return rc;
+    CCM_RESERVE(c, S.poses, 7 * (size_t)P * 8); CCM_RESERVE(c, S.intr, 4 * (size_t)P * 8);
+    CCM_RESERVE(c, S.points, std::max<size_t>(3 * (size_t)L * 8, 16)); CCM_RESERVE(c, S.obs, std::max<size_t>(2 * (size_t)E * 8, 16));
+    CCM_RESERVE(c, S.info, std::max<size_t>((size_t)E * 8, 16));
+    CCM_HIP(c, hipMemcpyAsync(S.poses.p, G.dev<double>(route->o_pose_in), 7 * (size_t)P * 8, hipMemcpyDeviceToDevice, st));
+    CCM_HIP(c, hipMemcpyAsync(S.intr.p, G.dev<double>(route->o_intr), 4 * (size_t)P * 8, hipMemcpyDeviceToDevice, st));
+    st_reads_host = true;                                      // until reserve_workspace has synchronised
+    if ((rc = upload(S.pose_of_free, pose_of_free.data(), nfree))) return rc;
+    if ((rc = upload(S.free_of, free_of.data(), P))) return rc;
+    if ((rc = upload(S.edge_pose, ix.e_pose, E))) return rc;
+    if ((rc = upload(S.edge_point, ix.e_pt, E))) return rc;
+    if ((rc = upload(S.pt_first, ix.pt_first.data(), L + 1))) return rc;
+    if ((rc = upload(S.pose_first, ix.pose_first.data(), nfree + 1))) return rc;
+    if ((rc = upload(S.pose_edges, ix.pose_edges.get(), ix.n_pose_edges))) return rc;
+    A.P = P; A.L = L; A.E = E;
+    A.edge_pose = S.edge_pose.as<int>(); A.edge_feat = G.dev<int>(route->o_feat);
+    A.poses = S.poses.as<double>(); A.points = S.points.as<double>(); A.obs = S.obs.as<double>(); A.info = S.info.as<double>();
+    ba_launch_gather_table(st, A);
+    CCM_HIP(c, hipGetLastError());
     return CCM_OK;
 }
 
@@ -1107,6 +1143,7 @@ int BaCall::read_phase_timers()
 int BaCall::download()
 {
     int rc;
+    if (route) return publish();
     CCM_HIP(c, hipMemcpyAsync(pb->poses, D.poses, 7 * (size_t)P * 8, hipMemcpyDeviceToHost, st));
     if (ranks == 1) {
         // (a page-locked landing area + a threaded copy for pageable destinations was measured: 1.19 against 0.75 ms for config 5's 4.8 MB --
@@ -1151,13 +1188,38 @@ int BaCall::download()
     return CCM_OK;
 }
 
-// The stages of one call.  Every stage returns a CCM code (0 or negative) and nothing else: ccm_ba_solve cannot return a positive value.
-int ba_solve_impl(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res)
+// The table route's download: the points narrowed into the table and the published poses into their handles (k_ba_publish_table),
+// unless the stop flag ended the call before its first iteration (src/Optimizer.cpp:531-533 returns before writing anything); then
+// one download of poses, outlier flags and the positions as the table holds them.
+int BaCall::publish()
 {
-    RoctxRange roctx_("ccm_ba_solve");
     int rc;
-    if ((rc = ba_begin(c, pb, opt))) return rc;
-    BaCall k(c, pb, opt, res);
+    Staging& G = *route->G;
+    BaTableArgs& A = route->A;
+    route->wrote = !(res->stopped && res->iterations_done == 0);
+    A.poses = D.poses; A.points = D.points; A.scatter = route->wrote ? 1 : 0;
+    ba_launch_publish_table(st, A);
+    CCM_HIP(c, hipMemcpyAsync(G.dev<double>(route->o_pose_out), D.poses, 7 * (size_t)P * 8, hipMemcpyDeviceToDevice, st));
+    if (outlier_out && E > 0) {
+        ba_launch_pose_rt(st, D);
+        ba_launch_outliers(st, D, opt->outlier_chi2, G.dev<uint8_t>(route->o_outl));
+    }
+    CCM_HIP(c, hipGetLastError());
+    if ((rc = G.download(c, 0, route->res_end)) || (rc = G.wait(c))) return rc;
+    std::memcpy(pb->poses, G.host<double>(route->o_pose_out), 7 * (size_t)P * 8);
+    if (outlier_out) { const uint8_t* fl = G.host<uint8_t>(route->o_outl); for (int k = 0; k < E; k++) outlier_out[ix.edge_id(k)] = fl[k]; }
+    G.get(route->pos_out, route->o_pos, 3 * (size_t)L * 4);
+    lap("publish + download results");
+    return CCM_OK;
+}
+
+// The stages of one call.  Every stage returns a CCM code (0 or negative) and nothing else: ccm_ba_solve cannot return a positive value.
+int ba_solve_impl(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res, BaTableRoute* route)
+{
+    RoctxRange roctx_(route ? "ccm_ba_solve_table_frames" : "ccm_ba_solve");
+    int rc;
+    if ((rc = ba_begin(c, pb, opt, route != nullptr))) return rc;
+    BaCall k(c, pb, opt, res, route);
     if ((rc = k.vertex_maps_and_shard())) return rc;
     if ((rc = k.index_on_device())) return rc;
     if ((rc = k.index_on_host())) return rc;
@@ -1173,7 +1235,12 @@ int ba_solve_impl(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm
 }
 }  // namespace
 
+int ba_solve_table(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res, BaTableRoute* route)
+{
+    return ba_solve_impl(c, pb, opt, res, route);
+}
+
 extern "C" int ccm_ba_solve(ccm_ctx* c, ccm_ba_problem* pb, const ccm_ba_options* opt, ccm_ba_result* res)
 {
-    return ccm_guard(c, "ccm_ba_solve", [&] { return ba_solve_impl(c, pb, opt, res); });
+    return ccm_guard(c, "ccm_ba_solve", [&] { return ba_solve_impl(c, pb, opt, res, nullptr); });
 }

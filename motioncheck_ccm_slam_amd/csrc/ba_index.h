@@ -133,11 +133,13 @@ inline BaEdgeIndex ba_index_edges(const int32_t* edge_pose, const int32_t* edge_
     const int E = n_local;
     ix.direct = direct; ix.E = E;
     if (!direct) {
-        ix.e_pose_v.resize(E); ix.e_pt_v.resize(E); ix.e_obs_v.resize(2 * (size_t)E); ix.e_info_v.resize(E);
+        const bool values = obs && info;       // (the table route has neither on the host: the device gathers them in this order)
+        ix.e_pose_v.resize(E); ix.e_pt_v.resize(E);
+        if (values) { ix.e_obs_v.resize(2 * (size_t)E); ix.e_info_v.resize(E); }
         for (int k = 0; k < E; k++) {
             const int e = perm[k];
             ix.e_pose_v[k] = edge_pose[e]; ix.e_pt_v[k] = edge_point[e] - l0;
-            ix.e_obs_v[2 * k] = obs[2 * e]; ix.e_obs_v[2 * k + 1] = obs[2 * e + 1]; ix.e_info_v[k] = info[e];
+            if (values) { ix.e_obs_v[2 * k] = obs[2 * e]; ix.e_obs_v[2 * k + 1] = obs[2 * e + 1]; ix.e_info_v[k] = info[e]; }
         }
     }
     const int32_t* e_pose = ix.e_pose = direct ? edge_pose : ix.e_pose_v.data();

@@ -34,6 +34,10 @@ void ba_launch_diag(hipStream_t, const BaDev&, double* tmp_ll, double* pp_diag, 
 void ba_launch_outliers(hipStream_t, const BaDev&, double th, uint8_t* flag);
 void ba_launch_deactivate(hipStream_t, const BaDev&, const uint8_t* flag);
 
+// ---- ba_table.hip: the table route's source (obs, info, points from handles and table) and sink (table positions, handle poses)
+void ba_launch_gather_table(hipStream_t, const BaTableArgs&);
+void ba_launch_publish_table(hipStream_t, const BaTableArgs&);
+
 // ---- ba_structure.hip: scans and sorts, block structure of the reduced camera system
 size_t sp_scan_temp_bytes(size_t n);
 hipError_t sp_scan_int(hipStream_t, void* tmp, size_t tmp_bytes, const int* in, int* out, size_t n);

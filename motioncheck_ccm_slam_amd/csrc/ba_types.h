@@ -30,6 +30,23 @@ struct BaDev {
     double* Z; double* db; double* ce;
 };
 
+// ccm_ba_solve_table_frames (ba_table.hip).  What the two kernels read and write of keyframe k: device pointers its handle owns
+// (cam: Tcw [12] then Ow [3] of the handle's camera, nullptr for a handle that is not published)
+struct BaTableKf { const float* kx; const float* ky; const int* oct; float* cam; };
+struct BaTableArgs {
+    int P, L, E, n_levels;
+    const BaTableKf* kf;           // [P]
+    const int* slot;               // [L] table slot of landmark l
+    const int* edge_pose;          // [E] the device's edge order, as BaDev
+    const int* edge_feat;          // [E] feature index in that keyframe
+    const float* level_info;       // [n_levels] mvInvLevelSigma2
+    const uint8_t* publish;        // [P], read by the publish kernel
+    float* table_pos;              // [capacity][3] the table's pos column
+    double* poses; double* points; double* obs; double* info;      // BaDev's
+    float* pos_out;                // [L][3] the positions as the table holds them after the call
+    int scatter;                   // 0: the publish kernel fills pos_out only
+};
+
 // coarse level of the PCG preconditioner (ba_pcg_precond.hip); Aci == nullptr switches it off
 struct PcgCoarse {
     double* Aci;                   // [nc][nc] inverse of the coarse matrix, nc = 7 per aggregate

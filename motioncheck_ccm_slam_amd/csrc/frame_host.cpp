@@ -123,7 +123,7 @@ static KfLayout kf_layout(int n)
 }
 
 // The handle's second block, taken from the pool of keyframe parts on the first setter.
-static int kf_block(ccm_ctx* c, ccm_frame* f)
+int kf_block(ccm_ctx* c, ccm_frame* f)
 {
     if (f->kf_mem) return CCM_OK;
     FrameState& S = *frame_state(c);
@@ -557,6 +557,23 @@ int ccm_frame_set_pose(ccm_frame* f, const float* Tcw, const float* Ow)
         G.put(0, &m, sizeof(MapCam));
         if ((rc = G.upload(c, 0, sizeof(MapCam), f->d_cam))) return rc;
         f->cam = m; f->has_pose = true;
+        return CCM_OK;
+    });
+}
+
+// Test tap: Tcw and Ow as the DEVICE holds them (ccm_frame_set_pose uploads them, ccm_ba_solve_table_frames writes them there)
+int ccm_frame_get_pose(ccm_frame* f, float* Tcw, float* Ow)
+{
+    if (!f || !Tcw || !Ow) return CCM_E_ARG;
+    ccm_ctx* c = f->ctx;
+    if (!c) return CCM_E_STATE;
+    return ccm_guard(c, "ccm_frame_get_pose", [&]() -> int {
+        if (!f->has_pose || !f->d_cam) return ccm_fail(c, CCM_E_STATE, "ccm_frame_get_pose: no pose");
+        CCM_HIP(c, hipSetDevice(c->device));
+        MapCam m;
+        int rc = frame_fetch(c, &m, f->d_cam, sizeof(MapCam));
+        if (rc) return rc;
+        std::memcpy(Tcw, m.Tcw, 48); std::memcpy(Ow, m.Ow, 12);
         return CCM_OK;
     });
 }

@@ -77,6 +77,8 @@ int frame_check(ccm_ctx* c, const ccm_frame* f);
 // A handle passed under a name of the caller's (printf-style, e.g. "kfs[%d]", k): CCM_E_ARG for a null handle or one of another context,
 // `orphaned` (CCM_E_STATE, or CCM_E_ARG where the entry point has always answered so) for one that outlived its context
 int frame_named_check(ccm_ctx* c, const ccm_frame* f, int orphaned, const char* fn, const char* who, ...) __attribute__((format(printf, 5, 6)));
+// The handle's keyframe block (the layout above), taken from the pool on the first setter; nothing when it has one (frame_host.cpp)
+int kf_block(ccm_ctx* c, ccm_frame* f);
 // What a handle lacks to serve as a keyframe of CreateNewMapPoints ("bow", "camera", "pose"), or nullptr
 const char* frame_keyframe_lacks(const ccm_frame* f);
 

@@ -190,6 +190,12 @@ class DeviceFrame:
         T = np.ascontiguousarray(Tcw, "f4").reshape(12); O = np.ascontiguousarray(Ow, "f4").reshape(3)
         self.ctx.check(self.lib.ccm_frame_set_pose(C.c_void_p(self.handle), _lib.ptr(T), _lib.ptr(O)))
 
+    def pose(self):
+        """(Tcw [3][4], Ow [3]) as the DEVICE copy of the handle holds them (ccm_frame_get_pose, a test tap: synchronises)."""
+        T = np.zeros(12, "f4"); O = np.zeros(3, "f4")
+        self.ctx.check(self.lib.ccm_frame_get_pose(C.c_void_p(self.handle), _lib.ptr(T), _lib.ptr(O)))
+        return T.reshape(3, 4), O
+
     def bow(self):
         """(order, nodes, first) of the device-resident node directory (ccm_frame_debug_bow)."""
         order = np.zeros(max(self.n, 1), "i4"); nodes = np.zeros(max(self.n, 1), "i4"); first = np.zeros(self.n + 1, "i4")

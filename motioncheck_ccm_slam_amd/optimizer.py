@@ -96,8 +96,61 @@ def _solve(ctx, graph, iterations, huber, iterations2=0, stop_flag=None, pcg_tol
                 pcg_fallbacks=res.pcg_fallbacks, pcg_pipelined=res.pcg_pipelined)
 
 
+def _solve_table(table, kfs, lists, iterations, huber, iterations2=0, stop_flag=None, want_outliers=False, ctx=None):
+    """ccm_ba_solve_table_frames.  `lists` is a dict: poses [n_kf][7], fixed [n_kf], intr [n_kf][4], slot [n_points], obs_first
+    [n_points + 1], obs_kf / obs_feat [obs_first[-1]], inv_level_sigma2 [n_levels] (float32) and optionally publish [n_kf].  Returns
+    the dict of `_solve` without `points`, plus `pos` [n_points][3] float32: the positions the table holds after the call."""
+    ctx = ctx or table.ctx
+    lib = _lib.load()
+    a = np.ascontiguousarray
+    poses = a(lists["poses"], "f8").reshape(-1, 7).copy(); n_kf = len(poses)
+    if len(kfs) != n_kf:
+        raise ValueError("%d handles for %d poses" % (len(kfs), n_kf))
+    fixed = a(lists["fixed"], np.uint8).reshape(-1); intr = a(lists["intr"], "f8").reshape(-1, 4)
+    slot = a(lists["slot"], "i4").reshape(-1); n = len(slot)
+    first = a(lists["obs_first"], "i4").reshape(-1); okf = a(lists["obs_kf"], "i4").reshape(-1); ofeat = a(lists["obs_feat"], "i4").reshape(-1)
+    if len(fixed) != n_kf or len(intr) != n_kf or len(first) != n + 1 or len(okf) != len(ofeat) or (n and len(okf) < first[-1]):
+        raise ValueError("fixed / intr need n_kf entries, obs_first n_points + 1 and obs_kf / obs_feat obs_first[-1] each")
+    is2 = a(lists["inv_level_sigma2"], "f4").reshape(-1)
+    publish = None if lists.get("publish") is None else a(lists["publish"], np.uint8).reshape(-1)
+    if publish is not None and len(publish) != n_kf:
+        raise ValueError("publish needs n_kf entries")
+    n_edges = int(first[-1]) if n else 0
+    pos = np.zeros((max(n, 1), 3), "f4")
+    handles = (C.c_void_p * max(n_kf, 1))(*[k.handle for k in kfs])
+    pad = lambda v: v if len(v) else np.zeros(1, v.dtype)  # noqa: E731  (an empty array may have no address)
+    p = _lib.ptr
+    keep = [pad(slot), pad(okf), pad(ofeat)]
+    pb = _lib.BaTableProblem(n_kf, handles, p(poses), p(fixed), p(intr), p(publish), n, p(keep[0]), p(first), p(keep[1]), p(keep[2]),
+                             p(is2), len(is2), p(pos))
+    outl = np.zeros(max(n_edges, 1), np.uint8) if want_outliers else None
+    flag = _stop_flag_view(stop_flag)
+    opt = BaOptions(int(iterations), float(huber), int(iterations2), CHI2_MONO, p(flag), 0.0)
+    res = BaResult()
+    res.edge_outlier = p(outl) if want_outliers else None
+    ctx.check(lib.ccm_ba_solve_table_frames(ctx.handle, C.c_void_p(table.handle), C.byref(pb), C.byref(opt), C.byref(res)))
+    return dict(poses=poses, pos=pos[:n], outlier=outl[:n_edges] if want_outliers else None,
+                iterations_done=res.iterations_done, trials=res.trials, chi2_initial=res.chi2_initial,
+                chi2_final=res.chi2_final, lambda_final=res.lambda_final, stopped=bool(res.stopped),
+                t_linearize=res.t_linearize, t_schur=res.t_schur, t_solve=res.t_solve, t_update=res.t_update,
+                schur_blocks=res.schur_blocks, schur_pairs=res.schur_pairs, pcg_iterations=res.pcg_iterations,
+                pcg_fallbacks=res.pcg_fallbacks, pcg_pipelined=res.pcg_pipelined)
+
+
 class Optimizer:
     """Static-method style like the reference; `ctx` selects the GPU context (default: device 0)."""
+
+    @staticmethod
+    def LocalBundleAdjustmentClientTable(table, kfs, graph_lists, pbStopFlag=None, ctx=None):
+        """LocalBundleAdjustmentClient on a `tracking.MapPointTable` and `frame.DeviceFrame` keyframes (ccm_ba_solve_table_frames):
+        observations, information values and points are read on the device, the optimised positions are written into the table and
+        the poses of the keyframes `graph_lists["publish"]` marks into their handles.  See `_solve_table` for the lists and the result."""
+        return _solve_table(table, kfs, graph_lists, 5, TH_HUBER_2D_LOCAL, 10, pbStopFlag, want_outliers=True, ctx=ctx)
+
+    @staticmethod
+    def BundleAdjustmentClientTable(table, kfs, graph_lists, nIterations: int = 5, pbStopFlag=None, bRobust: bool = True, ctx=None):
+        """BundleAdjustmentClient on the same inputs: one stage, no outlier output."""
+        return _solve_table(table, kfs, graph_lists, nIterations, TH_HUBER_2D_GLOBAL if bRobust else 0.0, 0, pbStopFlag, ctx=ctx)
 
     @staticmethod
     def BundleAdjustmentClient(graph, nIterations: int = 5, pbStopFlag=None, bRobust: bool = True, ctx=None, workspace=None):
@@ -203,6 +256,13 @@ def pose_to_mat4f(pose: np.ndarray) -> np.ndarray:
     pose = np.ascontiguousarray(pose, np.float64); out = np.zeros((4, 4), np.float32)
     _lib.load().ccm_pose_to_mat4f(_lib.ptr(pose), _lib.ptr(out))
     return out
+
+
+def pose_to_camera(pose: np.ndarray):
+    """(Tcw [3][4], Ow [3]) float32 of an SE3Quat pose, as a keyframe stores them (ccm_pose_to_camera)."""
+    pose = np.ascontiguousarray(pose, np.float64); T = np.zeros(12, np.float32); O = np.zeros(3, np.float32)
+    _lib.load().ccm_pose_to_camera(_lib.ptr(pose), _lib.ptr(T), _lib.ptr(O))
+    return T.reshape(3, 4), O
 
 
 def pose_delta(p_a: np.ndarray, p_b: np.ndarray) -> np.ndarray:

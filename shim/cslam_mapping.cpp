@@ -247,6 +247,22 @@ void LocalMapping::CreateNewMapPoints()
 
 }  // namespace cslam
 
+// fuse_steps.h: the cache above for the local bundle adjustment on the table (cslam_optimizer.cpp), which runs on this thread
+ccm_frame* ccm_shim::local_keyframe_handle(const cslam::ORBmatcher::kfptr& pKF)
+{
+    using namespace cslam;
+    return ccm_shim::keyframe_handles_on() ? keyframe_handle(pKF) : nullptr;
+}
+
+void ccm_shim::local_keyframe_pose_published(const cslam::ORBmatcher::kfptr& pKF, uint64_t stamp_before)
+{
+    using namespace cslam;
+    KfHandles& H = kf_handles();
+    const auto it = H.of.find(std::make_pair(pKF->mId.first, pKF->mId.second));
+    if (it == H.of.end() || stamp_before == 0 || it->second.stamp != stamp_before) return;      // not up to date before: sent again on its next use
+    it->second.stamp = ccm_shim::keyframe_stamp(pKF->mId.first, pKF->mId.second);
+}
+
 // The first Fuse loop of LocalMapping::SearchInNeighbors (src/Mapping.cpp:499-504) on keyframe handles.  First choice: ONE
 // ccm_fuse_select_table_frames projects the current keyframe's map points into every target keyframe, gates and selects on the
 // device, reading the points from the map-point table (ccm_shim::fuse_select_on_table, fuse_steps.h).  Where that is not possible --

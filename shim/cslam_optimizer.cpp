@@ -17,11 +17,13 @@
 #include <vector>
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <list>
 #include <map>
 #include "ccm_shim.h"
 #include "flat_graph.h"
+#include "fuse_steps.h"
 
 namespace cslam {
 namespace {
@@ -47,6 +49,41 @@ struct CvAccess {
     }
 };
 typedef ccm_shim::FlatGraph<Optimizer::kfptr, Optimizer::mpptr, CvAccess> FlatGraph;
+
+// CCM_SHIM_LOCAL_BA_TABLE=0: the local bundle adjustment keeps the array route (A/B timing of the two routes)
+bool local_ba_table_on()
+{
+    static const bool on = !(getenv("CCM_SHIM_LOCAL_BA_TABLE") && atoi(getenv("CCM_SHIM_LOCAL_BA_TABLE")) == 0);
+    return on;
+}
+
+// What the table route of the local bundle adjustment needs beside the flat graph (INTEGRATION.md "Local BA on the table"): the calling
+// thread's handle on the map-point table, a slot for every local map point, a handle with a camera for every keyframe of the graph.
+// false = something is missing and nothing was touched: the caller takes the array route.
+struct LocalBaTable {
+    ccm_map_table* table = nullptr;
+    std::vector<ccm_frame*> kfs;
+    std::vector<int32_t> slot, obs_first;
+    std::vector<uint8_t> publish;
+    std::vector<float> pos;
+
+    bool prepare(const FlatGraph& g, size_t n_local)
+    {
+        if (!local_ba_table_on() || g.kfs.empty() || g.kfs[0]->mvInvLevelSigma2.size() > CCM_MAX_LEVELS) return false;
+        slot.resize(g.mps.size());
+        for (size_t r = 0; r < g.mps.size(); r++) if ((slot[r] = ccm_shim::map_slot_of(g.mps[r])) < 0) return false;
+        kfs.resize(g.kfs.size());
+        for (size_t r = 0; r < g.kfs.size(); r++) if (!(kfs[r] = ccm_shim::local_keyframe_handle(g.kfs[r]))) return false;
+        if (!(table = ccm_shim::map_table_here())) return false;              // (flushed: the rows hold what GetWorldPos() gives)
+        obs_first.assign(g.mps.size() + 1, 0);                                // the edges are point-major: add_map_point appends them
+        for (size_t e = 0; e < g.edge_point.size(); e++) obs_first[g.edge_point[e] + 1]++;
+        for (size_t r = 0; r < g.mps.size(); r++) obs_first[r + 1] += obs_first[r];
+        publish.assign(g.kfs.size(), 0);
+        for (size_t r = 0; r < n_local; r++) publish[r] = 1;                  // the local keyframes; the fixed ones do not move
+        pos.resize(3 * g.mps.size() + 3);
+        return true;
+    }
+};
 
 cv::Mat pose_mat(const double* p7)
 {
@@ -156,12 +193,26 @@ void Optimizer::LocalBundleAdjustmentClient(kfptr pKF, bool* pbStopFlag, mapptr 
     // ccm_ba_solve runs that schedule in one call and skips the second stage when the stop flag came up during the first (bDoMore).
     // (An edge whose map point another thread has culled in between keeps level 0 and its kernel in the reference, :555-556; here
     // every edge is classified.)
-    ccm_ba_problem pb = g.problem();
+    // Two routes to the same solve (ccm_hot.h "local BA on the table": bit for bit the same poses, results and outlier flags).  On the
+    // table: observations, information values and positions are read where they lie on the device, the new positions are written into
+    // the table's rows and the local keyframes' poses into their handles.  Otherwise: the arrays of the flat graph, both ways.
     std::vector<uint8_t> outlier(g.edge_pose.size() + 1, 0);
     ccm_ba_options opt{5, (double)(float)std::sqrt(5.991), 10, 5.991, reinterpret_cast<const volatile uint8_t*>(pbStopFlag), /*pcg_tol=*/0.0};
     ccm_ba_result res{};
     res.edge_outlier = outlier.data();
-    if (ccm_ba_solve(ccm_shim::ctx(), &pb, &opt, &res)) throw estd::infrastructure_ex();
+    LocalBaTable T;
+    const bool on_table = T.prepare(g, n_local);
+    if (on_table) {
+        const std::vector<float>& is2 = g.kfs[0]->mvInvLevelSigma2;          // one client's keyframes share the extractor's tables
+        ccm_ba_table_problem tp{(int32_t)g.kfs.size(), T.kfs.data(), g.poses.data(), g.fixed.data(), g.intr.data(), T.publish.data(),
+                                (int32_t)g.mps.size(), T.slot.data(), T.obs_first.data(), g.edge_pose.data(), g.edge_feat.data(),
+                                is2.data(), (int32_t)is2.size(), T.pos.data()};
+        if (ccm_ba_solve_table_frames(ccm_shim::ctx(), T.table, &tp, &opt, &res)) throw estd::infrastructure_ex();
+    } else {
+        ccm_ba_problem pb = g.problem();
+        if (ccm_ba_solve(ccm_shim::ctx(), &pb, &opt, &res)) throw estd::infrastructure_ex();
+    }
+    const bool published = on_table && !(res.stopped && res.iterations_done == 0);   // (stopped on entry: nothing was written)
 
     // observations to erase: the same test on the final state (:577-595)
     std::vector<std::pair<kfptr, mpptr> > vToErase;
@@ -174,13 +225,51 @@ void Optimizer::LocalBundleAdjustmentClient(kfptr pKF, bool* pbStopFlag, mapptr 
 
     if (SysState != eSystemState::SERVER)                                                         // :597-599
         while (!pMap->LockMapUpdate()) { usleep(params::timings::miLockSleep); }
+    if (on_table) {
+        // The table's rows hold the new positions already, so the points take them FIRST, without the put hook (MapPoint::StoreWorldPos):
+        // the erasures below carry that hook (EraseObservation), and a row it queues reads GetWorldPos() -- with the old position still
+        // in the point, the next flush would write it over the device's new one.  map_positions_on_device then brings the table's row
+        // copies, and any row another thread queued for these slots since the solve, to the same positions.
+        std::vector<mpptr> moved;
+        moved.reserve(g.mps.size());
+        for (size_t r = 0; r < g.mps.size(); r++) {
+            const mpptr& pMP = g.mps[r];
+            if (pMP->isBad()) continue;
+            cv::Mat Xw(3, 1, CV_32F);
+            for (int i = 0; i < 3; i++) Xw.at<float>(i) = T.pos[3 * r + i];
+            pMP->StoreWorldPos(Xw);
+            moved.push_back(pMP);
+        }
+        ccm_shim::map_positions_on_device(moved);
+    }
     for (const auto& er : vToErase) {                                                             // :601-610
         er.first->EraseMapPointMatch(er.second);
         er.second->EraseObservation(er.first);
     }
     for (size_t r = 0; r < n_local; r++) {                                                        // :614-624 (local keyframes only: the fixed ones did not move)
+        const uint64_t stamp = published ? ccm_shim::keyframe_stamp(g.kfs[r]->mId.first, g.kfs[r]->mId.second) : 0;
         g.kfs[r]->SetPose(pose_mat(&g.poses[7 * r]), false);
         g.kfs[r]->mbUpdatedByServer = false;
+        if (published) ccm_shim::local_keyframe_pose_published(g.kfs[r], stamp);                  // the handle holds this pose already
+    }
+    if (on_table) {
+        // :626-644 with the rows and the points' positions already written (above): ONE refresh after the erasures -- they changed
+        // observation lists, reference keyframes and bad flags -- computes normal and depth of the points still good on the device
+        // from the table's positions (pos = NULL) and stores them (MapPoint::StoreRefreshed).
+        std::vector<mpptr> good;
+        good.reserve(g.mps.size());
+        for (size_t r = 0; r < g.mps.size(); r++) {
+            const mpptr& pMP = g.mps[r];
+            if (pMP->isBad()) {
+                if (pMap->GetMpPtr(pMP->mId)) throw estd::infrastructure_ex();
+                continue;
+            }
+            good.push_back(pMP);
+        }
+        if (!ccm_shim::refresh_map_points(good, CCM_MPR_NORMAL_DEPTH, &ccm_shim::local_keyframe_handle, /*pos_on_device=*/true))
+            for (const mpptr& pMP : good) pMP->UpdateNormalAndDepth();                            // a handle went missing: point by point, rows by the hook
+        if (SysState != eSystemState::SERVER) pMap->UnLockMapUpdate();
+        return;
     }
     for (size_t r = 0; r < g.mps.size(); r++) {                                                   // :626-644
         const mpptr& pMP = g.mps[r];

@@ -144,7 +144,30 @@ public:
     // it returns false and touches nothing before the tracking thread has made the table, when the view cannot be attached, or when a
     // keyframe has no handle in this thread's context.  Points the call cannot express stay with the reference's functions: a bad point
     // (both return at once) and a point whose observing keyframes are all bad (normal / 0).
-    bool refresh(const std::vector<mpptr>& pts, int what, KeyframeHandleOf handle_of)
+    // After ccm_ba_solve_table_frames has written the positions of pts into the device rows and the caller has stored the same values
+    // in the points (MapPoint::StoreWorldPos, no put): the row copies kept here take them, and so does every row already QUEUED for
+    // one of these slots -- a row queued by any thread between the solve and the store snapshotted the old position, and the next
+    // flush would send it over the new one.  Rows queued from here on read the new position from the point itself.
+    void positions_on_device(const std::vector<mpptr>& pts)
+    {
+        std::lock_guard<std::mutex> lock(mMutex);
+        std::map<int, const float*> moved;                                       // slot -> its row copy's pos
+        for (const mpptr& pMP : pts) {
+            if (!pMP) continue;
+            const auto it = mSlotOf.find(pMP->mId);
+            if (it == mSlotOf.end()) continue;
+            const cv::Mat P = pMP->GetWorldPos();
+            Row& row = mRows[it->second];
+            for (int k = 0; k < 3; k++) row.pos[k] = P.at<float>(k);
+            moved[it->second] = row.pos;
+        }
+        for (Row& q : mQueue) {
+            const auto it = moved.find(q.slot);
+            if (it != moved.end() && (q.flags & CCM_MP_LIVE)) for (int k = 0; k < 3; k++) q.pos[k] = it->second[k];
+        }
+    }
+    // pos_on_device (after ccm_ba_solve_table_frames and positions_on_device): the rows hold the positions already, so none travels.
+    bool refresh(const std::vector<mpptr>& pts, int what, KeyframeHandleOf handle_of, bool pos_on_device = false)
     {
         ccm_ctx* c = ctx();
         if (!exists()) return false;                                             // the tracking thread's first flush makes the table
@@ -199,8 +222,8 @@ public:
             for (int k = 0; k < 3; k++) pos[3 * (size_t)i + k] = P.at<float>(k);
             flags[i] = CCM_MP_LIVE | (use[i]->Observations() > 0 ? CCM_MP_HAS_OBS : 0);
         }
-        const ccm_map_refresh u{n, slot.data(), pos.data(), flags.data(), (int32_t)kfs.size(), kfs.data(), obs_first.data(), obs_kf.data(),
-                                obs_feat.data(), ref_kf.data(), ref_feat.data(), what};
+        const ccm_map_refresh u{n, slot.data(), pos_on_device ? nullptr : pos.data(), flags.data(), (int32_t)kfs.size(), kfs.data(), obs_first.data(),
+                                obs_kf.data(), obs_feat.data(), ref_kf.data(), ref_feat.data(), what};
         ccm_map_refresh_result r{best.data(), normal.data(), mn.data(), mx.data()};
         if (ccm_map_table_refresh(c, table, &u, &r)) return false;
         std::lock_guard<std::mutex> lock(mMutex);
@@ -319,10 +342,12 @@ private:
     int32_t mZero = 0;
 };
 
-bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of)
+bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of, bool pos_on_device)
 {
-    return MapTable::get().refresh(pts, what, handle_of);
+    return MapTable::get().refresh(pts, what, handle_of, pos_on_device);
 }
+
+void map_positions_on_device(const std::vector<ORBmatcher::mpptr>& pts) { MapTable::get().positions_on_device(pts); }
 
 int map_slot_of(const ORBmatcher::mpptr& pMP) { return pMP ? MapTable::get().slot_of(pMP) : -1; }
 

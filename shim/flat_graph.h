@@ -29,6 +29,7 @@ struct FlatGraph {
     std::vector<uint8_t> fixed;
     std::vector<int32_t> edge_pose, edge_point;
     std::vector<KfPtr> edge_kf;                        // edge -> observing keyframe (vpEdgeKFMono of the local BA)
+    std::vector<int32_t> edge_feat;                    // edge -> feature index in that keyframe (the table route's obs_feat)
 
     void add_keyframe(const KfPtr& pKF, bool is_fixed)
     {
@@ -70,7 +71,7 @@ struct FlatGraph {
             double xy[2], inv_sigma2;
             Access::keypoint(pKF, ob.second, xy, &inv_sigma2);
             edge_pose.push_back(it->second); edge_point.push_back(row);
-            edge_kf.push_back(pKF);
+            edge_kf.push_back(pKF); edge_feat.push_back((int32_t)ob.second);
             obs.push_back(xy[0]); obs.push_back(xy[1]);
             info.push_back(inv_sigma2);                                      // Identity * invSigma2 (:769-770)
         }

@@ -84,8 +84,24 @@ void fuse_into_targets(const std::vector<ORBmatcher::kfptr>& vpTargetKFs, const 
 // It works through the calling thread's own handle on the table (a view where another thread made it, ccm_map_table_attach).
 // false = nothing was done (there is no table yet, the view cannot be attached, or a handle is missing): the caller then runs the
 // reference's two functions point by point, whose hooks queue the rows.
+// pos_on_device: the table's rows already hold the points' positions (ccm_ba_solve_table_frames wrote them, the caller has stored them
+// with MapPoint::StoreWorldPos and told the table with map_positions_on_device): the call goes with pos = NULL.
 using KeyframeHandleOf = ccm_frame* (*)(const ORBmatcher::kfptr&);
-bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of);
+bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, KeyframeHandleOf handle_of, bool pos_on_device = false);
+
+// LocalMapping's cache of keyframe handles (defined in cslam_mapping.cpp; LocalMapping's thread only), for the local bundle adjustment
+// on the table (cslam_optimizer.cpp).  local_keyframe_handle: the handle of pKF in that thread's context with its map-point ids,
+// camera and pose up to date, or nullptr (handles switched off, or a call failed).  local_keyframe_pose_published: the device has
+// written pKF's optimised pose into the handle and KeyFrame::SetPose has stored the same pose; stamp_before = the keyframe's stamp
+// (ccm_shim::keyframe_stamp) read just before that SetPose.  A handle that was up to date then stays so, and no pose is uploaded.
+ccm_frame* local_keyframe_handle(const ORBmatcher::kfptr& pKF);
+void local_keyframe_pose_published(const ORBmatcher::kfptr& pKF, uint64_t stamp_before);
+
+// After ccm_ba_solve_table_frames: the device rows of pts hold new positions and the caller has stored the same values in the points
+// with MapPoint::StoreWorldPos (no put).  Brings the table's row copies and every row ALREADY QUEUED for these slots to those positions
+// (ccm_shim::MapTable::positions_on_device, cslam_tracking.cpp), so that no flush writes an old position over a new one.  To be called
+// before anything that may queue rows of these points (the erase loop's EraseObservation carries the put hook).
+void map_positions_on_device(const std::vector<ORBmatcher::mpptr>& pts);
 
 // The slot of pMP in the calling process's map-point table, or -1 (ccm_shim::MapTable::slot_of, cslam_tracking.cpp).  A keyframe handle
 // that is to serve fuse_select_on_table carries these in its map-point ids.
