@@ -610,13 +610,13 @@ int ccm_search_by_bow_frames(ccm_ctx*, const ccm_frame* kf1, int n_kf2, ccm_fram
  * Table views.  The reference runs Tracking, LocalMapping, LoopFinder, MapMatcher and MapMerger on threads of their own, each with a
  * context of its own, and all of them work on one map.  ccm_map_table_attach gives a context a handle of its own (a view) on the
  * ROWS of an existing table; a view is used exactly like a table, with the view's context, by every call that takes a table:
- * ccm_map_table_update, _set_order, _fetch, _refresh, ccm_frame_search_local_points, ccm_frame_pose_optimize_table,
+ * ccm_map_table_update, _set_order, _fetch, _refresh, _correct_frames, ccm_frame_search_local_points, ccm_frame_pose_optimize_table,
  * ccm_frame_track_motion_model, ccm_fuse_select_table_frames, ccm_search_by_sim3_table_frames and
  * ccm_search_by_projection_table_frames.  The frame handles and vocabularies such a call names belong to that same context.
  *   Shared between the handles of the same rows: the columns pos, normal, min_dist, max_dist, desc and flags, and the capacity.
  *   Owned by each handle: the `seen` column and its stamp (ccm_map_table_fetch returns the calling handle's), the visiting order
  *   (ccm_map_table_set_order), and the scratch of the Fuse and ComputeSim3 calls.
- *   Visibility: rows written through one handle (ccm_map_table_update, ccm_map_table_refresh) are seen by every call through any
+ *   Visibility: rows written through one handle (ccm_map_table_update, _refresh, _correct_frames) are seen by every call through any
  *   handle that starts after the writing call has returned, also where that call returned without synchronising (_update, and
  *   _refresh without a result): the later call's stream is made to wait for the write.
  *   Concurrency: calls on handles of the same rows may be made from different threads at the same time, each thread with its own
@@ -718,6 +718,79 @@ typedef struct {
 } ccm_map_refresh;
 typedef struct { int32_t* best; float* normal; float* min_dist; float* max_dist; } ccm_map_refresh_result;  /* each [n] / [n][3], each optional */
 int ccm_map_table_refresh(ccm_ctx*, ccm_map_table*, const ccm_map_refresh*, ccm_map_refresh_result* /* or NULL */);
+
+/* Loop and merge corrections on the table: the step that moves keyframes and their map points, on keyframe handles and the table.
+ *   CCM_MC_SIM3 + CCM_MC_IN_ORDER     LoopFinder::CorrectLoop (src/LoopFinder.cpp:543-613) and MapMerger::MergeMaps
+ *                                     (src/MapMerger.cpp:349-392): for every corrected keyframe, in the iteration order of
+ *                                     CorrectedSim3, the map points it owns become correctedSwi.map(Siw.map(P)) and
+ *                                     UpdateNormalAndDepth runs on each at once; then the keyframe's pose becomes [R | t/s]
+ *   CCM_MC_SIM3 + CCM_MC_POSES_FIRST  the tail of OptimizeEssentialGraphLoopClosure / MapFusion (src/Optimizer.cpp:1279-1330): every
+ *                                     keyframe takes its pose, then every point moves through its reference keyframe and
+ *                                     UpdateNormalAndDepth runs
+ *   CCM_MC_RIGID                      the tail of the global BA (src/MapMerger.cpp:637-753 and its twin in LoopFinder): points outside
+ *                                     the BA move as Rwc * (Rcw_before * P + tcw_before) + twc
+ * Keyframes: kfs[0 .. n_moved) take a new pose, in the caller's iteration order; kfs[n_moved ..) are only read (their camera centres
+ * and, as reference keyframes, their octaves and scale factors).  Points: row slot[p] is moved by keyframe owner[p] (an index into
+ * the moved keyframes); owner[p] == -1 leaves the row exactly as it is.
+ *   Position, CCM_MC_SIM3: pos[slot[p]] = (float)Q, Q = what ccm_correct_map_points gives for the point (double)pos[slot[p]] with
+ *   ref_vertex = owner[p] and the same two Sim3 arrays, bit for bit (the widening is Converter::toVector3d, the narrowing
+ *   Converter::toCvMat).
+ *   Position, CCM_MC_RIGID, with Tb the owner handle's device pose when the call is made, Ta / Oa its Tcw_after / Ow_after:
+ *     Xc[r] = (float)(((double)Tb[4r]*P[0] + (double)Tb[4r+1]*P[1] + (double)Tb[4r+2]*P[2]) + (double)Tb[4r+3])
+ *     P'[r] = (float)(((double)Ta[r]*Xc[0] + (double)Ta[4+r]*Xc[1] + (double)Ta[8+r]*Xc[2]) + (double)Oa[r])
+ *   that is Rwc * Xc + twc of GetPoseInverse (src/KeyFrame.cpp:299-306) as a float cv::Mat expression; nothing is fused.
+ *   Poses: every moved keyframe's handle takes the new pose, on the device and in the handle's host copy; a handle without a keyframe
+ *   block gets one, as ccm_frame_set_pose would give it.  SIM3: the pose is ccm_pose_to_camera((qx,qy,qz,qw, tx*(1.0/s), ty*(1.0/s),
+ *   tz*(1.0/s))) of sim3_after (eigt *= (1./s), then toCvSE3).  RIGID: the given Tcw_after / Ow_after.
+ *   Normal and depth (only with obs_first != NULL, the lists of ccm_map_refresh): for every point with owner >= 0 and at least one
+ *   observation, exactly the arithmetic of CCM_MPR_NORMAL_DEPTH above on the new position.  The Ow of observing keyframe j and of the
+ *   reference keyframe is chosen by `order`:
+ *     CCM_MC_POSES_FIRST  the new Ow for every j < n_moved, the handle's Ow for the others
+ *     CCM_MC_IN_ORDER     keyframe k's points are refreshed before k's own SetPose and after that of every earlier keyframe: the new
+ *                         Ow iff j < owner[p], the handle's (old) Ow for j >= owner[p] and for every unmoved keyframe
+ *   A point with owner >= 0 and no observations moves and keeps its normal, min_dist and max_dist.
+ *   Untouched bit for bit: flags, desc, the seen stamps, and every row not listed or with owner == -1.
+ * The outputs (each optional) report the listed rows as they stand after the call, rows with owner == -1 included.
+ * The call is a writer of the table's rows (a view on another thread sees the new rows in any call that starts after this one
+ * returns) and is ordered on the context's stream behind earlier ccm_frame_set_* / ccm_map_table_update / _refresh calls.  One
+ * page-locked staging copy goes up: the Sim3 pairs or poses, slots, owners, the index lists and one small view of device pointers per
+ * keyframe; nothing per point beyond 4-byte indices.  Three launches: the new poses into staging, the points (which read the
+ * handles' old poses), the publish into the handles.  One download, and only if an output is given; otherwise the call neither
+ * downloads nor synchronises.
+ * Errors are found on the host before anything is queued; table, handles and outputs are then untouched.  CCM_E_ARG: a NULL required
+ * array for the chosen transform (sim3_before / sim3_after or Tcw_after / Ow_after with n_moved > 0; slot and owner with points;
+ * ref_kf / ref_feat with obs_first; obs_kf / obs_feat when there are observations), an unknown transform or order, n_moved outside
+ * [0, n_kf], a handle twice, a slot out of range or twice, an owner outside [-1, n_moved), a non-finite Sim3 entry or s <= 0 in
+ * sim3_after, the list errors of ccm_map_refresh (the message names the point and the entry), a handle or table of another context.
+ * CCM_E_STATE: a handle or table that outlived its context; RIGID with an owner handle that has no pose; with lists, for the points
+ * that move, an observed handle without a pose or a reference handle without a pose or a camera.
+ * n_points == 0 still publishes the poses; n_moved == 0 with no points is CCM_OK. */
+enum { CCM_MC_SIM3 = 0, CCM_MC_RIGID = 1 };          /* transform */
+enum { CCM_MC_POSES_FIRST = 0, CCM_MC_IN_ORDER = 1 }; /* order */
+typedef struct {
+    int32_t           n_kf;
+    ccm_frame* const* kfs;          /* [n_kf] every keyframe the call names; no handle twice */
+    int32_t           n_moved;      /* kfs[0 .. n_moved) take a new pose, in the caller's iteration order; 0 <= n_moved <= n_kf */
+    int32_t           transform;    /* CCM_MC_SIM3 or CCM_MC_RIGID */
+    int32_t           order;        /* CCM_MC_POSES_FIRST or CCM_MC_IN_ORDER */
+    const double*     sim3_before;  /* SIM3: [n_moved][8] qx,qy,qz,qw,tx,ty,tz,s  (g2oSiw / vScw) */
+    const double*     sim3_after;   /* SIM3: [n_moved][8] CorrectedSiw */
+    const float*      Tcw_after;    /* RIGID: [n_moved][12], rows of [Rcw|tcw], as ccm_frame_set_pose */
+    const float*      Ow_after;     /* RIGID: [n_moved][3] */
+    int32_t           n_points;
+    const int32_t*    slot;         /* [n_points], each in [0, capacity), no slot twice */
+    const int32_t*    owner;        /* [n_points] index into the moved keyframes, or -1: the row is left exactly as it is */
+    const int32_t*    obs_first;    /* [n_points+1] the lists of ccm_map_refresh, or NULL: no normal / depth */
+    const int32_t*    obs_kf;       /* [obs_first[n_points]] index into kfs */
+    const int32_t*    obs_feat;     /* [obs_first[n_points]] feature index in that keyframe */
+    const int32_t*    ref_kf;       /* [n_points] mpRefKF as an index into kfs */
+    const int32_t*    ref_feat;     /* [n_points] observations[pRefKF] */
+    float*            pos_out;      /* optional [n_points][3]: the rows after the call */
+    float*            normal_out;   /* optional [n_points][3] */
+    float*            min_dist_out; /* optional [n_points] */
+    float*            max_dist_out; /* optional [n_points] */
+} ccm_map_correct;
+int ccm_map_table_correct_frames(ccm_ctx*, ccm_map_table*, const ccm_map_correct*);
 
 /* Tracking::SearchLocalPoints (src/Tracking.cpp:860-922) with Frame::isInFrustum (src/Frame.cpp:139-198), MapPoint::PredictScale
  * (src/MapPoint.cpp:854-869) and ORBmatcher::SearchByProjection(Frame&, map points, th) (ORBmatcher.cpp:71-148) on a frame handle

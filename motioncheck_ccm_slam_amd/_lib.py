@@ -40,7 +40,7 @@ SYMBOLS = [
     "ccm_frame_pose_optimize",
     "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
-    "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_map_table_attach", "ccm_map_table_handles", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
+    "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_map_table_correct_frames", "ccm_map_table_attach", "ccm_map_table_handles", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
     "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model",
     "ccm_search_by_sim3_table_frames", "ccm_search_by_projection_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
@@ -180,6 +180,18 @@ class MapRefresh(C.Structure):
 
 class MapRefreshResult(C.Structure):
     _fields_ = [("best", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p)]
+
+
+MC_SIM3, MC_RIGID = 0, 1                       # CCM_MC_* of include/ccm_hot.h: transform
+MC_POSES_FIRST, MC_IN_ORDER = 0, 1             # order
+
+
+class MapCorrect(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("kfs", C.POINTER(C.c_void_p)), ("n_moved", C.c_int32), ("transform", C.c_int32), ("order", C.c_int32),
+                ("sim3_before", C.c_void_p), ("sim3_after", C.c_void_p), ("Tcw_after", C.c_void_p), ("Ow_after", C.c_void_p),
+                ("n_points", C.c_int32), ("slot", C.c_void_p), ("owner", C.c_void_p), ("obs_first", C.c_void_p), ("obs_kf", C.c_void_p),
+                ("obs_feat", C.c_void_p), ("ref_kf", C.c_void_p), ("ref_feat", C.c_void_p), ("pos_out", C.c_void_p),
+                ("normal_out", C.c_void_p), ("min_dist_out", C.c_void_p), ("max_dist_out", C.c_void_p)]
 
 
 class SlpParams(C.Structure):
@@ -405,6 +417,7 @@ def load():
     lib.ccm_map_table_set_order.argtypes = [vp, vp, C.c_int, vp]
     lib.ccm_map_table_fetch.argtypes = [vp, vp, C.c_int] + [vp] * 8
     lib.ccm_map_table_refresh.argtypes = [vp, vp, C.POINTER(MapRefresh), C.POINTER(MapRefreshResult)]
+    lib.ccm_map_table_correct_frames.argtypes = [vp, vp, C.POINTER(MapCorrect)]
     lib.ccm_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(SlpParams), C.POINTER(SlpResult)]
     lib.ccm_frame_search_local_points_timing.argtypes = [vp, vp]
     lib.ccm_frame_pose_optimize_table.argtypes = [vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]

@@ -1,5 +1,6 @@
 // mpt_internal.h -- what the host translation units of the map-point table share: mpt_host.cpp (the table itself and its refresh),
-// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_track_host.cpp (SearchLocalPoints,
+// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_correct_host.cpp (loop and
+// merge corrections), mpt_track_host.cpp (SearchLocalPoints,
 // TrackWithMotionModel) and frame_pose_host.cpp (the pose on table points).  Every call stages through the frame handles' block (FrameState::stage, frame_internal.h).
 #pragma once
 #include "frame_internal.h"
@@ -12,7 +13,7 @@
 // The rows of a table: the shared columns pos | normal | min_dist | max_dist | desc | flags (and, in the same block, the `seen` column
 // of the handle that created them).  Every handle on them (ccm_map_table_create, ccm_map_table_attach) holds one reference; the memory
 // goes with the last one.  Handles of several contexts, each on a thread of its own, may name the same rows:
-//   mu       a call whose kernels write a shared column (ccm_map_table_update, _refresh) holds it exclusively from entry to return, a
+//   mu       a call whose kernels write a shared column (ccm_map_table_update, _refresh, _correct_frames) holds it exclusively from entry to return, a
 //            call that only reads them holds it shared; the handle count changes under the exclusive lock
 //   written  "last unsynchronised write": recorded on the writer's stream when a writing call returns with its kernels still queued
 //            and the rows have more than one handle; a call of another context makes its stream wait for it before it queues anything

@@ -1,4 +1,5 @@
-// mpt_types.h -- kernel argument structures and launchers of the map-point table, shared by mpt_kernels.hip and mpt_host.cpp.
+// mpt_types.h -- kernel argument structures and launchers of the map-point table, shared by the mpt_*.hip kernel files and the
+// mpt_*_host.cpp files that launch them.
 #pragma once
 #include <cstdint>
 #include <hip/hip_runtime.h>
@@ -38,6 +39,26 @@ struct MptRefreshArgs {
     const MptKfView* view;
     int* best; float* normal; float* min_dist; float* max_dist;      // per listed point, in the call's result block
 };
+
+// ---- mpt_correct_kernels.hip: ccm_map_table_correct_frames
+// What the three kernels read and write of keyframe k: cam = &d_cam->Tcw of the handle, Tcw [12] then Ow [3] (nullptr for a handle
+// without a keyframe block, which the host lets no point read); oct and sf as in MptKfView.
+struct MptCorrectKf { float* cam; const int* oct; const float* sf; int n_levels; int pad_; };
+#define MPC_CAM_STRIDE 16  // floats per moved keyframe in cam_new: Tcw [12], Ow [3], one unused
+
+struct MptCorrectArgs {
+    int n_points, n_moved, transform, order;     // CCM_MC_*
+    const int* slot; const int* owner;
+    const int* obs_first; const int* obs_kf; const int* obs_feat; const int* ref_kf; const int* ref_feat;   // obs_first == nullptr: no normal / depth
+    const double* sim3_before; const double* sim3_after;        // SIM3: [n_moved][8]
+    const float* Tcw_after; const float* Ow_after;              // RIGID: [n_moved][12], [n_moved][3]
+    const MptCorrectKf* kf;                                     // [n_kf], the moved ones first
+    float* cam_new;                                             // [n_moved][MPC_CAM_STRIDE], written by k_mpt_correct_poses
+    float* pos; float* normal; float* min_dist; float* max_dist;     // per listed point, in the call's result block
+};
+// k_mpt_correct_poses (the moved keyframes' new Tcw / Ow into cam_new), k_mpt_correct (the points, reading the handles' old cameras)
+// and k_mpt_correct_publish (cam_new into the handles), in this order on one stream
+void mpt_launch_correct(hipStream_t, const MptCorrectArgs&, const MptTable&);
 
 // ccm_fuse_select_table_frames.  What k_fuse_project reads of keyframe k: the caller's pose and camera and the handle's map-point ids.
 struct FuseView { float Tcw[12], Ow[3], fx, fy, cx, cy, min_x, max_x, min_y, max_y; int n; int pad_; const int* mp_id; };

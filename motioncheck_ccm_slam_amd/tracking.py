@@ -109,6 +109,53 @@ class MapPointTable:
         self.ctx.check(self.lib.ccm_map_table_refresh(self.ctx.handle, C.c_void_p(self.handle), C.byref(u), C.byref(r)))
         return {k: v[:n] for k, v in out.items()}
 
+    def correct(self, kfs, n_moved, slot, owner, sim3_before=None, sim3_after=None, Tcw_after=None, Ow_after=None, in_order=False, lists=None,
+                fetch=True):
+        """The keyframe and map-point correction of a loop closure or a map merge on the table (ccm_map_table_correct_frames).
+        kfs[:n_moved] (DeviceFrame) take a new pose, in the caller's iteration order; the others are only read.  Row slot[p] is moved
+        by keyframe owner[p], or left exactly as it is for owner[p] == -1.  With sim3_before / sim3_after [n_moved][8] the points become
+        correctedSwi.map(Siw.map(P)) and the poses [R | t/s] (MC_SIM3); with Tcw_after [n_moved][12] / Ow_after [n_moved][3] the points
+        move rigidly from the handles' present poses to the given ones (MC_RIGID).  lists = (obs_first, obs_kf, obs_feat, ref_kf,
+        ref_feat) as in `refresh`: UpdateNormalAndDepth on every moved point, with each keyframe's old or new camera centre as the
+        reference's loop order has it -- in_order=False: every pose is set before any point (the essential-graph tail), in_order=True:
+        keyframe by keyframe, the points before their keyframe's own SetPose (CorrectLoop, MergeMaps).  `DeviceFrame.pose` reports the
+        new poses afterwards.  Returns a dict: pos, normal, min_dist, max_dist of the listed rows after the call; with fetch=False
+        nothing is read back, the call does not synchronise and returns None."""
+        a = np.ascontiguousarray
+        slot = a(slot, "i4").reshape(-1); owner = a(owner, "i4").reshape(-1); n = len(slot); nm = int(n_moved)
+        if len(owner) != n:
+            raise ValueError("owner needs one entry per slot")
+        rigid = Tcw_after is not None or Ow_after is not None
+        if rigid and (sim3_before is not None or sim3_after is not None):
+            raise ValueError("either the Sim3 pairs or Tcw_after / Ow_after")
+
+        def col(v, t, shape):
+            if v is None:
+                return None
+            v = a(v, t)
+            if v.size != shape[0] * shape[1]:
+                raise ValueError("array of shape %s, expected %s" % (v.shape, shape))
+            return v.reshape(shape)
+        pad = lambda v: v if v is None or len(v) else np.zeros(1, v.dtype)  # noqa: E731  (an empty array may have no address)
+        sb, sa = pad(col(sim3_before, "f8", (nm, 8))), pad(col(sim3_after, "f8", (nm, 8)))
+        Ta, Oa = pad(col(Tcw_after, "f4", (nm, 12))), pad(col(Ow_after, "f4", (nm, 3)))
+        first = okf = ofeat = rkf = rfeat = None
+        if lists is not None:
+            first, okf, ofeat, rkf, rfeat = [a(v, "i4").reshape(-1) for v in lists]
+            if len(first) != n + 1 or len(okf) != len(ofeat) or (n and len(okf) < first[-1]) or len(rkf) != n or len(rfeat) != n:
+                raise ValueError("obs_first needs n + 1 entries, obs_kf / obs_feat obs_first[n] each, ref_kf / ref_feat n each")
+            okf, ofeat, rkf, rfeat = pad(okf), pad(ofeat), pad(rkf), pad(rfeat)
+        handles = (C.c_void_p * max(len(kfs), 1))(*[k.handle for k in kfs])
+        m = max(n, 1)
+        out = dict(pos=np.zeros((m, 3), "f4"), normal=np.zeros((m, 3), "f4"), min_dist=np.zeros(m, "f4"), max_dist=np.zeros(m, "f4")) if fetch else {}
+        g = lambda k: _lib.ptr(out[k]) if fetch else None  # noqa: E731
+        u = _lib.MapCorrect(len(kfs), handles, nm, _lib.MC_RIGID if rigid else _lib.MC_SIM3, _lib.MC_IN_ORDER if in_order else _lib.MC_POSES_FIRST,
+                            _lib.ptr(sb), _lib.ptr(sa), _lib.ptr(Ta), _lib.ptr(Oa), n, _lib.ptr(pad(slot)), _lib.ptr(pad(owner)),
+                            _lib.ptr(first), _lib.ptr(okf), _lib.ptr(ofeat), _lib.ptr(rkf), _lib.ptr(rfeat),
+                            g("pos"), g("normal"), g("min_dist"), g("max_dist"))
+        self.ctx.check(self.lib.ccm_map_table_correct_frames(self.ctx.handle, C.c_void_p(self.handle), C.byref(u)))
+        return {k: v[:n] for k, v in out.items()} if fetch else None
+
     def close(self):
         if getattr(self, "handle", None):
             self.lib.ccm_map_table_destroy(C.c_void_p(self.handle))

@@ -491,6 +491,21 @@ void essential_graph(Optimizer::mapptr pMap, Optimizer::kfptr pLoopKF, Optimizer
         const cv::Mat P3Dw = pMP->GetWorldPos();
         for (int k = 0; k < 3; k++) pts[3 * (size_t)i + k] = P3Dw.at<float>(k);
     }
+    // On the table (ccm_hot.h "loop and merge corrections on the table", CCM_MC_POSES_FIRST: every pose above is set before any point):
+    // the positions are read and written where they lie on the device, UpdateNormalAndDepth runs there, the handles take the new
+    // poses, and only indices and the Sim3 pairs travel.  Needs this thread's handle on the table, a slot for every point and a handle
+    // of this thread for every keyframe with a vertex (ccm_shim::thread_keyframe_handles, bound by the thread that closes loops);
+    // otherwise nothing is touched and the arrays below do the same work.
+    {
+        std::vector<kfptr> moved((size_t)eg.n_vertices);
+        for (size_t i = 0; i < vpKFs.size(); i++) if (vertex_of[vpKFs[i]->mUniqueId] >= 0) moved[vertex_of[vpKFs[i]->mUniqueId]] = vpKFs[i];
+        std::vector<mpptr> on_table;
+        std::vector<int32_t> owner;
+        for (int i = 0; i < nMP; i++) if (ref[i] >= 0) { on_table.push_back(vpMPs[i]); owner.push_back(ref[i]); }
+        if (ccm_shim::thread_keyframe_handles() &&
+            ccm_shim::correct_on_table(moved, sim3_before.data(), sim3.data(), on_table, owner, CCM_MC_POSES_FIRST, &ccm_shim::thread_keyframe_handle))
+            return;
+    }
     if (ccm_correct_map_points(ccm_shim::ctx(), nMP, pts.data(), ref.data(), eg.n_vertices, sim3_before.data(), sim3.data()))
         throw estd::infrastructure_ex();
     for (int i = 0; i < nMP; i++) {

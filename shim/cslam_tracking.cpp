@@ -18,8 +18,12 @@
 #include <cslam/Optimizer.h>
 #include <cslam/Converter.h>
 #include <cslam/ORBmatcher.h>
+#include <algorithm>
+#include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
+#include <set>
 #include "ccm_shim.h"
 #include "fuse_steps.h"
 
@@ -243,6 +247,83 @@ public:
         }
         return true;
     }
+    // The map-point half of a loop or merge correction in one ccm_map_table_correct_frames (fuse_steps.h, correct_on_table): moved[k]
+    // takes the pose of sim3_after[k], point pts[i] moves through keyframe owner[i] and UpdateNormalAndDepth runs on it with the camera
+    // centres `order` prescribes.  The observation lists are built as refresh() builds them; keyframes that are only observed follow
+    // the moved ones in the handle list.  The one download gives what the MapPoint objects keep: MapPoint::StoreWorldPos and
+    // MapPoint::StoreRefreshed assign it without put(), and the row copies kept here are brought up to date instead.  A point whose
+    // observing keyframes are all bad moves on the device and runs the reference's UpdateNormalAndDepth afterwards (normal / 0), whose
+    // hook queues its row.  The keyframes' host poses stay with the caller (KeyFrame::SetPose; the handles hold the new poses already).
+    // false = nothing was done: no table in this thread, a point without a slot, a keyframe without a handle, or the call failed.
+    bool correct(const std::vector<cslam::Tracking::kfptr>& moved, const double* sim3_before, const double* sim3_after, const std::vector<mpptr>& pts,
+                 const std::vector<int32_t>& owner, int order, KeyframeHandleOf handle_of)
+    {
+        ccm_ctx* c = ctx();
+        if (!exists() || pts.size() != owner.size()) return false;
+        typedef cslam::Tracking::kfptr kfptr;
+        std::vector<int32_t> obs_first(1, 0), obs_kf, obs_feat, ref_kf, ref_feat;
+        std::vector<ccm_frame*> kfs;
+        std::map<cslam::idpair, int> kf_index;
+        auto index_of = [&](const kfptr& pKF) -> int {
+            const auto it = kf_index.find(pKF->mId);
+            if (it != kf_index.end()) return it->second;
+            ccm_frame* h = handle_of(pKF);
+            if (!h) return -1;
+            kf_index[pKF->mId] = (int)kfs.size(); kfs.push_back(h);
+            return (int)kfs.size() - 1;
+        };
+        for (const kfptr& pKF : moved) if (index_of(pKF) < 0) return false;
+        if (kfs.size() != moved.size()) return false;                            // a keyframe twice
+        const int n = (int)pts.size(), n_moved = (int)moved.size();
+        std::vector<uint8_t> all_bad(n, 0);
+        for (int i = 0; i < n; i++) {
+            const mpptr& pMP = pts[i];
+            if (!pMP || pMP->isBad() || owner[i] < 0 || owner[i] >= n_moved || slot_of(pMP) < 0) return false;
+            const std::map<kfptr, size_t> obs = pMP->GetObservations();
+            const size_t mark = obs_kf.size();
+            for (const auto& kv : obs) {
+                if (kv.first->isBad()) continue;
+                const int k = index_of(kv.first);
+                if (k < 0) return false;
+                obs_kf.push_back(k); obs_feat.push_back((int32_t)kv.second);
+            }
+            int kr = 0, fr = 0;
+            if (obs_kf.size() > mark) {
+                const kfptr pRef = pMP->GetReferenceKeyFrame();
+                if ((kr = index_of(pRef)) < 0) return false;
+                const auto itr = obs.find(pRef);
+                fr = itr == obs.end() ? 0 : (int32_t)itr->second;                // observations[pRefKF] (src/MapPoint.cpp:813)
+            } else all_bad[i] = obs.empty() ? 0 : 1;
+            ref_kf.push_back(kr); ref_feat.push_back(fr);
+            obs_first.push_back((int32_t)obs_kf.size());
+        }
+        ccm_map_table* table = flush();                                          // rows queued earlier must not land behind the correction
+        if (!table) return false;
+        std::vector<int32_t> slot(std::max(n, 1));
+        for (int i = 0; i < n; i++) slot[i] = slot_of(pts[i]);
+        std::vector<float> pos(3 * (size_t)n + 3), normal(3 * (size_t)n + 3), mn(n + 1), mx(n + 1);
+        const ccm_map_correct u{(int32_t)kfs.size(), kfs.data(), n_moved, CCM_MC_SIM3, order, sim3_before, sim3_after, nullptr, nullptr, n, slot.data(),
+                                owner.data(), obs_first.data(), obs_kf.data(), obs_feat.data(), ref_kf.data(), ref_feat.data(), pos.data(),
+                                normal.data(), mn.data(), mx.data()};
+        if (ccm_map_table_correct_frames(c, table, &u)) return false;
+        {
+            std::lock_guard<std::mutex> lock(mMutex);
+            for (int i = 0; i < n; i++) {
+                cv::Mat Xw = (cv::Mat_<float>(3, 1) << pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2]);
+                pts[i]->StoreWorldPos(Xw);
+                Row& row = mRows[slot[i]];
+                for (int k = 0; k < 3; k++) row.pos[k] = pos[3 * (size_t)i + k];
+                for (Row& q : mQueue) if (q.slot == slot[i] && (q.flags & CCM_MP_LIVE)) for (int k = 0; k < 3; k++) q.pos[k] = row.pos[k];
+                if (obs_first[i + 1] == obs_first[i]) continue;
+                cv::Mat Nv = (cv::Mat_<float>(3, 1) << normal[3 * (size_t)i], normal[3 * (size_t)i + 1], normal[3 * (size_t)i + 2]);
+                pts[i]->StoreRefreshed(cv::Mat(), Nv, mn[i], mx[i]);             // empty Mat: the descriptor stays
+                for (int k = 0; k < 3; k++) row.normal[k] = normal[3 * (size_t)i + k];
+                row.min_dist = mn[i]; row.max_dist = mx[i];
+            }
+        }
+        for (int i = 0; i < n; i++) if (all_bad[i]) pts[i]->UpdateNormalAndDepth();
+        return true;
+    }
     // ORBmatcher::Fuse up to the selection for every (keyframe, point) pair in one ccm_fuse_select_table_frames (fuse_steps.h,
     // fuse_select_on_table).  As refresh(): on any thread through its own handle, rows queued earlier are flushed first, and on any
     // failure nothing of the caller's is touched.
@@ -348,6 +429,45 @@ bool refresh_map_points(const std::vector<ORBmatcher::mpptr>& pts, int what, Key
 }
 
 void map_positions_on_device(const std::vector<ORBmatcher::mpptr>& pts) { MapTable::get().positions_on_device(pts); }
+
+bool correct_on_table(const std::vector<ORBmatcher::kfptr>& moved, const double* sim3_before, const double* sim3_after,
+                      const std::vector<ORBmatcher::mpptr>& pts, const std::vector<int32_t>& owner, int order, KeyframeHandleOf handle_of)
+{
+    return MapTable::get().correct(moved, sim3_before, sim3_after, pts, owner, order, handle_of);
+}
+
+bool correct_keyframes_on_table(const std::vector<KeyframeCorrection>& corrected, const std::function<bool(const ORBmatcher::mpptr&)>& tagged,
+                                const std::function<void(const ORBmatcher::mpptr&)>& tag, KeyframeHandleOf handle_of)
+{
+    const int n_kf = (int)corrected.size();
+    std::vector<ORBmatcher::kfptr> moved(n_kf);
+    std::vector<double> before(8 * (size_t)n_kf + 8), after(8 * (size_t)n_kf + 8);
+    std::vector<ORBmatcher::mpptr> pts;
+    std::vector<int32_t> owner;
+    std::set<cslam::idpair> taken;                                               // what the reference's tag does within one pass
+    for (int k = 0; k < n_kf; k++) {
+        moved[k] = corrected[k].pKF;
+        std::memcpy(&before[8 * (size_t)k], corrected[k].before, 64); std::memcpy(&after[8 * (size_t)k], corrected[k].after, 64);
+        const std::vector<ORBmatcher::mpptr> vpMPsi = corrected[k].pKF->GetMapPointMatches();
+        for (const ORBmatcher::mpptr& pMPi : vpMPsi) {                           // src/LoopFinder.cpp:577-585
+            if (!pMPi || pMPi->isBad() || tagged(pMPi) || !taken.insert(pMPi->mId).second) continue;
+            pts.push_back(pMPi); owner.push_back(k);
+        }
+    }
+    if (!MapTable::get().correct(moved, before.data(), after.data(), pts, owner, CCM_MC_IN_ORDER, handle_of)) return false;
+    for (const ORBmatcher::mpptr& pMP : pts) tag(pMP);                           // :594-595
+    for (int k = 0; k < n_kf; k++) {                                             // :599-608; the handle holds this pose already
+        const double* S = corrected[k].after;
+        const double is = 1.0 / S[7];
+        const double pose7[7] = { S[0], S[1], S[2], S[3], S[4] * is, S[5] * is, S[6] * is };
+        float Tcw[12], Ow[3];
+        ccm_pose_to_camera(pose7, Tcw, Ow);
+        cv::Mat T = cv::Mat::eye(4, 4, CV_32F);
+        for (int r = 0; r < 3; r++) for (int cc = 0; cc < 4; cc++) T.at<float>(r, cc) = Tcw[4 * r + cc];
+        corrected[k].pKF->SetPose(T, true);
+    }
+    return true;
+}
 
 int map_slot_of(const ORBmatcher::mpptr& pMP) { return pMP ? MapTable::get().slot_of(pMP) : -1; }
 

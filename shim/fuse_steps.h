@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 namespace ccm_shim {
@@ -102,6 +103,36 @@ void local_keyframe_pose_published(const ORBmatcher::kfptr& pKF, uint64_t stamp_
 // (ccm_shim::MapTable::positions_on_device, cslam_tracking.cpp), so that no flush writes an old position over a new one.  To be called
 // before anything that may queue rows of these points (the erase loop's EraseObservation carries the put hook).
 void map_positions_on_device(const std::vector<ORBmatcher::mpptr>& pts);
+
+// Loop and merge corrections on the table (ccm_map_table_correct_frames; defined in cslam_tracking.cpp, INTEGRATION.md "Loop and merge
+// corrections on the table").  Both work through the calling thread's handle on the table and keyframe handles of that thread's
+// context (handle_of), and return false with nothing touched when there is no table here, a point has no slot, a handle is missing
+// or the call fails: the caller then runs the reference's loop.
+// correct_on_table: moved[k] takes the pose [R | t/s] of sim3_after[k] in its HANDLE (the caller makes KeyFrame::SetPose on the host
+// object), pts[i] -- not bad, with a slot -- becomes correctedSwi.map(Siw.map(P)) through keyframe owner[i] in [0, moved.size()), and
+// UpdateNormalAndDepth runs on it with the camera centres `order` (CCM_MC_POSES_FIRST / CCM_MC_IN_ORDER) prescribes.  The points take
+// the results with MapPoint::StoreWorldPos / StoreRefreshed (no put), and the table's row copies and queued rows follow, so that no
+// flush writes an old position over a new one.
+bool correct_on_table(const std::vector<ORBmatcher::kfptr>& moved, const double* sim3_before /* [n][8] */, const double* sim3_after /* [n][8] */,
+                      const std::vector<ORBmatcher::mpptr>& pts, const std::vector<int32_t>& owner, int order, KeyframeHandleOf handle_of);
+// The loop of LoopFinder::CorrectLoop (src/LoopFinder.cpp:568-613) and MapMerger::MergeMaps (src/MapMerger.cpp:349-392) in one call:
+// walks `corrected` in the caller's order (the iteration order of CorrectedSim3), gives each map point that is not bad and not yet
+// tagged -- tagged(pMP), e.g. mCorrectedByKF_LC == mpCurrentKF->mId -- to the FIRST keyframe that carries it, issues the
+// CCM_MC_IN_ORDER call, and afterwards tags the points (tag(pMP)), stores positions, normals and depths in them, and makes
+// pKF->SetPose([R | t/s], true) on every keyframe.  before / after = g2oSiw / g2oCorrectedSiw as qx,qy,qz,qw,tx,ty,tz,s.
+// UpdateConnections and the caller's bookkeeping (sChangedKFs) stay with the caller.
+struct KeyframeCorrection { ORBmatcher::kfptr pKF; double before[8], after[8]; };
+bool correct_keyframes_on_table(const std::vector<KeyframeCorrection>& corrected, const std::function<bool(const ORBmatcher::mpptr&)>& tagged,
+                                const std::function<void(const ORBmatcher::mpptr&)>& tag, KeyframeHandleOf handle_of);
+// The keyframe handles of a thread that is not LocalMapping's (LoopFinder, MapMerger), for the entry points that have no handle_of
+// argument of their own (Optimizer::OptimizeEssentialGraph*, cslam_optimizer.cpp): the thread binds its lookup once, and
+// thread_keyframe_handle gives the handle or nullptr (nothing bound, or the lookup has none).
+inline KeyframeHandleOf& thread_keyframe_handles()
+{
+    static thread_local KeyframeHandleOf f = nullptr;
+    return f;
+}
+inline ccm_frame* thread_keyframe_handle(const ORBmatcher::kfptr& pKF) { return thread_keyframe_handles() ? thread_keyframe_handles()(pKF) : nullptr; }
 
 // The slot of pMP in the calling process's map-point table, or -1 (ccm_shim::MapTable::slot_of, cslam_tracking.cpp).  A keyframe handle
 // that is to serve fuse_select_on_table carries these in its map-point ids.
