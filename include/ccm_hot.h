@@ -167,6 +167,12 @@ int ccm_debug_fast_score(const uint8_t* vr /* n x 17: v, ring */, int n, int t_l
  * Writes at most max rows of six int32 -- run, wave, lane, row, dword, pos0 (tile offset of the item's first pixel) -- run by
  * run, and returns the number of items (>= 0, it may exceed max) or an error. */
 int ccm_debug_fc_items(int pitch, int bh, int dw_lo, int dw_hi, int32_t* out /* max x 6 */, int max);
+/* Test tap of the descriptor kernel's orientation and steering: for each of n moment pairs (m01, m10) of IC_Angle, one wave runs the
+ * device functions the kernel runs and writes the angle in degrees (cv::fastAtan2), (a, b) = (cos, sin) of it as the kernel steers
+ * with them, and the rounded offsets (dx, dy) of the pattern's 512 sample points in pattern order (ORBextractor.cpp:104-110).
+ * Synchronises internally. */
+int ccm_debug_od_steer(ccm_ctx*, const int32_t* m01, const int32_t* m10, int n,
+                       float* angle_deg, float* ab /* n x 2 */, int8_t* offs /* n x 512 x 2 */);
 
 /* ------------------------------------------------------------------ matcher
  * ORBmatcher::DescriptorDistance (cslam/src/ORBmatcher.cpp:1653-1669): host helper. */

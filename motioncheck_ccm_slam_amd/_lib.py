@@ -28,7 +28,7 @@ SYMBOLS = [
     "ccm_host_register", "ccm_host_unregister", "ccm_profile_enable", "ccm_profile_read",
     "ccm_orb_tables", "ccm_orb_level_sizes", "ccm_orb_extract", "ccm_orb_extract_dev", "ccm_orb_fetch",
     "ccm_orb_result_dev", "ccm_orb_debug_level", "ccm_orb_debug_candidates", "ccm_orb_debug_lane_plan", "ccm_debug_fast_score", "ccm_debug_fc_items",
-    "ccm_descriptor_distance", "ccm_hamming_match", "ccm_hamming_match_dev", "ccm_debug_fp4_tile", "ccm_ratio_test", "ccm_match_bow",
+    "ccm_debug_od_steer", "ccm_descriptor_distance", "ccm_hamming_match", "ccm_hamming_match_dev", "ccm_debug_fp4_tile", "ccm_ratio_test", "ccm_match_bow",
     "ccm_window_candidates", "ccm_search_by_projection", "ccm_search_by_projection_frame", "ccm_search_for_initialization", "ccm_fuse_select", "ccm_fuse_select_batch", "ccm_search_by_sim3", "ccm_search_by_projection_sim3", "ccm_search_by_projection_sim3_batch",
     "ccm_search_for_triangulation", "ccm_voc_create", "ccm_voc_destroy", "ccm_voc_words", "ccm_voc_transform", "ccm_voc_transform_dev",
     "ccm_bow_vector", "ccm_bow_score_l1", "ccm_distinctive_descriptors", "ccm_optimize_sim3", "ccm_optimize_essential_graph", "ccm_correct_map_points",
@@ -344,6 +344,8 @@ def load():
         lib.ccm_debug_fast_score.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     if hasattr(lib, "ccm_debug_fc_items"):             # (likewise)
         lib.ccm_debug_fc_items.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    if hasattr(lib, "ccm_debug_od_steer"):             # (likewise)
+        lib.ccm_debug_od_steer.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     lib.ccm_descriptor_distance.argtypes = [vp, vp]
     lib.ccm_hamming_match.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.ccm_hamming_match_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, vp, C.c_int, C.c_size_t, C.c_int,

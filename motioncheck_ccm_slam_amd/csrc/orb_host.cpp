@@ -740,4 +740,29 @@ int ccm_debug_fc_items(int pitch, int bh, int dw_lo, int dw_hi, int32_t* out, in
     });
 }
 
+int ccm_debug_od_steer(ccm_ctx* c, const int32_t* m01, const int32_t* m10, int n, float* angle_deg, float* ab, int8_t* offs)
+{
+    return ccm_guard(c, "ccm_debug_od_steer", [&]() -> int {
+        if (!c) return CCM_E_ARG;
+        if (n < 0 || n > (1 << 20) || (n > 0 && (!m01 || !m10 || !angle_deg || !ab || !offs))) return ccm_fail(c, CCM_E_ARG, "bad steering tap arguments");
+        if (n == 0) return CCM_OK;
+        CCM_HIP(c, hipSetDevice(c->device));
+        CCM_HIP(c, orb_upload_pattern());
+        DevBuf in, out;                                        // in: m01 | m10; out: angle | ab | offs
+        const size_t nb = (size_t)n * 4;
+        CCM_RESERVE(c, in, 2 * nb);
+        CCM_RESERVE(c, out, 3 * nb + (size_t)n * 1024);
+        CCM_HIP(c, hipMemcpyAsync(in.as<char>(), m01, nb, hipMemcpyHostToDevice, c->stream));
+        CCM_HIP(c, hipMemcpyAsync(in.as<char>() + nb, m10, nb, hipMemcpyHostToDevice, c->stream));
+        orb_launch_od_steer_debug(c->stream, in.as<int>(), in.as<int>() + n, n, out.as<float>(), out.as<float>() + n,
+                                  reinterpret_cast<int8_t*>(out.as<float>() + 3 * (size_t)n));
+        CCM_HIP(c, hipGetLastError());
+        CCM_HIP(c, hipMemcpyAsync(angle_deg, out.as<char>(), nb, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipMemcpyAsync(ab, out.as<char>() + nb, 2 * nb, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipMemcpyAsync(offs, out.as<char>() + 3 * nb, (size_t)n * 1024, hipMemcpyDeviceToHost, c->stream));
+        CCM_HIP(c, hipStreamSynchronize(c->stream));
+        return CCM_OK;
+    });
+}
+
 }  // extern "C"

@@ -14,6 +14,24 @@
 //   sum_ij q_i q_j src is exact in integers, so it equals the reference's full-image separable
 //   blur bit for bit and the blurred pyramid is never written to HBM;
 //   computeOrbDescriptor (:100-316): bit k = I(p_2k) < I(p_2k+1) with the pattern rotated by the angle.
+//
+// The kernel is vector-issue bound (514 VALU wave-instructions per keypoint before, 463 now; prices of the classes:
+// profiles/od_diet_valu_calibration.txt), and its instruction stream was gone through part by part, every part bit-exact, each timed
+// as a library of its own against the parent on one box (profiles/od_diet_ab.txt; k_orient_desc<8> per 256-frame batch, ranges over 8
+// rounds, parent 0.2371-0.2385 ms in run 1 and 0.2368-0.2384 in run 2).  KEPT:
+//   C  the pattern's pairs as floats in LDS (od_build_pattern; 16 SDWA conversions per keypoint less)       0.2325-0.2341
+//   D  the centre offset in one pinned base, a point's four dwords off one address (od_gather_base)         0.2332-0.2351
+//   E  on top of D: round to nearest even by adding 1.5 * 2^23, addresses from the biased bits (od_rn)      0.2283-0.2303
+//   C + D + E = this file: 0.2254-0.2258 ms, step 0.7589-0.7638 against 0.7702-0.7745 ms.
+// BUILT, MEASURED AND TAKEN OUT (fewer instructions each, no faster):
+//   A  fast_atan2_deg with one division and one polynomial for both arms (-20 instructions, all on wave-uniform values): 0.2381-0.2395
+//   B  ccm_sincosf's sine and cosine chains on even / odd lanes, coefficients per lane from LDS, (a, b) in scalar registers
+//      (42 -> 26 f64 instructions): 0.2408-0.2420; with C + D + E 0.2357-0.2375 against 0.2253-0.2263 without it
+//   F  the row blur on unshifted dwords with ten shifted weight words (92 v_dot4 and no v_alignbyte against 74 + 30): 0.2383-0.2395; the
+//      dependent v_dot4 of a column then stand back to back with wait states between them, where the shifts used to fill in
+//   A + C + D + E + F: 0.2271-0.2279; all six: 0.2256-0.2267.
+//   E with the column term pinned into one v_mad_i32_i24 (+ v_add_u32) instead of v_mul_i32_i24 + v_add3_u32: 0.2261-0.2280 with C + D + E
+//      (no better), and 0.2372-0.2382 with all six parts (as slow as the parent).
 __device__ __forceinline__ int reflect101(int i, int n)
 {
     if (i < 0) i = -i;
@@ -44,6 +62,8 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x)
     return a;
 }
 
+static constexpr float OD_FACTOR_PI = (float)(3.14159265358979323846 / 180.f);      // degrees to radians (:103)
+
 // Per-wave LDS: hT[37][46] u16 (horizontally blurred, transposed: column-major, so the 7 tap rows of a
 // blurred pixel are 4 consecutive dwords of its column; the 92-byte pitch = 23 dwords is odd, which spreads
 // the scattered gathers of the descriptor over the banks).  The vertical pass runs at the sample points only,
@@ -70,9 +90,24 @@ __device__ __forceinline__ unsigned od_dot2(unsigned a, unsigned w, unsigned acc
 #define OD_BRIEF_BATCH 2         // BRIEF rounds whose gathers are in flight together (1, 2 or 4)
 #endif
 struct OdTaps { unsigned d[4], sh; };
-__device__ __forceinline__ void od_gather(const uint8_t* ctr, int dx, int dy, OdTaps& t)
+typedef const __attribute__((address_space(3))) unsigned od_lu32;      // a dword of LDS by its 32-bit address
+// A steered coordinate rounded to nearest even, as an integer with OD_RN_BIAS added: for |t| < 2^22 the float t + 1.5 * 2^23 has
+// ulp 1 and the exponent of 1.5 * 2^23, so the IEEE add rounds t exactly as v_rndne_f32 would and the sum's bit pattern is
+// 0x4B400000 + rint(t).  The bias is even and its low 24 bits are positive, so od_gather works on the biased value as it is.
+#define OD_RN_BIAS 0x4B400000
+__device__ __forceinline__ int od_rn(float t) { return __float_as_int(t + 12582912.f); }
+// the LDS address od_gather takes for a wave whose hT starts at LDS address wl: column 18, the dword of rows 18-19, less what the
+// biased coordinates add (the low 24 bits of the bias times the pitch; twice the bias for the row dword); wraps mod 2^32
+__device__ __forceinline__ unsigned od_gather_base(unsigned wl)
 {
-    const unsigned* p = reinterpret_cast<const unsigned*>(ctr + __mul24(dx, OD_HT_PITCH) + 4 * (dy >> 1));
+    return wl + 18u * OD_HT_PITCH + 4u * 9u - (unsigned)(OD_RN_BIAS & 0xFFFFFF) * OD_HT_PITCH - ((unsigned)OD_RN_BIAS << 1);
+}
+// dx, dy: od_rn's.  The point's four dwords are two ds_read2_b32 off one address.
+__device__ __forceinline__ void od_gather(unsigned base, int dx, int dy, OdTaps& t)
+{
+    // column: a 24-bit multiply (the low 24 bits of dx); row: 4 * (dy >> 1) = (dy << 1) & ~3, bias included (it is even)
+    const unsigned addr = (unsigned)(__mul24(dx, OD_HT_PITCH) + (int)base) + (((unsigned)dy << 1) & ~3u);
+    od_lu32* p = (od_lu32*)(uintptr_t)addr;
 #pragma unroll
     for (int i = 0; i < 4; i++) t.d[i] = p[i];
     t.sh = (unsigned)dy << 4;                                       // v_alignbit / v_lshrrev read bits 4:0 = 16 * (dy & 1)
@@ -83,6 +118,31 @@ __device__ __forceinline__ unsigned od_blur_at(const OdTaps& t)
     const unsigned e2 = __builtin_amdgcn_alignbit(t.d[3], t.d[2], t.sh), e3 = t.d[3] >> (t.sh & 31u);
     const unsigned v = od_dot2(e3, 18u, od_dot2(e2, 49u | (34u << 16), od_dot2(e1, 49u | (55u << 16), od_dot2(e0, 18u | (34u << 16), 32768u))));
     return min(v, 0xFFFFFFu) >> 16;                                 // = min(v >> 16, 255)
+}
+
+// The pattern's 256 test pairs (x0, y0, x1, y1) in LDS, as floats: lane L evaluates pairs L, 64 + L, 128 + L, 192 + L of every keypoint
+// of its wave, so the bytes are converted once per workgroup, not once per keypoint, and a round's pair is one ds_read_b128.
+typedef float4 OdPat;
+struct OdPair { float x0, y0, x1, y1; };
+__device__ __forceinline__ void od_build_pattern(OdPat* pat, int tid, int nthreads)
+{
+    for (int i = tid; i < 256; i += nthreads) {
+        const unsigned pr = *reinterpret_cast<const unsigned*>(c_pattern + 4 * i);
+        pat[i] = make_float4((float)(signed char)(pr & 255u), (float)(signed char)((pr >> 8) & 255u),
+                             (float)(signed char)((pr >> 16) & 255u), (float)(signed char)(pr >> 24));
+    }
+}
+__device__ __forceinline__ OdPair od_pair(const OdPat* pat, int i)
+{
+    const float4 q = pat[i];
+    return OdPair{ q.x, q.y, q.z, q.w };
+}
+// A pair's two sample points steered by (a, b) = (cos, sin) of the keypoint's angle (computeOrbDescriptor's GET_VALUE, :107-110) and
+// rounded: od_rn's biased integers.
+struct OdPts { int x0, y0, x1, y1; };
+__device__ __forceinline__ OdPts od_steer(const OdPair& q, float a, float b)
+{
+    return OdPts{ od_rn(q.x0 * a - q.y0 * b), od_rn(q.x0 * b + q.y0 * a), od_rn(q.x1 * a - q.y1 * b), od_rn(q.x1 * b + q.y1 * a) };
 }
 
 #ifndef OD_WAVES
@@ -125,7 +185,8 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
     __shared__ __attribute__((aligned(16))) uint8_t lds[OD_WAVES][OD_WAVE_LDS_PAD];
     // IC_Angle weights per |v| and patch dword k (columns 4k..4k+3, u = column - 21):
     //   wone = 1 inside the disc row, wu = u + 16 inside (so that sum u*I = dot(wu) - 16*dot(wone) stays unsigned)
-    __shared__ unsigned wone[16][11], wu[16][11], pat[256];
+    __shared__ unsigned wone[16][11], wu[16][11];
+    __shared__ __attribute__((aligned(16))) OdPat pat[256];
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
     int wx, wy;
     xcd_work_item(xcd_on, wx, wy);
@@ -136,7 +197,7 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
     const unsigned key_l = slot < g.out_per_frame ? sel[(long long)f * g.out_per_frame + slot] : 0u;     // (requested before the tables are built)
     // the 256 test pairs (x0, y0, x1, y1 as signed bytes): read from LDS per keypoint (as global loads they put a wait for ALL of the
     // wave's outstanding memory operations, the previous descriptor stores included, in front of each of the four rounds)
-    for (int i = threadIdx.x; i < 256; i += 64 * OD_WAVES) pat[i] = *reinterpret_cast<const unsigned*>(c_pattern + 4 * i);
+    od_build_pattern(pat, threadIdx.x, 64 * OD_WAVES);
     for (int i = threadIdx.x; i < 16 * 11; i += 64 * OD_WAVES) {
         const int av = i / 11, k = i - av * 11;
         const int lim = g.umax[av];
@@ -169,7 +230,6 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
     if (todo == 0) return;
 
     uint8_t* wl = lds[wv];
-    const float factorPI = (float)(3.14159265358979323846 / 180.f);
     auto item_of = [&](int j, OdItem& it, int& level, int& score, int& row) {
         const unsigned key = (unsigned)__builtin_amdgcn_readlane((int)key_l, j);
         level = __builtin_amdgcn_readlane(level_l, j); row = __builtin_amdgcn_readlane(row_l, j);
@@ -233,9 +293,12 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
         // ---- steered BRIEF: lane L evaluates pairs L, 64+L, 128+L, 192+L; a ballot is 8 descriptor bytes.  The vertical taps are
         //      applied at the 512 sample points only (od_blur_at), straight from hT: no blurred patch is built.
         float a, b;
-        ccm_sincosf(angle * factorPI, &b, &a);
+        ccm_sincosf(angle * OD_FACTOR_PI, &b, &a);
         uint8_t* drow = desc + ((long long)f * max_per_image + row_c) * 32;
-        const uint8_t* ctr = wl + 18 * OD_HT_PITCH + 4 * 9;          // column 18, the dword of rows 18-19 (blurred row 18's first tap)
+        // one uniform value that the compiler cannot take apart again: left alone it adds the centre offset (too large for ds_read2_b32's
+        // 8-bit offsets) to every point's address
+        unsigned ctr = od_gather_base((unsigned)(uintptr_t)(const __attribute__((address_space(3))) uint8_t*)wl);
+        asm volatile("" : "+s"(ctr));
         unsigned long long mybits = 0;
         // OD_BRIEF_BATCH rounds' gathers are requested before the first of them is used (the scheduler, left alone, waits for each
         // point's two reads before it requests the next point's)
@@ -244,11 +307,9 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
             OdTaps tp[OD_BRIEF_BATCH][2];
 #pragma unroll
             for (int q = 0; q < OD_BRIEF_BATCH; q++) {
-                const unsigned pr = pat[(r0 + q) * 64 + lane];
-                const float x0 = (float)(signed char)(pr & 255u), y0 = (float)(signed char)((pr >> 8) & 255u);
-                const float x1 = (float)(signed char)((pr >> 16) & 255u), y1 = (float)(signed char)(pr >> 24);
-                od_gather(ctr, __float2int_rn(x0 * a - y0 * b), __float2int_rn(x0 * b + y0 * a), tp[q][0]);
-                od_gather(ctr, __float2int_rn(x1 * a - y1 * b), __float2int_rn(x1 * b + y1 * a), tp[q][1]);
+                const OdPts pt = od_steer(od_pair(pat, (r0 + q) * 64 + lane), a, b);
+                od_gather(ctr, pt.x0, pt.y0, tp[q][0]);
+                od_gather(ctr, pt.x1, pt.y1, tp[q][1]);
             }
             if (OD_BRIEF_BATCH > 1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -272,9 +333,36 @@ __global__ __launch_bounds__(64 * OD_WAVES) __attribute__((amdgpu_waves_per_eu(8
     }
 }
 
+// ccm_debug_od_steer's kernel: a wave per moment pair, through the device functions k_orient_desc calls for the angle, for (a, b) and
+// for the steered, rounded sample points (lane L: pairs L, 64 + L, 128 + L, 192 + L, as there).
+__global__ __launch_bounds__(64) void k_od_steer_debug(const int* __restrict__ m01, const int* __restrict__ m10, int n,
+                                                       float* __restrict__ angle_deg, float* __restrict__ ab, signed char* __restrict__ offs)
+{
+    __shared__ __attribute__((aligned(16))) OdPat pat[256];
+    od_build_pattern(pat, threadIdx.x, 64);
+    __syncthreads();
+    const int i = blockIdx.x, lane = lane_id();
+    if (i >= n) return;
+    const float angle = fast_atan2_deg((float)m01[i], (float)m10[i]);
+    float a, b;
+    ccm_sincosf(angle * OD_FACTOR_PI, &b, &a);
+    if (lane == 0) { angle_deg[i] = angle; ab[2 * i] = a; ab[2 * i + 1] = b; }
+    for (int r = 0; r < 4; r++) {
+        const int pair = r * 64 + lane;
+        const OdPts pt = od_steer(od_pair(pat, pair), a, b);
+        const int v[4] = { pt.x0 - OD_RN_BIAS, pt.y0 - OD_RN_BIAS, pt.x1 - OD_RN_BIAS, pt.y1 - OD_RN_BIAS };
+        signed char* o = offs + ((long long)i * 512 + 2 * pair) * 2;
+        for (int j = 0; j < 4; j++) o[j] = (signed char)min(max(v[j], -128), 127);
+    }
+}
+
 extern "C" hipError_t orb_upload_pattern()
 {
     return hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), ccm_orb_pattern, 1024);
+}
+void orb_launch_od_steer_debug(hipStream_t s, const int* m01, const int* m10, int n, float* angle_deg, float* ab, int8_t* offs)
+{
+    hipLaunchKernelGGL(k_od_steer_debug, dim3(n), dim3(64), 0, s, m01, m10, n, angle_deg, ab, reinterpret_cast<signed char*>(offs));
 }
 void orb_launch_orient_desc(hipStream_t s, const OrbGeom& g_dev, int out_per_frame, int nframes, const unsigned* sel,
                             const int* sel_count, ccm_keypoint* kps, uint8_t* desc, int* counts, int max_per_image,

@@ -105,3 +105,4 @@ void orb_launch_octree(hipStream_t, const OrbGeom&, const OrbCell*, int nlevels,
 void orb_launch_orient_desc(hipStream_t, const OrbGeom&, int out_per_frame, int nframes, const unsigned* sel,
                             const int* sel_count, ccm_keypoint* kps, uint8_t* desc, int* counts, int max_per_image,
                             int* status);
+void orb_launch_od_steer_debug(hipStream_t, const int* m01, const int* m10, int n, float* angle_deg, float* ab, int8_t* offs);
