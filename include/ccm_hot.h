@@ -1503,6 +1503,83 @@ int ccm_comm_destroy(ccm_ctx*);
 int ccm_pose_from_mat4f(const float* T16, double* pose7);
 int ccm_pose_to_mat4f(const double* pose7, float* T16);
 
+/* --------------------------------------------------------- KeyFrameDatabase
+ * Place recognition: KeyFrameDatabase::add / erase / clear (cslam/src/Database.cpp:37-70) and the candidate queries
+ * DetectLoopCandidates / DetectMapMatchCandidates (:72-327), which name the keyframes the loop and map-match chain then works on
+ * (ccm_search_by_bow_frames, ccm_sim3_solver_*, ...).
+ *
+ * The reference walks an inverted file and keeps mnLoopWords / mLoopQuery / mLoopScore on the keyframes.  For a keyframe that
+ * queries once -- all LoopFinder and MapMatcher do -- the outcome equals the following, which is what is implemented (DESIGN.md
+ * section 4 shows the equivalence).  Every stored entry e is a BowVector (word ids strictly ascending, double values), a sequence
+ * number seq[e] from a counter that grows with every add (an erased and re-added key gets a new, larger one), and a stable slot.
+ * For a query BowVector q the DEVICE computes per slot
+ *     words[e]       number of word ids common to q and e
+ *     first_word[e]  the smallest common word id, -1 without one
+ *     score[e]       L1Scoring::score(q, e) (ScoringObject.cpp:23-68) in double: s = 0; over the common ids in ascending order
+ *                    s += (fabs(vi - wi) - fabs(vi)) - fabs(wi) with vi the query's value and wi the entry's; score = -s / 2.0.
+ *                    The left-to-right sum is part of the definition: the value is bit-identical to ccm_bow_score_l1.
+ *                    0 without a common word.
+ * and every order-dependent decision is replayed on the HOST over those arrays by ccm_kfdb_shortlist and ccm_kfdb_candidates.
+ *
+ * The database lives on the device of the context that creates it; afterwards only queries need a context, and any context on
+ * that device will do.  add / erase / clear / size / slot / slots / keys take no context, do no GPU work and may be called from any
+ * thread: they copy into a host-side pending list under the database's mutex.  A query holds that mutex from its flush to the end
+ * of its download, so queries from several threads (each per-client LoopFinder, the MapMatcher), each with its own context,
+ * serialise.  The arena of words grows when it is full and is compacted when more than half of it is holes; both happen inside a
+ * query.  Nothing is sized by the vocabulary: n_words only bounds the word ids. */
+typedef struct ccm_kfdb ccm_kfdb;
+#define CCM_KFDB_NEIGHBOURS 10      /* GetBestCovisibilityKeyFrames(10), Database.cpp:155 */
+int  ccm_kfdb_create(ccm_ctx*, int n_words, int64_t initial_capacity_words, ccm_kfdb** out);
+void ccm_kfdb_destroy(ccm_kfdb*);
+/* add: CCM_E_ARG, with the database unchanged, unless the ids are strictly ascending, every id lies in [0, n_words) and the key is
+ * not present; n = 0 is a legal entry.  The entry takes a free slot (a slot freed by erase may be reused).  erase of an unknown key
+ * does nothing, as in the reference.  clear forgets every entry and every slot. */
+int ccm_kfdb_add(ccm_kfdb*, int64_t key, int n, const int32_t* ids, const double* vals);
+int ccm_kfdb_erase(ccm_kfdb*, int64_t key);
+int ccm_kfdb_clear(ccm_kfdb*);
+int ccm_kfdb_size(ccm_kfdb*);                  /* stored entries */
+int ccm_kfdb_slot(ccm_kfdb*, int64_t key);     /* the key's slot, -1 when it is not stored */
+int ccm_kfdb_slots(ccm_kfdb*);                 /* high-water mark of the slots = length of the query arrays */
+/* keys[s] = the key in slot s, -1 for a free slot; seq[s] (may be null) = its sequence number, -1 for a free slot.  Returns the
+ * number of slots, CCM_E_CAPACITY when that exceeds capacity. */
+int ccm_kfdb_keys(ccm_kfdb*, int capacity, int64_t* keys, int64_t* seq);
+/* The query: applies the pending adds and erases on the context's stream, runs one kernel launch over every slot, downloads and
+ * synchronises.  The outputs have room for `capacity` slots; returns the number of slots written (ccm_kfdb_slots at the time of
+ * the query) or CCM_E_CAPACITY.  Free slots give words 0, first_word -1, score 0, seq -1; the query's own slot is reported like
+ * any other.  CCM_E_ARG for a context on another device, an unknown query_key, or (second form, for a Frame that is not stored) a
+ * query vector that fails the checks of add. */
+int ccm_kfdb_query(ccm_ctx*, ccm_kfdb*, int64_t query_key, int capacity, int32_t* words, double* score, int32_t* first_word, int64_t* seq);
+int ccm_kfdb_query_vector(ccm_ctx*, ccm_kfdb*, int n, const int32_t* ids, const double* vals, int capacity, int32_t* words,
+                          double* score, int32_t* first_word, int64_t* seq);
+/* Query words the kernel stages in LDS; a longer query is searched in global memory (same results). */
+int ccm_kfdb_query_lds_words(void);
+/* Taps: the arena in words (allocated, tail, held by live entries) after the last flush; milliseconds the last query spent in
+ * its flush, its kernel and its download (HIP events on the querying context's stream). */
+int ccm_kfdb_arena(ccm_kfdb*, int64_t* capacity_words, int64_t* used_words, int64_t* live_words);
+int ccm_kfdb_last_timing(ccm_kfdb*, double ms3[3]);
+
+/* Host step A (lKFsSharingWords and lScoreAndMatch, :111-146 / :236-271); needs no device.  eligible[s]: loop query -- the entry is
+ * in the query's map and is not connected to the query; map-match query -- the entry's client is not in msuAssClients.  A free slot
+ * (seq < 0) and query_slot (-1 for a query that is not stored) are ineligible whatever their byte says.  An entry is LISTED when it
+ * is eligible and words > 0; listed entries are ordered by (first_word, seq) ascending, the walk's first-encounter order.
+ * maxCommonWords = the largest words of a listed entry, *min_common_words = (int)(maxCommonWords * 0.8f); an entry passes the gate
+ * when words > *min_common_words.  shortlist = the gated entries with (float)score >= min_score, in listed order.  Returns its
+ * length (CCM_E_CAPACITY beyond capacity); nothing listed or nothing shortlisted gives 0 and *min_common_words = 0. */
+int ccm_kfdb_shortlist(int n_slots, const int32_t* words, const double* score, const int32_t* first_word, const int64_t* seq,
+                       const uint8_t* eligible, int query_slot, float min_score, int capacity, int32_t* shortlist, int32_t* min_common_words);
+/* Host step B (the covisibility accumulation, :148-201 / :273-326), all in float as there.  neighbours[i * CCM_KFDB_NEIGHBOURS + k]:
+ * the slots of GetBestCovisibilityKeyFrames(10) of shortlist[i] in its order, -1 for none or for a keyframe that is not stored.
+ * Per shortlisted entry acc = best = (float)score and bestKF = the entry; each neighbour that is listed and gated adds its
+ * (float)score to acc and replaces bestKF when its score is strictly greater than best.  retain = 0.75f * max(min_score, every
+ * acc).  candidates (room for n_shortlist) = the bestKF of the entries with acc > retain, in shortlist order, each once.  Returns
+ * their number. */
+int ccm_kfdb_candidates(int n_slots, const int32_t* words, const double* score, const int64_t* seq, const uint8_t* eligible, int query_slot,
+                        float min_score, int min_common_words, int n_shortlist, const int32_t* shortlist, const int32_t* neighbours,
+                        int32_t* candidates);
+/* minScore of LoopFinder.cpp:122-139 / MapMatcher.cpp:130-147 from the arrays of the SAME query: float 1, lowered to the least
+ * (float)score of the connected slots; -1 and free slots are skipped (pass the keyframes that are not bad). */
+float ccm_kfdb_min_score(int n_slots, const double* score, const int64_t* seq, int n_connected, const int32_t* connected);
+
 #ifdef __cplusplus
 }
 #endif

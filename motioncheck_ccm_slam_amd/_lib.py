@@ -48,6 +48,9 @@ SYMBOLS = [
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
     "ccm_frame_compute_bow", "ccm_frame_search_by_bow", "ccm_search_by_bow_frames",
     "ccm_undistort_points", "ccm_image_bounds", "ccm_frame_from_extract_camera", "ccm_frames_from_extract_camera", "ccm_frame_get_keypoints",
+    "ccm_kfdb_create", "ccm_kfdb_destroy", "ccm_kfdb_add", "ccm_kfdb_erase", "ccm_kfdb_clear", "ccm_kfdb_size", "ccm_kfdb_slot", "ccm_kfdb_slots",
+    "ccm_kfdb_keys", "ccm_kfdb_query", "ccm_kfdb_query_vector", "ccm_kfdb_query_lds_words", "ccm_kfdb_arena", "ccm_kfdb_last_timing",
+    "ccm_kfdb_shortlist", "ccm_kfdb_candidates", "ccm_kfdb_min_score",
 ]
 
 
@@ -442,6 +445,24 @@ def load():
     lib.ccm_frame_compute_bow.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     lib.ccm_frame_search_by_bow.argtypes = [vp, vp, vp, C.POINTER(BowOptions), vp, C.c_int, vp]
     lib.ccm_search_by_bow_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(BowOptions), vp, vp, vp, vp, vp]
+    if hasattr(lib, "ccm_kfdb_create"):                # (an older build timed through CCM_HOT_LIB has no KeyFrameDatabase)
+        lib.ccm_kfdb_create.argtypes = [vp, C.c_int, C.c_int64, C.POINTER(vp)]
+        lib.ccm_kfdb_destroy.argtypes = [vp]; lib.ccm_kfdb_destroy.restype = None
+        lib.ccm_kfdb_add.argtypes = [vp, C.c_int64, C.c_int, vp, vp]
+        lib.ccm_kfdb_erase.argtypes = [vp, C.c_int64]
+        lib.ccm_kfdb_clear.argtypes = [vp]
+        lib.ccm_kfdb_size.argtypes = [vp]
+        lib.ccm_kfdb_slot.argtypes = [vp, C.c_int64]
+        lib.ccm_kfdb_slots.argtypes = [vp]
+        lib.ccm_kfdb_keys.argtypes = [vp, C.c_int, vp, vp]
+        lib.ccm_kfdb_query.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp]
+        lib.ccm_kfdb_query_vector.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+        lib.ccm_kfdb_query_lds_words.argtypes = []
+        lib.ccm_kfdb_arena.argtypes = [vp, vp, vp, vp]
+        lib.ccm_kfdb_last_timing.argtypes = [vp, vp]
+        lib.ccm_kfdb_shortlist.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp]
+        lib.ccm_kfdb_candidates.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp]
+        lib.ccm_kfdb_min_score.argtypes = [C.c_int, vp, vp, C.c_int, vp]; lib.ccm_kfdb_min_score.restype = C.c_float
     _lib = lib
     return lib
 

@@ -1,0 +1,178 @@
+"""Mirror of `cslam::KeyFrameDatabase` (src/Database.cpp) on the device: `add` / `erase` / `clear`, and the candidate queries
+`DetectLoopCandidates` / `DetectMapMatchCandidates` with the `minScore` loop LoopFinder and MapMatcher run in front of them.
+
+The device computes, per stored entry, the number of words it shares with the query, the smallest shared word and the L1 score
+(one kernel launch, `ccm_kfdb_query`); the ordered rest of the reference's two functions is replayed on the host over those arrays
+(`shortlist`, `candidates`: pure host functions, usable without a device).  What the reference reads from the keyframes -- the
+map, the covisibility graph, `msuAssClients` -- the caller passes in as `eligible` and `neighbours`."""
+from __future__ import annotations
+
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+NEIGHBOURS = 10                                         # CCM_KFDB_NEIGHBOURS: GetBestCovisibilityKeyFrames(10)
+
+QueryResult = collections.namedtuple("QueryResult", "words score first_word seq query_slot")
+
+
+def _check(rc: int, what: str) -> int:
+    if rc < 0:
+        raise _lib.CcmError(rc, what)
+    return rc
+
+
+def shortlist(words, score, first_word, seq, eligible, min_score: float, query_slot: int = -1):
+    """Host step A (ccm_kfdb_shortlist): (slots shortlisted, in the inverted-file walk's order; minCommonWords)."""
+    lib = _lib.load()
+    w = np.ascontiguousarray(words, "i4"); s = np.ascontiguousarray(score, "f8"); f = np.ascontiguousarray(first_word, "i4")
+    q = np.ascontiguousarray(seq, "i8"); e = np.ascontiguousarray(eligible).astype(np.uint8)
+    n = len(w)
+    assert len(s) == n and len(f) == n and len(q) == n and len(e) == n
+    out = np.zeros(max(n, 1), "i4"); mcw = C.c_int32(0)
+    m = _check(lib.ccm_kfdb_shortlist(n, _lib.ptr(w), _lib.ptr(s), _lib.ptr(f), _lib.ptr(q), _lib.ptr(e), int(query_slot),
+                                      C.c_float(min_score), n, _lib.ptr(out), C.byref(mcw)), "ccm_kfdb_shortlist")
+    return out[:m].copy(), int(mcw.value)
+
+
+def candidates(words, score, seq, eligible, min_score: float, min_common_words: int, short, neighbours, query_slot: int = -1):
+    """Host step B (ccm_kfdb_candidates).  neighbours: [len(short), <= 10] slots, -1 for none; returns the candidate slots."""
+    lib = _lib.load()
+    w = np.ascontiguousarray(words, "i4"); s = np.ascontiguousarray(score, "f8"); q = np.ascontiguousarray(seq, "i8")
+    e = np.ascontiguousarray(eligible).astype(np.uint8); sl = np.ascontiguousarray(short, "i4")
+    nb = np.full((max(len(sl), 1), NEIGHBOURS), -1, "i4")
+    for i, row in enumerate(neighbours):
+        row = list(row)[:NEIGHBOURS]
+        nb[i, :len(row)] = row
+    out = np.zeros(max(len(sl), 1), "i4")
+    m = _check(lib.ccm_kfdb_candidates(len(w), _lib.ptr(w), _lib.ptr(s), _lib.ptr(q), _lib.ptr(e), int(query_slot), C.c_float(min_score),
+                                       int(min_common_words), len(sl), _lib.ptr(sl), _lib.ptr(nb), _lib.ptr(out)), "ccm_kfdb_candidates")
+    return out[:m].copy()
+
+
+def min_score_of(score, seq, connected_slots) -> float:
+    """minScore of LoopFinder.cpp:122-139 / MapMatcher.cpp:130-147 over the connected slots (ccm_kfdb_min_score), a float32 value."""
+    lib = _lib.load()
+    s = np.ascontiguousarray(score, "f8"); q = np.ascontiguousarray(seq, "i8"); c = np.ascontiguousarray(connected_slots, "i4")
+    return float(lib.ccm_kfdb_min_score(len(s), _lib.ptr(s), _lib.ptr(q), len(c), _lib.ptr(c)))
+
+
+class KeyFrameDatabase:
+    """Keys are int64 (e.g. the keyframe's idpair packed by the caller); a BowVector is (ids ascending, values)."""
+
+    def __init__(self, n_words: int, initial_capacity_words: int = 1 << 20, ctx: _lib.Context | None = None):
+        self.lib = _lib.load()
+        self.ctx = ctx if ctx is not None else _lib.default_context(0)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.ccm_kfdb_create(self.ctx.handle, int(n_words), int(initial_capacity_words), C.byref(h)))
+        self.handle = h
+        self.lds_words = self.lib.ccm_kfdb_query_lds_words()
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            self.lib.ccm_kfdb_destroy(h); self.handle = None
+
+    # ---- the store (no GPU work: the entries wait in a pending list until the next query)
+    def add(self, key: int, ids, vals):
+        i = np.ascontiguousarray(ids, "i4"); v = np.ascontiguousarray(vals, "f8")
+        assert i.ndim == 1 and i.shape == v.shape
+        _check(self.lib.ccm_kfdb_add(self.handle, int(key), len(i), _lib.ptr(i), _lib.ptr(v)),
+               "ccm_kfdb_add: ids must be strictly ascending and inside the vocabulary, the key new")
+
+    def erase(self, key: int):
+        _check(self.lib.ccm_kfdb_erase(self.handle, int(key)), "ccm_kfdb_erase")
+
+    def clear(self):
+        _check(self.lib.ccm_kfdb_clear(self.handle), "ccm_kfdb_clear")
+
+    def size(self) -> int:
+        return self.lib.ccm_kfdb_size(self.handle)
+
+    def slots(self) -> int:
+        return self.lib.ccm_kfdb_slots(self.handle)
+
+    def slot(self, key: int) -> int:
+        return self.lib.ccm_kfdb_slot(self.handle, int(key))
+
+    def keys(self):
+        """(key per slot, -1 for a free slot; sequence number per slot)."""
+        n = self.slots()
+        k = np.zeros(max(n, 1), "i8"); q = np.zeros(max(n, 1), "i8")
+        m = _check(self.lib.ccm_kfdb_keys(self.handle, len(k), _lib.ptr(k), _lib.ptr(q)), "ccm_kfdb_keys")
+        return k[:m], q[:m]
+
+    def arena(self):
+        """(allocated, tail, live) words of the device arena after the last query's flush."""
+        a = (C.c_int64 * 3)()
+        _check(self.lib.ccm_kfdb_arena(self.handle, C.byref(a, 0), C.byref(a, 8), C.byref(a, 16)), "ccm_kfdb_arena")
+        return int(a[0]), int(a[1]), int(a[2])
+
+    def last_timing(self):
+        """Milliseconds the last query spent in (flush, kernel, download)."""
+        t = np.zeros(3, "f8")
+        _check(self.lib.ccm_kfdb_last_timing(self.handle, _lib.ptr(t)), "ccm_kfdb_last_timing")
+        return tuple(float(x) for x in t)
+
+    # ---- queries
+    def query(self, key: int | None = None, bow=None, ctx: _lib.Context | None = None) -> QueryResult:
+        """The raw per-slot arrays for a stored key, or for bow = (ids, vals) of a Frame that is not stored."""
+        ctx = ctx if ctx is not None else self.ctx
+        assert (key is None) != (bow is None), "query a stored key or a BowVector"
+        cap = self.slots() + 64                                         # (another thread may add before the query takes the mutex)
+        w = np.zeros(cap, "i4"); s = np.zeros(cap, "f8"); f = np.zeros(cap, "i4"); q = np.zeros(cap, "i8")
+        if key is not None:
+            n = ctx.check(self.lib.ccm_kfdb_query(ctx.handle, self.handle, int(key), cap, _lib.ptr(w), _lib.ptr(s), _lib.ptr(f), _lib.ptr(q)))
+            qs = self.slot(key)
+        else:
+            i = np.ascontiguousarray(bow[0], "i4"); v = np.ascontiguousarray(bow[1], "f8")
+            assert i.ndim == 1 and i.shape == v.shape
+            n = ctx.check(self.lib.ccm_kfdb_query_vector(ctx.handle, self.handle, len(i), _lib.ptr(i), _lib.ptr(v), cap, _lib.ptr(w), _lib.ptr(s),
+                                                         _lib.ptr(f), _lib.ptr(q)))
+            qs = -1
+        return QueryResult(w[:n], s[:n], f[:n], q[:n], qs)
+
+    def min_score(self, key: int, connected_keys, ctx: _lib.Context | None = None, result: QueryResult | None = None) -> float:
+        """minScore of the query keyframe over its connected keyframes that are not bad (pass `result` to reuse a query)."""
+        r = result if result is not None else self.query(key, ctx=ctx)
+        return min_score_of(r.score, r.seq, [self.slot(k) for k in connected_keys])
+
+    def _eligible(self, eligible, n):
+        if isinstance(eligible, np.ndarray) and eligible.dtype in (np.bool_, np.uint8):
+            assert len(eligible) == n, "an eligibility mask has one byte per slot"
+            return eligible.astype(np.uint8)
+        m = np.zeros(n, np.uint8)
+        for k in eligible:
+            s = self.slot(k)
+            if 0 <= s < n:
+                m[s] = 1
+        return m
+
+    def _detect(self, key, min_score, eligible, neighbours, bow, ctx, result):
+        r = result if result is not None else self.query(key if bow is None else None, bow=bow, ctx=ctx)
+        n = len(r.words)
+        keys, _ = self.keys()
+        el = self._eligible(eligible, n)
+        short, mcw = shortlist(r.words, r.score, r.first_word, r.seq, el, min_score, r.query_slot)
+        if len(short) == 0:
+            return []
+        nb = []
+        for s in short:
+            ks = neighbours(int(keys[s])) if callable(neighbours) else neighbours.get(int(keys[s]), ())
+            nb.append([self.slot(k) for k in list(ks)[:NEIGHBOURS]])
+        cand = candidates(r.words, r.score, r.seq, el, min_score, mcw, short, nb, r.query_slot)
+        return [int(keys[s]) for s in cand]
+
+    def DetectLoopCandidates(self, key: int, min_score: float, eligible, neighbours, ctx=None, result=None):
+        """KeyFrameDatabase::DetectLoopCandidates (:72-202).  eligible: the keys (or a per-slot mask) of the entries that are in the
+        query's map and not connected to it; neighbours: key -> GetBestCovisibilityKeyFrames(10) keys (a callable or a mapping).
+        LoopFinder passes min_score = float(minScore * 0.8) (the product is a double, the parameter a float).  Returns keys."""
+        return self._detect(key, min_score, eligible, neighbours, None, ctx, result)
+
+    def DetectMapMatchCandidates(self, key: int, min_score: float, eligible, neighbours, ctx=None, result=None, bow=None):
+        """KeyFrameDatabase::DetectMapMatchCandidates (:204-327).  eligible: the entries whose client is not in msuAssClients of the
+        query's map.  bow = (ids, vals) queries with a BowVector that is not stored (key is then ignored)."""
+        return self._detect(key, min_score, eligible, neighbours, bow, ctx, result)
