@@ -1,5 +1,8 @@
 """Row F3: vocabulary descent and ComputeDistinctiveDescriptors on the GPU vs the CPU oracle, on a synthetic tree of
-ORBvoc's shape (the vocabulary file itself is not in the reference tree)."""
+ORBvoc's shape (the vocabulary file itself is not in the reference tree).  The inputs are random, so ties and threshold equalities
+do not occur here; the oracle these tests compare with is itself held to tests/bow_ref.py, the definition restated from the
+reference's text, on exactly these inputs (tests/test_bow_cases_cpu.py), and the tie and boundary rules are forced by the hand-built
+cases of tests/test_bow_cases_gpu.py."""
 import numpy as np
 import pytest
 
@@ -7,6 +10,8 @@ from motioncheck_ccm_slam_amd import synth
 from motioncheck_ccm_slam_amd.matcher import ORBmatcher
 from motioncheck_ccm_slam_amd.orb import ORBextractor
 from motioncheck_ccm_slam_amd.vocabulary import ORBVocabulary, synthetic_tree
+import bow_inputs
+import frame_bow_ref as fb
 
 pytestmark = pytest.mark.gpu
 
@@ -17,12 +22,7 @@ def tree():
 
 
 def _features(tree, rng, n):
-    par, desc, w = tree
-    leaves = rng.integers(1, len(par), n)
-    flips = np.packbits(rng.random((n, 256)) < 0.1, axis=1, bitorder="little")
-    f = desc[leaves] ^ flips
-    f[: n // 10] = rng.integers(0, 256, (n // 10, 32), dtype=np.uint8)
-    return f
+    return fb.features(tree, rng, n)
 
 
 def test_transform_matches_oracle(ctx, oracle, tree):
@@ -93,16 +93,7 @@ def test_full_batch_transform_properties(ctx, oracle, tree):
 def test_distinctive_descriptors(ctx, oracle, tree):
     par, desc, w = tree
     voc = ORBVocabulary(10, 4, par, desc, w, ctx=ctx)
-    rng = np.random.default_rng(4)
-    counts = np.concatenate([[0, 1, 2, 3, 64, 65, 130], rng.integers(2, 40, 300)]).astype("i4")
-    first = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype("i8")
-    total = int(counts.sum())
-    base = rng.integers(0, 256, (len(counts), 32), dtype=np.uint8)
-    d = np.zeros((total, 32), np.uint8)
-    for p, (f, c) in enumerate(zip(first, counts)):
-        flips = np.packbits(rng.random((c, 256)) < rng.uniform(0.02, 0.2), axis=1, bitorder="little")
-        d[f:f + c] = base[p] ^ flips
-    d[first[4]:first[4] + 5] = d[first[4]]                               # identical observations: ties
+    d, first, counts = bow_inputs.distinctive_clusters()
     best = voc.distinctive_descriptors(d, first, counts)
     for p, (f, c) in enumerate(zip(first, counts)):
         assert best[p] == oracle.distinctive_descriptor(d[f:f + c]), p
