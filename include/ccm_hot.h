@@ -1213,6 +1213,111 @@ int ccm_sim3_solver_state(const ccm_sim3_solver*, int k, int32_t* iterations, in
  * correspondence i at bit i % 64 of word i / 64. */
 int ccm_sim3_solver_hypotheses(const ccm_sim3_solver*, int k, int32_t* sample, int32_t* count, float* rts, uint64_t* mask);
 
+/* ---------------------------------------------------------------- PnPsolver (src/PnPSolver.cpp), batched EPnP RANSAC
+ * The link between SearchByBoW against the relocalisation candidates (ccm_kfdb_query_vector, ccm_search_by_bow_frames) and the
+ * relocalisation overload of SearchByProjection: one PnPsolver per candidate keyframe, iterate(5) round-robin as ORB-SLAM's
+ * Tracking::Relocalization does.  The minimal-set hypotheses of PnPsolver::iterate (:155-249) do not depend on each other (min_set
+ * sampled correspondences -> EPnP compute_pose :468-516 -> CheckInliers :299-330), and Refine (:251-296) depends only on which
+ * hypothesis is the running best.  ccm_pnp_solver_create evaluates ALL hypotheses of ALL solvers in one launch and every reachable
+ * Refine() in a second one; ccm_pnp_solver_iterate / _find replay the ordered bookkeeping over the stored results on the host, so
+ * any calling pattern returns what the sequential code returns for the same random draws and the same per-hypothesis poses.
+ *
+ * Constructor data (:57-100), flattened by the caller: correspondence e of solver k (first[k] <= e < first[k+1], N = first[k+1] -
+ * first[k]) = one vpMapPointMatches[i] that is set and not bad, in i order.
+ *
+ * SetRansacParameters (:111-147) is part of the create call: solver k gets (mRansacMinInliers, mRansacMaxIts) =
+ * ccm_pnp_ransac_parameters(N, ...) and mvMaxError[i] = sigma2[i] * th2 (float).  Carrying mnBestInliers over a later
+ * SetRansacParameters (the reference does not reset it) is NOT supported: a batch always starts from mnBestInliers = 0, and a caller
+ * that changes the parameters creates a new batch.
+ *
+ * Which hypotheses are stored: the loop condition is mnIterations < mRansacMaxIts || nCurrentIterations < nIterations (:172), so
+ * with its || a call can run past mRansacMaxIts.  Solver k evaluates H_k = mRansacMaxIts_k + reserve hypotheses, or none when N <
+ * mRansacMinInliers_k (iterate leaves at :163).  iterate with n_iterations needs at most max(mRansacMaxIts_k, mnIterations +
+ * n_iterations) hypotheses; beyond H_k it returns CCM_E_STATE and changes nothing.  reserve = the caller's n_iterations covers every
+ * caller that drops a solver at bNoMore or at its first return (the call that crosses mRansacMaxIts starts below it and runs at
+ * most n_iterations - 1 past it).  A return at or past mRansacMaxIts does not set bNoMore; a caller that rejects such a pose and
+ * resumes the solver draws up to n_iterations more per call, so it reserves n_iterations for each rejection it allows for.
+ *
+ * Sampling (:178-192): the random source stays with the caller.  draws holds the raw RandomInt results: draw i of hypothesis h of
+ * solver k at draws[((k * (max_iterations + reserve)) + h) * min_set + i], in [0, N-1-i]; the library applies the reference's
+ * swap-with-last removal (position randi takes the last element, :190).  Only the rows of hypotheses that are evaluated are read;
+ * one of them outside its range is CCM_E_ARG.
+ *
+ * Arithmetic: EPnP in double.  What the reference takes from OpenCV (cvSVD of the 3x3 covariance and of the 12x12 M^T M, cvInvert,
+ * cvSolve, the 3x3 cvSVD of estimate_R_and_t) is restated with Jacobi iterations.  With min_set = 4 M^T M has a 4-dimensional null
+ * space and "the four smallest right singular vectors" (:755-758) are an ARBITRARY basis of it, on which the resulting pose depends
+ * (DESIGN.md "PnPsolver"); so does it on the signs of the PCA axes (:391).  Agreement with the reference per hypothesis is therefore
+ * not definable.  The contract: the tapped (control points, basis) satisfy their definitions, and everything behind them agrees with
+ * a float64 restatement fed with that pair; CheckInliers follows the reference's mixed float / double types step by step without
+ * floating-point contraction, so flags and counts are exact functions of the double pose the library reports.  One deviation:
+ * qr_solve (:851-941) returns at eta == 0 with X stale (uninitialised on the first step); here that Gauss-Newton step is zero. */
+typedef struct {
+    int32_t        n_solvers;
+    const int32_t* first;        /* [n_solvers+1], first[0] = 0, non-decreasing */
+    const int32_t* n1;           /* [n_solvers] mvpMapPointMatches.size(), the length of vbInliers */
+    const float*   K;            /* [n_solvers][4] fx, fy, cx, cy (:94-97) */
+    const float*   P2D;          /* [..][2] mvKeysUn[i].pt */
+    const float*   P3Dw;         /* [..][3] GetWorldPos() */
+    const float*   sigma2;       /* [..] mvLevelSigma2[octave] */
+    const int32_t* kp_index;     /* [..] mvKeyPointIndices, each in [0, n1[k]) */
+    double         probability;  /* SetRansacParameters(probability = 0.99, minInliers = 8, maxIterations = 300, minSet = 4, */
+    int32_t        min_inliers;  /*                     epsilon = 0.4, th2 = 5.991)  (PnPSolver.h:91) */
+    int32_t        max_iterations;
+    int32_t        min_set;      /* 4 .. 8, otherwise CCM_E_ARG */
+    float          epsilon;
+    float          th2;
+    int32_t        reserve;      /* hypotheses stored past mRansacMaxIts, >= 0 (see above) */
+    const int32_t* draws;        /* [n_solvers][max_iterations + reserve][min_set] */
+    uint32_t       flags;        /* bit 0: keep the detail tap */
+} ccm_pnp_ransac_problem;
+typedef struct ccm_pnp_solver ccm_pnp_solver;
+#define CCM_PNP_DETAIL 68        /* doubles per row of the detail tap: cws[12], basis[4][12] (v[0..3] = ut rows 11..8), betas[4] of
+                                  * the chosen candidate, rep_error[3], which (1..3) */
+
+/* SetRansacParameters (:119-142) for N = n correspondences: nMinInliers = (int)(N * epsilon) in float, raised to min_inliers and to
+ * min_set; epsilon raised to (float)nMinInliers / N; nIterations = 1 if nMinInliers == N, else ceil(log(1 - probability) / log(1 -
+ * pow(epsilon, 3))) with the float epsilon raised to 3 in double; max(1, min(nIterations, max_iterations)).  For N < nMinInliers
+ * (which includes N = 0) the reference's value is undefined and unused (iterate leaves at :163); it is 1 here.  Host only; each
+ * output may be NULL. */
+int ccm_pnp_ransac_parameters(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                              int32_t* min_inliers_out, int32_t* max_its_out, float* epsilon_out);
+/* EPnP compute_pose (:468-516) of n >= 4 correspondences on the host, the same arithmetic as the kernels: Rt = R (9, row-major), t
+ * (3).  detail may be NULL, else CCM_PNP_DETAIL doubles.  Needs no device.  n < 4 or a null array: CCM_E_ARG, outputs untouched. */
+int ccm_pnp_compute_pose(int n, const float* P3Dw, const float* P2D, const float* K, double* Rt, double* detail);
+/* One upload of the batch, k_pnp_hypotheses, one download and synchronisation; the records (hypotheses that become the running best)
+ * are found by a scan over the counts on the host and their list (24 bytes each) goes up; k_pnp_refine, one download and a second
+ * synchronisation (none of the three when no hypothesis reaches mRansacMinInliers).  Device memory is the context's
+ * (grow-only, reused by the next batch); the solver object holds host memory only and belongs to the thread that made it.  On an
+ * error *out is untouched. */
+int ccm_pnp_solver_create(ccm_ctx*, const ccm_pnp_ransac_problem*, ccm_pnp_solver** out);
+/* NULL is a no-op. */
+void ccm_pnp_solver_destroy(ccm_pnp_solver*);
+/* n_solvers of the batch, or CCM_E_ARG for NULL. */
+int ccm_pnp_solver_count(const ccm_pnp_solver*);
+/* PnPsolver::iterate(nIterations, bNoMore, vbInliers, nInliers) (:155-249) of solver k, exactly.  The outputs are cleared first
+ * (:157-159); N < mRansacMinInliers -> *no_more = 1 and nothing else (:163-167).  For each hypothesis in order with mnInliersi >=
+ * mRansacMinInliers: it becomes the running best if mnInliersi > mnBestInliers (:203); then Refine() of the CURRENT best is
+ * consulted (:217) and returns when its count is > mRansacMinInliers (:283, strict): *found = 1, Tcw = the refined pose as float
+ * (4x4 row-major), *n_inliers the refined count, inliers[mvKeyPointIndices[i]] = 1 over the refined mask.  After the loop,
+ * mnIterations >= mRansacMaxIts sets *no_more = 1 and, if mnBestInliers >= mRansacMinInliers, returns found with the best
+ * hypothesis' own pose, count and mask (:232-246).  mnIterations and mnBestInliers persist over calls.  inliers has n1[k] entries;
+ * inliers and Tcw may be NULL; Tcw is untouched unless *found.  CCM_E_STATE: the call would need hypotheses beyond the reserve. */
+int ccm_pnp_solver_iterate(ccm_pnp_solver*, int k, int n_iterations, int32_t* found, int32_t* no_more, uint8_t* inliers,
+                           int32_t* n_inliers, float* Tcw);
+/* PnPsolver::find (:149-153) = iterate(mRansacMaxIts) without bNoMore. */
+int ccm_pnp_solver_find(ccm_pnp_solver*, int k, int32_t* found, uint8_t* inliers, int32_t* n_inliers, float* Tcw);
+/* The RANSAC state of solver k (each output may be NULL): mnIterations, mnBestInliers, the hypothesis behind the running best
+ * (-1 = none yet), mRansacMaxIts and mRansacMinInliers. */
+int ccm_pnp_solver_state(const ccm_pnp_solver*, int k, int32_t* iterations, int32_t* best_inliers, int32_t* best_hypothesis,
+                         int32_t* max_iterations, int32_t* min_inliers);
+/* Test / diagnostic taps of solver k.  Each returns the number of rows (>= 0) or an error; each output may be NULL.
+ * _hypotheses: H rows: sample [H][min_set] correspondence indices, count [H], Rt [H][12] double, mask [H][ceil(N/64)] with
+ * correspondence i at bit i % 64 of word i / 64, detail [H][CCM_PNP_DETAIL] (CCM_E_STATE unless the batch was created with flag bit
+ * 0).  _refinements: R rows, one per record in hypothesis order: hyp [R] the record hypothesis whose mask was refined (:256-272),
+ * count [R] mnRefinedInliers, Rt, mask = mvbRefinedInliers, detail. */
+int ccm_pnp_solver_hypotheses(const ccm_pnp_solver*, int k, int32_t* sample, int32_t* count, double* Rt, uint64_t* mask, double* detail);
+int ccm_pnp_solver_refinements(const ccm_pnp_solver*, int k, int32_t* hyp, int32_t* count, double* Rt, uint64_t* mask, double* detail);
+
 /* ---- Initializer: the monocular two-view initialisation (src/Initializer.cpp, called from Tracking::MonocularInitialization,
  * src/Tracking.cpp:293-357, between ccm_search_for_initialization and the first ccm_ba_solve).
  * Initializer::Initialize (:40-117) evaluates mMaxIterations minimal sets of 8 matches twice -- FindHomography (:120-168) and

@@ -45,6 +45,8 @@ SYMBOLS = [
     "ccm_search_by_sim3_table_frames", "ccm_search_by_projection_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
+    "ccm_pnp_ransac_parameters", "ccm_pnp_compute_pose", "ccm_pnp_solver_create", "ccm_pnp_solver_destroy", "ccm_pnp_solver_count",
+    "ccm_pnp_solver_iterate", "ccm_pnp_solver_find", "ccm_pnp_solver_state", "ccm_pnp_solver_hypotheses", "ccm_pnp_solver_refinements",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
     "ccm_frame_compute_bow", "ccm_frame_search_by_bow", "ccm_search_by_bow_frames",
     "ccm_undistort_points", "ccm_image_bounds", "ccm_frame_from_extract_camera", "ccm_frames_from_extract_camera", "ccm_frame_get_keypoints",
@@ -113,6 +115,13 @@ class Sim3RansacProblem(C.Structure):
                 ("K2", C.c_void_p), ("X1", C.c_void_p), ("X2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
                 ("indices1", C.c_void_p), ("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32),
                 ("draws", C.c_void_p), ("best_inliers", C.c_void_p)]
+
+
+class PnpRansacProblem(C.Structure):                  # ccm_pnp_ransac_problem
+    _fields_ = [("n_solvers", C.c_int32), ("first", C.c_void_p), ("n1", C.c_void_p), ("K", C.c_void_p), ("P2D", C.c_void_p),
+                ("P3Dw", C.c_void_p), ("sigma2", C.c_void_p), ("kp_index", C.c_void_p), ("probability", C.c_double),
+                ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float),
+                ("th2", C.c_float), ("reserve", C.c_int32), ("draws", C.c_void_p), ("flags", C.c_uint32)]
 
 
 class InitializerProblem(C.Structure):
@@ -439,6 +448,17 @@ def load():
     lib.ccm_sim3_solver_estimate.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.ccm_sim3_solver_state.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ccm_sim3_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    if hasattr(lib, "ccm_pnp_solver_create"):          # (an older build timed through CCM_HOT_LIB has no PnPsolver)
+        lib.ccm_pnp_ransac_parameters.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, vp, vp, vp]
+        lib.ccm_pnp_compute_pose.argtypes = [C.c_int, vp, vp, vp, vp, vp]
+        lib.ccm_pnp_solver_create.argtypes = [vp, C.POINTER(PnpRansacProblem), C.POINTER(vp)]
+        lib.ccm_pnp_solver_destroy.argtypes = [vp]; lib.ccm_pnp_solver_destroy.restype = None
+        lib.ccm_pnp_solver_count.argtypes = [vp]
+        lib.ccm_pnp_solver_iterate.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        lib.ccm_pnp_solver_find.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+        lib.ccm_pnp_solver_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.ccm_pnp_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.ccm_pnp_solver_refinements.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
     lib.ccm_create_new_map_points.argtypes = [vp, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)]
     lib.ccm_create_new_map_points_frames.argtypes = [vp, C.POINTER(NewPointsFrames), C.POINTER(NewPointsResult)]

@@ -55,6 +55,7 @@ void ccm_destroy(ccm_ctx* c)
     sim3_state_free(c->sim3);
     sim3_ransac_state_free(c->sim3_ransac);
     init_state_free(c->init);
+    pnp_state_free(c->pnp);
     map_state_free(c->map);
     ess_state_free(c->ess);
     for (ProfLabel& L : c->prof) for (auto& e : L.ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }

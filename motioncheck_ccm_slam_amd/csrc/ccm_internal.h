@@ -22,6 +22,7 @@ struct PoseState;
 struct Sim3State;
 struct Sim3RansacState;
 struct InitState;
+struct PnpState;
 struct MapState;
 struct EssState;
 struct FrameState;
@@ -49,6 +50,7 @@ struct ccm_ctx {
     Sim3State* sim3 = nullptr;
     Sim3RansacState* sim3_ransac = nullptr;   // batched Sim3Solver: staging and device buffers (sim3_ransac_host.cpp)
     InitState* init = nullptr;                // monocular Initializer: staging and device buffers (init_host.cpp)
+    PnpState* pnp = nullptr;                  // batched PnPsolver: staging and device buffers (pnp_host.cpp)
     MapState* map = nullptr;                  // CreateNewMapPoints: staging and device buffers (map_host.cpp)
     EssState* ess = nullptr;
     FrameState* frame = nullptr;   // frame handles: pool, staging, live frames (frame_internal.h)
@@ -153,6 +155,7 @@ void pose_state_free(PoseState*);
 void sim3_state_free(Sim3State*);
 void sim3_ransac_state_free(Sim3RansacState*);
 void init_state_free(InitState*);
+void pnp_state_free(PnpState*);
 void map_state_free(MapState*);
 void ess_state_free(EssState*);
 void frame_state_free(ccm_ctx*);                       // also orphans the frames still alive
