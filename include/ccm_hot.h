@@ -915,6 +915,114 @@ typedef struct {
 } ccm_tmm_result;
 int ccm_frame_track_motion_model(ccm_ctx*, ccm_frame* cur, const ccm_frame* last, ccm_map_table*, const ccm_tmm_params*, ccm_tmm_result*);
 
+/* The relocalisation overload ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cpp:
+ * 1478-1605) on the current frame's handle, a keyframe handle whose map-point ids are table slots, and the table; it replaces the
+ * route through ccm_frame_search_by_projection_frame on host arrays, where the caller projects every map point of the keyframe and
+ * uploads u, v, level, angle and a descriptor per point.  In the reference's order, one thread per keyframe feature (k_reloc_project):
+ *   Keyframe feature i with id = kf's mp_id[i] < 0 is no query (:1498).  An id outside the table or naming a slot that is not LIVE
+ *     returns CCM_E_ARG with cur's ids as they were on entry.  A BAD slot is skipped: isBad() IS asked here (:1500), unlike Current/Last.
+ *     A slot in the found set is skipped (:1500).
+ *   Project, with P the slot's pos, in the arithmetic ccm_frame_track_motion_model states (one device function for both):
+ *       Pc[r] = (float)((double)R[r][0] P[0] + (double)R[r][1] P[1] + (double)R[r][2] P[2] + (double)t[r])
+ *       invz = 1.0f / Pc[2]   (:1508 divides in double and narrows; for one division of two floats that is the same float)
+ *       u = fx * PcX * invz + cx;  v = fy * PcY * invz + cy
+ *     There is NO depth test in this overload: a point behind the camera whose u, v land inside the bounds is a query.  One deviation,
+ *     as in ccm_frame_track_motion_model: a u or v that is not finite (Pc[2] == 0 only) is rejected.
+ *       reject u < min_x || u > max_x, then v < min_y || v > max_y   (:1513-1516, both ends inside)
+ *   Distance: dist3D = (float)sqrt of the squares of P - Ow summed in double (cv::norm); reject dist3D < 0.8f * min_dist || dist3D >
+ *     1.2f * max_dist (:1526 with GetMin/MaxDistanceInvariance, strict on both sides).
+ *   Level = PredictScale(dist3D, Frame) (src/MapPoint.cpp:854-869): ratio = max_dist / dist3D, (float)log((double)ratio) /
+ *     log_scale_factor, ceilf, clamped to [0, n_levels - 1], a NaN gives 0 -- the device function of ccm_fuse_select_table_frames.
+ *   Query: radius = th * scale_factors[level], levels level-1 .. level+1 (:1532-1534), the slot's descriptor, angle kf's angle[i].
+ *   Search and acceptance: window selection, the sequential acceptance of :1544-1564 in i order and the rotation histogram of
+ *     :1566-1601 exactly as ccm_frame_search_by_projection_frame runs them (on the device, or on the host with
+ *     CCM_WINDOW_HOST_ACCEPT=1 or a frame too large for the acceptance kernel's LDS).  A current feature is occupied when its mp_id >=
+ *     0, WHATEVER the slot's HAS_OBS says (:1547), and a feature matched in this call is occupied for the later queries; accepted is
+ *     bestDist <= orb_dist.  cur's ids are NOT cleared first; the accepted features receive the slot, a feature the rotation filter
+ *     removes keeps -1.  n_matches is the count after the rotation filter.
+ * The found set (sAlreadyFound): n_found >= 0: the slots found[0 .. n_found); n_found < 0: every id cur holds on entry, derived on
+ * the device from cur's mp_id.  Membership is a stamp per table slot in a column of the table handle; nothing is cleared per call.
+ * Traffic, as the code has it: the view, th and the scale factors travel as kernel arguments; one page-locked copy up of the found
+ * list when it is explicit (4 bytes per entry), nothing per map point.  One read-back and stream synchronisation (status, match,
+ * occupancy flags, mp_id, the bad-id word: 9 N_cur + 32 bytes and the padding; the taps with it when asked for), repeated only by the
+ * overflow retry of the candidate lists.  On the host acceptance route the candidate lists and what the loops read of both frames
+ * are fetched as well, each fetch synchronising.
+ * Errors, found before anything changes the handle.  CCM_E_ARG: a NULL ctx, cur, kf, table, view, result, scale_factors, match or
+ * mp_id (N_cur > 0), found (n_found > 0); only some of the taps; n_levels outside 1..CCM_MAX_LEVELS; cur == kf; a handle or table of
+ * another context; check_ori with a handle that has no angles; a found slot outside the table.  CCM_E_STATE: a handle or table that
+ * outlived its context.  N_kf == 0 or N_cur == 0: CCM_OK with zero matches.  Returns CCM_OK or an error. */
+typedef struct {
+    float Tcw[12];                      /* CurrentFrame.mTcw, rows of [Rcw | tcw] */
+    float Ow[3];                        /* -Rcw^T tcw (:1484) */
+    float fx, fy, cx, cy;
+    float min_x, max_x, min_y, max_y;   /* mnMinX .. mnMaxY */
+    int32_t n_levels; const float* scale_factors;          /* mvScaleFactors [n_levels], 1..CCM_MAX_LEVELS */
+    float log_scale_factor;             /* mfLogScaleFactor */
+} ccm_reloc_view;
+typedef struct {
+    int32_t n_matches;     /* after the rotation filter: what SearchByProjection returned */
+    int32_t* match;        /* [N_cur] keyframe feature assigned to current feature i by this call, or -1 */
+    int32_t* mp_id;        /* [N_cur] the handle's ids after the call */
+    float* u; float* v; int32_t* level; uint8_t* valid;   /* optional taps [N_kf] (all four or none); u = v = 0, level = 0 where valid is 0 */
+} ccm_reloc_search_result;
+int ccm_frame_search_by_projection_keyframe(ccm_ctx*, ccm_frame* cur, const ccm_frame* kf, ccm_map_table*, const ccm_reloc_view*, float th,
+                                            int orb_dist, int check_ori, int n_found, const int32_t* found, ccm_reloc_search_result*);
+
+/* One relocalisation candidate from the PnP pose to the verdict, in one call: the body of the candidate loop of ORB-SLAM's
+ * Tracking::Relocalization behind PnPsolver::iterate.  The reference has no such function -- its Tracking stays LOST
+ * (src/Tracking.cpp:187-201) -- so the steps are defined here, with ORB-SLAM's nesting and its thresholds as the defaults in brackets:
+ *   1. Matches: cur's ids all become -1, then feature[j] receives slot[j] for each of the n_matched PnP inliers (vbInliers of
+ *      ccm_pnp_solver_iterate over the candidate's vpMapPointMatches).  found = those slots.  pose7 = ccm_pose_from_mat4f(Tcw).
+ *   2. First pose: n_good = the pose optimisation, exactly ccm_frame_pose_optimize_table from pose7.  n_good < min_good [10]: success =
+ *      0 and the call stops (the ids stay the inliers).  Otherwise the features with outlier != 0 lose their id; found keeps them.
+ *   3. First search, only if n_good < enough [50]: n_add1 = ccm_frame_search_by_projection_keyframe with found, th1 [10] and dist1
+ *      [100]; its Tcw / Ow are those of pose7 (the definition of ccm_pose_to_camera, evaluated on the device: the pose is not read
+ *      back for it), the rest of the view is `view`.
+ *   4. Second pose, only if 3 ran and n_good + n_add1 >= enough: n_good = the pose again from the current pose7.  The outliers keep
+ *      their ids.
+ *   5. Second search, only if 4 ran and narrow_above [30] < n_good < enough: found = every id cur holds now; n_add2 = the search with
+ *      th2 [3] and dist2 [64] at the new pose7.
+ *   6. Third pose, only if 5 ran and n_good + n_add2 >= enough: n_good = the pose once more; the outliers lose their id.
+ *   7. success = n_good >= enough.  On success the handle's pose is set as ccm_frame_set_pose(cur, ccm_pose_to_camera(pose7)) would.
+ * stages has one bit per stage that ran (CCM_RELOC_*); n_add of a search that did not run is 0; outlier is that of the last pose that
+ * ran; mp_id and the handle agree after the call.
+ * Traffic: one page-locked copy up (pose7, intr, inv_level_sigma2, and 8 bytes per inlier); nothing per map point.  Every stage
+ * decides the next, so each ends in ONE read-back and stream synchronisation and nothing is queued between them that is waited for:
+ * a pose stage brings n_inliers, the bad-id word, outlier and pose7 (N_cur + 184 bytes and the padding), a search stage what
+ * ccm_frame_search_by_projection_keyframe reads back.  "The outliers lose their id" is decided on the device from n_inliers, behind
+ * the pose and in front of its read-back.  Synchronisations per path: stop at 2, or success at once: 1; search 1 failing the sum: 2;
+ * searches 1 and pose 2 with n_good outside (narrow_above, enough): 3; search 2 failing the sum: 4; all stages: 5.  On the host
+ * acceptance route each search fetches the candidate lists and what its loops read as well.
+ * Errors leave cur's ids as they were on entry (they are kept aside and put back).  CCM_E_ARG: a NULL ctx, cur, kf, table, params,
+ * result, Tcw, intr, inv_level_sigma2, scale_factors, feature or slot (n_matched > 0), mp_id or outlier (N_cur > 0); n_matched < 0;
+ * n_levels outside 1..CCM_MAX_LEVELS; cur == kf; a handle or table of another context; check_ori with a handle that has no angles;
+ * a feature outside [0, N_cur) or named twice; a slot outside the table or not LIVE; an octave of cur that is >= n_levels; an id of
+ * kf outside the table or not LIVE (found by the first search).  CCM_E_STATE: a handle or table that outlived its context. */
+enum { CCM_RELOC_POSE1 = 1, CCM_RELOC_SEARCH1 = 2, CCM_RELOC_POSE2 = 4, CCM_RELOC_SEARCH2 = 8, CCM_RELOC_POSE3 = 16 };
+typedef struct {
+    const float* Tcw;                   /* [16] the 4x4 float of ccm_pnp_solver_iterate */
+    int32_t n_matched;                  /* PnP inliers */
+    const int32_t* feature;             /* [n_matched] feature of cur, each once */
+    const int32_t* slot;                /* [n_matched] its map point's table slot */
+    const double* intr;                 /* [4] fx, fy, cx, cy of the pose optimisation */
+    const float* inv_level_sigma2;      /* [view.n_levels] */
+    ccm_reloc_view view;                /* of the searches; its Tcw and Ow are not read */
+    int32_t min_good, enough, narrow_above;             /* 10, 50, 30 */
+    float th1; int32_t dist1;           /* 10, 100 */
+    float th2; int32_t dist2;           /* 3, 64 */
+    int32_t check_ori;                  /* 1 */
+} ccm_reloc_params;
+typedef struct {
+    int32_t success;       /* 7. */
+    int32_t n_good;        /* nGood of the last pose that ran */
+    int32_t stages;        /* CCM_RELOC_* bits of the stages that ran */
+    int32_t n_add1, n_add2;/* what the two searches returned */
+    double  pose7[7];      /* ccm_pose_from_mat4f(Tcw), optimised by every pose stage */
+    int32_t* mp_id;        /* [N_cur] the handle's ids after the call */
+    uint8_t* outlier;      /* [N_cur] mvbOutlier of the last pose that ran */
+} ccm_reloc_result;
+int ccm_frame_relocalize_candidate(ccm_ctx*, ccm_frame* cur, const ccm_frame* kf, ccm_map_table*, const ccm_reloc_params*, ccm_reloc_result*);
+
 /* ORBmatcher::Fuse, both overloads (src/ORBmatcher.cpp:854-1000 and :1002-1122), up to and including the selection, on keyframe
  * handles and the table: ONE list of map points is projected into EVERY keyframe, as LoopFinder::SearchAndFuse (src/LoopFinder.cpp:
  * 806-831), MapMerger::SearchAndFuse (src/MapMerger.cpp:574-600) and the first loop of LocalMapping::SearchInNeighbors
@@ -1290,6 +1398,41 @@ int ccm_pnp_compute_pose(int n, const float* P3Dw, const float* P2D, const float
  * (grow-only, reused by the next batch); the solver object holds host memory only and belongs to the thread that made it.  On an
  * error *out is untouched. */
 int ccm_pnp_solver_create(ccm_ctx*, const ccm_pnp_ransac_problem*, ccm_pnp_solver** out);
+/* ccm_pnp_solver_create with the constructor's loop (:69-91) on the device: correspondence e is named by two 4-byte numbers, feature
+ * i = feature[e] of the current frame's handle and slot[e], the table slot of vpMapPointMatches[i], in the place of P2D, P3Dw,
+ * sigma2 and kp_index (24 bytes).  k_pnp_gather, one thread per correspondence in front of k_pnp_hypotheses, fills the same three
+ * device arrays the array route uploads: P2D = (kx[i], ky[i]) of the handle, P3D = the slot's pos, max_err = level_sigma2[oct[i]] *
+ * th2 in float, the product ccm_pnp_solver_create forms.  kp_index is feature and n1[k] is the handle's N for every solver, so
+ * iterate's inliers has N entries.  Everything else -- first, K (per solver), the RANSAC parameters, draws, flags, the two solver
+ * kernels and the host replay -- is ccm_pnp_solver_create's, and the solver object answers every ccm_pnp_solver_* call alike: for
+ * the same frame, table rows and draws both routes store the same bits.  The caller still filters "set and not bad" (:75-80): it
+ * needs N_k for its draws.
+ * Errors, each CCM_E_ARG with *out untouched: n_levels outside 1..CCM_MAX_LEVELS; a feature outside [0, N) or a slot outside the
+ * table (found on the host); a slot that is not LIVE or an octave outside [0, n_levels) (found by the kernel, which writes zeros for
+ * that correspondence and never forms the address; reported with the first download, before the refinements).  When no solver has
+ * enough correspondences to evaluate a hypothesis nothing is launched and only the host checks run.  BAD is not an error: a caller
+ * that keeps a bad point gets its position, as the array route would.
+ * Traffic: the upload is 8 bytes per correspondence plus 64 bytes of level_sigma2, 16 per hypothesis and 64 per solver as before;
+ * downloads and the two synchronisations are those of ccm_pnp_solver_create.  Reads the table's rows (a shared lock). */
+typedef struct {
+    int32_t        n_solvers;
+    const int32_t* first;        /* [n_solvers+1], as ccm_pnp_ransac_problem */
+    const float*   K;            /* [n_solvers][4] */
+    const int32_t* feature;      /* [..] feature of cur (mvKeyPointIndices) */
+    const int32_t* slot;         /* [..] table slot */
+    const float*   level_sigma2; /* [n_levels] mvLevelSigma2 */
+    int32_t        n_levels;
+    double         probability;  /* the rest as ccm_pnp_ransac_problem */
+    int32_t        min_inliers;
+    int32_t        max_iterations;
+    int32_t        min_set;
+    float          epsilon;
+    float          th2;
+    int32_t        reserve;
+    const int32_t* draws;
+    uint32_t       flags;
+} ccm_pnp_frames_problem;
+int ccm_pnp_solver_create_frames(ccm_ctx*, ccm_frame* cur, ccm_map_table* table, const ccm_pnp_frames_problem*, ccm_pnp_solver** out);
 /* NULL is a no-op. */
 void ccm_pnp_solver_destroy(ccm_pnp_solver*);
 /* n_solvers of the batch, or CCM_E_ARG for NULL. */
@@ -1681,6 +1824,24 @@ int ccm_kfdb_shortlist(int n_slots, const int32_t* words, const double* score, c
 int ccm_kfdb_candidates(int n_slots, const int32_t* words, const double* score, const int64_t* seq, const uint8_t* eligible, int query_slot,
                         float min_score, int min_common_words, int n_shortlist, const int32_t* shortlist, const int32_t* neighbours,
                         int32_t* candidates);
+/* DetectRelocalizationCandidates(Frame&) (:329-439) over the arrays of one ccm_kfdb_query_vector call, on the host; needs no device.
+ * Step A is ccm_kfdb_shortlist itself with every slot eligible, query_slot = -1 and min_score = -INFINITY: the walk (:337-352) lists
+ * every entry with words > 0 in (first_word, seq) order, minCommonWords = (int)(maxCommonWords * 0.8f) (:365) and the gate is the
+ * strict words > minCommonWords (:376); there is no score test.
+ * Step B, this call (:372-436), all in float as there.  mRelocScore lives on the keyframe and survives from one query to the next:
+ * it is the caller's reloc_score [n_slots], in and out.  First every shortlisted entry stores (float)score there (:380).  Then, per
+ * shortlisted entry in order, acc = best = (float)score and bestKF = the entry; a neighbour (neighbours[i * CCM_KFDB_NEIGHBOURS + k]
+ * as for ccm_kfdb_candidates, -1 or a free slot skipped) counts when it is listed, i.e. words > 0 -- mRelocQuery == F.mId (:403) --
+ * whether or not it passed the gate; a counting neighbour adds reloc_score[nb], which is the value an EARLIER query left there when
+ * this query did not gate it, and replaces bestKF when that value is strictly greater than best.  bestAccScore starts at 0 (:389,
+ * not at a min_score); retain = 0.75f * bestAccScore; candidates (room for n_shortlist) = the bestKF of the entries with acc >
+ * retain, in shortlist order, each once.  Returns their number; n_shortlist = 0 gives 0 and touches nothing; a shortlist entry
+ * outside [0, n_slots) is CCM_E_ARG with reloc_score untouched.
+ * One deviation: the reference never initialises mRelocScore (src/KeyFrame.cpp:56), so a listed neighbour that no query has gated
+ * reads an indeterminate value there; here it reads what the caller put into the array.  The Python KeyFrameDatabase and the shim
+ * put 0 there when a slot is taken by add (a reused slot included). */
+int ccm_kfdb_reloc_candidates(int n_slots, const int32_t* words, const double* score, const int64_t* seq, int n_shortlist,
+                              const int32_t* shortlist, const int32_t* neighbours, float* reloc_score, int32_t* candidates);
 /* minScore of LoopFinder.cpp:122-139 / MapMatcher.cpp:130-147 from the arrays of the SAME query: float 1, lowered to the least
  * (float)score of the connected slots; -1 and free slots are skipped (pass the keyframes that are not bad). */
 float ccm_kfdb_min_score(int n_slots, const double* score, const int64_t* seq, int n_connected, const int32_t* connected);

@@ -41,18 +41,20 @@ SYMBOLS = [
     "ccm_frame_set_bow", "ccm_frame_set_camera", "ccm_frame_set_pose", "ccm_frame_debug_bow", "ccm_fuse_select_batch_frames",
     "ccm_map_table_create", "ccm_map_table_destroy", "ccm_map_table_capacity", "ccm_map_table_update", "ccm_map_table_set_order",
     "ccm_map_table_fetch", "ccm_map_table_refresh", "ccm_map_table_correct_frames", "ccm_map_table_attach", "ccm_map_table_handles", "ccm_frame_search_local_points", "ccm_frame_search_local_points_timing", "ccm_frame_pose_optimize_table",
-    "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model",
+    "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model", "ccm_frame_search_by_projection_keyframe",
+    "ccm_frame_relocalize_candidate",
     "ccm_search_by_sim3_table_frames", "ccm_search_by_projection_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_pnp_ransac_parameters", "ccm_pnp_compute_pose", "ccm_pnp_solver_create", "ccm_pnp_solver_destroy", "ccm_pnp_solver_count",
     "ccm_pnp_solver_iterate", "ccm_pnp_solver_find", "ccm_pnp_solver_state", "ccm_pnp_solver_hypotheses", "ccm_pnp_solver_refinements",
+    "ccm_pnp_solver_create_frames",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
     "ccm_frame_compute_bow", "ccm_frame_search_by_bow", "ccm_search_by_bow_frames",
     "ccm_undistort_points", "ccm_image_bounds", "ccm_frame_from_extract_camera", "ccm_frames_from_extract_camera", "ccm_frame_get_keypoints",
     "ccm_kfdb_create", "ccm_kfdb_destroy", "ccm_kfdb_add", "ccm_kfdb_erase", "ccm_kfdb_clear", "ccm_kfdb_size", "ccm_kfdb_slot", "ccm_kfdb_slots",
     "ccm_kfdb_keys", "ccm_kfdb_query", "ccm_kfdb_query_vector", "ccm_kfdb_query_lds_words", "ccm_kfdb_arena", "ccm_kfdb_last_timing",
-    "ccm_kfdb_shortlist", "ccm_kfdb_candidates", "ccm_kfdb_min_score",
+    "ccm_kfdb_shortlist", "ccm_kfdb_candidates", "ccm_kfdb_min_score", "ccm_kfdb_reloc_candidates",
 ]
 
 
@@ -120,6 +122,13 @@ class Sim3RansacProblem(C.Structure):
 class PnpRansacProblem(C.Structure):                  # ccm_pnp_ransac_problem
     _fields_ = [("n_solvers", C.c_int32), ("first", C.c_void_p), ("n1", C.c_void_p), ("K", C.c_void_p), ("P2D", C.c_void_p),
                 ("P3Dw", C.c_void_p), ("sigma2", C.c_void_p), ("kp_index", C.c_void_p), ("probability", C.c_double),
+                ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float),
+                ("th2", C.c_float), ("reserve", C.c_int32), ("draws", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class PnpFramesProblem(C.Structure):                  # ccm_pnp_frames_problem
+    _fields_ = [("n_solvers", C.c_int32), ("first", C.c_void_p), ("K", C.c_void_p), ("feature", C.c_void_p), ("slot", C.c_void_p),
+                ("level_sigma2", C.c_void_p), ("n_levels", C.c_int32), ("probability", C.c_double),
                 ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32), ("epsilon", C.c_float),
                 ("th2", C.c_float), ("reserve", C.c_int32), ("draws", C.c_void_p), ("flags", C.c_uint32)]
 
@@ -231,6 +240,32 @@ class TmmResult(C.Structure):
     _fields_ = [("n_matches", C.c_int32), ("passes", C.c_int32), ("posed", C.c_int32), ("n_inliers", C.c_int32),
                 ("n_matches_map", C.c_int32), ("pose7", C.c_double * 7), ("match", C.c_void_p), ("mp_id", C.c_void_p),
                 ("outlier", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class RelocView(C.Structure):                         # ccm_reloc_view
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factors", C.c_void_p), ("log_scale_factor", C.c_float)]
+
+
+class RelocSearchResult(C.Structure):                 # ccm_reloc_search_result
+    _fields_ = [("n_matches", C.c_int32), ("match", C.c_void_p), ("mp_id", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+                ("level", C.c_void_p), ("valid", C.c_void_p)]
+
+
+RELOC_POSE1, RELOC_SEARCH1, RELOC_POSE2, RELOC_SEARCH2, RELOC_POSE3 = 1, 2, 4, 8, 16      # CCM_RELOC_*
+
+
+class RelocParams(C.Structure):                       # ccm_reloc_params
+    _fields_ = [("Tcw", C.c_void_p), ("n_matched", C.c_int32), ("feature", C.c_void_p), ("slot", C.c_void_p), ("intr", C.c_void_p),
+                ("inv_level_sigma2", C.c_void_p), ("view", RelocView), ("min_good", C.c_int32), ("enough", C.c_int32),
+                ("narrow_above", C.c_int32), ("th1", C.c_float), ("dist1", C.c_int32), ("th2", C.c_float), ("dist2", C.c_int32),
+                ("check_ori", C.c_int32)]
+
+
+class RelocResult(C.Structure):                       # ccm_reloc_result
+    _fields_ = [("success", C.c_int32), ("n_good", C.c_int32), ("stages", C.c_int32), ("n_add1", C.c_int32), ("n_add2", C.c_int32),
+                ("pose7", C.c_double * 7), ("mp_id", C.c_void_p), ("outlier", C.c_void_p)]
 
 
 FG_GATES = ("SEARCHED", "SKIPPED", "IN_KEYFRAME", "BEHIND", "OUTSIDE", "DISTANCE", "ANGLE", "EMPTY_KF")   # CCM_FG_* of include/ccm_hot.h
@@ -439,6 +474,9 @@ def load():
     lib.ccm_search_by_sim3_table_frames.argtypes = [vp, vp, C.POINTER(Sim3SearchProblem), C.POINTER(Sim3SearchResult)]
     lib.ccm_search_by_projection_table_frames.argtypes = [vp, vp, C.POINTER(LoopProjectionProblem), C.POINTER(LoopProjectionResult)]
     lib.ccm_frame_track_motion_model.argtypes = [vp, vp, vp, vp, C.POINTER(TmmParams), C.POINTER(TmmResult)]
+    lib.ccm_frame_search_by_projection_keyframe.argtypes = [vp, vp, vp, vp, C.POINTER(RelocView), C.c_float, C.c_int, C.c_int, C.c_int, vp,
+                                                            C.POINTER(RelocSearchResult)]
+    lib.ccm_frame_relocalize_candidate.argtypes = [vp, vp, vp, vp, C.POINTER(RelocParams), C.POINTER(RelocResult)]
     lib.ccm_sim3_ransac_iterations.argtypes =[C.c_int, C.c_double, C.c_int, C.c_int]
     lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]
     lib.ccm_sim3_solver_destroy.argtypes = [vp]; lib.ccm_sim3_solver_destroy.restype = None
@@ -459,6 +497,7 @@ def load():
         lib.ccm_pnp_solver_state.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
         lib.ccm_pnp_solver_hypotheses.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
         lib.ccm_pnp_solver_refinements.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.ccm_pnp_solver_create_frames.argtypes = [vp, vp, vp, C.POINTER(PnpFramesProblem), C.POINTER(vp)]
     lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
     lib.ccm_create_new_map_points.argtypes = [vp, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)]
     lib.ccm_create_new_map_points_frames.argtypes = [vp, C.POINTER(NewPointsFrames), C.POINTER(NewPointsResult)]
@@ -482,6 +521,7 @@ def load():
         lib.ccm_kfdb_last_timing.argtypes = [vp, vp]
         lib.ccm_kfdb_shortlist.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, vp, vp]
         lib.ccm_kfdb_candidates.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp]
+        lib.ccm_kfdb_reloc_candidates.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         lib.ccm_kfdb_min_score.argtypes = [C.c_int, vp, vp, C.c_int, vp]; lib.ccm_kfdb_min_score.restype = C.c_float
     _lib = lib
     return lib

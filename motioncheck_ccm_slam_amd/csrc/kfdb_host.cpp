@@ -2,6 +2,7 @@
 // KeyFrameDatabase::add / erase / clear (src/Database.cpp:37-70), the per-entry query that replaces the inverted-file walk of
 // DetectLoopCandidates / DetectMapMatchCandidates (:72-327), and the ordered remainder of those two functions replayed on the
 // host over the query's arrays (ccm_kfdb_shortlist, ccm_kfdb_candidates), as ccm_sim3_solver_iterate replays Sim3Solver::iterate.
+// DetectRelocalizationCandidates (:329-439) is the same shortlist followed by ccm_kfdb_reloc_candidates.
 #include "ccm_internal.h"
 #include "kfdb_types.h"
 #include <cmath>
@@ -410,6 +411,48 @@ int ccm_kfdb_candidates(int n_slots, const int32_t* words, const double* score, 
             if (a > best_acc) best_acc = a;
         }
         const float retain = 0.75f * best_acc;                                  // :181
+        int n = 0;
+        for (int i = 0; i < n_shortlist; i++) {
+            if (!(acc[i] > retain)) continue;
+            bool seen = false;
+            for (int j = 0; j < n && !seen; j++) seen = candidates[j] == best_kf[i];
+            if (!seen) candidates[n++] = best_kf[i];
+        }
+        return n;
+    });
+}
+
+// The covisibility accumulation of DetectRelocalizationCandidates (src/Database.cpp:372-436) behind ccm_kfdb_shortlist.  mRelocScore is
+// the caller's reloc_score: a neighbour that shares a word with the query (mRelocQuery == F.mId, :403) counts whether this query
+// scored it or not, with whatever the array holds for it.
+int ccm_kfdb_reloc_candidates(int n_slots, const int32_t* words, const double* score, const int64_t* seq, int n_shortlist,
+                              const int32_t* shortlist, const int32_t* neighbours, float* reloc_score, int32_t* candidates)
+{
+    RoctxRange roctx_("ccm_kfdb_reloc_candidates");
+    if (n_slots < 0 || n_shortlist < 0 || (n_shortlist > 0 && (!words || !score || !seq || !shortlist || !neighbours || !reloc_score || !candidates)))
+        return CCM_E_ARG;
+    for (int i = 0; i < n_shortlist; i++) if (shortlist[i] < 0 || shortlist[i] >= n_slots) return CCM_E_ARG;
+    return ccm_guard(nullptr, "ccm_kfdb_reloc_candidates", [&]() -> int {
+        for (int i = 0; i < n_shortlist; i++) reloc_score[shortlist[i]] = (float)score[shortlist[i]];       // :379-380, all before :392
+        std::vector<float> acc(n_shortlist);
+        std::vector<int32_t> best_kf(n_shortlist);
+        float best_acc = 0;                                                     // :389
+        for (int i = 0; i < n_shortlist; i++) {
+            const int32_t s = shortlist[i];
+            float best = (float)score[s], a = best;                             // it->first
+            int32_t kf = s;
+            for (int k = 0; k < CCM_KFDB_NEIGHBOURS; k++) {
+                const int32_t nb = neighbours[(size_t)i * CCM_KFDB_NEIGHBOURS + k];
+                if (nb < 0 || nb >= n_slots) continue;
+                if (seq[nb] < 0 || !(words[nb] > 0)) continue;                  // :403
+                const float sn = reloc_score[nb];
+                a += sn;
+                if (sn > best) { kf = nb; best = sn; }
+            }
+            acc[i] = a; best_kf[i] = kf;
+            if (a > best_acc) best_acc = a;
+        }
+        const float retain = 0.75f * best_acc;                                  // :420
         int n = 0;
         for (int i = 0; i < n_shortlist; i++) {
             if (!(acc[i] > retain)) continue;

@@ -21,6 +21,7 @@
 #include <cstdint>
 #include "../../include/ccm_hot.h"
 #include "mpt_types.h"
+#include "mpt_device.h"
 
 // ---------------------------------------------------------------------------------------------------------------- table rows
 __global__ void k_mpt_scatter(MptTable T, int n, const int* slot, const float* pos, const float* normal, const float* min_dist,
@@ -77,21 +78,7 @@ __global__ void k_slp_mark(MptTable T, int n, const int* mp_id, int stamp, int* 
 // ---------------------------------------------------------------------------------------------------------------- second loop
 __device__ inline int slp_slot(const SlpArgs& A, int j) { return A.order ? A.order[j] : j; }
 
-// The projection both SearchLocalPoints and TrackWithMotionModel's SearchByProjection(Current, Last) use (src/Frame.cpp:150-163,
-// src/ORBmatcher.cpp:1380-1396): Pc = Rcw P + tcw summed in double and stored as float, invz = 1 / PcZ, u = fx * PcX * invz + cx in
-// float, left to right, every operation rounded (the build's -ffp-contract=off keeps the compiler from fusing them).  What rejects a
-// point behind the camera differs between the two callers and stays with them.
-__device__ inline void mpt_to_camera(const float* Tcw, const float* P, float* Pc)
-{
-    for (int r = 0; r < 3; r++)
-        Pc[r] = (float)((double)Tcw[4 * r] * (double)P[0] + (double)Tcw[4 * r + 1] * (double)P[1] + (double)Tcw[4 * r + 2] * (double)P[2] +
-                        (double)Tcw[4 * r + 3]);
-}
-__device__ inline void mpt_pinhole(float fx, float fy, float cx, float cy, const float* Pc, float invz, float& u, float& v)
-{
-    u = fx * Pc[0] * invz + cx;
-    v = fy * Pc[1] * invz + cy;
-}
+// (mpt_to_camera and mpt_pinhole, the projection of SearchLocalPoints and TrackWithMotionModel: mpt_device.h)
 
 // Frame::isInFrustum + PredictScale for one point, in the arithmetic of float cv::Mat expressions (map_math.h: the products of
 // a matrix product, dot and norm are summed in double and stored as float; everything else is float, left to right).
@@ -356,15 +343,7 @@ __global__ void k_fuse_held(FuseArgs A, int capacity)
     if ((unsigned)(w >> 32) == A.stamp && pos < (unsigned)A.n_points) A.held[(size_t)k * A.n_points + pos] = 1;   // several features: same value
 }
 
-// MapPoint::PredictScale (src/MapPoint.cpp:837-852) with the raw mfMaxDistance, the expression slp_in_frustum ends with: the double log
-// rounded to float, ceilf, clamped; a NaN gives 0
-__device__ inline int fuse_predict_level(float max_d, float dist, float log_scale, int n_levels)
-{
-    const float ratio = max_d / dist;
-    const float lg = (float)log((double)ratio);
-    const float q = ceilf(lg / log_scale);
-    return !(q >= 0.0f) ? 0 : (q >= (float)n_levels ? n_levels - 1 : (int)q);
-}
+// (fuse_predict_level, MapPoint::PredictScale: mpt_device.h)
 
 // One thread per (keyframe, point) pair; blockIdx.y = the keyframe, so the view is the same for the whole workgroup and is read
 // through scalar loads.  Arithmetic of a float cv::Mat as in slp_in_frustum (products of a matrix product, dot and norm summed in

@@ -9,7 +9,7 @@
 // found by a scan over the counts on the host after the first download: the counts are needed on the host anyway, the scan is a
 // few hundred comparisons per solver, and a device scan would save neither of the two synchronisations (the mask and pose of the
 // hypotheses come down with the counts).
-#include "staging.h"
+#include "mpt_internal.h"
 #include "pnp_types.h"
 #include "pnp_math.h"
 #include <cmath>
@@ -90,148 +90,205 @@ extern "C" int ccm_pnp_compute_pose(int n, const float* P3Dw, const float* P2D, 
     });
 }
 
+// Where the correspondences of ccm_pnp_solver_create_frames come from: feature / slot [first[n_solvers]] name a feature of `cur` and a
+// slot of `t`; k_pnp_gather fills the P2D / P3D / max_err segments from them.  pb then carries no P2D / P3Dw / sigma2, and kp_index =
+// feature.
+struct PnpFrames { const ccm_frame* cur; const ccm_map_table* t; const int32_t* feature; const int32_t* slot; const float* level_sigma2; int n_levels; };
+
+// The body of both create calls (fr == nullptr: the correspondences are the caller's arrays), under the caller's ccm_guard.
+static int pnp_create(ccm_ctx* c, const ccm_pnp_ransac_problem* pb, const PnpFrames* fr, ccm_pnp_solver** out)
+{
+    if (!pb || !out || pb->n_solvers < 0) return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem");
+    if (pb->min_set < 4 || pb->min_set > PNP_MAXSET) return ccm_fail(c, CCM_E_ARG, "min_set = %d outside [4, %d]", pb->min_set, PNP_MAXSET);
+    if (pb->max_iterations < 1 || pb->min_inliers < 0 || pb->reserve < 0)
+        return ccm_fail(c, CCM_E_ARG, "bad RANSAC parameters: max_iterations %d, min_inliers %d, reserve %d", pb->max_iterations, pb->min_inliers, pb->reserve);
+    const int F = pb->n_solvers, ms = pb->min_set;
+    std::unique_ptr<ccm_pnp_solver> S(new ccm_pnp_solver());
+    S->min_set = ms; S->detail = (pb->flags & 1u) != 0;
+    if (F == 0) { *out = S.release(); return CCM_OK; }
+    if (!pb->first || !pb->n1 || !pb->K) return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem: null per-solver array");
+    if (pb->first[0] != 0) return ccm_fail(c, CCM_E_ARG, "first[0] must be 0");
+    for (int f = 0; f < F; f++) if (pb->first[f + 1] < pb->first[f]) return ccm_fail(c, CCM_E_ARG, "first[] must be non-decreasing");
+    const size_t T = (size_t)pb->first[F];
+    if (T > 0 && (!pb->kp_index || (fr ? !fr->slot : (!pb->P2D || !pb->P3Dw || !pb->sigma2))))
+        return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem: null correspondence array");
+    if (fr)
+        for (size_t e = 0; e < T; e++)
+            if (fr->slot[e] < 0 || fr->slot[e] >= fr->t->capacity)
+                return ccm_fail(c, CCM_E_ARG, "correspondence %zu: slot %d outside [0, %d)", e, fr->slot[e], fr->t->capacity);
+
+    // ---- per-solver geometry of the batch, and the checks that keep every index the kernels and iterate() form in range
+    S->k.resize(F);
+    const size_t rows = (size_t)pb->max_iterations + (size_t)pb->reserve;       // rows of draws per solver
+    size_t H = 0, W = 0, n_blocks = 0, Rmax = 0, RWmax = 0;
+    for (int f = 0; f < F; f++) {
+        PnpHost& k = S->k[f];
+        k.first = (size_t)pb->first[f]; k.n = pb->first[f + 1] - pb->first[f]; k.n1 = pb->n1[f];
+        if (k.n1 < 0) return ccm_fail(c, CCM_E_ARG, "solver %d: n1 = %d", f, k.n1);
+        for (int i = 0; i < k.n; i++) {
+            const int32_t kp = pb->kp_index[k.first + i];
+            if (kp < 0 || kp >= k.n1) return ccm_fail(c, CCM_E_ARG, "solver %d: kp_index[%d] = %d outside [0, %d)", f, i, kp, k.n1);
+        }
+        int32_t mi = 0, it = 1;
+        ccm_pnp_ransac_parameters(k.n, pb->probability, pb->min_inliers, pb->max_iterations, ms, pb->epsilon, &mi, &it, nullptr);
+        k.min_inliers = mi; k.max_its = it;
+        k.n_hyp = k.n >= k.min_inliers ? (int)std::min<size_t>((size_t)k.max_its + pb->reserve, (size_t)INT32_MAX / 64) : 0;
+        k.words = (k.n + 63) / 64;
+        k.hyp_first = (int)H; k.mask_first = W;
+        H += (size_t)k.n_hyp; W += (size_t)k.n_hyp * k.words;
+        n_blocks += ((size_t)k.n_hyp + PNP_HPB - 1) / PNP_HPB;
+        // records have strictly increasing counts in [min_inliers, N]
+        const size_t rmax = k.n_hyp ? std::min<size_t>((size_t)k.n_hyp, (size_t)(k.n - k.min_inliers + 1)) : 0;
+        Rmax += rmax; RWmax += rmax * k.words;
+        if (H > (size_t)INT32_MAX / 256) return ccm_fail(c, CCM_E_ARG, "too many hypotheses in one batch");
+    }
+    if (H > 0 && !pb->draws) return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem: null draws");
+    S->sample.assign(H * (size_t)ms, 0);
+    for (int f = 0; f < F; f++) {
+        const PnpHost& k = S->k[f];
+        const int32_t* d = pb->draws + (size_t)f * rows * ms;
+        for (int h = 0; h < k.n_hyp; h++) {
+            for (int i = 0; i < ms; i++)
+                if (d[ms * h + i] < 0 || d[ms * h + i] > k.n - 1 - i)
+                    return ccm_fail(c, CCM_E_ARG, "solver %d, hypothesis %d: draw %d = %d outside [0, %d]", f, h, i, d[ms * h + i], k.n - 1 - i);
+            pnp_sample(k.n, ms, d + (size_t)ms * h, S->sample.data() + ((size_t)k.hyp_first + h) * ms);       // :178-192
+        }
+    }
+    S->kp_index.assign(pb->kp_index, pb->kp_index + T);
+    if (H == 0) { *out = S.release(); return CCM_OK; }                  // nothing to evaluate: every solver reports bNoMore
+
+    // ---- staging: [solvers | blocks | sample | P2D | P3D | max_err] up, [status | count | Rt | mask | detail] down, then [records]
+    // up and [count | Rt | mask | detail] of the refinements down.  With frames [feature | slot | level_sigma2] go up in the place
+    // of P2D | P3D | max_err, which k_pnp_gather fills on the device.
+    const size_t DB = S->detail ? (size_t)PNP_DETAIL * 8 : 0;
+    size_t off = 0;
+    const size_t o_solvers = seg(off, (size_t)F * sizeof(PnpSolver)), o_blocks = seg(off, n_blocks * sizeof(PnpBlock));
+    const size_t o_sample = seg(off, H * PNP_MAXSET * 4);
+    const size_t o_feat = seg(off, fr ? T * 4 : 0), o_slot = seg(off, fr ? T * 4 : 0), o_sig = seg(off, fr ? CCM_MAX_LEVELS * 4 : 0);
+    const size_t up_end = off;                                          // with frames: the end of the upload
+    const size_t o_p2 = seg(off, T * 8), o_p3 = seg(off, T * 12), o_me = seg(off, T * 4);
+    const size_t in_end = off;
+    const size_t o_status = seg(off, 16);
+    const size_t o_count = seg(off, H * 4), o_rt = seg(off, H * 96), o_mask = seg(off, W * 8), o_det = seg(off, H * DB);
+    const size_t out_end = off;
+    const size_t o_rec = seg(off, Rmax * sizeof(PnpRecord));
+    const size_t rec_end = off;
+    const size_t o_rcount = seg(off, Rmax * 4), o_rrt = seg(off, Rmax * 96), o_rmask = seg(off, RWmax * 8), o_rdet = seg(off, Rmax * DB);
+    const size_t end = off;
+    CCM_HIP(c, hipSetDevice(c->device));
+    if (!c->pnp) c->pnp = new PnpState();
+    Staging& G = c->pnp->stage;
+    int rc;
+    if ((rc = G.reserve(c, end))) return rc;
+    PnpSolver* hs = G.host<PnpSolver>(o_solvers);
+    PnpBlock* hb = G.host<PnpBlock>(o_blocks);
+    int32_t* hsm = G.host<int32_t>(o_sample);
+    size_t nb = 0;
+    for (int f = 0; f < F; f++) {
+        const PnpHost& k = S->k[f];
+        PnpSolver& s = hs[f];
+        std::memset(&s, 0, sizeof s);
+        s.first = (int32_t)k.first; s.n = k.n; s.hyp_first = k.hyp_first; s.n_hyp = k.n_hyp; s.words = k.words; s.min_set = ms;
+        s.mask_first = (int64_t)k.mask_first;
+        std::memcpy(s.K, pb->K + 4 * f, 16);
+        for (int h0 = 0; h0 < k.n_hyp; h0 += PNP_HPB) hb[nb++] = PnpBlock{ f, h0, std::min(PNP_HPB, k.n_hyp - h0), 0 };
+        for (int h = 0; h < k.n_hyp; h++)
+            for (int i = 0; i < PNP_MAXSET; i++)
+                hsm[((size_t)k.hyp_first + h) * PNP_MAXSET + i] = i < ms ? S->sample[((size_t)k.hyp_first + h) * ms + i] : 0;
+    }
+    const PnpDev D{ G.dev<PnpSolver>(o_solvers), G.dev<PnpBlock>(o_blocks), G.dev<float>(o_p2), G.dev<float>(o_p3), G.dev<float>(o_me),
+                    G.dev<int32_t>(o_sample), G.dev<int32_t>(o_count), G.dev<double>(o_rt), G.dev<unsigned long long>(o_mask),
+                    S->detail ? G.dev<double>(o_det) : nullptr };
+    if (fr) {
+        G.put(o_feat, fr->feature, T * 4); G.put(o_slot, fr->slot, T * 4);
+        fill_levels(G.host<float>(o_sig), fr->level_sigma2, fr->n_levels);
+        if ((rc = G.upload(c, 0, up_end))) return rc;
+        CCM_HIP(c, hipMemsetAsync(G.dev<int32_t>(o_status), 0, 16, c->stream));
+        const MptTable& Tb = fr->t->T;
+        pnp_gather_launch(c->stream, PnpGather{ (int32_t)T, fr->cur->n, Tb.capacity, fr->n_levels, pb->th2, G.dev<int32_t>(o_feat), G.dev<int32_t>(o_slot),
+                                                fr->cur->kx, fr->cur->ky, fr->cur->oct, Tb.pos, Tb.flags, G.dev<float>(o_sig),
+                                                G.dev<float>(o_p2), G.dev<float>(o_p3), G.dev<float>(o_me), G.dev<int32_t>(o_status) });
+        CCM_HIP(c, hipGetLastError());
+    } else {
+        float* hme = G.host<float>(o_me);
+        for (size_t e = 0; e < T; e++) hme[e] = pb->sigma2[e] * pb->th2;    // mvMaxError (:146), a float product
+        G.put(o_p2, pb->P2D, T * 8); G.put(o_p3, pb->P3Dw, T * 12);
+        if ((rc = G.upload(c, 0, in_end))) return rc;
+    }
+    pnp_hypotheses_launch(c->stream, D, (int)n_blocks);
+    CCM_HIP(c, hipGetLastError());
+    if ((rc = G.download(c, fr ? o_status : o_count, out_end)) || (rc = G.wait(c))) return rc;
+    if (fr && *G.host<int32_t>(o_status))
+        return ccm_fail(c, CCM_E_ARG, "a correspondence names a feature outside [0, %d), a slot that is not LIVE or an octave outside [0, %d)",
+                        fr->cur->n, fr->n_levels);
+    {
+        const int32_t* rn = G.host<int32_t>(o_count); const double* rr = G.host<double>(o_rt);
+        const uint64_t* rm = G.host<uint64_t>(o_mask); const double* rd = G.host<double>(o_det);
+        S->count.assign(rn, rn + H); S->rt.assign(rr, rr + 12 * H); S->mask.assign(rm, rm + W);
+        if (S->detail) S->det.assign(rd, rd + PNP_DETAIL * H);
+    }
+
+    // ---- the records (see the head of this file), one Refine() each
+    PnpRecord* hr = G.host<PnpRecord>(o_rec);
+    size_t R = 0, RW = 0;
+    for (int f = 0; f < F; f++) {
+        PnpHost& k = S->k[f];
+        k.ref_first = (int)R; k.ref_mask_first = RW;
+        int best = 0;
+        for (int h = 0; h < k.n_hyp; h++) {
+            const int cnt = S->count[(size_t)k.hyp_first + h];
+            if (cnt >= k.min_inliers && cnt > best && cnt <= k.n && R < Rmax && RW + k.words <= RWmax) {      // :200-206
+                best = cnt;
+                hr[R] = PnpRecord{ f, h, (int32_t)R, 0, (int64_t)RW };
+                S->ref_hyp.push_back(h);
+                R++; RW += (size_t)k.words; k.n_ref++;
+            }
+        }
+    }
+    if (R > 0) {
+        if ((rc = G.upload(c, o_rec, o_rec + R * sizeof(PnpRecord)))) return rc;
+        const PnpRefineDev Q{ D.solvers, G.dev<PnpRecord>(o_rec), D.P2D, D.P3D, D.max_err, D.mask, G.dev<int32_t>(o_rcount),
+                              G.dev<double>(o_rrt), G.dev<unsigned long long>(o_rmask), S->detail ? G.dev<double>(o_rdet) : nullptr };
+        pnp_refine_launch(c->stream, Q, (int)R);
+        CCM_HIP(c, hipGetLastError());
+        if ((rc = G.download(c, rec_end, end)) || (rc = G.wait(c))) return rc;
+        const int32_t* rn = G.host<int32_t>(o_rcount); const double* rr = G.host<double>(o_rrt);
+        const uint64_t* rm = G.host<uint64_t>(o_rmask); const double* rd = G.host<double>(o_rdet);
+        S->ref_count.assign(rn, rn + R); S->ref_rt.assign(rr, rr + 12 * R); S->ref_mask.assign(rm, rm + RW);
+        if (S->detail) S->ref_det.assign(rd, rd + PNP_DETAIL * R);
+    }
+    *out = S.release();
+    return CCM_OK;
+}
+
 extern "C" int ccm_pnp_solver_create(ccm_ctx* c, const ccm_pnp_ransac_problem* pb, ccm_pnp_solver** out)
 {
     RoctxRange roctx_("ccm_pnp_solver_create");
     return ccm_guard(c, "ccm_pnp_solver_create", [&]() -> int {
         if (!c) return CCM_E_ARG;
-        if (!pb || !out || pb->n_solvers < 0) return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem");
-        if (pb->min_set < 4 || pb->min_set > PNP_MAXSET) return ccm_fail(c, CCM_E_ARG, "min_set = %d outside [4, %d]", pb->min_set, PNP_MAXSET);
-        if (pb->max_iterations < 1 || pb->min_inliers < 0 || pb->reserve < 0)
-            return ccm_fail(c, CCM_E_ARG, "bad RANSAC parameters: max_iterations %d, min_inliers %d, reserve %d", pb->max_iterations, pb->min_inliers, pb->reserve);
-        const int F = pb->n_solvers, ms = pb->min_set;
-        std::unique_ptr<ccm_pnp_solver> S(new ccm_pnp_solver());
-        S->min_set = ms; S->detail = (pb->flags & 1u) != 0;
-        if (F == 0) { *out = S.release(); return CCM_OK; }
-        if (!pb->first || !pb->n1 || !pb->K) return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem: null per-solver array");
-        if (pb->first[0] != 0) return ccm_fail(c, CCM_E_ARG, "first[0] must be 0");
-        for (int f = 0; f < F; f++) if (pb->first[f + 1] < pb->first[f]) return ccm_fail(c, CCM_E_ARG, "first[] must be non-decreasing");
-        const size_t T = (size_t)pb->first[F];
-        if (T > 0 && (!pb->P2D || !pb->P3Dw || !pb->sigma2 || !pb->kp_index))
-            return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem: null correspondence array");
+        return pnp_create(c, pb, nullptr, out);
+    });
+}
 
-        // ---- per-solver geometry of the batch, and the checks that keep every index the kernels and iterate() form in range
-        S->k.resize(F);
-        const size_t rows = (size_t)pb->max_iterations + (size_t)pb->reserve;       // rows of draws per solver
-        size_t H = 0, W = 0, n_blocks = 0, Rmax = 0, RWmax = 0;
-        for (int f = 0; f < F; f++) {
-            PnpHost& k = S->k[f];
-            k.first = (size_t)pb->first[f]; k.n = pb->first[f + 1] - pb->first[f]; k.n1 = pb->n1[f];
-            if (k.n1 < 0) return ccm_fail(c, CCM_E_ARG, "solver %d: n1 = %d", f, k.n1);
-            for (int i = 0; i < k.n; i++) {
-                const int32_t kp = pb->kp_index[k.first + i];
-                if (kp < 0 || kp >= k.n1) return ccm_fail(c, CCM_E_ARG, "solver %d: kp_index[%d] = %d outside [0, %d)", f, i, kp, k.n1);
-            }
-            int32_t mi = 0, it = 1;
-            ccm_pnp_ransac_parameters(k.n, pb->probability, pb->min_inliers, pb->max_iterations, ms, pb->epsilon, &mi, &it, nullptr);
-            k.min_inliers = mi; k.max_its = it;
-            k.n_hyp = k.n >= k.min_inliers ? (int)std::min<size_t>((size_t)k.max_its + pb->reserve, (size_t)INT32_MAX / 64) : 0;
-            k.words = (k.n + 63) / 64;
-            k.hyp_first = (int)H; k.mask_first = W;
-            H += (size_t)k.n_hyp; W += (size_t)k.n_hyp * k.words;
-            n_blocks += ((size_t)k.n_hyp + PNP_HPB - 1) / PNP_HPB;
-            // records have strictly increasing counts in [min_inliers, N]
-            const size_t rmax = k.n_hyp ? std::min<size_t>((size_t)k.n_hyp, (size_t)(k.n - k.min_inliers + 1)) : 0;
-            Rmax += rmax; RWmax += rmax * k.words;
-            if (H > (size_t)INT32_MAX / 256) return ccm_fail(c, CCM_E_ARG, "too many hypotheses in one batch");
-        }
-        if (H > 0 && !pb->draws) return ccm_fail(c, CCM_E_ARG, "bad PnP RANSAC problem: null draws");
-        S->sample.assign(H * (size_t)ms, 0);
-        for (int f = 0; f < F; f++) {
-            const PnpHost& k = S->k[f];
-            const int32_t* d = pb->draws + (size_t)f * rows * ms;
-            for (int h = 0; h < k.n_hyp; h++) {
-                for (int i = 0; i < ms; i++)
-                    if (d[ms * h + i] < 0 || d[ms * h + i] > k.n - 1 - i)
-                        return ccm_fail(c, CCM_E_ARG, "solver %d, hypothesis %d: draw %d = %d outside [0, %d]", f, h, i, d[ms * h + i], k.n - 1 - i);
-                pnp_sample(k.n, ms, d + (size_t)ms * h, S->sample.data() + ((size_t)k.hyp_first + h) * ms);       // :178-192
-            }
-        }
-        S->kp_index.assign(pb->kp_index, pb->kp_index + T);
-        if (H == 0) { *out = S.release(); return CCM_OK; }                  // nothing to evaluate: every solver reports bNoMore
-
-        // ---- staging: [solvers | blocks | P2D | P3D | max_err | sample] up, [count | Rt | mask | detail] down, then [records] up and
-        // [count | Rt | mask | detail] of the refinements down
-        const size_t DB = S->detail ? (size_t)PNP_DETAIL * 8 : 0;
-        size_t off = 0;
-        const size_t o_solvers = seg(off, (size_t)F * sizeof(PnpSolver)), o_blocks = seg(off, n_blocks * sizeof(PnpBlock));
-        const size_t o_p2 = seg(off, T * 8), o_p3 = seg(off, T * 12), o_me = seg(off, T * 4), o_sample = seg(off, H * PNP_MAXSET * 4);
-        const size_t in_end = off;
-        const size_t o_count = seg(off, H * 4), o_rt = seg(off, H * 96), o_mask = seg(off, W * 8), o_det = seg(off, H * DB);
-        const size_t out_end = off;
-        const size_t o_rec = seg(off, Rmax * sizeof(PnpRecord));
-        const size_t rec_end = off;
-        const size_t o_rcount = seg(off, Rmax * 4), o_rrt = seg(off, Rmax * 96), o_rmask = seg(off, RWmax * 8), o_rdet = seg(off, Rmax * DB);
-        const size_t end = off;
-        CCM_HIP(c, hipSetDevice(c->device));
-        if (!c->pnp) c->pnp = new PnpState();
-        Staging& G = c->pnp->stage;
-        int rc;
-        if ((rc = G.reserve(c, end))) return rc;
-        PnpSolver* hs = G.host<PnpSolver>(o_solvers);
-        PnpBlock* hb = G.host<PnpBlock>(o_blocks);
-        int32_t* hsm = G.host<int32_t>(o_sample);
-        float* hme = G.host<float>(o_me);
-        size_t nb = 0;
-        for (int f = 0; f < F; f++) {
-            const PnpHost& k = S->k[f];
-            PnpSolver& s = hs[f];
-            std::memset(&s, 0, sizeof s);
-            s.first = (int32_t)k.first; s.n = k.n; s.hyp_first = k.hyp_first; s.n_hyp = k.n_hyp; s.words = k.words; s.min_set = ms;
-            s.mask_first = (int64_t)k.mask_first;
-            std::memcpy(s.K, pb->K + 4 * f, 16);
-            for (int h0 = 0; h0 < k.n_hyp; h0 += PNP_HPB) hb[nb++] = PnpBlock{ f, h0, std::min(PNP_HPB, k.n_hyp - h0), 0 };
-            for (int h = 0; h < k.n_hyp; h++)
-                for (int i = 0; i < PNP_MAXSET; i++)
-                    hsm[((size_t)k.hyp_first + h) * PNP_MAXSET + i] = i < ms ? S->sample[((size_t)k.hyp_first + h) * ms + i] : 0;
-        }
-        for (size_t e = 0; e < T; e++) hme[e] = pb->sigma2[e] * pb->th2;    // mvMaxError (:146), a float product
-        G.put(o_p2, pb->P2D, T * 8); G.put(o_p3, pb->P3Dw, T * 12);
-        if ((rc = G.upload(c, 0, in_end))) return rc;
-        const PnpDev D{ G.dev<PnpSolver>(o_solvers), G.dev<PnpBlock>(o_blocks), G.dev<float>(o_p2), G.dev<float>(o_p3), G.dev<float>(o_me),
-                        G.dev<int32_t>(o_sample), G.dev<int32_t>(o_count), G.dev<double>(o_rt), G.dev<unsigned long long>(o_mask),
-                        S->detail ? G.dev<double>(o_det) : nullptr };
-        pnp_hypotheses_launch(c->stream, D, (int)n_blocks);
-        CCM_HIP(c, hipGetLastError());
-        if ((rc = G.download(c, in_end, out_end)) || (rc = G.wait(c))) return rc;
-        {
-            const int32_t* rn = G.host<int32_t>(o_count); const double* rr = G.host<double>(o_rt);
-            const uint64_t* rm = G.host<uint64_t>(o_mask); const double* rd = G.host<double>(o_det);
-            S->count.assign(rn, rn + H); S->rt.assign(rr, rr + 12 * H); S->mask.assign(rm, rm + W);
-            if (S->detail) S->det.assign(rd, rd + PNP_DETAIL * H);
-        }
-
-        // ---- the records (see the head of this file), one Refine() each
-        PnpRecord* hr = G.host<PnpRecord>(o_rec);
-        size_t R = 0, RW = 0;
-        for (int f = 0; f < F; f++) {
-            PnpHost& k = S->k[f];
-            k.ref_first = (int)R; k.ref_mask_first = RW;
-            int best = 0;
-            for (int h = 0; h < k.n_hyp; h++) {
-                const int cnt = S->count[(size_t)k.hyp_first + h];
-                if (cnt >= k.min_inliers && cnt > best && cnt <= k.n && R < Rmax && RW + k.words <= RWmax) {      // :200-206
-                    best = cnt;
-                    hr[R] = PnpRecord{ f, h, (int32_t)R, 0, (int64_t)RW };
-                    S->ref_hyp.push_back(h);
-                    R++; RW += (size_t)k.words; k.n_ref++;
-                }
-            }
-        }
-        if (R > 0) {
-            if ((rc = G.upload(c, o_rec, o_rec + R * sizeof(PnpRecord)))) return rc;
-            const PnpRefineDev Q{ D.solvers, G.dev<PnpRecord>(o_rec), D.P2D, D.P3D, D.max_err, D.mask, G.dev<int32_t>(o_rcount),
-                                  G.dev<double>(o_rrt), G.dev<unsigned long long>(o_rmask), S->detail ? G.dev<double>(o_rdet) : nullptr };
-            pnp_refine_launch(c->stream, Q, (int)R);
-            CCM_HIP(c, hipGetLastError());
-            if ((rc = G.download(c, rec_end, end)) || (rc = G.wait(c))) return rc;
-            const int32_t* rn = G.host<int32_t>(o_rcount); const double* rr = G.host<double>(o_rrt);
-            const uint64_t* rm = G.host<uint64_t>(o_rmask); const double* rd = G.host<double>(o_rdet);
-            S->ref_count.assign(rn, rn + R); S->ref_rt.assign(rr, rr + 12 * R); S->ref_mask.assign(rm, rm + RW);
-            if (S->detail) S->ref_det.assign(rd, rd + PNP_DETAIL * R);
-        }
-        *out = S.release();
-        return CCM_OK;
+extern "C" int ccm_pnp_solver_create_frames(ccm_ctx* c, ccm_frame* cur, ccm_map_table* t, const ccm_pnp_frames_problem* fp, ccm_pnp_solver** out)
+{
+    RoctxRange roctx_("ccm_pnp_solver_create_frames");
+    if (!c || !cur || !t || !fp || !out) return CCM_E_ARG;
+    const char* fn = "ccm_pnp_solver_create_frames";
+    int rc;
+    if ((rc = frame_named_check(c, cur, CCM_E_STATE, fn, "cur")) || (rc = check_table(c, t))) return rc;
+    if (fp->n_solvers < 0 || fp->n_levels < 1 || fp->n_levels > CCM_MAX_LEVELS || !fp->level_sigma2)
+        return ccm_fail(c, CCM_E_ARG, "%s: n_solvers = %d, n_levels = %d (1..%d), level_sigma2 %s", fn, fp->n_solvers, fp->n_levels, CCM_MAX_LEVELS,
+                        fp->level_sigma2 ? "given" : "null");
+    if (fp->n_solvers > 0 && !fp->first) return ccm_fail(c, CCM_E_ARG, "%s: null first", fn);
+    const int T = fp->n_solvers > 0 ? fp->first[fp->n_solvers] : 0;
+    if (T > 0 && (!fp->feature || !fp->slot)) return ccm_fail(c, CCM_E_ARG, "%s: null correspondence array", fn);
+    return table_call(c, t, false, fn, [&]() -> int {                       // reads pos and flags
+        const std::vector<int32_t> n1((size_t)std::max(fp->n_solvers, 1), cur->n);      // mvpMapPointMatches.size() = the frame's N
+        const ccm_pnp_ransac_problem pb{ fp->n_solvers, fp->first, n1.data(), fp->K, nullptr, nullptr, nullptr, fp->feature, fp->probability,
+                                         fp->min_inliers, fp->max_iterations, fp->min_set, fp->epsilon, fp->th2, fp->reserve, fp->draws, fp->flags };
+        const PnpFrames fr{ cur, t, fp->feature, fp->slot, fp->level_sigma2, fp->n_levels };
+        return pnp_create(c, &pb, &fr, out);
     });
 }
 

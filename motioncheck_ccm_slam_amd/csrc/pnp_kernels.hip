@@ -14,8 +14,12 @@
 // the inlier set are taken lane-strided and reduced by a butterfly of shuffles: a fixed order, the same total in every lane, no
 // atomics.  The 3x3 algebra runs redundantly in every lane (same inputs, same result, no hand-off); the 12x12 eigenproblem and the
 // betas run in lane 0 on LDS.  CheckInliers then runs over all N correspondences.
+//
+// k_pnp_gather, in front of the two for ccm_pnp_solver_create_frames: the correspondence arrays from a frame handle and the map-point
+// table (at the end of this file).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "../../include/ccm_hot.h"
 #include "pnp_types.h"
 #include "pnp_math.h"
 
@@ -232,6 +236,35 @@ __global__ __launch_bounds__(PNP_RTPB) void k_pnp_refine(PnpRefineDev D)
     }
 }
 
+// The constructor's loop (:69-91) for correspondences named by (feature of a frame handle, slot of a map-point table), one thread
+// each: P2D = the feature's undistorted keypoint, P3D = the slot's position, max_err = mvLevelSigma2[octave] * th2, the float product
+// ccm_pnp_solver_create forms on the host (:146).  Every index is checked before it is used as an address; a feature outside the
+// frame, a slot outside the table or not LIVE, or an octave outside [0, n_levels) raises status[0] (every thread that finds one stores
+// the same 1) and leaves zeros, which the launch queued behind can read safely; the host then reports CCM_E_ARG.
+__global__ __launch_bounds__(PNP_GTPB) void k_pnp_gather(PnpGather G)
+{
+    const int e = blockIdx.x * PNP_GTPB + threadIdx.x;
+    if (e >= G.n) return;
+    const int f = G.feature[e], s = G.slot[e];
+    float u = 0.0f, v = 0.0f, X = 0.0f, Y = 0.0f, Z = 0.0f, me = 0.0f;
+    bool ok = f >= 0 && f < G.n_cur && s >= 0 && s < G.capacity;
+    if (ok) ok = (G.flags[s] & CCM_MP_LIVE) != 0;
+    int o = 0;
+    if (ok) { o = G.oct[f]; ok = o >= 0 && o < G.n_levels; }
+    if (ok) {
+        u = G.kx[f]; v = G.ky[f];
+        X = G.pos[3 * (size_t)s]; Y = G.pos[3 * (size_t)s + 1]; Z = G.pos[3 * (size_t)s + 2];
+        me = G.sigma2[o] * G.th2;
+    } else G.status[0] = 1;
+    G.P2D[2 * (size_t)e] = u; G.P2D[2 * (size_t)e + 1] = v;
+    G.P3D[3 * (size_t)e] = X; G.P3D[3 * (size_t)e + 1] = Y; G.P3D[3 * (size_t)e + 2] = Z;
+    G.max_err[e] = me;
+}
+
+void pnp_gather_launch(hipStream_t s, const PnpGather& G)
+{
+    if (G.n > 0) hipLaunchKernelGGL(k_pnp_gather, dim3((G.n + PNP_GTPB - 1) / PNP_GTPB), dim3(PNP_GTPB), 0, s, G);
+}
 void pnp_hypotheses_launch(hipStream_t s, const PnpDev& D, int n_blocks)
 {
     hipLaunchKernelGGL(k_pnp_hypotheses, dim3(n_blocks), dim3(PNP_TPB), 0, s, D);

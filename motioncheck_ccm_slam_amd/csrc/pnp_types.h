@@ -42,5 +42,19 @@ struct PnpRefineDev {
     int32_t* count; double* Rt; unsigned long long* mask; double* detail;      // per record
 };
 
+// k_pnp_gather (ccm_pnp_solver_create_frames): correspondence e = (feature[e] of a frame handle, slot[e] of a map-point table)
+#define PNP_GTPB   256
+struct PnpGather {
+    int32_t n, n_cur, capacity, n_levels;             // correspondences; features of the frame; slots of the table; entries of sigma2
+    float th2;
+    const int32_t* feature; const int32_t* slot;
+    const float* kx; const float* ky; const int* oct; // the frame handle's columns
+    const float* pos; const uint8_t* flags;           // the table's columns
+    const float* sigma2;                              // mvLevelSigma2, [CCM_MAX_LEVELS] in device memory
+    float* P2D; float* P3D; float* max_err;           // what PnpDev reads
+    int32_t* status;                                  // [0] raised by a correspondence that cannot be gathered
+};
+
+void pnp_gather_launch(hipStream_t, const PnpGather&);
 void pnp_hypotheses_launch(hipStream_t, const PnpDev&, int n_blocks);
 void pnp_refine_launch(hipStream_t, const PnpRefineDev&, int n_records);

@@ -1,5 +1,6 @@
 """Mirror of `cslam::KeyFrameDatabase` (src/Database.cpp) on the device: `add` / `erase` / `clear`, and the candidate queries
-`DetectLoopCandidates` / `DetectMapMatchCandidates` with the `minScore` loop LoopFinder and MapMatcher run in front of them.
+`DetectLoopCandidates` / `DetectMapMatchCandidates` with the `minScore` loop LoopFinder and MapMatcher run in front of them, and
+`DetectRelocalizationCandidates` for a Frame that is not stored.
 
 The device computes, per stored entry, the number of words it shares with the query, the smallest shared word and the L1 score
 (one kernel launch, `ccm_kfdb_query`); the ordered rest of the reference's two functions is replayed on the host over those arrays
@@ -53,6 +54,23 @@ def candidates(words, score, seq, eligible, min_score: float, min_common_words: 
     return out[:m].copy()
 
 
+def reloc_candidates(words, score, seq, short, neighbours, reloc_score):
+    """Host step B of DetectRelocalizationCandidates (ccm_kfdb_reloc_candidates) behind `shortlist` with every slot eligible and
+    min_score = -inf.  reloc_score: float32 [n_slots], mRelocScore per slot, updated in place.  Returns the candidate slots."""
+    lib = _lib.load()
+    w = np.ascontiguousarray(words, "i4"); s = np.ascontiguousarray(score, "f8"); q = np.ascontiguousarray(seq, "i8")
+    sl = np.ascontiguousarray(short, "i4")
+    assert isinstance(reloc_score, np.ndarray) and reloc_score.dtype == np.float32 and reloc_score.flags.c_contiguous and len(reloc_score) >= len(w)
+    nb = np.full((max(len(sl), 1), NEIGHBOURS), -1, "i4")
+    for i, row in enumerate(neighbours):
+        row = list(row)[:NEIGHBOURS]
+        nb[i, :len(row)] = row
+    out = np.zeros(max(len(sl), 1), "i4")
+    m = _check(lib.ccm_kfdb_reloc_candidates(len(w), _lib.ptr(w), _lib.ptr(s), _lib.ptr(q), len(sl), _lib.ptr(sl), _lib.ptr(nb),
+                                             _lib.ptr(reloc_score), _lib.ptr(out)), "ccm_kfdb_reloc_candidates")
+    return out[:m].copy()
+
+
 def min_score_of(score, seq, connected_slots) -> float:
     """minScore of LoopFinder.cpp:122-139 / MapMatcher.cpp:130-147 over the connected slots (ccm_kfdb_min_score), a float32 value."""
     lib = _lib.load()
@@ -70,6 +88,7 @@ class KeyFrameDatabase:
         self.ctx.check(self.lib.ccm_kfdb_create(self.ctx.handle, int(n_words), int(initial_capacity_words), C.byref(h)))
         self.handle = h
         self.lds_words = self.lib.ccm_kfdb_query_lds_words()
+        self.reloc_score = np.zeros(0, np.float32)                      # mRelocScore per slot, kept from one query to the next
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -82,12 +101,24 @@ class KeyFrameDatabase:
         assert i.ndim == 1 and i.shape == v.shape
         _check(self.lib.ccm_kfdb_add(self.handle, int(key), len(i), _lib.ptr(i), _lib.ptr(v)),
                "ccm_kfdb_add: ids must be strictly ascending and inside the vocabulary, the key new")
+        self._reloc_reset(key)
 
     def erase(self, key: int):
         _check(self.lib.ccm_kfdb_erase(self.handle, int(key)), "ccm_kfdb_erase")
 
     def clear(self):
         _check(self.lib.ccm_kfdb_clear(self.handle), "ccm_kfdb_clear")
+        self.reloc_score = np.zeros(0, np.float32)
+
+    def _reloc_reset(self, key: int):
+        """mRelocScore of a keyframe that has just been added: 0, also in a slot another keyframe held before."""
+        s = self.slot(key)
+        self._reloc_room(s + 1)[s] = 0
+
+    def _reloc_room(self, n: int) -> np.ndarray:
+        if len(self.reloc_score) < n:
+            self.reloc_score = np.concatenate([self.reloc_score, np.zeros(max(n, 2 * len(self.reloc_score)) - len(self.reloc_score), np.float32)])
+        return self.reloc_score
 
     def size(self) -> int:
         return self.lib.ccm_kfdb_size(self.handle)
@@ -164,6 +195,23 @@ class KeyFrameDatabase:
             ks = neighbours(int(keys[s])) if callable(neighbours) else neighbours.get(int(keys[s]), ())
             nb.append([self.slot(k) for k in list(ks)[:NEIGHBOURS]])
         cand = candidates(r.words, r.score, r.seq, el, min_score, mcw, short, nb, r.query_slot)
+        return [int(keys[s]) for s in cand]
+
+    def DetectRelocalizationCandidates(self, bow, neighbours, ctx=None, result=None):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (:329-439) for a Frame's bow = (ids, vals): every stored entry is
+        eligible and there is no minimum score.  neighbours as for DetectLoopCandidates.  mRelocScore of every slot is kept in
+        self.reloc_score between queries (0 for an entry no query has scored).  Returns keys."""
+        r = result if result is not None else self.query(bow=bow, ctx=ctx)
+        n = len(r.words)
+        keys, _ = self.keys()
+        short, _ = shortlist(r.words, r.score, r.first_word, r.seq, np.ones(n, np.uint8), -np.inf, -1)
+        if len(short) == 0:
+            return []
+        nb = []
+        for s in short:
+            ks = neighbours(int(keys[s])) if callable(neighbours) else neighbours.get(int(keys[s]), ())
+            nb.append([self.slot(k) for k in list(ks)[:NEIGHBOURS]])
+        cand = reloc_candidates(r.words, r.score, r.seq, short, nb, self._reloc_room(n))
         return [int(keys[s]) for s in cand]
 
     def DetectLoopCandidates(self, key: int, min_score: float, eligible, neighbours, ctx=None, result=None):

@@ -222,7 +222,48 @@ def _search_by_bow_frames(self, kf1, kfs2, valid1=None, valid2=None):
     return nm[:K], np.ascontiguousarray(m12.reshape(-1)[:K * kf1.n].reshape(K, kf1.n))
 
 
+def reloc_view(Tcw, intr, scale_factors, Ow=None, bounds=(0.0, 752.0, 0.0, 480.0), log_scale_factor=None):
+    """A _lib.RelocView (ccm_reloc_view) of the current frame: Tcw 3x4 or 4x4, Ow = -Rcw^T tcw as a float cv::Mat expression when
+    not given, intr = fx, fy, cx, cy, bounds = mnMinX, mnMaxX, mnMinY, mnMaxY, mfLogScaleFactor = log(mfScaleFactor) when not given.
+    The structure keeps the scale factors alive."""
+    from .tracking import Tracking
+    T, Ow = Tracking.camera(Tcw, Ow)
+    sf = np.ascontiguousarray(scale_factors, "f4")
+    if log_scale_factor is None:
+        log_scale_factor = np.float32(np.log(np.float64(sf[1]))) if len(sf) > 1 else np.float32(1.0)
+    p = _lib.RelocView()
+    p.Tcw[:] = [float(v) for v in T.reshape(-1)]; p.Ow[:] = [float(v) for v in Ow]
+    p.fx, p.fy, p.cx, p.cy = [float(np.float32(v)) for v in intr]
+    p.min_x, p.max_x, p.min_y, p.max_y = [float(np.float32(v)) for v in bounds]
+    p.n_levels = len(sf); p.scale_factors = sf.ctypes.data; p.log_scale_factor = float(log_scale_factor)
+    p._keep = sf
+    return p
+
+
+def _search_by_projection_keyframe_handle(self, cur, kf, table, view, th: float, orb_dist: int, found=None, taps: bool = False):
+    """The relocalisation SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) on two DeviceFrames and a MapPointTable
+    (ccm_frame_search_by_projection_keyframe).  view: a reloc_view; found: the slots of sAlreadyFound, or None = every id `cur` holds
+    now.  Returns a dict: nmatches, match [feature of cur] = feature of kf or -1, mp_id [feature of cur] = cur's map_points after the
+    call and, with taps, u / v / level / valid per feature of kf."""
+    n, nk = cur.n, kf.n
+    match = np.full(max(n, 1), -1, "i4"); mp_id = np.full(max(n, 1), -1, "i4")
+    r = _lib.RelocSearchResult()
+    r.match = match.ctypes.data; r.mp_id = mp_id.ctypes.data
+    if taps:
+        u = np.zeros(max(nk, 1), "f4"); v = np.zeros(max(nk, 1), "f4"); lv = np.zeros(max(nk, 1), "i4"); va = np.zeros(max(nk, 1), np.uint8)
+        r.u = u.ctypes.data; r.v = v.ctypes.data; r.level = lv.ctypes.data; r.valid = va.ctypes.data
+    f = None if found is None else np.ascontiguousarray(found, "i4").reshape(-1)
+    self.ctx.check(self.lib.ccm_frame_search_by_projection_keyframe(
+        self.ctx.handle, C.c_void_p(cur.handle), C.c_void_p(kf.handle), C.c_void_p(table.handle), C.byref(view), C.c_float(th), int(orb_dist),
+        int(self.mbCheckOrientation), -1 if f is None else len(f), None if f is None or len(f) == 0 else f.ctypes.data, C.byref(r)))
+    out = dict(nmatches=int(r.n_matches), match=match[:n], mp_id=mp_id[:n])
+    if taps:
+        out.update(u=u[:nk], v=v[:nk], level=lv[:nk], valid=va[:nk])
+    return out
+
+
 ORBmatcher.SearchByBoWHandle = _search_by_bow_handle
+ORBmatcher.SearchByProjectionKeyFrameHandle = _search_by_projection_keyframe_handle
 ORBmatcher.SearchByBoWFrames = _search_by_bow_frames
 ORBmatcher.SearchByProjectionHandle = _search_by_projection_handle
 ORBmatcher.SearchByProjectionFrameHandle = _search_by_projection_frame_handle

@@ -78,6 +78,30 @@ class PnPSolver:
         self._handle = None
         self.SetRansacParameters()                      # :99
 
+    @classmethod
+    def from_frames(cls, cur, table, first, K, feature, slot, level_sigma2, draws, reserve: int = 0, detail: bool = False, ctx=None):
+        """The same solvers with the constructor's loop on the device (ccm_pnp_solver_create_frames): correspondence e is feature
+        feature[e] of the DeviceFrame `cur` and slot[e] of the MapPointTable `table` -- the features i whose vpMapPointMatches[i] is
+        set and not bad, in i order, and that point's slot.  P2D, P3Dw, sigma2 and kp_index are not passed: the keypoints and
+        octaves come from the handle, the positions from the table; n1 is the frame's feature count for every solver."""
+        a = np.ascontiguousarray
+        self = cls.__new__(cls)
+        self.ctx = ctx or cur.ctx
+        self.lib = _lib.load()
+        self.first = a(first, "i4"); self.n = len(self.first) - 1
+        self.n1 = np.full(max(self.n, 1), cur.n, "i4")[:self.n]
+        self.K = a(K, "f4").reshape(-1, 4)
+        self.kp_index = a(feature, "i4").reshape(-1); self.slot = a(slot, "i4").reshape(-1)
+        if len(self.kp_index) != len(self.slot):
+            raise ValueError("feature and slot differ in length")
+        self.level_sigma2 = a(level_sigma2, "f4").reshape(-1)
+        self.frames = (cur, table)
+        self.draws = np.asarray(draws, "i4")
+        self.reserve, self.detail = int(reserve), bool(detail)
+        self._handle = None
+        self.SetRansacParameters()
+        return self
+
     def SetRansacParameters(self, probability: float = 0.99, minInliers: int = 8, maxIterations: int = 300, minSet: int = 4,
                             epsilon: float = 0.4, th2: float = 5.991):
         self.close()
@@ -93,10 +117,18 @@ class PnPSolver:
             raise ValueError("draws holds %d hypotheses per solver, maxIterations + reserve is %d" % (d.shape[1], rows))
         d = np.ascontiguousarray(d[:, :rows])
         p = _lib.ptr
+        h = C.c_void_p()
+        if getattr(self, "frames", None) is not None:
+            cur, table = self.frames
+            fp = _lib.PnpFramesProblem(self.n, p(self.first), p(self.K), p(self.kp_index), p(self.slot), p(self.level_sigma2),
+                                       len(self.level_sigma2), self.probability, self.min_inliers, self.max_iterations, self.min_set,
+                                       self.epsilon, self.th2, self.reserve, p(d), 1 if self.detail else 0)
+            self.ctx.check(self.lib.ccm_pnp_solver_create_frames(self.ctx.handle, C.c_void_p(cur.handle), C.c_void_p(table.handle), C.byref(fp), C.byref(h)))
+            self._handle = h
+            return
         pb = _lib.PnpRansacProblem(self.n, p(self.first), p(self.n1), p(self.K), p(self.P2D), p(self.P3Dw), p(self.sigma2), p(self.kp_index),
                                    self.probability, self.min_inliers, self.max_iterations, self.min_set, self.epsilon, self.th2,
                                    self.reserve, p(d), 1 if self.detail else 0)
-        h = C.c_void_p()
         self.ctx.check(self.lib.ccm_pnp_solver_create(self.ctx.handle, C.byref(pb), C.byref(h)))
         self._handle = h
 

@@ -190,7 +190,8 @@ class MotionModelResult:
 
 
 class Tracking:
-    """The per-frame calls of Tracking::TrackLocalMap and Tracking::TrackWithMotionModel on `frame.DeviceFrame`s and a `MapPointTable`."""
+    """The per-frame calls of Tracking::TrackLocalMap and Tracking::TrackWithMotionModel, and ORB-SLAM's Relocalization, on
+    `frame.DeviceFrame`s and a `MapPointTable`."""
 
     @staticmethod
     def camera(Tcw, Ow=None):
@@ -321,6 +322,106 @@ class Tracking:
         if taps:
             res.u, res.v, res.valid = u[:nl], v[:nl], valid[:nl]
         return res
+
+    @staticmethod
+    def RelocalizeCandidate(cur, kf, table: MapPointTable, Tcw, feature, slot, intr, scale_factors, inv_level_sigma2, bounds=(0.0, 752.0, 0.0, 480.0),
+                            min_good=10, enough=50, narrow_above=30, th1=10.0, dist1=100, th2=3.0, dist2=64, check_ori=True, log_scale_factor=None,
+                            ctx=None):
+        """One relocalisation candidate from the PnP pose to the verdict (ccm_frame_relocalize_candidate): Tcw = the 4x4 float of
+        PnPSolver.iterate, (feature, slot) = the PnP inliers as features of `cur` and their map points' slots.  Returns a
+        `MotionModelResult`-style object: success, n_good, stages (RELOC_* bits), n_add1, n_add2, pose7, mp_id, outlier."""
+        from .matcher import reloc_view
+        ctx = ctx or cur.ctx
+        lib = _lib.load()
+        a = np.ascontiguousarray
+        T = a(np.asarray(Tcw, "f4").reshape(4, 4)); ft = a(feature, "i4").reshape(-1); sl = a(slot, "i4").reshape(-1)
+        if len(ft) != len(sl):
+            raise ValueError("feature and slot differ in length")
+        k4 = a(intr, "f8"); is2 = a(inv_level_sigma2, "f4")
+        p = _lib.RelocParams()
+        p.Tcw = T.ctypes.data; p.n_matched = len(ft)
+        p.feature = ft.ctypes.data if len(ft) else None; p.slot = sl.ctypes.data if len(sl) else None
+        p.intr = k4.ctypes.data; p.inv_level_sigma2 = is2.ctypes.data
+        view = reloc_view(np.eye(4, dtype="f4"), intr, scale_factors, np.zeros(3, "f4"), bounds, log_scale_factor)
+        p.view = view
+        p.min_good, p.enough, p.narrow_above = int(min_good), int(enough), int(narrow_above)
+        p.th1, p.dist1, p.th2, p.dist2, p.check_ori = float(th1), int(dist1), float(th2), int(dist2), int(bool(check_ori))
+        n = cur.n
+        mp_id = np.full(max(n, 1), -1, "i4"); outl = np.zeros(max(n, 1), np.uint8)
+        r = _lib.RelocResult()
+        r.mp_id = mp_id.ctypes.data; r.outlier = outl.ctypes.data
+        ctx.check(lib.ccm_frame_relocalize_candidate(ctx.handle, C.c_void_p(cur.handle), C.c_void_p(kf.handle), C.c_void_p(table.handle),
+                                                     C.byref(p), C.byref(r)))
+        return MotionModelResult(success=bool(r.success), n_good=int(r.n_good), stages=int(r.stages), n_add1=int(r.n_add1), n_add2=int(r.n_add2),
+                                 pose7=np.array(r.pose7[:], "f8"), mp_id=mp_id[:n], outlier=outl[:n])
+
+    @staticmethod
+    def Relocalization(cur, candidates, table: MapPointTable, intr, scale_factors, level_sigma2, inv_level_sigma2, draws, usable=None,
+                       candidate_ids=None, min_bow_matches=15, reserve=40, ransac=(0.99, 10, 300, 4, 0.5, 5.991), ctx=None, **refine):
+        """ORB-SLAM's Tracking::Relocalization on handles and the table.  `cur` has its bow (compute_bow); `candidates` are the
+        keyframe handles DetectRelocalizationCandidates named (KeyFrameDatabase.DetectRelocalizationCandidates gives their keys), each
+        with bow and map_points.  SearchByBoW against all of them in one call (ccm_search_by_bow_frames); a candidate with fewer than
+        min_bow_matches matches is dropped; one PnPsolver per kept candidate, all created at once from the handle and the table
+        (PnPSolver.from_frames) with SetRansacParameters(*ransac); then the round-robin: 5 iterations per candidate and turn, a
+        candidate is dropped at bNoMore (or beyond the reserve), a pose goes through RelocalizeCandidate(**refine) and the first success
+        ends the loop.  draws: the caller's random source -- an array [kept][>= maxIterations + reserve][minSet], or a callable (sizes,
+        rows) -> such an array (pnpsolver.make_draws with the caller's Generator).  usable [capacity] bool: the slots that are not bad
+        (None: all).  candidate_ids: the candidates' map_points when the caller has them on the host already.
+        Returns a dict: success, candidate (index into candidates, or -1), result (of the successful refinement or None), n_bow [K],
+        kept (the candidates that got a solver) and tried [(candidate, result)] in order."""
+        from .matcher import ORBmatcher
+        from .pnpsolver import PnPSolver
+        ctx = ctx or cur.ctx
+        K = len(candidates)
+        out = dict(success=False, candidate=-1, result=None, n_bow=np.zeros(K, "i4"), kept=[], tried=[])
+        if K == 0 or cur.n == 0:
+            return out
+        nm, m12 = ORBmatcher(0.75, True, ctx=ctx).SearchByBoWFrames(cur, candidates, valid1=np.ones(cur.n, np.uint8))
+        out["n_bow"] = nm
+        ids = [np.asarray(candidates[k].map_points if candidate_ids is None else candidate_ids[k], "i4") for k in range(K)]
+        kept, vp, feats, slots = [], [], [], []
+        for k in range(K):
+            if nm[k] < min_bow_matches:
+                continue
+            v = np.where(m12[k] >= 0, ids[k][np.maximum(m12[k], 0)], -1).astype("i4")      # vvpMapPointMatches[k]
+            f = np.flatnonzero(v >= 0)
+            if usable is not None:
+                f = f[np.asarray(usable, bool)[v[f]]]
+            kept.append(k); vp.append(v); feats.append(f.astype("i4")); slots.append(v[f])
+        out["kept"] = kept
+        if not kept:
+            return out
+        sizes = [len(f) for f in feats]
+        first = np.concatenate([[0], np.cumsum(sizes)]).astype("i4")
+        rows = int(ransac[2]) + int(reserve)
+        d = draws(sizes, rows) if callable(draws) else draws
+        solver = PnPSolver.from_frames(cur, table, first, np.tile(np.asarray(intr, "f4").reshape(1, 4), (len(kept), 1)), np.concatenate(feats),
+                                       np.concatenate(slots), level_sigma2, d, reserve=reserve, ctx=ctx)
+        solver.SetRansacParameters(*ransac)
+        try:
+            alive = list(range(len(kept)))
+            while alive and not out["success"]:
+                for j in list(alive):
+                    try:
+                        T, no_more, inl, _ = solver.iterate(j, 5)
+                    except _lib.CcmError as e:
+                        if e.code != -7:                                         # CCM_E_STATE: beyond the reserve
+                            raise
+                        T, no_more = None, True
+                    if no_more:
+                        alive.remove(j)
+                    if T is None:
+                        continue
+                    f = np.flatnonzero(inl).astype("i4")
+                    res = Tracking.RelocalizeCandidate(cur, candidates[kept[j]], table, T, f, vp[j][f], intr, scale_factors, inv_level_sigma2,
+                                                       ctx=ctx, **refine)
+                    out["tried"].append((kept[j], res))
+                    if res.success:
+                        out.update(success=True, candidate=kept[j], result=res)
+                        break
+        finally:
+            solver.close()
+        return out
 
     @staticmethod
     def TrackLocalMap(frame, table: MapPointTable, pose, Tcw, intr, scale_factors, inv_level_sigma2, **kw):

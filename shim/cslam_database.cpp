@@ -1,7 +1,7 @@
 // cslam_database.cpp -- drop-in bodies of cslam::KeyFrameDatabase::add / erase / clear / DetectLoopCandidates /
-// DetectMapMatchCandidates (src/Database.cpp:37-327) on the device KeyFrameDatabase of include/ccm_hot.h.  The constructor,
-// DetectRelocalizationCandidates (which the reference never calls) and the map-point bookkeeping stay the reference's: remove the five
-// bodies above from src/Database.cpp and link this file.  The reference's header (include/cslam/Database.h) stays untouched, so the
+// DetectMapMatchCandidates / DetectRelocalizationCandidates (src/Database.cpp:37-439) on the device KeyFrameDatabase of
+// include/ccm_hot.h.  The constructor and the map-point bookkeeping stay the reference's: remove the six bodies above from
+// src/Database.cpp and link this file.  The reference's header (include/cslam/Database.h) stays untouched, so the
 // ccm_kfdb handle and the key -> keyframe table live in a side table keyed on the object; mvInvertedFile stays empty.
 //
 // What the walk read from the keyframes while it ran is handed over as arrays: `eligible` from the map's keyframes and
@@ -11,6 +11,7 @@
 #include <cslam/Database.h>
 #include <cslam/KeyFrame.h>
 #include <cslam/Map.h>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -24,6 +25,7 @@ typedef boost::shared_ptr<cslam::KeyFrame> kfdb_kfptr;
 struct KfdbSide {
     ccm_kfdb* db = nullptr;
     std::unordered_map<int64_t, kfdb_kfptr> kf;            // what is stored, by key
+    std::vector<float> reloc_score;                        // mRelocScore per slot (ccm_kfdb_reloc_candidates), 0 from add on
     ~KfdbSide() { ccm_kfdb_destroy(db); }
 };
 
@@ -140,7 +142,12 @@ void KeyFrameDatabase::add(kfptr pKF)
     std::lock_guard<std::mutex> lock(g_kfdb_mutex);
     KfdbSide& S = kfdb_side(this, (int)mpVoc->size());
     const int64_t key = kfdb_key(pKF->mId);
-    if (ccm_kfdb_add(S.db, key, (int)ids.size(), ids.data(), vals.data()) == CCM_OK) S.kf[key] = pKF;
+    if (ccm_kfdb_add(S.db, key, (int)ids.size(), ids.data(), vals.data()) == CCM_OK) {
+        S.kf[key] = pKF;
+        const int slot = ccm_kfdb_slot(S.db, key);          // a new keyframe, also in a slot another one held: mRelocScore starts at 0
+        if (slot >= (int)S.reloc_score.size()) S.reloc_score.resize((size_t)slot + 1, 0.0f);
+        if (slot >= 0) S.reloc_score[slot] = 0.0f;
+    }
 }
 
 void KeyFrameDatabase::erase(kfptr pKF)
@@ -158,6 +165,7 @@ void KeyFrameDatabase::clear()
     KfdbSide& S = kfdb_side(this, (int)mpVoc->size());
     ccm_kfdb_clear(S.db);
     S.kf.clear();
+    S.reloc_score.clear();
 }
 
 vector<KeyFrameDatabase::kfptr> KeyFrameDatabase::DetectLoopCandidates(kfptr pKF, float minScore)
@@ -194,6 +202,71 @@ vector<KeyFrameDatabase::kfptr> KeyFrameDatabase::DetectMapMatchCandidates(kfptr
     for (int s = 0; s < A.n; s++)
         if (A.key[s] >= 0 && !pMap->msuAssClients.count((size_t)((uint64_t)A.key[s] >> 40))) eligible[s] = 1;
     return kfdb_detect(*S, A, eligible, minScore);
+}
+
+// :329-439: the query vector is the frame's, every stored entry is eligible and there is no minimum score; the accumulation reads and
+// writes the per-slot mRelocScore kept beside the database (ccm_kfdb_reloc_candidates).
+vector<KeyFrameDatabase::kfptr> KeyFrameDatabase::DetectRelocalizationCandidates(Frame& F)
+{
+    std::vector<int32_t> ids; std::vector<double> vals;
+    for (DBoW2::BowVector::const_iterator vit = F.mBowVec.begin(); vit != F.mBowVec.end(); vit++) {
+        ids.push_back((int32_t)vit->first); vals.push_back(vit->second);
+    }
+    KfdbSide* S;
+    {
+        std::lock_guard<std::mutex> lock(g_kfdb_mutex);
+        S = &kfdb_side(this, (int)mpVoc->size());
+    }
+    KfdbQueryArrays A;
+    for (;;) {
+        const int cap = ccm_kfdb_slots(S->db) + 256;
+        A.words.resize(cap); A.first_word.resize(cap); A.score.resize(cap); A.seq.resize(cap); A.key.resize(cap);
+        const int rc = ccm_kfdb_query_vector(ctx(), S->db, (int)ids.size(), ids.data(), vals.data(), cap, A.words.data(), A.score.data(),
+                                             A.first_word.data(), A.seq.data());
+        if (rc == CCM_E_CAPACITY) continue;
+        if (rc < 0) throw std::runtime_error(ccm_last_error(ctx()));
+        A.n = rc;
+        break;
+    }
+    std::vector<int64_t> seq_now(A.key.size());
+    const int m = ccm_kfdb_keys(S->db, (int)A.key.size(), A.key.data(), seq_now.data());
+    for (int s = 0; s < A.n; s++)
+        if (s >= m || seq_now[s] != A.seq[s]) A.key[s] = -1;
+    vector<kfptr> out;
+    const std::vector<uint8_t> eligible(A.n > 0 ? A.n : 1, 1);
+    std::vector<int32_t> shortlist(A.n > 0 ? A.n : 1);
+    int32_t min_common = 0;
+    const int n_short = ccm_kfdb_shortlist(A.n, A.words.data(), A.score.data(), A.first_word.data(), A.seq.data(), eligible.data(), -1, -INFINITY,
+                                           (int)shortlist.size(), shortlist.data(), &min_common);
+    if (n_short <= 0) return out;
+    std::vector<int32_t> neighbours((size_t)n_short * CCM_KFDB_NEIGHBOURS, -1), candidates(n_short);
+    std::vector<kfptr> kf_of_slot(A.n);
+    {
+        std::lock_guard<std::mutex> lock(g_kfdb_mutex);
+        for (int s = 0; s < A.n; s++) {
+            const auto it = A.key[s] < 0 ? S->kf.end() : S->kf.find(A.key[s]);
+            if (it != S->kf.end()) kf_of_slot[s] = it->second;
+        }
+    }
+    for (int i = 0; i < n_short; i++) {                    // outside the lock, as kfdb_detect: the keyframes take their own mutexes
+        const kfptr& pKFi = kf_of_slot[shortlist[i]];
+        if (!pKFi) continue;
+        const std::vector<kfptr> vpNeighs = pKFi->GetBestCovisibilityKeyFrames(10);
+        for (size_t k = 0; k < vpNeighs.size() && k < CCM_KFDB_NEIGHBOURS; k++) {
+            const int32_t s = ccm_kfdb_slot(S->db, kfdb_key(vpNeighs[k]->mId));
+            neighbours[(size_t)i * CCM_KFDB_NEIGHBOURS + k] = (s >= 0 && s < A.n && kf_of_slot[s] == vpNeighs[k]) ? s : -1;
+        }
+    }
+    int n_cand;
+    {
+        std::lock_guard<std::mutex> lock(g_kfdb_mutex);    // the score array is the side table's; add resizes and zeroes it
+        if ((int)S->reloc_score.size() < A.n) S->reloc_score.resize(A.n, 0.0f);
+        n_cand = ccm_kfdb_reloc_candidates(A.n, A.words.data(), A.score.data(), A.seq.data(), n_short, shortlist.data(), neighbours.data(),
+                                           S->reloc_score.data(), candidates.data());
+    }
+    for (int i = 0; i < n_cand; i++)
+        if (kf_of_slot[candidates[i]]) out.push_back(kf_of_slot[candidates[i]]);
+    return out;
 }
 
 }  // namespace cslam

@@ -20,6 +20,7 @@
 #include <memory>
 #include <mutex>
 #include "ccm_shim.h"
+#include "fuse_steps.h"
 
 namespace ccm_shim {
 
@@ -32,8 +33,9 @@ struct PnpParams {
 // The constructor data of one solver (:57-100), appended to the flat arrays of a batch
 struct PnpFlat {
     std::vector<int32_t> first{ 0 }, n1, kp_index;
+    std::vector<int32_t> slot;           // with_slots: the point's slot in the map-point table beside every kp_index entry, -1 without one
     std::vector<float> K, P2D, P3Dw, sigma2;
-    void add(const cslam::Frame& F, const std::vector<cslam::PnPsolver::mpptr>& vpMapPointMatches)
+    void add(const cslam::Frame& F, const std::vector<cslam::PnPsolver::mpptr>& vpMapPointMatches, bool with_slots = false)
     {
         for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {
             const cslam::PnPsolver::mpptr pMP = vpMapPointMatches[i];
@@ -44,6 +46,7 @@ struct PnpFlat {
             const cv::Mat Pos = pMP->GetWorldPos();
             for (int k = 0; k < 3; k++) P3Dw.push_back(Pos.at<float>(k));
             kp_index.push_back((int32_t)i);
+            if (with_slots) slot.push_back(map_slot_of(pMP));
         }
         first.push_back((int32_t)kp_index.size());
         n1.push_back((int32_t)vpMapPointMatches.size());
@@ -77,6 +80,31 @@ static ccm_pnp_solver* create(const PnpFlat& flat, const PnpParams& p, int reser
     pb.epsilon = p.epsilon; pb.th2 = p.th2; pb.reserve = reserve; pb.draws = draws.data(); pb.flags = 0;
     ccm_pnp_solver* s = nullptr;
     if (ccm_pnp_solver_create(ctx(), &pb, &s)) throw estd::infrastructure_ex();
+    return s;
+}
+
+// The same batch through ccm_pnp_solver_create_frames: the keypoints and octaves come from the frame's handle, the positions from the
+// map-point table, and 8 bytes per correspondence go up in the place of 24.  flat was filled with_slots, so feature (kp_index) and slot
+// of a correspondence were taken from the same point in the same pass.  nullptr = this route is not available (no handle of F in the
+// cache, no table on this thread, a point without a slot, or match vectors that are not as long as the frame): the caller takes the
+// array route, with draws of its own.
+static ccm_pnp_solver* create_frames(const cslam::Frame& F, const PnpFlat& flat, const PnpParams& p, int reserve)
+{
+    if (flat.slot.size() != flat.kp_index.size()) return nullptr;
+    for (int32_t s : flat.slot) if (s < 0) return nullptr;
+    for (int32_t n : flat.n1) if (n != F.N) return nullptr;                          // iterate's vbInliers has the handle's N entries
+    ccm_frame* cur = frame_handle(F);
+    ccm_map_table* table = cur ? map_table_here() : nullptr;
+    if (!cur || !table) return nullptr;
+    const int max_its = p.max_iterations < 1 ? 1 : p.max_iterations;
+    const std::vector<int32_t> draws = draw(flat, max_its + reserve, p.min_set);
+    ccm_pnp_frames_problem fp{};
+    fp.n_solvers = flat.solvers(); fp.first = flat.first.data(); fp.K = flat.K.data(); fp.feature = flat.kp_index.data(); fp.slot = flat.slot.data();
+    fp.level_sigma2 = F.mvLevelSigma2.data(); fp.n_levels = (int32_t)F.mvLevelSigma2.size();
+    fp.probability = p.probability; fp.min_inliers = p.min_inliers; fp.max_iterations = max_its; fp.min_set = p.min_set;
+    fp.epsilon = p.epsilon; fp.th2 = p.th2; fp.reserve = reserve; fp.draws = draws.data(); fp.flags = 0;
+    ccm_pnp_solver* s = nullptr;
+    if (ccm_pnp_solver_create_frames(ctx(), cur, table, &fp, &s)) throw estd::infrastructure_ex();
     return s;
 }
 
@@ -127,11 +155,12 @@ std::unique_ptr<PnpBatch> pnp_candidates(const cslam::Frame& F, const std::vecto
     for (size_t i = 0; i < vvpMapPointMatches.size(); i++) {
         if (!skip.empty() && skip[i]) continue;
         slot[i] = flat.solvers();
-        flat.add(F, vvpMapPointMatches[i]);
+        flat.add(F, vvpMapPointMatches[i], /*with_slots=*/true);
     }
     PnpParams p;
     p.probability = probability; p.min_inliers = minInliers; p.max_iterations = maxIterations; p.min_set = minSet; p.epsilon = epsilon; p.th2 = th2;
-    ccm_pnp_solver* s = create(flat, p, reserve < 0 ? 0 : reserve);
+    ccm_pnp_solver* s = create_frames(F, flat, p, reserve < 0 ? 0 : reserve);       // nullptr: no handle, or a point without a slot
+    if (!s) s = create(flat, p, reserve < 0 ? 0 : reserve);
     return std::unique_ptr<PnpBatch>(new PnpBatch(s, slot, flat.n1));
 }
 

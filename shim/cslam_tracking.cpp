@@ -479,6 +479,52 @@ bool fuse_select_on_table(const std::vector<ORBmatcher::kfptr>& kfs, const std::
     return MapTable::get().fuse_select(kfs, poses, pts, th, chi2_check, accept_th, handle_of, best);
 }
 
+// One relocalisation candidate from the PnP pose to the verdict (ccm_frame_relocalize_candidate; fuse_steps.h, INTEGRATION.md
+// "Relocalisation").  vpMapPointMatches / vbInliers are the candidate's SearchByBoW matches and what PnPsolver::iterate marked.  On
+// return F.mvpMapPoints and F.mvbOutlier are what the stages left, nGood their last count, and with `true` F's pose is the optimised one.
+bool relocalize(cslam::Frame& F, const ORBmatcher::kfptr& pKF, const cv::Mat& Tcw, const std::vector<ORBmatcher::mpptr>& vpMapPointMatches,
+                const std::vector<bool>& vbInliers, KeyframeHandleOf handle_of, bool& bMatch, int& nGood)
+{
+    MapTable& T = MapTable::get();
+    ccm_frame* cur = frame_handle(F);
+    ccm_frame* kf = handle_of ? handle_of(pKF) : nullptr;
+    ccm_map_table* table = cur && kf ? T.flush() : nullptr;
+    if (!cur || !kf || !table || Tcw.empty() || vbInliers.size() != vpMapPointMatches.size() || (int)vbInliers.size() != F.N) return false;
+    std::vector<int32_t> feature, slot;
+    for (int i = 0; i < F.N; i++) {
+        if (!vbInliers[i] || !vpMapPointMatches[i]) continue;
+        const int s = T.slot_of(vpMapPointMatches[i]);
+        if (s < 0) return false;                                               // a point without a slot: the caller takes the array route
+        feature.push_back(i); slot.push_back(s);
+    }
+    float T16[16];
+    for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) T16[4 * r + c] = Tcw.at<float>(r, c);
+    const double intr[4] = { cslam::Frame::fx, cslam::Frame::fy, cslam::Frame::cx, cslam::Frame::cy };
+    ccm_reloc_params p{};
+    p.Tcw = T16; p.n_matched = (int32_t)feature.size(); p.feature = feature.data(); p.slot = slot.data();
+    p.intr = intr; p.inv_level_sigma2 = F.mvInvLevelSigma2.data();
+    p.view.fx = cslam::Frame::fx; p.view.fy = cslam::Frame::fy; p.view.cx = cslam::Frame::cx; p.view.cy = cslam::Frame::cy;
+    p.view.min_x = cslam::Frame::mnMinX; p.view.max_x = cslam::Frame::mnMaxX; p.view.min_y = cslam::Frame::mnMinY; p.view.max_y = cslam::Frame::mnMaxY;
+    p.view.n_levels = F.mnScaleLevels; p.view.scale_factors = F.mvScaleFactors.data(); p.view.log_scale_factor = F.mfLogScaleFactor;
+    p.min_good = 10; p.enough = 50; p.narrow_above = 30; p.th1 = 10.f; p.dist1 = 100; p.th2 = 3.f; p.dist2 = 64; p.check_ori = 1;
+    std::vector<int32_t> ids(std::max(F.N, 1), -1);
+    std::vector<uint8_t> outlier(std::max(F.N, 1), 0);
+    ccm_reloc_result r{};
+    r.mp_id = ids.data(); r.outlier = outlier.data();
+    if (ccm_frame_relocalize_candidate(ctx(), cur, kf, table, &p, &r)) return false;      // the handle's ids are as on entry
+    for (int i = 0; i < F.N; i++) {
+        F.mvpMapPoints[i] = ids[i] >= 0 ? T.point(ids[i]) : nullptr;
+        F.mvbOutlier[i] = outlier[i] != 0;
+    }
+    float T16o[16];
+    ccm_pose_to_mat4f(r.pose7, T16o);
+    cv::Mat Tout(4, 4, CV_32F);
+    std::memcpy(Tout.ptr<float>(), T16o, sizeof T16o);
+    F.SetPose(Tout);
+    bMatch = r.success != 0; nGood = r.n_good;
+    return true;
+}
+
 }  // namespace ccm_shim
 
 namespace cslam {

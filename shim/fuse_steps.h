@@ -134,6 +134,13 @@ inline KeyframeHandleOf& thread_keyframe_handles()
 }
 inline ccm_frame* thread_keyframe_handle(const ORBmatcher::kfptr& pKF) { return thread_keyframe_handles() ? thread_keyframe_handles()(pKF) : nullptr; }
 
+// One candidate of ORB-SLAM's Tracking::Relocalization from the PnP pose to the verdict in ONE ccm_frame_relocalize_candidate (defined in
+// cslam_tracking.cpp; INTEGRATION.md "Relocalisation"): the pose optimisations, both relocalisation SearchByProjection calls and the
+// outlier handling on the frame's handle, pKF's keyframe handle and the table.  false = nothing was touched: F has no handle, pKF none
+// in handle_of, there is no table, or a matched point has no slot; the caller then runs the steps on the array route.
+bool relocalize(cslam::Frame& F, const ORBmatcher::kfptr& pKF, const cv::Mat& Tcw, const std::vector<ORBmatcher::mpptr>& vpMapPointMatches,
+                const std::vector<bool>& vbInliers, KeyframeHandleOf handle_of, bool& bMatch, int& nGood);
+
 // The slot of pMP in the calling process's map-point table, or -1 (ccm_shim::MapTable::slot_of, cslam_tracking.cpp).  A keyframe handle
 // that is to serve fuse_select_on_table carries these in its map-point ids.
 int map_slot_of(const ORBmatcher::mpptr& pMP);
