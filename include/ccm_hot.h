@@ -1846,6 +1846,103 @@ int ccm_kfdb_reloc_candidates(int n_slots, const int32_t* words, const double* s
  * (float)score of the connected slots; -1 and free slots are skipped (pass the keyframes that are not bad). */
 float ccm_kfdb_min_score(int n_slots, const double* score, const int64_t* seq, int n_connected, const int32_t* connected);
 
+/* ------------------------------------------------------------------ Covisibility
+ * The covisibility counts of a map, for ALL of its keyframes: the counter of KeyFrame::UpdateConnections (cslam/src/KeyFrame.cpp:629-711,
+ * called for every new keyframe, src/Mapping.cpp:272, :546, for every connected keyframe after a loop closure, src/LoopFinder.cpp:514,
+ * :612, :655, and after a map merge, src/MapMerger.cpp:267, :392, :487) and the observer counts of LocalMapping::KeyFrameCullingV3
+ * (src/Mapping.cpp:771-863).  Keyframe handles cannot serve: the counts run against every keyframe of the map, so the index keeps one
+ * light RECORD per keyframe, as the KeyFrameDatabase keeps one BowVector:
+ *     key        int64, the caller's name of the keyframe
+ *     slot[n]    int32 per feature: the map-point table slot the feature holds (mp_id of the handles)
+ *     octave[n]  uint8 per feature: mvKeysUn[i].octave
+ * An entry HOLDS A POINT iff 0 <= slot < INT32_MAX.  Negative: no map point.  INT32_MAX: a point that has no table slot yet; it
+ * never matches anything, not even another INT32_MAX.
+ *
+ * The counts are derived from "which keyframe holds which slot", not from MapPoint::mObservations.  They equal the reference's
+ * wherever  pMP->mObservations contains (pKF, idx)  iff  pKF->mvpMapPoints[idx] == pMP  ("Covisibility
+ * index"); the server keeps that invariant, a client's mObservationsLock can break it (src/MapPoint.cpp), so the index is for server
+ * paths.
+ *
+ * Storage and threads as for the KeyFrameDatabase: one device arena of 5 bytes a feature, a stable slot number and a sequence number
+ * per record; put / erase / clear / size / slot / slots / keys take no context, do no GPU work and may be called from any thread
+ * (a host-side pending list under the index's mutex).  A query holds that mutex from its flush to the end of its download, so queries
+ * from several threads, each with its own context on the index's device, serialise.  The arena grows when it is full and is
+ * compacted when more than half of it is holes; both happen inside a query. */
+typedef struct ccm_covis ccm_covis;
+enum { CCM_COVIS_WEIGHTS = 1,       /* weights[q][s]: KFcounter of UpdateConnections */
+       CCM_COVIS_REDUNDANCY = 2 };  /* n_redundant[q]: nRedundantObservations of KeyFrameCullingV3 */
+/* The index lives on the context's device.  The context may be NULL: the index then belongs to the device of the first context
+ * that queries it (bookkeeping needs no device at all).  initial_capacity_features >= 0 sizes the first arena. */
+int  ccm_covis_create(ccm_ctx*, int64_t initial_capacity_features, ccm_covis** out);
+void ccm_covis_destroy(ccm_covis*);
+/* put: stores a record (n = 0 is legal; n < 0 or a NULL array with n > 0: CCM_E_ARG, the index unchanged).  For a key that is present
+ * it REPLACES the contents and keeps the record's slot number and sequence number: what the caller does whenever the keyframe's map
+ * points change.  A new key takes a free slot (one freed by erase may be reused) and the next sequence number.  erase of an unknown
+ * key does nothing; the caller erases a keyframe when it turns bad, which is pKFi->isBad() of src/Mapping.cpp:835.  clear forgets
+ * every record and every slot. */
+int ccm_covis_put(ccm_covis*, int64_t key, int n, const int32_t* slot, const uint8_t* octave);
+int ccm_covis_erase(ccm_covis*, int64_t key);
+int ccm_covis_clear(ccm_covis*);
+int ccm_covis_size(ccm_covis*);                /* stored records */
+int ccm_covis_slot(ccm_covis*, int64_t key);   /* the key's slot number, -1 when it is not stored */
+int ccm_covis_slots(ccm_covis*);               /* high-water mark of the slot numbers = length of a query's rows */
+/* keys[s] = the key in slot s, -1 for a free slot; seq[s] (may be null) = its sequence number, -1 for a free slot.  Returns the
+ * number of slots, CCM_E_CAPACITY when that exceeds capacity. */
+int ccm_covis_keys(ccm_covis*, int capacity, int64_t* keys, int64_t* seq);
+/* The query, for n_q stored keyframes at once: applies the pending changes on the context's stream, computes, downloads once and
+ * synchronises.  table: a map-point table or view of the calling context, or NULL; it supplies MapPoint::isBad() (src/KeyFrame.cpp:651,
+ * src/Mapping.cpp:823).  An entry of a query record COUNTS iff it holds a point and, with a table, its slot is below the table's
+ * capacity and the row is CCM_MP_LIVE and not CCM_MP_BAD; with table == NULL every entry that holds a point counts.  The entries of
+ * the OTHER records are not filtered: an entry that matches a counting entry names the same row.
+ *   skipped[q]      entries of query q that hold a point but do not count.  An output, not an error: stale ids in old keyframes
+ *                   are normal.
+ *   CCM_COVIS_WEIGHTS:  weights[q * capacity + s], for every slot number s below the returned count = the number of pairs (counting
+ *                   entry i of the query, entry j of record s) with equal slots: KFcounter of src/KeyFrame.cpp:644-662.  A free slot
+ *                   gives 0 and so does the query's own (:658).  The reference never holds a point at two features of a keyframe,
+ *                   and the weight is then the number of shared points; where that is broken the pair count is the defined result.
+ *   CCM_COVIS_REDUNDANCY, with th_obs (thObs = 3, src/Mapping.cpp:815; 1 .. 2^20):
+ *                   n_mps[q] = the number of counting entries (nMPs, :825);
+ *                   n_redundant[q] = the number of counting entries i with fine_i >= th_obs, fine_i = the number of pairs (record s
+ *                   other than the query's, entry j of s) with slot_s[j] == slot_q[i] and octave_s[j] <= octave_q[i] + 1 (:831-851).
+ *                   The reference's further gate Observations() > thObs (:826) is implied under the invariant above: fine_i >= 3
+ *                   names three other keyframes, which with the query itself are at least four observations.
+ *                   n_mps is written with either bit.
+ *   seq[s]          (may be null) the sequence number per slot, -1 for a free slot.
+ * capacity = the slots the rows of weights and seq have room for; returns the number of slots (ccm_covis_slots at the time of the
+ * query), CCM_E_CAPACITY when that exceeds capacity.  n_q == 0 returns CCM_OK and touches nothing.
+ * Errors are found on the host before any work is queued, the outputs are then untouched.  CCM_E_ARG: a NULL argument or a NULL
+ * array that `what` needs, an unknown query key, a context on another device than the index, a table of another context, what == 0 or
+ * with unknown bits, th_obs out of range with CCM_COVIS_REDUNDANCY.  CCM_E_STATE: a table that outlived its context.
+ * What stays with the caller: the parent selection of UpdateConnections (src/KeyFrame.cpp:713-833), AddConnection /
+ * UpdateBestCovisibles on the neighbours (:687, :694), and the verdict nRedundantObservations > mfRedundancyThres * nMPs
+ * (src/Mapping.cpp:857) in double, as fptype is double (include/cslam/config.h). */
+typedef struct {
+    int32_t  th_obs;        /* in: thObs, read with CCM_COVIS_REDUNDANCY */
+    int32_t* weights;       /* [n_q][capacity], needed with CCM_COVIS_WEIGHTS */
+    int32_t* n_mps;         /* [n_q] or NULL */
+    int32_t* n_redundant;   /* [n_q], needed with CCM_COVIS_REDUNDANCY */
+    int32_t* skipped;       /* [n_q] or NULL */
+    int64_t* seq;           /* [capacity] or NULL */
+} ccm_covis_result;
+int ccm_covis_query(ccm_ctx*, ccm_covis*, ccm_map_table* table /* or NULL */, int n_q, const int64_t* query_keys, int what, int capacity,
+                    ccm_covis_result* result);
+/* Features of a query record up to which its hash is held in LDS; a longer query is hashed in global scratch (same results).  The
+ * environment variable CCM_COVIS_LDS_FEATURES=N, read once, lowers it (tests reach the global path with small inputs). */
+int ccm_covis_lds_features(void);
+/* Taps: the arena in features (allocated, tail, held by live records) after the last flush; milliseconds the last query spent in
+ * its flush, its kernels and its download (HIP events on the querying context's stream). */
+int ccm_covis_arena(ccm_covis*, int64_t* capacity_features, int64_t* used_features, int64_t* live_features);
+int ccm_covis_last_timing(ccm_covis*, double ms3[3]);
+/* The ordered lists of UpdateConnections (src/KeyFrame.cpp:664-711) from one row of weights, on the host; needs no device.  Returns 0
+ * when no weight is > 0 (the reference returns early, :664, and leaves the keyframe's connections as they are).  Listed are the slots
+ * with weight >= th (th = 15, :673); when none reaches th, the single slot of maximum weight, among equal maxima the FIRST in
+ * iteration order (:679 compares strictly).  Output order = sort(vPairs) followed by push_front (:697-704): descending weight, among
+ * equal weights DESCENDING iteration position.  The iteration position of slot s is rank[s]: the reference's std::map<kfptr,int>
+ * iterates in pointer order, so the caller fixes it (as for ccm_map_table_refresh); distinct values, rank == NULL: the slot number.
+ * order_slot / order_weight [capacity] (order_weight may be NULL): returns the number written, CCM_E_CAPACITY beyond capacity. */
+int ccm_covis_connections(int n_slots, const int32_t* weights, const int32_t* rank /* or NULL */, int th, int capacity, int32_t* order_slot,
+                          int32_t* order_weight);
+
 #ifdef __cplusplus
 }
 #endif

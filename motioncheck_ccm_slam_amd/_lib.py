@@ -55,6 +55,9 @@ SYMBOLS = [
     "ccm_kfdb_create", "ccm_kfdb_destroy", "ccm_kfdb_add", "ccm_kfdb_erase", "ccm_kfdb_clear", "ccm_kfdb_size", "ccm_kfdb_slot", "ccm_kfdb_slots",
     "ccm_kfdb_keys", "ccm_kfdb_query", "ccm_kfdb_query_vector", "ccm_kfdb_query_lds_words", "ccm_kfdb_arena", "ccm_kfdb_last_timing",
     "ccm_kfdb_shortlist", "ccm_kfdb_candidates", "ccm_kfdb_min_score", "ccm_kfdb_reloc_candidates",
+    "ccm_covis_create", "ccm_covis_destroy", "ccm_covis_put", "ccm_covis_erase", "ccm_covis_clear", "ccm_covis_size", "ccm_covis_slot",
+    "ccm_covis_slots", "ccm_covis_keys", "ccm_covis_query", "ccm_covis_lds_features", "ccm_covis_arena", "ccm_covis_last_timing",
+    "ccm_covis_connections",
 ]
 
 
@@ -344,6 +347,14 @@ class BaResult(C.Structure):
                 ("pcg_fallbacks", C.c_int32), ("pcg_pipelined", C.c_int32)]
 
 
+COVIS_WEIGHTS, COVIS_REDUNDANCY = 1, 2          # CCM_COVIS_* of include/ccm_hot.h
+
+
+class CovisResult(C.Structure):                       # ccm_covis_result
+    _fields_ = [("th_obs", C.c_int32), ("weights", C.c_void_p), ("n_mps", C.c_void_p), ("n_redundant", C.c_void_p),
+                ("skipped", C.c_void_p), ("seq", C.c_void_p)]
+
+
 ABI_VERSION = 3        # CCM_ABI_VERSION of the include/ccm_hot.h these ctypes structures were written against
 _lib = None
 
@@ -523,6 +534,21 @@ def load():
         lib.ccm_kfdb_candidates.argtypes = [C.c_int, vp, vp, vp, vp, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, vp]
         lib.ccm_kfdb_reloc_candidates.argtypes = [C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         lib.ccm_kfdb_min_score.argtypes = [C.c_int, vp, vp, C.c_int, vp]; lib.ccm_kfdb_min_score.restype = C.c_float
+    if hasattr(lib, "ccm_covis_create"):               # (an older build timed through CCM_HOT_LIB has no covisibility index)
+        lib.ccm_covis_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
+        lib.ccm_covis_destroy.argtypes = [vp]; lib.ccm_covis_destroy.restype = None
+        lib.ccm_covis_put.argtypes = [vp, C.c_int64, C.c_int, vp, vp]
+        lib.ccm_covis_erase.argtypes = [vp, C.c_int64]
+        lib.ccm_covis_clear.argtypes = [vp]
+        lib.ccm_covis_size.argtypes = [vp]
+        lib.ccm_covis_slot.argtypes = [vp, C.c_int64]
+        lib.ccm_covis_slots.argtypes = [vp]
+        lib.ccm_covis_keys.argtypes = [vp, C.c_int, vp, vp]
+        lib.ccm_covis_query.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(CovisResult)]
+        lib.ccm_covis_lds_features.argtypes = []
+        lib.ccm_covis_arena.argtypes = [vp, vp, vp, vp]
+        lib.ccm_covis_last_timing.argtypes = [vp, vp]
+        lib.ccm_covis_connections.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]
     _lib = lib
     return lib
 

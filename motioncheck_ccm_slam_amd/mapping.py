@@ -156,3 +156,32 @@ class LocalMapping:
         if self._tap is None:
             raise RuntimeError("the last CreateNewMapPoints ran without a tap")
         return self._tap
+
+
+def KeyFrameCulling(index, table, local_keys, protected_keys, thres: float, th_obs: int = 3, ctx=None, on_cull=None):
+    """The loop of LocalMapping::KeyFrameCullingV3 (src/Mapping.cpp:802-862) on a covisibility.CovisibilityIndex: local_keys =
+    GetVectorCovisibleKeyFrames() of the picked keyframe in its order, protected_keys = the keyframes the loop skips (mId.first 0
+    or 1, :807, and mlpRecentAddedKFs, :810), thres = mfRedundancyThres.  One query covers every local keyframe that is left.  The
+    verdict nRedundantObservations > mfRedundancyThres * nMPs (:857) is taken in double.  At the first keyframe that is culled the
+    loop erases it from the index and calls on_cull(key): the caller's pKF->SetBadFlag() (:859) on the map.  That takes the
+    keyframe's observations away, and a point left with two observers turns bad and leaves the keyframes that held it
+    (src/MapPoint.cpp:494), so the caller writes such rows BAD into the table (or puts the records that changed) there; the
+    keyframes behind the culled one are then queried again, since their verdicts may have changed.  Returns the culled keys in
+    order."""
+    from .covisibility import COVIS_REDUNDANCY
+    protected = set(int(k) for k in protected_keys)
+    todo = [int(k) for k in local_keys if int(k) not in protected]
+    culled = []
+    while todo:
+        r = index.query(todo, table=table, what=COVIS_REDUNDANCY, th_obs=th_obs, ctx=ctx)
+        for i, key in enumerate(todo):
+            if float(r.n_redundant[i]) > float(thres) * float(r.n_mps[i]):
+                index.erase(key)
+                if on_cull is not None:
+                    on_cull(key)
+                culled.append(key)
+                todo = todo[i + 1:]
+                break
+        else:
+            todo = []
+    return culled
