@@ -12,18 +12,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import COVIS_REDUNDANCY, COVIS_WEIGHTS  # noqa: F401
+from ._store import _Store, _check
 
 NO_SLOT = 2 ** 31 - 1                                   # a point without a table slot yet: it never matches anything
 TH_CONNECTION = 15                                      # th of UpdateConnections, src/KeyFrame.cpp:673
 TH_OBS = 3                                              # thObs of KeyFrameCullingV3, src/Mapping.cpp:815
 
 QueryResult = collections.namedtuple("QueryResult", "weights n_mps n_redundant skipped seq query_slots")
-
-
-def _check(rc: int, what: str) -> int:
-    if rc < 0:
-        raise _lib.CcmError(rc, what)
-    return rc
 
 
 def connections(weights, rank=None, th: int = TH_CONNECTION):
@@ -39,9 +34,10 @@ def connections(weights, rank=None, th: int = TH_CONNECTION):
     return s[:m].copy(), ow[:m].copy()
 
 
-class CovisibilityIndex:
+class CovisibilityIndex(_Store):
     """Keys are int64 (e.g. the keyframe's idpair packed by the caller).  With ctx=None and bind=False the index is created without
     a device and belongs to the device of the first context that queries it."""
+    _prefix = "ccm_covis_"
 
     def __init__(self, initial_capacity_features: int = 1 << 20, ctx: _lib.Context | None = None, bind: bool = True):
         self.lib = _lib.load()
@@ -52,12 +48,7 @@ class CovisibilityIndex:
             self.ctx.check(rc)
         else:
             _check(rc, "ccm_covis_create")
-        self.handle = h
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            self.lib.ccm_covis_destroy(h); self.handle = None
+        self._open(h)
 
     # ---- the store (no GPU work: the records wait in a pending list until the next query)
     def put(self, key: int, slot, octave):
@@ -67,43 +58,17 @@ class CovisibilityIndex:
         assert s.ndim == 1 and s.shape == o.shape
         _check(self.lib.ccm_covis_put(self.handle, int(key), len(s), _lib.ptr(s), _lib.ptr(o)), "ccm_covis_put")
 
-    def erase(self, key: int):
-        _check(self.lib.ccm_covis_erase(self.handle, int(key)), "ccm_covis_erase")
-
-    def clear(self):
-        _check(self.lib.ccm_covis_clear(self.handle), "ccm_covis_clear")
-
-    def size(self) -> int:
-        return self.lib.ccm_covis_size(self.handle)
-
-    def slots(self) -> int:
-        return self.lib.ccm_covis_slots(self.handle)
-
-    def slot(self, key: int) -> int:
-        return self.lib.ccm_covis_slot(self.handle, int(key))
-
-    def keys(self):
-        """(key per slot, -1 for a free slot; sequence number per slot)."""
-        n = self.slots()
-        k = np.zeros(max(n, 1), "i8"); q = np.zeros(max(n, 1), "i8")
-        m = _check(self.lib.ccm_covis_keys(self.handle, len(k), _lib.ptr(k), _lib.ptr(q)), "ccm_covis_keys")
-        return k[:m], q[:m]
-
     def lds_features(self) -> int:
         """The longest query record whose hash is held in LDS (ccm_covis_lds_features)."""
         return self.lib.ccm_covis_lds_features()
 
     def arena(self):
         """(allocated, tail, live) features of the device arena after the last query's flush."""
-        a = (C.c_int64 * 3)()
-        _check(self.lib.ccm_covis_arena(self.handle, C.byref(a, 0), C.byref(a, 8), C.byref(a, 16)), "ccm_covis_arena")
-        return int(a[0]), int(a[1]), int(a[2])
+        return super().arena()
 
     def last_timing(self):
         """Milliseconds the last query spent in (flush, kernels, download)."""
-        t = np.zeros(3, "f8")
-        _check(self.lib.ccm_covis_last_timing(self.handle, _lib.ptr(t)), "ccm_covis_last_timing")
-        return tuple(float(x) for x in t)
+        return super().last_timing()
 
     # ---- the query
     def query(self, keys, table=None, what: int = COVIS_WEIGHTS | COVIS_REDUNDANCY, th_obs: int = TH_OBS,

@@ -43,7 +43,7 @@ __device__ __forceinline__ bool covis_counts(const CovisQuery& a, int32_t v)
 // The whole workgroup: clears `cells` cells, inserts the counting entries of record r and returns (to every thread) their number
 // in cnt[0] and the number of entries that hold a point but do not count in cnt[1].  cnt: two LDS words, or nullptr when nobody
 // asks.  val may be nullptr.
-__device__ __forceinline__ void covis_build(const CovisQuery& a, const CovisSlot r, int cells, int32_t* key, int32_t* val, int32_t* cnt)
+__device__ __forceinline__ void covis_build(const CovisQuery& a, const RecordSlot r, int cells, int32_t* key, int32_t* val, int32_t* cnt)
 {
     const int tpb = blockDim.x;
     for (int h = threadIdx.x; h < cells; h += tpb) { key[h] = COVIS_EMPTY; if (val) val[h] = 0; }
@@ -73,7 +73,7 @@ __device__ __forceinline__ int covis_wave_sum(int v)
 }
 
 // one wave: the pair count of stored record r against the hash
-__device__ __forceinline__ int covis_record_weight(const CovisQuery& a, const CovisSlot r, int lane, const int32_t* key, uint32_t mask)
+__device__ __forceinline__ int covis_record_weight(const CovisQuery& a, const RecordSlot r, int lane, const int32_t* key, uint32_t mask)
 {
     int pairs = 0;
     for (int base = 0; base < r.len; base += 64 * COVIS_UNROLL) {             // (r.len = -1 for a free slot: no trip)
@@ -153,7 +153,7 @@ __device__ __forceinline__ void covis_redundancy(const CovisQuery& a, const Covi
         for (; todo; todo &= todo - 1, seen++) {
             if (seen % n_waves != wave) continue;                             // wave-uniform
             const int s = s0 + (int)__builtin_ctzll(todo);
-            const CovisSlot r = a.slot[s];
+            const RecordSlot r = a.slot[s];
             for (int base = 0; base < r.len; base += 64 * COVIS_UNROLL) {
                 int32_t v[COVIS_UNROLL];
 #pragma unroll
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(COVIS_TPB) void k_covis_move(CovisMove a)
 {
     const int j = blockIdx.x * COVIS_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= a.n_jobs) return;
-    const CovisMoveJob job = a.job[j];
+    const RecordMoveJob job = a.job[j];
     for (int i = lane; i < job.len; i += 64) {
         a.dst_slots[job.dst + i] = a.src_slots[job.src + i];
         a.dst_octave[job.dst + i] = a.src_octave[job.src + i];

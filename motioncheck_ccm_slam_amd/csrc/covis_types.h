@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "record_types.h"
 
 // Features of a query record up to which its hash lives in LDS: cells = the power of two >= 2 * features (load factor <= 0.5), so
 // 2048 features take 4096 cells: 16 KiB of keys in k_covis_weights, 32 KiB of keys and counters in k_covis_redundancy.  A longer
@@ -15,12 +16,6 @@
 #define COVIS_MP_LIVE 1                    // CCM_MP_LIVE / CCM_MP_BAD of include/ccm_hot.h (covis_host.cpp asserts the equality)
 #define COVIS_MP_BAD 2
 
-struct CovisSlot {                         // one slot of the index as the device sees it
-    int64_t off;                           // first feature of the record in the arena
-    int32_t len;                           // features of the record; -1 = free slot
-    int32_t pad;
-};
-
 struct CovisQ {                            // one query of a launch
     int32_t slot;                          // the stored record that queries
     int32_t cells;                         // hash cells, a power of two >= max(2 * len, 64)
@@ -30,7 +25,7 @@ struct CovisQ {                            // one query of a launch
 struct CovisQuery {
     const int32_t* slots;                  // arena: table slot per feature
     const uint8_t* octave;                 //        octave per feature
-    const CovisSlot* slot;                 // [n_slots]
+    const RecordSlot* slot;                // [n_slots]: offset and length in features
     int32_t n_slots, n_q;
     const CovisQ* q;                       // [n_q]
     const uint8_t* flags;                  // the map-point table's flags column, or nullptr: every entry that holds a point counts
@@ -44,11 +39,10 @@ struct CovisQuery {
     int32_t* skipped;
 };
 
-struct CovisMoveJob { int64_t src, dst; int32_t len, pad; };
 struct CovisMove {                         // copies n_jobs records from one arena into another (growth, compaction)
     const int32_t* src_slots; const uint8_t* src_octave;
     int32_t* dst_slots; uint8_t* dst_octave;
-    const CovisMoveJob* job;
+    const RecordMoveJob* job;
     int32_t n_jobs;
 };
 

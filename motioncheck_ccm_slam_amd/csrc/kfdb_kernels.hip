@@ -23,7 +23,7 @@ __device__ __forceinline__ double kfdb_read_lane(double v, int lane)          //
 
 __device__ __forceinline__ void kfdb_slot(const KfdbQuery& a, int slot, int lane, const int32_t* q_ids, const double* q_vals)
 {
-    const KfdbSlot s = a.slot[slot];
+    const RecordSlot s = a.slot[slot];
     const int q_n = a.q_n;
     const int top = q_n > 0 ? 1 << (31 - __builtin_clz(q_n)) : 0;             // the largest power of two <= q_n
     int count = 0, first = -1;
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64 * KFDB_WAVES) void k_kfdb_move(KfdbMove a)
 {
     const int j = blockIdx.x * KFDB_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= a.n_jobs) return;
-    const KfdbMoveJob job = a.job[j];
+    const RecordMoveJob job = a.job[j];
     for (int i = lane; i < job.len; i += 64) {
         a.dst_ids[job.dst + i] = a.src_ids[job.src + i];
         a.dst_vals[job.dst + i] = a.src_vals[job.src + i];

@@ -2,22 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "record_types.h"
 
 // Query words the kernel stages in LDS (ids int32 + values double = 12 bytes a word, 24 KiB a workgroup); a longer query is
 // searched where it lies in global memory.  ccm_kfdb_query_lds_words() reports it.
 #define KFDB_QUERY_LDS_WORDS 2048
 #define KFDB_WAVES 4                       // waves (= slots) per workgroup of both kernels
 
-struct KfdbSlot {                          // one slot of the database as the device sees it
-    int64_t off;                           // first word of the entry in the arena
-    int32_t len;                           // words of the entry; -1 = free slot
-    int32_t pad;
-};
-
 struct KfdbQuery {
     const int32_t* ids;                    // arena
     const double* vals;
-    const KfdbSlot* slot;                  // [n_slots]
+    const RecordSlot* slot;                // [n_slots]: offset and length in words
     int32_t n_slots;
     int32_t q_n;                           // the query BowVector, on the device (it may lie inside the arena)
     const int32_t* q_ids;
@@ -27,11 +22,10 @@ struct KfdbQuery {
     double* score;
 };
 
-struct KfdbMoveJob { int64_t src, dst; int32_t len, pad; };
 struct KfdbMove {                          // copies n_jobs entries from one arena into another (growth, compaction)
     const int32_t* src_ids; const double* src_vals;
     int32_t* dst_ids; double* dst_vals;
-    const KfdbMoveJob* job;
+    const RecordMoveJob* job;
     int32_t n_jobs;
 };
 

@@ -14,16 +14,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._store import _Store, _check
 
 NEIGHBOURS = 10                                         # CCM_KFDB_NEIGHBOURS: GetBestCovisibilityKeyFrames(10)
 
 QueryResult = collections.namedtuple("QueryResult", "words score first_word seq query_slot")
-
-
-def _check(rc: int, what: str) -> int:
-    if rc < 0:
-        raise _lib.CcmError(rc, what)
-    return rc
 
 
 def shortlist(words, score, first_word, seq, eligible, min_score: float, query_slot: int = -1):
@@ -78,22 +73,18 @@ def min_score_of(score, seq, connected_slots) -> float:
     return float(lib.ccm_kfdb_min_score(len(s), _lib.ptr(s), _lib.ptr(q), len(c), _lib.ptr(c)))
 
 
-class KeyFrameDatabase:
+class KeyFrameDatabase(_Store):
     """Keys are int64 (e.g. the keyframe's idpair packed by the caller); a BowVector is (ids ascending, values)."""
+    _prefix = "ccm_kfdb_"
 
     def __init__(self, n_words: int, initial_capacity_words: int = 1 << 20, ctx: _lib.Context | None = None):
         self.lib = _lib.load()
         self.ctx = ctx if ctx is not None else _lib.default_context(0)
         h = C.c_void_p()
         self.ctx.check(self.lib.ccm_kfdb_create(self.ctx.handle, int(n_words), int(initial_capacity_words), C.byref(h)))
-        self.handle = h
+        self._open(h)
         self.lds_words = self.lib.ccm_kfdb_query_lds_words()
         self.reloc_score = np.zeros(0, np.float32)                      # mRelocScore per slot, kept from one query to the next
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            self.lib.ccm_kfdb_destroy(h); self.handle = None
 
     # ---- the store (no GPU work: the entries wait in a pending list until the next query)
     def add(self, key: int, ids, vals):
@@ -103,11 +94,8 @@ class KeyFrameDatabase:
                "ccm_kfdb_add: ids must be strictly ascending and inside the vocabulary, the key new")
         self._reloc_reset(key)
 
-    def erase(self, key: int):
-        _check(self.lib.ccm_kfdb_erase(self.handle, int(key)), "ccm_kfdb_erase")
-
     def clear(self):
-        _check(self.lib.ccm_kfdb_clear(self.handle), "ccm_kfdb_clear")
+        super().clear()
         self.reloc_score = np.zeros(0, np.float32)
 
     def _reloc_reset(self, key: int):
@@ -120,33 +108,13 @@ class KeyFrameDatabase:
             self.reloc_score = np.concatenate([self.reloc_score, np.zeros(max(n, 2 * len(self.reloc_score)) - len(self.reloc_score), np.float32)])
         return self.reloc_score
 
-    def size(self) -> int:
-        return self.lib.ccm_kfdb_size(self.handle)
-
-    def slots(self) -> int:
-        return self.lib.ccm_kfdb_slots(self.handle)
-
-    def slot(self, key: int) -> int:
-        return self.lib.ccm_kfdb_slot(self.handle, int(key))
-
-    def keys(self):
-        """(key per slot, -1 for a free slot; sequence number per slot)."""
-        n = self.slots()
-        k = np.zeros(max(n, 1), "i8"); q = np.zeros(max(n, 1), "i8")
-        m = _check(self.lib.ccm_kfdb_keys(self.handle, len(k), _lib.ptr(k), _lib.ptr(q)), "ccm_kfdb_keys")
-        return k[:m], q[:m]
-
     def arena(self):
         """(allocated, tail, live) words of the device arena after the last query's flush."""
-        a = (C.c_int64 * 3)()
-        _check(self.lib.ccm_kfdb_arena(self.handle, C.byref(a, 0), C.byref(a, 8), C.byref(a, 16)), "ccm_kfdb_arena")
-        return int(a[0]), int(a[1]), int(a[2])
+        return super().arena()
 
     def last_timing(self):
         """Milliseconds the last query spent in (flush, kernel, download)."""
-        t = np.zeros(3, "f8")
-        _check(self.lib.ccm_kfdb_last_timing(self.handle, _lib.ptr(t)), "ccm_kfdb_last_timing")
-        return tuple(float(x) for x in t)
+        return super().last_timing()
 
     # ---- queries
     def query(self, key: int | None = None, bow=None, ctx: _lib.Context | None = None) -> QueryResult:

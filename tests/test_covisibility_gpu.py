@@ -382,6 +382,33 @@ def test_arena_grows_and_is_compacted(ctx):
     check(ix, records, [77, 78])
 
 
+def test_replacing_uploaded_records_triggers_the_compaction(ctx):
+    """Holes left by `put` of present keys alone (no erase) pass half of the used arena: the next query compacts around the records
+    that were not replaced and appends the replacements, in a capacity that does not change."""
+    rng = np.random.default_rng(16)
+    ix = V.CovisibilityIndex(512, ctx=ctx)
+    records = {}
+
+    def put(key, n):
+        records[key] = (rng.choice(200, n, replace=False).astype("i4"), rng.integers(0, 8, n).astype(U8))
+        ix.put(key, *records[key])
+
+    for key in range(12):
+        put(key, 30)
+    before = check(ix, records, [0, 5, 11])
+    assert ix.arena() == (512, 360, 360)
+    for key in range(1, 9):                                             # 240 of the 360 uploaded features become holes
+        put(key, 25 + key)
+    after = check(ix, records, [0, 5, 11])                              # 5 was replaced; 0 and 11 were moved
+    live = sum(len(s) for s, _ in records.values())
+    assert ix.arena() == (512, live, live) and live == 120 + 8 * 25 + 36
+    assert np.array_equal(after.seq, before.seq) and [ix.slot(k) for k in range(12)] == list(range(12))
+    assert np.array_equal(after.weights[[0, 2]][:, [0, 9, 10, 11]], before.weights[[0, 2]][:, [0, 9, 10, 11]])
+    put(9, 31)                                                          # one hole of 30 in 356: no compaction, the record goes to the tail
+    check(ix, records, [9, 0])
+    assert ix.arena() == (512, live + 31, live + 1)
+
+
 def test_argument_checks(ctx):
     lib = _lib.load()
     ix = V.CovisibilityIndex(64, ctx=ctx)
