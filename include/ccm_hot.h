@@ -1321,6 +1321,118 @@ int ccm_sim3_solver_state(const ccm_sim3_solver*, int k, int32_t* iterations, in
  * correspondence i at bit i % 64 of word i / 64. */
 int ccm_sim3_solver_hypotheses(const ccm_sim3_solver*, int k, int32_t* sample, int32_t* count, float* rts, uint64_t* mask);
 
+/* ---- ComputeSim3 on handles: the solver, OptimizeSim3 and the chain.  Links 2 and 4 of LoopFinder::ComputeSim3 / MapMatcher::ComputeSim3
+ * with their correspondences named by features, and links 3 + 4 as one call.  A correspondence is a pair of features, i1 of kf1 and i2
+ * of kf2; its two map points are the slots the handles hold at those features in mp_id (ccm_frame_set_map_points; the handles need no
+ * bow, camera or pose part).  That is vpKeyFrameMP1[i1] exactly, and vpMatched12[i1] for side 2 as long as mObservations and
+ * mvpMapPoints agree -- the assumption `observed` of ccm_search_by_projection_table_frames already rests on.  Eight bytes a
+ * correspondence go up and nothing per map point.  Per pair the call carries T1w and T2w (rows of [R | t], as in
+ * ccm_sim3_search_pair) and K1, K2 (fx, fy, cx, cy); per side and call a table per pyramid level, which the kernels index by the
+ * feature's octave without arithmetic: max_err_level for the solver -- mvnMaxError is a vector of size_t (include/cslam/Sim3Solver.h:
+ * 74-75), so the caller passes (float)(size_t)(9.210 * mvLevelSigma2[level]) -- and inv_level_sigma2 for the optimiser.
+ * Camera-frame points are Xc = R X + t as the "matrix product" defined under "ComputeSim3 on keyframe handles and the table": the
+ * solver reads that float, the optimiser reads it, the keypoint and inv_level_sigma2[octave] widened to double (Converter::toVector3d
+ * and the Eigen assignments of src/Optimizer.cpp:938-989).  The gathers therefore store the bits the array routes are given by a
+ * caller who forms them so, and everything behind them is the array routes' own kernel. */
+typedef struct {
+    ccm_frame* kf1; ccm_frame* kf2;    /* features and mp_id (table slots) are read; may be the same handle */
+    float T1w[12], T2w[12];            /* rows of [R1w | t1w], [R2w | t2w] */
+    float K1[4], K2[4];                /* fx, fy, cx, cy of pKF1 / pKF2 */
+} ccm_sim3_frames_pair;
+
+/* ccm_sim3_solver_create with the constructor's loop (src/Sim3Solver.cpp:30-83) on the device: k_sim3_solver_gather, one thread per
+ * correspondence, fills the four arrays X1 / X2 / max_err1 / max_err2 in front of k_sim3_ransac.  indices1 = feature1, n1[k] = kf1's N.
+ * first, fix_scale, the RANSAC parameters, draws, best_inliers and the solver object (every ccm_sim3_solver_* call) are
+ * ccm_sim3_solver_create's.  The caller still filters "set and not bad" (:32-59): it needs N for its draws.  Takes a shared lock on
+ * the table's rows, works through a view (ccm_map_table_attach), ordered behind earlier writes of handles and table on the context's
+ * stream.  CCM_E_ARG with *out untouched: what ccm_sim3_solver_create refuses, a NULL pair, handle or table, n_levels outside
+ * 1..CCM_MAX_LEVELS, and -- found on the device before an address is formed -- a feature outside its handle, an mp_id below 0 or
+ * outside the table, a slot that is not LIVE, an octave outside [0, n_levels).  A BAD slot is not an error.  (A batch none of whose
+ * solvers evaluates a hypothesis launches nothing, the gather included, as for ccm_pnp_solver_create_frames.) */
+typedef struct {
+    int32_t        n_solvers;
+    const ccm_sim3_frames_pair* pairs;          /* [n_solvers] */
+    const int32_t* first;        /* [n_solvers+1] */
+    const int32_t* fix_scale;    /* [n_solvers] */
+    const int32_t* feature1;     /* [..] feature of kf1 */
+    const int32_t* feature2;     /* [..] feature of kf2 */
+    int32_t n_levels1;  const float* max_err_level1;    /* [n_levels1] side 1 */
+    int32_t n_levels2;  const float* max_err_level2;
+    double         probability;
+    int32_t        min_inliers;
+    int32_t        max_iterations;
+    const int32_t* draws;        /* [n_solvers][max_iterations][3] */
+    const int32_t* best_inliers; /* [n_solvers] or NULL */
+} ccm_sim3_solver_frames_problem;
+int ccm_sim3_solver_create_frames(ccm_ctx*, ccm_map_table*, const ccm_sim3_solver_frames_problem*, ccm_sim3_solver** out);
+
+/* ccm_optimize_sim3 for n_problems pairs whose correspondences are (feature1, feature2) lists; the caller has applied
+ * src/Optimizer.cpp:922-935.  k_sim3_opt_gather fills P1, P2, obs1, obs2, info1, info2 and the unchanged k_sim3_opt runs: for the same
+ * pairs the call stores the bits ccm_optimize_sim3 stores.  sim3 [n_problems][8] is in/out, inlier [first[n_problems]] and n_inliers
+ * [n_problems] as there.  Locking, order and the errors of a correspondence as for ccm_sim3_solver_create_frames; on an error the
+ * outputs are untouched.  One staging copy up, one download, one synchronisation. */
+typedef struct {
+    int32_t        n_problems;
+    const ccm_sim3_frames_pair* pairs;          /* [n_problems] */
+    const int32_t* first;        /* [n_problems+1] */
+    const int32_t* fix_scale;    /* [n_problems] */
+    const float*   th2;          /* [n_problems] */
+    const int32_t* feature1;
+    const int32_t* feature2;
+    int32_t n_levels1;  const float* inv_level_sigma2_1;    /* [n_levels1] mvInvLevelSigma2 of side 1 */
+    int32_t n_levels2;  const float* inv_level_sigma2_2;
+} ccm_sim3_opt_frames_problem;
+typedef struct {
+    double*  sim3;               /* [n_problems][8] in/out */
+    uint8_t* inlier;             /* [..] out */
+    int32_t* n_inliers;          /* [n_problems] out */
+} ccm_sim3_opt_frames_result;
+int ccm_optimize_sim3_table_frames(ccm_ctx*, ccm_map_table*, const ccm_sim3_opt_frames_problem*, ccm_sim3_opt_frames_result*);
+
+/* From the RANSAC estimate to OptimizeSim3's verdict (src/LoopFinder.cpp:313-330, src/MapMatcher.cpp:318-333) in one call, for every
+ * candidate that returned an Scm in one pass of the round-robin.
+ *   a. ccm_search_by_sim3_table_frames on `search` of every pair, unchanged; match12 stays on the device.
+ *   b. k_sim3_chain_list: per pair, in ascending i1, feature i1 has a match when matched12[i1] >= 0 (then i2 = matched_idx2[i1]) or
+ *      match12[i1] >= 0 (then i2 = match12[i1]).  A match becomes a correspondence when kf1's mp_id[i1] names a LIVE slot that is not
+ *      BAD, 0 <= i2 < N2 and kf2's mp_id[i2] names a LIVE slot that is not BAD (src/Optimizer.cpp:933-935).  Any other match is left
+ *      alone, as the reference `continue`s with vpMatches1[i] still set: a filtered match is never an error.
+ *   c. k_sim3_opt_gather and k_sim3_opt on the list, with sim3 (the gScm the caller made of R, t, s), fix_scale and th2 per pair,
+ *      K1 = search.fx .. cy and K2.
+ *   d. pruned[i1] = 1 exactly where OptimizeSim3 set vpMatches1[i1] to NULL, the first-round prunes of a problem that then
+ *      returned 0 (:1032) included; 0 elsewhere.
+ * Result: search.match12 / n_found (and the search call's taps) as ccm_search_by_sim3_table_frames gives them; pruned flat over the
+ * side-1 features like match12; n_correspondences, n_inliers and sim3 per pair, sim3 untouched in bits where fewer than 10
+ * correspondences survive the first round.  Optional taps: corr, the list as (i1, i2) rows, pair p's rows from n_correspondences[0]
+ * + .. + n_correspondences[p-1] on ([sum N1][2] holds any list), and inlier per row ([sum N1]).
+ * Traffic: one staging copy up; two synchronisations, on the number of queries and on the result; the downloads of the result.
+ * Everything behind the query count is queued without a host round trip.  Locking, stream order and errors as for
+ * ccm_search_by_sim3_table_frames: found on the host before anything is queued, the outputs then untouched.  In addition CCM_E_ARG for
+ * NULL pruned / n_correspondences / n_inliers / sim3, inv_level_sigma2_1 / 2, or a handle whose octaves reach beyond n_levels1 / 2
+ * (the handle knows its highest octave).  The function returns the sum of n_found. */
+typedef struct {
+    ccm_sim3_search_pair search;       /* matched12 / matched_idx2: the solver's inliers; only matched12 >= 0 is read of it */
+    float   K2[4];                     /* fx, fy, cx, cy of pKF2 (search.fx .. cy are pKF1's) */
+    double  sim3[8];                   /* gScm: qx, qy, qz, qw, tx, ty, tz, s */
+    int32_t fix_scale;
+    float   th2;                       /* 10 in LoopFinder, 20 in MapMatcher */
+} ccm_compute_sim3_pair;
+typedef struct {
+    int32_t n_pairs;  const ccm_compute_sim3_pair* pairs;
+    float th;                                                    /* the search threshold, 7.5 */
+    float log_scale_factor1;  int32_t n_levels1;  const float* scale_factors1;  const float* inv_level_sigma2_1;   /* [n_levels1] */
+    float log_scale_factor2;  int32_t n_levels2;  const float* scale_factors2;  const float* inv_level_sigma2_2;
+} ccm_compute_sim3_problem;
+typedef struct {
+    ccm_sim3_search_result search;     /* match12, n_found and the optional taps of the search */
+    uint8_t* pruned;                   /* [sum N1] */
+    int32_t* n_correspondences;        /* [n_pairs] */
+    int32_t* n_inliers;                /* [n_pairs] OptimizeSim3's return value */
+    double*  sim3;                     /* [n_pairs][8] */
+    int32_t* corr;                     /* optional tap [sum N1][2] */
+    uint8_t* inlier;                   /* optional tap [sum N1] */
+} ccm_compute_sim3_result;
+int ccm_compute_sim3_table_frames(ccm_ctx*, ccm_map_table*, const ccm_compute_sim3_problem*, ccm_compute_sim3_result*);
+
 /* ---------------------------------------------------------------- PnPsolver (src/PnPSolver.cpp), batched EPnP RANSAC
  * The link between SearchByBoW against the relocalisation candidates (ccm_kfdb_query_vector, ccm_search_by_bow_frames) and the
  * relocalisation overload of SearchByProjection: one PnPsolver per candidate keyframe, iterate(5) round-robin as ORB-SLAM's

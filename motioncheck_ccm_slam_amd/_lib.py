@@ -44,6 +44,7 @@ SYMBOLS = [
     "ccm_fuse_select_table_frames", "ccm_frame_track_motion_model", "ccm_frame_search_by_projection_keyframe",
     "ccm_frame_relocalize_candidate",
     "ccm_search_by_sim3_table_frames", "ccm_search_by_projection_table_frames",
+    "ccm_sim3_solver_create_frames", "ccm_optimize_sim3_table_frames", "ccm_compute_sim3_table_frames",
     "ccm_sim3_ransac_iterations", "ccm_sim3_solver_create", "ccm_sim3_solver_destroy", "ccm_sim3_solver_count", "ccm_sim3_solver_iterate",
     "ccm_sim3_solver_find", "ccm_sim3_solver_estimate", "ccm_sim3_solver_state", "ccm_sim3_solver_hypotheses",
     "ccm_pnp_ransac_parameters", "ccm_pnp_compute_pose", "ccm_pnp_solver_create", "ccm_pnp_solver_destroy", "ccm_pnp_solver_count",
@@ -312,6 +313,42 @@ class Sim3SearchResult(C.Structure):
                 ("gate2", C.c_void_p), ("u2", C.c_void_p), ("v2", C.c_void_p), ("level2", C.c_void_p), ("sel2", C.c_void_p)]
 
 
+class Sim3FramesPair(C.Structure):                    # ccm_sim3_frames_pair
+    _fields_ = [("kf1", C.c_void_p), ("kf2", C.c_void_p), ("T1w", C.c_float * 12), ("T2w", C.c_float * 12), ("K1", C.c_float * 4), ("K2", C.c_float * 4)]
+
+
+class Sim3SolverFramesProblem(C.Structure):           # ccm_sim3_solver_frames_problem
+    _fields_ = [("n_solvers", C.c_int32), ("pairs", C.POINTER(Sim3FramesPair)), ("first", C.c_void_p), ("fix_scale", C.c_void_p),
+                ("feature1", C.c_void_p), ("feature2", C.c_void_p), ("n_levels1", C.c_int32), ("max_err_level1", C.c_void_p),
+                ("n_levels2", C.c_int32), ("max_err_level2", C.c_void_p), ("probability", C.c_double), ("min_inliers", C.c_int32),
+                ("max_iterations", C.c_int32), ("draws", C.c_void_p), ("best_inliers", C.c_void_p)]
+
+
+class Sim3OptFramesProblem(C.Structure):              # ccm_sim3_opt_frames_problem
+    _fields_ = [("n_problems", C.c_int32), ("pairs", C.POINTER(Sim3FramesPair)), ("first", C.c_void_p), ("fix_scale", C.c_void_p),
+                ("th2", C.c_void_p), ("feature1", C.c_void_p), ("feature2", C.c_void_p), ("n_levels1", C.c_int32),
+                ("inv_level_sigma2_1", C.c_void_p), ("n_levels2", C.c_int32), ("inv_level_sigma2_2", C.c_void_p)]
+
+
+class Sim3OptFramesResult(C.Structure):               # ccm_sim3_opt_frames_result
+    _fields_ = [("sim3", C.c_void_p), ("inlier", C.c_void_p), ("n_inliers", C.c_void_p)]
+
+
+class ComputeSim3Pair(C.Structure):                   # ccm_compute_sim3_pair
+    _fields_ = [("search", Sim3SearchPair), ("K2", C.c_float * 4), ("sim3", C.c_double * 8), ("fix_scale", C.c_int32), ("th2", C.c_float)]
+
+
+class ComputeSim3Problem(C.Structure):                # ccm_compute_sim3_problem
+    _fields_ = [("n_pairs", C.c_int32), ("pairs", C.POINTER(ComputeSim3Pair)), ("th", C.c_float),
+                ("log_scale_factor1", C.c_float), ("n_levels1", C.c_int32), ("scale_factors1", C.c_void_p), ("inv_level_sigma2_1", C.c_void_p),
+                ("log_scale_factor2", C.c_float), ("n_levels2", C.c_int32), ("scale_factors2", C.c_void_p), ("inv_level_sigma2_2", C.c_void_p)]
+
+
+class ComputeSim3Result(C.Structure):                 # ccm_compute_sim3_result
+    _fields_ = [("search", Sim3SearchResult), ("pruned", C.c_void_p), ("n_correspondences", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("sim3", C.c_void_p), ("corr", C.c_void_p), ("inlier", C.c_void_p)]
+
+
 class LoopView(C.Structure):
     _fields_ = [("view", FuseView), ("matched_slot", C.c_void_p)]
 
@@ -490,6 +527,9 @@ def load():
     lib.ccm_frame_relocalize_candidate.argtypes = [vp, vp, vp, vp, C.POINTER(RelocParams), C.POINTER(RelocResult)]
     lib.ccm_sim3_ransac_iterations.argtypes =[C.c_int, C.c_double, C.c_int, C.c_int]
     lib.ccm_sim3_solver_create.argtypes = [vp, C.POINTER(Sim3RansacProblem), C.POINTER(vp)]
+    lib.ccm_sim3_solver_create_frames.argtypes = [vp, vp, C.POINTER(Sim3SolverFramesProblem), C.POINTER(vp)]
+    lib.ccm_optimize_sim3_table_frames.argtypes = [vp, vp, C.POINTER(Sim3OptFramesProblem), C.POINTER(Sim3OptFramesResult)]
+    lib.ccm_compute_sim3_table_frames.argtypes = [vp, vp, C.POINTER(ComputeSim3Problem), C.POINTER(ComputeSim3Result)]
     lib.ccm_sim3_solver_destroy.argtypes = [vp]; lib.ccm_sim3_solver_destroy.restype = None
     lib.ccm_sim3_solver_count.argtypes = [vp]
     lib.ccm_sim3_solver_iterate.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]

@@ -1,10 +1,11 @@
 // mpt_internal.h -- what the host translation units of the map-point table share: mpt_host.cpp (the table itself and its refresh),
-// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_correct_host.cpp (loop and
+// mpt_fuse_host.cpp (Fuse on the table), mpt_sim3_host.cpp (ComputeSim3's two matchers on the table), mpt_sim3_opt_host.cpp (its solver, optimiser and chain), mpt_correct_host.cpp (loop and
 // merge corrections), mpt_track_host.cpp (SearchLocalPoints,
 // TrackWithMotionModel) and frame_pose_host.cpp (the pose on table points).  Every call stages through the frame handles' block (FrameState::stage, frame_internal.h).
 #pragma once
 #include "frame_internal.h"
 #include "mpt_types.h"
+#include "sim3_frames_types.h"
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -138,3 +139,36 @@ static inline int mark_slots(ccm_ctx* c, ccm_map_table* t, int n, const int32_t*
     }
     return CCM_OK;
 }
+
+// What the gathers of mpt_sim3_opt_kernels.hip read of a pair of the caller's
+static inline Sim3FramesPair sim3_frames_pair(const ccm_frame* k1, const ccm_frame* k2, const float* T1w, const float* T2w)
+{
+    Sim3FramesPair V{};
+    std::memcpy(V.T1w, T1w, sizeof V.T1w); std::memcpy(V.T2w, T2w, sizeof V.T2w);
+    V.n1 = k1->n; V.n2 = k2->n;
+    V.kx1 = k1->kx; V.ky1 = k1->ky; V.oct1 = k1->oct; V.mp1 = k1->mp_id;
+    V.kx2 = k2->kx; V.ky2 = k2->ky; V.oct2 = k2->oct; V.mp2 = k2->mp_id;
+    return V;
+}
+
+// What ccm_compute_sim3_table_frames (mpt_sim3_opt_host.cpp) hangs on the pipeline of ccm_search_by_sim3_table_frames (mpt_sim3_host.cpp):
+// a segment of its own in the result part and in the input part of the staging block and in the work area, the launches behind
+// k_sim3_agree, and the delivery after the one download.  The search lays the block out, uploads and downloads; the chain says how
+// much it needs (size) and works inside its segments.
+struct Sim3Chain {
+    const ccm_compute_sim3_problem* p; ccm_compute_sim3_result* r;
+    int n_pairs = 0; size_t sum1 = 0;
+    size_t res_bytes = 0, in_bytes = 0, work_bytes = 0;
+    size_t r_pruned = 0, r_first = 0, r_nin = 0, r_status = 0, r_f1 = 0, r_f2 = 0, r_inl = 0;         // offsets inside the segments
+    size_t i_sim3 = 0, i_K1 = 0, i_K2 = 0, i_fix = 0, i_th2 = 0, i_view = 0, i_t1 = 0, i_t2 = 0, w_cnt = 0, w_f1 = 0, w_f2 = 0, w_inl = 0;
+    void size(int n_pairs, size_t sum1);
+    void fill(Staging& G, size_t o_in) const;                                  // the inputs, before the upload
+    // everything from the list to the scatter, and the download of sim3; nothing is awaited
+    int queue(ccm_ctx* c, const MptTable& T, Staging& G, size_t o_res, size_t o_in, uint8_t* work, int max_n1, const Sim3Pair* d_pair,
+              const int* d_matched12, const int* d_matched_idx2, const int* d_match12) const;
+    int deliver(ccm_ctx* c, const Staging& G, size_t o_res, size_t o_in) const;
+    void none() const;                                                         // a call without a feature on either side
+};
+// What ccm_search_by_sim3_table_frames refuses before it takes the lock (n_pairs == 0 passes), and its body under the lock, with the chain (or nullptr) behind the agreement kernel
+int sim3_search_check(ccm_ctx* c, const ccm_map_table* t, const ccm_sim3_search_problem* p, const ccm_sim3_search_result* r, const char* fn);
+int sim3_search_run(ccm_ctx* c, ccm_map_table* t, const ccm_sim3_search_problem* p, ccm_sim3_search_result* r, const char* fn, Sim3Chain* chain);

@@ -8,6 +8,141 @@
 static_assert(sizeof(Sim3View) == 168 && sizeof(Sim3Pair) == 16 && sizeof(WinGrid) == 80, "per-pair upload of ccm_search_by_sim3_table_frames");
 static_assert(sizeof(FuseView) == 112 && sizeof(GreedyKf) == 16, "per-view upload of ccm_search_by_projection_table_frames");
 
+// What ccm_search_by_sim3_table_frames refuses before it takes the lock; n_pairs == 0 passes
+int sim3_search_check(ccm_ctx* c, const ccm_map_table* t, const ccm_sim3_search_problem* p, const ccm_sim3_search_result* r, const char* fn)
+{
+    int rc = check_table(c, t);
+    if (rc) return rc;
+    if (p->n_pairs < 0) return ccm_fail(c, CCM_E_ARG, "%s: n_pairs = %d", fn, p->n_pairs);
+    if (p->n_pairs == 0) return CCM_OK;
+    if (!p->pairs || !p->scale_factors1 || !p->scale_factors2 || !r->n_found)
+        return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !p->pairs ? "pairs" : !r->n_found ? "n_found" : "scale_factors1 / scale_factors2");
+    if (p->n_levels1 < 1 || p->n_levels1 > CCM_MAX_LEVELS || p->n_levels2 < 1 || p->n_levels2 > CCM_MAX_LEVELS)
+        return ccm_fail(c, CCM_E_ARG, "%s: n_levels = %d, %d outside 1..%d", fn, p->n_levels1, p->n_levels2, CCM_MAX_LEVELS);
+    if (((r->u1 || r->v1 || r->level1) && !(r->u1 && r->v1 && r->level1)) || ((r->u2 || r->v2 || r->level2) && !(r->u2 && r->v2 && r->level2)))
+        return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and level of a direction come together", fn);
+    if (p->n_pairs > 32767) return ccm_fail(c, CCM_E_CAPACITY, "%s: %d pairs; at most 32767 a call", fn, p->n_pairs);
+    return CCM_OK;
+}
+
+// The pipeline of ccm_search_by_sim3_table_frames, whose arguments the entry point has checked, under the table's lock
+int sim3_search_run(ccm_ctx* c, ccm_map_table* t, const ccm_sim3_search_problem* p, ccm_sim3_search_result* r, const char* fn, Sim3Chain* chain)
+{
+    int rc;
+    const int n_pairs = p->n_pairs, n_views = 2 * n_pairs;
+    std::vector<Sim3Pair> pr(n_pairs);
+    size_t sum1 = 0, sum2 = 0;
+    int max_n = 0, max_n1 = 0;
+    for (int k = 0; k < n_pairs; k++) {
+        const ccm_sim3_search_pair& P = p->pairs[k];
+        if (!P.kf1 || !P.kf2) return ccm_fail(c, CCM_E_ARG, "%s: null pairs[%d].%s", fn, k, !P.kf1 ? "kf1" : "kf2");
+        if ((rc = frame_named_check(c, P.kf1, CCM_E_STATE, fn, "pairs[%d].kf1", k)) || (rc = frame_named_check(c, P.kf2, CCM_E_STATE, fn, "pairs[%d].kf2", k)))
+            return rc;
+        if (P.kf1->n > 0 && (!P.matched12 || !P.matched_idx2)) return ccm_fail(c, CCM_E_ARG, "%s: null pairs[%d].matched12 / matched_idx2", fn, k);
+        pr[k] = Sim3Pair{ P.kf1->n, P.kf2->n, (int)sum1, (int)sum2 };
+        sum1 += (size_t)P.kf1->n; sum2 += (size_t)P.kf2->n;
+        max_n = std::max(max_n, std::max(P.kf1->n, P.kf2->n)); max_n1 = std::max(max_n1, P.kf1->n);
+        if (sum1 + sum2 > ((size_t)1 << 24)) return ccm_fail(c, CCM_E_CAPACITY, "%s: more than 2^24 features in one call", fn);
+    }
+    if (sum1 > 0 && !r->match12) return ccm_fail(c, CCM_E_ARG, "%s: null match12", fn);
+    const size_t E = sum1 + sum2;
+    if (E == 0 || max_n1 == 0) {                                           // no feature on side 1: nothing can match
+        for (int k = 0; k < n_pairs; k++) r->n_found[k] = 0;
+        if (E == 0) { if (chain) chain->none(); return 0; }
+    }
+    if (chain) chain->size(n_pairs, sum1);
+
+    CCM_HIP(c, hipSetDevice(c->device));
+    FrameState& S = *frame_state(c);
+    Staging& G = S.stage;
+    hipStream_t st = c->stream;
+    const bool tap_sel = r->sel1 || r->sel2, tap_gate = r->gate1 || r->gate2, taps = r->u1 || r->u2;
+    size_t off = 0;
+    const size_t o_cnt = seg(off, 16), o_m12 = seg(off, sum1 * 4), o_sel = seg(off, tap_sel ? E * 4 : 0), o_gate = seg(off, tap_gate ? E : 0);
+    const size_t o_u = seg(off, taps ? E * 4 : 0), o_v = seg(off, taps ? E * 4 : 0), o_lvl = seg(off, taps ? E * 4 : 0);
+    const size_t o_chain = seg(off, chain ? chain->res_bytes : 0);
+    const size_t res_end = off;
+    const size_t o_view = seg(off, (size_t)n_views * sizeof(Sim3View)), o_grid = seg(off, (size_t)n_views * sizeof(WinGrid));
+    const size_t o_pair = seg(off, (size_t)n_pairs * sizeof(Sim3Pair)), o_mi = seg(off, sum1 * 4), o_mx = seg(off, sum1 * 4);
+    const size_t o_chin = seg(off, chain ? chain->in_bytes : 0);
+    const size_t end = off;
+    if ((rc = G.reserve(c, end))) return rc;
+    size_t w = 0;                                                          // device-only work area
+    const size_t w_am2 = seg(w, sum2), w_sel = seg(w, tap_sel ? 0 : E * 4), w_qx = seg(w, E * 4), w_qy = seg(w, E * 4), w_qr = seg(w, E * 4);
+    const size_t w_minl = seg(w, E * 4), w_maxl = seg(w, E * 4), w_qview = seg(w, E * 4), w_qent = seg(w, E * 4), w_qdesc = seg(w, E * 32);
+    const size_t w_si = seg(w, E * 4), w_sd = seg(w, E * 4), w_chain = seg(w, chain ? chain->work_bytes : 0);
+    CCM_RESERVE(c, S.fuse, w + 64);
+    uint8_t* wk = S.fuse.as<uint8_t>();
+
+    Sim3View* hv = G.host<Sim3View>(o_view); WinGrid* hg = G.host<WinGrid>(o_grid);
+    const int* d_mi = G.dev<int>(o_mi);
+    for (int k = 0; k < n_pairs; k++) {
+        const ccm_sim3_search_pair& P = p->pairs[k];
+        for (int d = 0; d < 2; d++) {
+            const ccm_frame* src = d ? P.kf2 : P.kf1; const ccm_frame* dst = d ? P.kf1 : P.kf2;
+            const float* bounds = d ? P.bounds1 : P.bounds2;
+            Sim3View& D = hv[2 * k + d];
+            std::memcpy(D.Tsw, d ? P.T2w : P.T1w, sizeof D.Tsw); std::memcpy(D.Sts, d ? P.S12 : P.S21, sizeof D.Sts);
+            D.fx = P.fx; D.fy = P.fy; D.cx = P.cx; D.cy = P.cy;
+            D.min_x = bounds[0]; D.max_x = bounds[1]; D.min_y = bounds[2]; D.max_y = bounds[3];
+            D.n = src->n; D.n_target = dst->n; D.e0 = d ? (int)sum1 + pr[k].first2 : pr[k].first1; D.side_t = d ? 0 : 1;
+            D.mp_id = src->mp_id;
+            D.mark_i = d ? nullptr : d_mi + pr[k].first1;
+            D.mark_b = d ? wk + w_am2 + pr[k].first2 : nullptr;
+            hg[2 * k + d] = frame_win_grid(dst);
+        }
+        G.put(o_mi + (size_t)pr[k].first1 * 4, P.matched12, (size_t)pr[k].n1 * 4);
+        G.put(o_mx + (size_t)pr[k].first1 * 4, P.matched_idx2, (size_t)pr[k].n1 * 4);
+    }
+    std::memcpy(G.host<Sim3Pair>(o_pair), pr.data(), (size_t)n_pairs * sizeof(Sim3Pair));
+    if (chain) chain->fill(G, o_chin);
+    if ((rc = G.upload(c, o_view, end))) return rc;
+
+    Sim3Args A{};
+    A.n_views = n_views; A.n_entries = (int)E; A.views = G.dev<Sim3View>(o_view);
+    A.log_scale[0] = p->log_scale_factor1; A.log_scale[1] = p->log_scale_factor2; A.n_levels[0] = p->n_levels1; A.n_levels[1] = p->n_levels2;
+    fill_levels(A.scale[0], p->scale_factors1, p->n_levels1); fill_levels(A.scale[1], p->scale_factors2, p->n_levels2);
+    A.th = p->th;
+    A.sel = tap_sel ? G.dev<int>(o_sel) : (int*)(wk + w_sel);
+    A.gate = tap_gate ? G.dev<uint8_t>(o_gate) : nullptr;
+    A.u = taps ? G.dev<float>(o_u) : nullptr; A.v = taps ? G.dev<float>(o_v) : nullptr; A.level = taps ? G.dev<int>(o_lvl) : nullptr;
+    A.cnt = G.dev<int>(o_cnt); A.qx = (float*)(wk + w_qx); A.qy = (float*)(wk + w_qy); A.qr = (float*)(wk + w_qr);
+    A.minl = (int*)(wk + w_minl); A.maxl = (int*)(wk + w_maxl); A.qview = (int*)(wk + w_qview); A.qent = (int*)(wk + w_qent); A.qdesc = wk + w_qdesc;
+    const Sim3Pair* d_pair = G.dev<Sim3Pair>(o_pair);
+    CCM_HIP(c, hipMemsetAsync(A.cnt, 0, 16, st));
+    if (sum2) CCM_HIP(c, hipMemsetAsync(wk + w_am2, 0, sum2, st));
+    sim3_launch_marks(st, n_pairs, max_n1, d_pair, d_mi, G.dev<int>(o_mx), wk + w_am2);
+    sim3_launch_project(st, A, t->T, max_n);
+    CCM_HIP(c, hipGetLastError());
+    if ((rc = G.download(c, 0, 16)) || (rc = G.wait(c))) return rc;        // the number of queries: the first synchronisation
+    int nq = 0;
+    G.get(&nq, o_cnt, 4);
+    if (nq < 0 || (size_t)nq > E) return ccm_fail(c, CCM_E_DEVICE, "%s: %d queries of %zu features", fn, nq, E);
+    if (nq > 0) {
+        match_launch_window_select_batch(st, G.dev<WinGrid>(o_grid), A.qview, nq, A.qx, A.qy, A.qr, A.minl, A.maxl, A.qdesc, nullptr, 100,   // TH_HIGH
+                                         (int*)(wk + w_si), (int*)(wk + w_sd));
+        fuse_launch_scatter(st, nq, (int)E, A.qent, (const int*)(wk + w_si), (const int*)(wk + w_sd), A.sel, nullptr);
+    }
+    sim3_launch_agree(st, n_pairs, max_n1, d_pair, A.sel, (int)sum1, G.dev<int>(o_m12));
+    CCM_HIP(c, hipGetLastError());
+    if (chain && (rc = chain->queue(c, t->T, G, o_chain, o_chin, wk + w_chain, max_n1, d_pair, d_mi, G.dev<int>(o_mx), G.dev<int>(o_m12)))) return rc;
+    if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;   // the second
+    if (chain && (rc = chain->deliver(c, G, o_chain, o_chin))) return rc;
+    G.get(r->match12, o_m12, sum1 * 4);
+    G.get(r->sel1, o_sel, sum1 * 4); G.get(r->sel2, o_sel + sum1 * 4, sum2 * 4);
+    G.get(r->gate1, o_gate, sum1); G.get(r->gate2, o_gate + sum1, sum2);
+    G.get(r->u1, o_u, sum1 * 4); G.get(r->v1, o_v, sum1 * 4); G.get(r->level1, o_lvl, sum1 * 4);
+    G.get(r->u2, o_u + sum1 * 4, sum2 * 4); G.get(r->v2, o_v + sum1 * 4, sum2 * 4); G.get(r->level2, o_lvl + sum1 * 4, sum2 * 4);
+    int total = 0;
+    const int* m12 = G.host<int>(o_m12);
+    for (int k = 0; k < n_pairs; k++) {
+        int found = 0;
+        for (int i = 0; i < pr[k].n1; i++) found += m12[pr[k].first1 + i] >= 0;
+        r->n_found[k] = found; total += found;
+    }
+    return total;
+}
+
 extern "C" {
 
 // ORBmatcher::SearchBySim3 (src/ORBmatcher.cpp:1124-1348) for n_pairs candidate pairs.  Entries: the features of every side-1 handle,
@@ -18,125 +153,9 @@ int ccm_search_by_sim3_table_frames(ccm_ctx* c, ccm_map_table* t, const ccm_sim3
     RoctxRange roctx_("ccm_search_by_sim3_table_frames");
     if (!c || !t || !p || !r) return CCM_E_ARG;
     const char* fn = "ccm_search_by_sim3_table_frames";
-    int rc = check_table(c, t);
-    if (rc) return rc;
-    if (p->n_pairs < 0) return ccm_fail(c, CCM_E_ARG, "%s: n_pairs = %d", fn, p->n_pairs);
-    if (p->n_pairs == 0) return 0;
-    if (!p->pairs || !p->scale_factors1 || !p->scale_factors2 || !r->n_found)
-        return ccm_fail(c, CCM_E_ARG, "%s: null %s", fn, !p->pairs ? "pairs" : !r->n_found ? "n_found" : "scale_factors1 / scale_factors2");
-    if (p->n_levels1 < 1 || p->n_levels1 > CCM_MAX_LEVELS || p->n_levels2 < 1 || p->n_levels2 > CCM_MAX_LEVELS)
-        return ccm_fail(c, CCM_E_ARG, "%s: n_levels = %d, %d outside 1..%d", fn, p->n_levels1, p->n_levels2, CCM_MAX_LEVELS);
-    if (((r->u1 || r->v1 || r->level1) && !(r->u1 && r->v1 && r->level1)) || ((r->u2 || r->v2 || r->level2) && !(r->u2 && r->v2 && r->level2)))
-        return ccm_fail(c, CCM_E_ARG, "%s: the taps u, v and level of a direction come together", fn);
-    if (p->n_pairs > 32767) return ccm_fail(c, CCM_E_CAPACITY, "%s: %d pairs; at most 32767 a call", fn, p->n_pairs);
-    return table_call(c, t, false, fn, [&]() -> int {
-        const int n_pairs = p->n_pairs, n_views = 2 * n_pairs;
-        std::vector<Sim3Pair> pr(n_pairs);
-        size_t sum1 = 0, sum2 = 0;
-        int max_n = 0, max_n1 = 0;
-        for (int k = 0; k < n_pairs; k++) {
-            const ccm_sim3_search_pair& P = p->pairs[k];
-            if (!P.kf1 || !P.kf2) return ccm_fail(c, CCM_E_ARG, "%s: null pairs[%d].%s", fn, k, !P.kf1 ? "kf1" : "kf2");
-            if ((rc = frame_named_check(c, P.kf1, CCM_E_STATE, fn, "pairs[%d].kf1", k)) || (rc = frame_named_check(c, P.kf2, CCM_E_STATE, fn, "pairs[%d].kf2", k)))
-                return rc;
-            if (P.kf1->n > 0 && (!P.matched12 || !P.matched_idx2)) return ccm_fail(c, CCM_E_ARG, "%s: null pairs[%d].matched12 / matched_idx2", fn, k);
-            pr[k] = Sim3Pair{ P.kf1->n, P.kf2->n, (int)sum1, (int)sum2 };
-            sum1 += (size_t)P.kf1->n; sum2 += (size_t)P.kf2->n;
-            max_n = std::max(max_n, std::max(P.kf1->n, P.kf2->n)); max_n1 = std::max(max_n1, P.kf1->n);
-            if (sum1 + sum2 > ((size_t)1 << 24)) return ccm_fail(c, CCM_E_CAPACITY, "%s: more than 2^24 features in one call", fn);
-        }
-        if (sum1 > 0 && !r->match12) return ccm_fail(c, CCM_E_ARG, "%s: null match12", fn);
-        const size_t E = sum1 + sum2;
-        if (E == 0 || max_n1 == 0) {                                           // no feature on side 1: nothing can match
-            for (int k = 0; k < n_pairs; k++) r->n_found[k] = 0;
-            if (E == 0) return 0;
-        }
-
-        CCM_HIP(c, hipSetDevice(c->device));
-        FrameState& S = *frame_state(c);
-        Staging& G = S.stage;
-        hipStream_t st = c->stream;
-        const bool tap_sel = r->sel1 || r->sel2, tap_gate = r->gate1 || r->gate2, taps = r->u1 || r->u2;
-        size_t off = 0;
-        const size_t o_cnt = seg(off, 16), o_m12 = seg(off, sum1 * 4), o_sel = seg(off, tap_sel ? E * 4 : 0), o_gate = seg(off, tap_gate ? E : 0);
-        const size_t o_u = seg(off, taps ? E * 4 : 0), o_v = seg(off, taps ? E * 4 : 0), o_lvl = seg(off, taps ? E * 4 : 0);
-        const size_t res_end = off;
-        const size_t o_view = seg(off, (size_t)n_views * sizeof(Sim3View)), o_grid = seg(off, (size_t)n_views * sizeof(WinGrid));
-        const size_t o_pair = seg(off, (size_t)n_pairs * sizeof(Sim3Pair)), o_mi = seg(off, sum1 * 4), o_mx = seg(off, sum1 * 4);
-        const size_t end = off;
-        if ((rc = G.reserve(c, end))) return rc;
-        size_t w = 0;                                                          // device-only work area
-        const size_t w_am2 = seg(w, sum2), w_sel = seg(w, tap_sel ? 0 : E * 4), w_qx = seg(w, E * 4), w_qy = seg(w, E * 4), w_qr = seg(w, E * 4);
-        const size_t w_minl = seg(w, E * 4), w_maxl = seg(w, E * 4), w_qview = seg(w, E * 4), w_qent = seg(w, E * 4), w_qdesc = seg(w, E * 32);
-        const size_t w_si = seg(w, E * 4), w_sd = seg(w, E * 4);
-        CCM_RESERVE(c, S.fuse, w + 64);
-        uint8_t* wk = S.fuse.as<uint8_t>();
-
-        Sim3View* hv = G.host<Sim3View>(o_view); WinGrid* hg = G.host<WinGrid>(o_grid);
-        const int* d_mi = G.dev<int>(o_mi);
-        for (int k = 0; k < n_pairs; k++) {
-            const ccm_sim3_search_pair& P = p->pairs[k];
-            for (int d = 0; d < 2; d++) {
-                const ccm_frame* src = d ? P.kf2 : P.kf1; const ccm_frame* dst = d ? P.kf1 : P.kf2;
-                const float* bounds = d ? P.bounds1 : P.bounds2;
-                Sim3View& D = hv[2 * k + d];
-                std::memcpy(D.Tsw, d ? P.T2w : P.T1w, sizeof D.Tsw); std::memcpy(D.Sts, d ? P.S12 : P.S21, sizeof D.Sts);
-                D.fx = P.fx; D.fy = P.fy; D.cx = P.cx; D.cy = P.cy;
-                D.min_x = bounds[0]; D.max_x = bounds[1]; D.min_y = bounds[2]; D.max_y = bounds[3];
-                D.n = src->n; D.n_target = dst->n; D.e0 = d ? (int)sum1 + pr[k].first2 : pr[k].first1; D.side_t = d ? 0 : 1;
-                D.mp_id = src->mp_id;
-                D.mark_i = d ? nullptr : d_mi + pr[k].first1;
-                D.mark_b = d ? wk + w_am2 + pr[k].first2 : nullptr;
-                hg[2 * k + d] = frame_win_grid(dst);
-            }
-            G.put(o_mi + (size_t)pr[k].first1 * 4, P.matched12, (size_t)pr[k].n1 * 4);
-            G.put(o_mx + (size_t)pr[k].first1 * 4, P.matched_idx2, (size_t)pr[k].n1 * 4);
-        }
-        std::memcpy(G.host<Sim3Pair>(o_pair), pr.data(), (size_t)n_pairs * sizeof(Sim3Pair));
-        if ((rc = G.upload(c, o_view, end))) return rc;
-
-        Sim3Args A{};
-        A.n_views = n_views; A.n_entries = (int)E; A.views = G.dev<Sim3View>(o_view);
-        A.log_scale[0] = p->log_scale_factor1; A.log_scale[1] = p->log_scale_factor2; A.n_levels[0] = p->n_levels1; A.n_levels[1] = p->n_levels2;
-        fill_levels(A.scale[0], p->scale_factors1, p->n_levels1); fill_levels(A.scale[1], p->scale_factors2, p->n_levels2);
-        A.th = p->th;
-        A.sel = tap_sel ? G.dev<int>(o_sel) : (int*)(wk + w_sel);
-        A.gate = tap_gate ? G.dev<uint8_t>(o_gate) : nullptr;
-        A.u = taps ? G.dev<float>(o_u) : nullptr; A.v = taps ? G.dev<float>(o_v) : nullptr; A.level = taps ? G.dev<int>(o_lvl) : nullptr;
-        A.cnt = G.dev<int>(o_cnt); A.qx = (float*)(wk + w_qx); A.qy = (float*)(wk + w_qy); A.qr = (float*)(wk + w_qr);
-        A.minl = (int*)(wk + w_minl); A.maxl = (int*)(wk + w_maxl); A.qview = (int*)(wk + w_qview); A.qent = (int*)(wk + w_qent); A.qdesc = wk + w_qdesc;
-        const Sim3Pair* d_pair = G.dev<Sim3Pair>(o_pair);
-        CCM_HIP(c, hipMemsetAsync(A.cnt, 0, 16, st));
-        if (sum2) CCM_HIP(c, hipMemsetAsync(wk + w_am2, 0, sum2, st));
-        sim3_launch_marks(st, n_pairs, max_n1, d_pair, d_mi, G.dev<int>(o_mx), wk + w_am2);
-        sim3_launch_project(st, A, t->T, max_n);
-        CCM_HIP(c, hipGetLastError());
-        if ((rc = G.download(c, 0, 16)) || (rc = G.wait(c))) return rc;        // the number of queries: the first synchronisation
-        int nq = 0;
-        G.get(&nq, o_cnt, 4);
-        if (nq < 0 || (size_t)nq > E) return ccm_fail(c, CCM_E_DEVICE, "%s: %d queries of %zu features", fn, nq, E);
-        if (nq > 0) {
-            match_launch_window_select_batch(st, G.dev<WinGrid>(o_grid), A.qview, nq, A.qx, A.qy, A.qr, A.minl, A.maxl, A.qdesc, nullptr, 100,   // TH_HIGH
-                                             (int*)(wk + w_si), (int*)(wk + w_sd));
-            fuse_launch_scatter(st, nq, (int)E, A.qent, (const int*)(wk + w_si), (const int*)(wk + w_sd), A.sel, nullptr);
-        }
-        sim3_launch_agree(st, n_pairs, max_n1, d_pair, A.sel, (int)sum1, G.dev<int>(o_m12));
-        CCM_HIP(c, hipGetLastError());
-        if ((rc = G.download(c, 0, res_end)) || (rc = G.wait(c))) return rc;   // the second
-        G.get(r->match12, o_m12, sum1 * 4);
-        G.get(r->sel1, o_sel, sum1 * 4); G.get(r->sel2, o_sel + sum1 * 4, sum2 * 4);
-        G.get(r->gate1, o_gate, sum1); G.get(r->gate2, o_gate + sum1, sum2);
-        G.get(r->u1, o_u, sum1 * 4); G.get(r->v1, o_v, sum1 * 4); G.get(r->level1, o_lvl, sum1 * 4);
-        G.get(r->u2, o_u + sum1 * 4, sum2 * 4); G.get(r->v2, o_v + sum1 * 4, sum2 * 4); G.get(r->level2, o_lvl + sum1 * 4, sum2 * 4);
-        int total = 0;
-        const int* m12 = G.host<int>(o_m12);
-        for (int k = 0; k < n_pairs; k++) {
-            int found = 0;
-            for (int i = 0; i < pr[k].n1; i++) found += m12[pr[k].first1 + i] >= 0;
-            r->n_found[k] = found; total += found;
-        }
-        return total;
-    });
+    const int rc = sim3_search_check(c, t, p, r, fn);
+    if (rc || p->n_pairs == 0) return rc;
+    return table_call(c, t, false, fn, [&]() -> int { return sim3_search_run(c, t, p, r, fn, nullptr); });
 }
 
 // ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cpp:308-446) for n_kf views of one slot list.

@@ -1,10 +1,8 @@
 // sim3_host.cpp -- C ABI of the batched Optimizer::OptimizeSim3 (cslam/src/Optimizer.cpp:867-1062); the whole
 // schedule of every problem runs in one kernel launch (sim3_kernels.hip).
-#include "ccm_internal.h"
-#include "sim3_types.h"
+#include "sim3_internal.h"
 #include <algorithm>
 
-struct Sim3State { DevBuf sim3, fix, K1, K2, first, P1, P2, o1, o2, i1, i2, th2, err, inl, nin; };
 void sim3_state_free(Sim3State* s) { delete s; }
 
 extern "C" int ccm_optimize_sim3(ccm_ctx* c, ccm_sim3_problem* pb)

@@ -1,13 +1,10 @@
 // sim3_ransac_host.cpp -- C ABI of the batched Sim3Solver (src/Sim3Solver.cpp): create evaluates every hypothesis of every solver in
 // one kernel launch (sim3_ransac_kernels.hip); iterate / find replay the ordered bookkeeping of Sim3Solver::iterate (:120-191) over
 // the stored per-hypothesis counts on the host.
-#include "staging.h"
-#include "sim3_ransac_types.h"
+#include "sim3_internal.h"
 #include <cmath>
 #include <memory>
 
-// The staging area (staging.h), laid out [inputs | outputs]: one upload, one launch, one download per batch.
-struct Sim3RansacState { Staging stage{ false }; };
 void sim3_ransac_state_free(Sim3RansacState* s)
 {
     if (!s) return;
@@ -45,94 +42,122 @@ extern "C" int ccm_sim3_ransac_iterations(int n, double probability, int min_inl
     return std::max(1, std::min(it, max_iterations));                       // :115
 }
 
+int sim3_solver_create_body(ccm_ctx* c, const ccm_sim3_ransac_problem* pb, const Sim3SolverFrames* fr, ccm_sim3_solver** out)
+{
+    if (!pb || !out || pb->n_solvers < 0) return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem");
+    const int F = pb->n_solvers;
+    std::unique_ptr<ccm_sim3_solver> S(new ccm_sim3_solver());
+    S->min_inliers = pb->min_inliers;
+    if (F == 0) { *out = S.release(); return CCM_OK; }
+    if (!pb->first || !pb->n1 || !pb->fix_scale || !pb->K1 || !pb->K2) return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem: null per-solver array");
+    if (pb->max_iterations < 1 || pb->min_inliers < 0) return ccm_fail(c, CCM_E_ARG, "bad RANSAC parameters: max_iterations %d, min_inliers %d", pb->max_iterations, pb->min_inliers);
+    if (pb->first[0] != 0) return ccm_fail(c, CCM_E_ARG, "first[0] must be 0");
+    for (int f = 0; f < F; f++) if (pb->first[f + 1] < pb->first[f]) return ccm_fail(c, CCM_E_ARG, "first[] must be non-decreasing");
+    const size_t T = (size_t)pb->first[F];
+    if (T > 0 && (!pb->indices1 || (fr ? !fr->feature2 : (!pb->X1 || !pb->X2 || !pb->max_err1 || !pb->max_err2))))
+        return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem: null correspondence array");
+
+    // ---- per-solver geometry of the batch, and the checks that keep every index the kernel and iterate() form in range
+    S->k.resize(F);
+    size_t H = 0, W = 0, n_blocks = 0;
+    for (int f = 0; f < F; f++) {
+        S3rHost& k = S->k[f];
+        k.first = (size_t)pb->first[f]; k.n = pb->first[f + 1] - pb->first[f]; k.n1 = pb->n1[f];
+        if (k.n1 < 0) return ccm_fail(c, CCM_E_ARG, "solver %d: n1 = %d", f, k.n1);
+        for (int i = 0; i < k.n; i++) {
+            const int32_t i1 = pb->indices1[k.first + i];
+            if (i1 < 0 || i1 >= k.n1) return ccm_fail(c, CCM_E_ARG, "solver %d: indices1[%d] = %d outside [0, %d)", f, i, i1, k.n1);
+        }
+        k.max_its = ccm_sim3_ransac_iterations(k.n, pb->probability, pb->min_inliers, pb->max_iterations);
+        k.best_inliers = pb->best_inliers ? pb->best_inliers[f] : 0;
+        k.n_hyp = (k.n >= 3 && k.n >= pb->min_inliers) ? k.max_its : 0;
+        k.words = (k.n + 63) / 64;
+        k.hyp_first = (int)H; k.mask_first = W;
+        H += (size_t)k.n_hyp; W += (size_t)k.n_hyp * k.words;
+        n_blocks += ((size_t)k.n_hyp + S3R_HPB - 1) / S3R_HPB;
+        if (H > (size_t)INT32_MAX / 16) return ccm_fail(c, CCM_E_ARG, "too many hypotheses in one batch");
+    }
+    if (H > 0 && !pb->draws) return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem: null draws");
+    for (int f = 0; f < F; f++) {
+        const S3rHost& k = S->k[f];
+        const int32_t* d = pb->draws + (size_t)f * pb->max_iterations * 3;
+        for (int h = 0; h < k.n_hyp; h++)
+            for (int i = 0; i < 3; i++)
+                if (d[3 * h + i] < 0 || d[3 * h + i] > k.n - 1 - i)
+                    return ccm_fail(c, CCM_E_ARG, "solver %d, hypothesis %d: draw %d = %d outside [0, %d]", f, h, i, d[3 * h + i], k.n - 1 - i);
+    }
+    S->indices1.assign(pb->indices1, pb->indices1 + T);
+    if (H == 0) { *out = S.release(); return CCM_OK; }                  // nothing to evaluate: every solver reports bNoMore
+
+    // ---- staging: [solvers | blocks | draws | X1 | X2 | bounds] up, [status | count | sample | rts | mask] down.  With frames
+    // [pairs | feature1 | feature2 | level tables] go up in the place of X1 | X2 | bounds, which k_sim3_solver_gather fills on the device.
+    size_t off = 0;
+    const size_t o_solvers = seg(off, (size_t)F * sizeof(S3rSolver)), o_blocks = seg(off, n_blocks * sizeof(S3rBlock)), o_draws = seg(off, H * 12);
+    const size_t o_pairs = seg(off, fr ? (size_t)F * sizeof(Sim3FramesPair) : 0), o_f1 = seg(off, fr ? T * 4 : 0), o_f2 = seg(off, fr ? T * 4 : 0);
+    const size_t o_t1 = seg(off, fr ? CCM_MAX_LEVELS * 4 : 0), o_t2 = seg(off, fr ? CCM_MAX_LEVELS * 4 : 0);
+    const size_t up_end = off;                                          // with frames: the end of the upload
+    const size_t o_x1 = seg(off, T * 12), o_x2 = seg(off, T * 12), o_m1 = seg(off, T * 4), o_m2 = seg(off, T * 4);
+    const size_t in_end = off;
+    const size_t o_status = seg(off, 16);
+    const size_t o_count = seg(off, H * 4), o_sample = seg(off, H * 12), o_rts = seg(off, H * 52), o_mask = seg(off, W * 8);
+    const size_t end = off;
+    CCM_HIP(c, hipSetDevice(c->device));
+    if (!c->sim3_ransac) c->sim3_ransac = new Sim3RansacState();
+    Staging& G = c->sim3_ransac->stage;
+    int rc;
+    if ((rc = G.reserve(c, end))) return rc;
+    S3rSolver* hs = G.host<S3rSolver>(o_solvers);
+    S3rBlock* hb = G.host<S3rBlock>(o_blocks);
+    size_t nb = 0;
+    int max_n = 0;
+    for (int f = 0; f < F; f++) {
+        const S3rHost& k = S->k[f];
+        S3rSolver& s = hs[f];
+        s.first = (int32_t)k.first; s.n = k.n; s.fix_scale = pb->fix_scale[f]; s.hyp_first = k.hyp_first; s.n_hyp = k.n_hyp;
+        s.words = k.words; s.mask_first = (int64_t)k.mask_first;
+        std::memcpy(s.K1, pb->K1 + 4 * f, 16); std::memcpy(s.K2, pb->K2 + 4 * f, 16);
+        for (int h0 = 0; h0 < k.n_hyp; h0 += S3R_HPB) hb[nb++] = S3rBlock{ f, h0, std::min(S3R_HPB, k.n_hyp - h0), 0 };
+        G.put(o_draws + (size_t)k.hyp_first * 12, pb->draws + (size_t)f * pb->max_iterations * 3, (size_t)k.n_hyp * 12);
+        max_n = std::max(max_n, k.n);
+    }
+    const S3rDev D{ G.dev<S3rSolver>(o_solvers), G.dev<S3rBlock>(o_blocks), G.dev<float>(o_x1), G.dev<float>(o_x2), G.dev<float>(o_m1),
+                    G.dev<float>(o_m2), G.dev<int32_t>(o_draws), G.dev<int32_t>(o_count), G.dev<int32_t>(o_sample), G.dev<float>(o_rts),
+                    G.dev<unsigned long long>(o_mask) };
+    if (fr) {
+        G.put(o_pairs, fr->pairs, (size_t)F * sizeof(Sim3FramesPair));
+        G.put(o_f1, fr->feature1, T * 4); G.put(o_f2, fr->feature2, T * 4);
+        G.put(o_t1, fr->max_err_level1, (size_t)fr->n_levels1 * 4); G.put(o_t2, fr->max_err_level2, (size_t)fr->n_levels2 * 4);
+        if ((rc = G.upload(c, 0, up_end))) return rc;
+        CCM_HIP(c, hipMemsetAsync(G.dev<int32_t>(o_status), 0, 16, c->stream));
+        sim3_solver_gather_launch(c->stream, Sim3SolverGather{ G.dev<Sim3FramesPair>(o_pairs), D.solvers, G.dev<int32_t>(o_f1), G.dev<int32_t>(o_f2),
+                                                               fr->n_levels1, fr->n_levels2, G.dev<float>(o_t1), G.dev<float>(o_t2),
+                                                               G.dev<float>(o_x1), G.dev<float>(o_x2), G.dev<float>(o_m1), G.dev<float>(o_m2),
+                                                               G.dev<int32_t>(o_status) }, fr->T, F, max_n);
+        CCM_HIP(c, hipGetLastError());
+    } else {
+        G.put(o_x1, pb->X1, T * 12); G.put(o_x2, pb->X2, T * 12);
+        G.put(o_m1, pb->max_err1, T * 4); G.put(o_m2, pb->max_err2, T * 4);
+        if ((rc = G.upload(c, 0, in_end))) return rc;
+    }
+    sim3_ransac_launch(c->stream, D, (int)n_blocks);
+    CCM_HIP(c, hipGetLastError());
+    if ((rc = G.download(c, fr ? o_status : o_count, end)) || (rc = G.wait(c))) return rc;
+    if (fr && *G.host<int32_t>(o_status))
+        return ccm_fail(c, CCM_E_ARG, "a correspondence names a feature outside its handle, a slot that is not LIVE or an octave outside [0, %d) / [0, %d)",
+                        fr->n_levels1, fr->n_levels2);
+    const int32_t* rn = G.host<int32_t>(o_count); const int32_t* rs = G.host<int32_t>(o_sample);
+    const float* rr = G.host<float>(o_rts); const uint64_t* rm = G.host<uint64_t>(o_mask);
+    S->count.assign(rn, rn + H); S->sample.assign(rs, rs + 3 * H); S->rts.assign(rr, rr + 13 * H); S->mask.assign(rm, rm + W);
+    *out = S.release();
+    return CCM_OK;
+}
+
 extern "C" int ccm_sim3_solver_create(ccm_ctx* c, const ccm_sim3_ransac_problem* pb, ccm_sim3_solver** out)
 {
     RoctxRange roctx_("ccm_sim3_solver_create");
     return ccm_guard(c, "ccm_sim3_solver_create", [&]() -> int {
         if (!c) return CCM_E_ARG;
-        if (!pb || !out || pb->n_solvers < 0) return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem");
-        const int F = pb->n_solvers;
-        std::unique_ptr<ccm_sim3_solver> S(new ccm_sim3_solver());
-        S->min_inliers = pb->min_inliers;
-        if (F == 0) { *out = S.release(); return CCM_OK; }
-        if (!pb->first || !pb->n1 || !pb->fix_scale || !pb->K1 || !pb->K2) return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem: null per-solver array");
-        if (pb->max_iterations < 1 || pb->min_inliers < 0) return ccm_fail(c, CCM_E_ARG, "bad RANSAC parameters: max_iterations %d, min_inliers %d", pb->max_iterations, pb->min_inliers);
-        if (pb->first[0] != 0) return ccm_fail(c, CCM_E_ARG, "first[0] must be 0");
-        for (int f = 0; f < F; f++) if (pb->first[f + 1] < pb->first[f]) return ccm_fail(c, CCM_E_ARG, "first[] must be non-decreasing");
-        const size_t T = (size_t)pb->first[F];
-        if (T > 0 && (!pb->X1 || !pb->X2 || !pb->max_err1 || !pb->max_err2 || !pb->indices1))
-            return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem: null correspondence array");
-
-        // ---- per-solver geometry of the batch, and the checks that keep every index the kernel and iterate() form in range
-        S->k.resize(F);
-        size_t H = 0, W = 0, n_blocks = 0;
-        for (int f = 0; f < F; f++) {
-            S3rHost& k = S->k[f];
-            k.first = (size_t)pb->first[f]; k.n = pb->first[f + 1] - pb->first[f]; k.n1 = pb->n1[f];
-            if (k.n1 < 0) return ccm_fail(c, CCM_E_ARG, "solver %d: n1 = %d", f, k.n1);
-            for (int i = 0; i < k.n; i++) {
-                const int32_t i1 = pb->indices1[k.first + i];
-                if (i1 < 0 || i1 >= k.n1) return ccm_fail(c, CCM_E_ARG, "solver %d: indices1[%d] = %d outside [0, %d)", f, i, i1, k.n1);
-            }
-            k.max_its = ccm_sim3_ransac_iterations(k.n, pb->probability, pb->min_inliers, pb->max_iterations);
-            k.best_inliers = pb->best_inliers ? pb->best_inliers[f] : 0;
-            k.n_hyp = (k.n >= 3 && k.n >= pb->min_inliers) ? k.max_its : 0;
-            k.words = (k.n + 63) / 64;
-            k.hyp_first = (int)H; k.mask_first = W;
-            H += (size_t)k.n_hyp; W += (size_t)k.n_hyp * k.words;
-            n_blocks += ((size_t)k.n_hyp + S3R_HPB - 1) / S3R_HPB;
-            if (H > (size_t)INT32_MAX / 16) return ccm_fail(c, CCM_E_ARG, "too many hypotheses in one batch");
-        }
-        if (H > 0 && !pb->draws) return ccm_fail(c, CCM_E_ARG, "bad Sim3 RANSAC problem: null draws");
-        for (int f = 0; f < F; f++) {
-            const S3rHost& k = S->k[f];
-            const int32_t* d = pb->draws + (size_t)f * pb->max_iterations * 3;
-            for (int h = 0; h < k.n_hyp; h++)
-                for (int i = 0; i < 3; i++)
-                    if (d[3 * h + i] < 0 || d[3 * h + i] > k.n - 1 - i)
-                        return ccm_fail(c, CCM_E_ARG, "solver %d, hypothesis %d: draw %d = %d outside [0, %d]", f, h, i, d[3 * h + i], k.n - 1 - i);
-        }
-        S->indices1.assign(pb->indices1, pb->indices1 + T);
-        if (H == 0) { *out = S.release(); return CCM_OK; }                  // nothing to evaluate: every solver reports bNoMore
-
-        // ---- staging: [solvers | blocks | X1 | X2 | bounds | draws] up, [count | sample | rts | mask] down
-        size_t off = 0;
-        const size_t o_solvers = seg(off, (size_t)F * sizeof(S3rSolver)), o_blocks = seg(off, n_blocks * sizeof(S3rBlock));
-        const size_t o_x1 = seg(off, T * 12), o_x2 = seg(off, T * 12), o_m1 = seg(off, T * 4), o_m2 = seg(off, T * 4), o_draws = seg(off, H * 12);
-        const size_t in_end = off;
-        const size_t o_count = seg(off, H * 4), o_sample = seg(off, H * 12), o_rts = seg(off, H * 52), o_mask = seg(off, W * 8);
-        const size_t end = off;
-        CCM_HIP(c, hipSetDevice(c->device));
-        if (!c->sim3_ransac) c->sim3_ransac = new Sim3RansacState();
-        Staging& G = c->sim3_ransac->stage;
-        int rc;
-        if ((rc = G.reserve(c, end))) return rc;
-        S3rSolver* hs = G.host<S3rSolver>(o_solvers);
-        S3rBlock* hb = G.host<S3rBlock>(o_blocks);
-        size_t nb = 0;
-        for (int f = 0; f < F; f++) {
-            const S3rHost& k = S->k[f];
-            S3rSolver& s = hs[f];
-            s.first = (int32_t)k.first; s.n = k.n; s.fix_scale = pb->fix_scale[f]; s.hyp_first = k.hyp_first; s.n_hyp = k.n_hyp;
-            s.words = k.words; s.mask_first = (int64_t)k.mask_first;
-            std::memcpy(s.K1, pb->K1 + 4 * f, 16); std::memcpy(s.K2, pb->K2 + 4 * f, 16);
-            for (int h0 = 0; h0 < k.n_hyp; h0 += S3R_HPB) hb[nb++] = S3rBlock{ f, h0, std::min(S3R_HPB, k.n_hyp - h0), 0 };
-            G.put(o_draws + (size_t)k.hyp_first * 12, pb->draws + (size_t)f * pb->max_iterations * 3, (size_t)k.n_hyp * 12);
-        }
-        G.put(o_x1, pb->X1, T * 12); G.put(o_x2, pb->X2, T * 12);
-        G.put(o_m1, pb->max_err1, T * 4); G.put(o_m2, pb->max_err2, T * 4);
-        if ((rc = G.upload(c, 0, in_end))) return rc;
-        const S3rDev D{ G.dev<S3rSolver>(o_solvers), G.dev<S3rBlock>(o_blocks), G.dev<float>(o_x1), G.dev<float>(o_x2), G.dev<float>(o_m1),
-                        G.dev<float>(o_m2), G.dev<int32_t>(o_draws), G.dev<int32_t>(o_count), G.dev<int32_t>(o_sample), G.dev<float>(o_rts),
-                        G.dev<unsigned long long>(o_mask) };
-        sim3_ransac_launch(c->stream, D, (int)n_blocks);
-        CCM_HIP(c, hipGetLastError());
-        if ((rc = G.download(c, in_end, end)) || (rc = G.wait(c))) return rc;
-        const int32_t* rn = G.host<int32_t>(o_count); const int32_t* rs = G.host<int32_t>(o_sample);
-        const float* rr = G.host<float>(o_rts); const uint64_t* rm = G.host<uint64_t>(o_mask);
-        S->count.assign(rn, rn + H); S->sample.assign(rs, rs + 3 * H); S->rts.assign(rr, rr + 13 * H); S->mask.assign(rm, rm + W);
-        *out = S.release();
-        return CCM_OK;
+        return sim3_solver_create_body(c, pb, nullptr, out);
     });
 }
 

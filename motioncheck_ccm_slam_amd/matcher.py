@@ -413,17 +413,7 @@ def _search_by_sim3_table_frames(self, table, pairs, scale_factors1, scale_facto
     keep = []
     n1 = [p["kf1"].n for p in pairs]; n2 = [p["kf2"].n for p in pairs]
     for k, p in enumerate(pairs):
-        R = recs[k]
-        R.kf1 = p["kf1"].handle; R.kf2 = p["kf2"].handle
-        for name in ("T1w", "T2w", "S21", "S12"):
-            getattr(R, name)[:] = [float(x) for x in a(p[name], "f4").reshape(12)]
-        R.fx, R.fy, R.cx, R.cy = [float(x) for x in p["intr"]]
-        R.bounds1[:] = [float(x) for x in p["bounds1"]]; R.bounds2[:] = [float(x) for x in p["bounds2"]]
-        m12 = a(p.get("matched12", np.full(n1[k], -1)), "i4").reshape(-1); mi2 = a(p.get("matched_idx2", np.full(n1[k], -1)), "i4").reshape(-1)
-        if len(m12) != n1[k] or len(mi2) != n1[k]:
-            raise ValueError("matched12 / matched_idx2 need one entry per feature of kf1")
-        keep += [m12, mi2]
-        R.matched12 = _lib.ptr(m12) if n1[k] else None; R.matched_idx2 = _lib.ptr(mi2) if n1[k] else None
+        _fill_search_pair(recs[k], p, n1[k], keep)
     prob = _lib.Sim3SearchProblem(K, recs, float(th), float(l1), len(sf1), _lib.ptr(sf1), float(l2), len(sf2), _lib.ptr(sf2))
     s1, s2 = max(sum(n1), 1), max(sum(n2), 1)
     out = dict(match12=np.full(s1, -1, "i4"), n_found=np.zeros(max(K, 1), "i4"))
@@ -489,7 +479,73 @@ def _search_by_projection_table_frames(self, table, frames, Tcw, Ow, intr, bound
     return ret
 
 
+def _fill_search_pair(R, p, n1, keep):
+    a = np.ascontiguousarray
+    R.kf1 = p["kf1"].handle; R.kf2 = p["kf2"].handle
+    for name in ("T1w", "T2w", "S21", "S12"):
+        getattr(R, name)[:] = [float(x) for x in a(p[name], "f4").reshape(12)]
+    R.fx, R.fy, R.cx, R.cy = [float(x) for x in p["intr"]]
+    R.bounds1[:] = [float(x) for x in p["bounds1"]]; R.bounds2[:] = [float(x) for x in p["bounds2"]]
+    m12 = a(p.get("matched12", np.full(n1, -1)), "i4").reshape(-1); mi2 = a(p.get("matched_idx2", np.full(n1, -1)), "i4").reshape(-1)
+    if len(m12) != n1 or len(mi2) != n1:
+        raise ValueError("matched12 / matched_idx2 need one entry per feature of kf1")
+    keep += [m12, mi2]
+    R.matched12 = _lib.ptr(m12) if n1 else None; R.matched_idx2 = _lib.ptr(mi2) if n1 else None
+
+
+def _compute_sim3_table_frames(self, table, pairs, scale_factors1, inv_level_sigma2_1, scale_factors2=None, inv_level_sigma2_2=None, th: float = 7.5,
+                               log_scale_factor1=None, log_scale_factor2=None, taps: bool = False):
+    """SearchBySim3 and OptimizeSim3 (src/LoopFinder.cpp:313-330) for a batch of candidate pairs in one call
+    (ccm_compute_sim3_table_frames): the matches stay on the device, the correspondences of src/Optimizer.cpp:920-957 are listed there
+    and optimised.  pairs: the dicts of SearchBySim3TableFrames -- matched12 / matched_idx2 are the solver's inliers -- plus intr2 (fx,
+    fy, cx, cy of kf2; default intr), sim3 ([8] gScm: qx, qy, qz, qw, tx, ty, tz, s), fix_scale and th2.  Returns a dict: match12,
+    pruned (lists of [N1] arrays), n_found, n_correspondences, n_inliers (lists), sim3 [K][8], total, and with taps the search's taps,
+    corr (a list of [n][2] arrays of (i1, i2)) and inlier (a list of [n] arrays)."""
+    a = np.ascontiguousarray
+    K = len(pairs)
+    sf1 = a(scale_factors1, "f4"); sf2 = sf1 if scale_factors2 is None else a(scale_factors2, "f4")
+    is1 = a(inv_level_sigma2_1, "f4"); is2 = is1 if inv_level_sigma2_2 is None else a(inv_level_sigma2_2, "f4")
+    if len(is1) != len(sf1) or len(is2) != len(sf2):
+        raise ValueError("one inv_level_sigma2 per scale factor")
+    l1 = _log_sf(sf1) if log_scale_factor1 is None else log_scale_factor1
+    l2 = (_log_sf(sf2) if scale_factors2 is not None else l1) if log_scale_factor2 is None else log_scale_factor2
+    recs = (_lib.ComputeSim3Pair * max(K, 1))()
+    keep = []
+    n1 = [p["kf1"].n for p in pairs]; n2 = [p["kf2"].n for p in pairs]
+    for k, p in enumerate(pairs):
+        _fill_search_pair(recs[k].search, p, n1[k], keep)
+        recs[k].K2[:] = [float(x) for x in p.get("intr2", p["intr"])]
+        recs[k].sim3[:] = [float(x) for x in a(p["sim3"], "f8").reshape(8)]
+        recs[k].fix_scale = int(p.get("fix_scale", 0)); recs[k].th2 = float(p.get("th2", 10.0))
+    prob = _lib.ComputeSim3Problem(K, recs, float(th), float(l1), len(sf1), _lib.ptr(sf1), _lib.ptr(is1), float(l2), len(sf2), _lib.ptr(sf2), _lib.ptr(is2))
+    s1, s2 = max(sum(n1), 1), max(sum(n2), 1)
+    out = dict(match12=np.full(s1, -1, "i4"), n_found=np.zeros(max(K, 1), "i4"), pruned=np.zeros(s1, np.uint8), n_correspondences=np.zeros(max(K, 1), "i4"),
+               n_inliers=np.zeros(max(K, 1), "i4"), sim3=np.zeros((max(K, 1), 8), "f8"))
+    if taps:
+        for d, s in (("1", s1), ("2", s2)):
+            out.update({"gate" + d: np.zeros(s, np.uint8), "u" + d: np.zeros(s, "f4"), "v" + d: np.zeros(s, "f4"), "level" + d: np.zeros(s, "i4"),
+                        "sel" + d: np.full(s, -1, "i4")})
+        out.update(corr=np.full((s1, 2), -1, "i4"), inlier=np.zeros(s1, np.uint8))
+    g = lambda k: _lib.ptr(out[k]) if k in out else None  # noqa: E731
+    search = _lib.Sim3SearchResult(*[g(k) for k in ("match12", "n_found", "gate1", "u1", "v1", "level1", "sel1", "gate2", "u2", "v2", "level2", "sel2")])
+    res = _lib.ComputeSim3Result(search, g("pruned"), g("n_correspondences"), g("n_inliers"), g("sim3"), g("corr"), g("inlier"))
+    total = self.ctx.check(self.lib.ccm_compute_sim3_table_frames(self.ctx.handle, C.c_void_p(table.handle), C.byref(prob), C.byref(res)))
+    f1 = np.concatenate([[0], np.cumsum(n1)]).astype(int); f2 = np.concatenate([[0], np.cumsum(n2)]).astype(int)
+    nc = out["n_correspondences"][:K]; fc = np.concatenate([[0], np.cumsum(nc)]).astype(int)
+    ret = dict(total=int(total), sim3=out["sim3"][:K].copy())
+    for k, v in out.items():
+        if k in ("n_found", "n_correspondences", "n_inliers"):
+            ret[k] = [int(x) for x in v[:K]]
+        elif k in ("corr", "inlier"):
+            ret[k] = [v[fc[i]:fc[i + 1]].copy() for i in range(K)]
+        elif k != "sim3":
+            f = f2 if k.endswith("2") and k != "match12" else f1
+            ret[k] = [v[f[i]:f[i + 1]].copy() for i in range(K)]
+    return ret
+
+
 ORBmatcher.SearchBySim3TableFrames = _search_by_sim3_table_frames
+ORBmatcher.ComputeSim3TableFrames = _compute_sim3_table_frames
 ORBmatcher.SearchByProjectionTableFrames = _search_by_projection_table_frames
 
 

@@ -220,6 +220,29 @@ class Optimizer:
         ctx.check(lib.ccm_optimize_sim3(ctx.handle, C.byref(pb)))
         return s3, inl[:len(A[4])], nin
 
+    @staticmethod
+    def OptimizeSim3TableFrames(table, pairs, sim3, fix_scale, first, feature1, feature2, inv_level_sigma2_1, inv_level_sigma2_2=None, th2=10.0, ctx=None):
+        """OptimizeSim3 for pairs of DeviceFrame handles whose correspondences are (feature1, feature2) lists and whose map points are
+        the slots the handles hold there in `table` (ccm_optimize_sim3_table_frames).  pairs: dicts kf1, kf2, T1w, T2w, K1, K2 as for
+        Sim3Solver.from_frames.  Returns (sim3, inlier flags per correspondence, nIn per problem), the bits OptimizeSim3 returns for
+        the arrays a caller forms from the same pairs."""
+        from .sim3solver import fill_frames_pair
+        ctx = ctx or _lib.default_context(0)
+        lib = _lib.load()
+        a = np.ascontiguousarray
+        s3 = a(sim3, "f8").copy().reshape(-1, 8); n = len(s3)
+        fs = a(np.broadcast_to(fix_scale, n), "i4"); t2 = a(np.broadcast_to(th2, n), "f4"); fr = a(first, "i4")
+        f1 = a(feature1, "i4").reshape(-1); f2 = a(feature2, "i4").reshape(-1)
+        is1 = a(inv_level_sigma2_1, "f4").reshape(-1); is2 = is1 if inv_level_sigma2_2 is None else a(inv_level_sigma2_2, "f4").reshape(-1)
+        recs = (_lib.Sim3FramesPair * max(n, 1))()
+        for k, q in enumerate(pairs):
+            fill_frames_pair(recs[k], q)
+        inl = np.zeros(max(len(f1), 1), np.uint8); nin = np.zeros(max(n, 1), "i4")
+        p = _lib.ptr
+        pb = _lib.Sim3OptFramesProblem(n, recs, p(fr), p(fs), p(t2), p(f1), p(f2), len(is1), p(is1), len(is2), p(is2))
+        res = _lib.Sim3OptFramesResult(p(s3) if n else None, p(inl), p(nin))
+        ctx.check(lib.ccm_optimize_sim3_table_frames(ctx.handle, C.c_void_p(table.handle), C.byref(pb), C.byref(res)))
+        return s3, inl[:len(f1)], nin[:n]
 
     @staticmethod
     def OptimizeEssentialGraph(sim3, fixed, edge_i, edge_j, measurement, bFixScale: bool = False, iterations: int = 20, ctx=None):

@@ -25,6 +25,19 @@ def make_draws(rng, n_correspondences, max_iterations: int) -> np.ndarray:
     return rng.integers(0, np.broadcast_to(hi, (len(n), int(max_iterations), 3))).astype("i4")
 
 
+def level_max_err(level_sigma2) -> np.ndarray:
+    """mvnMaxError per pyramid level: 9.210 * mvLevelSigma2[level] (src/Sim3Solver.cpp:67) pushed into a std::vector<size_t>
+    (include/cslam/Sim3Solver.h:74-75), which drops the fraction, and read back as a float."""
+    return np.trunc(9.210 * np.asarray(level_sigma2, "f4").astype("f8")).astype("f4")
+
+
+def fill_frames_pair(rec, q):
+    """A ccm_sim3_frames_pair from a dict kf1, kf2, T1w, T2w, K1, K2."""
+    rec.kf1 = q["kf1"].handle; rec.kf2 = q["kf2"].handle
+    for name, n in (("T1w", 12), ("T2w", 12), ("K1", 4), ("K2", 4)):
+        getattr(rec, name)[:] = [float(x) for x in np.ascontiguousarray(q[name], "f4").reshape(n)]
+
+
 class Sim3Solver:
     def __init__(self, first, n1, X1, X2, max_err1, max_err2, indices1, K1, K2, fix_scale, draws, ctx=None):
         """The constructor data of n solvers (:5-92), flattened: correspondences of solver k are rows first[k] .. first[k+1]-1 of
@@ -47,6 +60,51 @@ class Sim3Solver:
         self._prev = [None] * self.n                    # and the estimate that belongs to it
         self.SetRansacParameters()                      # :91
 
+    @classmethod
+    def from_frames(cls, table, pairs, first, feature1, feature2, max_err_level1, max_err_level2=None, fix_scale=False, draws=None, ctx=None):
+        """The same solvers with the constructor's loop on the device (ccm_sim3_solver_create_frames): correspondence e of solver k
+        is (feature1[e] of pairs[k]['kf1'], feature2[e] of pairs[k]['kf2']), its two map points the slots the handles hold there in
+        `table`.  pairs: dicts kf1, kf2 (DeviceFrame handles), T1w, T2w ([12] or [3][4]), K1, K2 (fx, fy, cx, cy).  max_err_level:
+        per pyramid level, (float)(size_t)(9.210 * mvLevelSigma2[level]) -- level_max_err() -- for either side."""
+        a = np.ascontiguousarray
+        self = cls.__new__(cls)
+        self.ctx = ctx or _lib.default_context(0)
+        self.lib = _lib.load()
+        self.first = a(first, "i4"); self.n = len(self.first) - 1
+        self.table = table; self.pairs = list(pairs)
+        if len(self.pairs) != self.n:
+            raise ValueError("one pair per solver")
+        self.n1 = a([p["kf1"].n for p in self.pairs], "i4").reshape(-1)
+        self.feature1 = a(feature1, "i4").reshape(-1); self.feature2 = a(feature2, "i4").reshape(-1)
+        self.indices1 = self.feature1
+        self.max_err_level1 = a(max_err_level1, "f4").reshape(-1)
+        self.max_err_level2 = self.max_err_level1 if max_err_level2 is None else a(max_err_level2, "f4").reshape(-1)
+        self.fix_scale = a(np.broadcast_to(np.asarray(fix_scale, "i4"), (self.n,)), "i4")
+        self.draws = np.asarray(draws, "i4").reshape(self.n, -1, 3) if self.n else np.zeros((0, 0, 3), "i4")
+        self._handle = None
+        self._best0 = np.zeros(self.n, "i4"); self._prev = [None] * self.n
+        self.SetRansacParameters()
+        return self
+
+    def frames_problem(self, draws, n_levels1=None, n_levels2=None):
+        """The ccm_sim3_solver_frames_problem of this batch and the objects that keep its arrays alive."""
+        recs = (_lib.Sim3FramesPair * max(self.n, 1))()
+        for k, q in enumerate(self.pairs):
+            fill_frames_pair(recs[k], q)
+        p = _lib.ptr
+        draws = np.ascontiguousarray(draws, "i4")
+        pb = _lib.Sim3SolverFramesProblem(self.n, recs, p(self.first), p(self.fix_scale), p(self.feature1), p(self.feature2),
+                                          len(self.max_err_level1) if n_levels1 is None else n_levels1, p(self.max_err_level1),
+                                          len(self.max_err_level2) if n_levels2 is None else n_levels2, p(self.max_err_level2),
+                                          self.probability, self.min_inliers, self.max_iterations, p(draws), p(self._best0))
+        return pb, (recs, draws)
+
+    def _create_frames(self, draws):
+        pb, keep = self.frames_problem(draws)
+        h = C.c_void_p()
+        self.ctx.check(self.lib.ccm_sim3_solver_create_frames(self.ctx.handle, C.c_void_p(self.table.handle), C.byref(pb), C.byref(h)))
+        self._handle = h
+
     def SetRansacParameters(self, probability: float = 0.99, minInliers: int = 6, maxIterations: int = 300):
         if self._handle is not None:
             for k in range(self.n):
@@ -63,6 +121,8 @@ class Sim3Solver:
         if self.n and self.draws.shape[1] < self.max_iterations:
             raise ValueError("draws holds %d hypotheses per solver, maxIterations is %d" % (self.draws.shape[1], self.max_iterations))
         draws = np.ascontiguousarray(self.draws[:, :self.max_iterations])
+        if getattr(self, "table", None) is not None:
+            return self._create_frames(draws)
         p = _lib.ptr
         pb = _lib.Sim3RansacProblem(self.n, p(self.first), p(self.n1), p(self.fix_scale), p(self.K1), p(self.K2), p(self.X1), p(self.X2),
                                     p(self.max_err1), p(self.max_err2), p(self.indices1), self.probability, self.min_inliers,

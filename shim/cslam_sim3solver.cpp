@@ -13,7 +13,8 @@
 // SearchByBoW(mpCurrentKF, pKF, ...) calls of the same loop (src/LoopFinder.cpp:265, src/MapMatcher.cpp:271) as one
 // ccm_search_by_bow_frames call over all candidates; ccm_shim::search_by_sim3_on_table and search_by_projection_on_table are the two
 // matchers behind the solver (SearchBySim3 for all candidates in one call, SearchByProjection(pKF, Scw, ...)) on keyframe handles and
-// the map-point table.  They take the calling thread's handle on the table (map_table_here: on LoopFinder's and MapMatcher's threads a
+// the map-point table, sim3_solvers_on_table the solver batch with its constructor's loop on the device, and
+// compute_sim3_candidates_on_table SearchBySim3 and OptimizeSim3 of one pass in one call.  They take the calling thread's handle on the table (map_table_here: on LoopFinder's and MapMatcher's threads a
 // view of the rows the tracking thread's table holds), as Fuse on the table does; without one they decline and the caller's ORBmatcher
 // call takes the array route.
 #include <cslam/Sim3Solver.h>
@@ -260,6 +261,137 @@ bool search_by_projection_on_table(const ORBmatcher::kfptr& pKF, const cv::Mat& 
         pKF->RemapMapPointMatch(pMP, existing_idx, best[i]);
     }
     nmatches = nm;
+    return true;
+}
+
+// mvnMaxError per level as the constructor leaves it (:67-68 into a std::vector<size_t>), and the two poses of a pair
+static std::vector<float> max_err_levels(const ORBmatcher::kfptr& pKF)
+{
+    std::vector<float> out(pKF->mvLevelSigma2.size());
+    for (size_t l = 0; l < out.size(); l++) out[l] = (float)(size_t)(9.210 * pKF->mvLevelSigma2[l]);
+    return out;
+}
+static void intrinsics_of(const ORBmatcher::kfptr& pKF, float K[4]) { K[0] = pKF->fx; K[1] = pKF->fy; K[2] = pKF->cx; K[3] = pKF->cy; }
+
+// Link 2 on handles.  The filter "set and not bad" (:32-59) stays here: the caller sizes its draws by N.  A correspondence is (i1,
+// GetIndexInKeyFrame(pKF2)): the kernel reads the two points at those features of the handles, which are pMP1 and pMP2 as long as
+// mObservations and mvpMapPoints agree.
+bool sim3_solvers_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<ORBmatcher::kfptr>& candidates,
+                           const std::vector<std::vector<ORBmatcher::mpptr>>& vvpMatches12, bool fix_scale, double probability, int min_inliers,
+                           int max_iterations, const std::vector<int32_t>& draws, KeyframeHandleOf handle_of, std::vector<int>& n, ccm_sim3_solver** out)
+{
+    typedef ORBmatcher::mpptr mpptr;
+    const int K = (int)candidates.size();
+    if (vvpMatches12.size() != candidates.size() || !out) return false;
+    ccm_map_table* table = map_table_here();
+    ccm_frame* h1 = table ? handle_of(pKF1) : nullptr;
+    if (!table || !h1 || K == 0) return false;
+    const std::vector<mpptr> mps1 = pKF1->GetMapPointMatches();
+    std::vector<ccm_sim3_frames_pair> pairs(K);
+    std::vector<int32_t> first(K + 1, 0), fix(K, fix_scale ? 1 : 0), f1, f2;
+    const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation();
+    for (int k = 0; k < K; k++) {
+        const ORBmatcher::kfptr& pKF2 = candidates[k];
+        ccm_sim3_frames_pair& P = pairs[k];
+        P.kf1 = h1;
+        if (!(P.kf2 = handle_of(pKF2)) || vvpMatches12[k].size() != mps1.size()) return false;
+        rows_of(R1w, t1w, P.T1w); rows_of(pKF2->GetRotation(), pKF2->GetTranslation(), P.T2w);
+        intrinsics_of(pKF1, P.K1); intrinsics_of(pKF2, P.K2);
+        for (size_t i1 = 0; i1 < mps1.size(); i1++) {                          // :30-59
+            const mpptr& pMP1 = mps1[i1]; const mpptr& pMP2 = vvpMatches12[k][i1];
+            if (!pMP2 || !pMP1 || pMP1->isBad() || pMP2->isBad()) continue;
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (pMP1->GetIndexInKeyFrame(pKF1) < 0 || i2 < 0) continue;
+            if (map_slot_of(pMP1) < 0 || map_slot_of(pMP2) < 0) return false;  // a point without a slot: the array route
+            f1.push_back((int32_t)i1); f2.push_back(i2);
+        }
+        first[k + 1] = (int32_t)f1.size();
+    }
+    if ((int)draws.size() < K * max_iterations * 3) return false;
+    const std::vector<float> e1 = max_err_levels(pKF1), e2 = max_err_levels(candidates[0]);
+    ccm_sim3_solver_frames_problem p{};
+    p.n_solvers = K; p.pairs = pairs.data(); p.first = first.data(); p.fix_scale = fix.data(); p.feature1 = f1.data(); p.feature2 = f2.data();
+    p.n_levels1 = (int32_t)e1.size(); p.max_err_level1 = e1.data(); p.n_levels2 = (int32_t)e2.size(); p.max_err_level2 = e2.data();
+    p.probability = probability; p.min_inliers = min_inliers; p.max_iterations = max_iterations; p.draws = draws.data();
+    ccm_sim3_solver* s = nullptr;
+    if (ccm_sim3_solver_create_frames(ctx(), table, &p, &s)) return false;
+    n.assign(K, 0);
+    for (int k = 0; k < K; k++) n[k] = first[k + 1] - first[k];
+    *out = s;
+    return true;
+}
+
+// Links 3 and 4 in one call.  Nothing of a map point is projected or uploaded here; the entry marks go up as for
+// search_by_sim3_on_table, and vpMatches1[i] = NULL comes back as `pruned`.
+bool compute_sim3_candidates_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<ORBmatcher::kfptr>& candidates,
+                                      std::vector<std::vector<ORBmatcher::mpptr>>& vvpMatches12, const std::vector<float>& s12,
+                                      const std::vector<cv::Mat>& R12, const std::vector<cv::Mat>& t12, float th, float th2, bool fix_scale,
+                                      KeyframeHandleOf handle_of, std::vector<double>& sim3, std::vector<int>& n_inliers)
+{
+    typedef ORBmatcher::mpptr mpptr;
+    const int K = (int)candidates.size();
+    if (vvpMatches12.size() != candidates.size() || s12.size() != candidates.size() || R12.size() != candidates.size() || t12.size() != candidates.size() ||
+        sim3.size() != 8 * candidates.size() || K == 0)
+        return false;
+    ccm_map_table* table = map_table_here();
+    ccm_frame* h1 = table ? handle_of(pKF1) : nullptr;
+    if (!table || !h1) return false;
+    const int n1 = (int)pKF1->GetMapPointMatches().size();
+    std::vector<ccm_compute_sim3_pair> pairs(K);
+    std::vector<std::vector<int32_t>> m12(K), mi2(K);
+    std::vector<std::vector<mpptr>> mps2(K);
+    const cv::Mat R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation();
+    for (int k = 0; k < K; k++) {
+        const ORBmatcher::kfptr& pKF2 = candidates[k];
+        ccm_compute_sim3_pair& C = pairs[k];
+        ccm_sim3_search_pair& P = C.search;
+        P.kf1 = h1;
+        if (!(P.kf2 = handle_of(pKF2)) || (int)vvpMatches12[k].size() != n1) return false;
+        mps2[k] = pKF2->GetMapPointMatches();
+        const cv::Mat sR12 = s12[k] * R12[k], sR21 = (1.0 / s12[k]) * R12[k].t(), t21 = -sR21 * t12[k];    // src/ORBmatcher.cpp:1141-1143
+        rows_of(R1w, t1w, P.T1w); rows_of(pKF2->GetRotation(), pKF2->GetTranslation(), P.T2w);
+        rows_of(sR21, t21, P.S21); rows_of(sR12, t12[k], P.S12);
+        P.fx = pKF1->fx; P.fy = pKF1->fy; P.cx = pKF1->cx; P.cy = pKF1->cy;
+        P.bounds1[0] = pKF1->mnMinX; P.bounds1[1] = pKF1->mnMaxX; P.bounds1[2] = pKF1->mnMinY; P.bounds1[3] = pKF1->mnMaxY;
+        P.bounds2[0] = pKF2->mnMinX; P.bounds2[1] = pKF2->mnMaxX; P.bounds2[2] = pKF2->mnMinY; P.bounds2[3] = pKF2->mnMaxY;
+        m12[k].assign(std::max(n1, 1), -1); mi2[k].assign(std::max(n1, 1), -1);
+        for (int i = 0; i < n1; i++) {
+            const mpptr& pMP = vvpMatches12[k][i];
+            if (!pMP) continue;
+            const int s = map_slot_of(pMP);
+            if (s < 0) return false;                                           // a point without a slot: the array route
+            m12[k][i] = s;
+            mi2[k][i] = pMP->GetIndexInKeyFrame(pKF2);
+        }
+        P.matched12 = m12[k].data(); P.matched_idx2 = mi2[k].data();
+        intrinsics_of(pKF2, C.K2);
+        for (int i = 0; i < 8; i++) C.sim3[i] = sim3[8 * (size_t)k + i];
+        C.fix_scale = fix_scale ? 1 : 0; C.th2 = th2;
+    }
+    const ORBmatcher::kfptr& pKF2 = candidates[0];                             // one client's keyframes share the extractor's scale tables
+    ccm_compute_sim3_problem p{};
+    p.n_pairs = K; p.pairs = pairs.data(); p.th = th;
+    p.log_scale_factor1 = pKF1->mfLogScaleFactor; p.n_levels1 = (int32_t)pKF1->mvScaleFactors.size(); p.scale_factors1 = pKF1->mvScaleFactors.data();
+    p.inv_level_sigma2_1 = pKF1->mvInvLevelSigma2.data();
+    p.log_scale_factor2 = pKF2->mfLogScaleFactor; p.n_levels2 = (int32_t)pKF2->mvScaleFactors.size(); p.scale_factors2 = pKF2->mvScaleFactors.data();
+    p.inv_level_sigma2_2 = pKF2->mvInvLevelSigma2.data();
+    std::vector<int32_t> match12((size_t)K * std::max(n1, 1), -1), n_found(K, 0), n_corr(K, 0), n_in(K, 0);
+    std::vector<uint8_t> pruned((size_t)K * std::max(n1, 1), 0);
+    std::vector<double> s3(8 * (size_t)K, 0.0);
+    ccm_compute_sim3_result r{};
+    r.search.match12 = match12.data(); r.search.n_found = n_found.data();
+    r.pruned = pruned.data(); r.n_correspondences = n_corr.data(); r.n_inliers = n_in.data(); r.sim3 = s3.data();
+    if (ccm_compute_sim3_table_frames(ctx(), table, &p, &r) < 0) return false;
+    n_inliers.assign(K, 0);
+    for (int k = 0; k < K; k++) {
+        n_inliers[k] = n_in[k];
+        for (int i = 0; i < n1; i++) {
+            const int32_t i2 = match12[(size_t)k * n1 + i];
+            if (i2 >= 0) vvpMatches12[k][i] = mps2[k][i2];                     // src/ORBmatcher.cpp:1337-1342
+            if (pruned[(size_t)k * n1 + i]) vvpMatches12[k][i] = static_cast<mpptr>(NULL);       // src/Optimizer.cpp:1017, :1051
+        }
+    }
+    sim3 = s3;
     return true;
 }
 

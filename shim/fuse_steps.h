@@ -159,6 +159,20 @@ bool search_by_sim3_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<OR
 // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th), RemapMapPointMatch (:414-435) included; nmatches = its return value.
 bool search_by_projection_on_table(const ORBmatcher::kfptr& pKF, const cv::Mat& Scw, const std::vector<ORBmatcher::mpptr>& vpPoints,
                                    std::vector<ORBmatcher::mpptr>& vpMatched, int th, KeyframeHandleOf handle_of, int& nmatches);
+// The Sim3Solver batch of the first loop of ComputeSim3 (src/LoopFinder.cpp:251-282) with the constructor's loop on the device: one
+// ccm_sim3_solver_create_frames for the candidates' vvpMatches12, correspondences named by features.  draws: the caller's RandomInt
+// results, [candidates][max_iterations][3].  n[i] = the correspondences of candidate i, those that passed src/Sim3Solver.cpp:32-59.
+// Declines like its neighbours; *out is then untouched.
+bool sim3_solvers_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<ORBmatcher::kfptr>& candidates,
+                           const std::vector<std::vector<ORBmatcher::mpptr>>& vvpMatches12, bool fix_scale, double probability, int min_inliers,
+                           int max_iterations, const std::vector<int32_t>& draws, KeyframeHandleOf handle_of, std::vector<int>& n, ccm_sim3_solver** out);
+// SearchBySim3 and OptimizeSim3 (src/LoopFinder.cpp:313-330, src/MapMatcher.cpp:318-333) for every candidate that returned an Scm in one
+// pass, in ONE ccm_compute_sim3_table_frames: vvpMatches12[i] holds the solver's inliers on entry and vpMapPointMatches after
+// OptimizeSim3 on return, sim3[i] = gScm in and out (8 doubles: qx, qy, qz, qw, tx, ty, tz, s), n_inliers[i] = OptimizeSim3's verdict.
+bool compute_sim3_candidates_on_table(const ORBmatcher::kfptr& pKF1, const std::vector<ORBmatcher::kfptr>& candidates,
+                                      std::vector<std::vector<ORBmatcher::mpptr>>& vvpMatches12, const std::vector<float>& s12,
+                                      const std::vector<cv::Mat>& R12, const std::vector<cv::Mat>& t12, float th, float th2, bool fix_scale,
+                                      KeyframeHandleOf handle_of, std::vector<double>& sim3, std::vector<int>& n_inliers);
 
 // The projection, the gates and the selection of ORBmatcher::Fuse (:870-955, :1018-1101) for every keyframe of kfs and every point of
 // pts in ONE ccm_fuse_select_table_frames on the map-point table: nothing is projected on the host and nothing is uploaded per pair.
