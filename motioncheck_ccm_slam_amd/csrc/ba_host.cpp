@@ -528,7 +528,9 @@ int BaCall::build_block_structure()
     if ((long long)nfree * nfree >= (1LL << 32)) return ccm_fail(c, CCM_E_ARG, "too many free keyframes (%d) for 32-bit block keys", nfree);
     const long long n2 = (long long)nfree * nfree;
     if (nfree > 0) {
-        const size_t scan_tmp = sp_scan_temp_bytes((size_t)std::max<long long>(n2, L + 1));
+        // (both scans run over one item more than they count: the total lands behind the last prefix.  Sized for n2 items, rocPRIM
+        // refused the n2 + 1 of the flag scan where n2 fills its last block exactly -- 256 free keyframes)
+        const size_t scan_tmp = sp_scan_temp_bytes((size_t)std::max<long long>(n2 + 1, L + 1));
         CCM_RESERVE(c, S.sp_cnt, ((size_t)L + 2) * 4); CCM_RESERVE(c, S.sp_off, ((size_t)L + 2) * 4);
         CCM_RESERVE(c, S.sp_tmp, scan_tmp + 256);
         CCM_HIP(c, hipMemsetAsync(S.sp_cnt.p, 0, ((size_t)L + 2) * 4, st));
@@ -633,7 +635,7 @@ int BaCall::select_solver()
     }
     // Which iteration: the pipelined one (two kernels per iteration, ba_ppcg.hip) for the tolerances a BA asks for; its recurrences
     // stall near a relative residual of 1e-9, so a caller that wants more than 1e-7 gets the classic four-kernel iteration.
-    pcg_tol = env.pcg_tol > 0 ? env.pcg_tol : (opt->pcg_tol > 0 ? opt->pcg_tol : 1e-6);   // relative residual (default: see ccm_hot.h)
+    pcg_tol = env.pcg_tol > 0 ? env.pcg_tol : (opt->pcg_tol > 0 ? opt->pcg_tol : 1e-7);   // relative residual (default: see ccm_hot.h)
     pipelined = use_pcg && nfree > 0 && ppcg_supported(nfree) && pcg_tol >= 1e-7;
     if (pipelined) {
         CCM_RESERVE(c, S.pcg_hf, 36 * 2 * (size_t)nb * 8 + 64); CCM_RESERVE(c, S.pcg_ecol, 2 * (size_t)nb * 4 + 64);
@@ -849,8 +851,16 @@ int BaCall::pcg_run(PcgTrial& t, bool pip, PcgStatus* status)
         CCM_HIP(c, hipMemcpyAsync(S.pinned + PIN_PCG_SC, S.pcg_sc.p, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
         CCM_HIP(c, hipStreamSynchronize(st));
         if (t.coarse_unverified) { t.coarse_unverified = false; if (pinned_int(PIN_COARSE_INFO) != 0) { *status = PcgStatus::stale_coarse; return CCM_OK; } }
-        if (badh || !(sc[3] > 0.0) || !std::isfinite(sc[2])) { *status = PcgStatus::not_positive_definite; return CCM_OK; }
+        if (badh || !std::isfinite(sc[2])) { *status = PcgStatus::not_positive_definite; return CCM_OK; }
+        // Convergence is looked at before the smallest p.Ap: the host looks once per chunk, and a system that converges within a few
+        // iterations (one cluster: the preconditioner is the exact inverse) spends the rest of the chunk at rounding level, where the
+        // residual underflows to zero (p = 0, p.Ap = 0) or the pipelined recurrences cancel.  While p.Ap <= 0 the classic kernels
+        // take no step (alpha = 0) and the pipelined ones one of 1e-300 p, and |r|^2 follows every step that is taken, so it still
+        // is the residual of x as far as the iteration knows it: a p.Ap <= 0 seen on the way is no verdict on the matrix then.
+        // (In the pipelined solve sc[2] is the recurrence's |r|^2 -- see the TODO below -- so a breakdown of the recurrences with a
+        // small recurrence residual is accepted as converged here, exactly as a run without breakdown is.)
         if (sc[2] <= t.tol2 * sc[1]) { *status = PcgStatus::converged; return CCM_OK; }
+        if (!(sc[3] > 0.0)) { *status = PcgStatus::not_positive_definite; return CCM_OK; }
         // TODO (deferred: changes numerical behaviour): "At exit of a pipelined solve, at least once per trial or under CCM_DEBUG and in
         // tests, compute the true residual with one k_ppcg_row-style mat-vec."  sc[2] is the recurrence's |r|^2, which drifts.
         if (t.itc >= t.max_it) { *status = PcgStatus::no_convergence; return CCM_OK; }

@@ -166,11 +166,12 @@ __global__ __launch_bounds__(PP_TPB) void k_ppcg_prec(const double* __restrict__
             double beta = 0.0, den = dl;
             if (it > 0.0) { beta = g_old != 0.0 ? g / g_old : 0.0; den = dl - beta * g / a_old; }
             // den = (p, A p) in exact arithmetic: not positive = the system (or the preconditioner) is not positive definite, or the
-            // recurrences have broken down; the host looks at sc[3] and abandons the solve
+            // recurrences have broken down.  The host (pcg_run) looks at |r|^2 first and at sc[3] only while that is above the
+            // tolerance: a breakdown at rounding level, after the recurrence's residual has converged, does not abandon the solve
             double alpha = den > 0.0 ? g / den : 0.0;
             if (!(g > 0.0) && rr > 0.0) den = -1.0;
             if (!(den >= sc[3])) sc[3] = den;                    // (also catches NaN)
-            if (alpha == 0.0) alpha = 1e-300;                     // keeps the next iteration's division finite; the solve is abandoned anyway
+            if (alpha == 0.0) alpha = 1e-300;                     // no step to speak of (x moves by 1e-300 p), and the next iteration's division stays finite
             sc[0] = g; sc[2] = rr; sc[4] = it + 1.0; sc[5] = alpha; sc[6] = beta;
         }
         return;

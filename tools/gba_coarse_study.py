@@ -12,7 +12,7 @@ from motioncheck_ccm_slam_amd import synth
 from oracle import oracle_py as O
 
 ap = argparse.ArgumentParser(); ap.add_argument("--iters", type=int, default=8); ap.add_argument("--lam", type=float, default=0.042)
-ap.add_argument("--kf", type=int, default=2000); ap.add_argument("--tol", type=float, default=1e-6); a = ap.parse_args()
+ap.add_argument("--kf", type=int, default=2000); ap.add_argument("--tol", type=float, default=1e-7); a = ap.parse_args()
 g = synth.gba_graph() if a.kf == 2000 else synth.gba_graph(n_kf=a.kf, n_points=100 * a.kf)
 t = time.time()
 if a.iters > 0:

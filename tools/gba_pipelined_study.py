@@ -7,13 +7,13 @@
   3. the keyframe-segment-sharded solve VERDICT r2 #5 asks to price: additive Schwarz over N contiguous keyframe segments,
      each applying the exact inverse of its own diagonal block, plus the shipped coarse level: outer iterations for N = 2, 4, 8.
 The system is cached in /tmp (the oracle needs ~1 min to reach the late trial).
-usage: python3 tools/gba_pipelined_study.py [--iters 8] [--lam 0.042] [--tol 1e-6]"""
+usage: python3 tools/gba_pipelined_study.py [--iters 8] [--lam 0.042] [--tol 1e-7]"""
 import argparse, os, sys, time
 import numpy as np, scipy.sparse as sp, scipy.sparse.linalg as spla
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 
 ap = argparse.ArgumentParser(); ap.add_argument("--iters", type=int, default=8); ap.add_argument("--lam", type=float, default=0.042)
-ap.add_argument("--tol", type=float, default=1e-6); ap.add_argument("--segments", action="store_true"); a = ap.parse_args()
+ap.add_argument("--tol", type=float, default=1e-7); ap.add_argument("--segments", action="store_true"); a = ap.parse_args()
 cache = "/tmp/gba_late_system_%d_%g.npz" % (a.iters, a.lam)
 if os.path.exists(cache):
     z = np.load(cache); Hs = sp.csr_matrix((z["data"], z["indices"], z["indptr"]), shape=tuple(z["shape"])); b = z["b"]; tt = z["tt"]
