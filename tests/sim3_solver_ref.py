@@ -5,6 +5,7 @@ generators shared by the CPU and GPU tests.  Restated, not copied: each function
   sample_indices      the sampling loop of iterate (:146-161), as a Python list simulation
   horn                ComputeSim3 (:210-321) for many hypotheses at once, eigenvectors from numpy.linalg.eigh
   errors              CheckInliers / Project / FromCameraToImage (:324-348, :366-407)
+  check32             the transforms of :305-320 and CheckInliers in float32, the reference's operation order, for given (R, t, s)
   RefSolver           the bookkeeping of iterate / find (:120-197) over given per-hypothesis counts and masks
 """
 import math
@@ -15,7 +16,9 @@ from sim3_problems import rand_sim3, sim3_map
 
 
 def ransac_iterations(n, probability, min_inliers, max_iterations):
-    """mRansacMaxIts (:100-115).  N < minInliers: the reference's value is undefined and unused (:129); defined as 1."""
+    """mRansacMaxIts (:100-115).  N < minInliers: the reference's value is undefined and unused (:129); defined as 1.
+    log(1 - epsilon^3) = 0 (minInliers 0, or an epsilon^3 below double's resolution at 1): the quotient is -inf, its conversion to
+    int is out of range and :115 clamps it with max(1, ...); defined as 1, what the clamp gives for the value compilers produce."""
     if n <= 0 or n < min_inliers:
         return 1
     if min_inliers == n:
@@ -23,7 +26,7 @@ def ransac_iterations(n, probability, min_inliers, max_iterations):
     else:
         eps = float(np.float32(min_inliers) / np.float32(n))                 # float epsilon = (float)mRansacMinInliers / N
         den = math.log(1 - eps ** 3)
-        it = max_iterations if den == 0 else min(math.ceil(math.log(1 - probability) / den), max_iterations)
+        it = 1 if den == 0 else min(math.ceil(math.log(1 - probability) / den), max_iterations)
     return max(1, min(it, max_iterations))
 
 
@@ -90,6 +93,41 @@ def errors(R, t, s, X1, X2, K1, K2):
         q12 = np.einsum("hij,nj->hni", Ai, X1) + ti[:, None]
         d1 = p1[None] - project(K1, q21); d2 = project(K2, q12) - p2[None]
         return (d1 * d1).sum(-1), (d2 * d2).sum(-1)
+
+
+def check32(R, t, s, problem):
+    """:305-320 and CheckInliers (:324-348) in float32, operation by operation, for given float32 estimates R [H][3][3], t [H][3],
+    s [H] (what ComputeSim3 left in mR12i, mt12i, ms12i) -> (flags [H][N], err1 [H][N], err2 [H][N] float32).
+      T12 = [s R | t] (:307-310), every product rounded to float
+      T21 = [(1.0 / s) R^T | tinv] (:316): the quotient in double, each entry the double product stored as float
+      tinv = -sRinv t (:319): the three float products added left to right
+      Project (:366-407): the row of T times the point added left to right, invz = 1 / z, fx (x invz) + cx
+      err < maxError for both (:340): false for a NaN on either side"""
+    f = np.float32
+    R = np.asarray(R, f).reshape(-1, 3, 3); t = np.asarray(t, f).reshape(-1, 3); s = np.asarray(s, f).reshape(-1)
+    X1 = np.asarray(problem["X1"], f); X2 = np.asarray(problem["X2"], f); K1 = np.asarray(problem["K1"], f); K2 = np.asarray(problem["K2"], f)
+    m1 = np.asarray(problem["max_err1"], f); m2 = np.asarray(problem["max_err2"], f)
+
+    def image(K, px, py, pz):
+        invz = f(1.0) / pz
+        return K[0] * (px * invz) + K[2], K[1] * (py * invz) + K[3]
+
+    def through(A, tt, X):                                                   # rows of [A | tt] times X [N][3] -> three [H][N]
+        x, y, z = X[None, :, 0], X[None, :, 1], X[None, :, 2]
+        return [((A[:, r, 0, None] * x + A[:, r, 1, None] * y) + A[:, r, 2, None] * z) + tt[:, r, None] for r in range(3)]
+
+    with np.errstate(all="ignore"):
+        sR = s[:, None, None] * R
+        sRinv = ((1.0 / s.astype(np.float64))[:, None, None] * R.transpose(0, 2, 1).astype(np.float64)).astype(f)
+        tinv = -((sRinv[:, :, 0] * t[:, None, 0] + sRinv[:, :, 1] * t[:, None, 1]) + sRinv[:, :, 2] * t[:, None, 2])
+        p1u, p1v = image(K1, X1[:, 0], X1[:, 1], X1[:, 2]); p2u, p2v = image(K2, X2[:, 0], X2[:, 1], X2[:, 2])     # mvP1im1, mvP2im2
+        u, v = image(K1, *through(sR, t, X2))
+        d1x = p1u[None] - u; d1y = p1v[None] - v
+        u, v = image(K2, *through(sRinv, tinv, X1))
+        d2x = u - p2u[None]; d2y = v - p2v[None]
+        e1 = d1x * d1x + d1y * d1y; e2 = d2x * d2x + d2y * d2y
+        assert e1.dtype == f and e2.dtype == f
+        return (e1 < m1[None]) & (e2 < m2[None]), e1, e2
 
 
 def evaluate(problem, samples):

@@ -17,17 +17,24 @@ def _formula(n, p, min_inliers, cap):
         it = 1
     else:
         eps = float(np.float32(min_inliers) / np.float32(n))
-        it = math.ceil(math.log(1 - p) / math.log(1 - eps ** 3))
+        den = math.log(1 - eps ** 3)
+        # den = 0 (min_inliers = 0): the quotient is -inf, (int)ceil(-inf) is out of int's range and :115's max(1, ...) clamps what
+        # compilers make of it; the definition is 1
+        it = math.ceil(math.log(1 - p) / den) if den != 0 else 1
     return max(1, min(it, cap))
 
 
 def test_ransac_iterations_matches_set_ransac_parameters():
     f = _lib.load().ccm_sim3_ransac_iterations
     for n in range(3, 401):
-        for mi in (6, 20):
+        for mi in (0, 1, 3, 6, 20):
             for p in (0.99, 0.999):
                 for cap in (300, 50):
                     assert f(n, p, mi, cap) == _formula(n, p, mi, cap) == ref.ransac_iterations(n, p, mi, cap), (n, mi, p, cap)
+    for n in (3, 70, 400):                                # MinInliers 0: log(1 - 0) = 0, one iteration whatever the cap
+        assert f(n, 0.99, 0, 300) == ref.ransac_iterations(n, 0.99, 0, 300) == 1
+    for (n, mi), want in {(3, 1): 123, (4, 1): 210, (7, 1): 210, (3, 3): 1, (4, 3): 9, (70, 3): 210}.items():
+        assert f(n, 0.99, mi, 210) == want, (n, mi)
     for (n, mi), want in {(6, 6): 1, (7, 6): 5, (8, 6): 9, (20, 6): 169, (25, 20): 7, (100, 6): 300}.items():
         assert f(n, 0.99, mi, 300) == want, (n, mi)
     for n, mi in ((5, 6), (0, 6), (19, 20), (3, 20)):

@@ -20,8 +20,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from sim3_problems import rand_sim3, sim3_map  # noqa: E402
 
 
-def horn(P1, P2, fix, dt):
-    """P1, P2 [H][3][3], rows = points -> R [H][3][3], t [H][3], s [H], eigenvalue gap [H], all in precision dt."""
+def horn(P1, P2, fix, dt, stored_scale=False):
+    """P1, P2 [H][3][3], rows = points -> R [H][3][3], t [H][3], s [H], eigenvalue gap [H], all in precision dt.
+    stored_scale: the two sums of the scale as src/Sim3Solver.cpp:278-292 stores them -- nom a double sum of exact products of the dt
+    entries (cv::Mat::dot), den a double sum of squares rounded to dt first (cv::pow into a float matrix), the quotient rounded to dt.
+    Without it both sums round alike and cancel exactly wherever Pr1 = P3, which hides the one rounding an exact input leaves."""
     P1 = P1.astype(dt); P2 = P2.astype(dt)
     O1 = P1.sum(1) / dt(3); O2 = P2.sum(1) / dt(3)
     Pr1 = P1 - O1[:, None]; Pr2 = P2 - O2[:, None]
@@ -42,6 +45,9 @@ def horn(P1, P2, fix, dt):
                   np.stack([2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)], -1)], 1).astype(dt)
     P3 = np.einsum("hij,hkj->hki", R, Pr2)
     s = np.ones(len(P1), dt) if fix else ((Pr1 * P3).sum((1, 2)) / (P3 * P3).sum((1, 2))).astype(dt)
+    if stored_scale and not fix:
+        P3 = P3.astype(dt)
+        s = ((Pr1.astype("f8") * P3.astype("f8")).sum((1, 2)) / (P3 * P3).astype(dt).astype("f8").sum((1, 2))).astype(dt)
     t = O1 - s[:, None] * np.einsum("hij,hj->hi", R, O2)
     return R, t.astype(dt), s, gap
 
@@ -126,7 +132,30 @@ def study_estimates(H=300):
     print("estimates: (N, max |dR|, max |dt| / max(1, |t|), max |ds| / s)", rows)
 
 
+def study_special():
+    """The special inputs of tests/sim3_solver_cases.py (X1 = X2 with free and with fixed scale, X1 = diag(-1, -1, 1) X2 + t0): float32
+    against float64 R, t, s over the non-collinear samples of each solver's draws.  Returns {name: (max |dR|, max |dt| / max(1, |t|),
+    max |ds| / s)}; tests/test_sim3_solver_cases_gpu.py takes 4 x these as its bounds.  The float32 side forms the scale as the reference
+    stores it (horn's stored_scale): at X1 = X2 that is the only rounding left, and 0 would be the bound without it."""
+    import sim3_solver_cases as cases
+    import sim3_solver_ref as ref
+    out = {}
+    for name, (p, draws) in (("identity, free scale", cases.identity(False)), ("identity, fixed scale", cases.identity(True)),
+                             ("half turn", cases.half_turn())):
+        n = len(p["X1"])
+        tri = np.array([ref.sample_indices(n, d) for d in draws[0]])
+        tri = tri[cases.non_collinear(p, tri)]
+        R, t, s, g = horn(p["X1"][tri], p["X2"][tri], p["fix_scale"], np.float64)
+        r, tt, ss, _ = horn(p["X1"][tri], p["X2"][tri], p["fix_scale"], np.float32, stored_scale=True)
+        dR = np.abs(R - r).max((1, 2)); dt = np.abs(t - tt).max(1) / np.maximum(1, np.abs(t).max(1)); ds = np.abs(s - ss) / np.abs(s)
+        out[name] = (float(dR.max()), float(dt.max()), float(ds.max()))
+        print("special: %-22s %d samples, smallest eigenvalue gap %.3g, max |dR| %.3g, max |dt| / max(1, |t|) %.3g, max |ds| / s %.3g"
+              % (name, len(tri), float(g.min()), *out[name]))
+    return out
+
+
 if __name__ == "__main__":
     with np.errstate(all="ignore"):
         study_flags()
         study_estimates()
+        study_special()
