@@ -1751,6 +1751,39 @@ typedef struct {
 } ccm_new_points_frames;
 int ccm_create_new_map_points_frames(ccm_ctx*, const ccm_new_points_frames*, ccm_new_points_result*);
 
+/* ---- The per-neighbour inputs of the two calls above, defined.  median_depth, F12 and the epipole come from the caller; these
+ * plain host functions (no context, no GPU) state what the library means by them, in arithmetic a device kernel can repeat bit for
+ * bit (csrc/map_math.h: functions for host and device, built without fused multiply-add), so that a later form of the call can
+ * compute them on the device from the handles and the map-point table.
+ *
+ * ccm_map_pair_geometry = LocalMapping::ComputeF12 (src/Mapping.cpp:549-566) and the epipole of ORBmatcher.cpp:708-714, in the
+ * library's reading of float cv::Mat products: each entry of a product is summed in double (k ascending) and stored as float,
+ * element-wise adds are in float.  K = (fx, fy, cx, cy), Tcw = rows of [Rcw | tcw], 1 = the current keyframe, 2 = the neighbour:
+ *     R12 = R1w * R2w^T;   t12 = (-R1w * R2w^T) * t2w + t1w   (products left to right, each stored as float; the add in float)
+ *     F12 = ((K1^-T * [t12]x) * R12) * K2^-1                  (left to right, row-major [3][3])
+ *     K^-1 = [ a 0 c ; 0 b d ; 0 0 1 ] in closed form, each entry one division in double stored as float:
+ *            a = (float)(1.0 / fx), b = (float)(1.0 / fy), c = (float)(-(double)cx / fx), d = (float)(-(double)cy / fy)
+ *            -- not the product form -cx * (1 / fx).  K^-T is its transpose, entry for entry.
+ *     C2 = R2w * Ow1 + t2w;  invz = 1.0f / C2.z;  epipole = (fx2 * C2.x * invz + cx2, fy2 * C2.y * invz + cy2)   (float)
+ * This is the operation order of the Python helpers mapping.compute_f12 / compute_epipole.  A numerically inverted K (cv::Mat::inv,
+ * numpy.linalg.inv) may differ from the closed form by one float ulp in c or d, and not by the same amount for K and K^T; the C
+ * function is the definition, and mapping.compute_f12 is held to it by a bound, not by bits.  The epipole involves no inverse and is
+ * bit-equal.  Returns CCM_E_ARG for a NULL pointer. */
+int ccm_map_pair_geometry(const float K1[4], const float Tcw1[12], const float Ow1[3], const float K2[4], const float Tcw2[12],
+                          float F12[9], float epipole[2]);
+/* ccm_scene_median_depth = KeyFrame::ComputeSceneMedianDepth(2) (src/KeyFrame.cpp:1241-1272) of a keyframe whose features carry
+ * table slots in mp_id [n], on the table columns pos [capacity][3] and flags [capacity].
+ *   Feature i counts iff 0 <= mp_id[i] < capacity and the row has CCM_MP_LIVE.  CCM_MP_BAD rows count: the reference tests
+ *   IsEmpty(), not isBad().
+ *   Its depth is z = Rcw.row(2) . pos + tcw.z: the dot in double, the add in double, stored as float.
+ *   *median = the depth of rank (m - 1) / 2 in ascending order of the m counted depths (vDepths[(size - 1) / q], q = 2);
+ *   *n_depths = m.
+ * Deviations: a non-finite depth is not counted (the reference would sort it in); m == 0 is undefined behaviour in the reference
+ * (it indexes an empty vector) and gives n_depths = 0 and median = 0 here; -0.0f orders
+ * before +0.0f (std::sort leaves their order open).  Returns CCM_E_ARG for n < 0, capacity < 0 or a NULL array that would be read. */
+int ccm_scene_median_depth(int n, const int32_t* mp_id, int capacity, const float* pos, const uint8_t* flags, const float Tcw[12],
+                           float* median, int32_t* n_depths);
+
 /* The optimisation inside Optimizer::OptimizeEssentialGraphLoopClosure / OptimizeEssentialGraphMapFusion
  * (src/Optimizer.cpp:1064-1331, :1333-1574): one VertexSim3Expmap per keyframe (sim3 = Scw or the corrected Sim3,
  * :1094-1108; fixed = pLoopKF, :1110), one EdgeSim3 per loop / spanning-tree / covisibility edge built by the caller

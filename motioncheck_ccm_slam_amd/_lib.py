@@ -51,6 +51,7 @@ SYMBOLS = [
     "ccm_pnp_solver_iterate", "ccm_pnp_solver_find", "ccm_pnp_solver_state", "ccm_pnp_solver_hypotheses", "ccm_pnp_solver_refinements",
     "ccm_pnp_solver_create_frames",
     "ccm_initialize", "ccm_create_new_map_points", "ccm_create_new_map_points_frames",
+    "ccm_map_pair_geometry", "ccm_scene_median_depth",
     "ccm_frame_compute_bow", "ccm_frame_search_by_bow", "ccm_search_by_bow_frames",
     "ccm_undistort_points", "ccm_image_bounds", "ccm_frame_from_extract_camera", "ccm_frames_from_extract_camera", "ccm_frame_get_keypoints",
     "ccm_kfdb_create", "ccm_kfdb_destroy", "ccm_kfdb_add", "ccm_kfdb_erase", "ccm_kfdb_clear", "ccm_kfdb_size", "ccm_kfdb_slot", "ccm_kfdb_slots",
@@ -552,6 +553,9 @@ def load():
     lib.ccm_initialize.argtypes = [vp, C.POINTER(InitializerProblem), C.POINTER(InitializerResult)]
     lib.ccm_create_new_map_points.argtypes = [vp, C.POINTER(NewPointsProblem), C.POINTER(NewPointsResult)]
     lib.ccm_create_new_map_points_frames.argtypes = [vp, C.POINTER(NewPointsFrames), C.POINTER(NewPointsResult)]
+    if hasattr(lib, "ccm_map_pair_geometry"):          # (an older build timed through CCM_HOT_LIB has no host definitions)
+        lib.ccm_map_pair_geometry.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.ccm_scene_median_depth.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.ccm_frame_compute_bow.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp]
     lib.ccm_frame_search_by_bow.argtypes = [vp, vp, vp, C.POINTER(BowOptions), vp, C.c_int, vp]
     lib.ccm_search_by_bow_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(BowOptions), vp, vp, vp, vp, vp]

@@ -4,6 +4,7 @@
 // download of the result list, and synchronises once.  The tap arrays are downloaded only when a tap is given.
 // ccm_create_new_map_points_frames is the same call on frame handles (frame_internal.h): the keyframes already lie in device memory
 // in node order, so the staged upload holds the per-neighbour MapKf records and a table of per-keyframe device views, nothing else.
+// ccm_map_pair_geometry and ccm_scene_median_depth define, on the host, the three per-neighbour inputs of both calls (map_math.h).
 #include "frame_internal.h"
 #include "map_types.h"
 #include <cmath>
@@ -310,4 +311,25 @@ extern "C" int ccm_create_new_map_points_frames(ccm_ctx* c, const ccm_new_points
         CCM_HIP(c, hipGetLastError());
         return map_finish(c, G, fn, o, n_kf, n1, nullptr, nullptr, res);
     });
+}
+
+// ---------------------------------------------------------------- the per-neighbour inputs, defined (no context, no GPU)
+extern "C" int ccm_map_pair_geometry(const float K1[4], const float Tcw1[12], const float Ow1[3], const float K2[4], const float Tcw2[12],
+                                     float F12[9], float epipole[2])
+{
+    if (!K1 || !Tcw1 || !Ow1 || !K2 || !Tcw2 || !F12 || !epipole) return CCM_E_ARG;
+    map_pair_geometry(K1, Tcw1, Ow1, K2, Tcw2, F12, epipole);
+    return CCM_OK;
+}
+
+extern "C" int ccm_scene_median_depth(int n, const int32_t* mp_id, int capacity, const float* pos, const uint8_t* flags, const float Tcw[12],
+                                      float* median, int32_t* n_depths)
+{
+    if (n < 0 || capacity < 0 || (n > 0 && !mp_id) || (capacity > 0 && (!pos || !flags)) || !Tcw || !median || !n_depths) return CCM_E_ARG;
+    try {
+        float med = 0.0f;
+        *n_depths = map_scene_median_depth(n, mp_id, capacity, pos, flags, Tcw, &med);
+        *median = med;
+        return CCM_OK;
+    } catch (...) { return CCM_E_NOMEM; }
 }

@@ -4,8 +4,10 @@
 // arithmetic in the reference's operation order; the sums of cv::Mat products, dot and norm in double, stored as float; the null
 // vector of the float 4x4 from the Jacobi of init_math.h in double on A^T A.  Built with -ffp-contract=off.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 #include "init_math.h"
 
 #define MAP_FN INI_FN
@@ -31,6 +33,107 @@ MAP_FN bool map_baseline_too_short(const float* Ow1, const float* Ow2, float med
     const float baseline = (float)sqrt((double)b0 * b0 + (double)b1 * b1 + (double)b2 * b2);
     const float ratioBaselineDepth = baseline / medianDepthKF2;
     return (double)ratioBaselineDepth < 0.01;
+}
+
+// ---- the geometry of one (current, neighbour) pair: the definitions behind ccm_map_pair_geometry and ccm_scene_median_depth
+// (include/ccm_hot.h).  MAP_FN: the same text serves a device kernel that computes them from keyframe handles and the map-point table.
+
+// A product of float 3x3 matrices as cv::gemm on CV_32F is read here: each entry summed in double over k ascending, stored as float.
+// The products of two floats are exact in double, so a fused multiply-add would give the same sums.
+MAP_FN void map_mul33(const float A[9], const float B[9], float C[9])
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++)
+            C[3 * i + j] = (float)((double)A[3 * i] * B[j] + (double)A[3 * i + 1] * B[3 + j] + (double)A[3 * i + 2] * B[6 + j]);
+}
+// K^-1 of K = [fx 0 cx; 0 fy cy; 0 0 1] in closed form: [1/fx 0 -cx/fx; 0 1/fy -cy/fy; 0 0 1], each entry one division in double
+// stored as float: (float)(1.0 / fx) and (float)(-(double)cx / (double)fx) -- not the product form -cx * (1 / fx).  K^-T is its
+// transpose, entry for entry.
+MAP_FN void map_kinv(const float K[4], float Ki[9])
+{
+    Ki[0] = (float)(1.0 / (double)K[0]); Ki[1] = 0.0f; Ki[2] = (float)(-(double)K[2] / (double)K[0]);
+    Ki[3] = 0.0f; Ki[4] = (float)(1.0 / (double)K[1]); Ki[5] = (float)(-(double)K[3] / (double)K[1]);
+    Ki[6] = 0.0f; Ki[7] = 0.0f; Ki[8] = 1.0f;
+}
+// LocalMapping::ComputeF12 (src/Mapping.cpp:549-566) and the epipole of SearchForTriangulation (ORBmatcher.cpp:708-714).
+//   R12 = R1w * R2w^T;  t12 = (-R1w * R2w^T) * t2w + t1w  (the product chain left to right, each product stored as float, the add in float)
+//   F12 = ((K1^-T * [t12]x) * R12) * K2^-1
+//   C2 = R2w * Ow1 + t2w;  invz = 1.0f / C2z;  ex = fx2 * C2x * invz + cx2, ey = fy2 * C2y * invz + cy2  (float)
+// K = (fx, fy, cx, cy); Tcw = rows of [Rcw | tcw].
+MAP_FN void map_pair_geometry(const float K1[4], const float* Tcw1, const float* Ow1, const float K2[4], const float* Tcw2, float F12[9], float epipole[2])
+{
+    float R1[9], R2t[9], nR1[9], R12[9], nR12[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) { R1[3 * i + j] = Tcw1[4 * i + j]; nR1[3 * i + j] = -Tcw1[4 * i + j]; R2t[3 * i + j] = Tcw2[4 * j + i]; }
+    map_mul33(R1, R2t, R12);
+    map_mul33(nR1, R2t, nR12);
+    float t12[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        t12[i] = (float)((double)nR12[3 * i] * Tcw2[3] + (double)nR12[3 * i + 1] * Tcw2[7] + (double)nR12[3 * i + 2] * Tcw2[11]) + Tcw1[4 * i + 3];
+    const float tx[9] = { 0.0f, -t12[2], t12[1], t12[2], 0.0f, -t12[0], -t12[1], t12[0], 0.0f };
+    float K1i[9], K1it[9], K2i[9], A[9], B[9];
+    map_kinv(K1, K1i); map_kinv(K2, K2i);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) K1it[3 * i + j] = K1i[3 * j + i];
+    map_mul33(K1it, tx, A);
+    map_mul33(A, R12, B);
+    map_mul33(B, K2i, F12);
+    float C2[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        C2[i] = (float)((double)Tcw2[4 * i] * Ow1[0] + (double)Tcw2[4 * i + 1] * Ow1[1] + (double)Tcw2[4 * i + 2] * Ow1[2]) + Tcw2[4 * i + 3];
+    const float invz = 1.0f / C2[2];
+    epipole[0] = K2[0] * C2[0] * invz + K2[2];
+    epipole[1] = K2[1] * C2[1] * invz + K2[3];
+}
+
+// KeyFrame::ComputeSceneMedianDepth(2) (src/KeyFrame.cpp:1241-1272) on the map-point table.  Feature i counts iff its id names a
+// row of the table that is LIVE (bit 0 of the flags; a BAD row counts: the reference tests IsEmpty(), not isBad()) and its depth
+// z = Rcw.row(2) . pos + tcw[2] (the dot in double, the add in double, stored as float) is finite.  The median is the depth of rank
+// (m - 1) / 2 among the m counted ones, in the order of map_depth_key: ascending, -0.0f before +0.0f.
+#define MAP_KEY_NONE 0xFFFFFFFFu           // above the key of every finite float (+inf has 0xFF800000)
+MAP_FN float map_row(const float* T, int r, const float X[3]);      // below
+MAP_FN uint32_t map_depth_key(float z)
+{
+    union { float f; uint32_t u; } v; v.f = z;
+    return (v.u & 0x80000000u) ? ~v.u : (v.u | 0x80000000u);
+}
+MAP_FN float map_key_depth(uint32_t k)
+{
+    union { float f; uint32_t u; } v;
+    v.u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+    return v.f;
+}
+// The key of feature i's depth, MAP_KEY_NONE when the feature does not count
+MAP_FN uint32_t map_feature_depth_key(int32_t id, int capacity, const float* pos, const uint8_t* flags, const float* Tcw)
+{
+    if (id < 0 || id >= capacity || !(flags[id] & 1)) return MAP_KEY_NONE;
+    const float z = map_row(Tcw, 2, pos + 3 * (size_t)id);
+    return std::isfinite(z) ? map_depth_key(z) : MAP_KEY_NONE;
+}
+
+// The host form (ccm_scene_median_depth): the counted keys, then std::nth_element.  -> m, the number of counted depths; *median = 0 for m == 0.
+inline int map_scene_median_depth(int n, const int32_t* mp_id, int capacity, const float* pos, const uint8_t* flags, const float* Tcw, float* median)
+{
+    std::vector<uint32_t> keys;
+    keys.reserve((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const uint32_t key = map_feature_depth_key(mp_id[i], capacity, pos, flags, Tcw);
+        if (key != MAP_KEY_NONE) keys.push_back(key);
+    }
+    const int m = (int)keys.size();
+    *median = 0.0f;
+    if (m == 0) return 0;
+    std::nth_element(keys.begin(), keys.begin() + (m - 1) / 2, keys.end());
+    *median = map_key_depth(keys[(size_t)(m - 1) / 2]);
+    return m;
 }
 
 // The epipolar line of (x1, y1) in the second image, l = x1' F12 = [a b c] (ORBmatcher.cpp:162-164)

@@ -84,6 +84,37 @@ def compute_epipole(kf1: MapKeyFrame, kf2: MapKeyFrame) -> np.ndarray:
     return np.array([kf2.K[0] * C2[0] * invz + kf2.K[2], kf2.K[1] * C2[1] * invz + kf2.K[3]], "f4")
 
 
+def pair_geometry(K1, Tcw1, Ow1, K2, Tcw2):
+    """ccm_map_pair_geometry: (F12 [3][3], epipole [2]) float32 of the current keyframe (1) and a neighbour (2) -- the library's
+    definition of ComputeF12 and the epipole.  K = (fx, fy, cx, cy)."""
+    a = np.ascontiguousarray
+    K1, K2 = a(K1, "f4").reshape(4), a(K2, "f4").reshape(4)
+    T1, T2, O1 = a(Tcw1, "f4").reshape(12), a(Tcw2, "f4").reshape(12), a(Ow1, "f4").reshape(3)
+    F = np.zeros(9, "f4"); e = np.zeros(2, "f4")
+    p = _lib.ptr
+    rc = _lib.load().ccm_map_pair_geometry(p(K1), p(T1), p(O1), p(K2), p(T2), p(F), p(e))
+    if rc:
+        raise _lib.CcmError(rc, "ccm_map_pair_geometry")
+    return F.reshape(3, 3), e
+
+
+def scene_median_depth(mp_id, pos, flags, Tcw):
+    """ccm_scene_median_depth: (median float32, n_depths) of a keyframe whose features hold the table slots mp_id, on the table
+    columns pos [capacity][3] and flags [capacity] -- KeyFrame::ComputeSceneMedianDepth(2)."""
+    a = np.ascontiguousarray
+    ids = a(mp_id, "i4").reshape(-1); pos = a(pos, "f4").reshape(-1, 3); flags = a(flags, "u1").reshape(-1)
+    if len(flags) != len(pos):
+        raise ValueError("pos has %d rows, flags %d" % (len(pos), len(flags)))
+    T = a(Tcw, "f4").reshape(12)
+    med = np.zeros(1, "f4"); m = np.zeros(1, "i4")
+    p = _lib.ptr
+    pad = lambda v: v if len(v) else np.zeros(4, v.dtype)  # noqa: E731  (an empty array may have no address)
+    rc = _lib.load().ccm_scene_median_depth(len(ids), p(pad(ids)), len(pos), p(pad(pos.reshape(-1))), p(pad(flags)), p(T), p(med), p(m))
+    if rc:
+        raise _lib.CcmError(rc, "ccm_scene_median_depth")
+    return med[0], int(m[0])
+
+
 class LocalMapping:
     def __init__(self, ctx=None):
         self.ctx = ctx or _lib.default_context(0)
